@@ -26,10 +26,18 @@ point-mult instances on two; the point-add instances.  All but the first start w
 instance's phase-1 sum-check is done, so its kernels (the roofline sample) are timed undisturbed (--sat-only: two
 lanes, the add lane starts after the largest instance).  `--serial`: one instance at a time.
 
-The ONE line rank 0 prints is a flat, strict-JSON record of ~2 KB (tools/bench_common.py compact_line / dumps_line: at most
-4096 bytes, scalars only inside `roofline` and `cpu_baseline`); everything else -- per-instance spans, kernel classes, the
-reference span per instance and phase, power series, the strong sub-record in full -- goes to a side file whose path the line
-carries in `detail` (--detail-out, default gpurun_out/bench_detail_n<N>.json).  The line carries
+A plain run does only what the headline needs: it sets up, warms up, times the K steps (no per-launch HIP-event bracketing)
+and prints ONE flat, strict-JSON line on rank 0 (tools/bench_common.py compact_line / dumps_line: at most 4096 bytes) whose
+metric, value, unit, higher_is_better, dtype and ms_per_step are the headline; a side file only with --detail-out.
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its last step -- every instance's proof
+bytes and commitments, DIR/<instance>.<field>.npy in float32, at most 64 MB in all; the inputs and seeds are the same in every
+run with the same arguments, so two builds compare output for output.
+
+Everything else the benchmark measures or checks runs only with `--full` (as every run did before that option existed):
+per-launch HIP events, power sampling, verification of the last step and the oracle's digests, the passes after the timed
+region, the CPU baseline.  Its line holds scalars only inside `roofline` and `cpu_baseline`; everything else -- per-instance
+spans, kernel classes, the reference span per instance and phase, power series, the strong sub-record in full -- goes to a side
+file under the repository root whose path the line carries in `detail` (--detail-out to choose it).  With --full the line carries
   roofline     : the fused phase-1 sum-check round kernel (sc_cubic3_kernel<true, true>), algorithmic bytes / HIP-event time
                  over the timed region, against the 8 TB/s HBM3E peak; `traffic` and `limiter_frac` (share of SIMD-cycles
                  with a VALU instruction in flight) are measured by this run itself (three `rocprofv3 --pmc` child passes
@@ -167,7 +175,49 @@ def parse():
                     "end of the default run (the value is then replayed from profiles/, and labelled so)")
     ap.add_argument("--pmc-traffic", type=float, default=None,
                     help="HBM bytes per launch of the roofline kernel from a separate rocprofv3 --pmc pass")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-launch HIP events (kernels, roofline, its secondary pass, the live PMC "
+                         "passes), power sampling, HBM breakdown, verification and oracle digests of the last step, the reference-span "
+                         "pass, the CPU baseline, the N > 1 strong sub-record, the side file.  Off: set up, warm up, time the steps, "
+                         "dump the outputs if asked, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the timed path returned in its last step (proof bytes, commitments) as "
+                         "DIR/<instance>.<field>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(results, out_dir, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: every array the timed path returned per instance in its last step (results: instance name -> the prove
+    call's dict: `proof` bytes and the commitments as uint8; wider integers, the sat-only path's uint64 limbs, as their
+    little-endian bytes on a last axis) as out_dir/<name>.<field>.npy in float32 -- byte values, exact.  Should the whole exceed
+    cap_bytes, every array keeps the same share of its elements, a fixed seeded sample, so that two runs still compare element
+    for element.  Returns {file name: elements written}."""
+    import numpy as np
+    arrays = {}
+    for name in sorted(results):
+        for field, v in sorted(results[name].items()):
+            if isinstance(v, (bytes, bytearray)):
+                a = np.frombuffer(bytes(v), dtype=np.uint8)
+            elif isinstance(v, np.ndarray) and v.dtype.kind in "ui":
+                a = np.ascontiguousarray(v)
+                if a.itemsize > 1:
+                    a = a.astype(a.dtype.newbyteorder("<"), copy=False).view(np.uint8).reshape(a.shape + (a.itemsize,))
+            else:
+                continue
+            arrays[f"{name}.{field}"] = a
+    total = 4 * sum(a.size for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for key, a in arrays.items():
+        if total > cap_bytes and a.size:
+            k = max(1, a.size * cap_bytes // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))]
+        np.save(os.path.join(out_dir, key + ".npy"), a.astype(np.float32))
+        written[key + ".npy"] = int(a.size)
+    return written
 
 
 def ctypes_size_t():
@@ -272,6 +322,8 @@ def main():
     if slot == 128:
         os.environ.setdefault("VPIN_SPARK_GENS_BUDGET_GB", "100")
         os.environ.setdefault("VPIN_GENS_FREE_FRACTION", "0.45")
+    if args.dump_outputs and (args.scaling == "strong" or args.concurrent):
+        raise SystemExit("--dump-outputs: the weak-scaling line only (not --scaling strong or --concurrent)")
     if args.scaling == "strong":
         from bench_strong import main_strong
         return main_strong(args)
@@ -499,6 +551,7 @@ def main():
             r = cx.sat_prove_resident(di, tp, ti, tv, inp, SEED_C, SEED_P)
         last_spans[name] = cx.sat_timings()  # thread-local in the library: read on the proving thread
         proof_bytes[name] = len(r["proof"])
+        last_proof[name] = r
         return len(r["proof"])
 
     queue_state = {"lock": threading.Lock(), "order": [], "pos": 0, "all_on_every_lane": False}
@@ -637,13 +690,15 @@ def main():
                     load[k] += proof_ms.get(n, 0.0)
                 lane_names[1], lane_names[2] = plan
 
+    # the per-launch HIP events (kernels, roofline), the power samples and the host-throttling readout serve --full only
     for cx in ctxs:
         cx.prof_reset()
-        cx.prof_enable(not args.no_prof)
-    sampler = PowerSampler(local_rank)
+        cx.prof_enable(args.full and not args.no_prof)
+    sampler = PowerSampler(local_rank) if args.full else None
     barrier()
-    sampler.start()
-    thr0 = host_cpu_throttle()
+    if sampler:
+        sampler.start()
+    thr0 = host_cpu_throttle() if args.full else {}
     t0 = time.perf_counter()
     if pipelined:
         run_pipelined(args.steps, False)
@@ -654,11 +709,15 @@ def main():
         cx.sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    thr1 = host_cpu_throttle()
+    thr1 = host_cpu_throttle() if args.full else {}
     host_cpu = dict(thr1, throttled_ms_in_timed_region=round(thr1.get("throttled_ms", 0.0) - thr0.get("throttled_ms", 0.0), 2),
                     nr_throttled_in_timed_region=thr1.get("nr_throttled", 0) - thr0.get("nr_throttled", 0),
                     cpu_count=os.cpu_count(), host_threads_per_lane=int(os.environ.get("VPIN_HOST_THREADS", "0"))) if thr1 else {}
-    power_rec = sampler.stop()
+    power_rec = sampler.stop() if sampler else None
+    if args.dump_outputs and rank == 0:
+        # the arrays the last timed step's prove calls returned (every rank proves the same trace: rank 0 writes them)
+        dumped = dump_outputs(last_proof, args.dump_outputs)
+        print(f"[bench] --dump-outputs: {len(dumped)} arrays, {4 * sum(dumped.values())} bytes -> {args.dump_outputs}", file=sys.stderr, flush=True)
     stats, stats_lane0 = {}, {}
     for ci, cx in enumerate(ctxs):
         per_ctx = cx.prof_read()
@@ -670,25 +729,27 @@ def main():
                 a[kk] += v[kk]
         cx.prof_enable(False)
 
-    free_b, total_b = mem_get_info()
-    hbm_used_gb = round((total_b - free_b) / 2**30, 1)
-    # what the memory in use is made of: the shared window tables; per lane the pool's blocks that back live handles
-    # (instances, assignments, decommitments: the resident inputs of the step) and the blocks cached for the next proof's
-    # temporaries (forests, derefs, partials); the rest = runtime, torch, the HIP contexts' own allocations
-    L_ = vpin_amd.lib()
-    L_.vpin_gens_shared_bytes.restype = ctypes_size_t()
-    L_.vpin_gens_shared_bytes.argtypes = [__import__("ctypes").c_int]
-    gib = lambda b: round(b / 2**30, 2)
-    pools = [cx.pool_stats() for cx in ctxs]
-    tables_b = int(L_.vpin_gens_shared_bytes(local_rank))
-    hbm_breakdown = {
-        "window_tables_gib": gib(tables_b),
-        "resident_inputs_gib_per_lane": [gib(t - c_) for t, c_, _ in pools],
-        "cached_temporaries_gib_per_lane": [gib(c_) for _, c_, _ in pools],
-        "resident_inputs_gib": gib(sum(t - c_ for t, c_, _ in pools)), "cached_temporaries_gib": gib(sum(c_ for _, c_, _ in pools)),
-        "other_gib": gib((total_b - free_b) - tables_b - sum(t for t, _, _ in pools)),
-        "note": "after the timed region, no proof running: a lane's pool keeps the temporaries of its largest proof for the next one "
-                "(hipMalloc / hipFree per proof cost more than the proofs of the small instances)"}
+    hbm_used_gb, hbm_breakdown = None, None
+    if args.full:
+        free_b, total_b = mem_get_info()
+        hbm_used_gb = round((total_b - free_b) / 2**30, 1)
+        # what the memory in use is made of: the shared window tables; per lane the pool's blocks that back live handles
+        # (instances, assignments, decommitments: the resident inputs of the step) and the blocks cached for the next proof's
+        # temporaries (forests, derefs, partials); the rest = runtime, torch, the HIP contexts' own allocations
+        L_ = vpin_amd.lib()
+        L_.vpin_gens_shared_bytes.restype = ctypes_size_t()
+        L_.vpin_gens_shared_bytes.argtypes = [__import__("ctypes").c_int]
+        gib = lambda b: round(b / 2**30, 2)
+        pools = [cx.pool_stats() for cx in ctxs]
+        tables_b = int(L_.vpin_gens_shared_bytes(local_rank))
+        hbm_breakdown = {
+            "window_tables_gib": gib(tables_b),
+            "resident_inputs_gib_per_lane": [gib(t - c_) for t, c_, _ in pools],
+            "cached_temporaries_gib_per_lane": [gib(c_) for _, c_, _ in pools],
+            "resident_inputs_gib": gib(sum(t - c_ for t, c_, _ in pools)), "cached_temporaries_gib": gib(sum(c_ for _, c_, _ in pools)),
+            "other_gib": gib((total_b - free_b) - tables_b - sum(t for t, _, _ in pools)),
+            "note": "after the timed region, no proof running: a lane's pool keeps the temporaries of its largest proof for the next one "
+                    "(hipMalloc / hipFree per proof cost more than the proofs of the small instances)"}
     elapsed = grp.max_over_ranks(elapsed)
     value = total_cons_step * args.steps * world / elapsed
 
@@ -732,6 +793,8 @@ def main():
         line["config"]["cu_split"] = cu_split
     line["config"]["parallelism_short"] = (f"one trace per rank x {world} rank(s), no collective; {len(lanes)} stream(s) per rank")
     detail_path = args.detail_out or os.path.join(ROOT, "gpurun_out", f"bench_detail_n{world}.json")
+    if not args.full and not args.detail_out:
+        detail_path = None   # a plain run writes its side file only when asked to
     line["config"]["lanes"] = lane_names
     line["config"]["low_memory"] = bool(args.low_memory)
     line["config"]["table_slot_bytes"] = int(os.environ.get("VPIN_TABLE_SLOT", "96"))
@@ -744,7 +807,7 @@ def main():
     # start, so the roofline is taken over lane 0's launches only
     k = (stats_lane0 if len(lanes) > 1 else stats).get("sc_cubic_fused")
     k_all = stats.get("sc_cubic_fused")
-    if k and k["ms"] > 0:
+    if args.full and k and k["ms"] > 0:
         achieved = k["alg_bytes"] / (k["ms"] * 1e-3) / 1e9
         traffic = args.pmc_traffic
         pmc_all, pmc_l5 = {}, {}
@@ -817,7 +880,7 @@ def main():
     if args.snark:
         line["encode_ms"] = encode_ms
         line["comm_bytes"] = comm_bytes
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             # after the timed region: every proof of the last step through the product's verifier
             # (my_lib_verify: vpin_snark_verify), at full size
             tv = time.perf_counter()
@@ -1021,7 +1084,7 @@ def main():
             decomms.pop(name).free()
             dev_insts.pop(name).free()
         try:
-            if not args.no_span:
+            if args.full and not args.no_span:
                 if os.environ.get("VPIN_POOL_TRACE"):
                     print("[bench] ==== reference-span pass starts ====", file=sys.stderr, flush=True)
                 for cx in ctxs:
@@ -1143,7 +1206,7 @@ def main():
             print(f"[bench] reference_span failed: {e!r}", file=sys.stderr, flush=True)
     # ---- CPU baseline: the oracle on a bounded sample, rank 0, N=1 only ----
     try:
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             import oracle_lib as O
             all_cores = min(os.cpu_count() or 1, 64)
             lab = "L1" if trace == "lenet" else trace
@@ -1230,7 +1293,7 @@ def main():
     # The default line shards independent traces (one per rank, no data-path collective).  BASELINE.json's configs[4] is the
     # other question -- one LeNet trace over the node, the 2^25 instance proven by all ranks together -- and the driver only
     # ever runs the default command, so the strong schedule of --scaling strong runs here as well and lands in `strong`.
-    if world > 1 and args.snark and not args.no_strong and not args.host_buffers:
+    if args.full and world > 1 and args.snark and not args.no_strong and not args.host_buffers:
         for name in list(dev_insts):  # every rank's resident trace: the cooperative proofs build their own
             decomms.pop(name).free()
             dev_insts.pop(name).free()

@@ -104,3 +104,39 @@ def test_compact_line_carries_host_throttling_and_errors():
     d = _check(B.dumps_line(B.compact_line(full, None)))
     assert d["host_quota_cpus"] == 16.0 and d["host_throttled_ms"] == 12.5
     assert "parity" in d["errors"] and "reference_span" in d["errors"]
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    sys.argv = ["bench.py"]
+    try:
+        spec.loader.exec_module(bench)
+    finally:
+        sys.argv = argv
+    return bench
+
+
+def test_dump_outputs_writes_exact_float32_arrays_and_a_seeded_sample_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array a prove call returned, as <instance>.<field>.npy in float32 (byte values, exact; wider
+    integers as their little-endian bytes); above the cap the same seeded sample in every run"""
+    import numpy as np
+    bench = _load_bench()
+    limbs = np.array([[2**64 - 1, 2**63 + 5, 1, 0]], dtype=np.uint64)
+    results = {"X-mult": {"proof": bytes(range(256)) * 16, "comm_para": np.arange(64, dtype=np.uint8).reshape(2, 32)},
+               "X-add": {"proof": b"\x01\xff", "inst_evals": limbs, "note": "not an array"}}
+    w = bench.dump_outputs(results, str(tmp_path / "all"))
+    assert w == {"X-add.inst_evals.npy": 32, "X-add.proof.npy": 2, "X-mult.comm_para.npy": 64, "X-mult.proof.npy": 4096}
+    proof = np.load(tmp_path / "all" / "X-mult.proof.npy")
+    assert proof.dtype == np.float32 and proof.astype(np.uint8).tobytes() == results["X-mult"]["proof"]
+    ev = np.load(tmp_path / "all" / "X-add.inst_evals.npy")
+    assert ev.shape == (1, 4, 8) and ev.astype(np.uint8).tobytes() == limbs.astype("<u8").tobytes()
+    assert np.array_equal(np.load(tmp_path / "all" / "X-mult.comm_para.npy"), np.arange(64, dtype=np.float32).reshape(2, 32))
+    cap = 4 * 1000
+    a = bench.dump_outputs(results, str(tmp_path / "a"), cap_bytes=cap)
+    b = bench.dump_outputs(results, str(tmp_path / "b"), cap_bytes=cap)
+    assert a == b and 4 * sum(a.values()) <= cap and a["X-mult.proof.npy"] < 4096
+    for name in a:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name

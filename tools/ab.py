@@ -15,7 +15,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_COMMON = "--steps 10 --warmup 2 --no-cpu-baseline --no-span --no-roofline-pass --no-live-pmc"
+DEFAULT_COMMON = "--full --steps 10 --warmup 2 --no-cpu-baseline --no-span --no-roofline-pass --no-live-pmc"
 
 
 def main():

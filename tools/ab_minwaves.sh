@@ -3,7 +3,7 @@
 # kernels: 3 = 131-140 VGPRs without scratch, 4 = 128 VGPRs and 20-48 bytes of scratch per lane), BOTH libraries built on the box.
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-F="--no-cpu-baseline --no-live-pmc --no-span --no-verify"
+F="--full --no-cpu-baseline --no-live-pmc --no-span --no-verify"
 run() {  # $1 = tag
   for rep in 1 2; do
     timeout -k 10 300 python3 bench.py --trace L5 --only mult --serial --steps 8 --warmup 2 $F --detail-out gpurun_out/mw.json > gpurun_out/mw.line 2> gpurun_out/mw.err || { echo "$1 L5 failed"; tail -3 gpurun_out/mw.err; continue; }

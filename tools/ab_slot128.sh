@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export VPIN_SPARK_GENS_BUDGET_GB=100 VPIN_GENS_BUDGET_GB=24 VPIN_GENS_FREE_FRACTION=0.45
-F="--no-cpu-baseline --no-live-pmc --no-span --no-verify --no-roofline-pass"
+F="--full --no-cpu-baseline --no-live-pmc --no-span --no-verify --no-roofline-pass"
 run() {
   for rep in 1 2; do
     timeout -k 10 300 python3 bench.py --steps 15 --warmup 3 $F --detail-out gpurun_out/sl.json > gpurun_out/sl.line 2> gpurun_out/sl.err || { echo "$1 failed"; tail -3 gpurun_out/sl.err; continue; }

@@ -4,7 +4,7 @@
 # setting, interleaved, on one box.
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-F="--no-cpu-baseline --no-live-pmc --no-span --no-roofline-pass --no-verify"
+F="--full --no-cpu-baseline --no-live-pmc --no-span --no-roofline-pass --no-verify"
 for T in 3_32 A 7_256 E; do
   for rep in 1 2; do
     for W in 1 2 4 8; do

@@ -74,7 +74,7 @@ def live_pmc_traffic(timeout_s=240, cus=256):
                           ("VALU", ["SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "GRBM_GUI_ACTIVE"])):
             d = os.path.join(tmp, tag)
             cmd = [prof, "--pmc"] + ctrs + ["--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, BENCH,
-                   "--trace", "L5", "--only", "mult", "--serial", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-span",
+                   "--trace", "L5", "--only", "mult", "--serial", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-span",
                    "--no-verify", "--no-roofline-pass", "--no-live-pmc", "--sat-only", "--detail-out", os.path.join(d, "child.json")]
             r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=timeout_s)
             if r.returncode != 0:

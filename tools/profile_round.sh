@@ -10,12 +10,12 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 cd $R
 PARTS=${@:-bench configs hostbuf ktrace pmc}
-Q="--no-cpu-baseline --no-span --no-live-pmc"
+Q="--full --no-cpu-baseline --no-span --no-live-pmc"
 for part in $PARTS; do
 case $part in
 bench)
-  # the driver's own command (python3 bench.py --gpus 1 --steps 20 --warmup 5): the ONE line -> .line, the full record -> .json
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail-out $O/${T}_bench_default.json > $O/${T}_bench_default.line 2> $O/bench_default.err || exit 1
+  # the driver's own command with --full (python3 bench.py --gpus 1 --steps 20 --warmup 5 --full): the ONE line -> .line, the full record -> .json
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-out $O/${T}_bench_default.json > $O/${T}_bench_default.line 2> $O/bench_default.err || exit 1
   tools/check_bench.sh $O/${T}_bench_default.line || exit 1 ;;
 configs)
   for L in 3_32 A 7_256 E; do
@@ -35,13 +35,13 @@ hostbuf)
   for f in A_hostbuf_sat A_hostbuf_sat_pinned A_hostbuf_snark E_hostbuf_snark L5_hostbuf_snark; do python3 -c "import json;d=json.load(open('$O/${T}_bench_$f.json'));print('$f', round(d['ms_per_step'],2), 'ms/step')"; done ;;
 ktrace)
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -o kt -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-span --detail-out $O/${T}_bench_default_under_rocprof.json > $O/${T}_bench_default_under_rocprof.line 2> $O/ktrace.log || exit 4
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -o kt -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-span --detail-out $O/${T}_bench_default_under_rocprof.json > $O/${T}_bench_default_under_rocprof.line 2> $O/ktrace.log || exit 4
   cd $R
   python3 tools/summarize_rocprof.py $O/ktrace $O/${T}_rocprofv3 > $O/ktrace_summary.txt 2>&1
   find $O -name "*kernel_trace.csv" -size +20M -delete ;;
 pmc)
   cd /tmp && export TMPDIR=/tmp
-  P="--trace L5 --only mult --serial --steps 1 --warmup 1 --no-cpu-baseline --no-span --no-verify --no-live-pmc"
+  P="--trace L5 --only mult --serial --steps 1 --warmup 1 --full --no-cpu-baseline --no-span --no-verify --no-live-pmc"
   python3 $R/bench.py $P --detail-out $O/bench_L5_mult_for_pmc.json > $O/bench_L5_mult_for_pmc.line 2> $O/pmc_bench.err || exit 5
   timeout -k 10 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_L5_valu -o p -- python3 $R/bench.py $P --no-roofline-pass --detail-out $O/pmc_L5_valu.json > $O/pmc_L5_valu.line 2> $O/pmc_L5_valu.log || exit 5
   for ctr in FETCH_SIZE WRITE_SIZE; do
