@@ -141,30 +141,27 @@ def test_every_region_of_the_snark_is_checked(ctx):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("wgs", ["2", "8"])
-def test_tail_rounds_on_several_workgroups_per_circuit_give_the_same_bytes(wgs):
-    """VPIN_SPARK_TAIL_WGS (round 6, off by default: measured slower -- profiles/r06_ab_tail_wgs.txt): the rounds between 1024 and
-    8192 pairs per circuit inside the resident tail kernel, on up to 8 workgroups per circuit (classes of the pair index, partial
-    sums added by the last arrival).  Whole SNARKs of conv f=3 and CNN A (2^16 / 2^20 constraints) against the oracle's digests."""
-    import hashlib
+def test_tail_from_8192_pairs_gives_the_same_bytes():
+    """VPIN_SPARK_TAIL_PAIRS=8192: the resident tail kernel entered at up to 8192 pairs per circuit, one workgroup per circuit,
+    on layers with dot-product halves too (read once per process, hence the child).  Whole SNARKs of conv f=3 and CNN A
+    (2^16 / 2^20 constraints) against the oracle's digests."""
     import json
     import os
-    import vpin_amd
-    from vpin_amd import gadgets as G
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_digests.json")) as f:
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "golden", "config_digests.json")) as f:
         gold = json.load(f)["cases"]
-    seed_c, seed_p = bytes(range(64)), bytes((7 * i + 3) % 256 for i in range(64))
-    os.environ["VPIN_SPARK_TAIL_WGS"] = wgs
-    try:
-        with vpin_amd.Context(0) as ctx:
-            for key in ("3_32-mult", "A-add", "A-mult"):
-                g = gold[key]
-                inp = G.synthetic_mult_inputs(g["label"]) if g["kind"] == "mult" else G.synthetic_add_inputs(g["label"])
-                d = ctx.gadget_point_mult_dev(*inp) if g["kind"] == "mult" else ctx.gadget_point_add_dev(*inp)
-                try:
-                    res = d.snark_prove(seed_c, seed_p)
-                finally:
-                    d.free()
-                assert hashlib.sha256(res["proof"]).hexdigest() == g["snark_sha256"], key
-    finally:
-        del os.environ["VPIN_SPARK_TAIL_WGS"]
+    keys = ("3_32-mult", "A-add", "A-mult")
+    code = ("import hashlib, sys; sys.path.insert(0, %r); import vpin_amd; from vpin_amd import gadgets as G\n"
+            "c = vpin_amd.Context(0)\n"
+            "for label, kind in %r:\n"
+            "    inp = G.synthetic_mult_inputs(label) if kind == 'mult' else G.synthetic_add_inputs(label)\n"
+            "    d = c.gadget_point_mult_dev(*inp) if kind == 'mult' else c.gadget_point_add_dev(*inp)\n"
+            "    r = d.snark_prove(bytes(range(64)), bytes((7 * i + 3) %% 256 for i in range(64)))\n"
+            "    print(hashlib.sha256(r['proof']).hexdigest()); d.free()\n"
+            "c.close()\n" % (os.path.dirname(here), [(gold[k]["label"], gold[k]["kind"]) for k in keys]))
+    env = dict(os.environ, VPIN_SPARK_TAIL_PAIRS="8192")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.strip().splitlines()[-len(keys):] == [gold[k]["snark_sha256"] for k in keys]

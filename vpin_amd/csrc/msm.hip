@@ -276,15 +276,8 @@ __device__ __forceinline__ void table_mul_acc10(ge10& acc, fq s, const TableView
   }
 }
 
-// accumulator type of the row kernels: TEN = ten-limb form (default), false = the eight-limb form (A/B runs: VPIN_MSM_FP8)
-template <bool TEN> struct RowAcc;
-template <> struct RowAcc<false> {
-  ge_ext a = ge_identity();
-  __device__ __forceinline__ void mul_acc(const fq& s, const TableView& tv, size_t j) { table_mul_acc(a, s, tv, j); }
-  __device__ __forceinline__ void add_cached(const ge_cached& q) { a = ge_add_cached(a, q); }
-  __device__ __forceinline__ ge_ext ext() const { return a; }
-};
-template <> struct RowAcc<true> {
+// accumulator of the row kernels, in the ten-limb form (fp10_dev.h)
+struct RowAcc {
   ge10 a = ge10_identity();
   __device__ __forceinline__ void mul_acc(const fq& s, const TableView& tv, size_t j) { table_mul_acc10(a, s, tv, j); }
   __device__ __forceinline__ void add_cached(const ge_cached& q) { a = ge10_add_cached(a, q); }
@@ -335,12 +328,11 @@ constexpr unsigned kSharedPad = 40000u;
 // [extra_base0, extra_base0 + n_extra).  out[row] = sum_j s[row][j] * g_j  (extended coords)
 constexpr int kSeg = 8192;  // scalars per compaction segment (uint16 indices, 16 KiB of LDS)
 
-template <bool TEN>
 __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
                                                              const fq* __restrict__ extra, int n_extra, size_t extra_base0,
                                                              TableView tv, ge_ext* __restrict__ out) {
   const size_t row = blockIdx.x;
-  RowAcc<TEN> acc;
+  RowAcc acc;
   const size_t total = ncols + (size_t)n_extra;
   // A row of one repeated scalar s: s * (g_0 + ... + g_{ncols-1}) from the prefix-sum base (see gens_sum_kernel).
   // Three probes keep ordinary rows from paying for the full comparison pass.
@@ -432,14 +424,13 @@ __global__ __launch_bounds__(64) void scalar_times_bases_kernel(const fq* __rest
   fp_store(&T[j].YpX, cch.YpX); fp_store(&T[j].YmX, cch.YmX); fp_store(&T[j].Z, cch.Z); fp_store(&T[j].T2d, cch.T2d);
 }
 
-template <bool TEN>
 __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols, TableView tv,
                                                                  HotRows hr, ge_ext* __restrict__ out, size_t row_base, size_t row_step,
                                                                  int z_compact, const uint8_t* __restrict__ strip_flag) {
   const size_t row = row_base + (size_t)blockIdx.x * row_step;  // row of the polynomial; out[] is indexed by blockIdx.x
   // z_compact: Z holds only this launch's rows, densely (a rank's rows of a split commitment gathered on their own)
   const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
-  RowAcc<TEN> acc;
+  RowAcc acc;
   // strip_flag[row of this launch] != 0: the table walks of this row are msm_strip_kernel's; only its hot entries are added here
   const bool hot_only = strip_flag && strip_flag[blockIdx.x];
   // a row of one repeated scalar (padding tails): s * (g_0 + ... + g_{ncols-1}), as in msm_rows_kernel
@@ -1147,7 +1138,7 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
   };
   g->split = nbt;
   fit(nb, budget, cmax, &g->c, &g->W, &g->E);
-  if (nb > kSplitBases && getenv("VPIN_GENS_UNIFORM") == nullptr) {
+  if (nb > kSplitBases) {
     int c2, W2, E2;
     fit(kSplitBases, budget, cmax, &c2, &W2, &E2);
     const size_t lo_bytes = kSplitBases * (size_t)W2 * E2 * slot;
@@ -1343,12 +1334,6 @@ int vpin_gens_layout(const vpin_gens* g, size_t out[6]) {
 size_t vpin_gens_entry_bytes(void) { return table_slot_bytes(); }  // of the next table built (VPIN_TABLE_SLOT)
 
 // shared implementation: rows of scalars -> points (kept on device), then optional outputs
-// the row kernels' field arithmetic: ten 26/25-bit limbs (fp10_dev.h) unless VPIN_MSM_FP8 asks for the eight-limb form
-static inline bool msm_ten_limbs() {
-  static const bool ten = getenv("VPIN_MSM_FP8") == nullptr;
-  return ten;
-}
-
 static inline TableView view(const vpin_gens* g) {
   return TableView{g->table, g->table_hi, g->split, g->nbt, g->c, g->W, g->E, g->c_hi, g->W_hi, g->E_hi, g->nb, g->s32};
 }
@@ -1411,12 +1396,8 @@ static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, 
     // VPIN_MSM_LDS_PAD overrides (experiments)
     static const int env_pad = [] { const char* e = getenv("VPIN_MSM_LDS_PAD"); return e ? atoi(e) : -1; }();
     const unsigned pad = env_pad >= 0 ? (unsigned)env_pad : (c->shared_device ? kSharedPad : 0u);
-    if (msm_ten_limbs())
-      hipLaunchKernelGGL(msm_rows_kernel<true>, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, dZ, stride,
-                         ncols, d_extra, n_extra, extra_base0, view(g), dst);
-    else
-      hipLaunchKernelGGL(msm_rows_kernel<false>, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, dZ, stride,
-                         ncols, d_extra, n_extra, extra_base0, view(g), dst);
+    hipLaunchKernelGGL(msm_rows_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, dZ, stride, ncols,
+                       d_extra, n_extra, extra_base0, view(g), dst);
   }
   if (chunks > 1)
     hipLaunchKernelGGL(ge_sum_chunks_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dst,
@@ -1537,11 +1518,10 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
   // Montgomery conversion -> first gather, and its workgroups no longer step together: the default LeNet step of bench.py
   // measured 469-473 ms with it against 438-442 ms without (profiles/r04_ab_strip.txt), while the 2^25 instance proven alone
   // gains (313 -> 303 ms).  VPIN_MSM_STRIP > 0 forces it (A/B runs).
-  const bool strip_shared = getenv("VPIN_MSM_STRIP_SHARED") != nullptr;  // A/B: also on a shared device, one workgroup per CU
   // Nor for a rank's share of a split commitment (c->comm set: at W = 2 the share of 16384 rows is exactly min_rows, and
   // rehearsal ranks share one GPU without saying so): its workgroups would not all be resident and the bounded wait below
   // would be sat out per generator.
-  if (env_strip != 0 && (env_strip > 0 || ((!c->shared_device || strip_shared) && c->comm == nullptr)) && msm_ten_limbs() && nrows >= min_rows && R >= min_R && R <= g->split &&
+  if (env_strip != 0 && (env_strip > 0 || (!c->shared_device && c->comm == nullptr)) && nrows >= min_rows && R >= min_R && R <= g->split &&
       S % 8 == 0 && (size_t)S <= R / 8) {
     if (dflag.alloc(nrows) || dlist.alloc((nrows + 1) * sizeof(uint32_t))) return VPIN_ENOMEM;
     uint32_t* d_list = (uint32_t*)dlist.p;
@@ -1620,12 +1600,8 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
                          (const uint32_t*)dlist.p, (const uint32_t*)dlist.p + nrows, S, row0, row_step, z_compact, (ge_ext*)dsparts.p,
                          d_sync, lag);
     }
-    if (msm_ten_limbs())
-      hipLaunchKernelGGL(msm_rows_hot_kernel<true>, dim3((unsigned)nrows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, zbase,
-                         R, R, view(g), hr, chunks > 1 ? (ge_ext*)dparts.p : (ge_ext*)dpts.p, row0, row_step, z_compact, d_flag);
-    else
-      hipLaunchKernelGGL(msm_rows_hot_kernel<false>, dim3((unsigned)nrows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, zbase,
-                         R, R, view(g), hr, chunks > 1 ? (ge_ext*)dparts.p : (ge_ext*)dpts.p, row0, row_step, z_compact, d_flag);
+    hipLaunchKernelGGL(msm_rows_hot_kernel, dim3((unsigned)nrows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, zbase, R, R,
+                       view(g), hr, chunks > 1 ? (ge_ext*)dparts.p : (ge_ext*)dpts.p, row0, row_step, z_compact, d_flag);
     if (chunks > 1)
       hipLaunchKernelGGL(ge_sum_chunks_kernel, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dparts.p, nrows,
                          chunks, (ge_ext*)dpts.p);

@@ -499,22 +499,21 @@ static int dist_fingerprint_check(vpin_ctx* c, size_t nv, size_t ncons, size_t n
   vpin_comm* cm = c->comm;
   auto fnv = [](const uint8_t* p, size_t n) { uint64_t h = 0xcbf29ce484222325ull; for (size_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001b3ull; } return h; };
   auto env_num = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
-  uint64_t fp[10] = {
+  uint64_t fp[9] = {
       (uint64_t)nv, (uint64_t)ncons, (uint64_t)ni, fnv(seed_commit64, 64), fnv(seed_proof64, 64),
       (uint64_t)(getenv("VPIN_DIST_NO_SAT_SPLIT") != nullptr), (uint64_t)(getenv("VPIN_DIST_BY_CIRCUIT") != nullptr),
-      (uint64_t)env_num("VPIN_SPARK_TAIL_PAIRS", 1024), (uint64_t)(getenv("VPIN_NO_HOT_COLS") != nullptr),
-      (uint64_t)(getenv("VPIN_BULLET_CLASSIC") != nullptr)};
-  std::vector<uint64_t> all((size_t)cm->world * 10);
+      (uint64_t)env_num("VPIN_SPARK_TAIL_PAIRS", 1024), (uint64_t)(getenv("VPIN_BULLET_CLASSIC") != nullptr)};
+  std::vector<uint64_t> all((size_t)cm->world * 9);
   int rc = vpin::comm_allgather_ctx(c, fp, all.data(), sizeof fp, "fingerprint");
   if (rc) return rc;
-  static const char* what[10] = {"num_vars", "num_cons", "num_inputs", "seed_commit", "seed_proof", "VPIN_DIST_NO_SAT_SPLIT",
-                                 "VPIN_DIST_BY_CIRCUIT", "VPIN_SPARK_TAIL_PAIRS", "VPIN_NO_HOT_COLS", "VPIN_BULLET_CLASSIC"};
+  static const char* what[9] = {"num_vars", "num_cons", "num_inputs", "seed_commit", "seed_proof", "VPIN_DIST_NO_SAT_SPLIT",
+                                "VPIN_DIST_BY_CIRCUIT", "VPIN_SPARK_TAIL_PAIRS", "VPIN_BULLET_CLASSIC"};
   for (int r = 0; r < cm->world; r++)
-    for (int k = 0; k < 10; k++)
-      if (all[(size_t)r * 10 + k] != fp[k]) {
+    for (int k = 0; k < 9; k++)
+      if (all[(size_t)r * 9 + k] != fp[k]) {
         char msg[200];
         snprintf(msg, sizeof msg, "collective proof: rank %d and rank %d differ in %s (%llu vs %llu)", cm->rank, r, what[k],
-                 (unsigned long long)fp[k], (unsigned long long)all[(size_t)r * 10 + k]);
+                 (unsigned long long)fp[k], (unsigned long long)all[(size_t)r * 9 + k]);
         vpin::set_last_error(msg, hipErrorUnknown);
         return VPIN_ECOMM;
       }

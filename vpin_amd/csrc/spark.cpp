@@ -446,9 +446,7 @@ static int batched_prove(vpin_ctx* c, vpin::SparkForest& f, DotpCtx* dotp, Trans
       // Rounds with at most spark_tail_pairs() pairs per circuit are proven by ONE resident launch (spark.hip, persistent
       // tail): the kernel publishes a round's sums to pinned memory and polls a pinned mailbox for the challenge this
       // loop derives from the transcript.  Larger rounds take one launch each.
-      // (round 6: a layer without dot-product halves on a single GPU may start it at up to 8192 pairs, on several workgroups per
-      // circuit, when the device has room for them -- spark_tail_launch says so)
-      const size_t tail_pairs = lead_ok ? (pl ? vpin::spark_tail_pairs() : vpin::spark_tail_first_pairs(ndl_here > 0)) : 0;
+      const size_t tail_pairs = lead_ok ? vpin::spark_tail_pairs() : 0;
       if (pl && tail_pairs == 0) {  // the split rounds end in the persistent tail; a zero challenge (never) or VPIN_SPARK_TAIL_PAIRS=0 rules it out
         vpin::set_last_error("one proof over several GPUs needs the persistent tail rounds", hipErrorUnknown);
         return VPIN_ESHAPE;
@@ -462,15 +460,13 @@ static int batched_prove(vpin_ctx* c, vpin::SparkForest& f, DotpCtx* dotp, Trans
         const vpin::fq* E = runs ? pyr->d + pyramid_offset(k, j + 1) : nullptr;
         const uint8_t* rprev = j ? B(&r[j - 1]) : nullptr;
         if (!tail_on && (h >> (j + 1)) <= tail_pairs) {
-          rc = runs ? vpin::spark_tail_launch(c, &f, layer_id, k, j, len, pyr->d, rprev, ndl_here ? dotp->d->N : 0,
-                                              ndl_here ? dotp->d->vals : nullptr,
-                                              ndl_here ? dotp->comb_derefs : nullptr, ndl_here ? dotp->scratch : nullptr,
-                                              halves, ndl_here) : VPIN_OK;
-          if (rc < 0) return rc;
-          if (rc == 0) {   // (1: no room for the workgroups of an early start -- this round by a launch, asked again at the next)
-            tail_on = true;
-            tail_j0 = j;
-          }
+          if (runs && (rc = vpin::spark_tail_launch(c, &f, layer_id, k, j, len, pyr->d, rprev, ndl_here ? dotp->d->N : 0,
+                                                    ndl_here ? dotp->d->vals : nullptr,
+                                                    ndl_here ? dotp->comb_derefs : nullptr, ndl_here ? dotp->scratch : nullptr,
+                                                    halves, ndl_here)))
+            return rc;
+          tail_on = true;
+          tail_j0 = j;
         }
         const Fq* res = nullptr;
         if (tail_on) {
@@ -1464,7 +1460,7 @@ static int encode_commit(vpin_ctx* c, const Shape& s, std::unique_ptr<vpin_spark
   // (vpin_snark_prove from host buffers) would otherwise pay a 17 GB hipMalloc / hipFree pair every time -- 0.3 ms usually,
   // seconds every few calls (bench.py --trace E --host-buffers: 106 -> 975 ms/step when it struck).  A service that encodes
   // once and keeps proving trims the pool after its set-up (vpin_ctx_pool_trim), as bench.py does.
-  if (!getenv("VPIN_KEEP_COMB")) vpin::spark_comb_release(c, d.get(), false);
+  vpin::spark_comb_release(c, d.get(), false);
   lap("comb release");
   if ((rc = vpin::spark_find_hot_cols(c, d.get()))) return fail(rc);
   lap("hot columns");
@@ -1502,55 +1498,32 @@ int vpin_spark_encode(vpin_ctx* c, const vpin_r1cs* inst, vpin_spark_decomm** ou
 
   // sparse_to_dense_vecs (:368-380) + AddrTimestamps::new (:232-265).  Round 5: on the device -- the addresses go up as they
   // are (padded entries read address 0), the time stamps come from a stable sort of each side's 3N accesses (trace.hip); the
-  // host used to walk both traces sequentially (60 % of this call for CNN A).  VPIN_ENCODE_HOST_TRACE=1: the old host walk (A/B).
+  // host used to walk both traces sequentially (60 % of this call for CNN A).
   vpin::TraceLap lap(c, "spark_encode");
   int rc;
   if ((rc = vpin::dev_alloc(c, (12 * N + 2 * M) * 4, (void**)&d->idx))) return fail(rc);
-  if (getenv("VPIN_ENCODE_HOST_TRACE")) {
-    std::vector<uint32_t> idx(12 * N + 2 * M, 0);
+  vpin::DevBuf b_bad(c);
+  if (b_bad.alloc(4)) return fail(VPIN_ENOMEM);
+  if (hipMemsetAsync(b_bad.p, 0, 4, c->stream) != hipSuccess) return fail(VPIN_EHIP);
+  for (int side = 0; side < 2; side++) {
+    uint32_t* addr = d->idx + (size_t)side * 6 * N;
+    if (hipMemsetAsync(addr, 0, 3 * N * 4, c->stream) != hipSuccess) return fail(VPIN_EHIP);
     for (int m = 0; m < 3; m++) {
-      for (size_t k = 0; k < inst->nnz[m]; k++) {
-        if (inst->row[m][k] >= inst->num_cons || inst->col[m][k] >= 2 * inst->num_vars) return fail(VPIN_ESHAPE);
-        idx[(size_t)m * N + k] = inst->row[m][k];
-        idx[(size_t)(6 + m) * N + k] = inst->col[m][k];
-      }
+      const uint32_t* src = side ? inst->col[m] : inst->row[m];
+      if (inst->nnz[m] && hipMemcpyAsync(addr + (size_t)m * N, src, inst->nnz[m] * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return fail(VPIN_EHIP);
+      if ((rc = vpin::spark_check_bounds(c, addr + (size_t)m * N, inst->nnz[m], (uint32_t)(side ? 2 * inst->num_vars : inst->num_cons),
+                                         (uint32_t*)b_bad.p)))
+        return fail(rc);
     }
-#pragma omp parallel for schedule(static) num_threads(2)
-    for (int side = 0; side < 2; side++) {
-      uint32_t* audit = idx.data() + 12 * N + (size_t)side * M;
-      for (int m = 0; m < 3; m++) {
-        const uint32_t* addr = idx.data() + (size_t)(side * 6 + m) * N;
-        uint32_t* ts = idx.data() + (size_t)(side * 6 + 3 + m) * N;
-        for (size_t i = 0; i < N; i++) ts[i] = audit[addr[i]]++;
-      }
-    }
-    lap("host idx + timestamps");
-    if (hipMemcpyAsync(d->idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-      return fail(VPIN_EHIP);
-  } else {
-    vpin::DevBuf b_bad(c);
-    if (b_bad.alloc(4)) return fail(VPIN_ENOMEM);
-    if (hipMemsetAsync(b_bad.p, 0, 4, c->stream) != hipSuccess) return fail(VPIN_EHIP);
-    for (int side = 0; side < 2; side++) {
-      uint32_t* addr = d->idx + (size_t)side * 6 * N;
-      if (hipMemsetAsync(addr, 0, 3 * N * 4, c->stream) != hipSuccess) return fail(VPIN_EHIP);
-      for (int m = 0; m < 3; m++) {
-        const uint32_t* src = side ? inst->col[m] : inst->row[m];
-        if (inst->nnz[m] && hipMemcpyAsync(addr + (size_t)m * N, src, inst->nnz[m] * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-          return fail(VPIN_EHIP);
-        if ((rc = vpin::spark_check_bounds(c, addr + (size_t)m * N, inst->nnz[m], (uint32_t)(side ? 2 * inst->num_vars : inst->num_cons),
-                                           (uint32_t*)b_bad.p)))
-          return fail(rc);
-      }
-      if ((rc = vpin::spark_trace_timestamps(c, addr, 3 * N, M, addr + 3 * N, d->idx + 12 * N + (size_t)side * M))) return fail(rc);
-    }
-    uint32_t bad = 0;
-    if (hipMemcpyAsync(&bad, b_bad.p, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-      return fail(VPIN_EHIP);
-    if (bad) return fail(VPIN_ESHAPE);  // lib.rs:171-178 InvalidIndex
-    lap("device idx + timestamps");
+    if ((rc = vpin::spark_trace_timestamps(c, addr, 3 * N, M, addr + 3 * N, d->idx + 12 * N + (size_t)side * M))) return fail(rc);
   }
+  uint32_t bad = 0;
+  if (hipMemcpyAsync(&bad, b_bad.p, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+    return fail(VPIN_EHIP);
+  if (bad) return fail(VPIN_ESHAPE);  // lib.rs:171-178 InvalidIndex
+  b_bad.release();
+  lap("device idx + timestamps");
   if ((rc = vpin::dev_alloc(c, 3 * N * 32, (void**)&d->vals))) return fail(rc);
   if (hipMemsetAsync(d->vals, 0, 3 * N * 32, c->stream) != hipSuccess) return fail(VPIN_EHIP);
   for (int m = 0; m < 3; m++)

@@ -692,8 +692,7 @@ int vpin_eq_suffix_tables(vpin_ctx* c, const uint8_t* tau, int ell, vpin_table**
   hipError_t e = hipSuccess;
   {
     ProfScope ps(c, VPIN_K_EQ, 32.0 * 3.0 * (double)(((size_t)1 << (ell - 1)) - 1));
-    static const bool fused = getenv("VPIN_EQ_STEPWISE") == nullptr;
-    if (fused && ell >= kEqLoVars + 2 && ell <= 32) {
+    if (ell >= kEqLoVars + 2 && ell <= 32) {
       TauAll ta;
       for (int k = 0; k < ell; k++) ta.t[k] = load_host_fq(tau + 32 * (size_t)k);
       const int nbits = ell - kEqLoVars - 1, nlow = std::min(kEqMidVars, std::max(0, nbits - 8));
@@ -748,8 +747,7 @@ int vpin_eq_table(vpin_ctx* c, const uint8_t* r, int ell, vpin_table** out) {
   if (!c || !out || ell < 0 || ell > 40 || (ell > 0 && !r)) return VPIN_EINVAL;
   (void)hipSetDevice(c->device);
   size_t n = (size_t)1 << ell;
-  static const bool fused = getenv("VPIN_EQ_STEPWISE") == nullptr;
-  if (fused && ell >= kEqLoVars + 1 && ell <= 32) {
+  if (ell >= kEqLoVars + 1 && ell <= 32) {
     // one launch, every entry written once (eq_table_fused_kernel)
     vpin_table* t = nullptr;
     int rc1 = table_alloc_uninit(c, n, &t);
