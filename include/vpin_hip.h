@@ -262,6 +262,13 @@ int vpin_gens_msm(vpin_ctx* ctx, const vpin_gens* g, const uint8_t* scalars_mont
  * may be NULL. */
 int vpin_msm(vpin_ctx* ctx, const uint8_t* scalars_mont, const uint8_t* points_compressed, size_t n, uint8_t* out_compressed,
              uint8_t* out_xyzt);
+/* The same sum by a windowed bucket method (signed windows of c or c - 1 bits, one decompression per point, buckets
+ * accumulated with the complete addition, running-sum reduction per window, windows combined on the device).  Measured
+ * (profiles/r07_ab_msm_var_bucket.txt): slower than vpin_msm by a quarter up to 2^16 terms, faster by 11 % at 2^17;
+ * vpin_snark_verify_batch uses it from 2^17 terms on.  Same contract as vpin_msm, the compressed result is byte-identical.
+ * n < 2^31. */
+int vpin_msm_bucket(vpin_ctx* ctx, const uint8_t* scalars_mont, const uint8_t* points_compressed, size_t n, uint8_t* out_compressed,
+                    uint8_t* out_xyzt);
 /* out[i] = compress(decompress(a[i]) + decompress(b[i])), n points: the row-wise sum of two commitment vectors
  * (vPIN_proof_generation/src/commit_test.rs:340-361).  VPIN_EVERIFY when an encoding does not decode. */
 int vpin_points_add(vpin_ctx* ctx, const uint8_t* a_compressed, const uint8_t* b_compressed, size_t n, uint8_t* out_compressed);
@@ -504,6 +511,28 @@ int vpin_sat_verify(vpin_ctx* ctx, const uint8_t* proof, size_t proof_len, size_
                     const uint8_t* comm_input);
 int vpin_snark_verify(vpin_ctx* ctx, const uint8_t* proof, size_t proof_len, const uint8_t* comm, size_t comm_len,
                       const uint8_t* inputs, size_t num_inputs, const uint8_t* comm_para, const uint8_t* comm_input);
+/* SHA-256 (FIPS 180-4) of n bytes, as vpin_snark_verify_batch digests its items; touches no device.  Exported for the
+ * known-answer test of that digest (tests/test_sha256_kat.py), not as a service of the library. */
+void vpin_sha256(const uint8_t* data, size_t n, uint8_t out32[32]);
+
+typedef struct {
+  const uint8_t* proof; size_t proof_len;
+  const uint8_t* comm;  size_t comm_len;
+  const uint8_t* inputs; size_t num_inputs;
+  const uint8_t* comm_para; const uint8_t* comm_input;
+} vpin_verify_item;
+
+/* my_lib_verify over n proofs at once: every deferrable group equation of every proof in one random
+ * linear combination. ok_out[k] = 1 accept / 0 reject; return VPIN_OK when all accept, VPIN_EVERIFY
+ * when any is rejected (ok_out says which), other codes for infrastructure errors. seed32 may be NULL.
+ * Each proof's transcript runs as in vpin_snark_verify (its scalar checks, byte comparisons and the points it must derive for
+ * the transcript reject that proof at once); the sigma-protocol, sum-check and DotProductProofLog equations are collected as
+ * (scalar, point) terms, weighted by 128-bit values drawn from SHAKE256(domain, seed32, SHA-256 of every item) and summed:
+ * fixed-base terms per generator table, variable-base terms in one vpin_msm (vpin_msm_bucket from 2^17 terms on, or from
+ * VPIN_VERIFY_BATCH_BUCKET_MIN terms when that is set).  When the combined sum is
+ * not the identity every proof's own weighted sum is evaluated to find the rejected ones.  comm_para / comm_input hold the
+ * row count the commitment's num_vars implies (32 B per row).  seed32 = NULL: 32 bytes from the operating system. */
+int vpin_snark_verify_batch(vpin_ctx* ctx, const vpin_verify_item* items, size_t n, const uint8_t seed32[32], uint8_t* ok_out);
 /* wall-clock spans of the last encode / snark prove on this thread, seconds: [0] encode
  * [1] derefs + commit  [2] network build  [3] product-layer proofs  [4] hash-layer proofs
  * [5] sat part  [6] whole prove  [7] unused */

@@ -187,6 +187,23 @@ def host_unregister(token):
     _chk(L.vpin_host_unregister(C.c_void_p(token)), "vpin_host_unregister")
 
 
+def sha256(data):
+    """vpin_sha256: the library's SHA-256 (the per-item digest of vpin_snark_verify_batch); no device needed"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    L = lib()
+    L.vpin_sha256.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    L.vpin_sha256.restype = None
+    L.vpin_sha256(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, out.ctypes.data_as(C.c_void_p))
+    return bytes(out)
+
+
+class VerifyItem(C.Structure):
+    """vpin_verify_item"""
+    _fields_ = [("proof", C.c_void_p), ("proof_len", C.c_size_t), ("comm", C.c_void_p), ("comm_len", C.c_size_t),
+                ("inputs", C.c_void_p), ("num_inputs", C.c_size_t), ("comm_para", C.c_void_p), ("comm_input", C.c_void_p)]
+
+
 def declared_symbols():
     """Every function name declared in include/vpin_hip.h."""
     with open(HEADER) as f:
@@ -778,6 +795,18 @@ class Context:
         _chk(L.vpin_msm(self.h, p(s), p(pts), s.shape[0], p(out), p(xyzt) if want_xyzt else None), "vpin_msm")
         return (out, xyzt) if want_xyzt else out
 
+    def msm_bucket(self, scalars, points_compressed, want_xyzt=False):
+        """vpin_msm_bucket: vpin_msm's sum by the windowed bucket method (same arguments, byte-identical compressed result)"""
+        s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        pts = np.ascontiguousarray(points_compressed, dtype=np.uint8).reshape(-1, 32)
+        assert s.shape[0] == pts.shape[0]
+        out, xyzt = np.zeros(32, np.uint8), np.zeros(128, np.uint8)
+        L = lib()
+        L.vpin_msm_bucket.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(L.vpin_msm_bucket(self.h, p(s), p(pts), s.shape[0], p(out), p(xyzt) if want_xyzt else None), "vpin_msm_bucket")
+        return (out, xyzt) if want_xyzt else out
+
     def dense_mlpoly_commit_sum(self, t_vars, seed_commit):
         """vpin_dense_mlpoly_commit_sum: my_dense_mlpoly_commit of the whole assignment (the reference's third commitment,
         proof_point_mult.rs:58-59) -> (L, 32) uint8"""
@@ -992,6 +1021,35 @@ class Context:
         if rc not in (0, -6):
             _chk(rc, "vpin_snark_verify")
         return rc == 0
+
+    def snark_verify_batch(self, items, seed=None):
+        """vpin_snark_verify_batch: my_lib_verify over several proofs with one combined group equation.  items: (inst, res) pairs
+        as snark_verify takes them (inst: inputs, num_inputs; res: proof, comm, comm_para, comm_input).  seed: 32 bytes, or None
+        for the library's own randomness.  Returns the list of verdicts (True = accept)."""
+        n = len(items)
+        arr = (VerifyItem * max(n, 1))()
+        keep = []
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        for k, (inst, res) in enumerate(items):
+            pb = np.frombuffer(res["proof"], dtype=np.uint8).copy()
+            cb = np.frombuffer(res["comm"], dtype=np.uint8).copy()
+            inp = np.ascontiguousarray(inst["inputs"], dtype=np.uint64)
+            cp, ci = np.ascontiguousarray(res["comm_para"]), np.ascontiguousarray(res["comm_input"])
+            keep += [pb, cb, inp, cp, ci]
+            arr[k] = VerifyItem(p(pb), len(pb), p(cb), len(cb), p(inp) if inp.size else None, inst["num_inputs"], p(cp), p(ci))
+        sd = None
+        if seed is not None:
+            sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+            assert sd.size == 32
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        L = lib()
+        L.vpin_snark_verify_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        rc = L.vpin_snark_verify_batch(self.h, C.cast(arr, C.c_void_p), n, p(sd) if sd is not None else None, p(ok))
+        if rc not in (0, -6):
+            _chk(rc, "vpin_snark_verify_batch")
+        out = [bool(v) for v in ok[:n]]
+        assert (rc == 0) == all(out)
+        return out
 
     def sat_verify(self, inst, res, proof=None):
         pb = np.frombuffer(proof if proof is not None else res["proof"], dtype=np.uint8).copy()

@@ -12,6 +12,8 @@
 //   Spartan/src/product_tree.rs:387-485               ProductCircuitEvalProofBatched::verify
 // It exists so that `vpin_prove` can close the reference binary's loop ("Proof verification
 // successful!"); it shares no code with the test-side checker.
+#include <sys/random.h>
+
 #include <functional>
 
 #include "host/prover_common.h"
@@ -46,6 +48,56 @@ struct Deferred {
     jobs.clear();
     return ok;
   }
+};
+
+// ---- equation sink -------------------------------------------------------------------------------------------------------------
+// Every group equation the verifier checks has the form sum s_i P_i = 0 with scalars that are known once the transcript has run.
+// IMMEDIATE mode (sink == nullptr: vpin_sat_verify, vpin_snark_verify) evaluates each where it stands, exactly as before the
+// sink existed.  COLLECT mode (vpin_snark_verify_batch) appends the equation's terms, multiplied by a fresh 128-bit weight, and
+// checks nothing: the caller sums the terms of many proofs and tests one group element against the identity.  A term is
+//   (scalar, compressed point)       proof elements, commitments, points the verifier derived and compressed for the transcript;
+//   (scalar, generator)              one generator of a set (gens_1 / gens_3 / gens_4, h, gR): the FixedBase object the context's
+//                                    verifier cache keeps per (label, size, index) names it, so equal generators of equal shapes
+//                                    add up across a batch;
+//   (scalars, generator table)       DotProductProofLog's z1 <s, G> against the R generators of its table.
+// What stays on the sequential path in both modes, because it is absorbed by the transcript or compared as bytes: C_LZ = <L, C>
+// (polyeval_verify), the row-wise comm_para + comm_input recombination, each ZK sum-check round's target commitment,
+// compress((pProd - pCz) taus_bound_rx), claim2 and cz.mul(comb) (sat_verify).  They are not deferred and must not be.
+struct Sink {
+  struct Var { Fq s; CG p; };
+  struct Fix { Fq s; const FixedBase* g; };
+  struct Tab { const PcGens* pc; std::vector<Fq> s; };  // s[j] on generator j < pc->R of pc->dev
+  std::vector<Var> var;
+  std::vector<Fix> fix;
+  std::vector<Tab> tab;
+  Shake256 weights;       // finalized by the batch entry point: domain, seed, every item's digest, the proof's index
+  // In collect mode the proofs of a batch are the host team (one proof per thread): the verifier functions' own parallel loops
+  // take one thread then (num_threads(sk ? 1 : host_threads())), so the batch stays within host_threads() whatever
+  // OMP_MAX_ACTIVE_LEVELS says.
+  std::mutex* dev_mu;     // the context's stream is shared by the proofs of a batch: device calls take it
+  size_t equations = 0;
+  Fq w;                   // the weight of the equation being written
+  explicit Sink(std::mutex* mu) : dev_mu(mu) {}
+  void equation() {
+    uint64_t v[2] = {0, 0};
+    do weights.squeeze(reinterpret_cast<uint8_t*>(v), 16); while (!(v[0] | v[1]));
+    w = Fq{{v[0], v[1], 0, 0}} * Fq::r2();
+    equations++;
+  }
+  void add(const Fq& s, const CG& p) { var.push_back(Var{s * w, p}); }
+  void sub(const Fq& s, const CG& p) { var.push_back(Var{(s * w).neg(), p}); }
+  void add(const Fq& s, const FixedBase* g) { fix.push_back(Fix{s * w, g}); }
+  void sub(const Fq& s, const FixedBase* g) { fix.push_back(Fix{(s * w).neg(), g}); }
+  // - sum_i v[i] G[i] - blind h over a MultiCommitGens view (the right-hand side of a commitment equation)
+  void sub_commit(const Fq* v, int n, const Fq& blind, const Mcg& g) {
+    for (int i = 0; i < n; i++) sub(v[i], g.G[i]);
+    sub(blind, g.h);
+  }
+};
+struct DevLock {  // collect mode: one proof's device call at a time
+  std::mutex* mu;
+  explicit DevLock(Sink* sk) : mu(sk ? sk->dev_mu : nullptr) { if (mu) mu->lock(); }
+  ~DevLock() { if (mu) mu->unlock(); }
 };
 
 struct Reader {
@@ -89,8 +141,8 @@ static bool decompress(Point& out, const CG& c) { return Point::decompress(out, 
 static bool same(const CG& a, const CG& b) { return memcmp(a.b, b.b, 32) == 0; }
 
 // variable-base MSM on the host cores (the verifier's C_LZ = <L, C> over the row commitments)
-static Point msm_var(const Fq* s, const Point* P, size_t n) {
-  const int nt = n >= 64 ? host_threads() : 1;
+static Point msm_var(const Fq* s, const Point* P, size_t n, bool team = true) {
+  const int nt = team && n >= 64 ? host_threads() : 1;
   std::vector<Point> part(nt, Point::identity());
 #pragma omp parallel for schedule(static) num_threads(nt)
   for (long i = 0; i < (long)n; i++) {
@@ -105,23 +157,33 @@ static Point msm_var(const Fq* s, const Point* P, size_t n) {
 // ---- Sigma protocols -----------------------------------------------------------------------
 
 struct KnowP { CG alpha; Fq z1, z2; };
-static bool knowledge_verify(const KnowP& pf, const Mcg& g, Transcript& tr, const CG& C) {
+static bool knowledge_verify(const KnowP& pf, const Mcg& g, Transcript& tr, const CG& C, Sink* sk) {
   tr.append_protocol_name("knowledge proof");
   tr.append_point("C", C.b);
   tr.append_point("alpha", pf.alpha.b);
   Fq c = tr.challenge_scalar("c");
+  if (sk) {  // c C + alpha - z1 G - z2 h = 0
+    sk->equation();
+    sk->add(c, C); sk->add(Fq::one(), pf.alpha); sk->sub_commit(&pf.z1, 1, pf.z2, g);
+    return true;
+  }
   Point pC, pa;
   if (!decompress(pC, C) || !decompress(pa, pf.alpha)) return false;
   return commit1(pf.z1, pf.z2, g).equals(pC.mul(c) + pa);
 }
 
 struct EqP { CG alpha; Fq z; };
-static bool equality_verify(const EqP& pf, const Mcg& g, Transcript& tr, const CG& C1, const CG& C2) {
+static bool equality_verify(const EqP& pf, const Mcg& g, Transcript& tr, const CG& C1, const CG& C2, Sink* sk) {
   tr.append_protocol_name("equality proof");
   tr.append_point("C1", C1.b);
   tr.append_point("C2", C2.b);
   tr.append_point("alpha", pf.alpha.b);
   Fq c = tr.challenge_scalar("c");
+  if (sk) {  // c (C1 - C2) + alpha - z h = 0
+    sk->equation();
+    sk->add(c, C1); sk->sub(c, C2); sk->add(Fq::one(), pf.alpha); sk->sub(pf.z, g.h);
+    return true;
+  }
   Point p1, p2, pa;
   if (!decompress(p1, C1) || !decompress(p2, C2) || !decompress(pa, pf.alpha)) return false;
   return g.h->mul(pf.z).equals((p1 - p2).mul(c) + pa);
@@ -131,7 +193,7 @@ struct ProdP { CG alpha, beta, delta; Fq z[5]; };
 static bool product_check(const Point& P, const Point& X, const Fq& c, const Point& lhs_g, const Point& h, const Fq& z1, const Fq& z2) {
   return (P + X.mul(c)).equals(lhs_g.mul(z1) + h.mul(z2));
 }
-static bool product_verify(const ProdP& pf, const Mcg& g, Transcript& tr, const CG& X, const CG& Y, const CG& Z) {
+static bool product_verify(const ProdP& pf, const Mcg& g, Transcript& tr, const CG& X, const CG& Y, const CG& Z, Sink* sk) {
   tr.append_protocol_name("product proof");
   tr.append_point("X", X.b);
   tr.append_point("Y", Y.b);
@@ -140,6 +202,16 @@ static bool product_verify(const ProdP& pf, const Mcg& g, Transcript& tr, const 
   tr.append_point("beta", pf.beta.b);
   tr.append_point("delta", pf.delta.b);
   Fq c = tr.challenge_scalar("c");
+  if (sk) {  // P + c X' - z1 G' - z2 h = 0 for (alpha, X, G), (beta, Y, G), (delta, Z, X)
+    const Fq one = Fq::one();
+    sk->equation();
+    sk->add(one, pf.alpha); sk->add(c, X); sk->sub(pf.z[0], g.G[0]); sk->sub(pf.z[1], g.h);
+    sk->equation();
+    sk->add(one, pf.beta); sk->add(c, Y); sk->sub(pf.z[2], g.G[0]); sk->sub(pf.z[3], g.h);
+    sk->equation();
+    sk->add(one, pf.delta); sk->add(c, Z); sk->sub(pf.z[2], X); sk->sub(pf.z[4], g.h);
+    return true;
+  }
   Point pX, pY, pZ, pa, pb, pd;
   if (!decompress(pX, X) || !decompress(pY, Y) || !decompress(pZ, Z) || !decompress(pa, pf.alpha) ||
       !decompress(pb, pf.beta) || !decompress(pd, pf.delta))
@@ -153,7 +225,7 @@ struct DotP { CG delta, beta; std::vector<Fq> z; Fq z_delta, z_beta; };
 // DotProductProof::verify (nizk/mod.rs:376-407) over the <= 4 sum-check generators: the transcript part now, the two group
 // equations into `later` (pf, g1, gn outlive it; pCx, pCy are the decoded Cx, Cy)
 static bool dotproduct_verify(const DotP& pf, const Mcg& g1, const Mcg& gn, Transcript& tr, const Fq* a, int n, const CG& Cx,
-                              const Point& pCx, const CG& Cy, const Point& pCy, Deferred& later) {
+                              const Point& pCx, const CG& Cy, const Point& pCy, Deferred& later, Sink* sk) {
   if ((int)pf.z.size() != n || gn.n != n) return false;
   tr.append_protocol_name("dot product proof");
   tr.append_point("Cx", Cx.b);
@@ -164,6 +236,13 @@ static bool dotproduct_verify(const DotP& pf, const Mcg& g1, const Mcg& gn, Tran
   const Fq c = tr.challenge_scalar("c");
   Fq dotp = Fq::zero();
   for (int i = 0; i < n; i++) dotp = dotp + pf.z[i] * a[i];
+  if (sk) {  // c Cx + delta - commit(z, z_delta; gens_n) = 0 and c Cy + beta - commit(<z, a>, z_beta; gens_1) = 0
+    sk->equation();
+    sk->add(c, Cx); sk->add(Fq::one(), pf.delta); sk->sub_commit(pf.z.data(), n, pf.z_delta, gn);
+    sk->equation();
+    sk->add(c, Cy); sk->add(Fq::one(), pf.beta); sk->sub_commit(&dotp, 1, pf.z_beta, g1);
+    return true;
+  }
   const DotP* pp = &pf;
   const Mcg *p1 = &g1, *pn = &gn;
   later.add([=]() {
@@ -192,7 +271,7 @@ static bool read_zksc(Reader& r, ZkScP& p, int rounds, int deg) {
 }
 
 static bool zksc_verify(const ZkScP& pf, const CG& comm_claim, int rounds, int deg, const Mcg& g1, const Mcg& gn, Transcript& tr,
-                        CG& comm_out, std::vector<Fq>& r_out, Deferred& later) {
+                        CG& comm_out, std::vector<Fq>& r_out, Deferred& later, Sink* sk) {
   if (gn.n != deg + 1 || (int)pf.comm_polys.size() != rounds || rounds < 1) return false;
   VSpan vs(" zk sum-check (transcript)");
   r_out.clear();
@@ -200,7 +279,7 @@ static bool zksc_verify(const ZkScP& pf, const CG& comm_claim, int rounds, int d
   std::vector<Point> p_polys(rounds), p_evals(rounds);
   Point p_claim;
   bool dec_ok = decompress(p_claim, comm_claim);
-#pragma omp parallel for schedule(static) num_threads(host_threads()) reduction(&& : dec_ok)
+#pragma omp parallel for schedule(static) num_threads(sk ? 1 : host_threads()) reduction(&& : dec_ok)
   for (int i = 0; i < rounds; i++) dec_ok = dec_ok && decompress(p_polys[i], pf.comm_polys[i]) && decompress(p_evals[i], pf.comm_evals[i]);
   if (!dec_ok) return false;
   for (int i = 0; i < rounds; i++) {
@@ -221,7 +300,7 @@ static bool zksc_verify(const ZkScP& pf, const CG& comm_claim, int rounds, int d
       a[j] = w[0] * a_sc + w[1] * pw;
       pw = pw * r_i;
     }
-    if (!dotproduct_verify(pf.proofs[i], g1, gn, tr, a.data(), deg + 1, pf.comm_polys[i], p_polys[i], target, p_target, later)) return false;
+    if (!dotproduct_verify(pf.proofs[i], g1, gn, tr, a.data(), deg + 1, pf.comm_polys[i], p_polys[i], target, p_target, later, sk)) return false;
     r_out.push_back(r_i);
   }
   comm_out = pf.comm_evals[rounds - 1];
@@ -241,7 +320,7 @@ static bool read_dplog(Reader& r, DpLogP& p, size_t lgR) {
 // DotProductProofLog::verify (nizk/mod.rs:533-588) + BulletReductionProof::verify (bullet.rs:134-231);
 // G_hat = <s, G> over the R generators is a fixed-base MSM on the device table
 static bool dplog_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transcript& tr, const std::vector<Fq>& a, const CG& Cx,
-                         const CG& Cy) {
+                         const CG& Cy, Sink* sk) {
   const size_t n = pc.R, lg = log2z(n);
   if (pf.Lv.size() != lg || a.size() != n) return false;
   VSpan vs("  dplog");
@@ -250,10 +329,12 @@ static bool dplog_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transc
   tr.append_point("Cy", Cy.b);
   tr.append_scalars("a", a.data(), n);
   Fq r = tr.challenge_scalar("r");
-  Point pCx, pCy;
-  if (!decompress(pCx, Cx) || !decompress(pCy, Cy)) return false;
-  const Point Gs = pc.fb_gR.mul(r);  // gens_1.scale(&r)
-  const Point Gamma = pCx + pCy.mul(r);
+  // collect mode: Cx, Cy and the L / R encodings are terms of the equation (decoded once, on the device, with every other
+  // term of the batch); G_hat, Gs and Gamma_hat are never formed
+  Point pCx = Point::identity(), pCy = Point::identity();
+  if (!sk && (!decompress(pCx, Cx) || !decompress(pCy, Cy))) return false;
+  const Point Gs = sk ? Point::identity() : pc.fb_gR.mul(r);  // gens_1.scale(&r)
+  const Point Gamma = sk ? Point::identity() : pCx + pCy.mul(r);
   std::vector<Fq> u(lg), ui(lg);
   for (size_t i = 0; i < lg; i++) {
     tr.append_point("L", pf.Lv[i].b);
@@ -273,6 +354,25 @@ static bool dplog_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transc
     while (((size_t)2 << lg_i) <= i) lg_i++;
     const size_t k = (size_t)1 << lg_i;
     s[i] = s[i - k] * usq[(lg - 1) - lg_i];
+  }
+  if (sk) {
+    Fq a_hat = Fq::zero();
+    for (size_t i = 0; i < n; i++) a_hat = a_hat + a[i] * s[i];
+    tr.append_point("delta", pf.delta.b);
+    tr.append_point("beta", pf.beta.b);
+    const Fq cc = tr.challenge_scalar("c");
+    // a_hat (cc (Cx + r Cy + sum usq_i L_i + uisq_i R_i) + beta) + delta - z1 (<s, G> + a_hat r gR) - z2 h = 0
+    const Fq ac = a_hat * cc;
+    sk->equation();
+    sk->add(ac, Cx); sk->add(ac * r, Cy);
+    for (size_t i = 0; i < lg; i++) { sk->add(ac * usq[i], pf.Lv[i]); sk->add(ac * uisq[i], pf.Rv[i]); }
+    sk->add(a_hat, pf.beta); sk->add(Fq::one(), pf.delta);
+    sk->sub(pf.z1 * a_hat * r, &pc.fb_gR); sk->sub(pf.z2, &pc.fb_h);
+    const Fq mz = (pf.z1 * sk->w).neg();
+    s.resize(n);
+    for (size_t i = 0; i < n; i++) s[i] = s[i] * mz;
+    sk->tab.push_back(Sink::Tab{&pc, std::move(s)});
+    return true;
   }
   Point G_hat;
   if (msm_rows_host_sum(c, pc.dev, s.data(), 1, n + 2, &G_hat)) return false;
@@ -304,7 +404,7 @@ static bool dplog_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transc
 
 // PolyEvalProof::verify (dense_mlpoly.rs:381-404): C_Zr given
 static bool polyeval_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transcript& tr, const Fq* r, const CG& C_Zr,
-                            const std::vector<CG>& comm) {
+                            const std::vector<CG>& comm, Sink* sk) {
   if (comm.size() != pc.L) return false;
   VSpan vs(" polyeval");
   tr.append_protocol_name("polynomial evaluation proof");
@@ -317,25 +417,30 @@ static bool polyeval_verify(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Tra
   bool on_device = false;
   if (pc.L >= 128 && !host_only) {
     // <L, C> over the row commitments on the device (msm_var.hip): decompression and the scalar multiplications, one lane each
-    const int rc = vpin_msm(c, B(Lv.data()), comm[0].b, pc.L, C_LZ.b, nullptr);
+    // (C_LZ goes into the transcript as Cx: this MSM is not deferrable)
+    int rc;
+    {
+      DevLock lock(sk);
+      rc = vpin_msm(c, B(Lv.data()), comm[0].b, pc.L, C_LZ.b, nullptr);
+    }
     if (rc == VPIN_EVERIFY) return false;  // a commitment that does not decode: the proof's fault
     on_device = rc == VPIN_OK;             // VPIN_ENOMEM / VPIN_EHIP are the machine's fault: the host path decides
   }
   if (!on_device) {
     std::vector<Point> Cd(pc.L);
     bool ok = true;
-#pragma omp parallel for schedule(static) num_threads(pc.L >= 64 ? host_threads() : 1) reduction(&& : ok)
+#pragma omp parallel for schedule(static) num_threads(!sk && pc.L >= 64 ? host_threads() : 1) reduction(&& : ok)
     for (long i = 0; i < (long)pc.L; i++) ok = ok && decompress(Cd[i], comm[i]);
     if (!ok) return false;
-    C_LZ = compress(msm_var(Lv.data(), Cd.data(), pc.L));
+    C_LZ = compress(msm_var(Lv.data(), Cd.data(), pc.L, !sk));
   }
-  return dplog_verify(c, pf, pc, tr, Rv, C_LZ, C_Zr);
+  return dplog_verify(c, pf, pc, tr, Rv, C_LZ, C_Zr, sk);
 }
 // PolyEvalProof::verify_plain (dense_mlpoly.rs:406-419)
 static bool polyeval_verify_plain(vpin_ctx* c, const DpLogP& pf, const PcGens& pc, Transcript& tr, const Fq* r, const Fq& Zr,
-                                  const std::vector<CG>& comm) {
+                                  const std::vector<CG>& comm, Sink* sk) {
   CG C_Zr = compress(commit1(Zr, Fq::zero(), pc.gens_1));
-  return polyeval_verify(c, pf, pc, tr, r, C_Zr, comm);
+  return polyeval_verify(c, pf, pc, tr, r, C_Zr, comm, sk);
 }
 
 // ---- sat proof ---------------------------------------------------------------------------------
@@ -425,7 +530,7 @@ static int eval_view_v(vpin_ctx* c, size_t ell, const PcGens** out) {
 // whole_snark: inst_evals are read from the bytes after the R1CSProof.  Returns false on rejection.
 static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars, const Fq* inputs, size_t num_inputs,
                        const Fq* inst_evals_in, Fq inst_evals[3], const uint8_t* comm_para, const uint8_t* comm_input,
-                       Transcript& tr, std::vector<Fq>& rx, std::vector<Fq>& ry, int* err) {
+                       Transcript& tr, std::vector<Fq>& rx, std::vector<Fq>& ry, int* err, Sink* sk = nullptr) {
   SatGensV* sgp = nullptr;
   if ((*err = sat_gens_v(c, num_vars, &sgp))) return false;
   SatGensV& sg = *sgp;
@@ -458,7 +563,11 @@ static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars,
   bool on_device = false;
   if (L >= 128 && !host_only) {
     // 2L decompressions, L additions and L compressions: one lane per row on the device (msm_var.hip)
-    const int rc = vpin_points_add(c, comm_para, comm_input, L, combined[0].b);
+    int rc;
+    {
+      DevLock lock(sk);
+      rc = vpin_points_add(c, comm_para, comm_input, L, combined[0].b);
+    }
     if (rc == VPIN_EVERIFY) return false;
     on_device = rc == VPIN_OK;  // any other failure is an infrastructure error, not a rejection: recombine on the host
     if (on_device)
@@ -483,9 +592,9 @@ static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars,
   const Fq zero = Fq::zero(), one = Fq::one();
   CG claim1 = compress(commit1(zero, zero, sg.gens_1)), post1, post2;
   Deferred later;  // sc1, sc2 and the generator sets outlive it
-  if (!zksc_verify(sc1, claim1, nrx, 3, sg.gens_1, sg.gens_4, tr, post1, rx, later)) return false;
-  if (!knowledge_verify(pok, sg.gens_1, tr, comm_Cz)) return false;
-  if (!product_verify(pp, sg.gens_1, tr, comm_Az, comm_Bz, comm_prod)) return false;
+  if (!zksc_verify(sc1, claim1, nrx, 3, sg.gens_1, sg.gens_4, tr, post1, rx, later, sk)) return false;
+  if (!knowledge_verify(pok, sg.gens_1, tr, comm_Cz, sk)) return false;
+  if (!product_verify(pp, sg.gens_1, tr, comm_Az, comm_Bz, comm_prod, sk)) return false;
   tr.append_point("comm_Az_claim", comm_Az.b);
   tr.append_point("comm_Bz_claim", comm_Bz.b);
   tr.append_point("comm_Cz_claim", comm_Cz.b);
@@ -494,15 +603,15 @@ static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars,
   for (int i = 0; i < nrx; i++) taus_bound_rx = taus_bound_rx * (rx[i] * tau[i] + (one - rx[i]) * (one - tau[i]));
   Point pAz, pBz, pCz, pProd;
   if (!decompress(pAz, comm_Az) || !decompress(pBz, comm_Bz) || !decompress(pCz, comm_Cz) || !decompress(pProd, comm_prod)) return false;
-  if (!equality_verify(eq1, sg.gens_1, tr, compress((pProd - pCz).mul(taus_bound_rx)), post1)) return false;
+  if (!equality_verify(eq1, sg.gens_1, tr, compress((pProd - pCz).mul(taus_bound_rx)), post1, sk)) return false;
   Fq r_A = tr.challenge_scalar("challenege_Az"), r_B = tr.challenge_scalar("challenege_Bz"), r_C = tr.challenge_scalar("challenege_Cz");
   CG claim2 = compress(Point::mul2(r_A, pAz, r_B, pBz) + pCz.mul(r_C));
-  if (!zksc_verify(sc2, claim2, nry, 2, sg.gens_1, sg.gens_3, tr, post2, ry, later)) return false;
+  if (!zksc_verify(sc2, claim2, nry, 2, sg.gens_1, sg.gens_3, tr, post2, ry, later, sk)) return false;
   {
     VSpan vs(" zk sum-check (equations)");
     if (!later.run()) return false;
   }
-  if (!polyeval_verify(c, pe, sg.pc, tr, ry.data() + 1, comm_vars_at_ry, comm_vars)) return false;
+  if (!polyeval_verify(c, pe, sg.pc, tr, ry.data() + 1, comm_vars_at_ry, comm_vars, sk)) return false;
   // poly_input_eval: SparsePolynomial over [1, inputs...] at ry[1..] (commit_test.rs:457-468)
   const int nvb = (int)log2z(num_vars);
   Fq pie = Fq::zero();
@@ -515,7 +624,7 @@ static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars,
   if (!decompress(pv, comm_vars_at_ry)) return false;
   Point cz = pv.mul(one - ry[0]) + commit1(pie, zero, sg.pc.gens_1).mul(ry[0]);
   Fq comb = r_A * inst_evals[0] + r_B * inst_evals[1] + r_C * inst_evals[2];
-  if (!equality_verify(eq2, sg.gens_1, tr, compress(cz.mul(comb)), post2)) return false;
+  if (!equality_verify(eq2, sg.gens_1, tr, compress(cz.mul(comb)), post2, sk)) return false;
   tr.append_scalar("Ar_claim", inst_evals[0]);
   tr.append_scalar("Br_claim", inst_evals[1]);
   tr.append_scalar("Cr_claim", inst_evals[2]);
@@ -648,7 +757,7 @@ static bool hash_helper(const std::vector<Fq>& rand_mem, const Fq& claim_init, c
 // SparseMatPolyEvalProof::verify (sparse_mlpoly.rs:1535-1571) and everything below it
 static bool spark_verify(vpin_ctx* c, Reader& r, size_t nx, size_t ny, size_t N, size_t M, const std::vector<CG>& c_ops,
                          const std::vector<CG>& c_mem, const std::vector<Fq>& rx, const std::vector<Fq>& ry, const Fq evals[3],
-                         Transcript& tr, int* err) {
+                         Transcript& tr, int* err, Sink* sk = nullptr) {
   const size_t lgN = log2z(N), lgM = log2z(M), nm = std::max(nx, ny);
   if (((size_t)1 << nm) != M) return false;
   const size_t v_ops = lgN + 4, v_mem = nm + 1, v_derefs = lgN + 3, vmax = std::max(v_ops, v_mem);
@@ -735,7 +844,7 @@ static bool spark_verify(vpin_ctx* c, Reader& r, size_t nx, size_t ny, size_t N,
     std::vector<Fq> rj(ch);
     rj.insert(rj.end(), rand_ops.begin(), rand_ops.end());
     tr.append_scalar("joint_claim_eval", joint);
-    if (!polyeval_verify_plain(c, pe_derefs, g_derefs, tr, rj.data(), joint, c_derefs)) return false;
+    if (!polyeval_verify_plain(c, pe_derefs, g_derefs, tr, rj.data(), joint, c_derefs, sk)) return false;
   }
   for (int m = 0; m < 3; m++)
     if (!(claims_dotp[3 * m] == d_row[m]) || !(claims_dotp[3 * m + 1] == d_col[m]) || !(claims_dotp[3 * m + 2] == vals[m])) return false;
@@ -748,7 +857,7 @@ static bool spark_verify(vpin_ctx* c, Reader& r, size_t nx, size_t ny, size_t N,
     std::vector<Fq> rj(ch);
     rj.insert(rj.end(), rand_ops.begin(), rand_ops.end());
     tr.append_scalar("joint_claim_eval_ops", joint);
-    if (!polyeval_verify_plain(c, pe_ops, g_ops, tr, rj.data(), joint, c_ops)) return false;
+    if (!polyeval_verify_plain(c, pe_ops, g_ops, tr, rj.data(), joint, c_ops, sk)) return false;
   }
   {
     std::vector<Fq> e2 = {row_audit, col_audit};
@@ -758,7 +867,7 @@ static bool spark_verify(vpin_ctx* c, Reader& r, size_t nx, size_t ny, size_t N,
     std::vector<Fq> rj(ch);
     rj.insert(rj.end(), rand_mem.begin(), rand_mem.end());
     tr.append_scalar("joint_claim_eval_mem", joint);
-    if (!polyeval_verify_plain(c, pe_mem, g_mem, tr, rj.data(), joint, c_mem)) return false;
+    if (!polyeval_verify_plain(c, pe_mem, g_mem, tr, rj.data(), joint, c_mem, sk)) return false;
   }
   // claims_ops = row read(3) row write(3) col read(3) col write(3); claims_mem = row init, row audit, col init, col audit
   if (!hash_helper(rand_mem, claims_mem[0], &claims_ops[0], &claims_ops[3], claims_mem[1], d_row, row_addr, row_ts, row_audit, rx_ext,
@@ -766,6 +875,141 @@ static bool spark_verify(vpin_ctx* c, Reader& r, size_t nx, size_t ny, size_t N,
     return false;
   return hash_helper(rand_mem, claims_mem[2], &claims_ops[6], &claims_ops[9], claims_mem[3], d_col, col_addr, col_ts, col_audit, ry_ext,
                      r_mem_check[0], r_mem_check[1]);
+}
+
+// ---- batch verification (vpin_snark_verify_batch) -----------------------------------------------------------------------------
+
+// SHA-256 (FIPS 180-4), for the per-item digests the batch weights are bound to
+struct Sha256 {
+  uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  uint8_t buf[64];
+  uint64_t total = 0;
+  static uint32_t ror(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+  void block(const uint8_t* p) {
+    static const uint32_t K[64] = {
+        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u,
+        0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu,
+        0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u,
+        0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+        0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u,
+        0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
+        0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+    uint32_t w[64];
+    for (int i = 0; i < 16; i++) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
+    for (int i = 16; i < 64; i++) {
+      const uint32_t s0 = ror(w[i - 15], 7) ^ ror(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = ror(w[i - 2], 17) ^ ror(w[i - 2], 19) ^ (w[i - 2] >> 10);
+      w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+    }
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+    for (int i = 0; i < 64; i++) {
+      const uint32_t t1 = hh + (ror(e, 6) ^ ror(e, 11) ^ ror(e, 25)) + ((e & f) ^ (~e & g)) + K[i] + w[i];
+      const uint32_t t2 = (ror(a, 2) ^ ror(a, 13) ^ ror(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+      hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+    h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+  }
+  void update(const void* data, size_t n) {
+    if (!n) return;
+    const uint8_t* p = static_cast<const uint8_t*>(data);
+    size_t fill = (size_t)(total & 63);
+    total += n;
+    if (fill) {
+      const size_t take = std::min(n, 64 - fill);
+      memcpy(buf + fill, p, take);
+      p += take; n -= take; fill += take;
+      if (fill < 64) return;
+      block(buf);
+    }
+    for (; n >= 64; p += 64, n -= 64) block(p);
+    if (n) memcpy(buf, p, n);
+  }
+  void u64(uint64_t v) { update(&v, 8); }
+  void finish(uint8_t out[32]) {
+    const uint64_t bits = total * 8;
+    const uint8_t one = 0x80, zero = 0;
+    update(&one, 1);
+    while ((total & 63) != 56) update(&zero, 1);
+    uint8_t len[8];
+    for (int i = 0; i < 8; i++) len[i] = (uint8_t)(bits >> (56 - 8 * i));
+    update(len, 8);
+    for (int i = 0; i < 8; i++) { out[4 * i] = (uint8_t)(h[i] >> 24); out[4 * i + 1] = (uint8_t)(h[i] >> 16); out[4 * i + 2] = (uint8_t)(h[i] >> 8); out[4 * i + 3] = (uint8_t)h[i]; }
+  }
+};
+
+// bincode(R1CSCommitment) as vpin_snark_verify reads it
+struct CommV {
+  bool ok = false;
+  size_t num_cons = 0, num_vars = 0, N = 0, M = 0, nx = 0, ny = 0;
+  std::vector<CG> c_ops, c_mem;
+};
+static void parse_comm(const vpin_verify_item& it, CommV& cv) {
+  Reader rc(it.comm, it.comm_len);
+  const size_t num_cons = rc.u64(), num_vars = rc.u64(), n_in = rc.u64(), batch = rc.u64(), N = rc.u64(), M = rc.u64();
+  if (rc.bad || batch != 3 || n_in != it.num_inputs || !vpin::is_pow2(num_cons) || !vpin::is_pow2(num_vars) || !vpin::is_pow2(N) ||
+      !vpin::is_pow2(M) || N < 4 || M < 4 || N > ((size_t)1 << 40) || it.num_inputs >= num_vars)
+    return;
+  cv.num_cons = num_cons; cv.num_vars = num_vars; cv.N = N; cv.M = M;
+  cv.nx = log2z(num_cons); cv.ny = log2z(2 * num_vars);
+  const size_t L_ops = (size_t)1 << ((log2z(N) + 4) / 2), L_mem = (size_t)1 << ((std::max(cv.nx, cv.ny) + 1) / 2);
+  if (!rc.points(cv.c_ops, L_ops) || !rc.points(cv.c_mem, L_mem) || rc.bad || rc.pos != rc.len) return;
+  cv.ok = true;
+}
+
+// From this many terms on the combined sum goes to the bucket kernel.  Measured at n = 2^10 .. 2^17
+// (profiles/r07_ab_msm_var_bucket.txt, tools/ab_msm_var_bucket.py): the one-lane kernel is 1.5 .. 1.7 ms up to 2^16 terms and 3.0 ms at 2^17,
+// the bucket kernel 2.0 .. 2.3 ms up to 2^16 and 2.7 ms at 2^17 -- it loses by a quarter
+// up to 2^16 terms and wins by 11 % at 2^17, the first size it was measured to win at.  VPIN_VERIFY_BATCH_BUCKET_MIN = n (read
+// per call) moves the threshold: the tests run a batch through the bucket kernel with it.
+constexpr size_t kBucketMinTerms = (size_t)1 << 17;
+static size_t bucket_min_terms() {
+  const char* e = getenv("VPIN_VERIFY_BATCH_BUCKET_MIN");
+  return e && atol(e) > 0 ? (size_t)atol(e) : kBucketMinTerms;
+}
+
+// sum over the proofs `which` of their weighted equations: 1 = the identity, 0 = not (or a term does not decode), < 0 = error
+static int combined_is_identity(vpin_ctx* c, const std::vector<std::unique_ptr<Sink>>& sinks, const std::vector<size_t>& which) {
+  size_t nv = 0;
+  for (size_t k : which) nv += sinks[k]->var.size();
+  std::vector<Fq> vs;
+  std::vector<CG> vp;
+  vs.reserve(nv); vp.reserve(nv);
+  std::map<const FixedBase*, Fq> fix;
+  std::map<std::pair<const vpin_gens*, size_t>, std::vector<Fq>> tabs;  // by table and size: proofs of one shape share a vector
+  for (size_t k : which) {
+    const Sink& sk = *sinks[k];
+    for (const auto& t : sk.var) { vs.push_back(t.s); vp.push_back(t.p); }
+    for (const auto& t : sk.fix) {
+      auto it = fix.find(t.g);
+      if (it == fix.end()) fix[t.g] = t.s;
+      else it->second = it->second + t.s;
+    }
+    for (const auto& t : sk.tab) {
+      auto& v = tabs[{t.pc->dev, t.pc->R}];
+      if (v.empty()) v.assign(t.pc->R + 2, Fq::zero());
+      for (size_t j = 0; j < t.pc->R; j++) v[j] = v[j] + t.s[j];
+    }
+  }
+  Point total = Point::identity();
+  if (nv) {
+    VSpan vs_("batch: variable-base MSM");
+    uint8_t xyzt[128];
+    const int rc = nv >= bucket_min_terms() ? vpin_msm_bucket(c, B(vs.data()), vp[0].b, nv, nullptr, xyzt)
+                                         : vpin_msm(c, B(vs.data()), vp[0].b, nv, nullptr, xyzt);
+    if (rc == VPIN_EVERIFY) return 0;
+    if (rc) return rc;
+    total = Point::from_xyzt(xyzt);
+  }
+  {
+    VSpan vs_("batch: fixed-base sums");
+    for (const auto& kv : tabs) {
+      Point p;
+      const int rc = msm_rows_host_sum(c, kv.first.first, kv.second.data(), 1, kv.second.size(), &p);
+      if (rc) return rc;
+      total = total + p;
+    }
+    for (const auto& kv : fix) kv.first->mul_acc(total, kv.second);
+  }
+  return total.equals(Point::identity()) ? 1 : 0;
 }
 
 }  // namespace
@@ -820,6 +1064,105 @@ int vpin_snark_verify(vpin_ctx* c, const uint8_t* proof, size_t proof_len, const
   ok = spark_verify(c, r, nx, ny, N, M, c_ops, c_mem, rx, ry, ie, tr, &err);
   if (err) return err;
   return ok ? VPIN_OK : VPIN_EVERIFY;
+}
+
+void vpin_sha256(const uint8_t* data, size_t n, uint8_t out32[32]) {
+  Sha256 h;
+  h.update(data, n);
+  h.finish(out32);
+}
+
+// my_lib_verify over n proofs: the transcripts one proof per host thread in collect mode, then one combined group equation
+int vpin_snark_verify_batch(vpin_ctx* c, const vpin_verify_item* items, size_t n, const uint8_t seed32[32], uint8_t* ok_out) {
+  if (!c || (n && (!items || !ok_out))) return VPIN_EINVAL;
+  if (n == 0) return VPIN_OK;
+  for (size_t k = 0; k < n; k++) {
+    const vpin_verify_item& it = items[k];
+    if (!it.proof || !it.comm || !it.comm_para || !it.comm_input || (it.num_inputs && !it.inputs)) return VPIN_EINVAL;
+  }
+  (void)hipSetDevice(c->device);
+  uint8_t seed[32];
+  if (seed32) memcpy(seed, seed32, 32);
+  else if (getrandom(seed, 32, 0) != 32) return VPIN_ENOMEM;  // the operating system gave no randomness: not the caller's arguments
+  // the commitments' shapes, the generator sets they need (the context's cache is filled here, before the threads read it) and
+  // the digest that binds the weights to every byte of the batch
+  std::vector<CommV> cv(n);
+  std::vector<uint8_t> digests(32 * n);
+  for (size_t k = 0; k < n; k++) {
+    const vpin_verify_item& it = items[k];
+    parse_comm(it, cv[k]);
+    Sha256 h;
+    h.u64(it.proof_len); h.update(it.proof, it.proof_len);
+    h.u64(it.comm_len); h.update(it.comm, it.comm_len);
+    h.u64(it.num_inputs); h.update(it.inputs, 32 * it.num_inputs);
+    if (cv[k].ok) {
+      const size_t L = (size_t)1 << (log2z(cv[k].num_vars) / 2);
+      h.update(it.comm_para, 32 * L); h.update(it.comm_input, 32 * L);
+      SatGensV* sg = nullptr;
+      const PcGens* pv = nullptr;
+      const size_t lgN = log2z(cv[k].N), nm = std::max(cv[k].nx, cv[k].ny), v_ops = lgN + 4, v_mem = nm + 1, v_derefs = lgN + 3;
+      int rc;
+      if ((rc = sat_gens_v(c, cv[k].num_vars, &sg)) || (rc = eval_view_v(c, std::max(v_ops, v_mem), &pv)) || (rc = eval_view_v(c, v_ops, &pv)) ||
+          (rc = eval_view_v(c, v_mem, &pv)) || (rc = eval_view_v(c, v_derefs, &pv)))
+        return rc;
+    }
+    h.finish(&digests[32 * k]);
+  }
+  std::mutex dev_mu;
+  std::vector<std::unique_ptr<Sink>> sinks(n);
+  std::vector<int> errs(n, 0);
+  std::vector<uint8_t> ok(n, 0);
+  const int team = (int)std::min<size_t>(n, (size_t)host_threads());
+  {
+    VSpan vs("batch: transcripts");
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team) if (team > 1)
+    for (long kk = 0; kk < (long)n; kk++) {
+      const size_t k = (size_t)kk;
+      sinks[k].reset(new Sink(&dev_mu));
+      if (!cv[k].ok) continue;
+      (void)hipSetDevice(c->device);
+      const vpin_verify_item& it = items[k];
+      Sink& sk = *sinks[k];
+      static const char domain[] = "vpin batch verification weights v1";
+      const uint64_t idx = k, cnt = n;
+      sk.weights.absorb(reinterpret_cast<const uint8_t*>(domain), sizeof(domain) - 1);
+      sk.weights.absorb(seed, 32);
+      sk.weights.absorb(reinterpret_cast<const uint8_t*>(&cnt), 8);
+      sk.weights.absorb(digests.data(), digests.size());
+      sk.weights.absorb(reinterpret_cast<const uint8_t*>(&idx), 8);
+      sk.weights.finalize();
+      Reader r(it.proof, it.proof_len);
+      Transcript tr("snark_example");
+      std::vector<Fq> rx, ry;
+      Fq ie[3];
+      int err = 0;
+      bool good = sat_verify(c, r, cv[k].num_cons, cv[k].num_vars, reinterpret_cast<const Fq*>(it.inputs), it.num_inputs, nullptr, ie,
+                             it.comm_para, it.comm_input, tr, rx, ry, &err, &sk);
+      if (good && !err) good = spark_verify(c, r, cv[k].nx, cv[k].ny, cv[k].N, cv[k].M, cv[k].c_ops, cv[k].c_mem, rx, ry, ie, tr, &err, &sk);
+      errs[k] = err;
+      ok[k] = good && !err;
+    }
+  }
+  for (size_t k = 0; k < n; k++)
+    if (errs[k]) return errs[k];
+  std::vector<size_t> live;
+  for (size_t k = 0; k < n; k++)
+    if (ok[k]) live.push_back(k);
+  if (!live.empty()) {
+    int rc = combined_is_identity(c, sinks, live);
+    if (rc < 0) return rc;
+    if (rc == 0) {
+      // some proof's equations do not hold: each proof's own weighted sum says which (the reject path's speed is not a goal)
+      for (size_t k : live) {
+        rc = combined_is_identity(c, sinks, std::vector<size_t>{k});
+        if (rc < 0) return rc;
+        ok[k] = (uint8_t)rc;
+      }
+    }
+  }
+  bool all = true;
+  for (size_t k = 0; k < n; k++) { ok_out[k] = ok[k]; all = all && ok[k]; }
+  return all ? VPIN_OK : VPIN_EVERIFY;
 }
 
 }  // extern "C"
