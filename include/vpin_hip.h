@@ -601,6 +601,56 @@ int vpin_snark_prove_dev(vpin_ctx* ctx, const vpin_dev_instance* g, const uint8_
                          uint8_t* comm_out, size_t comm_cap, size_t* comm_len, uint8_t* comm_para_out,
                          uint8_t* comm_input_out);
 
+/* ---- the encrypted convolution layer (the inference server's own work) ------------------------------------------
+ * The homomorphic convolution over exponential-ElGamal ciphertext planes on E2 (y^2 = x^3 + a x + b over F_q; the curve of
+ * vpin_synthetic_points) and the random-linear-combination check that reduces one convolution to fh*fw multiplications and
+ * fh*fw - 1 additions: the type-1 path of myConv2d with rLCL / rLCR of src/convolution/Server.py and src/LeNet/Server.py.
+ * A point crosses as x and y (32-byte canonical little-endian each) and an identity flag byte (1 = the identity; its x, y are
+ * ignored on input apart from the range check and written as zeros on output).
+ * VPIN_EINVAL: a coordinate >= q, a non-identity point off the curve (checked on the device), prf_bytes outside 1..16, a
+ * zero dimension, a window that does not fit the padded plane.  vpin_last_error() names the rule. */
+
+/* sum_i s_i * P_i: n scalars (u128 little-endian, n x 16 bytes), n points; exact for any n >= 1, identities and repeated
+ * points included (one lane per term, double-and-add, complete additions in the reduction trees) */
+int vpin_e2_msm(vpin_ctx* ctx, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n,
+                uint8_t out_x[32], uint8_t out_y[32], uint8_t* out_inf);
+/* One plane of H x W points (row-major) under an fh x fw filter of u128 weights (row-major, 16 bytes little-endian each):
+ * out[i][j] = sum_{ii,jj} w[ii][jj] * X[i*stride + ii][j*stride + jj], X = the plane padded with `pad` identities on every side;
+ * oh = (H + 2 pad - fh) / stride + 1, ow likewise; out_* hold oh x ow points. */
+int vpin_e2_conv2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t H, size_t W,
+                   const uint8_t* filter_le16, size_t fh, size_t fw, size_t pad, size_t stride, uint8_t* out_x, uint8_t* out_y,
+                   uint8_t* out_inf);
+/* The layer: P planes (the c1 image's batch x channel planes, then the c2 image's) of H x W points under ONE filter, and per
+ * plane the check  sum_t r_t * out[t] == sum_k w[k] * (sum_t r_t * window[t][k])  with
+ * r_t = int.from_bytes(HMAC-SHA256(key_p, ascii_decimal(t))[:prf_bytes], "big"), t = 0 .. oh*ow - 1 row-major, restarting
+ * for every plane.  keys32 = P x 32 bytes (the reference draws them with os.urandom: explicit here, like the provers' seeds).
+ * The trace holds the output ciphertext and, in plane order, the multiplications (w[k], B'[k]) and the additions
+ * (acc, T_k = w[k] * B'[k]; an identity T_k as rz = 1, rx = ry = 0) in the format of vpin_gadget_point_mult / _add.
+ * VPIN_ESHAPE when a B'[k] or an accumulator is the identity (no witness format for it: a filter whose first tap is 0, an
+ * all-identity plane); VPIN_EVERIFY when the two sides differ.  No trace is returned on failure. */
+typedef struct vpin_conv_trace vpin_conv_trace;
+int vpin_enc_conv2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
+                    const uint8_t* filter_le16, size_t fh, size_t fw, size_t pad, size_t stride, const uint8_t* keys32, int prf_bytes,
+                    vpin_conv_trace** out);
+void vpin_conv_trace_free(vpin_conv_trace* t);
+/* out = {P, oh, ow, multiplications, additions} */
+int vpin_conv_trace_dims(const vpin_conv_trace* t, size_t out[5]);
+/* Borrowed views, valid until vpin_conv_trace_free: the output ciphertext (P x oh x ow points) */
+int vpin_conv_trace_output(const vpin_conv_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf);
+/* the multiplication list: weights n x 16 bytes, points n x 32 bytes each */
+int vpin_conv_trace_mults(const vpin_conv_trace* t, const uint8_t** weights_le16, const uint8_t** px, const uint8_t** py);
+/* the addition list: n x 32 bytes each, rz n bytes */
+int vpin_conv_trace_adds(const vpin_conv_trace* t, const uint8_t** px, const uint8_t** py, const uint8_t** rx, const uint8_t** ry,
+                         const uint8_t** rz);
+/* the left side sum_t r_t * out[t] of every plane (P points) */
+int vpin_conv_trace_left(const vpin_conv_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf);
+/* the two lists through vpin_gadget_point_mult_dev / vpin_gadget_point_add_dev: instances ready for vpin_snark_prove_dev
+ * (*add_out stays NULL for a 1 x 1 filter, which has no additions); free them with vpin_dev_instance_free */
+int vpin_conv_trace_instances(vpin_ctx* ctx, const vpin_conv_trace* t, vpin_dev_instance** mult_out, vpin_dev_instance** add_out);
+/* wall-clock spans of the last vpin_enc_conv2d on this thread, seconds: [0] validate (upload + checks)  [1] convolution
+ * (+ normalisation, outputs to the host)  [2] PRF (HMAC-SHA256, host team)  [3] RLC sums  [4] host tail  [5] total */
+void vpin_enc_conv_last_timings(double out[8]);
+
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's
  * c*Q and blind*H terms are host work: nizk/mod.rs:447-531).  x = the vector being reduced (a in bullet.rs), a = the

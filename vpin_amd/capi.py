@@ -164,6 +164,19 @@ def lib():
     L.vpin_dev_instance_is_sat.argtypes = [vp, vp]
     L.vpin_spark_encode_dev.argtypes = [vp, vp, C.POINTER(vp), vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vpin_snark_prove_dev.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
+    L.vpin_e2_msm.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_conv2d.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
+    L.vpin_enc_conv2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
+    L.vpin_conv_trace_free.argtypes = [vp]
+    L.vpin_conv_trace_free.restype = None
+    L.vpin_conv_trace_dims.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.vpin_conv_trace_output.argtypes = [vp] + [C.POINTER(vp)] * 3
+    L.vpin_conv_trace_mults.argtypes = [vp] + [C.POINTER(vp)] * 3
+    L.vpin_conv_trace_adds.argtypes = [vp] + [C.POINTER(vp)] * 5
+    L.vpin_conv_trace_left.argtypes = [vp] + [C.POINTER(vp)] * 3
+    L.vpin_conv_trace_instances.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vpin_enc_conv_last_timings.restype = None
+    L.vpin_enc_conv_last_timings.argtypes = [C.POINTER(C.c_double)]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]
@@ -361,6 +374,59 @@ class DevInstance:
     def free(self):
         if self.h:
             lib().vpin_dev_instance_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class ConvTrace:
+    """What vpin_enc_conv2d returns: the output ciphertext of an encrypted convolution layer and the two operation lists
+    of its random-linear-combination check, in the gadgets' input format (host memory, owned by the library)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        d = (C.c_size_t * 5)()
+        _chk(lib().vpin_conv_trace_dims(handle, d), "vpin_conv_trace_dims")
+        self.P, self.oh, self.ow, self.n_mult, self.n_add = (int(v) for v in d)
+
+    def _views(self, fn, shapes):
+        ptrs = [C.c_void_p() for _ in shapes]
+        _chk(getattr(lib(), fn)(self.h, *[C.byref(p) for p in ptrs]), fn)
+        out = []
+        for p, shape in zip(ptrs, shapes):
+            n = int(np.prod(shape))
+            if n == 0 or not p.value:
+                out.append(np.zeros(shape, dtype=np.uint8))
+            else:
+                out.append(np.frombuffer((C.c_uint8 * n).from_address(p.value), dtype=np.uint8).reshape(shape).copy())
+        return out
+
+    def output(self):
+        """(x, y, inf): (P, oh, ow, 32), (P, oh, ow, 32), (P, oh, ow) uint8"""
+        s = (self.P, self.oh, self.ow)
+        return self._views("vpin_conv_trace_output", [s + (32,), s + (32,), s])
+
+    def mults(self):
+        """(weights as Python ints, px, py)"""
+        w, x, y = self._views("vpin_conv_trace_mults", [(self.n_mult, 16), (self.n_mult, 32), (self.n_mult, 32)])
+        return [int.from_bytes(bytes(r), "little") for r in w], x, y
+
+    def adds(self):
+        """(px, py, rx, ry, rz)"""
+        n = self.n_add
+        return self._views("vpin_conv_trace_adds", [(n, 32), (n, 32), (n, 32), (n, 32), (n,)])
+
+    def left(self):
+        """(x, y, inf) of the left side of every plane"""
+        return self._views("vpin_conv_trace_left", [(self.P, 32), (self.P, 32), (self.P,)])
+
+    def instances(self):
+        """(point-mult DevInstance, point-add DevInstance or None) through vpin_gadget_point_*_dev"""
+        hm, ha = C.c_void_p(), C.c_void_p()
+        _chk(lib().vpin_conv_trace_instances(self.ctx.h, self.h, C.byref(hm), C.byref(ha)), "vpin_conv_trace_instances")
+        return DevInstance(self.ctx, hm), (DevInstance(self.ctx, ha) if ha.value else None)
+
+    def free(self):
+        if self.h:
+            lib().vpin_conv_trace_free(self.h)
             self.h = None
 
 
@@ -1093,6 +1159,61 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _chk(lib().vpin_gadget_point_mult_dev(self.h, p(w), p(x), p(y), len(weights), C.byref(h)), "vpin_gadget_point_mult_dev")
         return DevInstance(self, h)
+
+    # ---- the encrypted convolution layer ----
+    @staticmethod
+    def _points(x, y, inf):
+        x = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32)
+        y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1, 32)
+        f = np.zeros(x.shape[0], dtype=np.uint8) if inf is None else np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+        assert y.shape == x.shape and f.shape[0] == x.shape[0]
+        return x, y, f
+
+    @staticmethod
+    def _u128s(vals):
+        return np.frombuffer(b"".join(int(v).to_bytes(16, "little") for v in vals), dtype=np.uint8).copy()
+
+    def e2_msm(self, scalars, x, y, inf=None):
+        """sum_i scalars[i] * P_i on E2 (vpin_e2_msm); scalars: Python ints < 2^128.  Returns (x, y) as ints, or None for the identity."""
+        x, y, f = self._points(x, y, inf)
+        s = self._u128s(scalars)
+        ox, oy, oi = np.zeros(32, np.uint8), np.zeros(32, np.uint8), np.zeros(1, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_msm(self.h, p(s), p(x), p(y), p(f), x.shape[0], p(ox), p(oy), p(oi)), "vpin_e2_msm")
+        return None if oi[0] else (int.from_bytes(bytes(ox), "little"), int.from_bytes(bytes(oy), "little"))
+
+    def e2_conv2d(self, x, y, inf, H, W, filt, fh, fw, pad=0, stride=1):
+        """one plane through vpin_e2_conv2d; filt: fh*fw Python ints row-major.  Returns (x, y, inf) of the oh x ow outputs."""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == H * W and len(filt) == fh * fw
+        oh, ow = (H + 2 * pad - fh) // stride + 1, (W + 2 * pad - fw) // stride + 1
+        n = max(oh, 0) * max(ow, 0)
+        ox, oy, oi = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        w = self._u128s(filt)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_conv2d(self.h, p(x), p(y), p(f), H, W, p(w), fh, fw, pad, stride, p(ox), p(oy), p(oi)), "vpin_e2_conv2d")
+        return ox.reshape(oh, ow, 32), oy.reshape(oh, ow, 32), oi.reshape(oh, ow)
+
+    def enc_conv2d(self, x, y, inf, P, H, W, filt, fh, fw, pad, stride, keys, prf_bytes=16):
+        """the layer (vpin_enc_conv2d): P planes of H x W points, one filter, one 32-byte key per plane -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == P * H * W and len(filt) == fh * fw
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy()
+        assert k.size == 32 * P
+        w = self._u128s(filt)
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_conv2d(self.h, p(x), p(y), p(f), P, H, W, p(w), fh, fw, pad, stride, p(k), prf_bytes, C.byref(h))
+        if rc:
+            assert not h.value, "vpin_enc_conv2d returned a handle with an error"
+            _chk(rc, "vpin_enc_conv2d")
+        return ConvTrace(self, h)
+
+    @staticmethod
+    def enc_conv_timings():
+        out = (C.c_double * 8)()
+        lib().vpin_enc_conv_last_timings(out)
+        return dict(zip(("validate", "conv", "prf", "rlc", "host_tail", "total"), out))
 
     # ---- profiling ----
     def prof_enable(self, on=True):

@@ -19,6 +19,9 @@ void set_last_error(const char* what, hipError_t e) {
   g_last_error = std::string(what) + ": " + hipGetErrorString(e);
 }
 
+// a rejection that is not a HIP failure (enc_conv.cpp: which input rule was broken)
+void set_last_error_text(const char* text) { g_last_error = text; }
+
 static hipEvent_t get_event(vpin_ctx* c) {
   if (!c->free_events.empty()) {
     hipEvent_t e = c->free_events.back();

@@ -1,0 +1,118 @@
+// e2_dev.h -- device-side arithmetic on the curve E2: y^2 = x^3 + a x + b over F_q (the curve of vPIN's
+// exponential-ElGamal ciphertexts; a is the gadget's public input, host/gadget_ops.h kAPdBytes).
+//
+// Points are Jacobian (X : Y : Z), x = X / Z^2, y = Y / Z^3, over fq_dev.h's Montgomery field; Z == 0 is the identity.
+// The additions are complete BY CASE: an identity operand, P == Q (falls to the doubling) and P == -Q (the identity)
+// are recognised from H = U2 - U1 and R = S2 - S1, so sums over arbitrary ciphertext planes (repeated pixels, P and -P,
+// flagged identities) are exact.  The field product is called, not inlined: a point operation is 10-16 products, and
+// the kernels of enc_conv.hip chain hundreds of them.
+#pragma once
+#include "fq_dev.h"
+
+namespace vpin {
+
+struct e2_jac {
+  fq X, Y, Z;
+};
+
+static __device__ __noinline__ fq e2_fqm(fq a, fq b) { return fq_mul(a, b); }
+
+__device__ __forceinline__ e2_jac e2_identity() {
+  e2_jac r;
+  r.X = fq_zero(); r.Y = fq_one(); r.Z = fq_zero();
+  return r;
+}
+
+__device__ __forceinline__ bool e2_is_identity(const e2_jac& p) { return fq_is_zero(p.Z); }
+
+__device__ __forceinline__ bool fq_eq(const fq& a, const fq& b) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
+  return o == 0;
+}
+
+// R^2 mod q: raw integer -> Montgomery form by one product
+__device__ __forceinline__ fq e2_fq_r2() {
+  fq r;
+  r.v[0] = 0x449c0f01u; r.v[1] = 0xa40611e3u; r.v[2] = 0x68859347u; r.v[3] = 0xd00e1ba7u;
+  r.v[4] = 0x17f5be65u; r.v[5] = 0xceec73d2u; r.v[6] = 0x7c309a3du; r.v[7] = 0x0399411bu;
+  return r;
+}
+
+// limb i of q - 2
+__device__ __forceinline__ constexpr uint32_t e2_qm2_limb(int i) { return i == 0 ? VPIN_Q0 - 2u : fq_modulus_limb(i); }
+
+// a^(q-2), plain square-and-multiply from the top bit (bit 252) down: no per-lane table
+__device__ __noinline__ fq e2_fq_inv(fq a) {
+  fq acc = a;
+#pragma unroll
+  for (int w = 7; w >= 0; w--) {
+    const uint32_t e = e2_qm2_limb(w);
+#pragma nounroll
+    for (int b = (w == 7 ? 27 : 31); b >= 0; b--) {
+      acc = e2_fqm(acc, acc);
+      if ((e >> b) & 1u) acc = e2_fqm(acc, a);
+    }
+  }
+  return acc;
+}
+
+// 2P for any a (dbl-2007-bl without the a = -3 / a = 0 shortcuts).  Z = 0 stays Z = 0; Y = 0 gives Z = 0.
+__device__ __forceinline__ e2_jac e2_dbl(const e2_jac& p, const fq& a) {
+  const fq XX = e2_fqm(p.X, p.X), YY = e2_fqm(p.Y, p.Y), YYYY = e2_fqm(YY, YY), ZZ = e2_fqm(p.Z, p.Z);
+  const fq S = fq_dbl(fq_dbl(e2_fqm(p.X, YY)));
+  const fq M = fq_add(fq_add(fq_dbl(XX), XX), e2_fqm(a, e2_fqm(ZZ, ZZ)));
+  e2_jac r;
+  r.X = fq_sub(e2_fqm(M, M), fq_dbl(S));
+  r.Y = fq_sub(e2_fqm(M, fq_sub(S, r.X)), fq_dbl(fq_dbl(fq_dbl(YYYY))));
+  r.Z = fq_dbl(e2_fqm(p.Y, p.Z));
+  return r;
+}
+
+// P + (x2, y2), the second operand affine and not the identity
+__device__ __forceinline__ e2_jac e2_add_mixed(const e2_jac& p, const fq& x2, const fq& y2, const fq& a) {
+  if (e2_is_identity(p)) {
+    e2_jac r;
+    r.X = x2; r.Y = y2; r.Z = fq_one();
+    return r;
+  }
+  const fq Z1Z1 = e2_fqm(p.Z, p.Z), U2 = e2_fqm(x2, Z1Z1), S2 = e2_fqm(y2, e2_fqm(p.Z, Z1Z1));
+  const fq H = fq_sub(U2, p.X), R = fq_sub(S2, p.Y);
+  if (fq_is_zero(H)) return fq_is_zero(R) ? e2_dbl(p, a) : e2_identity();
+  const fq HH = e2_fqm(H, H), HHH = e2_fqm(H, HH), V = e2_fqm(p.X, HH);
+  e2_jac r;
+  r.X = fq_sub(fq_sub(e2_fqm(R, R), HHH), fq_dbl(V));
+  r.Y = fq_sub(e2_fqm(R, fq_sub(V, r.X)), e2_fqm(p.Y, HHH));
+  r.Z = e2_fqm(p.Z, H);
+  return r;
+}
+
+// P + Q, both Jacobian
+__device__ __forceinline__ e2_jac e2_add(const e2_jac& p, const e2_jac& q, const fq& a) {
+  if (e2_is_identity(p)) return q;
+  if (e2_is_identity(q)) return p;
+  const fq Z1Z1 = e2_fqm(p.Z, p.Z), Z2Z2 = e2_fqm(q.Z, q.Z);
+  const fq U1 = e2_fqm(p.X, Z2Z2), U2 = e2_fqm(q.X, Z1Z1);
+  const fq S1 = e2_fqm(p.Y, e2_fqm(q.Z, Z2Z2)), S2 = e2_fqm(q.Y, e2_fqm(p.Z, Z1Z1));
+  const fq H = fq_sub(U2, U1), R = fq_sub(S2, S1);
+  if (fq_is_zero(H)) return fq_is_zero(R) ? e2_dbl(p, a) : e2_identity();
+  const fq HH = e2_fqm(H, H), HHH = e2_fqm(H, HH), V = e2_fqm(U1, HH);
+  e2_jac r;
+  r.X = fq_sub(fq_sub(e2_fqm(R, R), HHH), fq_dbl(V));
+  r.Y = fq_sub(e2_fqm(R, fq_sub(V, r.X)), e2_fqm(S1, HHH));
+  r.Z = e2_fqm(e2_fqm(p.Z, q.Z), H);
+  return r;
+}
+
+__device__ __forceinline__ e2_jac e2_load(const e2_jac* __restrict__ p) {
+  e2_jac r;
+  r.X = fq_load(&p->X); r.Y = fq_load(&p->Y); r.Z = fq_load(&p->Z);
+  return r;
+}
+
+__device__ __forceinline__ void e2_store(e2_jac* __restrict__ p, const e2_jac& v) {
+  fq_store(&p->X, v.X); fq_store(&p->Y, v.Y); fq_store(&p->Z, v.Z);
+}
+
+}  // namespace vpin

@@ -1,0 +1,364 @@
+// enc_conv.cpp -- the encrypted convolution layer of vPIN's inference server and its random-linear-combination check,
+// host side: input validation, the PRF scalars (HMAC-SHA256, one OpenMP team), the f^2 multiplications and f^2 - 1
+// additions that the check reduces one convolution to, the equality test, and the two operation lists in the order the
+// point-mult / point-add gadgets prove them.  The convolution itself and the f^2 + 1 sums of the check run on the device
+// (enc_conv.hip).  Restates the type-1 path of the reference's convolution service (src/convolution/Server.py,
+// src/LeNet/Server.py: myConv2d, rLCL, rLCR).
+#include <omp.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/vpin_hip.h"
+#include "enc_conv.h"
+#include "host/field.h"
+#include "host/gadget_ops.h"
+
+using vpin::ConvGeom;
+using vpin::EncConvDev;
+using vpin::set_last_error_text;
+using vpin_host::Fq;
+typedef unsigned __int128 u128;
+
+namespace {
+
+// ---- E2 on the host: affine in and out, Jacobian inside, complete by case -----------------------------------------
+
+struct Aff {
+  Fq x = Fq::zero(), y = Fq::zero();
+  bool inf = true;
+};
+struct Jac {
+  Fq X, Y, Z;
+  bool inf() const { return Z.is_zero(); }
+};
+
+Fq fq_from_le32(const uint8_t* b) {
+  Fq t;
+  memcpy(t.l, b, 32);
+  return t * Fq::r2();
+}
+
+const Fq& curve_a() {
+  static const Fq a = fq_from_le32(vpin_gadgets::kAPdBytes);
+  return a;
+}
+
+Jac jac_identity() { return Jac{Fq::zero(), Fq::one(), Fq::zero()}; }
+
+Jac jac_dbl(const Jac& p) {
+  if (p.inf()) return p;
+  const Fq XX = p.X * p.X, YY = p.Y * p.Y, YYYY = YY * YY, ZZ = p.Z * p.Z;
+  Fq S = p.X * YY; S = S + S; S = S + S;
+  const Fq M = XX + XX + XX + curve_a() * ZZ * ZZ;
+  Jac r;
+  r.X = M * M - S - S;
+  Fq t = YYYY + YYYY; t = t + t; t = t + t;
+  r.Y = M * (S - r.X) - t;
+  r.Z = p.Y * p.Z; r.Z = r.Z + r.Z;
+  return r;
+}
+
+Jac jac_add_mixed(const Jac& p, const Aff& q) {
+  if (q.inf) return p;
+  if (p.inf()) return Jac{q.x, q.y, Fq::one()};
+  const Fq ZZ = p.Z * p.Z, U2 = q.x * ZZ, S2 = q.y * ZZ * p.Z, H = U2 - p.X, R = S2 - p.Y;
+  if (H.is_zero()) return R.is_zero() ? jac_dbl(p) : jac_identity();
+  const Fq HH = H * H, HHH = HH * H, V = p.X * HH;
+  Jac r;
+  r.X = R * R - HHH - V - V;
+  r.Y = R * (V - r.X) - p.Y * HHH;
+  r.Z = p.Z * H;
+  return r;
+}
+
+Aff to_affine(const Jac& p) {
+  Aff r;
+  if (p.inf()) return r;
+  const Fq zi = p.Z.invert(), zi2 = zi * zi;
+  r.x = p.X * zi2;
+  r.y = p.Y * zi2 * zi;
+  r.inf = false;
+  return r;
+}
+
+Aff aff_add(const Aff& p, const Aff& q) {
+  if (p.inf) return q;
+  return to_affine(jac_add_mixed(Jac{p.x, p.y, Fq::one()}, q));
+}
+
+Aff aff_mul(u128 w, const Aff& p) {
+  Jac acc = jac_identity();
+  if (p.inf) return Aff();
+  for (int b = 127; b >= 0; b--) {
+    acc = jac_dbl(acc);
+    if ((w >> b) & 1) acc = jac_add_mixed(acc, p);
+  }
+  return to_affine(acc);
+}
+
+bool aff_eq(const Aff& p, const Aff& q) { return p.inf == q.inf && (p.inf || (p.x == q.x && p.y == q.y)); }
+
+// canonical little-endian coordinates; the identity is written as zeros
+void put_point(const Aff& p, uint8_t* x, uint8_t* y) {
+  if (p.inf) { memset(x, 0, 32); memset(y, 0, 32); return; }
+  p.x.to_bytes(x);
+  p.y.to_bytes(y);
+}
+
+// ---- HMAC-SHA256 (RFC 2104) over the library's SHA-256, key of 32 bytes --------------------------------------------
+
+void hmac_sha256_key32(const uint8_t key[32], const uint8_t* msg, size_t n, uint8_t out[32]) {
+  uint8_t inner[64 + 32], outer[64 + 32];  // n <= 32: a decimal index
+  memset(inner, 0x36, 64);
+  memset(outer, 0x5c, 64);
+  for (int i = 0; i < 32; i++) { inner[i] ^= key[i]; outer[i] ^= key[i]; }
+  memcpy(inner + 64, msg, n);
+  vpin_sha256(inner, 64 + n, outer + 64);
+  vpin_sha256(outer, 96, out);
+}
+
+// r_t = int.from_bytes(HMAC(key, ascii_decimal(t))[:prf_bytes], "big") as a little-endian u128
+void prf_scalar(const uint8_t key[32], size_t t, int prf_bytes, uint8_t out_le16[16]) {
+  char msg[32];
+  const int n = snprintf(msg, sizeof(msg), "%zu", t);
+  uint8_t mac[32];
+  hmac_sha256_key32(key, (const uint8_t*)msg, (size_t)n, mac);
+  memset(out_le16, 0, 16);
+  for (int i = 0; i < prf_bytes; i++) out_le16[i] = mac[prf_bytes - 1 - i];
+}
+
+int fail(int code, const char* why) {
+  set_last_error_text(why);
+  return code;
+}
+
+constexpr size_t kMaxDim = (size_t)1 << 24;
+
+int make_geom(size_t P, size_t H, size_t W, size_t fh, size_t fw, size_t pad, size_t stride, ConvGeom* g) {
+  if (!P || !H || !W || !fh || !fw || !stride) return fail(VPIN_EINVAL, "enc_conv: a dimension is zero");
+  if (P > 65535 || H > kMaxDim || W > kMaxDim || fh > kMaxDim || fw > kMaxDim || pad > kMaxDim || stride > kMaxDim || fh * fw > 65534)
+    return fail(VPIN_EINVAL, "enc_conv: a dimension is out of range");
+  if (H + 2 * pad < fh || W + 2 * pad < fw) return fail(VPIN_EINVAL, "enc_conv: the window does not fit the padded plane");
+  g->P = P; g->H = H; g->W = W; g->fh = fh; g->fw = fw; g->pad = pad; g->stride = stride;
+  g->oh = (H + 2 * pad - fh) / stride + 1;
+  g->ow = (W + 2 * pad - fw) / stride + 1;
+  if (g->oh * g->ow >= ((size_t)1 << 31) || H * W >= ((size_t)1 << 31))
+    return fail(VPIN_EINVAL, "enc_conv: a plane has 2^31 pixels or more");
+  return VPIN_OK;
+}
+
+int check_flags(uint32_t flags) {
+  if (flags & vpin::kE2FlagRange) return fail(VPIN_EINVAL, "enc_conv: a coordinate is not below q");
+  if (flags & vpin::kE2FlagOffCurve) return fail(VPIN_EINVAL, "enc_conv: a pixel is not on the curve E2");
+  return VPIN_OK;
+}
+
+Jac jac_from_bytes(const uint8_t* p) {
+  Jac r;
+  memcpy(r.X.l, p, 32); memcpy(r.Y.l, p + 32, 32); memcpy(r.Z.l, p + 64, 32);
+  return r;
+}
+
+thread_local double g_timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+struct Lap {
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  double operator()() {
+    const auto n = std::chrono::steady_clock::now();
+    const double s = std::chrono::duration<double>(n - t).count();
+    t = n;
+    return s;
+  }
+};
+
+int team_size() { return (int)std::max(1.0, std::min(16.0, vpin::host_cpu_quota())); }
+
+}  // namespace
+
+struct vpin_conv_trace {
+  size_t P = 0, oh = 0, ow = 0, n_mult = 0, n_add = 0;
+  std::vector<uint8_t> out_x, out_y, out_inf;        // P * oh * ow
+  std::vector<uint8_t> m_w, m_px, m_py;              // n_mult
+  std::vector<uint8_t> a_px, a_py, a_rx, a_ry, a_rz; // n_add
+  std::vector<uint8_t> left_x, left_y, left_inf;     // P
+};
+
+extern "C" {
+
+int vpin_e2_msm(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n,
+                uint8_t out_x[32], uint8_t out_y[32], uint8_t* out_inf) {
+  if (!c || !scalars_le16 || !px || !py || !pinf || !out_x || !out_y || !out_inf) return fail(VPIN_EINVAL, "vpin_e2_msm: null argument");
+  if (n == 0 || n >= ((size_t)1 << 31)) return fail(VPIN_EINVAL, "vpin_e2_msm: n must be in 1 .. 2^31 - 1");
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, n, &flags);
+  if (rc) return rc;
+  if ((rc = check_flags(flags))) return rc;
+  uint8_t sum[96];
+  if ((rc = d.msm(scalars_le16, n, sum))) return rc;
+  const Aff r = to_affine(jac_from_bytes(sum));
+  put_point(r, out_x, out_y);
+  *out_inf = r.inf ? 1 : 0;
+  return VPIN_OK;
+}
+
+int vpin_e2_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t H, size_t W,
+                   const uint8_t* filter_le16, size_t fh, size_t fw, size_t pad, size_t stride, uint8_t* out_x, uint8_t* out_y,
+                   uint8_t* out_inf) {
+  if (!c || !px || !py || !pinf || !filter_le16 || !out_x || !out_y || !out_inf) return fail(VPIN_EINVAL, "vpin_e2_conv2d: null argument");
+  ConvGeom g;
+  int rc = make_geom(1, H, W, fh, fw, pad, stride, &g);
+  if (rc) return rc;
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
+  if ((rc = check_flags(flags))) return rc;
+  return d.conv(g, filter_le16, out_x, out_y, out_inf);
+}
+
+int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
+                    const uint8_t* filter_le16, size_t fh, size_t fw, size_t pad, size_t stride, const uint8_t* keys32, int prf_bytes,
+                    vpin_conv_trace** out) {
+  if (out) *out = nullptr;
+  if (!c || !px || !py || !pinf || !filter_le16 || !keys32 || !out) return fail(VPIN_EINVAL, "vpin_enc_conv2d: null argument");
+  if (prf_bytes < 1 || prf_bytes > 16) return fail(VPIN_EINVAL, "vpin_enc_conv2d: prf_bytes must be in 1 .. 16");
+  ConvGeom g;
+  int rc = make_geom(P, H, W, fh, fw, pad, stride, &g);
+  if (rc) return rc;
+  for (double& v : g_timings) v = 0.0;
+  Lap total, lap;
+  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  if (!t) return VPIN_ENOMEM;
+  struct Guard { vpin_conv_trace* t; ~Guard() { delete t; } } guard{t};
+  const size_t taps = g.taps(), nsum = taps + 1, per_plane = g.oh * g.ow, n_out = g.outputs();
+  t->P = P; t->oh = g.oh; t->ow = g.ow;
+
+  // validate: upload, range and curve checks on the device
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
+  if ((rc = check_flags(flags))) return rc;
+  g_timings[0] = lap();
+
+  // the convolution
+  t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
+  if ((rc = d.conv(g, filter_le16, t->out_x.data(), t->out_y.data(), t->out_inf.data()))) return rc;
+  g_timings[1] = lap();
+
+  // the PRF scalars: the index restarts at 0 for every plane
+  std::vector<uint8_t> r(n_out * 16);
+#pragma omp parallel for schedule(static) num_threads(team_size())
+  for (long i = 0; i < (long)n_out; i++)
+    prf_scalar(keys32 + 32 * ((size_t)i / per_plane), (size_t)i % per_plane, prf_bytes, &r[16 * (size_t)i]);
+  g_timings[2] = lap();
+
+  // the f^2 + 1 sums of every plane
+  std::vector<uint8_t> sums(P * nsum * 96);
+  if ((rc = d.rlc(r.data(), sums.data()))) return rc;
+  g_timings[3] = lap();
+
+  // host tail: T_k = w[k] * B'[k], the chain of additions, the equation, the two lists
+  std::vector<Aff> B(P * nsum), T(P * taps);
+  std::vector<u128> w(taps);
+  for (size_t k = 0; k < taps; k++) memcpy(&w[k], filter_le16 + 16 * k, 16);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team_size())
+  for (long i = 0; i < (long)(P * nsum); i++) B[(size_t)i] = to_affine(jac_from_bytes(&sums[96 * (size_t)i]));
+  for (size_t p = 0; p < P; p++)
+    for (size_t k = 0; k < taps; k++)
+      if (B[p * nsum + k].inf) return fail(VPIN_ESHAPE, "vpin_enc_conv2d: a multiplication operand B'[k] is the identity (the witness format has no flag for it)");
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team_size())
+  for (long i = 0; i < (long)(P * taps); i++) {
+    const size_t p = (size_t)i / taps, k = (size_t)i % taps;
+    T[(size_t)i] = aff_mul(w[k], B[p * nsum + k]);
+  }
+  t->n_mult = P * taps;
+  t->n_add = P * (taps - 1);
+  t->m_w.resize(t->n_mult * 16); t->m_px.resize(t->n_mult * 32); t->m_py.resize(t->n_mult * 32);
+  t->a_px.resize(t->n_add * 32); t->a_py.resize(t->n_add * 32); t->a_rx.resize(t->n_add * 32); t->a_ry.resize(t->n_add * 32);
+  t->a_rz.resize(t->n_add);
+  t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
+  bool equal = true;
+  for (size_t p = 0; p < P; p++) {
+    Aff acc;
+    for (size_t k = 0; k < taps; k++) {
+      const size_t m = p * taps + k;
+      memcpy(&t->m_w[16 * m], filter_le16 + 16 * k, 16);
+      put_point(B[p * nsum + k], &t->m_px[32 * m], &t->m_py[32 * m]);
+      const Aff& Tk = T[m];
+      if (k == 0) { acc = Tk; continue; }
+      if (acc.inf) return fail(VPIN_ESHAPE, "vpin_enc_conv2d: an addition accumulator is the identity (the witness format has no flag for it)");
+      const size_t ai = p * (taps - 1) + (k - 1);
+      put_point(acc, &t->a_px[32 * ai], &t->a_py[32 * ai]);
+      put_point(Tk, &t->a_rx[32 * ai], &t->a_ry[32 * ai]);
+      t->a_rz[ai] = Tk.inf ? 1 : 0;
+      acc = aff_add(acc, Tk);
+    }
+    const Aff& left = B[p * nsum + taps];
+    put_point(left, &t->left_x[32 * p], &t->left_y[32 * p]);
+    t->left_inf[p] = left.inf ? 1 : 0;
+    if (!aff_eq(acc, left)) equal = false;
+  }
+  g_timings[4] = lap();
+  g_timings[5] = total();
+  if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_conv2d: the two sides of the random linear combination differ");
+  guard.t = nullptr;
+  *out = t;
+  return VPIN_OK;
+}
+
+void vpin_conv_trace_free(vpin_conv_trace* t) { delete t; }
+
+int vpin_conv_trace_dims(const vpin_conv_trace* t, size_t out[5]) {
+  if (!t || !out) return VPIN_EINVAL;
+  out[0] = t->P; out[1] = t->oh; out[2] = t->ow; out[3] = t->n_mult; out[4] = t->n_add;
+  return VPIN_OK;
+}
+
+int vpin_conv_trace_output(const vpin_conv_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf) {
+  if (!t || !x || !y || !inf) return VPIN_EINVAL;
+  *x = t->out_x.data(); *y = t->out_y.data(); *inf = t->out_inf.data();
+  return VPIN_OK;
+}
+
+int vpin_conv_trace_mults(const vpin_conv_trace* t, const uint8_t** weights_le16, const uint8_t** px, const uint8_t** py) {
+  if (!t || !weights_le16 || !px || !py) return VPIN_EINVAL;
+  *weights_le16 = t->m_w.data(); *px = t->m_px.data(); *py = t->m_py.data();
+  return VPIN_OK;
+}
+
+int vpin_conv_trace_adds(const vpin_conv_trace* t, const uint8_t** px, const uint8_t** py, const uint8_t** rx, const uint8_t** ry,
+                         const uint8_t** rz) {
+  if (!t || !px || !py || !rx || !ry || !rz) return VPIN_EINVAL;
+  *px = t->a_px.data(); *py = t->a_py.data(); *rx = t->a_rx.data(); *ry = t->a_ry.data(); *rz = t->a_rz.data();
+  return VPIN_OK;
+}
+
+int vpin_conv_trace_left(const vpin_conv_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf) {
+  if (!t || !x || !y || !inf) return VPIN_EINVAL;
+  *x = t->left_x.data(); *y = t->left_y.data(); *inf = t->left_inf.data();
+  return VPIN_OK;
+}
+
+int vpin_conv_trace_instances(vpin_ctx* c, const vpin_conv_trace* t, vpin_dev_instance** mult_out, vpin_dev_instance** add_out) {
+  if (mult_out) *mult_out = nullptr;
+  if (add_out) *add_out = nullptr;
+  if (!c || !t || !mult_out || !add_out) return VPIN_EINVAL;
+  int rc = vpin_gadget_point_mult_dev(c, t->m_w.data(), t->m_px.data(), t->m_py.data(), t->n_mult, mult_out);
+  if (rc) return rc;
+  if (t->n_add == 0) return VPIN_OK;  // a 1 x 1 filter: one multiplication per plane, nothing to add
+  rc = vpin_gadget_point_add_dev(c, t->a_px.data(), t->a_py.data(), t->a_rx.data(), t->a_ry.data(), t->a_rz.data(), t->n_add, add_out);
+  if (rc) { vpin_dev_instance_free(c, *mult_out); *mult_out = nullptr; }
+  return rc;
+}
+
+void vpin_enc_conv_last_timings(double out[8]) {
+  for (int i = 0; i < 8; i++) out[i] = g_timings[i];
+}
+
+}  // extern "C"

@@ -1,0 +1,302 @@
+// enc_conv.hip -- the server side of vPIN's encrypted convolution on the device: the homomorphic convolution over
+// exponential-ElGamal ciphertext planes on E2 and the sums of its random-linear-combination check.
+//
+//   e2_load_kernel       pixel bytes -> Montgomery coordinates; range (< q) and curve-equation checks, one lane per pixel
+//   e2_conv_kernel       one lane per output pixel: joint double-and-add over the taps, from the top set bit of the largest
+//                        weight down (the weights are launch-wide, so a wave diverges only on padding and identity pixels)
+//   e2_to_affine_kernel  Jacobian -> affine, 256 points per workgroup with ONE Fermat inversion: Montgomery's trick as a
+//                        product tree in LDS (up-sweep of products, inverse of the root, down-sweep of inverses)
+//   e2_rlc_kernel        one lane per (sum, term): 128-step double-and-add of r_t times the term's point (mixed addition:
+//                        window pixels and normalised outputs are affine), then an LDS tree with the complete addition
+//   e2_reduce_kernel     the second launch: one workgroup per sum over the partials of the first
+// Exactness: every addition is complete by case (e2_dev.h), so repeated pixels, P / -P pairs and identities are summed
+// correctly.  The accumulators are named registers (e2_jac locals, the scalar as four shifted words): no per-lane arrays.
+#include "e2_dev.h"
+#include "enc_conv.h"
+
+#include <cstring>
+#include <vector>
+
+#include "host/field.h"
+#include "host/gadget_ops.h"
+
+namespace vpin {
+
+namespace {
+
+constexpr int kEB = 256;
+
+struct GeomDev {
+  int H, W, fh, fw, pad, stride, oh, ow;
+};
+
+// index of tap k of output t's window inside its plane, or -1 in the padding
+__device__ __forceinline__ long window_index(const GeomDev& g, int t, int k) {
+  const int i = t / g.ow, j = t % g.ow, ii = k / g.fw, jj = k % g.fw;
+  const int r = i * g.stride + ii - g.pad, c = j * g.stride + jj - g.pad;
+  if (r < 0 || r >= g.H || c < 0 || c >= g.W) return -1;
+  return (long)r * g.W + c;
+}
+
+__global__ __launch_bounds__(kEB) void e2_load_kernel(const fq* __restrict__ xb, const fq* __restrict__ yb,
+                                                      const uint8_t* __restrict__ inf, size_t n, fq a, fq b,
+                                                      fq* __restrict__ X, fq* __restrict__ Y, uint32_t* __restrict__ flags) {
+  const size_t i = (size_t)blockIdx.x * kEB + threadIdx.x;
+  if (i >= n) return;
+  const fq xr = fq_load(xb + i), yr = fq_load(yb + i);
+  unsigned bx = 0, by = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    (void)__builtin_subc(xr.v[k], fq_modulus_limb(k), bx, &bx);
+    (void)__builtin_subc(yr.v[k], fq_modulus_limb(k), by, &by);
+  }
+  uint32_t f = (bx && by) ? 0u : kE2FlagRange;  // no borrow: the value is >= q
+  const fq x = e2_fqm(xr, e2_fq_r2()), y = e2_fqm(yr, e2_fq_r2());
+  if (!f && !inf[i]) {
+    const fq lhs = e2_fqm(y, y);
+    const fq rhs = fq_add(e2_fqm(fq_add(e2_fqm(x, x), a), x), b);
+    if (!fq_eq(lhs, rhs)) f = kE2FlagOffCurve;
+  }
+  fq_store(X + i, x);
+  fq_store(Y + i, y);
+  if (f) atomicOr(flags, f);
+}
+
+__global__ __launch_bounds__(64) void e2_conv_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                     const uint8_t* __restrict__ inf, GeomDev g,
+                                                     const uint32_t* __restrict__ w, int top_bit, fq a,
+                                                     e2_jac* __restrict__ out) {
+  const int t = (int)(blockIdx.x * 64 + threadIdx.x), n_out = g.oh * g.ow;
+  if (t >= n_out) return;
+  const size_t plane = blockIdx.y, base = plane * (size_t)g.H * g.W;
+  const int taps = g.fh * g.fw;
+  e2_jac acc = e2_identity();
+  for (int bit = top_bit; bit >= 0; bit--) {
+    if (!e2_is_identity(acc)) acc = e2_dbl(acc, a);
+    for (int k = 0; k < taps; k++) {
+      if (!((w[4 * k + (bit >> 5)] >> (bit & 31)) & 1u)) continue;  // the same for every lane
+      const long wi = window_index(g, t, k);
+      if (wi < 0 || inf[base + wi]) continue;  // padding and flagged pixels are the identity
+      acc = e2_add_mixed(acc, fq_load(X + base + wi), fq_load(Y + base + wi), a);
+    }
+  }
+  e2_store(out + plane * (size_t)n_out + t, acc);
+}
+
+// mx, my: Montgomery (for e2_rlc_kernel); cx, cy: canonical little-endian (the caller's bytes); identity: zeros and flag 1
+__global__ __launch_bounds__(kEB) void e2_to_affine_kernel(const e2_jac* __restrict__ in, size_t n, fq* __restrict__ mx,
+                                                           fq* __restrict__ my, fq* __restrict__ cx, fq* __restrict__ cy,
+                                                           uint8_t* __restrict__ oinf) {
+  __shared__ fq tree[2 * kEB];  // node j has children 2j and 2j + 1; the leaves are tree[kEB ..]
+  const int tid = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * kEB + tid;
+  e2_jac p = e2_identity();
+  if (i < n) p = e2_load(in + i);
+  const bool idn = e2_is_identity(p);
+  fq_store(&tree[kEB + tid], idn ? fq_one() : p.Z);
+  __syncthreads();
+  for (int wdt = kEB / 2; wdt >= 1; wdt >>= 1) {
+    if (tid < wdt) {
+      const int j = wdt + tid;
+      fq_store(&tree[j], e2_fqm(fq_load(&tree[2 * j]), fq_load(&tree[2 * j + 1])));
+    }
+    __syncthreads();
+  }
+  if (tid == 0) fq_store(&tree[1], e2_fq_inv(fq_load(&tree[1])));
+  __syncthreads();
+  for (int wdt = 1; wdt <= kEB / 2; wdt <<= 1) {
+    if (tid < wdt) {
+      const int j = wdt + tid;
+      const fq pi = fq_load(&tree[j]), l = fq_load(&tree[2 * j]), r = fq_load(&tree[2 * j + 1]);
+      fq_store(&tree[2 * j], e2_fqm(pi, r));
+      fq_store(&tree[2 * j + 1], e2_fqm(pi, l));
+    }
+    __syncthreads();
+  }
+  if (i >= n) return;
+  fq x = fq_zero(), y = fq_zero();
+  if (!idn) {
+    const fq zi = fq_load(&tree[kEB + tid]), zi2 = e2_fqm(zi, zi);
+    x = e2_fqm(p.X, zi2);
+    y = e2_fqm(p.Y, e2_fqm(zi2, zi));
+  }
+  fq_store(mx + i, x);
+  fq_store(my + i, y);
+  fq_store(cx + i, fq_from_mont(x));
+  fq_store(cy + i, fq_from_mont(y));
+  oinf[i] = idn ? 1 : 0;
+}
+
+// sum of the workgroup's kEB points into sh[0]
+__device__ __forceinline__ void e2_block_tree(e2_jac* sh, const e2_jac& mine, const fq& a) {
+  const int tid = threadIdx.x;
+  e2_store(&sh[tid], mine);
+  __syncthreads();
+  for (int wdt = kEB / 2; wdt >= 1; wdt >>= 1) {
+    if (tid < wdt) e2_store(&sh[tid], e2_add(e2_load(&sh[tid]), e2_load(&sh[tid + wdt]), a));
+    __syncthreads();
+  }
+}
+
+// grid: x = blocks of terms, y = sum (tap k, or taps = the outputs themselves), z = plane
+__global__ __launch_bounds__(kEB) void e2_rlc_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                     const uint8_t* __restrict__ inf, const fq* __restrict__ OX,
+                                                     const fq* __restrict__ OY, const uint8_t* __restrict__ oinf, GeomDev g,
+                                                     int taps, size_t n_terms, const uint4* __restrict__ r, fq a,
+                                                     e2_jac* __restrict__ parts) {
+  __shared__ e2_jac sh[kEB];
+  const size_t t = (size_t)blockIdx.x * kEB + threadIdx.x, plane = blockIdx.z;
+  const int s = (int)blockIdx.y;
+  bool have = false;
+  fq x = fq_zero(), y = fq_zero();
+  if (t < n_terms) {
+    if (s == taps) {
+      const size_t idx = plane * n_terms + t;
+      if (!oinf[idx]) { have = true; x = fq_load(OX + idx); y = fq_load(OY + idx); }
+    } else {
+      const long wi = window_index(g, (int)t, s);
+      const size_t idx = plane * (size_t)g.H * g.W + (size_t)(wi < 0 ? 0 : wi);
+      if (wi >= 0 && !inf[idx]) { have = true; x = fq_load(X + idx); y = fq_load(Y + idx); }
+    }
+  }
+  e2_jac acc = e2_identity();
+  if (have) {
+    const uint4 rr = r[plane * n_terms + t];
+    uint32_t r0 = rr.x, r1 = rr.y, r2 = rr.z, r3 = rr.w;
+    if (r0 | r1 | r2 | r3) {
+      int nb = 128;
+#define VPIN_E2_SHL1() do { r3 = (r3 << 1) | (r2 >> 31); r2 = (r2 << 1) | (r1 >> 31); r1 = (r1 << 1) | (r0 >> 31); r0 <<= 1; nb--; } while (0)
+      while (!(r3 >> 31)) VPIN_E2_SHL1();
+      acc.X = x; acc.Y = y; acc.Z = fq_one();  // the top set bit
+      VPIN_E2_SHL1();
+      for (; nb > 0;) {
+        acc = e2_dbl(acc, a);
+        if (r3 >> 31) acc = e2_add_mixed(acc, x, y, a);
+        VPIN_E2_SHL1();
+      }
+#undef VPIN_E2_SHL1
+    }
+  }
+  e2_block_tree(sh, acc, a);
+  if (threadIdx.x == 0)
+    e2_store(parts + ((plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
+}
+
+// one workgroup per sum: out[b] = sum of parts[b * n_parts ..][0 .. n_parts)
+__global__ __launch_bounds__(kEB) void e2_reduce_kernel(const e2_jac* __restrict__ parts, size_t n_parts, fq a,
+                                                        e2_jac* __restrict__ out) {
+  __shared__ e2_jac sh[kEB];
+  const e2_jac* p = parts + (size_t)blockIdx.x * n_parts;
+  e2_jac acc = e2_identity();
+  for (size_t i = threadIdx.x; i < n_parts; i += kEB) acc = e2_add(acc, e2_load(p + i), a);
+  e2_block_tree(sh, acc, a);
+  if (threadIdx.x == 0) e2_store(out + blockIdx.x, e2_load(&sh[0]));
+}
+
+using vpin_host::Fq;
+
+fq fq_of_le32(const uint8_t* b) {
+  Fq t;
+  memcpy(t.l, b, 32);
+  t = t * Fq::r2();
+  fq r;
+  memcpy(r.v, t.l, 32);
+  return r;
+}
+
+// the curve coefficient b of E2, little-endian (a: host/gadget_ops.h kAPdBytes)
+const uint8_t kE2BBytes[32] = {86, 83, 202, 68, 110, 236, 64, 249, 56, 118, 236, 1, 191, 143, 126, 100,
+                               4, 149, 41, 137, 111, 171, 93, 146, 250, 112, 171, 90, 44, 184, 8, 8};
+
+GeomDev geom_dev(const ConvGeom& g) {
+  return GeomDev{(int)g.H, (int)g.W, (int)g.fh, (int)g.fw, (int)g.pad, (int)g.stride, (int)g.oh, (int)g.ow};
+}
+
+unsigned blocks_of(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+#define VPIN_EC_ALLOC(buf, bytes) do { (buf).release(); if ((buf).alloc((bytes) ? (bytes) : 16)) return VPIN_ENOMEM; } while (0)
+
+// the sums of e2_rlc_kernel + e2_reduce_kernel: P x (taps + 1) Jacobian triples to the host
+int run_rlc(vpin_ctx* c, const fq* X, const fq* Y, const uint8_t* inf, const fq* OX, const fq* OY, const uint8_t* oinf,
+            const ConvGeom& g, size_t n_terms, const uint8_t* r_le16, uint8_t* sums_jac) {
+  const size_t nsum = g.taps() + 1, nblk = (n_terms + kEB - 1) / kEB, total = g.P * n_terms;
+  DevBuf r(c), parts(c), sums(c);
+  if (r.alloc(total * 16) || parts.alloc(g.P * nsum * nblk * sizeof(e2_jac)) || sums.alloc(g.P * nsum * sizeof(e2_jac)))
+    return VPIN_ENOMEM;
+  const fq a = fq_of_le32(vpin_gadgets::kAPdBytes);
+  VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le16, total * 16, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(e2_rlc_kernel, dim3((unsigned)nblk, (unsigned)nsum, (unsigned)g.P), dim3(kEB), 0, c->stream, X, Y, inf, OX, OY,
+                     oinf, geom_dev(g), (int)g.taps(), n_terms, (const uint4*)r.p, a, (e2_jac*)parts.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(e2_reduce_kernel, dim3((unsigned)(g.P * nsum)), dim3(kEB), 0, c->stream, (const e2_jac*)parts.p, nblk, a,
+                     (e2_jac*)sums.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  VPIN_HIP_TRY(hipMemcpyAsync(sums_jac, sums.p, g.P * nsum * sizeof(e2_jac), hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+}  // namespace
+
+int EncConvDev::load(const uint8_t* x, const uint8_t* y, const uint8_t* inf, size_t n, uint32_t* flags) {
+  (void)hipSetDevice(c->device);
+  DevBuf rx(c), ry(c), fl(c);
+  if (rx.alloc(n * 32) || ry.alloc(n * 32) || fl.alloc(16)) return VPIN_ENOMEM;
+  VPIN_EC_ALLOC(px, n * 32);
+  VPIN_EC_ALLOC(py, n * 32);
+  VPIN_EC_ALLOC(pinf, n);
+  VPIN_HIP_TRY(hipMemcpyAsync(rx.p, x, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(ry.p, y, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(pinf.p, inf, n, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemsetAsync(fl.p, 0, 4, c->stream));
+  hipLaunchKernelGGL(e2_load_kernel, dim3(blocks_of(n, kEB)), dim3(kEB), 0, c->stream, (const fq*)rx.p, (const fq*)ry.p,
+                     (const uint8_t*)pinf.p, n, fq_of_le32(vpin_gadgets::kAPdBytes), fq_of_le32(kE2BBytes), (fq*)px.p, (fq*)py.p,
+                     (uint32_t*)fl.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  VPIN_HIP_TRY(hipMemcpyAsync(flags, fl.p, 4, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+int EncConvDev::conv(const ConvGeom& geom, const uint8_t* filter_le16, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {
+  (void)hipSetDevice(c->device);
+  g = geom;
+  const size_t taps = g.taps(), n_out = g.outputs(), per_plane = g.oh * g.ow;
+  int top_bit = -1;
+  for (size_t k = 0; k < taps; k++)
+    for (int b = 127; b > top_bit; b--)
+      if ((filter_le16[16 * k + (b >> 3)] >> (b & 7)) & 1) { top_bit = b; break; }
+  DevBuf jac(c), cx(c), cy(c);
+  if (jac.alloc(n_out * sizeof(e2_jac)) || cx.alloc(n_out * 32) || cy.alloc(n_out * 32)) return VPIN_ENOMEM;
+  VPIN_EC_ALLOC(filt, taps * 16);
+  VPIN_EC_ALLOC(ox, n_out * 32);
+  VPIN_EC_ALLOC(oy, n_out * 32);
+  VPIN_EC_ALLOC(oinf, n_out);
+  VPIN_HIP_TRY(hipMemcpyAsync(filt.p, filter_le16, taps * 16, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(e2_conv_kernel, dim3(blocks_of(per_plane, 64), (unsigned)g.P), dim3(64), 0, c->stream, (const fq*)px.p,
+                     (const fq*)py.p, (const uint8_t*)pinf.p, geom_dev(g), (const uint32_t*)filt.p, top_bit,
+                     fq_of_le32(vpin_gadgets::kAPdBytes), (e2_jac*)jac.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(e2_to_affine_kernel, dim3(blocks_of(n_out, kEB)), dim3(kEB), 0, c->stream, (const e2_jac*)jac.p, n_out,
+                     (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, oinf.p, n_out, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+int EncConvDev::rlc(const uint8_t* r_le16, uint8_t* sums_jac) {
+  (void)hipSetDevice(c->device);
+  return run_rlc(c, (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, (const fq*)ox.p, (const fq*)oy.p,
+                 (const uint8_t*)oinf.p, g, g.oh * g.ow, r_le16, sums_jac);
+}
+
+int EncConvDev::msm(const uint8_t* r_le16, size_t n, uint8_t sum_jac[96]) {
+  (void)hipSetDevice(c->device);
+  ConvGeom one;  // no taps: the single sum runs over the loaded points themselves
+  return run_rlc(c, nullptr, nullptr, nullptr, (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, one, n, r_le16, sum_jac);
+}
+
+}  // namespace vpin
