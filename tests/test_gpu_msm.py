@@ -227,6 +227,7 @@ def test_commit_rows_blocks_equal_the_whole_commitment(ctx, gens34):
         assert np.array_equal(out, whole0[row0:row0 + nrows]), (row0, nrows)
     out = np.zeros((4, 32), dtype=np.uint8)
     assert L.vpin_hyrax_commit_rows(ctx.h, g.h, dZ.h, Ls, 14, 4, None, 33, out.ctypes.data_as(C.c_void_p)) == -5  # rows past L
+    assert L.vpin_hyrax_commit_rows(ctx.h, g.h, dZ.h, Ls, 0, 0, None, 33, out.ctypes.data_as(C.c_void_p)) == -1  # no rows
 
 
 def test_table_write_roundtrip(ctx):

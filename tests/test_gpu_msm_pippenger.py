@@ -114,12 +114,15 @@ def test_refused_arguments(ctx):
     xyzt, _ = O.gens_stream_xyzt(34)
     g = ctx.gens_create(xyzt)
     dZ = ctx.upload(np.zeros((64, 4), dtype=np.uint64))
-    with pytest.raises(vpin_amd.VpinError):
+    with pytest.raises(vpin_amd.VpinError) as ei:
         ctx.hyrax_commit_pippenger(g, dZ, None, 0, Ls=2, c_bits=8)       # fewer buckets than lanes
-    with pytest.raises(vpin_amd.VpinError):
+    assert ei.value.code == -1
+    with pytest.raises(vpin_amd.VpinError) as ei:
         ctx.hyrax_commit_pippenger(g, dZ, None, 0, Ls=1, c_bits=0)       # R = 64 > 34 generators
-    with pytest.raises(vpin_amd.VpinError):
+    assert ei.value.code == -5
+    with pytest.raises(vpin_amd.VpinError) as ei:
         ctx.hyrax_commit_pippenger(g, dZ, None, 0, Ls=3, c_bits=0)       # 64 scalars are not 3 rows
+    assert ei.value.code == -5
     dZ.free()
     g.free()
 

@@ -25,13 +25,6 @@ __device__ __forceinline__ e2_jac e2_identity() {
 
 __device__ __forceinline__ bool e2_is_identity(const e2_jac& p) { return fq_is_zero(p.Z); }
 
-__device__ __forceinline__ bool fq_eq(const fq& a, const fq& b) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
-  return o == 0;
-}
-
 // R^2 mod q: raw integer -> Montgomery form by one product
 __device__ __forceinline__ fq e2_fq_r2() {
   fq r;

@@ -206,7 +206,8 @@ __device__ __forceinline__ fp fp_const(uint32_t a0, uint32_t a1, uint32_t a2, ui
   r.v[0] = a0; r.v[1] = a1; r.v[2] = a2; r.v[3] = a3; r.v[4] = a4; r.v[5] = a5; r.v[6] = a6; r.v[7] = a7;
   return r;
 }
-// 2*d
+// d = -121665/121666 and 2*d
+__device__ __forceinline__ fp FP_D() { return fp_const(0x135978a3u, 0x75eb4dcau, 0x4141d8abu, 0x00700a4du, 0x7779e898u, 0x8cc74079u, 0x2b6ffe73u, 0x52036ceeu); }
 __device__ __forceinline__ fp FP_D2() { return fp_const(0x26b2f159u, 0xebd69b94u, 0x8283b156u, 0x00e0149au, 0xeef3d130u, 0x198e80f2u, 0x56dffce7u, 0x2406d9dcu); }
 __device__ __forceinline__ fp FP_SQRT_M1() { return fp_const(0x4a0ea0b0u, 0xc4ee1b27u, 0xad2fe478u, 0x2f431806u, 0x3dfbd7a7u, 0x2b4d0099u, 0x4fc1df0bu, 0x2b832480u); }
 __device__ __forceinline__ fp FP_INVSQRT_A_MINUS_D() { return fp_const(0x805d40eau, 0x99c8fdaau, 0x5a4172beu, 0x9d2f1617u, 0xfe01d840u, 0x16c27b91u, 0xcfaffca2u, 0x786c8905u); }

@@ -72,6 +72,13 @@ __device__ __forceinline__ bool fq_is_zero(const fq& a) {
   return o == 0;
 }
 
+__device__ __forceinline__ bool fq_eq(const fq& a, const fq& b) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
+  return o == 0;
+}
+
 // Carry chains use clang's add/sub-with-carry builtins: they lower to v_add_co_u32 / v_addc_co_u32
 // links (one VALU instruction per limb), a quarter of what the 64-bit-per-limb formulation cost.
 

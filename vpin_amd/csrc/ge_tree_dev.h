@@ -1,8 +1,95 @@
-// ge_tree_dev.h -- the block tree that sums the points of a workgroup with four lanes per addition (msm.hip, msm_pip.hip)
+// ge_tree_dev.h -- the group-element layer the MSM files share (msm.hip, msm_pip.hip, msm_var.hip): points to and from
+// global memory, the limb-strided ten-limb form, the signed-window recoding and the Horner sum of the bucket methods, and
+// the block tree that sums the points of a workgroup with four lanes per addition
 #pragma once
-#include "fp_dev.h"
+#include "fp10_dev.h"
 
 namespace vpin {
+
+// ---- points to and from global memory ----------------------------------------------------------------------------------
+__device__ __forceinline__ ge_ext ge_load(const ge_ext* p) {
+  ge_ext e;
+  e.X = fp_load(&p->X); e.Y = fp_load(&p->Y); e.Z = fp_load(&p->Z); e.T = fp_load(&p->T);
+  return e;
+}
+__device__ __forceinline__ void ge_store(ge_ext* o, const ge_ext& a) {
+  fp_store(&o->X, a.X); fp_store(&o->Y, a.Y); fp_store(&o->Z, a.Z); fp_store(&o->T, a.T);
+}
+__device__ __forceinline__ void ge_store_identity(ge_ext* o) { ge_store(o, ge_identity()); }
+__device__ __forceinline__ ge_niels ge_load(const ge_niels* p) {
+  ge_niels e;
+  e.ypx = fp_load(&p->ypx); e.ymx = fp_load(&p->ymx); e.xy2d = fp_load(&p->xy2d);
+  return e;
+}
+__device__ __forceinline__ void ge_store(ge_niels* o, const ge_niels& a) {
+  fp_store(&o->ypx, a.ypx); fp_store(&o->ymx, a.ymx); fp_store(&o->xy2d, a.xy2d);
+}
+__device__ __forceinline__ ge_cached ge_load(const ge_cached* p) {
+  ge_cached e;
+  e.YpX = fp_load(&p->YpX); e.YmX = fp_load(&p->YmX); e.Z = fp_load(&p->Z); e.T2d = fp_load(&p->T2d);
+  return e;
+}
+__device__ __forceinline__ void ge_store(ge_cached* o, const ge_cached& a) {
+  fp_store(&o->YpX, a.YpX); fp_store(&o->YmX, a.YmX); fp_store(&o->Z, a.Z); fp_store(&o->T2d, a.T2d);
+}
+// a point as X | Y | Z | T, four consecutive field elements (the form the host holds): as stored, or canonical
+__device__ __forceinline__ ge_ext ge_load(const fp* xyzt) { return ge_load(reinterpret_cast<const ge_ext*>(xyzt)); }
+__device__ __forceinline__ void ge_store(fp* xyzt, const ge_ext& a) { ge_store(reinterpret_cast<ge_ext*>(xyzt), a); }
+__device__ __forceinline__ void ge_store_frozen(fp* xyzt, const ge_ext& a) {
+  fp_store(xyzt, fp_freeze(a.X)); fp_store(xyzt + 1, fp_freeze(a.Y)); fp_store(xyzt + 2, fp_freeze(a.Z)); fp_store(xyzt + 3, fp_freeze(a.T));
+}
+// the end of a variable-base MSM: the compressed encoding and the canonical X | Y | Z | T
+__device__ __forceinline__ void ge_store_result(fp* out32, fp* out_xyzt, const ge_ext& r) {
+  fp_store(out32, ge_compress(r));
+  ge_store_frozen(out_xyzt, r);
+}
+
+// ---- ten-limb points, limb-strided: limb l of coordinate k at p[(10 k + l) stride] (lane- or bucket-major arrays) --------
+__device__ __forceinline__ void ge10_store_strided(uint32_t* __restrict__ p, size_t stride, const ge10& a) {
+#pragma unroll
+  for (int l = 0; l < 10; l++) {
+    p[(size_t)l * stride] = a.X.v[l]; p[(size_t)(10 + l) * stride] = a.Y.v[l];
+    p[(size_t)(20 + l) * stride] = a.Z.v[l]; p[(size_t)(30 + l) * stride] = a.T.v[l];
+  }
+}
+__device__ __forceinline__ ge10 ge10_load_strided(const uint32_t* __restrict__ p, size_t stride) {
+  ge10 a;
+#pragma unroll
+  for (int l = 0; l < 10; l++) {
+    a.X.v[l] = p[(size_t)l * stride]; a.Y.v[l] = p[(size_t)(10 + l) * stride];
+    a.Z.v[l] = p[(size_t)(20 + l) * stride]; a.T.v[l] = p[(size_t)(30 + l) * stride];
+  }
+  return a;
+}
+
+// ---- the bucket methods' windows -----------------------------------------------------------------------------------------
+// One signed window of a canonical scalar, low end first: takes the low cw bits of s and the carry of the window below,
+// shifts s right by cw bits and returns the digit as sign and magnitude (|d| in bits 0..14, sign in bit 15, 0 for a zero
+// digit); carry <- 1 when the digit was negated.  The top window is never negated: its value comes back as it is.
+__device__ __forceinline__ uint16_t fq_signed_window(fq& s, uint32_t& carry, uint32_t cw, bool top) {
+  const uint32_t mask = (1u << cw) - 1u, half = 1u << (cw - 1);
+  uint32_t v = (s.v[0] & mask) + carry;
+#pragma unroll
+  for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], cw);
+  s.v[7] >>= cw;
+  const bool neg = !top && v > half;
+  if (neg) v = (mask + 1u) - v;
+  carry = neg ? 1u : 0u;
+  return (uint16_t)(v | (neg && v ? 0x8000u : 0u));
+}
+// sum_w 2^(offset of window w) wsum[w] over W windows, window w being width(w) bits wide: Horner from the top window down,
+// one lane
+template <class Width>
+__device__ __forceinline__ ge10 ge10_horner_windows(const ge_ext* wsum, int W, Width width) {
+  ge10 acc = ge10_from_ext(ge_load(wsum + W - 1));
+#pragma unroll 1
+  for (int w = W - 2; w >= 0; w--) {
+#pragma unroll 1
+    for (int k = 0, cw = width(w); k < cw; k++) acc = ge10_double(acc);
+    acc = ge10_add_ge10(acc, ge10_from_ext(ge_load(wsum + w)));
+  }
+  return acc;
+}
 
 // ---- block tree with four lanes per addition -----------------------------------------------------------------
 // The few-row MSMs are latency bound: one wave per SIMD issues a modular product in ~0.5 us, and an addition of two

@@ -77,7 +77,9 @@ struct TableSeg {
   size_t j, nb;
   int c, W, E, s32;
   // entry d (multiple d + 1) of window w of this base
-  __device__ __forceinline__ const fp* entry(int w, uint32_t d) const { return t + (((size_t)w * nb + j) * (size_t)E + d) * (size_t)s32; }
+  __device__ __forceinline__ const ge_niels* entry(int w, uint32_t d) const {
+    return reinterpret_cast<const ge_niels*>(t + (((size_t)w * nb + j) * (size_t)E + d) * (size_t)s32);
+  }
 };
 __device__ __forceinline__ TableSeg table_seg(const TableView& tv, size_t j) {
   if (j < tv.split) return TableSeg{tv.t, j, tv.split, tv.c, tv.W, tv.E, tv.s32};
@@ -95,9 +97,7 @@ __global__ __launch_bounds__(256) void gens_sum_kernel(fp* __restrict__ xyzt, si
   const size_t lo = k ? ((size_t)1 << (k - 1)) : 0, hi = (size_t)1 << k;
   ge_ext acc = ge_identity();
   for (size_t j = lo + threadIdx.x; j < hi && j < nb; j += 256) {
-    ge_ext p;
-    p.X = fp_load(xyzt + 4 * j); p.Y = fp_load(xyzt + 4 * j + 1); p.Z = fp_load(xyzt + 4 * j + 2); p.T = fp_load(xyzt + 4 * j + 3);
-    acc = ge_add(acc, p);
+    acc = ge_add(acc, ge_load(xyzt + 4 * j));
   }
   __shared__ ge_ext sh[256];
   sh[threadIdx.x] = acc;
@@ -109,22 +109,15 @@ __global__ __launch_bounds__(256) void gens_sum_kernel(fp* __restrict__ xyzt, si
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    fp* o = xyzt + 4 * (nb + k);
-    fp_store(o, acc.X); fp_store(o + 1, acc.Y); fp_store(o + 2, acc.Z); fp_store(o + 3, acc.T);
-  }
+  if (threadIdx.x == 0) ge_store(xyzt + 4 * (nb + k), acc);
 }
 __global__ void gens_sum_scan_kernel(fp* __restrict__ xyzt, size_t nb, int nsum) {
   if (threadIdx.x || blockIdx.x) return;
-  ge_ext acc;
-  fp* o = xyzt + 4 * nb;
-  acc.X = fp_load(o); acc.Y = fp_load(o + 1); acc.Z = fp_load(o + 2); acc.T = fp_load(o + 3);
+  ge_ext acc = ge_load(xyzt + 4 * nb);
   for (int k = 1; k < nsum; k++) {
     fp* q = xyzt + 4 * (nb + k);
-    ge_ext d;
-    d.X = fp_load(q); d.Y = fp_load(q + 1); d.Z = fp_load(q + 2); d.T = fp_load(q + 3);
-    acc = ge_add(acc, d);
-    fp_store(q, acc.X); fp_store(q + 1, acc.Y); fp_store(q + 2, acc.Z); fp_store(q + 3, acc.T);
+    acc = ge_add(acc, ge_load(q));
+    ge_store(q, acc);
   }
 }
 
@@ -133,19 +126,11 @@ __global__ __launch_bounds__(64) void gens_shift_kernel(const fp* __restrict__ x
                                                         ge_ext* __restrict__ shifts) {
   size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nb) return;
-  ge_ext p;
-  p.X = fp_load(xyzt + 4 * j); p.Y = fp_load(xyzt + 4 * j + 1); p.Z = fp_load(xyzt + 4 * j + 2); p.T = fp_load(xyzt + 4 * j + 3);
+  ge_ext p = ge_load(xyzt + 4 * j);
   for (int w = 0; w < W; w++) {
-    ge_ext* o = shifts + j * W + w;
-    fp_store(&o->X, p.X); fp_store(&o->Y, p.Y); fp_store(&o->Z, p.Z); fp_store(&o->T, p.T);
+    ge_store(shifts + j * W + w, p);
     for (int k = 0; k < c; k++) p = ge_double(p);
   }
-}
-
-__device__ __forceinline__ ge_niels niels_load(const fp* o) {
-  ge_niels e;
-  e.ypx = fp_load(o); e.ymx = fp_load(o + 1); e.xy2d = fp_load(o + 2);
-  return e;
 }
 
 // one thread per (base, window): the E multiples of the shifted base, normalised to affine with
@@ -157,9 +142,7 @@ __global__ __launch_bounds__(64) void gens_table_kernel(const ge_ext* __restrict
   if (idx >= nb * (size_t)W) return;
   size_t j = idx / W;
   int w = (int)(idx % W);
-  const ge_ext* s = shifts + j * W + w;
-  ge_ext p;
-  p.X = fp_load(&s->X); p.Y = fp_load(&s->Y); p.Z = fp_load(&s->Z); p.T = fp_load(&s->T);
+  const ge_ext p = ge_load(shifts + j * W + w);
   ge_cached pc = ge_to_cached(p);
   fp* out = table + (((size_t)w * nb + j) * E) * (size_t)s32;  // slot k at out + k * s32: {ypx, ymx, xy2d}
   fp* pre = prefix + ((size_t)w * nb + j) * E;
@@ -185,13 +168,6 @@ __global__ __launch_bounds__(64) void gens_table_kernel(const ge_ext* __restrict
 }
 
 // ---- scalar handling --------------------------------------------------------------------
-
-__device__ __forceinline__ bool fq_same(const fq& a, const fq& b) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
-  return o == 0;
-}
 
 // accumulate s * g_j into acc through the window table; s canonical, non-zero
 // s -> q - s when s is in the upper half (bit 251 or 252 set): s*g = -((q - s)*g).  Nothing for a random scalar,
@@ -230,7 +206,7 @@ __device__ __forceinline__ void table_mul_acc(ge_ext& acc, fq s, const TableView
       carry = neg_next ? 1u : 0u;
       neg_next ^= flip;
       if (mag != 0) {
-        e_next = niels_load(sg.entry(w, mag - 1));
+        e_next = ge_load(sg.entry(w, mag - 1));
         have_next = true;
       }
     }
@@ -265,7 +241,7 @@ __device__ __forceinline__ void table_mul_acc10(ge10& acc, fq s, const TableView
       carry = neg_next ? 1u : 0u;
       neg_next ^= flip;
       if (mag != 0) {
-        e_next = niels_load(sg.entry(w, mag - 1));
+        e_next = ge_load(sg.entry(w, mag - 1));
         have_next = true;
       }
     }
@@ -314,7 +290,7 @@ __device__ __forceinline__ void table_mul_acc_range(ge_ext& acc, const fq& s_in,
     bool neg = v > half;
     uint32_t mag = neg ? full - v : v;
     carry = neg ? 1u : 0u;
-    if (mag != 0) acc = ge_add_niels(acc, niels_load(sg.entry(w, mag - 1)), neg != flip);
+    if (mag != 0) acc = ge_add_niels(acc, ge_load(sg.entry(w, mag - 1)), neg != flip);
   }
 }
 
@@ -339,9 +315,9 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(const fq* __rest
   if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
     const fq* zr = Z + row * stride;
     const fq first = fq_load(zr);
-    if (fq_same(first, fq_load(zr + 1)) && fq_same(first, fq_load(zr + ncols / 2)) && fq_same(first, fq_load(zr + ncols - 1))) {
+    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
       int same = 1;
-      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_same(first, fq_load(zr + j)) ? 1 : 0;
+      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
       if (__syncthreads_and(same)) {
         if (threadIdx.x == 0) {
           if (blockIdx.y == 0) {  // with column chunks every chunk sees the same row: the first one owns it, the others add nothing
@@ -353,7 +329,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(const fq* __rest
           }
           ge_ext* o = out + row * gridDim.y + blockIdx.y;
           const ge_ext av = acc.ext();
-          fp_store(&o->X, av.X); fp_store(&o->Y, av.Y); fp_store(&o->Z, av.Z); fp_store(&o->T, av.T);
+          ge_store(o, av);
         }
         return;
       }
@@ -394,8 +370,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(const fq* __rest
   ge_tree_quad(sh, kMsmBlock);
   if (threadIdx.x == 0) {
     const ge_ext av = sh[0];
-    ge_ext* o = out + row * gridDim.y + blockIdx.y;
-    fp_store(&o->X, av.X); fp_store(&o->Y, av.Y); fp_store(&o->Z, av.Z); fp_store(&o->T, av.T);
+    ge_store(out + row * gridDim.y + blockIdx.y, av);
   }
 }
 
@@ -420,8 +395,7 @@ __global__ __launch_bounds__(64) void scalar_times_bases_kernel(const fq* __rest
   const fq v = fq_load(vp);
   ge_ext acc = ge_identity();
   if (!fq_is_zero(v)) table_mul_acc(acc, fq_from_mont(v), tv, j);
-  const ge_cached cch = ge_to_cached(acc);
-  fp_store(&T[j].YpX, cch.YpX); fp_store(&T[j].YmX, cch.YmX); fp_store(&T[j].Z, cch.Z); fp_store(&T[j].T2d, cch.T2d);
+  ge_store(T + j, ge_to_cached(acc));
 }
 
 __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols, TableView tv,
@@ -436,16 +410,16 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __
   // a row of one repeated scalar (padding tails): s * (g_0 + ... + g_{ncols-1}), as in msm_rows_kernel
   if (!hot_only && ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
     const fq first = fq_load(zr);
-    if (fq_same(first, fq_load(zr + 1)) && fq_same(first, fq_load(zr + ncols / 2)) && fq_same(first, fq_load(zr + ncols - 1))) {
+    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
       int same = 1;
-      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_same(first, fq_load(zr + j)) ? 1 : 0;
+      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
       if (__syncthreads_and(same)) {
         if (threadIdx.x == 0) {
           // with column chunks every chunk sees the same row: the first one owns it, the others add nothing
           if (blockIdx.y == 0 && !fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
           ge_ext* o = out + (size_t)blockIdx.x * gridDim.y + blockIdx.y;
           const ge_ext av = acc.ext();
-          fp_store(&o->X, av.X); fp_store(&o->Y, av.Y); fp_store(&o->Z, av.Z); fp_store(&o->T, av.T);
+          ge_store(o, av);
         }
         return;
       }
@@ -484,12 +458,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __
       const size_t j = seg + list[k];
       acc.mul_acc(fq_from_mont(fq_load(zr + j)), tv, j);
     }
-    for (uint32_t k = threadIdx.x; k < nb; k += kMsmBlock) {
-      const ge_cached* t = T + seg + list[kSeg - 1 - k];
-      ge_cached q;
-      q.YpX = fp_load(&t->YpX); q.YmX = fp_load(&t->YmX); q.Z = fp_load(&t->Z); q.T2d = fp_load(&t->T2d);
-      acc.add_cached(q);
-    }
+    for (uint32_t k = threadIdx.x; k < nb; k += kMsmBlock) acc.add_cached(ge_load(T + seg + list[kSeg - 1 - k]));
     __syncthreads();
   }
   __shared__ ge_ext sh[kMsmBlock];
@@ -498,8 +467,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __
   ge_tree_quad(sh, kMsmBlock);
   if (threadIdx.x == 0) {
     const ge_ext av = sh[0];
-    ge_ext* o = out + (size_t)blockIdx.x * gridDim.y + blockIdx.y;
-    fp_store(&o->X, av.X); fp_store(&o->Y, av.Y); fp_store(&o->Z, av.Z); fp_store(&o->T, av.T);
+    ge_store(out + (size_t)blockIdx.x * gridDim.y + blockIdx.y, av);
   }
 }
 
@@ -535,7 +503,7 @@ __global__ __launch_bounds__(kMsmBlock) void strip_classify_kernel(const fq* __r
   uint32_t skipped = 0;
   for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) {
     const fq v = fq_load(zr + j);
-    same &= fq_same(first, v) ? 1 : 0;
+    same &= fq_eq(first, v) ? 1 : 0;
     skipped += (fq_is_zero(v) || (idx && idx[j] == hot)) ? 1u : 0u;
   }
   __shared__ uint32_t sh[kMsmBlock];
@@ -630,8 +598,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_strip_kernel(const fq* __res
   }
   if (live) {
     const ge_ext av = ge10_to_ext(acc);
-    ge_ext* o = parts + (size_t)li * (size_t)S + s;
-    fp_store(&o->X, av.X); fp_store(&o->Y, av.Y); fp_store(&o->Z, av.Z); fp_store(&o->T, av.T);
+    ge_store(parts + (size_t)li * (size_t)S + s, av);
   }
 }
 
@@ -641,15 +608,9 @@ __global__ __launch_bounds__(64) void strip_combine_kernel(const ge_ext* __restr
   const uint32_t li = blockIdx.x * 64 + threadIdx.x;
   if (li >= *list_count) return;
   ge_ext* o = out + list[li];
-  ge_ext a;
-  a.X = fp_load(&o->X); a.Y = fp_load(&o->Y); a.Z = fp_load(&o->Z); a.T = fp_load(&o->T);
-  for (int s = 0; s < S; s++) {
-    const ge_ext* p = parts + (size_t)li * (size_t)S + s;
-    ge_ext q;
-    q.X = fp_load(&p->X); q.Y = fp_load(&p->Y); q.Z = fp_load(&p->Z); q.T = fp_load(&p->T);
-    a = ge_add(a, q);
-  }
-  fp_store(&o->X, a.X); fp_store(&o->Y, a.Y); fp_store(&o->Z, a.Z); fp_store(&o->T, a.T);
+  ge_ext a = ge_load(o);
+  for (int s = 0; s < S; s++) a = ge_add(a, ge_load(parts + (size_t)li * (size_t)S + s));
+  ge_store(o, a);
 }
 
 // Profiling aid (vpin_prof_enable(ctx, 2)): the affine table additions msm_rows_kernel performs for the same
@@ -687,7 +648,7 @@ __global__ __launch_bounds__(kMsmBlock) void msm_count_adds_kernel(const fq* __r
   if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
     const fq first = fq_load(zr);
     int same = 1;
-    for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_same(first, fq_load(zr + j)) ? 1 : 0;
+    for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
     constant = __syncthreads_and(same) != 0;
     if (constant && threadIdx.x == 0 && !fq_is_zero(first))
       n += count_digits(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
@@ -743,8 +704,7 @@ __global__ __launch_bounds__(kMsmBlock) void msm_wide_kernel(const fq* __restric
   ge_tree_quad(sh, kMsmBlock);
   if (threadIdx.x == 0) {
     acc = sh[0];
-    fp* o = parts_xyzt + 4 * (row * gridDim.x + blockIdx.x);
-    fp_store(o, fp_freeze(acc.X)); fp_store(o + 1, fp_freeze(acc.Y)); fp_store(o + 2, fp_freeze(acc.Z)); fp_store(o + 3, fp_freeze(acc.T));
+    ge_store_frozen(parts_xyzt + 4 * (row * gridDim.x + blockIdx.x), acc);
   }
 }
 
@@ -855,8 +815,7 @@ __global__ __launch_bounds__(kMsmBlock) void bullet_step_kernel(BulletStep a, Ta
     if (threadIdx.x == 0 || split) {
       const ge_ext p = sh[threadIdx.x ? split : 0];
       const int row = threadIdx.x ? 0 : ((split || !first_is_L) ? 1 : 0);
-      fp* o = a.parts + 4 * ((size_t)row * a.nmsm + blk);
-      fp_store(o, fp_freeze(p.X)); fp_store(o + 1, fp_freeze(p.Y)); fp_store(o + 2, fp_freeze(p.Z)); fp_store(o + 3, fp_freeze(p.T));
+      ge_store_frozen(a.parts + 4 * ((size_t)row * a.nmsm + blk), p);
     }
   }
 }
@@ -873,20 +832,13 @@ __global__ __launch_bounds__(kMsmBlock) void bullet_parts_reduce_kernel(const fp
     const int b = g * per + (int)threadIdx.x;
     if ((int)threadIdx.x < per) {
       const bool is_L = finish || (((size_t)b * kWideScalars) & (2 * n - 1)) >= n;
-      if (finish || n < (size_t)kWideScalars || is_L == (row == 0)) {
-        const fp* q = in + 4 * ((size_t)row * nmsm + b);
-        p.X = fp_load(q); p.Y = fp_load(q + 1); p.Z = fp_load(q + 2); p.T = fp_load(q + 3);
-      }
+      if (finish || n < (size_t)kWideScalars || is_L == (row == 0)) p = ge_load(in + 4 * ((size_t)row * nmsm + b));
     }
     sh[threadIdx.x] = p;
   }
   __syncthreads();
   ge_tree_quad(sh, kMsmBlock / 2);
-  if (threadIdx.x == 0) {
-    const ge_ext p = sh[0];
-    fp* o = out + 4 * ((size_t)row * G + g);
-    fp_store(o, fp_freeze(p.X)); fp_store(o + 1, fp_freeze(p.Y)); fp_store(o + 2, fp_freeze(p.Z)); fp_store(o + 3, fp_freeze(p.T));
-  }
+  if (threadIdx.x == 0) ge_store_frozen(out + 4 * ((size_t)row * G + g), sh[0]);
 }
 
 // second stage for long rows: out[row][p] = sum of parts p, p+P, p+2P, ... of that row (frozen X|Y|Z|T)
@@ -896,14 +848,8 @@ __global__ __launch_bounds__(64) void parts_reduce_kernel(const fp* __restrict__
   if (t >= rows * (size_t)P) return;
   const size_t row = t / P, p = t % P;
   ge_ext acc = ge_identity();
-  for (size_t k = p; k < nraw; k += P) {
-    const fp* q = in + 4 * (row * nraw + k);
-    ge_ext e;
-    e.X = fp_load(q); e.Y = fp_load(q + 1); e.Z = fp_load(q + 2); e.T = fp_load(q + 3);
-    acc = ge_add(acc, e);
-  }
-  fp* o = out + 4 * t;
-  fp_store(o, fp_freeze(acc.X)); fp_store(o + 1, fp_freeze(acc.Y)); fp_store(o + 2, fp_freeze(acc.Z)); fp_store(o + 3, fp_freeze(acc.T));
+  for (size_t k = p; k < nraw; k += P) acc = ge_add(acc, ge_load(in + 4 * (row * nraw + k)));
+  ge_store_frozen(out + 4 * t, acc);
 }
 
 // out[i] = s_i * g[base] for n scalars (the blind terms of the row commitments): 8 threads per
@@ -932,10 +878,7 @@ __global__ __launch_bounds__(64) void single_base_mul_kernel(const fq* __restric
     }
     __syncthreads();
   }
-  if (grp == 0 && i < n) {
-    ge_ext* o = out + i;
-    fp_store(&o->X, acc.X); fp_store(&o->Y, acc.Y); fp_store(&o->Z, acc.Z); fp_store(&o->T, acc.T);
-  }
+  if (grp == 0 && i < n) ge_store(out + i, acc);
 }
 
 // out[row] = sum of the `chunks` partial points of that row
@@ -943,15 +886,10 @@ __global__ __launch_bounds__(64) void ge_sum_chunks_kernel(const ge_ext* __restr
                                                            ge_ext* __restrict__ out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
-  ge_ext acc;
   const ge_ext* p = parts + i * chunks;
-  acc.X = fp_load(&p->X); acc.Y = fp_load(&p->Y); acc.Z = fp_load(&p->Z); acc.T = fp_load(&p->T);
-  for (int k = 1; k < chunks; k++) {
-    ge_ext q;
-    q.X = fp_load(&p[k].X); q.Y = fp_load(&p[k].Y); q.Z = fp_load(&p[k].Z); q.T = fp_load(&p[k].T);
-    acc = ge_add(acc, q);
-  }
-  fp_store(&out[i].X, acc.X); fp_store(&out[i].Y, acc.Y); fp_store(&out[i].Z, acc.Z); fp_store(&out[i].T, acc.T);
+  ge_ext acc = ge_load(p);
+  for (int k = 1; k < chunks; k++) acc = ge_add(acc, ge_load(p + k));
+  ge_store(out + i, acc);
 }
 
 // out[i] = a[i] + b[i]  (row-wise commitment combination, proof_point_mult.rs:75-80)
@@ -959,11 +897,7 @@ __global__ __launch_bounds__(64) void ge_add_rows_kernel(const ge_ext* __restric
                                                          ge_ext* __restrict__ out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  ge_ext p, q;
-  p.X = fp_load(&a[i].X); p.Y = fp_load(&a[i].Y); p.Z = fp_load(&a[i].Z); p.T = fp_load(&a[i].T);
-  q.X = fp_load(&b[i].X); q.Y = fp_load(&b[i].Y); q.Z = fp_load(&b[i].Z); q.T = fp_load(&b[i].T);
-  ge_ext r = ge_add(p, q);
-  fp_store(&out[i].X, r.X); fp_store(&out[i].Y, r.Y); fp_store(&out[i].Z, r.Z); fp_store(&out[i].T, r.T);
+  ge_store(out + i, ge_add(ge_load(a + i), ge_load(b + i)));
 }
 
 // out[j] = generator j (j < n), out[n] = generator blind_base (n_extra = 1): multiple 1 of window 0 in the base's table row
@@ -971,8 +905,7 @@ __global__ __launch_bounds__(256) void pip_gens_kernel(TableView tv, size_t n, s
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n + (size_t)n_extra) return;
   const TableSeg sg = table_seg(tv, i < n ? i : blind_base);
-  const ge_niels e = niels_load(sg.entry(0, 0));
-  fp_store(&out[i].ypx, e.ypx); fp_store(&out[i].ymx, e.ymx); fp_store(&out[i].xy2d, e.xy2d);
+  ge_store(out + i, ge_load(sg.entry(0, 0)));
 }
 
 // RistrettoPoint::compress for n points, one thread each; also emits canonical X|Y|Z|T
@@ -980,13 +913,9 @@ __global__ __launch_bounds__(64) void ge_compress_kernel(const ge_ext* __restric
                                                          fp* __restrict__ out_xyzt) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  ge_ext p;
-  p.X = fp_load(&pts[i].X); p.Y = fp_load(&pts[i].Y); p.Z = fp_load(&pts[i].Z); p.T = fp_load(&pts[i].T);
+  const ge_ext p = ge_load(pts + i);
   if (out32) fp_store(out32 + i, ge_compress(p));
-  if (out_xyzt) {
-    fp_store(out_xyzt + 4 * i, fp_freeze(p.X)); fp_store(out_xyzt + 4 * i + 1, fp_freeze(p.Y));
-    fp_store(out_xyzt + 4 * i + 2, fp_freeze(p.Z)); fp_store(out_xyzt + 4 * i + 3, fp_freeze(p.T));
-  }
+  if (out_xyzt) ge_store_frozen(out_xyzt + 4 * i, p);
 }
 
 }  // namespace vpin
@@ -1000,7 +929,6 @@ namespace vpin {
 __device__ __forceinline__ fp FP_ONE_MINUS_D_SQ() { return fp_const(0x945fc176u, 0xe27c09c1u, 0xcd5e350fu, 0x2c81a138u, 0xbe70dfe4u, 0x9994abddu, 0xb2b3e0d7u, 0x029072a8u); }
 __device__ __forceinline__ fp FP_D_MINUS_ONE_SQ() { return fp_const(0x44ed4d20u, 0x31ad5aaau, 0xb01e1999u, 0xd29e4a2cu, 0x529b4eebu, 0x4cdcd32fu, 0xf66c2241u, 0x5968b37au); }
 __device__ __forceinline__ fp FP_SQRT_AD_MINUS_ONE() { return fp_const(0x497b2e1bu, 0x7e97f6a0u, 0x1b7854bdu, 0xaf9d8e0cu, 0x31f5d1fdu, 0x0f3cfcc9u, 0x2b8348acu, 0x376931bfu); }
-__device__ __forceinline__ fp FP_D_EDWARDS() { return fp_const(0x135978a3u, 0x75eb4dcau, 0x4141d8abu, 0x00700a4du, 0x7779e898u, 0x8cc74079u, 0x2b6ffe73u, 0x52036ceeu); }
 
 // RFC 9496 4.2 SQRT_RATIO_M1(u, v)
 __device__ __forceinline__ fp fp_sqrt_ratio_m1(const fp& u, const fp& v, bool* was_square) {
@@ -1015,7 +943,7 @@ __device__ __forceinline__ fp fp_sqrt_ratio_m1(const fp& u, const fp& v, bool* w
 }
 
 __device__ __noinline__ ge_ext ge_elligator(const fp& t) {
-  const fp one = fp_one(), m1 = fp_neg(one), d = FP_D_EDWARDS();
+  const fp one = fp_one(), m1 = fp_neg(one), d = FP_D();
   const fp r = fp_mul(FP_SQRT_M1(), fp_sqr(t));
   const fp u = fp_mul(fp_add(r, one), FP_ONE_MINUS_D_SQ());
   const fp v = fp_mul(fp_sub(m1, fp_mul(r, d)), fp_add(r, d));
@@ -1042,10 +970,7 @@ __global__ __launch_bounds__(64) void gens_derive_kernel(const uint32_t* __restr
   t0.v[7] &= 0x7fffffffu;  // FieldElement::from_bytes ignores bit 255
   t1.v[7] &= 0x7fffffffu;
   const ge_ext p = ge_add(ge_elligator(t0), ge_elligator(t1));
-  fp_store(xyzt + 4 * i + 0, fp_freeze(p.X));
-  fp_store(xyzt + 4 * i + 1, fp_freeze(p.Y));
-  fp_store(xyzt + 4 * i + 2, fp_freeze(p.Z));
-  fp_store(xyzt + 4 * i + 3, fp_freeze(p.T));
+  ge_store_frozen(xyzt + 4 * i, p);
 }
 
 }  // namespace vpin
@@ -1357,6 +1282,13 @@ static int msm_rows_pip(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t ro
                   c->prof_count_adds ? c->d_add_count : nullptr);
 }
 
+// dynamic LDS the row-commitment kernels do not use: it lowers the workgroups per CU from 3 to 2 on a shared device
+// (vpin_ctx_set_shared_device); VPIN_MSM_LDS_PAD overrides (experiments)
+static unsigned msm_lds_pad(const vpin_ctx* c) {
+  static const int env_pad = [] { const char* e = getenv("VPIN_MSM_LDS_PAD"); return e ? atoi(e) : -1; }();
+  return env_pad >= 0 ? (unsigned)env_pad : (c->shared_device ? kSharedPad : 0u);
+}
+
 static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols,
                     const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points) {
   if (const int pm = pip_mode())
@@ -1392,11 +1324,7 @@ static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, 
                        n_extra, extra_base0, view(g), c->d_add_count);
   {
     ProfScope ps(c, VPIN_K_MSM, 32.0 * nz_est, rows >= 128 ? VPIN_K_MSM_ROWS : -1);
-    // unused dynamic LDS lowers the workgroups per CU from 3 to 2 on a shared device (vpin_ctx_set_shared_device);
-    // VPIN_MSM_LDS_PAD overrides (experiments)
-    static const int env_pad = [] { const char* e = getenv("VPIN_MSM_LDS_PAD"); return e ? atoi(e) : -1; }();
-    const unsigned pad = env_pad >= 0 ? (unsigned)env_pad : (c->shared_device ? kSharedPad : 0u);
-    hipLaunchKernelGGL(msm_rows_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, dZ, stride, ncols,
+    hipLaunchKernelGGL(msm_rows_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, dZ, stride, ncols,
                        d_extra, n_extra, extra_base0, view(g), dst);
   }
   if (chunks > 1)
@@ -1406,26 +1334,44 @@ static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, 
   return VPIN_OK;
 }
 
-int vpin_hyrax_commit(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, const uint8_t* blinds, size_t L,
-                      size_t blind_base, uint8_t* out_compressed) {
-  if (!c || !g || !Z || !Z->d || !blinds || !out_compressed || L == 0) return VPIN_EINVAL;
-  if (Z->len % L != 0) return VPIN_ESHAPE;  // assert_eq!(L_size * R_size, self.Z.len())
-  size_t R = Z->len / L;
-  if (R > g->nb || blind_base >= g->nb) return VPIN_ESHAPE;  // assert_eq!(gens_n.n, self.len())
-  (void)hipSetDevice(c->device);
-  DevBuf dbl(c), dpts(c), dout(c);
-  if (dbl.alloc(L * 32) || dpts.alloc(L * sizeof(ge_ext)) || dout.alloc(L * 32)) return VPIN_ENOMEM;
-  VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds, L * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = msm_rows(c, g, Z->d, L, R, R, (const fq*)dbl.p, 1, blind_base, (ge_ext*)dpts.p);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dpts.p, L,
-                     (fp*)dout.p, (fp*)nullptr);
+// The end of every commitment: compress the n points at d_pts and bring the encodings home, the first n / k of them to out0,
+// the next to out1, .. for the k outputs given; synchronises.
+static int compress_to_host(vpin_ctx* c, const ge_ext* d_pts, size_t n, uint8_t* out0, uint8_t* out1 = nullptr, uint8_t* out2 = nullptr) {
+  uint8_t* const outs[3] = {out0, out1, out2};
+  const size_t k = out2 ? 3 : out1 ? 2 : 1, per = n / k * 32;
+  DevBuf dout(c);
+  if (dout.alloc(n * 32)) return VPIN_ENOMEM;
+  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, d_pts, n, (fp*)dout.p, (fp*)nullptr);
   VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_compressed, dout.p, L * 32, hipMemcpyDeviceToHost, c->stream));
+  for (size_t i = 0; i < k; i++) VPIN_HIP_TRY(hipMemcpyAsync(outs[i], (uint8_t*)dout.p + i * per, per, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }
 
+// out_compressed[i] = commitment of row i: R scalars at z + i * stride over generators [0, R), plus blinds[i] (host, optional)
+// on generator blind_base.  buckets: by msm_pip.hip with windows of c_bits (0: its default) instead of the table walk.
+// The entry points below have checked the arguments.
+static int commit_rows(vpin_ctx* c, const vpin_gens* g, const fq* z, size_t rows, size_t stride, size_t R, const uint8_t* blinds,
+                       size_t blind_base, bool buckets, int c_bits, uint8_t* out_compressed) {
+  (void)hipSetDevice(c->device);
+  const int n_extra = blinds ? 1 : 0;
+  DevBuf dbl(c), dpts(c);
+  if ((blinds && dbl.alloc(rows * 32)) || dpts.alloc(rows * sizeof(ge_ext))) return VPIN_ENOMEM;
+  if (blinds) VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds, rows * 32, hipMemcpyHostToDevice, c->stream));
+  const int rc = buckets ? msm_rows_pip(c, g, z, rows, stride, R, (const fq*)dbl.p, n_extra, blind_base, c_bits, (ge_ext*)dpts.p)
+                         : msm_rows(c, g, z, rows, stride, R, (const fq*)dbl.p, n_extra, blind_base, (ge_ext*)dpts.p);
+  if (rc) return rc;
+  return compress_to_host(c, (const ge_ext*)dpts.p, rows, out_compressed);
+}
+
+int vpin_hyrax_commit(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, const uint8_t* blinds, size_t L,
+                      size_t blind_base, uint8_t* out_compressed) {
+  if (!c || !g || !Z || !Z->d || !blinds || !out_compressed || L == 0) return VPIN_EINVAL;
+  if (Z->len % L != 0) return VPIN_ESHAPE;  // assert_eq!(L_size * R_size, self.Z.len())
+  const size_t R = Z->len / L;
+  if (R > g->nb || blind_base >= g->nb) return VPIN_ESHAPE;  // assert_eq!(gens_n.n, self.len())
+  return commit_rows(c, g, Z->d, L, R, R, blinds, blind_base, false, 0, out_compressed);
+}
 
 // the same commitment by Pippenger's bucket method from the generators alone (msm_pip.hip): same bytes, no table walked
 int vpin_hyrax_commit_pippenger(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, const uint8_t* blinds, size_t L,
@@ -1434,24 +1380,59 @@ int vpin_hyrax_commit_pippenger(vpin_ctx* c, const vpin_gens* g, const vpin_tabl
   if (Z->len % L != 0) return VPIN_ESHAPE;
   const size_t R = Z->len / L;
   if (R > g->nb || (blinds && blind_base >= g->nb)) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  const int n_extra = blinds ? 1 : 0;
-  DevBuf dbl(c), dpts(c), dout(c);
-  if (dbl.alloc(L * 32) || dpts.alloc(L * sizeof(ge_ext)) || dout.alloc(L * 32)) return VPIN_ENOMEM;
-  if (blinds) VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds, L * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = msm_rows_pip(c, g, Z->d, L, R, R, (const fq*)dbl.p, n_extra, blind_base, c_bits, (ge_ext*)dpts.p);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dpts.p, L,
-                     (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_compressed, dout.p, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return commit_rows(c, g, Z->d, L, R, R, blinds, blind_base, true, c_bits, out_compressed);
+}
+
+int vpin_hyrax_commit_rows(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, size_t L, size_t row0, size_t nrows,
+                           const uint8_t* blinds, size_t blind_base, uint8_t* out_compressed) {
+  if (!c || !g || !Z || !Z->d || !out_compressed || L == 0 || nrows == 0) return VPIN_EINVAL;
+  if (Z->len % L != 0 || row0 + nrows > L) return VPIN_ESHAPE;
+  const size_t R = Z->len / L;
+  if (R > g->nb || (blinds && blind_base >= g->nb)) return VPIN_ESHAPE;
+  return commit_rows(c, g, Z->d + row0 * R, nrows, R, R, blinds, blind_base, false, 0, out_compressed);
 }
 
 }  // extern "C"
 
 namespace vpin {
+
+// The shape of msm_strip_kernel's launch for `eligible` regular rows of R scalars on `slots` workgroup slots: `groups` x
+// `strips` workgroups that take the first `rows_used` eligible rows (0: none; the rows beyond the shape go back to the row
+// kernel).  Host arithmetic only.
+// Every CU must run the SAME number of strip workgroups, or the workgroups of a strip drift apart (a CU with two of them
+// runs each 1.5x faster than a CU with three) and a table block is long evicted from L2 when the slow ones want it: the
+// PMC pass of the first version (608 workgroups on 768 slots) showed 95 B of L2 misses per addition, more than the row
+// kernel's 34 B.
+// Choose the strips: every eligible row (G = ceil(n / 256) groups), S the largest multiple of 8 (a strip stays on one
+// XCD) with G x S workgroups all RESIDENT (3 per CU) -- they wait for each other (msm_strip_kernel's sync) -- and strips of
+// at least 128 generators.  Measured on the 2^25 instance (7844 eligible rows; profiles/r04_ab_strip.txt): free-running
+// workgroups 85.8 ms and 139 M FETCH_SIZE units per dispatch, one generator of slack 81.6 ms and 91 M, two 82.6 / 103, four
+// 85.0 / 111.
+struct StripShape { size_t groups; int strips; uint32_t rows_used; };
+static StripShape strip_shape(size_t R, uint32_t eligible, size_t slots, bool cu_masked, size_t min_list) {
+  const size_t G = ((size_t)eligible + kMsmBlock - 1) / kMsmBlock;
+  size_t bestG = 0;
+  int bestS = 0;
+  for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8)
+    if (G * (size_t)cand <= slots) { bestG = G; bestS = cand; }
+  // On a context confined to some of the CUs (vpin_ctx_create_cumask) "every eligible row" can leave the CUs unevenly
+  // loaded (31 groups x 16 strips on 576 slots): take fewer groups and more strips when that fills more slots.
+  // VPIN_MSM_STRIP_SHAPE=G,S forces a shape (A/B runs).
+  if (cu_masked)
+    for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8) {
+      const size_t g2 = std::min(G, slots / (size_t)cand);
+      if (g2 * kMsmBlock >= min_list && g2 * (size_t)cand > bestG * (size_t)bestS) { bestG = g2; bestS = cand; }
+    }
+  if (const char* eshape = getenv("VPIN_MSM_STRIP_SHAPE")) {
+    int eg = 0, esn = 0;
+    if (sscanf(eshape, "%d,%d", &eg, &esn) == 2 && eg > 0 && esn > 0 && esn % 8 == 0 && (size_t)esn <= R / 8) {
+      // the strip's workgroups wait for each other: a forced shape must be resident as a whole like the chosen ones
+      if (std::min(G, (size_t)eg) * (size_t)esn <= slots) { bestG = std::min(G, (size_t)eg); bestS = esn; }
+      else if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] VPIN_MSM_STRIP_SHAPE=%d,%d refused: %zu workgroups on %zu slots\n", eg, esn, std::min(G, (size_t)eg) * (size_t)esn, slots);
+    }
+  }
+  return StripShape{bestG, bestS, bestG ? (uint32_t)std::min<size_t>(eligible, bestG * kMsmBlock) : 0u};
+}
 
 // DensePolynomial::commit(gens, None) for the derefs polynomial (8N scalars as L rows of R; sparse_mlpoly.rs:525-531) with the
 // hot column of each matrix's col-derefs vector taken out (msm_rows_hot_kernel).  col_idx[m]: the N column indices of matrix
@@ -1470,8 +1451,8 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
   if (nrows == 0) return VPIN_OK;
   if (pip_mode()) return hyrax_commit_rows_strided(c, g, Z, L, row0, nrows, row_step, out_compressed, z_rows);  // plain rows, buckets
   (void)hipSetDevice(c->device);
-  DevBuf dpts(c), dout(c), dT(c);
-  if (dpts.alloc(nrows * sizeof(ge_ext)) || dout.alloc(nrows * 32)) return VPIN_ENOMEM;
+  DevBuf dpts(c), dT(c);
+  if (dpts.alloc(nrows * sizeof(ge_ext))) return VPIN_ENOMEM;
   HotRows hr{};
   hr.row0 = 3 * (N / R);
   hr.rows_per_vec = N / R;
@@ -1533,57 +1514,24 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
     VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
     if (n_strip < min_list) n_strip = 0;  // too few rows to share a block's fetch: the row kernel takes everything
     if (n_strip && env_strip < 0) {
-      // Every CU must run the SAME number of strip workgroups, or the workgroups of a strip drift apart (a CU with two of them
-      // runs each 1.5x faster than a CU with three) and a table block is long evicted from L2 when the slow ones want it: the
-      // PMC pass of the first version (608 workgroups on 768 slots) showed 95 B of L2 misses per addition, more than the row
-      // kernel's 34 B.  The eligible rows beyond the chosen shape go back to the row kernel.
-      // Choose the strips: every eligible row (G = ceil(n / 256) groups), S the largest multiple of 8 (a strip stays on one
-      // XCD) with G x S workgroups all RESIDENT (3 per CU) -- they wait for each other (msm_strip_kernel's sync) -- and strips of
-      // at least 128 generators.  Measured on the 2^25 instance (7844 eligible rows; profiles/r04_ab_strip.txt): free-running
-      // workgroups 85.8 ms and 139 M FETCH_SIZE units per dispatch, one generator of slack 81.6 ms and 91 M, two 82.6 / 103, four
-      // 85.0 / 111.
-      const uint32_t found = n_strip;
-      const size_t slots = (size_t)c->num_cus * (c->shared_device ? 1 : 3), G = ((size_t)n_strip + kMsmBlock - 1) / kMsmBlock;
-      size_t bestG = 0;
-      int bestS = 0;
-      for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8)
-        if (G * (size_t)cand <= slots) { bestG = G; bestS = cand; }
-      // On a context confined to some of the CUs (vpin_ctx_create_cumask) "every eligible row" can leave the CUs unevenly
-      // loaded (31 groups x 16 strips on 576 slots): take fewer groups and more strips when that fills more slots; the rows
-      // beyond the shape go back to the row kernel.  VPIN_MSM_STRIP_SHAPE=G,S forces a shape (A/B runs).
-      if (c->cu_masked)
-        for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8) {
-          const size_t g2 = std::min(G, slots / (size_t)cand);
-          if (g2 * kMsmBlock >= min_list && g2 * (size_t)cand > bestG * (size_t)bestS) { bestG = g2; bestS = cand; }
-        }
-      if (const char* eshape = getenv("VPIN_MSM_STRIP_SHAPE")) {
-        int eg = 0, esn = 0;
-        if (sscanf(eshape, "%d,%d", &eg, &esn) == 2 && eg > 0 && esn > 0 && esn % 8 == 0 && (size_t)esn <= R / 8) {
-          // the strip's workgroups wait for each other: a forced shape must be resident as a whole like the chosen ones
-          if (std::min(G, (size_t)eg) * (size_t)esn <= slots) { bestG = std::min(G, (size_t)eg); bestS = esn; }
-          else if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] VPIN_MSM_STRIP_SHAPE=%d,%d refused: %zu workgroups on %zu slots\n", eg, esn, std::min(G, (size_t)eg) * (size_t)esn, slots);
-        }
-      }
-      const uint32_t n_use = bestG ? (uint32_t)std::min<size_t>(n_strip, bestG * kMsmBlock) : 0;
-      if (n_use == 0) {
-        n_strip = 0;
-      } else {
-        if (n_use < n_strip)
-          hipLaunchKernelGGL(strip_trim_kernel, dim3((n_strip - n_use + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)d_list, d_count,
-                             n_use, n_strip, (uint8_t*)dflag.p);
-        n_strip = n_use;
-        S = bestS;
+      const size_t slots = (size_t)c->num_cus * (c->shared_device ? 1 : 3);
+      const StripShape shape = strip_shape(R, n_strip, slots, c->cu_masked, min_list);
+      if (shape.rows_used && shape.rows_used < n_strip)
+        hipLaunchKernelGGL(strip_trim_kernel, dim3((n_strip - shape.rows_used + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)d_list,
+                           d_count, shape.rows_used, n_strip, (uint8_t*)dflag.p);
+      if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] %zu rows: %u eligible, %u taken as %zu groups x %d strips on %zu slots\n", nrows, n_strip, shape.rows_used, shape.groups, shape.strips, slots);
+      n_strip = shape.rows_used;
+      if (n_strip) {
+        S = shape.strips;
         uniform_shape = true;
       }
-      if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] %zu rows: %u eligible, %u taken as %zu groups x %d strips on %zu slots\n", nrows, found, n_use, bestG, bestS, slots);
     }
     if (n_strip && dsparts.alloc((size_t)n_strip * (size_t)S * sizeof(ge_ext))) return VPIN_ENOMEM;
   }
   const uint8_t* d_flag = n_strip ? (const uint8_t*)dflag.p : nullptr;
   {
     ProfScope ps(c, VPIN_K_MSM, 32.0 * (double)(nrows * R), VPIN_K_MSM_ROWS);
-    static const int env_pad = [] { const char* e = getenv("VPIN_MSM_LDS_PAD"); return e ? atoi(e) : -1; }();
-    const unsigned pad = env_pad >= 0 ? (unsigned)env_pad : (c->shared_device ? kSharedPad : 0u);
+    const unsigned pad = msm_lds_pad(c);
     if (n_strip) {
       c->strip_rows_taken += n_strip;
       const unsigned groups = (unsigned)((n_strip + kMsmBlock - 1) / kMsmBlock);
@@ -1609,12 +1557,7 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
       hipLaunchKernelGGL(strip_combine_kernel, dim3((n_strip + 63) / 64), dim3(64), 0, c->stream, (const ge_ext*)dsparts.p,
                          (const uint32_t*)dlist.p, (const uint32_t*)dlist.p + nrows, S, (ge_ext*)dpts.p);
   }
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dpts.p, nrows,
-                     (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_compressed, dout.p, nrows * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return compress_to_host(c, (const ge_ext*)dpts.p, nrows, out_compressed);
 }
 
 int hyrax_commit_rows_strided(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, size_t L, size_t row0, size_t nrows, size_t row_step,
@@ -1624,43 +1567,13 @@ int hyrax_commit_rows_strided(vpin_ctx* c, const vpin_gens* g, const vpin_table*
   if (Z->len % L != 0 || row0 + (nrows - 1) * row_step >= L) return VPIN_ESHAPE;
   const size_t R = Z->len / L;
   if (R > g->nb) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  DevBuf dpts(c), dout(c);
-  if (dpts.alloc(nrows * sizeof(ge_ext)) || dout.alloc(nrows * 32)) return VPIN_ENOMEM;
-  int rc = z_rows ? msm_rows(c, g, z_rows, nrows, R, R, nullptr, 0, 0, (ge_ext*)dpts.p)
-                  : msm_rows(c, g, Z->d + row0 * R, nrows, row_step * R, R, nullptr, 0, 0, (ge_ext*)dpts.p);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dpts.p, nrows,
-                     (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_compressed, dout.p, nrows * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  if (z_rows) return commit_rows(c, g, z_rows, nrows, R, R, nullptr, 0, false, 0, out_compressed);
+  return commit_rows(c, g, Z->d + row0 * R, nrows, row_step * R, R, nullptr, 0, false, 0, out_compressed);
 }
 
 }  // namespace vpin
 
 extern "C" {
-
-int vpin_hyrax_commit_rows(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, size_t L, size_t row0, size_t nrows,
-                           const uint8_t* blinds, size_t blind_base, uint8_t* out_compressed) {
-  if (!c || !g || !Z || !Z->d || !out_compressed || L == 0 || nrows == 0) return VPIN_EINVAL;
-  if (Z->len % L != 0 || row0 + nrows > L) return VPIN_ESHAPE;
-  const size_t R = Z->len / L;
-  if (R > g->nb || (blinds && blind_base >= g->nb)) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  DevBuf dbl(c), dpts(c), dout(c);
-  if ((blinds && dbl.alloc(nrows * 32)) || dpts.alloc(nrows * sizeof(ge_ext)) || dout.alloc(nrows * 32)) return VPIN_ENOMEM;
-  if (blinds) VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds, nrows * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = msm_rows(c, g, Z->d + row0 * R, nrows, R, R, blinds ? (const fq*)dbl.p : nullptr, blinds ? 1 : 0, blind_base, (ge_ext*)dpts.p);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dpts.p, nrows,
-                     (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_compressed, dout.p, nrows * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
-}
 
 int vpin_hyrax_commit_pair(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za, const vpin_table* Zb,
                            const uint8_t* blinds_a, const uint8_t* blinds_b, size_t L, size_t blind_base,
@@ -1670,8 +1583,8 @@ int vpin_hyrax_commit_pair(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za
   size_t R = Za->len / L;
   if (R > g->nb || blind_base >= g->nb) return VPIN_ESHAPE;
   (void)hipSetDevice(c->device);
-  DevBuf dbl(c), dpts(c), dout(c);
-  if (dbl.alloc(2 * L * 32) || dpts.alloc(3 * L * sizeof(ge_ext)) || dout.alloc(3 * L * 32)) return VPIN_ENOMEM;
+  DevBuf dbl(c), dpts(c);
+  if (dbl.alloc(2 * L * 32) || dpts.alloc(3 * L * sizeof(ge_ext))) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds_a, L * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync((uint8_t*)dbl.p + L * 32, blinds_b, L * 32, hipMemcpyHostToDevice, c->stream));
   ge_ext* pts = (ge_ext*)dpts.p;
@@ -1680,14 +1593,7 @@ int vpin_hyrax_commit_pair(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za
   rc = msm_rows(c, g, Zb->d, L, R, R, (const fq*)dbl.p + L, 1, blind_base, pts + L);
   if (rc) return rc;
   hipLaunchKernelGGL(ge_add_rows_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, c->stream, pts, pts + L, L, pts + 2 * L);
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((3 * L + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)pts, 3 * L,
-                     (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_a, dout.p, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_b, (uint8_t*)dout.p + L * 32, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_sum, (uint8_t*)dout.p + 2 * L * 32, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return compress_to_host(c, pts, 3 * L, out_a, out_b, out_sum);
 }
 
 // partial points of few-row MSMs: parts_xyzt must hold rows * vpin_gens_msm_parts_count(ncols) * 128 bytes
@@ -1750,8 +1656,8 @@ int commit_pair_finish(vpin_ctx* c, const vpin_gens* g, CommitPairState* st, con
   if (!c || !g || !blinds_a || !blinds_b || !out_a || !out_b || !out_sum) return VPIN_EINVAL;
   if (blind_base >= g->nb) return VPIN_ESHAPE;
   const size_t L = st->L;
-  DevBuf dbl(c), dout(c);
-  if (dbl.alloc(2 * L * 32) || dout.alloc(3 * L * 32)) return VPIN_ENOMEM;
+  DevBuf dbl(c);
+  if (dbl.alloc(2 * L * 32)) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds_a, L * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync((uint8_t*)dbl.p + L * 32, blinds_b, L * 32, hipMemcpyHostToDevice, c->stream));
   ge_ext* pts = (ge_ext*)st->pts.p;
@@ -1762,14 +1668,7 @@ int commit_pair_finish(vpin_ctx* c, const vpin_gens* g, CommitPairState* st, con
   hipLaunchKernelGGL(ge_add_rows_kernel, dim3(gb), dim3(64), 0, c->stream, pts, pts + 2 * L, 2 * L, pts + 2 * L);  // a, b
   hipLaunchKernelGGL(ge_add_rows_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, c->stream, pts + 2 * L, pts + 3 * L, L,
                      pts + 4 * L);  // a + b
-  hipLaunchKernelGGL(ge_compress_kernel, dim3((unsigned)((3 * L + 63) / 64)), dim3(64), 0, c->stream,
-                     (const ge_ext*)(pts + 2 * L), 3 * L, (fp*)dout.p, (fp*)nullptr);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(out_a, dout.p, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_b, (uint8_t*)dout.p + L * 32, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_sum, (uint8_t*)dout.p + 2 * L * 32, L * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return compress_to_host(c, pts + 2 * L, 3 * L, out_a, out_b, out_sum);
 }
 }  // namespace vpin
 
@@ -1869,26 +1768,9 @@ int gens_msm_parts_dev(vpin_ctx* c, const vpin_gens* g, const fq* d_scalars, siz
   if (!c || !g || !d_scalars || !parts_xyzt || rows == 0 || ncols == 0) return VPIN_EINVAL;
   if (ncols > g->nb) return VPIN_ESHAPE;
   (void)hipSetDevice(c->device);
-  const size_t nraw = raw_parts(ncols), nparts = vpin_gens_msm_parts_count(ncols);
-  DevBuf dp(c), dr(c);
-  if (dp.alloc(rows * nraw * 128) || (nraw > nparts && dr.alloc(rows * nparts * 128))) return VPIN_ENOMEM;
-  {
-    ProfScope ps(c, VPIN_K_MSM, 32.0 * (double)rows * (double)ncols);
-    if (wide_q(ncols) == 4)
-      hipLaunchKernelGGL((msm_wide_kernel<4>), dim3((unsigned)nraw, (unsigned)rows), dim3(kMsmBlock), 0, c->stream, d_scalars, ncols,
-                         view(g), (fp*)dp.p);
-    else
-      hipLaunchKernelGGL((msm_wide_kernel<1>), dim3((unsigned)nraw, (unsigned)rows), dim3(kMsmBlock), 0, c->stream, d_scalars, ncols,
-                         view(g), (fp*)dp.p);
-  }
-  const void* src = dp.p;
-  if (nraw > nparts) {
-    hipLaunchKernelGGL(parts_reduce_kernel, dim3((unsigned)((rows * nparts + 63) / 64)), dim3(64), 0, c->stream, (const fp*)dp.p, rows,
-                       nraw, (int)nparts, (fp*)dr.p);
-    src = dr.p;
-  }
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(parts_xyzt, src, rows * nparts * 128, hipMemcpyDeviceToHost, c->stream));
+  DevBuf scratch(c);
+  if (scratch.alloc(gens_msm_parts_scratch_bytes(rows, ncols))) return VPIN_ENOMEM;
+  if (const int rc = gens_msm_parts_launch(c, g, d_scalars, rows, ncols, scratch.p, parts_xyzt, false)) return rc;
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }

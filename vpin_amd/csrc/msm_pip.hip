@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kPipBlock) void pip_recode_kernel(const fq* __restr
                                                                const fq* __restrict__ extra, int n_extra, size_t rows,
                                                                uint16_t* __restrict__ dig, uint32_t* __restrict__ bad) {
   constexpr int W = PipShape<C>::W;
-  constexpr uint32_t B = PipShape<C>::B, mask = (1u << C) - 1u;
+  constexpr uint32_t B = PipShape<C>::B;
   const size_t n = ncols + (size_t)n_extra;
   const size_t idx = (size_t)blockIdx.x * kPipBlock + threadIdx.x;
   if (idx >= rows * n) return;
@@ -69,46 +69,16 @@ __global__ __launch_bounds__(kPipBlock) void pip_recode_kernel(const fq* __restr
   uint32_t carry = 0;
 #pragma unroll
   for (int w = 0; w < W; w++) {
-    uint32_t v = (s.v[0] & mask) + carry;
-#pragma unroll
-    for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], C);
-    s.v[7] >>= C;
-    bool neg = false;
-    if (w + 1 < W) {
-      neg = v > B;
-      if (neg) v = (mask + 1u) - v;
-      carry = neg ? 1u : 0u;
-    } else if (v > B) {
+    uint16_t d = fq_signed_window(s, carry, C, w + 1 == W);
+    if (w + 1 == W && d > B) {
       *bad = 1u;
-      v = 0;
+      d = 0;
     }
-    out[(size_t)w * n] = (uint16_t)(v | (neg && v ? 0x8000u : 0u));
+    out[(size_t)w * n] = d;
   }
 }
 
 // ---- buckets ------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ ge_niels gn_load(const ge_niels* __restrict__ p) {
-  ge_niels e;
-  e.ypx = fp_load(&p->ypx); e.ymx = fp_load(&p->ymx); e.xy2d = fp_load(&p->xy2d);
-  return e;
-}
-__device__ __forceinline__ void ge10_store_strided(uint32_t* __restrict__ p, const ge10& a) {  // limb l at p[256 l]
-#pragma unroll
-  for (int l = 0; l < 10; l++) {
-    p[(size_t)l * kPipBlock] = a.X.v[l]; p[(size_t)(10 + l) * kPipBlock] = a.Y.v[l];
-    p[(size_t)(20 + l) * kPipBlock] = a.Z.v[l]; p[(size_t)(30 + l) * kPipBlock] = a.T.v[l];
-  }
-}
-__device__ __forceinline__ ge10 ge10_load_strided(const uint32_t* __restrict__ p) {
-  ge10 a;
-#pragma unroll
-  for (int l = 0; l < 10; l++) {
-    a.X.v[l] = p[(size_t)l * kPipBlock]; a.Y.v[l] = p[(size_t)(10 + l) * kPipBlock];
-    a.Z.v[l] = p[(size_t)(20 + l) * kPipBlock]; a.T.v[l] = p[(size_t)(30 + l) * kPipBlock];
-  }
-  return a;
-}
 
 __device__ __forceinline__ ge10 ge10_load_dense(const uint32_t* __restrict__ p) {  // 40 consecutive words
   ge10 a;
@@ -172,7 +142,7 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
   auto fetch = [&](uint32_t e, bool& neg) {
     const uint32_t v = sorted[e];
     neg = (v >> 15) != 0;
-    return gn_load(gn + (v & 0x7fffu));
+    return ge_load(gn + (v & 0x7fffu));
   };
 
   for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -218,8 +188,7 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
     const uint32_t nh = hcount, total = total_light + hfill;
     if (total == 0) {  // an empty window (the upper windows of a row of bits): the identity, uniform for the workgroup
       if (t == 0) {
-        ge_ext* o = wsum + item;
-        fp_store(&o->X, fp_zero()); fp_store(&o->Y, fp_one()); fp_store(&o->Z, fp_one()); fp_store(&o->T, fp_zero());
+        ge_store_identity(wsum + item);
       }
       __syncthreads();
       continue;
@@ -284,7 +253,7 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
         if (K > 1) {
           while ((uint32_t)e < lo) {  // bucket b is complete: acc = B_{K-1} + .. + B_b (b >= 1 here: lo of bucket 0 is beg)
             if (const uint32_t s = cursor[t * K + b]) acc = ge10_add_ge10(acc, ge10_load_dense(hsum + (size_t)(s - 1) * kLimbs));
-            ge10_store_strided(my_scr + (size_t)(b - 1) * kLimbs * kPipBlock, acc);
+            ge10_store_strided(my_scr + (size_t)(b - 1) * kLimbs * kPipBlock, kPipBlock, acc);
             b--;
             lo = start[t * K + b];
           }
@@ -301,7 +270,7 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
 #pragma unroll 1
         for (; b >= 1; b--) {  // the buckets below hold no light entries
           if (const uint32_t s = cursor[t * K + b]) acc = ge10_add_ge10(acc, ge10_load_dense(hsum + (size_t)(s - 1) * kLimbs));
-          ge10_store_strided(my_scr + (size_t)(b - 1) * kLimbs * kPipBlock, acc);
+          ge10_store_strided(my_scr + (size_t)(b - 1) * kLimbs * kPipBlock, kPipBlock, acc);
         }
       }
       if (const uint32_t s = cursor[t * K]) acc = ge10_add_ge10(acc, ge10_load_dense(hsum + (size_t)(s - 1) * kLimbs));
@@ -309,23 +278,23 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
     ge10 weighted = acc;
     if (K > 1) {
 #pragma unroll 1
-      for (int i = 1; i < K; i++) weighted = ge10_add_ge10(weighted, ge10_load_strided(my_scr + (size_t)(i - 1) * kLimbs * kPipBlock));
+      for (int i = 1; i < K; i++) weighted = ge10_add_ge10(weighted, ge10_load_strided(my_scr + (size_t)(i - 1) * kLimbs * kPipBlock, kPipBlock));
     }
     __syncthreads();  // the list and the counters are dead: LDS becomes the reduction's
 
     // 3. across lanes: Suf_t = S_t + S_{t+1} + .. (Hillis-Steele over the ten-limb form, limb l of lane t at lds[256 l + t])
     ge10 suf = acc;
-    ge10_store_strided(lds + t, suf);
+    ge10_store_strided(lds + t, kPipBlock, suf);
     __syncthreads();
 #pragma unroll 1
     for (int dlt = 1; dlt < kPipBlock; dlt <<= 1) {
       const bool has = t + dlt < kPipBlock;
       ge10 other = suf;
-      if (has) other = ge10_load_strided(lds + t + dlt);
+      if (has) other = ge10_load_strided(lds + t + dlt, kPipBlock);
       __syncthreads();
       if (has) {
         suf = ge10_add_ge10(suf, other);
-        ge10_store_strided(lds + t, suf);
+        ge10_store_strided(lds + t, kPipBlock, suf);
       }
       __syncthreads();
     }
@@ -340,8 +309,7 @@ __global__ __launch_bounds__(kPipBlock, 3) void pip_window_kernel(const uint16_t
     ge_tree_quad(sh, kPipBlock);
     if (t == 0) {
       const ge_ext r = sh[0];
-      ge_ext* o = wsum + item;
-      fp_store(&o->X, r.X); fp_store(&o->Y, r.Y); fp_store(&o->Z, r.Z); fp_store(&o->T, r.T);
+      ge_store(wsum + item, r);
     }
     __syncthreads();
   }
@@ -353,22 +321,8 @@ __global__ __launch_bounds__(64) void pip_finish_kernel(const ge_ext* __restrict
   constexpr int W = PipShape<C>::W;
   const size_t row = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (row >= rows) return;
-  auto load = [&](int w) {
-    const ge_ext* p = wsum + row * W + w;
-    ge_ext e;
-    e.X = fp_load(&p->X); e.Y = fp_load(&p->Y); e.Z = fp_load(&p->Z); e.T = fp_load(&p->T);
-    return ge10_from_ext(e);
-  };
-  ge10 acc = load(W - 1);
-#pragma unroll 1
-  for (int w = W - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int k = 0; k < C; k++) acc = ge10_double(acc);
-    acc = ge10_add_ge10(acc, load(w));
-  }
-  const ge_ext r = ge10_to_ext(acc);
-  ge_ext* o = out + row;
-  fp_store(&o->X, r.X); fp_store(&o->Y, r.Y); fp_store(&o->Z, r.Z); fp_store(&o->T, r.T);
+  const ge_ext r = ge10_to_ext(ge10_horner_windows(wsum + row * W, W, [](int) { return C; }));
+  ge_store(out + row, r);
 }
 
 template <int C>

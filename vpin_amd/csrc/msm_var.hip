@@ -21,9 +21,6 @@
 
 namespace vpin {
 
-// d = -121665/121666 (RFC 9496 section 4)
-__device__ __forceinline__ fp FP_D() { return fp_const(0x135978a3u, 0x75eb4dcau, 0x4141d8abu, 0x00700a4du, 0x7779e898u, 0x8cc74079u, 0x2b6ffe73u, 0x52036ceeu); }
-
 // CompressedRistretto::decompress (RFC 9496 4.3.1); false for a non-canonical, negative or off-group encoding
 __device__ __noinline__ bool ge_decompress(const fp& s_in, ge_ext& out) {
   const fp s = fp_freeze(s_in);
@@ -44,48 +41,6 @@ __device__ __noinline__ bool ge_decompress(const fp& s_in, ge_ext& out) {
 }
 
 constexpr int kVarBlock = 64;  // one wave per workgroup: 16384 points fill the chip
-
-// sh[0] = sum of sh[0..n) with four lanes per addition (the tree of msm.hip, for a 64-lane block)
-__device__ __forceinline__ fp fpv_shfl_from(const fp& a, int src) {
-  fp r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __shfl(a.v[i], src, 64);
-  return r;
-}
-__device__ __forceinline__ fp fpv_pick(bool c, const fp& a, const fp& b) {
-  fp r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = c ? a.v[i] : b.v[i];
-  return r;
-}
-__device__ __forceinline__ void ge_tree_quad64(ge_ext* sh, int n) {
-  const int role = threadIdx.x & 3, qbase = (threadIdx.x & 63) & ~3;
-  const fp* shf = reinterpret_cast<const fp*>(sh);
-  fp* shw = reinterpret_cast<fp*>(sh);
-  for (int s = n / 2; s >= 1; s >>= 1) {
-    for (int w = threadIdx.x >> 2; w < s; w += (int)(blockDim.x >> 2)) {
-      const int i = w;
-      const int f0 = role < 2 ? 1 : (role == 2 ? 3 : 2);
-      const fp p0 = shf[4 * i + f0], q0 = shf[4 * (i + s) + f0];
-      fp u = p0, v = q0;
-      if (role < 2) {
-        const fp p1 = shf[4 * i], q1 = shf[4 * (i + s)];
-        u = fpv_pick(role == 0, fp_sub(p0, p1), fp_add(p0, p1));
-        v = fpv_pick(role == 0, fp_sub(q0, q1), fp_add(q0, q1));
-      }
-      fp m = fp_mul(u, v);
-      m = fp_mul(m, fpv_pick(role == 2, FP_D2(), fp_one()));
-      m = fpv_pick(role == 3, fp_add(m, m), m);
-      const fp a = fpv_shfl_from(m, qbase), b = fpv_shfl_from(m, qbase + 1), c = fpv_shfl_from(m, qbase + 2),
-               d = fpv_shfl_from(m, qbase + 3);
-      const fp E = fp_sub(b, a), H = fp_add(b, a), F = fp_sub(d, c), G = fp_add(d, c);
-      u = fpv_pick(role == 0 || role == 3, E, fpv_pick(role == 1, G, F));
-      v = fpv_pick(role == 0, F, fpv_pick(role == 2, G, H));
-      shw[4 * i + role] = fp_mul(u, v);
-    }
-    __syncthreads();
-  }
-}
 
 // partial[b] = sum over the block's lanes of s_i * P_i; bad[0] != 0 when a point does not decode.
 // scalars: Montgomery form (mont != 0) or canonical integers.
@@ -115,11 +70,8 @@ __global__ __launch_bounds__(kVarBlock) void msm_var_kernel(const fq* __restrict
   __shared__ ge_ext sh[kVarBlock];
   sh[threadIdx.x] = ge10_to_ext(acc);
   __syncthreads();
-  ge_tree_quad64(sh, kVarBlock);
-  if (threadIdx.x == 0) {
-    ge_ext* o = partial + blockIdx.x;
-    fp_store(&o->X, sh[0].X); fp_store(&o->Y, sh[0].Y); fp_store(&o->Z, sh[0].Z); fp_store(&o->T, sh[0].T);
-  }
+  ge_tree_quad(sh, kVarBlock);
+  if (threadIdx.x == 0) ge_store(partial + blockIdx.x, sh[0]);
 }
 
 // out[i] = compress(decompress(a[i]) + decompress(b[i]))
@@ -138,19 +90,13 @@ __global__ __launch_bounds__(kVarBlock) void msm_var_finish_kernel(const ge_ext*
                                                                    fp* __restrict__ out_xyzt) {
   __shared__ ge_ext sh[kVarBlock];
   ge_ext acc = ge_identity();
-  for (size_t k = threadIdx.x; k < m; k += kVarBlock) {
-    ge_ext p;
-    p.X = fp_load(&partial[k].X); p.Y = fp_load(&partial[k].Y); p.Z = fp_load(&partial[k].Z); p.T = fp_load(&partial[k].T);
-    acc = ge_add(acc, p);
-  }
+  for (size_t k = threadIdx.x; k < m; k += kVarBlock) acc = ge_add(acc, ge_load(partial + k));
   sh[threadIdx.x] = acc;
   __syncthreads();
-  ge_tree_quad64(sh, kVarBlock);
+  ge_tree_quad(sh, kVarBlock);
   if (threadIdx.x == 0) {
     const ge_ext r = sh[0];
-    fp_store(out32, ge_compress(r));
-    fp_store(out_xyzt, fp_freeze(r.X)); fp_store(out_xyzt + 1, fp_freeze(r.Y)); fp_store(out_xyzt + 2, fp_freeze(r.Z));
-    fp_store(out_xyzt + 3, fp_freeze(r.T));
+    ge_store_result(out32, out_xyzt, r);
   }
 }
 
@@ -203,23 +149,14 @@ __global__ __launch_bounds__(kVarBlock) void bkt_prep_kernel(const fq* __restric
     atomicOr(bad, 1u);
     P = ge_identity();
   }
-  fp_store(&gn[i].ypx, fp_add(P.Y, P.X));
-  fp_store(&gn[i].ymx, fp_sub(P.Y, P.X));
-  fp_store(&gn[i].xy2d, fp_mul(P.T, FP_D2()));
+  ge_store(gn + i, ge_niels{fp_add(P.Y, P.X), fp_sub(P.Y, P.X), fp_mul(P.T, FP_D2())});
   fq s = fq_from_mont(fq_load(scalars + i));  // canonical: below 2^253
   uint32_t carry = 0;
 #pragma unroll 1
   for (int w = 0; w < W; w++) {
-    const uint32_t cw = (uint32_t)(w < wide ? c : c - 1), mask = (1u << cw) - 1u, half = 1u << (cw - 1);
-    uint32_t v = (s.v[0] & mask) + carry;
-#pragma unroll
-    for (int k = 0; k < 7; k++) s.v[k] = __builtin_amdgcn_alignbit(s.v[k + 1], s.v[k], cw);
-    s.v[7] >>= cw;
     // the top window holds c - 1 bits and a carry: at most 2^(c-1) = the number of buckets, never negated
-    const bool neg = w + 1 < W && v > half;
-    if (neg) v = (mask + 1u) - v;
-    carry = neg ? 1u : 0u;
-    dig[(size_t)w * n + i] = ok ? (uint16_t)(v | (neg && v ? 0x8000u : 0u)) : (uint16_t)0;
+    const uint16_t d = fq_signed_window(s, carry, (uint32_t)(w < wide ? c : c - 1), w + 1 == W);
+    dig[(size_t)w * n + i] = ok ? d : (uint16_t)0;
   }
 }
 
@@ -269,24 +206,7 @@ __global__ __launch_bounds__(kBktSortBlock) void bkt_sort_kernel(const uint16_t*
   }
 }
 
-// limb l of bucket (w, b) at bkt[(w 40 + l) B + b]
-__device__ __forceinline__ void bkt_store(uint32_t* __restrict__ p, size_t B, const ge10& a) {
-#pragma unroll
-  for (int l = 0; l < 10; l++) {
-    p[(size_t)l * B] = a.X.v[l]; p[(size_t)(10 + l) * B] = a.Y.v[l];
-    p[(size_t)(20 + l) * B] = a.Z.v[l]; p[(size_t)(30 + l) * B] = a.T.v[l];
-  }
-}
-__device__ __forceinline__ ge10 bkt_load(const uint32_t* __restrict__ p, size_t B) {
-  ge10 a;
-#pragma unroll
-  for (int l = 0; l < 10; l++) {
-    a.X.v[l] = p[(size_t)l * B]; a.Y.v[l] = p[(size_t)(10 + l) * B];
-    a.Z.v[l] = p[(size_t)(20 + l) * B]; a.T.v[l] = p[(size_t)(30 + l) * B];
-  }
-  return a;
-}
-
+// limb l of bucket (w, b) at bkt[(w 40 + l) B + b]: limb-strided with stride B
 __global__ __launch_bounds__(kVarBlock) void bkt_accum_kernel(const ge_niels* __restrict__ gn, const uint32_t* __restrict__ start,
                                                               const uint32_t* __restrict__ sorted, size_t n, uint32_t B, int W,
                                                               uint32_t* __restrict__ bkt) {
@@ -299,12 +219,9 @@ __global__ __launch_bounds__(kVarBlock) void bkt_accum_kernel(const ge_niels* __
 #pragma unroll 1
   for (uint32_t e = lo; e < hi; e++) {
     const uint32_t v = list[e];
-    const ge_niels* q = gn + (v & 0x7fffffffu);
-    ge_niels g;
-    g.ypx = fp_load(&q->ypx); g.ymx = fp_load(&q->ymx); g.xy2d = fp_load(&q->xy2d);
-    acc = ge10_add_niels(acc, g, (v >> 31) != 0);
+    acc = ge10_add_niels(acc, ge_load(gn + (v & 0x7fffffffu)), (v >> 31) != 0);
   }
-  bkt_store(bkt + (w * kBktLimbs) * B + b, B, acc);
+  ge10_store_strided(bkt + (w * kBktLimbs) * B + b, B, acc);
 }
 
 // wsum[w] = sum_b (b + 1) bucket(w, b)
@@ -318,7 +235,7 @@ __global__ __launch_bounds__(kBktBlock) void bkt_reduce_kernel(const uint32_t* _
     ge10 acc = ge10_identity();
 #pragma unroll 1
     for (int i = (int)K - 1; i >= 0; i--) {
-      acc = ge10_add_ge10(acc, bkt_load(base + t * K + (uint32_t)i, B));
+      acc = ge10_add_ge10(acc, ge10_load_strided(base + t * K + (uint32_t)i, B));
       wt = ge10_add_ge10(wt, acc);
     }
     const uint32_t m = t * K;  // the lane's buckets weigh m + 1 .. m + K: m times their plain sum on top of the running sums
@@ -335,37 +252,47 @@ __global__ __launch_bounds__(kBktBlock) void bkt_reduce_kernel(const uint32_t* _
   sh[t] = ge10_to_ext(wt);
   __syncthreads();
   ge_tree_quad(sh, kBktBlock);
-  if (t == 0) {
-    ge_ext* o = wsum + w;
-    fp_store(&o->X, sh[0].X); fp_store(&o->Y, sh[0].Y); fp_store(&o->Z, sh[0].Z); fp_store(&o->T, sh[0].T);
-  }
+  if (t == 0) ge_store(wsum + w, sh[0]);
 }
 
 // one wave: sum_w 2^(c w) wsum[w] -> compressed and canonical X|Y|Z|T
 __global__ __launch_bounds__(kVarBlock) void bkt_finish_kernel(const ge_ext* __restrict__ wsum, int W, int c, int wide, fp* __restrict__ out32,
                                                                fp* __restrict__ out_xyzt) {
   if (threadIdx.x != 0) return;
-  auto load = [&](int w) {
-    ge_ext e;
-    e.X = fp_load(&wsum[w].X); e.Y = fp_load(&wsum[w].Y); e.Z = fp_load(&wsum[w].Z); e.T = fp_load(&wsum[w].T);
-    return ge10_from_ext(e);
-  };
-  ge10 acc = load(W - 1);
-#pragma unroll 1
-  for (int w = W - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int k = 0, cw = w < wide ? c : c - 1; k < cw; k++) acc = ge10_double(acc);  // window w is cw bits wide
-    acc = ge10_add_ge10(acc, load(w));
-  }
-  const ge_ext r = ge10_to_ext(acc);
-  fp_store(out32, ge_compress(r));
-  fp_store(out_xyzt, fp_freeze(r.X)); fp_store(out_xyzt + 1, fp_freeze(r.Y)); fp_store(out_xyzt + 2, fp_freeze(r.Z));
-  fp_store(out_xyzt + 3, fp_freeze(r.T));
+  const ge_ext r = ge10_to_ext(ge10_horner_windows(wsum, W, [=](int w) { return w < wide ? c : c - 1; }));  // window w: c or c - 1 bits
+  ge_store_result(out32, out_xyzt, r);
 }
 
 }  // namespace vpin
 
 using namespace vpin;
+
+// What vpin_msm and vpin_msm_bucket share: the argument checks, the scalars and points to the device, the `bad` flag of a
+// point that does not decode, and the result (compressed | X|Y|Z|T) home.  launch(scalars, points, out32, out_xyzt, bad)
+// enqueues the kernels between; n_limit: the first n the method cannot take.
+template <class Launch>
+static int msm_var_run(vpin_ctx* c, const uint8_t* scalars_mont, const uint8_t* points_compressed, size_t n, size_t n_limit,
+                       uint8_t* out_compressed, uint8_t* out_xyzt, Launch launch) {
+  if (!c || !scalars_mont || !points_compressed || n == 0 || (!out_compressed && !out_xyzt)) return VPIN_EINVAL;
+  if (n >= n_limit) return VPIN_ESHAPE;
+  (void)hipSetDevice(c->device);
+  DevBuf ds(c), dp(c), dout(c), dbad(c);
+  if (ds.alloc(n * 32) || dp.alloc(n * 32) || dout.alloc(32 + 128) || dbad.alloc(4)) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(ds.p, scalars_mont, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(dp.p, points_compressed, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, c->stream));
+  if (const int rc = launch((const fq*)ds.p, (const fp*)dp.p, (fp*)dout.p, (fp*)((uint8_t*)dout.p + 32), (uint32_t*)dbad.p)) return rc;
+  VPIN_HIP_TRY(hipGetLastError());
+  uint8_t host[160];
+  uint32_t bad = 0;
+  VPIN_HIP_TRY(hipMemcpyAsync(host, dout.p, 160, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (bad) return VPIN_EVERIFY;
+  if (out_compressed) memcpy(out_compressed, host, 32);
+  if (out_xyzt) memcpy(out_xyzt, host + 32, 128);
+  return VPIN_OK;
+}
 
 extern "C" {
 
@@ -374,71 +301,41 @@ extern "C" {
 // unwraps CompressedGroup::decompress and panics).
 int vpin_msm(vpin_ctx* c, const uint8_t* scalars_mont, const uint8_t* points_compressed, size_t n, uint8_t* out_compressed,
              uint8_t* out_xyzt) {
-  if (!c || !scalars_mont || !points_compressed || n == 0 || (!out_compressed && !out_xyzt)) return VPIN_EINVAL;
-  (void)hipSetDevice(c->device);
-  const size_t nb = (n + kVarBlock - 1) / kVarBlock;
-  DevBuf ds(c), dp(c), dpart(c), dout(c), dbad(c);
-  if (ds.alloc(n * 32) || dp.alloc(n * 32) || dpart.alloc(nb * sizeof(ge_ext)) || dout.alloc(32 + 128) || dbad.alloc(4)) return VPIN_ENOMEM;
-  VPIN_HIP_TRY(hipMemcpyAsync(ds.p, scalars_mont, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(dp.p, points_compressed, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, c->stream));
-  {
+  return msm_var_run(c, scalars_mont, points_compressed, n, (size_t)-1, out_compressed, out_xyzt,
+                     [&](const fq* ds, const fp* dp, fp* out32, fp* out128, uint32_t* dbad) -> int {
+    const size_t nb = (n + kVarBlock - 1) / kVarBlock;
+    DevBuf dpart(c);
+    if (dpart.alloc(nb * sizeof(ge_ext))) return VPIN_ENOMEM;
     ProfScope ps(c, VPIN_K_MSM, 64.0 * (double)n);
-    hipLaunchKernelGGL(msm_var_kernel, dim3((unsigned)nb), dim3(kVarBlock), 0, c->stream, (const fq*)ds.p, (const fp*)dp.p, n, 1,
-                       (ge_ext*)dpart.p, (uint32_t*)dbad.p);
-    hipLaunchKernelGGL(msm_var_finish_kernel, dim3(1), dim3(kVarBlock), 0, c->stream, (const ge_ext*)dpart.p, nb, (fp*)dout.p,
-                       (fp*)((uint8_t*)dout.p + 32));
-  }
-  VPIN_HIP_TRY(hipGetLastError());
-  uint8_t host[160];
-  uint32_t bad = 0;
-  VPIN_HIP_TRY(hipMemcpyAsync(host, dout.p, 160, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (bad) return VPIN_EVERIFY;
-  if (out_compressed) memcpy(out_compressed, host, 32);
-  if (out_xyzt) memcpy(out_xyzt, host + 32, 128);
-  return VPIN_OK;
+    hipLaunchKernelGGL(msm_var_kernel, dim3((unsigned)nb), dim3(kVarBlock), 0, c->stream, ds, dp, n, 1, (ge_ext*)dpart.p, dbad);
+    hipLaunchKernelGGL(msm_var_finish_kernel, dim3(1), dim3(kVarBlock), 0, c->stream, (const ge_ext*)dpart.p, nb, out32, out128);
+    return VPIN_OK;
+  });
 }
 
-
-// vpin_msm by the bucket method (see the kernels above): the same contract; the batch verifier's kernel from 2^17 terms on
+// vpin_msm by the bucket method (see the kernels above): the same contract; the batch verifier's kernel from 2^17 terms on.
+// n < 2^31: a list entry is a 31-bit index and a sign
 int vpin_msm_bucket(vpin_ctx* c, const uint8_t* scalars_mont, const uint8_t* points_compressed, size_t n, uint8_t* out_compressed,
                     uint8_t* out_xyzt) {
-  if (!c || !scalars_mont || !points_compressed || n == 0 || (!out_compressed && !out_xyzt)) return VPIN_EINVAL;
-  if (n >= ((size_t)1 << 31)) return VPIN_ESHAPE;  // a list entry is a 31-bit index and a sign
-  (void)hipSetDevice(c->device);
-  const BktShape sh = bkt_shape(n);
-  const size_t W = (size_t)sh.W, B = sh.B;
-  DevBuf ds(c), dp(c), dgn(c), ddig(c), dstart(c), dsorted(c), dbkt(c), dws(c), dout(c), dbad(c);
-  if (ds.alloc(n * 32) || dp.alloc(n * 32) || dgn.alloc(n * sizeof(ge_niels)) || ddig.alloc(W * n * 2) || dstart.alloc(W * (B + 1) * 4) ||
-      dsorted.alloc(W * n * 4) || dbkt.alloc(W * B * kBktLimbs * 4) || dws.alloc(W * sizeof(ge_ext)) || dout.alloc(32 + 128) || dbad.alloc(4))
-    return VPIN_ENOMEM;
-  VPIN_HIP_TRY(hipMemcpyAsync(ds.p, scalars_mont, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(dp.p, points_compressed, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, c->stream));
-  {
+  return msm_var_run(c, scalars_mont, points_compressed, n, (size_t)1 << 31, out_compressed, out_xyzt,
+                     [&](const fq* ds, const fp* dp, fp* out32, fp* out128, uint32_t* dbad) -> int {
+    const BktShape sh = bkt_shape(n);
+    const size_t W = (size_t)sh.W, B = sh.B;
+    DevBuf dgn(c), ddig(c), dstart(c), dsorted(c), dbkt(c), dws(c);
+    if (dgn.alloc(n * sizeof(ge_niels)) || ddig.alloc(W * n * 2) || dstart.alloc(W * (B + 1) * 4) || dsorted.alloc(W * n * 4) ||
+        dbkt.alloc(W * B * kBktLimbs * 4) || dws.alloc(W * sizeof(ge_ext)))
+      return VPIN_ENOMEM;
     ProfScope ps(c, VPIN_K_MSM, 64.0 * (double)n);
-    hipLaunchKernelGGL(bkt_prep_kernel, dim3((unsigned)((n + kVarBlock - 1) / kVarBlock)), dim3(kVarBlock), 0, c->stream, (const fq*)ds.p,
-                       (const fp*)dp.p, n, sh.c, sh.W, sh.wide, (ge_niels*)dgn.p, (uint16_t*)ddig.p, (uint32_t*)dbad.p);
+    hipLaunchKernelGGL(bkt_prep_kernel, dim3((unsigned)((n + kVarBlock - 1) / kVarBlock)), dim3(kVarBlock), 0, c->stream, ds, dp, n, sh.c,
+                       sh.W, sh.wide, (ge_niels*)dgn.p, (uint16_t*)ddig.p, dbad);
     hipLaunchKernelGGL(bkt_sort_kernel, dim3((unsigned)W), dim3(kBktSortBlock), 0, c->stream, (const uint16_t*)ddig.p, n, sh.B,
                        (uint32_t*)dstart.p, (uint32_t*)dsorted.p);
     hipLaunchKernelGGL(bkt_accum_kernel, dim3((unsigned)((W * B + kVarBlock - 1) / kVarBlock)), dim3(kVarBlock), 0, c->stream,
                        (const ge_niels*)dgn.p, (const uint32_t*)dstart.p, (const uint32_t*)dsorted.p, n, sh.B, sh.W, (uint32_t*)dbkt.p);
     hipLaunchKernelGGL(bkt_reduce_kernel, dim3((unsigned)W), dim3(kBktBlock), 0, c->stream, (const uint32_t*)dbkt.p, sh.B, (ge_ext*)dws.p);
-    hipLaunchKernelGGL(bkt_finish_kernel, dim3(1), dim3(kVarBlock), 0, c->stream, (const ge_ext*)dws.p, sh.W, sh.c, sh.wide, (fp*)dout.p,
-                       (fp*)((uint8_t*)dout.p + 32));
-  }
-  VPIN_HIP_TRY(hipGetLastError());
-  uint8_t host[160];
-  uint32_t bad = 0;
-  VPIN_HIP_TRY(hipMemcpyAsync(host, dout.p, 160, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (bad) return VPIN_EVERIFY;
-  if (out_compressed) memcpy(out_compressed, host, 32);
-  if (out_xyzt) memcpy(out_xyzt, host + 32, 128);
-  return VPIN_OK;
+    hipLaunchKernelGGL(bkt_finish_kernel, dim3(1), dim3(kVarBlock), 0, c->stream, (const ge_ext*)dws.p, sh.W, sh.c, sh.wide, out32, out128);
+    return VPIN_OK;
+  });
 }
 
 // out[i] = compress(decompress(a[i]) + decompress(b[i])): the row-wise sum of two Hyrax commitments
