@@ -645,11 +645,44 @@ int vpin_conv_trace_adds(const vpin_conv_trace* t, const uint8_t** px, const uin
 /* the left side sum_t r_t * out[t] of every plane (P points) */
 int vpin_conv_trace_left(const vpin_conv_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf);
 /* the two lists through vpin_gadget_point_mult_dev / vpin_gadget_point_add_dev: instances ready for vpin_snark_prove_dev
- * (*add_out stays NULL for a 1 x 1 filter, which has no additions); free them with vpin_dev_instance_free */
+ * (*add_out stays NULL for a 1 x 1 filter, which has no additions, *mult_out for a pooling trace, which has no
+ * multiplications); free them with vpin_dev_instance_free */
 int vpin_conv_trace_instances(vpin_ctx* ctx, const vpin_conv_trace* t, vpin_dev_instance** mult_out, vpin_dev_instance** add_out);
-/* wall-clock spans of the last vpin_enc_conv2d on this thread, seconds: [0] validate (upload + checks)  [1] convolution
- * (+ normalisation, outputs to the host)  [2] PRF (HMAC-SHA256, host team)  [3] RLC sums  [4] host tail  [5] total */
+/* wall-clock spans of the last encrypted-layer call on this thread (vpin_enc_conv2d, vpin_enc_fc, vpin_enc_avgpool2d), seconds:
+ * [0] validate (upload + checks)  [1] the layer's own compute: convolution, matrix-vector product (+ bias) or pooling
+ * (+ normalisation, outputs to the host)  [2] PRF (HMAC-SHA256, host team)  [3] RLC sums  [4] host tail  [5] total; a stage the
+ * layer does not have (pooling: PRF, RLC) reads 0 */
 void vpin_enc_conv_last_timings(double out[8]);
+
+/* The fully connected layer: FCLayer (flag 1) with the type-1 branch of rLCL / rLCR of src/LeNet/Server.py, where the random
+ * scalars fold into the WEIGHTS.  P rows of K input points (the c1 vector, then the c2 vector), one K x N matrix of u32 weights
+ * (W[k][j] row-major, 4 bytes little-endian each), P x N encrypted bias points and one 32-byte key per row.  Per row p, in
+ * this order:
+ *   1. C[j] = sum_k W[k][j] * X[k], out[j] = C[j] + bias[j]: N additions (C[j], bias[j]); an identity bias as rz = 1,
+ *      rx = ry = 0.  VPIN_ESHAPE if a C[j] is the identity (an accumulator has no flag).
+ *   2. r_j = the PRF of vpin_enc_conv2d under key_p, j = 0 .. N - 1; left = sum_j r_j * C[j] (over C, not out).
+ *   3. s_k = sum_j r_j * W[k][j] as an exact integer; VPIN_ESHAPE if an s_k does not fit 128 bits (the gadget's weights are
+ *      u128; with u32 weights it stays far below q, so the reference's reduction mod the base field never fires).
+ *   4. K multiplications (s_k, X[k]); VPIN_ESHAPE if an X[k] is the identity.
+ *   5. T_k = s_k * X[k]; acc = T_0 and, for k >= 1, the addition (acc, T_k), then acc += T_k: K - 1 additions; an identity
+ *      T_k as rz = 1.  VPIN_ESHAPE if acc is the identity before a step.
+ *   6. VPIN_EVERIFY unless acc == left.
+ * The trace's dims are {P, 1, N, P * K, P * (N + K - 1)}; its output is out (P x N points, an identity allowed and flagged),
+ * its left sides are P points.  VPIN_EINVAL as for vpin_enc_conv2d, for the inputs and the bias: a null argument, P, K or N
+ * zero, prf_bytes outside 1..16, a coordinate >= q, a point off the curve.  No trace is returned on failure. */
+int vpin_enc_fc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K,
+                const uint8_t* weights_le4, size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf,
+                const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out);
+/* The average pooling: myAvgPool2d (type1 = 1, flag = 1) of src/LeNet/Server.py over P planes of H x W points with a k x k
+ * window.  oh = (H - k) / stride + 1, ow likewise, outputs row-major.  Per output, with the window's elements e_0 .. e_{k*k-1}
+ * taken row-major: acc = e_0 and, for m >= 1, the addition (acc, e_m), then acc += e_m; out = scale * acc (scale: u128
+ * little-endian; the reference's is 2^10 / k^2).  An identity e_m, m >= 1, is written as rz = 1.  VPIN_ESHAPE if an accumulator is
+ * the identity (e_0 is, or a partial sum cancels before the last step); the last sum may be the identity, the output is then
+ * flagged.  No multiplication is recorded and no RLC check runs: dims are {P, oh, ow, 0, P * oh * ow * (k*k - 1)},
+ * vpin_conv_trace_mults and _left give NULL views, vpin_conv_trace_instances leaves *mult_out NULL (and *add_out too for
+ * k = 1).  VPIN_EINVAL: a null argument, a zero dimension, k > H, k > W, stride = 0, a coordinate >= q, a point off the curve. */
+int vpin_enc_avgpool2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
+                       size_t k, size_t stride, const uint8_t scale_le16[16], vpin_conv_trace** out);
 
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's

@@ -167,6 +167,8 @@ def lib():
     L.vpin_e2_msm.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_conv2d.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
     L.vpin_enc_conv2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
+    L.vpin_enc_fc.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.vpin_enc_avgpool2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, C.POINTER(vp)]
     L.vpin_conv_trace_free.argtypes = [vp]
     L.vpin_conv_trace_free.restype = None
     L.vpin_conv_trace_dims.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -378,8 +380,9 @@ class DevInstance:
 
 
 class ConvTrace:
-    """What vpin_enc_conv2d returns: the output ciphertext of an encrypted convolution layer and the two operation lists
-    of its random-linear-combination check, in the gadgets' input format (host memory, owned by the library)."""
+    """What vpin_enc_conv2d, vpin_enc_fc and vpin_enc_avgpool2d return: the output ciphertext of an encrypted layer and its
+    two operation lists (for pooling: additions only, and no left side), in the gadgets' input format (host memory, owned
+    by the library)."""
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
@@ -415,14 +418,15 @@ class ConvTrace:
         return self._views("vpin_conv_trace_adds", [(n, 32), (n, 32), (n, 32), (n, 32), (n,)])
 
     def left(self):
-        """(x, y, inf) of the left side of every plane"""
-        return self._views("vpin_conv_trace_left", [(self.P, 32), (self.P, 32), (self.P,)])
+        """(x, y, inf) of the left side of every plane; empty for a pooling trace, which has no check"""
+        n = self.P if self.n_mult else 0
+        return self._views("vpin_conv_trace_left", [(n, 32), (n, 32), (n,)])
 
     def instances(self):
-        """(point-mult DevInstance, point-add DevInstance or None) through vpin_gadget_point_*_dev"""
+        """(point-mult DevInstance, point-add DevInstance) through vpin_gadget_point_*_dev; None for an empty list"""
         hm, ha = C.c_void_p(), C.c_void_p()
         _chk(lib().vpin_conv_trace_instances(self.ctx.h, self.h, C.byref(hm), C.byref(ha)), "vpin_conv_trace_instances")
-        return DevInstance(self.ctx, hm), (DevInstance(self.ctx, ha) if ha.value else None)
+        return (DevInstance(self.ctx, hm) if hm.value else None), (DevInstance(self.ctx, ha) if ha.value else None)
 
     def free(self):
         if self.h:
@@ -1204,10 +1208,38 @@ class Context:
         h = C.c_void_p()
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         rc = lib().vpin_enc_conv2d(self.h, p(x), p(y), p(f), P, H, W, p(w), fh, fw, pad, stride, p(k), prf_bytes, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_conv2d")
+
+    def _trace(self, rc, h, where):
         if rc:
-            assert not h.value, "vpin_enc_conv2d returned a handle with an error"
-            _chk(rc, "vpin_enc_conv2d")
+            assert not h.value, where + " returned a handle with an error"
+            _chk(rc, where)
         return ConvTrace(self, h)
+
+    def enc_fc(self, x, y, inf, P, K, weights, N, bx, by, binf, keys, prf_bytes=16):
+        """the fully connected layer (vpin_enc_fc): P rows of K points, weights[k][j] (K x N ints below 2^32), P x N bias
+        points, one 32-byte key per row -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        bx, by, bf = self._points(bx, by, binf)
+        w = np.asarray(weights, dtype=np.uint64).reshape(-1)
+        assert x.shape[0] == P * K and bx.shape[0] == P * N and w.size == K * N and (w.size == 0 or int(w.max()) < 2**32)
+        w = np.ascontiguousarray(w.astype("<u4"))
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy()
+        assert k.size == 32 * P
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_fc(self.h, p(x), p(y), p(f), P, K, p(w), N, p(bx), p(by), p(bf), p(k), prf_bytes, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_fc")
+
+    def enc_avgpool2d(self, x, y, inf, P, H, W, k, stride, scale):
+        """the average pooling (vpin_enc_avgpool2d): P planes of H x W points, a k x k window, scale a Python int < 2^128 -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == P * H * W
+        s = self._u128s([scale])
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_avgpool2d(self.h, p(x), p(y), p(f), P, H, W, k, stride, p(s), C.byref(h))
+        return self._trace(rc, h, "vpin_enc_avgpool2d")
 
     @staticmethod
     def enc_conv_timings():

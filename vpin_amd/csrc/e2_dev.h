@@ -108,4 +108,51 @@ __device__ __forceinline__ void e2_store(e2_jac* __restrict__ p, const e2_jac& v
   fq_store(&p->X, v.X); fq_store(&p->Y, v.Y); fq_store(&p->Z, v.Z);
 }
 
+// ---- shared by the kernels of enc_conv.hip and enc_fc.hip ------------------------------------------------------------
+
+// s * (x, y) for an affine point that is not the identity: double-and-add from the top set bit down.  The scalar is the nb-bit
+// number at the top of r3:r2:r1:r0 (a u128: nb = 128; a u32 passed as r3: nb = 32), kept as four shifted words
+__device__ __forceinline__ e2_jac e2_mul_affine(const fq& x, const fq& y, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, int nb,
+                                                const fq& a) {
+  e2_jac acc = e2_identity();
+  if (r0 | r1 | r2 | r3) {
+#define VPIN_E2_SHL1() do { r3 = (r3 << 1) | (r2 >> 31); r2 = (r2 << 1) | (r1 >> 31); r1 = (r1 << 1) | (r0 >> 31); r0 <<= 1; nb--; } while (0)
+    while (!(r3 >> 31)) VPIN_E2_SHL1();
+    acc.X = x; acc.Y = y; acc.Z = fq_one();  // the top set bit
+    VPIN_E2_SHL1();
+    for (; nb > 0;) {
+      acc = e2_dbl(acc, a);
+      if (r3 >> 31) acc = e2_add_mixed(acc, x, y, a);
+      VPIN_E2_SHL1();
+    }
+#undef VPIN_E2_SHL1
+  }
+  return acc;
+}
+
+constexpr int kE2Block = 256;
+
+// sum of the workgroup's kE2Block points into sh[0]
+__device__ __forceinline__ void e2_block_tree(e2_jac* sh, const e2_jac& mine, const fq& a) {
+  const int tid = threadIdx.x;
+  e2_store(&sh[tid], mine);
+  __syncthreads();
+  for (int wdt = kE2Block / 2; wdt >= 1; wdt >>= 1) {
+    if (tid < wdt) e2_store(&sh[tid], e2_add(e2_load(&sh[tid]), e2_load(&sh[tid + wdt]), a));
+    __syncthreads();
+  }
+}
+
+struct E2Geom {
+  int H, W, fh, fw, pad, stride, oh, ow;
+};
+
+// index of tap k of output t's window inside its plane, or -1 in the padding
+__device__ __forceinline__ long e2_window_index(const E2Geom& g, int t, int k) {
+  const int i = t / g.ow, j = t % g.ow, ii = k / g.fw, jj = k % g.fw;
+  const int r = i * g.stride + ii - g.pad, c = j * g.stride + jj - g.pad;
+  if (r < 0 || r >= g.H || c < 0 || c >= g.W) return -1;
+  return (long)r * g.W + c;
+}
+
 }  // namespace vpin

@@ -3,7 +3,8 @@
 // additions that the check reduces one convolution to, the equality test, and the two operation lists in the order the
 // point-mult / point-add gadgets prove them.  The convolution itself and the f^2 + 1 sums of the check run on the device
 // (enc_conv.hip).  Restates the type-1 path of the reference's convolution service (src/convolution/Server.py,
-// src/LeNet/Server.py: myConv2d, rLCL, rLCR).
+// src/LeNet/Server.py: myConv2d, rLCL, rLCR).  The E2 host code, the PRF and the trace accessors here also serve the fully
+// connected and pooling layers (enc_fc.cpp) through namespace vpin::enc of enc_conv.h.
 #include <omp.h>
 
 #include <algorithm>
@@ -25,33 +26,25 @@ using vpin::set_last_error_text;
 using vpin_host::Fq;
 typedef unsigned __int128 u128;
 
-namespace {
+namespace vpin {
+namespace enc {
 
 // ---- E2 on the host: affine in and out, Jacobian inside, complete by case -----------------------------------------
 
-struct Aff {
-  Fq x = Fq::zero(), y = Fq::zero();
-  bool inf = true;
-};
-struct Jac {
-  Fq X, Y, Z;
-  bool inf() const { return Z.is_zero(); }
-};
-
-Fq fq_from_le32(const uint8_t* b) {
+static Fq fq_from_le32(const uint8_t* b) {
   Fq t;
   memcpy(t.l, b, 32);
   return t * Fq::r2();
 }
 
-const Fq& curve_a() {
+static const Fq& curve_a() {
   static const Fq a = fq_from_le32(vpin_gadgets::kAPdBytes);
   return a;
 }
 
-Jac jac_identity() { return Jac{Fq::zero(), Fq::one(), Fq::zero()}; }
+static Jac jac_identity() { return Jac{Fq::zero(), Fq::one(), Fq::zero()}; }
 
-Jac jac_dbl(const Jac& p) {
+static Jac jac_dbl(const Jac& p) {
   if (p.inf()) return p;
   const Fq XX = p.X * p.X, YY = p.Y * p.Y, YYYY = YY * YY, ZZ = p.Z * p.Z;
   Fq S = p.X * YY; S = S + S; S = S + S;
@@ -64,7 +57,7 @@ Jac jac_dbl(const Jac& p) {
   return r;
 }
 
-Jac jac_add_mixed(const Jac& p, const Aff& q) {
+static Jac jac_add_mixed(const Jac& p, const Aff& q) {
   if (q.inf) return p;
   if (p.inf()) return Jac{q.x, q.y, Fq::one()};
   const Fq ZZ = p.Z * p.Z, U2 = q.x * ZZ, S2 = q.y * ZZ * p.Z, H = U2 - p.X, R = S2 - p.Y;
@@ -92,7 +85,7 @@ Aff aff_add(const Aff& p, const Aff& q) {
   return to_affine(jac_add_mixed(Jac{p.x, p.y, Fq::one()}, q));
 }
 
-Aff aff_mul(u128 w, const Aff& p) {
+static Aff aff_mul(u128 w, const Aff& p) {
   Jac acc = jac_identity();
   if (p.inf) return Aff();
   for (int b = 127; b >= 0; b--) {
@@ -104,6 +97,15 @@ Aff aff_mul(u128 w, const Aff& p) {
 
 bool aff_eq(const Aff& p, const Aff& q) { return p.inf == q.inf && (p.inf || (p.x == q.x && p.y == q.y)); }
 
+Aff aff_from_bytes(const uint8_t* x, const uint8_t* y, uint8_t inf) {
+  Aff r;
+  if (inf) return r;
+  r.x = fq_from_le32(x);
+  r.y = fq_from_le32(y);
+  r.inf = false;
+  return r;
+}
+
 // canonical little-endian coordinates; the identity is written as zeros
 void put_point(const Aff& p, uint8_t* x, uint8_t* y) {
   if (p.inf) { memset(x, 0, 32); memset(y, 0, 32); return; }
@@ -113,7 +115,7 @@ void put_point(const Aff& p, uint8_t* x, uint8_t* y) {
 
 // ---- HMAC-SHA256 (RFC 2104) over the library's SHA-256, key of 32 bytes --------------------------------------------
 
-void hmac_sha256_key32(const uint8_t key[32], const uint8_t* msg, size_t n, uint8_t out[32]) {
+static void hmac_sha256_key32(const uint8_t key[32], const uint8_t* msg, size_t n, uint8_t out[32]) {
   uint8_t inner[64 + 32], outer[64 + 32];  // n <= 32: a decimal index
   memset(inner, 0x36, 64);
   memset(outer, 0x5c, 64);
@@ -138,8 +140,6 @@ int fail(int code, const char* why) {
   return code;
 }
 
-constexpr size_t kMaxDim = (size_t)1 << 24;
-
 int make_geom(size_t P, size_t H, size_t W, size_t fh, size_t fw, size_t pad, size_t stride, ConvGeom* g) {
   if (!P || !H || !W || !fh || !fw || !stride) return fail(VPIN_EINVAL, "enc_conv: a dimension is zero");
   if (P > 65535 || H > kMaxDim || W > kMaxDim || fh > kMaxDim || fw > kMaxDim || pad > kMaxDim || stride > kMaxDim || fh * fw > 65534)
@@ -153,9 +153,9 @@ int make_geom(size_t P, size_t H, size_t W, size_t fh, size_t fw, size_t pad, si
   return VPIN_OK;
 }
 
-int check_flags(uint32_t flags) {
-  if (flags & vpin::kE2FlagRange) return fail(VPIN_EINVAL, "enc_conv: a coordinate is not below q");
-  if (flags & vpin::kE2FlagOffCurve) return fail(VPIN_EINVAL, "enc_conv: a pixel is not on the curve E2");
+int check_flags(uint32_t flags, const char* who, const char* what) {
+  if (flags & vpin::kE2FlagRange) return fail(VPIN_EINVAL, (std::string(who) + ": a coordinate is not below q").c_str());
+  if (flags & vpin::kE2FlagOffCurve) return fail(VPIN_EINVAL, (std::string(who) + ": a " + what + " is not on the curve E2").c_str());
   return VPIN_OK;
 }
 
@@ -165,29 +165,16 @@ Jac jac_from_bytes(const uint8_t* p) {
   return r;
 }
 
-thread_local double g_timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static thread_local double g_timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-struct Lap {
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  double operator()() {
-    const auto n = std::chrono::steady_clock::now();
-    const double s = std::chrono::duration<double>(n - t).count();
-    t = n;
-    return s;
-  }
-};
+double* last_timings() { return g_timings; }
 
 int team_size() { return (int)std::max(1.0, std::min(16.0, vpin::host_cpu_quota())); }
 
-}  // namespace
+}  // namespace enc
+}  // namespace vpin
 
-struct vpin_conv_trace {
-  size_t P = 0, oh = 0, ow = 0, n_mult = 0, n_add = 0;
-  std::vector<uint8_t> out_x, out_y, out_inf;        // P * oh * ow
-  std::vector<uint8_t> m_w, m_px, m_py;              // n_mult
-  std::vector<uint8_t> a_px, a_py, a_rx, a_ry, a_rz; // n_add
-  std::vector<uint8_t> left_x, left_y, left_inf;     // P
-};
+using namespace vpin::enc;
 
 extern "C" {
 
@@ -279,9 +266,7 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
   }
   t->n_mult = P * taps;
   t->n_add = P * (taps - 1);
-  t->m_w.resize(t->n_mult * 16); t->m_px.resize(t->n_mult * 32); t->m_py.resize(t->n_mult * 32);
-  t->a_px.resize(t->n_add * 32); t->a_py.resize(t->n_add * 32); t->a_rx.resize(t->n_add * 32); t->a_ry.resize(t->n_add * 32);
-  t->a_rz.resize(t->n_add);
+  t->resize_lists();
   t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
   bool equal = true;
   for (size_t p = 0; p < P; p++) {
@@ -349,11 +334,11 @@ int vpin_conv_trace_instances(vpin_ctx* c, const vpin_conv_trace* t, vpin_dev_in
   if (mult_out) *mult_out = nullptr;
   if (add_out) *add_out = nullptr;
   if (!c || !t || !mult_out || !add_out) return VPIN_EINVAL;
-  int rc = vpin_gadget_point_mult_dev(c, t->m_w.data(), t->m_px.data(), t->m_py.data(), t->n_mult, mult_out);
-  if (rc) return rc;
-  if (t->n_add == 0) return VPIN_OK;  // a 1 x 1 filter: one multiplication per plane, nothing to add
+  int rc = VPIN_OK;
+  if (t->n_mult && (rc = vpin_gadget_point_mult_dev(c, t->m_w.data(), t->m_px.data(), t->m_py.data(), t->n_mult, mult_out))) return rc;  // pooling multiplies nothing
+  if (t->n_add == 0) return VPIN_OK;  // a 1 x 1 filter or window: nothing to add
   rc = vpin_gadget_point_add_dev(c, t->a_px.data(), t->a_py.data(), t->a_rx.data(), t->a_ry.data(), t->a_rz.data(), t->n_add, add_out);
-  if (rc) { vpin_dev_instance_free(c, *mult_out); *mult_out = nullptr; }
+  if (rc && *mult_out) { vpin_dev_instance_free(c, *mult_out); *mult_out = nullptr; }
   return rc;
 }
 

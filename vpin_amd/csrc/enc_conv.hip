@@ -24,24 +24,10 @@ namespace vpin {
 
 namespace {
 
-constexpr int kEB = 256;
-
-struct GeomDev {
-  int H, W, fh, fw, pad, stride, oh, ow;
-};
-
-// index of tap k of output t's window inside its plane, or -1 in the padding
-__device__ __forceinline__ long window_index(const GeomDev& g, int t, int k) {
-  const int i = t / g.ow, j = t % g.ow, ii = k / g.fw, jj = k % g.fw;
-  const int r = i * g.stride + ii - g.pad, c = j * g.stride + jj - g.pad;
-  if (r < 0 || r >= g.H || c < 0 || c >= g.W) return -1;
-  return (long)r * g.W + c;
-}
-
-__global__ __launch_bounds__(kEB) void e2_load_kernel(const fq* __restrict__ xb, const fq* __restrict__ yb,
-                                                      const uint8_t* __restrict__ inf, size_t n, fq a, fq b,
-                                                      fq* __restrict__ X, fq* __restrict__ Y, uint32_t* __restrict__ flags) {
-  const size_t i = (size_t)blockIdx.x * kEB + threadIdx.x;
+__global__ __launch_bounds__(kE2Block) void e2_load_kernel(const fq* __restrict__ xb, const fq* __restrict__ yb,
+                                                           const uint8_t* __restrict__ inf, size_t n, fq a, fq b,
+                                                           fq* __restrict__ X, fq* __restrict__ Y, uint32_t* __restrict__ flags) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
   if (i >= n) return;
   const fq xr = fq_load(xb + i), yr = fq_load(yb + i);
   unsigned bx = 0, by = 0;
@@ -63,7 +49,7 @@ __global__ __launch_bounds__(kEB) void e2_load_kernel(const fq* __restrict__ xb,
 }
 
 __global__ __launch_bounds__(64) void e2_conv_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
-                                                     const uint8_t* __restrict__ inf, GeomDev g,
+                                                     const uint8_t* __restrict__ inf, E2Geom g,
                                                      const uint32_t* __restrict__ w, int top_bit, fq a,
                                                      e2_jac* __restrict__ out) {
   const int t = (int)(blockIdx.x * 64 + threadIdx.x), n_out = g.oh * g.ow;
@@ -75,7 +61,7 @@ __global__ __launch_bounds__(64) void e2_conv_kernel(const fq* __restrict__ X, c
     if (!e2_is_identity(acc)) acc = e2_dbl(acc, a);
     for (int k = 0; k < taps; k++) {
       if (!((w[4 * k + (bit >> 5)] >> (bit & 31)) & 1u)) continue;  // the same for every lane
-      const long wi = window_index(g, t, k);
+      const long wi = e2_window_index(g, t, k);
       if (wi < 0 || inf[base + wi]) continue;  // padding and flagged pixels are the identity
       acc = e2_add_mixed(acc, fq_load(X + base + wi), fq_load(Y + base + wi), a);
     }
@@ -84,18 +70,18 @@ __global__ __launch_bounds__(64) void e2_conv_kernel(const fq* __restrict__ X, c
 }
 
 // mx, my: Montgomery (for e2_rlc_kernel); cx, cy: canonical little-endian (the caller's bytes); identity: zeros and flag 1
-__global__ __launch_bounds__(kEB) void e2_to_affine_kernel(const e2_jac* __restrict__ in, size_t n, fq* __restrict__ mx,
-                                                           fq* __restrict__ my, fq* __restrict__ cx, fq* __restrict__ cy,
-                                                           uint8_t* __restrict__ oinf) {
-  __shared__ fq tree[2 * kEB];  // node j has children 2j and 2j + 1; the leaves are tree[kEB ..]
+__global__ __launch_bounds__(kE2Block) void e2_to_affine_kernel(const e2_jac* __restrict__ in, size_t n, fq* __restrict__ mx,
+                                                                fq* __restrict__ my, fq* __restrict__ cx, fq* __restrict__ cy,
+                                                                uint8_t* __restrict__ oinf) {
+  __shared__ fq tree[2 * kE2Block];  // node j has children 2j and 2j + 1; the leaves are tree[kE2Block ..]
   const int tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kEB + tid;
+  const size_t i = (size_t)blockIdx.x * kE2Block + tid;
   e2_jac p = e2_identity();
   if (i < n) p = e2_load(in + i);
   const bool idn = e2_is_identity(p);
-  fq_store(&tree[kEB + tid], idn ? fq_one() : p.Z);
+  fq_store(&tree[kE2Block + tid], idn ? fq_one() : p.Z);
   __syncthreads();
-  for (int wdt = kEB / 2; wdt >= 1; wdt >>= 1) {
+  for (int wdt = kE2Block / 2; wdt >= 1; wdt >>= 1) {
     if (tid < wdt) {
       const int j = wdt + tid;
       fq_store(&tree[j], e2_fqm(fq_load(&tree[2 * j]), fq_load(&tree[2 * j + 1])));
@@ -104,7 +90,7 @@ __global__ __launch_bounds__(kEB) void e2_to_affine_kernel(const e2_jac* __restr
   }
   if (tid == 0) fq_store(&tree[1], e2_fq_inv(fq_load(&tree[1])));
   __syncthreads();
-  for (int wdt = 1; wdt <= kEB / 2; wdt <<= 1) {
+  for (int wdt = 1; wdt <= kE2Block / 2; wdt <<= 1) {
     if (tid < wdt) {
       const int j = wdt + tid;
       const fq pi = fq_load(&tree[j]), l = fq_load(&tree[2 * j]), r = fq_load(&tree[2 * j + 1]);
@@ -116,7 +102,7 @@ __global__ __launch_bounds__(kEB) void e2_to_affine_kernel(const e2_jac* __restr
   if (i >= n) return;
   fq x = fq_zero(), y = fq_zero();
   if (!idn) {
-    const fq zi = fq_load(&tree[kEB + tid]), zi2 = e2_fqm(zi, zi);
+    const fq zi = fq_load(&tree[kE2Block + tid]), zi2 = e2_fqm(zi, zi);
     x = e2_fqm(p.X, zi2);
     y = e2_fqm(p.Y, e2_fqm(zi2, zi));
   }
@@ -127,25 +113,14 @@ __global__ __launch_bounds__(kEB) void e2_to_affine_kernel(const e2_jac* __restr
   oinf[i] = idn ? 1 : 0;
 }
 
-// sum of the workgroup's kEB points into sh[0]
-__device__ __forceinline__ void e2_block_tree(e2_jac* sh, const e2_jac& mine, const fq& a) {
-  const int tid = threadIdx.x;
-  e2_store(&sh[tid], mine);
-  __syncthreads();
-  for (int wdt = kEB / 2; wdt >= 1; wdt >>= 1) {
-    if (tid < wdt) e2_store(&sh[tid], e2_add(e2_load(&sh[tid]), e2_load(&sh[tid + wdt]), a));
-    __syncthreads();
-  }
-}
-
 // grid: x = blocks of terms, y = sum (tap k, or taps = the outputs themselves), z = plane
-__global__ __launch_bounds__(kEB) void e2_rlc_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
-                                                     const uint8_t* __restrict__ inf, const fq* __restrict__ OX,
-                                                     const fq* __restrict__ OY, const uint8_t* __restrict__ oinf, GeomDev g,
-                                                     int taps, size_t n_terms, const uint4* __restrict__ r, fq a,
-                                                     e2_jac* __restrict__ parts) {
-  __shared__ e2_jac sh[kEB];
-  const size_t t = (size_t)blockIdx.x * kEB + threadIdx.x, plane = blockIdx.z;
+__global__ __launch_bounds__(kE2Block) void e2_rlc_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                          const uint8_t* __restrict__ inf, const fq* __restrict__ OX,
+                                                          const fq* __restrict__ OY, const uint8_t* __restrict__ oinf, E2Geom g,
+                                                          int taps, size_t n_terms, const uint4* __restrict__ r, fq a,
+                                                          e2_jac* __restrict__ parts) {
+  __shared__ e2_jac sh[kE2Block];
+  const size_t t = (size_t)blockIdx.x * kE2Block + threadIdx.x, plane = blockIdx.z;
   const int s = (int)blockIdx.y;
   bool have = false;
   fq x = fq_zero(), y = fq_zero();
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(kEB) void e2_rlc_kernel(const fq* __restrict__ X, c
       const size_t idx = plane * n_terms + t;
       if (!oinf[idx]) { have = true; x = fq_load(OX + idx); y = fq_load(OY + idx); }
     } else {
-      const long wi = window_index(g, (int)t, s);
+      const long wi = e2_window_index(g, (int)t, s);
       const size_t idx = plane * (size_t)g.H * g.W + (size_t)(wi < 0 ? 0 : wi);
       if (wi >= 0 && !inf[idx]) { have = true; x = fq_load(X + idx); y = fq_load(Y + idx); }
     }
@@ -162,20 +137,7 @@ __global__ __launch_bounds__(kEB) void e2_rlc_kernel(const fq* __restrict__ X, c
   e2_jac acc = e2_identity();
   if (have) {
     const uint4 rr = r[plane * n_terms + t];
-    uint32_t r0 = rr.x, r1 = rr.y, r2 = rr.z, r3 = rr.w;
-    if (r0 | r1 | r2 | r3) {
-      int nb = 128;
-#define VPIN_E2_SHL1() do { r3 = (r3 << 1) | (r2 >> 31); r2 = (r2 << 1) | (r1 >> 31); r1 = (r1 << 1) | (r0 >> 31); r0 <<= 1; nb--; } while (0)
-      while (!(r3 >> 31)) VPIN_E2_SHL1();
-      acc.X = x; acc.Y = y; acc.Z = fq_one();  // the top set bit
-      VPIN_E2_SHL1();
-      for (; nb > 0;) {
-        acc = e2_dbl(acc, a);
-        if (r3 >> 31) acc = e2_add_mixed(acc, x, y, a);
-        VPIN_E2_SHL1();
-      }
-#undef VPIN_E2_SHL1
-    }
+    acc = e2_mul_affine(x, y, rr.x, rr.y, rr.z, rr.w, 128, a);
   }
   e2_block_tree(sh, acc, a);
   if (threadIdx.x == 0)
@@ -183,12 +145,12 @@ __global__ __launch_bounds__(kEB) void e2_rlc_kernel(const fq* __restrict__ X, c
 }
 
 // one workgroup per sum: out[b] = sum of parts[b * n_parts ..][0 .. n_parts)
-__global__ __launch_bounds__(kEB) void e2_reduce_kernel(const e2_jac* __restrict__ parts, size_t n_parts, fq a,
-                                                        e2_jac* __restrict__ out) {
-  __shared__ e2_jac sh[kEB];
+__global__ __launch_bounds__(kE2Block) void e2_reduce_kernel(const e2_jac* __restrict__ parts, size_t n_parts, fq a,
+                                                             e2_jac* __restrict__ out) {
+  __shared__ e2_jac sh[kE2Block];
   const e2_jac* p = parts + (size_t)blockIdx.x * n_parts;
   e2_jac acc = e2_identity();
-  for (size_t i = threadIdx.x; i < n_parts; i += kEB) acc = e2_add(acc, e2_load(p + i), a);
+  for (size_t i = threadIdx.x; i < n_parts; i += kE2Block) acc = e2_add(acc, e2_load(p + i), a);
   e2_block_tree(sh, acc, a);
   if (threadIdx.x == 0) e2_store(out + blockIdx.x, e2_load(&sh[0]));
 }
@@ -208,35 +170,44 @@ fq fq_of_le32(const uint8_t* b) {
 const uint8_t kE2BBytes[32] = {86, 83, 202, 68, 110, 236, 64, 249, 56, 118, 236, 1, 191, 143, 126, 100,
                                4, 149, 41, 137, 111, 171, 93, 146, 250, 112, 171, 90, 44, 184, 8, 8};
 
-GeomDev geom_dev(const ConvGeom& g) {
-  return GeomDev{(int)g.H, (int)g.W, (int)g.fh, (int)g.fw, (int)g.pad, (int)g.stride, (int)g.oh, (int)g.ow};
-}
-
-unsigned blocks_of(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
-#define VPIN_EC_ALLOC(buf, bytes) do { (buf).release(); if ((buf).alloc((bytes) ? (bytes) : 16)) return VPIN_ENOMEM; } while (0)
-
 // the sums of e2_rlc_kernel + e2_reduce_kernel: P x (taps + 1) Jacobian triples to the host
 int run_rlc(vpin_ctx* c, const fq* X, const fq* Y, const uint8_t* inf, const fq* OX, const fq* OY, const uint8_t* oinf,
             const ConvGeom& g, size_t n_terms, const uint8_t* r_le16, uint8_t* sums_jac) {
-  const size_t nsum = g.taps() + 1, nblk = (n_terms + kEB - 1) / kEB, total = g.P * n_terms;
+  const size_t nsum = g.taps() + 1, nblk = (n_terms + kE2Block - 1) / kE2Block, total = g.P * n_terms;
   DevBuf r(c), parts(c), sums(c);
   if (r.alloc(total * 16) || parts.alloc(g.P * nsum * nblk * sizeof(e2_jac)) || sums.alloc(g.P * nsum * sizeof(e2_jac)))
     return VPIN_ENOMEM;
-  const fq a = fq_of_le32(vpin_gadgets::kAPdBytes);
+  const fq a = e2_curve_a();
   VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le16, total * 16, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_rlc_kernel, dim3((unsigned)nblk, (unsigned)nsum, (unsigned)g.P), dim3(kEB), 0, c->stream, X, Y, inf, OX, OY,
-                     oinf, geom_dev(g), (int)g.taps(), n_terms, (const uint4*)r.p, a, (e2_jac*)parts.p);
+  hipLaunchKernelGGL(e2_rlc_kernel, dim3((unsigned)nblk, (unsigned)nsum, (unsigned)g.P), dim3(kE2Block), 0, c->stream, X, Y, inf, OX, OY,
+                     oinf, e2_geom(g), (int)g.taps(), n_terms, (const uint4*)r.p, a, (e2_jac*)parts.p);
   VPIN_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(e2_reduce_kernel, dim3((unsigned)(g.P * nsum)), dim3(kEB), 0, c->stream, (const e2_jac*)parts.p, nblk, a,
-                     (e2_jac*)sums.p);
-  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_reduce(c, (const e2_jac*)parts.p, g.P * nsum, nblk, (e2_jac*)sums.p);
+  if (rc) return rc;
   VPIN_HIP_TRY(hipMemcpyAsync(sums_jac, sums.p, g.P * nsum * sizeof(e2_jac), hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }
 
 }  // namespace
+
+E2Geom e2_geom(const ConvGeom& g) {
+  return E2Geom{(int)g.H, (int)g.W, (int)g.fh, (int)g.fw, (int)g.pad, (int)g.stride, (int)g.oh, (int)g.ow};
+}
+
+fq e2_curve_a() { return fq_of_le32(vpin_gadgets::kAPdBytes); }
+
+int e2_to_affine(vpin_ctx* c, const e2_jac* in, size_t n, fq* mx, fq* my, fq* cx, fq* cy, uint8_t* oinf) {
+  hipLaunchKernelGGL(e2_to_affine_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, in, n, mx, my, cx, cy, oinf);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+int e2_reduce(vpin_ctx* c, const e2_jac* parts, size_t n_sums, size_t n_parts, e2_jac* out) {
+  hipLaunchKernelGGL(e2_reduce_kernel, dim3((unsigned)n_sums), dim3(kE2Block), 0, c->stream, parts, n_parts, e2_curve_a(), out);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
 
 int EncConvDev::load(const uint8_t* x, const uint8_t* y, const uint8_t* inf, size_t n, uint32_t* flags) {
   (void)hipSetDevice(c->device);
@@ -249,8 +220,8 @@ int EncConvDev::load(const uint8_t* x, const uint8_t* y, const uint8_t* inf, siz
   VPIN_HIP_TRY(hipMemcpyAsync(ry.p, y, n * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(pinf.p, inf, n, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemsetAsync(fl.p, 0, 4, c->stream));
-  hipLaunchKernelGGL(e2_load_kernel, dim3(blocks_of(n, kEB)), dim3(kEB), 0, c->stream, (const fq*)rx.p, (const fq*)ry.p,
-                     (const uint8_t*)pinf.p, n, fq_of_le32(vpin_gadgets::kAPdBytes), fq_of_le32(kE2BBytes), (fq*)px.p, (fq*)py.p,
+  hipLaunchKernelGGL(e2_load_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)rx.p, (const fq*)ry.p,
+                     (const uint8_t*)pinf.p, n, e2_curve_a(), fq_of_le32(kE2BBytes), (fq*)px.p, (fq*)py.p,
                      (uint32_t*)fl.p);
   VPIN_HIP_TRY(hipGetLastError());
   VPIN_HIP_TRY(hipMemcpyAsync(flags, fl.p, 4, hipMemcpyDeviceToHost, c->stream));
@@ -274,12 +245,11 @@ int EncConvDev::conv(const ConvGeom& geom, const uint8_t* filter_le16, uint8_t* 
   VPIN_EC_ALLOC(oinf, n_out);
   VPIN_HIP_TRY(hipMemcpyAsync(filt.p, filter_le16, taps * 16, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(e2_conv_kernel, dim3(blocks_of(per_plane, 64), (unsigned)g.P), dim3(64), 0, c->stream, (const fq*)px.p,
-                     (const fq*)py.p, (const uint8_t*)pinf.p, geom_dev(g), (const uint32_t*)filt.p, top_bit,
-                     fq_of_le32(vpin_gadgets::kAPdBytes), (e2_jac*)jac.p);
+                     (const fq*)py.p, (const uint8_t*)pinf.p, e2_geom(g), (const uint32_t*)filt.p, top_bit,
+                     e2_curve_a(), (e2_jac*)jac.p);
   VPIN_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(e2_to_affine_kernel, dim3(blocks_of(n_out, kEB)), dim3(kEB), 0, c->stream, (const e2_jac*)jac.p, n_out,
-                     (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p);
-  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n_out, (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p);
+  if (rc) return rc;
   VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(out_inf, oinf.p, n_out, hipMemcpyDeviceToHost, c->stream));

@@ -1,0 +1,203 @@
+// enc_fc.cpp -- the encrypted fully connected layer with its random-linear-combination check, and the encrypted average
+// pooling, host side: input validation, the PRF scalars, the folded weights s_k = sum_j r_j * W[k][j] (exact, in 128 bits),
+// out = C + bias, the chains of additions, the equality test and the operation lists in the order the point-mult /
+// point-add gadgets prove them.  The matrix-vector product, the left sum, the K multiplications s_k * X[k], the pooling's
+// accumulators and its scaled outputs run on the device (enc_fc.hip, enc_conv.hip).  Restates FCLayer (flag 1) with the
+// type-1 branch of rLCL / rLCR, and myAvgPool2d (type1 = 1, flag = 1), of the reference's src/LeNet/Server.py.
+#include <omp.h>
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/vpin_hip.h"
+#include "enc_conv.h"
+
+using namespace vpin::enc;
+using vpin::ConvGeom;
+using vpin::EncConvDev;
+typedef unsigned __int128 u128;
+
+namespace {
+
+// acc += r * w; false when the sum leaves 128 bits
+bool mul_add_u128(u128& acc, u128 r, uint32_t w) {
+  const u128 lo = (u128)(uint64_t)r * w, hi = (u128)(uint64_t)(r >> 64) * w;
+  if (hi >> 64) return false;
+  const u128 prod = lo + (hi << 64);
+  if (prod < lo) return false;
+  acc += prod;
+  return acc >= prod;
+}
+
+struct TraceGuard {
+  vpin_conv_trace* t;
+  ~TraceGuard() { delete t; }
+};
+
+}  // namespace
+
+extern "C" {
+
+int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const uint8_t* weights_le4,
+                size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
+                vpin_conv_trace** out) {
+  if (out) *out = nullptr;
+  if (!c || !px || !py || !pinf || !weights_le4 || !bx || !by || !binf || !keys32 || !out) return fail(VPIN_EINVAL, "vpin_enc_fc: null argument");
+  if (prf_bytes < 1 || prf_bytes > 16) return fail(VPIN_EINVAL, "vpin_enc_fc: prf_bytes must be in 1 .. 16");
+  if (!P || !K || !N) return fail(VPIN_EINVAL, "vpin_enc_fc: a dimension is zero");
+  if (P > 65535 || N > 65535 || K > kMaxDim) return fail(VPIN_EINVAL, "vpin_enc_fc: a dimension is out of range");
+  double* tm = last_timings();
+  for (int i = 0; i < 8; i++) tm[i] = 0.0;
+  Lap total, lap;
+  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  if (!t) return VPIN_ENOMEM;
+  TraceGuard guard{t};
+  const size_t n_in = P * K, n_out = P * N, adds_per_row = N + K - 1;
+  t->P = P; t->oh = 1; t->ow = N; t->n_mult = n_in; t->n_add = P * adds_per_row;
+
+  // validate: upload, range and curve checks on the device, for the inputs and the bias
+  EncConvDev d(c), b(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, n_in, &flags);
+  if (rc) return rc;
+  if ((rc = check_flags(flags, "vpin_enc_fc", "input point"))) return rc;
+  if ((rc = b.load(bx, by, binf, n_out, &flags))) return rc;
+  if ((rc = check_flags(flags, "vpin_enc_fc", "bias point"))) return rc;
+  tm[0] = lap();
+
+  // C = X * W on the device, out = C + bias here; the first N additions of every row
+  t->resize_lists();
+  t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
+  t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
+  std::vector<uint8_t> cx(n_out * 32), cy(n_out * 32), cinf(n_out);
+  if ((rc = d.matvec(P, K, N, weights_le4, cx.data(), cy.data(), cinf.data()))) return rc;
+  for (size_t i = 0; i < n_out; i++)
+    if (cinf[i]) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator C[j] is the identity (the witness format has no flag for it)");
+#pragma omp parallel for schedule(static) num_threads(team_size())
+  for (long li = 0; li < (long)n_out; li++) {
+    const size_t i = (size_t)li, ai = (i / N) * adds_per_row + i % N;
+    const Aff bias = aff_from_bytes(bx + 32 * i, by + 32 * i, binf[i]);
+    const Aff o = aff_add(aff_from_bytes(&cx[32 * i], &cy[32 * i], 0), bias);
+    memcpy(&t->a_px[32 * ai], &cx[32 * i], 32); memcpy(&t->a_py[32 * ai], &cy[32 * i], 32);
+    put_point(bias, &t->a_rx[32 * ai], &t->a_ry[32 * ai]);
+    t->a_rz[ai] = bias.inf ? 1 : 0;
+    put_point(o, &t->out_x[32 * i], &t->out_y[32 * i]);
+    t->out_inf[i] = o.inf ? 1 : 0;
+  }
+  tm[1] = lap();
+
+  // the PRF scalars: the index restarts at 0 for every row
+  std::vector<uint8_t> r(n_out * 16);
+#pragma omp parallel for schedule(static) num_threads(team_size())
+  for (long i = 0; i < (long)n_out; i++) prf_scalar(keys32 + 32 * ((size_t)i / N), (size_t)i % N, prf_bytes, &r[16 * (size_t)i]);
+  tm[2] = lap();
+
+  // left = sum_j r_j * C[j] of every row, over the resident C
+  std::vector<uint8_t> sums(P * 96);
+  if ((rc = d.rlc(r.data(), sums.data()))) return rc;
+  tm[3] = lap();
+
+  // host tail: the folded weights, T_k = s_k * X[k] (device), the chain of additions, the equation
+  for (size_t p = 0; p < P; p++)
+    for (size_t k = 0; k < K; k++) {
+      u128 s = 0;
+      for (size_t j = 0; j < N; j++) {
+        u128 rj;
+        uint32_t w;
+        memcpy(&rj, &r[16 * (p * N + j)], 16);
+        memcpy(&w, weights_le4 + 4 * (k * N + j), 4);
+        if (!mul_add_u128(s, rj, w)) return fail(VPIN_ESHAPE, "vpin_enc_fc: a folded weight sum_j r_j * W[k][j] does not fit 128 bits");
+      }
+      memcpy(&t->m_w[16 * (p * K + k)], &s, 16);
+    }
+  for (size_t i = 0; i < n_in; i++)
+    if (pinf[i]) return fail(VPIN_ESHAPE, "vpin_enc_fc: a multiplication operand X[k] is the identity (the witness format has no flag for it)");
+  memcpy(t->m_px.data(), px, n_in * 32);
+  memcpy(t->m_py.data(), py, n_in * 32);
+  std::vector<uint8_t> tx(n_in * 32), ty(n_in * 32), tinf(n_in);
+  if ((rc = d.scalar_mul(t->m_w.data(), n_in, tx.data(), ty.data(), tinf.data()))) return rc;
+  bool equal = true;
+  for (size_t p = 0; p < P; p++) {
+    Aff acc;
+    for (size_t k = 0; k < K; k++) {
+      const size_t m = p * K + k;
+      const Aff Tk = aff_from_bytes(&tx[32 * m], &ty[32 * m], tinf[m]);
+      if (k == 0) { acc = Tk; continue; }
+      if (acc.inf) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator is the identity (the witness format has no flag for it)");
+      const size_t ai = p * adds_per_row + N + (k - 1);
+      put_point(acc, &t->a_px[32 * ai], &t->a_py[32 * ai]);
+      memcpy(&t->a_rx[32 * ai], &tx[32 * m], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * m], 32);
+      t->a_rz[ai] = tinf[m];
+      acc = aff_add(acc, Tk);
+    }
+    const Aff left = to_affine(jac_from_bytes(&sums[96 * p]));
+    put_point(left, &t->left_x[32 * p], &t->left_y[32 * p]);
+    t->left_inf[p] = left.inf ? 1 : 0;
+    if (!aff_eq(acc, left)) equal = false;
+  }
+  tm[4] = lap();
+  tm[5] = total();
+  if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_fc: the two sides of the random linear combination differ");
+  guard.t = nullptr;
+  *out = t;
+  return VPIN_OK;
+}
+
+int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W, size_t k,
+                       size_t stride, const uint8_t scale_le16[16], vpin_conv_trace** out) {
+  if (out) *out = nullptr;
+  if (!c || !px || !py || !pinf || !scale_le16 || !out) return fail(VPIN_EINVAL, "vpin_enc_avgpool2d: null argument");
+  ConvGeom g;
+  int rc = make_geom(P, H, W, k, k, 0, stride, &g);  // zero dimensions, k > H, k > W
+  if (rc) return rc;
+  double* tm = last_timings();
+  for (int i = 0; i < 8; i++) tm[i] = 0.0;
+  Lap total, lap;
+  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  if (!t) return VPIN_ENOMEM;
+  TraceGuard guard{t};
+  const size_t taps = g.taps(), n_out = g.outputs(), per_plane = g.oh * g.ow;
+  t->P = P; t->oh = g.oh; t->ow = g.ow; t->n_add = n_out * (taps - 1);
+
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
+  if ((rc = check_flags(flags, "vpin_enc_avgpool2d", "pixel"))) return rc;
+  tm[0] = lap();
+
+  // the accumulators of the additions, then out = scale * (window sum) as the convolution under a constant filter
+  t->resize_lists();
+  if (t->n_add) {
+    std::vector<uint8_t> bad(n_out);
+    if ((rc = d.pool_sums(g, t->a_px.data(), t->a_py.data(), bad.data()))) return rc;
+    for (size_t i = 0; i < n_out; i++)
+      if (bad[i]) return fail(VPIN_ESHAPE, "vpin_enc_avgpool2d: an addition accumulator is the identity (the witness format has no flag for it)");
+  }
+  std::vector<uint8_t> filt(taps * 16);
+  for (size_t m = 0; m < taps; m++) memcpy(&filt[16 * m], scale_le16, 16);
+  t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
+  if ((rc = d.conv(g, filt.data(), t->out_x.data(), t->out_y.data(), t->out_inf.data()))) return rc;
+  tm[1] = lap();
+
+  // host tail: the second operands e_1 .. e_{k*k-1} of every output, from the caller's bytes
+#pragma omp parallel for schedule(static) num_threads(team_size())
+  for (long lo = 0; lo < (long)n_out; lo++) {
+    const size_t o = (size_t)lo, plane = o / per_plane, i = (o % per_plane) / g.ow, j = o % g.ow;
+    for (size_t m = 1; m < taps; m++) {
+      const size_t src = plane * H * W + (i * stride + m / k) * W + j * stride + m % k, ai = o * (taps - 1) + (m - 1);
+      if (pinf[src]) {
+        t->a_rz[ai] = 1;  // rx, ry stay zero
+      } else {
+        memcpy(&t->a_rx[32 * ai], px + 32 * src, 32); memcpy(&t->a_ry[32 * ai], py + 32 * src, 32);
+      }
+    }
+  }
+  tm[4] = lap();
+  tm[5] = total();
+  guard.t = nullptr;
+  *out = t;
+  return VPIN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,137 @@
+// enc_fc.hip -- the device stages of the encrypted fully connected layer and of the encrypted average pooling (driven by
+// enc_fc.cpp), beside enc_conv.hip whose load, convolution, normalisation, RLC and reduce kernels they reuse.
+//
+//   e2_matvec_kernel      C[p][j] = sum_k W[k][j] * X[p][k]: one lane per (k, j) term on grid (blocks of k, N, P), double-and-add
+//                         over the lane's own 32-bit weight (mixed addition), then the workgroup's LDS tree with the complete
+//                         addition; e2_reduce_kernel sums over the blocks of k
+//   e2_scalar_mul_kernel  T_i = s_i * X_i, one lane per point, s_i a u128: the multiplications of the layer's RLC check
+//   e2_pool_sums_kernel   one lane per pooled output: the k*k - 1 accumulators e_0, e_0 + e_1, ... of its window (the first
+//                         operands of the pooling's additions) and a flag when one of them is the identity
+// As in enc_conv.hip the accumulators are named registers (one e2_jac, the scalar as shifted words): no per-lane arrays.
+#include "e2_dev.h"
+#include "enc_conv.h"
+
+namespace vpin {
+
+namespace {
+
+// grid: x = blocks of k, y = output j, z = row p; W is K x N row-major
+__global__ __launch_bounds__(kE2Block) void e2_matvec_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                             const uint8_t* __restrict__ inf, const uint32_t* __restrict__ W,
+                                                             size_t K, size_t N, fq a, e2_jac* __restrict__ parts) {
+  __shared__ e2_jac sh[kE2Block];
+  const size_t k = (size_t)blockIdx.x * kE2Block + threadIdx.x, j = blockIdx.y, p = blockIdx.z;
+  e2_jac acc = e2_identity();
+  if (k < K && !inf[p * K + k])  // a zero weight gives the identity inside e2_mul_affine
+    acc = e2_mul_affine(fq_load(X + p * K + k), fq_load(Y + p * K + k), 0u, 0u, 0u, W[k * N + j], 32, a);
+  e2_block_tree(sh, acc, a);
+  if (threadIdx.x == 0) e2_store(parts + ((p * N + j) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
+}
+
+__global__ __launch_bounds__(kE2Block) void e2_scalar_mul_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                                 const uint8_t* __restrict__ inf, const uint4* __restrict__ s,
+                                                                 size_t n, fq a, e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  e2_jac acc = e2_identity();
+  if (!inf[i]) {
+    const uint4 ss = s[i];
+    acc = e2_mul_affine(fq_load(X + i), fq_load(Y + i), ss.x, ss.y, ss.z, ss.w, 128, a);
+  }
+  e2_store(out + i, acc);
+}
+
+// grid: x = blocks of outputs, y = plane.  acc[(plane * n_out + t) * (taps - 1) + m] = e_0 + .. + e_m for m < taps - 1: the
+// accumulator BEFORE element m + 1 is added; acc_identity[plane * n_out + t] = 1 when one of them is the identity
+__global__ __launch_bounds__(64) void e2_pool_sums_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                          const uint8_t* __restrict__ inf, E2Geom g, fq a,
+                                                          e2_jac* __restrict__ acc_out, uint8_t* __restrict__ acc_identity) {
+  const int t = (int)(blockIdx.x * 64 + threadIdx.x), n_out = g.oh * g.ow;
+  if (t >= n_out) return;
+  const size_t plane = blockIdx.y, base = plane * (size_t)g.H * g.W, o = plane * (size_t)n_out + t;
+  const int taps = g.fh * g.fw;
+  e2_jac acc = e2_identity();
+  uint8_t bad = 0;
+  for (int m = 0; m + 1 < taps; m++) {
+    const size_t idx = base + (size_t)e2_window_index(g, t, m);  // no padding: every window lies inside the plane
+    if (!inf[idx]) acc = e2_add_mixed(acc, fq_load(X + idx), fq_load(Y + idx), a);
+    if (e2_is_identity(acc)) bad = 1;
+    e2_store(acc_out + o * (size_t)(taps - 1) + m, acc);
+  }
+  acc_identity[o] = bad;
+}
+
+}  // namespace
+
+// C = X * W per row over the loaded points (P x K), normalised: canonical bytes to the host, Montgomery coordinates resident
+// as this object's outputs with the geometry "P planes of 1 x N and no taps", so that rlc() returns sum_j r[p][j] * C[p][j]
+int EncConvDev::matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
+  (void)hipSetDevice(c->device);
+  g = ConvGeom();
+  g.P = P; g.oh = 1; g.ow = N;
+  const size_t nblk = blocks_of(K, kE2Block), n_out = P * N;
+  DevBuf w(c), parts(c), jac(c), cx(c), cy(c);
+  if (w.alloc(K * N * 4) || parts.alloc(n_out * nblk * sizeof(e2_jac)) || jac.alloc(n_out * sizeof(e2_jac)) || cx.alloc(n_out * 32) ||
+      cy.alloc(n_out * 32))
+    return VPIN_ENOMEM;
+  VPIN_EC_ALLOC(ox, n_out * 32);
+  VPIN_EC_ALLOC(oy, n_out * 32);
+  VPIN_EC_ALLOC(oinf, n_out);
+  const fq a = e2_curve_a();
+  VPIN_HIP_TRY(hipMemcpyAsync(w.p, weights_le4, K * N * 4, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(e2_matvec_kernel, dim3((unsigned)nblk, (unsigned)N, (unsigned)P), dim3(kE2Block), 0, c->stream, (const fq*)px.p,
+                     (const fq*)py.p, (const uint8_t*)pinf.p, (const uint32_t*)w.p, K, N, a, (e2_jac*)parts.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  int rc = e2_reduce(c, (const e2_jac*)parts.p, n_out, nblk, (e2_jac*)jac.p);
+  if (rc) return rc;
+  if ((rc = e2_to_affine(c, (const e2_jac*)jac.p, n_out, (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p))) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(c_x, cx.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c_y, cy.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c_inf, oinf.p, n_out, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+// T_i = s_i * X_i over the n loaded points, normalised, as canonical bytes
+int EncConvDev::scalar_mul(const uint8_t* s_le16, size_t n, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf) {
+  (void)hipSetDevice(c->device);
+  DevBuf s(c), jac(c), mx(c), my(c), cx(c), cy(c), ti(c);
+  if (s.alloc(n * 16) || jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) ||
+      ti.alloc(n))
+    return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(s.p, s_le16, n * 16, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(e2_scalar_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
+                     (const uint8_t*)pinf.p, (const uint4*)s.p, n, e2_curve_a(), (e2_jac*)jac.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ti.p);
+  if (rc) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(t_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(t_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(t_inf, ti.p, n, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+// the accumulators of every pooled output's additions (geom: fh = fw = k, pad 0), normalised, as canonical bytes in the
+// order of the addition list: outputs() x (taps() - 1) points; acc_identity: one byte per output
+int EncConvDev::pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity) {
+  (void)hipSetDevice(c->device);
+  const size_t n_out = geom.outputs(), n = n_out * (geom.taps() - 1);
+  DevBuf jac(c), mx(c), my(c), cx(c), cy(c), ai(c), bad(c);
+  if (jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || ai.alloc(n) ||
+      bad.alloc(n_out))
+    return VPIN_ENOMEM;
+  hipLaunchKernelGGL(e2_pool_sums_kernel, dim3(blocks_of(geom.oh * geom.ow, 64), (unsigned)geom.P), dim3(64), 0, c->stream,
+                     (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, e2_geom(geom), e2_curve_a(), (e2_jac*)jac.p,
+                     (uint8_t*)bad.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ai.p);
+  if (rc) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_identity, bad.p, n_out, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+}  // namespace vpin

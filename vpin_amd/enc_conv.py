@@ -1,6 +1,7 @@
-"""The encrypted convolution layer of vPIN's inference server over the C ABI (vpin_enc_conv2d): ciphertext planes and a
-filter in, the output ciphertext and the two gadget operation lists out -- as device instances for vpin_snark_prove_dev, or
-as the witness files the reference's Python service writes, so that the unchanged CLI proves a real layer."""
+"""The encrypted layers of vPIN's inference server over the C ABI (vpin_enc_conv2d, vpin_enc_fc, vpin_enc_avgpool2d):
+ciphertext planes and a filter (or rows and a weight matrix, or a pooling window) in, the output ciphertext and the two gadget
+operation lists out -- as device instances for vpin_snark_prove_dev, or as the witness files the reference's Python service
+writes, so that the unchanged CLI proves a real layer."""
 import json
 import os
 
@@ -25,6 +26,37 @@ def conv_layer(ctx, c1, c2, filt, pad, stride, keys, prf_bytes=16):
     rows = [list(r) for r in filt]
     fh, fw = len(rows), len(rows[0])
     return ctx.enc_conv2d(x, y, inf, x.shape[0] // (H * W), H, W, [int(v) for r in rows for v in r], fh, fw, pad, stride, keys, prf_bytes)
+
+
+def _flat(img):
+    """(x, y, inf) of any leading shape -> x, y (n, 32) and inf (n)"""
+    x, y, inf = img
+    x = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32)
+    y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1, 32)
+    return x, y, (np.zeros(x.shape[0], np.uint8) if inf is None else np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1))
+
+
+def fc_layer(ctx, c1, c2, weights, bias_c1, bias_c2, keys, prf_bytes=16):
+    """c1, c2: the two ciphertext vectors, each (x, y, inf) with x, y of shape (K, 32); weights: K x N array-like of ints
+    below 2^32; bias_c1, bias_c2: the encrypted bias, (x, y, inf) with x, y of shape (N, 32); keys: the c1 row's 32-byte
+    key, then the c2 row's.  Returns the ConvTrace of vpin_enc_fc over the two rows."""
+    rows, bias = [_flat(c1), _flat(c2)], [_flat(bias_c1), _flat(bias_c2)]
+    w = np.asarray(weights, dtype=np.uint64)
+    K, N = w.shape
+    assert all(r[0].shape[0] == K for r in rows) and all(b[0].shape[0] == N for b in bias)
+    cat = lambda parts, i: np.concatenate([p[i] for p in parts])
+    return ctx.enc_fc(cat(rows, 0), cat(rows, 1), cat(rows, 2), 2, K, w, N, cat(bias, 0), cat(bias, 1), cat(bias, 2), keys, prf_bytes)
+
+
+def avgpool_layer(ctx, c1, c2, k, stride, scale=None):
+    """c1, c2 as for conv_layer: (x, y, inf) with x, y of shape (planes, H, W, 32).  scale defaults to the reference's
+    fixed-point 1 / k^2 with 10 fractional bits.  Returns the ConvTrace of vpin_enc_avgpool2d, c1 planes first."""
+    shape = np.asarray(c1[0]).shape
+    assert len(shape) == 4 and np.asarray(c2[0]).shape[1:] == shape[1:], "planes of one H x W"
+    parts = [_flat(c1), _flat(c2)]
+    H, W = shape[1:3]
+    x, y, inf = (np.concatenate([p[i] for p in parts]) for i in range(3))
+    return ctx.enc_avgpool2d(x, y, inf, x.shape[0] // (H * W), H, W, k, stride, 2**10 // (k * k) if scale is None else scale)
 
 
 def write_witness_files(trace, root, label):
