@@ -684,6 +684,52 @@ int vpin_enc_fc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8
 int vpin_enc_avgpool2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
                        size_t k, size_t stride, const uint8_t scale_le16[16], vpin_conv_trace** out);
 
+/* ---- the client side: exponential ElGamal on E2 (key generation, encryption, decryption with a discrete-log table) ------
+ * What the reference's client does around every layer (src/LeNet/Client.py: encrypt, decrypt, bsgs): with the generator G of
+ * prime order n, a key sk and H = sk * G, a signed message m is (c1, c2) = (r * G, m * G + r * H), and
+ * m = log_G(c2 - sk * c1) is found by baby steps / giant steps.  The randomness r and the key are explicit inputs, like the
+ * provers' seeds.  Points cross as in vpin_e2_msm (an identity is written as zeros with flag 1); scalars mod n as 32 bytes
+ * little-endian; messages as int64_t.
+ * VPIN_EINVAL: a null argument, cnt = 0, a scalar >= n (for r and sk also 0), |msg| >= 2^62, a coordinate >= q or a point off
+ * the curve (checked on the device), an identity base point, nb outside 2 .. 2^28, max_giant * nb past 2^62.  VPIN_ENOMEM: a
+ * table does not fit.  vpin_last_error() names the rule.  A table belongs to the context that made it and is freed before it. */
+
+/* window table of one fixed base point B, device-resident: the affine points d * 2^(10 k) * B for every window k and digit d
+ * (1.7 MB), so that s * B is at most 26 mixed additions and no doubling.  x = y = NULL: B = G */
+typedef struct vpin_e2_base vpin_e2_base;
+int vpin_e2_base_create(vpin_ctx* ctx, const uint8_t* x, const uint8_t* y, vpin_e2_base** out);
+/* the same with an explicit window width w in 4 .. 12 (tools/time_e2_client.py measures the widths; 10 is the default) */
+int vpin_e2_base_create_w(vpin_ctx* ctx, const uint8_t* x, const uint8_t* y, int w, vpin_e2_base** out);
+void vpin_e2_base_free(vpin_e2_base* b);
+/* out[i] = s_i * B, 0 <= s_i < n (s_i = 0 gives the flagged identity) */
+int vpin_e2_base_mul(vpin_ctx* ctx, const vpin_e2_base* b, const uint8_t* scalars_le32, size_t cnt, uint8_t* out_x, uint8_t* out_y,
+                     uint8_t* out_inf);
+/* out[i] = s_i * P_i, 0 <= s_i < n, by double-and-add: the variable-base form (decryption multiplies every c1 by sk with it) */
+int vpin_e2_mul256(vpin_ctx* ctx, const uint8_t* scalars_le32, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
+                   uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+/* c1[i] = r_i * G, c2[i] = msg_i * G + r_i * H; baseG / baseH: the tables of G and of the public key H = sk * G
+ * (vpin_e2_base_mul of sk under baseG).  The last addition is complete: c2 may be the identity (flagged).  One launch chain
+ * for all cnt elements */
+int vpin_e2_encrypt(vpin_ctx* ctx, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const int64_t* msgs, const uint8_t* r_le32,
+                    size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+/* the baby steps j * G, 0 <= j < nb, device-resident: 32 bytes of x and a parity byte per entry and an open-addressing index
+ * of 2^ceil(log2(2 nb)) 64-bit slots (49 to 65 bytes per entry in all; 2^24 entries: 0.8 GB).  2 <= nb <= 2^28 */
+typedef struct vpin_e2_dlog vpin_e2_dlog;
+int vpin_e2_dlog_create(vpin_ctx* ctx, uint64_t nb, vpin_e2_dlog** out);
+void vpin_e2_dlog_free(vpin_e2_dlog* t);
+/* out = {nb, device bytes held} */
+int vpin_e2_dlog_info(const vpin_e2_dlog* t, uint64_t out[2]);
+/* v_out[i] = the v with P_i = v * G and |v| <= max_giant * nb + nb - 1, found_out[i] = 1; found_out[i] = 0 (and v_out[i] = 0)
+ * when there is none in that range, which is not an error.  Exact: a hit is confirmed on the full coordinates, never on a
+ * truncated hash.  A step is two affine additions whose inversion the lanes of a workgroup share; a point has up to 64 lanes
+ * that take the giant steps in turn, so the walk is max_giant / 64 to max_giant shared inversions deep */
+int vpin_e2_dlog_solve(vpin_ctx* ctx, const vpin_e2_dlog* t, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
+                       uint64_t max_giant, int64_t* v_out, uint8_t* found_out);
+/* M_i = c2_i - sk * c1_i, then as vpin_e2_dlog_solve */
+int vpin_e2_decrypt(vpin_ctx* ctx, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y,
+                    const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant,
+                    int64_t* v_out, uint8_t* found_out);
+
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's
  * c*Q and blind*H terms are host work: nizk/mod.rs:447-531).  x = the vector being reduced (a in bullet.rs), a = the

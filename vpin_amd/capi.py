@@ -179,6 +179,19 @@ def lib():
     L.vpin_conv_trace_instances.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_enc_conv_last_timings.restype = None
     L.vpin_enc_conv_last_timings.argtypes = [C.POINTER(C.c_double)]
+    L.vpin_e2_base_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.vpin_e2_base_create_w.argtypes = [vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.vpin_e2_base_free.argtypes = [vp]
+    L.vpin_e2_base_free.restype = None
+    L.vpin_e2_base_mul.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_mul256.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_encrypt.argtypes = [vp, vp, vp, vp, vp, C.c_size_t] + [vp] * 6
+    L.vpin_e2_dlog_create.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
+    L.vpin_e2_dlog_free.argtypes = [vp]
+    L.vpin_e2_dlog_free.restype = None
+    L.vpin_e2_dlog_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vpin_e2_dlog_solve.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, vp]
+    L.vpin_e2_decrypt.argtypes = [vp, vp, vp] + [vp] * 6 + [C.c_size_t, C.c_uint64, vp, vp]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]
@@ -1246,6 +1259,97 @@ class Context:
         out = (C.c_double * 8)()
         lib().vpin_enc_conv_last_timings(out)
         return dict(zip(("validate", "conv", "prf", "rlc", "host_tail", "total"), out))
+
+    # ---- the client side: ElGamal on E2 (vpin_amd.elgamal wraps these) ----
+    @staticmethod
+    def _u256s(vals):
+        return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).copy()
+
+    def e2_base_create(self, x=None, y=None, w=None):
+        """window table of the base point (x, y) (Python ints; None: the generator G) -> handle for e2_base_free"""
+        h = C.c_void_p()
+        bx = by = None
+        if x is not None:
+            bx, by = self._u256s([x]), self._u256s([y])
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        if w is None:
+            _chk(lib().vpin_e2_base_create(self.h, p(bx), p(by), C.byref(h)), "vpin_e2_base_create")
+        else:
+            _chk(lib().vpin_e2_base_create_w(self.h, p(bx), p(by), w, C.byref(h)), "vpin_e2_base_create_w")
+        return h
+
+    @staticmethod
+    def e2_base_free(h):
+        lib().vpin_e2_base_free(h)
+
+    def e2_base_mul(self, base, scalars):
+        """scalars[i] * B for Python ints below the group order -> (x, y, inf) arrays"""
+        s = self._u256s(scalars)
+        n = len(scalars)
+        ox, oy, oi = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_base_mul(self.h, base, p(s), n, p(ox), p(oy), p(oi)), "vpin_e2_base_mul")
+        return ox, oy, oi
+
+    def e2_mul256(self, scalars, x, y, inf=None):
+        """scalars[i] * P_i by double-and-add -> (x, y, inf) arrays"""
+        x, y, f = self._points(x, y, inf)
+        s = self._u256s(scalars)
+        n = x.shape[0]
+        assert len(scalars) == n
+        ox, oy, oi = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_mul256(self.h, p(s), p(x), p(y), p(f), n, p(ox), p(oy), p(oi)), "vpin_e2_mul256")
+        return ox, oy, oi
+
+    def e2_encrypt(self, base_g, base_h, msgs, rs):
+        """(c1, c2), each (x, y, inf): c1 = r * G, c2 = msg * G + r * H for signed ints msgs and randomness rs"""
+        m = np.ascontiguousarray(np.array([int(v) for v in msgs], dtype=np.int64))
+        r = self._u256s(rs)
+        n = m.shape[0]
+        assert len(rs) == n
+        out = [np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8),
+               np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_encrypt(self.h, base_g, base_h, p(m), p(r), n, *[p(a) for a in out]), "vpin_e2_encrypt")
+        return tuple(out[:3]), tuple(out[3:])
+
+    def e2_dlog_create(self, nb):
+        h = C.c_void_p()
+        _chk(lib().vpin_e2_dlog_create(self.h, nb, C.byref(h)), "vpin_e2_dlog_create")
+        return h
+
+    @staticmethod
+    def e2_dlog_free(h):
+        lib().vpin_e2_dlog_free(h)
+
+    @staticmethod
+    def e2_dlog_info(h):
+        out = (C.c_uint64 * 2)()
+        _chk(lib().vpin_e2_dlog_info(h, out), "vpin_e2_dlog_info")
+        return int(out[0]), int(out[1])
+
+    def e2_dlog_solve(self, table, x, y, inf, max_giant):
+        """-> (v, found): int64 and uint8 arrays"""
+        x, y, f = self._points(x, y, inf)
+        n = x.shape[0]
+        v, found = np.zeros(n, np.int64), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_dlog_solve(self.h, table, p(x), p(y), p(f), n, max_giant, p(v), p(found)), "vpin_e2_dlog_solve")
+        return v, found
+
+    def e2_decrypt(self, table, sk, c1, c2, max_giant):
+        """c1, c2: (x, y, inf) -> (v, found)"""
+        x1, y1, f1 = self._points(*c1)
+        x2, y2, f2 = self._points(*c2)
+        n = x1.shape[0]
+        assert x2.shape[0] == n
+        k = self._u256s([sk])
+        v, found = np.zeros(n, np.int64), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_decrypt(self.h, table, p(k), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), n, max_giant, p(v), p(found)),
+             "vpin_e2_decrypt")
+        return v, found
 
     # ---- profiling ----
     def prof_enable(self, on=True):

@@ -1,0 +1,54 @@
+// e2_client.h -- the client side of vPIN's exponential ElGamal on E2, device stages (e2_client.hip) as the entry points of
+// e2_client.cpp drive them.  Every stage validates its points on the device (EncConvDev::load: range and curve equation),
+// works on the context's stream and synchronises it before it returns.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "ctx.h"
+
+// window table of one fixed base point B: entry k * (2^w - 1) + d - 1 = d * 2^(w k) * B, affine, Montgomery form
+struct vpin_e2_base {
+  vpin_ctx* owner = nullptr;
+  int w = 0, nwin = 0;
+  void *tx = nullptr, *ty = nullptr;  // device, nwin * (2^w - 1) coordinates each
+};
+
+// baby steps j * G, 0 <= j < nb: the affine x (Montgomery form) and the parity of the canonical y of every entry, and an
+// open-addressing index of `slots` (a power of two >= 2 nb) 64-bit words keyed on x: 0 = empty, else (tag << 32) | j.
+// Entry 0 (the identity) has no coordinates and is not in the index.
+struct vpin_e2_dlog {
+  vpin_ctx* owner = nullptr;
+  uint64_t nb = 0, slots = 0, bytes = 0;
+  void *tx = nullptr, *par = nullptr, *idx = nullptr;
+  void *dmx = nullptr, *dmy = nullptr;  // l * D for l = 1 .. kDlogLanes, D = nb * G the giant step: affine, Montgomery form
+};
+
+namespace vpin {
+namespace client {
+
+constexpr int kDefaultWindow = 10;  // measured against 4, 6, 8 and 12: DESIGN.md section 9
+// the walk gives a point up to this many lanes: lane l visits the giant steps l, l + L, l + 2 L, .. (strides of L * D)
+constexpr int kDlogLanes = 64;
+
+// x, y: the base point, canonical little-endian.  VPIN_EINVAL (through enc::check_flags) when it is not on the curve
+int base_build(vpin_ctx* c, const uint8_t x[32], const uint8_t y[32], int w, vpin_e2_base** out);
+void base_free(vpin_e2_base* b);
+// out[i] = s_i * B (scalars: cnt x 32 bytes little-endian, already checked to be below the group order)
+int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, size_t cnt, uint8_t* ox, uint8_t* oy, uint8_t* oinf);
+// c1[i] = r_i * G, c2[i] = (+-)m_i * G + r_i * H with m_i = |msg_i| as a 32-byte scalar and neg[i] = 1 for a negative message
+int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg,
+            size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+// out[i] = s_i * P_i, or s_0 * P_i for every i when one_scalar
+int mul256(vpin_ctx* c, const uint8_t* scalars_le32, bool one_scalar, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
+           uint8_t* ox, uint8_t* oy, uint8_t* oinf);
+int dlog_build(vpin_ctx* c, uint64_t nb, vpin_e2_dlog** out);
+void dlog_free(vpin_e2_dlog* t);
+int dlog_solve(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt, uint64_t max_giant,
+               int64_t* v_out, uint8_t* found_out);
+int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int64_t* v_out,
+            uint8_t* found_out);
+
+}  // namespace client
+}  // namespace vpin

@@ -1,0 +1,508 @@
+// e2_client.hip -- the client side of vPIN's exponential ElGamal on E2 on the device (driven by e2_client.cpp): fixed-base
+// multiplication from a window table, batched encryption, the 252-bit variable-base multiplication of decryption, and the
+// discrete logarithm of small messages by baby steps / giant steps with the baby-step table resident in HBM.
+//
+//   e2_base_rows_kernel    window table of a base point B: lane k doubles B w k times and adds along the digits d = 1 .. 2^w - 1
+//   e2_base_mul_kernel     s_i * B, one lane per scalar: a mixed addition per non-zero digit, no doubling; optional negation
+//   e2_add_pairs_kernel    A_i + B_i, complete (the last addition of a ciphertext's c2)
+//   e2_mul256_kernel       s_i * P_i (or one s for all): double-and-add over eight shifted words
+//   e2_sub_kernel          C_i - T_i, complete (M = c2 - sk * c1)
+//   e2_dlog_steps_kernel   baby steps: lane l starts at (j0 + l * chunk) * G from G's window table and steps by + G
+//   e2_dlog_insert_kernel  parity of y and the open-addressing index keyed on x (64-bit compare-and-swap)
+//   e2_dlog_walk_kernel    the walkers P - i D and P + i D in AFFINE coordinates: the 256 lanes of a workgroup share one
+//                          inversion per step (e2_block_inverse); every step is looked up by x and confirmed on the stored
+//                          coordinates.  A point has up to 64 lanes, which take the giant steps in turn (the step's latency
+//                          is that one inversion, so a walk is as long as its deepest lane)
+// e2_to_affine_kernel (enc_conv.hip) normalises every output and the baby steps.  As in the layers' kernels the accumulators
+// are named registers: no per-lane arrays.
+#include "e2_dev.h"
+#include "e2_client.h"
+#include "enc_conv.h"
+
+#include <cstring>
+#include <new>
+
+#include "host/field.h"
+
+namespace vpin {
+
+namespace {
+
+constexpr int kStepsBlock = 64;       // lanes of a workgroup of e2_dlog_steps_kernel
+constexpr int kStepsChunk = 64;       // baby steps one lane takes
+constexpr size_t kTile = (size_t)1 << 20;  // baby steps normalised and inserted at a time: bounds the Jacobian scratch (96 MiB)
+
+// grid: one workgroup of 64; lane k < nwin writes the 2^w - 1 entries of window k, Jacobian
+__global__ __launch_bounds__(64) void e2_base_rows_kernel(fq bx, fq by, int w, int nwin, fq a, e2_jac* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= nwin) return;
+  e2_jac p;
+  p.X = bx; p.Y = by; p.Z = fq_one();
+  for (int i = 0; i < k * w; i++) p = e2_dbl(p, a);
+  const size_t m = ((size_t)1 << w) - 1;
+  e2_jac acc = p;
+  for (size_t d = 0; d < m; d++) {
+    e2_store(out + (size_t)k * m + d, acc);
+    acc = e2_add(acc, p, a);
+  }
+}
+
+__global__ __launch_bounds__(kE2Block) void e2_base_mul_kernel(const fq* __restrict__ tx, const fq* __restrict__ ty, int w,
+                                                               const uint32_t* __restrict__ s, const uint8_t* __restrict__ neg, size_t n,
+                                                               fq a, e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  e2_jac acc = e2_mul_base(tx, ty, w, e2_scalar256_load(s + 8 * i), a);
+  if (neg && neg[i]) acc.Y = fq_neg(acc.Y);
+  e2_store(out + i, acc);
+}
+
+__global__ __launch_bounds__(kE2Block) void e2_add_pairs_kernel(const e2_jac* __restrict__ A, const e2_jac* __restrict__ B, size_t n, fq a,
+                                                                e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  e2_store(out + i, e2_add(e2_load(A + i), e2_load(B + i), a));
+}
+
+// stride = 8: a scalar per point; stride = 0: one scalar for all
+__global__ __launch_bounds__(kE2Block) void e2_mul256_kernel(const fq* __restrict__ X, const fq* __restrict__ Y, const uint8_t* __restrict__ inf,
+                                                             const uint32_t* __restrict__ s, size_t stride, size_t n, fq a,
+                                                             e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  e2_jac acc = e2_identity();
+  if (!inf[i]) acc = e2_mul_affine256(fq_load(X + i), fq_load(Y + i), e2_scalar256_load(s + stride * i), a);
+  e2_store(out + i, acc);
+}
+
+// out_i = (X_i, Y_i) - T_i
+__global__ __launch_bounds__(kE2Block) void e2_sub_kernel(const e2_jac* __restrict__ T, const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                          const uint8_t* __restrict__ inf, size_t n, fq a, e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  e2_jac t = e2_load(T + i);
+  t.Y = fq_neg(t.Y);
+  if (!inf[i]) t = e2_add_mixed(t, fq_load(X + i), fq_load(Y + i), a);
+  e2_store(out + i, t);
+}
+
+// out[l * kStepsChunk + t] = (j0 + l * kStepsChunk + t) * G for the n_lanes lanes of one tile
+__global__ __launch_bounds__(kStepsBlock) void e2_dlog_steps_kernel(const fq* __restrict__ gtx, const fq* __restrict__ gty, int w, uint64_t j0,
+                                                                    size_t n_lanes, fq gx, fq gy, fq a, e2_jac* __restrict__ out) {
+  const size_t l = (size_t)blockIdx.x * kStepsBlock + threadIdx.x;
+  if (l >= n_lanes) return;
+  const uint64_t j = j0 + l * kStepsChunk;
+  e2_jac acc = e2_mul_base(gtx, gty, w, e2_scalar256{(uint32_t)j, (uint32_t)(j >> 32), 0u, 0u, 0u, 0u, 0u, 0u}, a);
+  for (int t = 0; t < kStepsChunk; t++) {
+    e2_store(out + l * kStepsChunk + t, acc);
+    acc = e2_add_mixed(acc, gx, gy, a);
+  }
+}
+
+__device__ __forceinline__ uint64_t dlog_slot(const fq& x, uint64_t mask) {
+  return (((uint64_t)(x.v[1] * 0x9e3779b1u) << 32) | x.v[0]) & mask;  // Montgomery limbs of an x coordinate: already spread
+}
+__device__ __forceinline__ uint32_t dlog_tag(const fq& x) { return x.v[2]; }
+
+// entries j0 .. j0 + count of the table (their x is in place): parity of y from the tile's canonical y, and the index
+__global__ __launch_bounds__(kE2Block) void e2_dlog_insert_kernel(const fq* __restrict__ tx, const fq* __restrict__ cy, uint64_t j0, size_t count,
+                                                                  uint8_t* __restrict__ par, unsigned long long* __restrict__ idx,
+                                                                  uint64_t mask) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= count) return;
+  const uint64_t j = j0 + i;
+  if (j == 0) return;  // the identity: a case of the walk, not an entry
+  par[j] = (uint8_t)(cy[i].v[0] & 1u);
+  const fq x = fq_load(tx + j);
+  const unsigned long long e = ((unsigned long long)dlog_tag(x) << 32) | j;
+  for (uint64_t slot = dlog_slot(x, mask);; slot = (slot + 1) & mask)  // load factor <= 1/2: an empty slot exists
+    if (atomicCAS(idx + slot, 0ull, e) == 0ull) break;
+}
+
+// (x, y) == +- j * G for a stored j?  *j_out = +j or -j.  A tag match is confirmed on the full x; the sign is the parity of y
+__device__ __forceinline__ bool dlog_lookup(const fq& x, const fq& y, bool idn, const fq* __restrict__ tx, const uint8_t* __restrict__ par,
+                                            const unsigned long long* __restrict__ idx, uint64_t mask, long long* j_out) {
+  if (idn) { *j_out = 0; return true; }
+  const uint32_t tag = dlog_tag(x);
+  for (uint64_t slot = dlog_slot(x, mask);; slot = (slot + 1) & mask) {
+    const unsigned long long e = idx[slot];
+    if (!e) return false;
+    if ((uint32_t)(e >> 32) != tag) continue;
+    const uint64_t j = e & 0xffffffffull;
+    if (!fq_eq(fq_load(tx + j), x)) continue;
+    const uint32_t p = fq_from_mont(y).v[0] & 1u;
+    *j_out = p == par[j] ? (long long)j : -(long long)j;
+    return true;
+  }
+}
+
+// One affine step W += (ex, ey), split around the shared inversion.  By case, never a division by zero:
+//   0  W is the identity: the sum is (ex, ey)            2  W == (ex, ey): the doubling, lambda = (3 x^2 + a) / (2 y)
+//   1  the chord, lambda = (ey - y) / (ex - x)           3  W == -(ex, ey): the sum is the identity
+struct e2_walker {
+  fq x, y;
+  bool idn;
+};
+
+__device__ __forceinline__ int walk_prepare(const e2_walker& W, const fq& ex, const fq& ey, const fq& a, fq* num, fq* den) {
+  *den = fq_one();
+  *num = fq_zero();
+  if (W.idn) return 0;
+  if (fq_eq(W.x, ex)) {
+    if (!fq_eq(W.y, ey)) return 3;
+    const fq xx = e2_fqm(W.x, W.x);
+    *num = fq_add(fq_add(fq_dbl(xx), xx), a);
+    *den = fq_dbl(W.y);  // not zero: the group has odd order
+    return 2;
+  }
+  *num = fq_sub(ey, W.y);
+  *den = fq_sub(ex, W.x);
+  return 1;
+}
+
+__device__ __forceinline__ void walk_apply(e2_walker& W, const fq& ex, const fq& ey, int kase, const fq& num, const fq& inv_den) {
+  if (kase == 0) { W.x = ex; W.y = ey; W.idn = false; return; }
+  if (kase == 3) { W.idn = true; return; }
+  const fq lam = e2_fqm(num, inv_den);
+  const fq x3 = fq_sub(fq_sub(e2_fqm(lam, lam), W.x), ex);
+  W.y = fq_sub(e2_fqm(lam, fq_sub(W.x, x3)), W.y);
+  W.x = x3;
+}
+
+// v_out[i] = the v with P_i = v * G, |v| <= max_giant * nb + nb - 1.  Giant step i looks up Wm = P - i D (v = i nb +- j) and
+// Wp = P + i D (v = -i nb +- j), D = nb G.  A point has L = 2^lpp_log lanes of one workgroup: lane l starts at P -+ l D (one
+// shared inversion, l D from the table's multiples dmx / dmy) and visits i = l, l + L, l + 2 L, .. by strides of L D, so the
+// walk is max_giant / L shared inversions deep.  The value is unique in range, so whichever lane meets it writes it (the
+// outputs are zeroed before the launch).  Lanes that are done keep feeding a one into the shared inversion until the
+// workgroup votes that all are
+__global__ __launch_bounds__(kE2Block) void e2_dlog_walk_kernel(const fq* __restrict__ X, const fq* __restrict__ Y, const uint8_t* __restrict__ inf,
+                                                                size_t n, const fq* __restrict__ tx, const uint8_t* __restrict__ par,
+                                                                const unsigned long long* __restrict__ idx, uint64_t mask, uint64_t nb,
+                                                                const fq* __restrict__ dmx, const fq* __restrict__ dmy, int lpp_log,
+                                                                uint64_t max_giant, fq a, long long* __restrict__ v_out,
+                                                                uint8_t* __restrict__ found_out) {
+  __shared__ fq tree[2 * kE2Block];
+  __shared__ int pt_done[kE2Block];  // per point of this workgroup: a lane has met the value
+  const int tid = threadIdx.x, lanes = 1 << lpp_log, pt = tid >> lpp_log;
+  const size_t g = (size_t)blockIdx.x * kE2Block + tid, i = g >> lpp_log;
+  uint64_t step = g & (uint64_t)(lanes - 1);  // the giant step this lane is at
+  pt_done[tid] = 0;
+  bool done = i >= n || step > max_giant;
+  long long j = 0;
+  e2_walker Wm, Wp;
+  Wm.x = fq_zero(); Wm.y = fq_zero(); Wm.idn = true;
+  if (!done) { Wm.x = fq_load(X + i); Wm.y = fq_load(Y + i); Wm.idn = inf[i] != 0; }
+  Wp = Wm;
+  fq num_m, den_m, num_p, den_p;
+  int km, kp;
+  // (ex, ey): what this lane adds to Wp and, negated, to Wm: first its offset l D, then the stride L D
+  fq ex = fq_load(dmx + (step ? step - 1 : 0)), ey = fq_load(dmy + (step ? step - 1 : 0));
+  bool first = true;
+  for (;;) {
+    const bool move = !done && (!first || step != 0);  // lane 0 starts on P itself
+    num_m = fq_zero(); den_m = fq_one(); num_p = fq_zero(); den_p = fq_one();
+    km = kp = 0;
+    if (move) {
+      km = walk_prepare(Wm, ex, fq_neg(ey), a, &num_m, &den_m);
+      kp = walk_prepare(Wp, ex, ey, a, &num_p, &den_p);
+    }
+    const fq inv = e2_block_inverse(tree, e2_fqm(den_m, den_p));
+    if (move) {
+      walk_apply(Wm, ex, fq_neg(ey), km, num_m, e2_fqm(inv, den_p));
+      walk_apply(Wp, ex, ey, kp, num_p, e2_fqm(inv, den_m));
+    }
+    if (!done) {
+      const long long far = (long long)(step * nb);
+      bool hit = dlog_lookup(Wm.x, Wm.y, Wm.idn, tx, par, idx, mask, &j);
+      long long v = far + j;
+      if (!hit && step != 0) {
+        hit = dlog_lookup(Wp.x, Wp.y, Wp.idn, tx, par, idx, mask, &j);
+        v = j - far;
+      }
+      if (hit) { v_out[i] = v; found_out[i] = 1; pt_done[pt] = 1; }
+      step += (uint64_t)lanes;
+      if (first) { ex = fq_load(dmx + lanes - 1); ey = fq_load(dmy + lanes - 1); }
+    }
+    first = false;
+    __syncthreads();
+    done = done || pt_done[pt] != 0 || step > max_giant;
+    if (__syncthreads_and(done)) break;
+  }
+}
+
+using vpin_host::Fq;
+
+fq to_fq(const uint8_t* le32) {
+  Fq t;
+  memcpy(t.l, le32, 32);
+  t = t * Fq::r2();
+  fq r;
+  memcpy(r.v, t.l, 32);
+  return r;
+}
+
+// the generator G of E2, canonical little-endian
+const uint8_t kGx[32] = {0x74, 0xa7, 0xeb, 0x7c, 0x9d, 0xce, 0x1e, 0x21, 0x93, 0x6a, 0x35, 0x97, 0x79, 0x50, 0x40, 0x24,
+                         0x72, 0x67, 0xcd, 0xa5, 0x3c, 0xba, 0x65, 0xf5, 0x70, 0xab, 0xb3, 0x3b, 0x6b, 0xfd, 0x15, 0x0a};
+const uint8_t kGy[32] = {0x96, 0xbb, 0x87, 0x62, 0x3d, 0xaf, 0x8a, 0x1f, 0xbe, 0xfd, 0x07, 0xa8, 0x82, 0x88, 0x01, 0x59,
+                         0xc5, 0x7c, 0x0a, 0x85, 0x5b, 0x90, 0x8f, 0xb3, 0x7f, 0x29, 0x12, 0x66, 0xc7, 0x32, 0x83, 0x01};
+
+// Jacobian points -> canonical bytes on the host; synchronises
+int emit(vpin_ctx* c, const e2_jac* jac, size_t n, uint8_t* ox, uint8_t* oy, uint8_t* oinf) {
+  DevBuf mx(c), my(c), cx(c), cy(c), fl(c);
+  if (mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || fl.alloc(n)) return VPIN_ENOMEM;
+  const int rc = e2_to_affine(c, jac, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
+  if (rc) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(ox, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(oy, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(oinf, fl.p, n, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+int launch_base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint32_t* d_s, const uint8_t* d_neg, size_t n, e2_jac* out) {
+  hipLaunchKernelGGL(e2_base_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)b->tx, (const fq*)b->ty, b->w,
+                     d_s, d_neg, n, e2_curve_a(), out);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+// lanes per point, as a power of two: no more than kDlogLanes, than the giant steps there are, or than keeps the launch
+// within what the device holds at once (2 workgroups on each of its 256 compute units)
+int walk_lanes_log(size_t n, uint64_t max_giant) {
+  int l = 0;
+  while ((2 << l) <= client::kDlogLanes && ((uint64_t)2 << l) <= max_giant + 1 && (n << (l + 1)) <= (size_t)2 * 256 * kE2Block) l++;
+  return l;
+}
+
+// the walk over n points resident as Montgomery coordinates
+int run_walk(vpin_ctx* c, const vpin_e2_dlog* t, const fq* X, const fq* Y, const uint8_t* inf, size_t n, uint64_t max_giant, int64_t* v_out,
+             uint8_t* found_out) {
+  DevBuf v(c), f(c);
+  if (v.alloc(n * 8) || f.alloc(n)) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemsetAsync(v.p, 0, n * 8, c->stream));
+  VPIN_HIP_TRY(hipMemsetAsync(f.p, 0, n, c->stream));
+  const int ll = walk_lanes_log(n, max_giant);
+  hipLaunchKernelGGL(e2_dlog_walk_kernel, dim3(blocks_of(n << ll, kE2Block)), dim3(kE2Block), 0, c->stream, X, Y, inf, n, (const fq*)t->tx,
+                     (const uint8_t*)t->par, (const unsigned long long*)t->idx, t->slots - 1, t->nb, (const fq*)t->dmx, (const fq*)t->dmy, ll,
+                     max_giant, e2_curve_a(), (long long*)v.p, (uint8_t*)f.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  VPIN_HIP_TRY(hipMemcpyAsync(v_out, v.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(found_out, f.p, n, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+}  // namespace
+
+namespace client {
+
+void base_free(vpin_e2_base* b) {
+  if (!b) return;
+  dev_free_owned(b->owner, nullptr, b->tx);
+  dev_free_owned(b->owner, nullptr, b->ty);
+  delete b;
+}
+
+int base_build(vpin_ctx* c, const uint8_t x[32], const uint8_t y[32], int w, vpin_e2_base** out) {
+  (void)hipSetDevice(c->device);
+  const uint8_t* bx = x ? x : kGx;
+  const uint8_t* by = x ? y : kGy;
+  EncConvDev d(c);  // the range and curve checks of every loaded point
+  uint32_t flags = 0;
+  const uint8_t not_inf = 0;
+  int rc = d.load(bx, by, &not_inf, 1, &flags);
+  if (rc) return rc;
+  if ((rc = enc::check_flags(flags, "vpin_e2_base_create", "base point"))) return rc;
+  vpin_e2_base* b = new (std::nothrow) vpin_e2_base();
+  if (!b) return VPIN_ENOMEM;
+  b->owner = c;
+  b->w = w;
+  b->nwin = (252 + w - 1) / w;  // the group order has 252 bits
+  const size_t n = (size_t)b->nwin * (((size_t)1 << w) - 1);
+  DevBuf jac(c), cx(c), cy(c), fl(c);
+  if (jac.alloc(n * sizeof(e2_jac)) || cx.alloc(n * 32) || cy.alloc(n * 32) || fl.alloc(n) || dev_alloc(c, n * 32, &b->tx) ||
+      dev_alloc(c, n * 32, &b->ty)) {
+    base_free(b);
+    return VPIN_ENOMEM;
+  }
+  hipLaunchKernelGGL(e2_base_rows_kernel, dim3(1), dim3(64), 0, c->stream, to_fq(bx), to_fq(by), w, b->nwin, e2_curve_a(), (e2_jac*)jac.p);
+  rc = hipGetLastError() == hipSuccess ? VPIN_OK : VPIN_EHIP;
+  // no entry is the identity: the group order is prime and d * 2^(w k) is not a multiple of it
+  if (!rc) rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)b->tx, (fq*)b->ty, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = VPIN_EHIP;
+  if (rc) {
+    base_free(b);
+    return rc;
+  }
+  *out = b;
+  return VPIN_OK;
+}
+
+int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, size_t cnt, uint8_t* ox, uint8_t* oy, uint8_t* oinf) {
+  (void)hipSetDevice(c->device);
+  DevBuf s(c), jac(c);
+  if (s.alloc(cnt * 32) || jac.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(s.p, scalars_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  const int rc = launch_base_mul(c, b, (const uint32_t*)s.p, nullptr, cnt, (e2_jac*)jac.p);
+  if (rc) return rc;
+  return emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
+}
+
+int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg,
+            size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf) {
+  (void)hipSetDevice(c->device);
+  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
+  DevBuf r(c), m(c), ng(c), ct(c), rh(c), mg(c);
+  if (r.alloc(cnt * 32) || m.alloc(cnt * 32) || ng.alloc(cnt) || ct.alloc(2 * cnt * sizeof(e2_jac)) || rh.alloc(cnt * sizeof(e2_jac)) ||
+      mg.alloc(cnt * sizeof(e2_jac)))
+    return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(m.p, m_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(ng.p, neg, cnt, hipMemcpyHostToDevice, c->stream));
+  e2_jac* c1 = (e2_jac*)ct.p;
+  int rc = launch_base_mul(c, g, (const uint32_t*)r.p, nullptr, cnt, c1);
+  if (!rc) rc = launch_base_mul(c, h, (const uint32_t*)r.p, nullptr, cnt, (e2_jac*)rh.p);
+  if (!rc) rc = launch_base_mul(c, g, (const uint32_t*)m.p, (const uint8_t*)ng.p, cnt, (e2_jac*)mg.p);
+  if (rc) return rc;
+  hipLaunchKernelGGL(e2_add_pairs_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)mg.p, (const e2_jac*)rh.p,
+                     cnt, e2_curve_a(), c1 + cnt);
+  VPIN_HIP_TRY(hipGetLastError());
+  DevBuf mx(c), my(c), cx(c), cy(c), fl(c);
+  if (mx.alloc(2 * cnt * 32) || my.alloc(2 * cnt * 32) || cx.alloc(2 * cnt * 32) || cy.alloc(2 * cnt * 32) || fl.alloc(2 * cnt)) return VPIN_ENOMEM;
+  if ((rc = e2_to_affine(c, c1, 2 * cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(c1x, cx.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c1y, cy.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c1inf, fl.p, cnt, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c2x, (const uint8_t*)cx.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c2y, (const uint8_t*)cy.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(c2inf, (const uint8_t*)fl.p + cnt, cnt, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+// T_i = s * P_i over the points loaded in d, Jacobian, not synchronised
+static int launch_mul256(vpin_ctx* c, const EncConvDev& d, const uint32_t* d_s, bool one_scalar, size_t cnt, e2_jac* out) {
+  hipLaunchKernelGGL(e2_mul256_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)d.px.p, (const fq*)d.py.p,
+                     (const uint8_t*)d.pinf.p, d_s, (size_t)(one_scalar ? 0 : 8), cnt, e2_curve_a(), out);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+int mul256(vpin_ctx* c, const uint8_t* scalars_le32, bool one_scalar, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
+           uint8_t* ox, uint8_t* oy, uint8_t* oinf) {
+  (void)hipSetDevice(c->device);
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, cnt, &flags);
+  if (rc) return rc;
+  if ((rc = enc::check_flags(flags, "vpin_e2_mul256", "point"))) return rc;
+  const size_t ns = one_scalar ? 1 : cnt;
+  DevBuf s(c), jac(c);
+  if (s.alloc(ns * 32) || jac.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(s.p, scalars_le32, ns * 32, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_mul256(c, d, (const uint32_t*)s.p, one_scalar, cnt, (e2_jac*)jac.p))) return rc;
+  return emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
+}
+
+void dlog_free(vpin_e2_dlog* t) {
+  if (!t) return;
+  dev_free_owned(t->owner, nullptr, t->tx);
+  dev_free_owned(t->owner, nullptr, t->par);
+  dev_free_owned(t->owner, nullptr, t->idx);
+  dev_free_owned(t->owner, nullptr, t->dmx);
+  dev_free_owned(t->owner, nullptr, t->dmy);
+  delete t;
+}
+
+int dlog_build(vpin_ctx* c, uint64_t nb, vpin_e2_dlog** out) {
+  (void)hipSetDevice(c->device);
+  vpin_e2_dlog* t = new (std::nothrow) vpin_e2_dlog();
+  if (!t) return VPIN_ENOMEM;
+  t->owner = c;
+  t->nb = nb;
+  t->slots = 16;
+  while (t->slots < 2 * nb) t->slots <<= 1;
+  t->bytes = nb * 32 + nb + t->slots * 8 + 2 * kDlogLanes * 32;
+  vpin_e2_base* g = nullptr;
+  int rc = base_build(c, nullptr, nullptr, kDefaultWindow, &g);
+  if (rc) { dlog_free(t); return rc; }
+  struct Guard {
+    vpin_e2_base* g;
+    vpin_e2_dlog* t;
+    ~Guard() { base_free(g); dlog_free(t); }
+  } guard{g, t};
+  const size_t tile = (size_t)(nb < kTile ? (nb + kStepsChunk - 1) / kStepsChunk * kStepsChunk : kTile);
+  DevBuf jac(c), my(c), cx(c), cy(c), fl(c), s(c);
+  if (dev_alloc(c, nb * 32, &t->tx) || dev_alloc(c, nb, &t->par) || dev_alloc(c, t->slots * 8, &t->idx) || jac.alloc(tile * sizeof(e2_jac)) ||
+      my.alloc(tile * 32) || cx.alloc(tile * 32) || cy.alloc(tile * 32) || fl.alloc(tile) || s.alloc(kDlogLanes * 32) ||
+      dev_alloc(c, kDlogLanes * 32, &t->dmx) || dev_alloc(c, kDlogLanes * 32, &t->dmy)) {
+    set_last_error_text("vpin_e2_dlog_create: the baby-step table does not fit the device memory");
+    return VPIN_ENOMEM;
+  }
+  VPIN_HIP_TRY(hipMemsetAsync(t->idx, 0, t->slots * 8, c->stream));
+  VPIN_HIP_TRY(hipMemsetAsync(t->par, 0, nb, c->stream));
+  const fq a = e2_curve_a(), gx = to_fq(kGx), gy = to_fq(kGy);
+  for (uint64_t j0 = 0; j0 < nb; j0 += tile) {
+    const size_t count = (size_t)(nb - j0 < tile ? nb - j0 : tile), lanes = (count + kStepsChunk - 1) / kStepsChunk;
+    hipLaunchKernelGGL(e2_dlog_steps_kernel, dim3(blocks_of(lanes, kStepsBlock)), dim3(kStepsBlock), 0, c->stream, (const fq*)g->tx,
+                       (const fq*)g->ty, g->w, j0, lanes, gx, gy, a, (e2_jac*)jac.p);
+    VPIN_HIP_TRY(hipGetLastError());
+    if ((rc = e2_to_affine(c, (const e2_jac*)jac.p, count, (fq*)t->tx + j0, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
+    hipLaunchKernelGGL(e2_dlog_insert_kernel, dim3(blocks_of(count, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)t->tx, (const fq*)cy.p,
+                       j0, count, (uint8_t*)t->par, (unsigned long long*)t->idx, t->slots - 1);
+    VPIN_HIP_TRY(hipGetLastError());
+  }
+  // the multiples l * D, l = 1 .. kDlogLanes, of the giant step D = nb * G, kept in Montgomery form (l * nb <= 2^34)
+  uint8_t mult_le32[kDlogLanes * 32] = {};
+  for (uint64_t l = 1; l <= (uint64_t)kDlogLanes; l++) {
+    const uint64_t m = l * nb;
+    memcpy(mult_le32 + 32 * (l - 1), &m, 8);
+  }
+  VPIN_HIP_TRY(hipMemcpyAsync(s.p, mult_le32, sizeof(mult_le32), hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_base_mul(c, g, (const uint32_t*)s.p, nullptr, kDlogLanes, (e2_jac*)jac.p))) return rc;
+  if ((rc = e2_to_affine(c, (const e2_jac*)jac.p, kDlogLanes, (fq*)t->dmx, (fq*)t->dmy, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  guard.t = nullptr;
+  *out = t;
+  return VPIN_OK;
+}
+
+int dlog_solve(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt, uint64_t max_giant,
+               int64_t* v_out, uint8_t* found_out) {
+  (void)hipSetDevice(c->device);
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, cnt, &flags);
+  if (rc) return rc;
+  if ((rc = enc::check_flags(flags, "vpin_e2_dlog_solve", "point"))) return rc;
+  return run_walk(c, t, (const fq*)d.px.p, (const fq*)d.py.p, (const uint8_t*)d.pinf.p, cnt, max_giant, v_out, found_out);
+}
+
+int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int64_t* v_out,
+            uint8_t* found_out) {
+  (void)hipSetDevice(c->device);
+  EncConvDev d1(c), d2(c);
+  uint32_t flags = 0;
+  int rc = d1.load(c1x, c1y, c1inf, cnt, &flags);
+  if (rc) return rc;
+  if ((rc = enc::check_flags(flags, "vpin_e2_decrypt", "c1 point"))) return rc;
+  if ((rc = d2.load(c2x, c2y, c2inf, cnt, &flags))) return rc;
+  if ((rc = enc::check_flags(flags, "vpin_e2_decrypt", "c2 point"))) return rc;
+  DevBuf s(c), T(c), M(c), mx(c), my(c), cx(c), cy(c), fl(c);
+  if (s.alloc(32) || T.alloc(cnt * sizeof(e2_jac)) || M.alloc(cnt * sizeof(e2_jac)) || mx.alloc(cnt * 32) || my.alloc(cnt * 32) ||
+      cx.alloc(cnt * 32) || cy.alloc(cnt * 32) || fl.alloc(cnt))
+    return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(s.p, sk_le32, 32, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_mul256(c, d1, (const uint32_t*)s.p, true, cnt, (e2_jac*)T.p))) return rc;
+  hipLaunchKernelGGL(e2_sub_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)T.p, (const fq*)d2.px.p,
+                     (const fq*)d2.py.p, (const uint8_t*)d2.pinf.p, cnt, e2_curve_a(), (e2_jac*)M.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  if ((rc = e2_to_affine(c, (const e2_jac*)M.p, cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
+  return run_walk(c, t, (const fq*)mx.p, (const fq*)my.p, (const uint8_t*)fl.p, cnt, max_giant, v_out, found_out);
+}
+
+}  // namespace client
+
+}  // namespace vpin

@@ -130,7 +130,89 @@ __device__ __forceinline__ e2_jac e2_mul_affine(const fq& x, const fq& y, uint32
   return acc;
 }
 
+// s * (x, y) for a scalar of up to 256 bits (the ElGamal key, a scalar mod the group order): e2_mul_affine's walk with eight
+// shifted words.  A function of its own, so that the 128-bit kernels keep their four scalar registers
+struct e2_scalar256 {
+  uint32_t w0, w1, w2, w3, w4, w5, w6, w7;
+};
+
+__device__ __forceinline__ e2_scalar256 e2_scalar256_load(const uint32_t* __restrict__ p) {
+  const uint4 lo = reinterpret_cast<const uint4*>(p)[0], hi = reinterpret_cast<const uint4*>(p)[1];
+  return e2_scalar256{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+}
+
+__device__ __forceinline__ bool e2_scalar256_is_zero(const e2_scalar256& s) {
+  return !(s.w0 | s.w1 | s.w2 | s.w3 | s.w4 | s.w5 | s.w6 | s.w7);
+}
+
+__device__ __forceinline__ e2_jac e2_mul_affine256(const fq& x, const fq& y, e2_scalar256 s, const fq& a) {
+  e2_jac acc = e2_identity();
+  if (!e2_scalar256_is_zero(s)) {
+    int nb = 256;
+#define VPIN_E2_SHL1() do { s.w7 = (s.w7 << 1) | (s.w6 >> 31); s.w6 = (s.w6 << 1) | (s.w5 >> 31); s.w5 = (s.w5 << 1) | (s.w4 >> 31); \
+                            s.w4 = (s.w4 << 1) | (s.w3 >> 31); s.w3 = (s.w3 << 1) | (s.w2 >> 31); s.w2 = (s.w2 << 1) | (s.w1 >> 31); \
+                            s.w1 = (s.w1 << 1) | (s.w0 >> 31); s.w0 <<= 1; nb--; } while (0)
+    while (!(s.w7 >> 31)) VPIN_E2_SHL1();
+    acc.X = x; acc.Y = y; acc.Z = fq_one();  // the top set bit
+    VPIN_E2_SHL1();
+    for (; nb > 0;) {
+      acc = e2_dbl(acc, a);
+      if (s.w7 >> 31) acc = e2_add_mixed(acc, x, y, a);
+      VPIN_E2_SHL1();
+    }
+#undef VPIN_E2_SHL1
+  }
+  return acc;
+}
+
+// s * B from B's window table (e2_client.hip): entry k * (2^w - 1) + d - 1 is the affine point d * 2^(w k) * B, so the
+// product is one mixed addition per non-zero digit and no doubling.  Stops when the remaining digits are zero; the additions
+// are complete, so a small scalar that lands on acc == +-entry is exact
+__device__ __forceinline__ e2_jac e2_mul_base(const fq* __restrict__ tx, const fq* __restrict__ ty, int w, e2_scalar256 s, const fq& a) {
+  e2_jac acc = e2_identity();
+  const uint32_t mask = (1u << w) - 1u;
+  const int up = 32 - w;
+  for (uint32_t row = 0; !e2_scalar256_is_zero(s); row += mask) {
+    const uint32_t d = s.w0 & mask;
+    if (d) acc = e2_add_mixed(acc, fq_load(tx + row + d - 1), fq_load(ty + row + d - 1), a);
+    s.w0 = (s.w0 >> w) | (s.w1 << up); s.w1 = (s.w1 >> w) | (s.w2 << up); s.w2 = (s.w2 >> w) | (s.w3 << up);
+    s.w3 = (s.w3 >> w) | (s.w4 << up); s.w4 = (s.w4 >> w) | (s.w5 << up); s.w5 = (s.w5 >> w) | (s.w6 << up);
+    s.w6 = (s.w6 >> w) | (s.w7 << up); s.w7 >>= w;
+  }
+  return acc;
+}
+
 constexpr int kE2Block = 256;
+
+// 1 / v for every lane of a workgroup of kE2Block with ONE Fermat inversion: Montgomery's trick as the product tree of
+// e2_to_affine_kernel (up-sweep of products, inverse of the root, down-sweep).  v must not be zero; tree: 2 * kE2Block elements
+// of LDS.  Every lane of the workgroup calls it
+__device__ __forceinline__ fq e2_block_inverse(fq* tree, const fq& v) {
+  const int tid = threadIdx.x;
+  fq_store(&tree[kE2Block + tid], v);
+  __syncthreads();
+  for (int wdt = kE2Block / 2; wdt >= 1; wdt >>= 1) {
+    if (tid < wdt) {
+      const int j = wdt + tid;
+      fq_store(&tree[j], e2_fqm(fq_load(&tree[2 * j]), fq_load(&tree[2 * j + 1])));
+    }
+    __syncthreads();
+  }
+  if (tid == 0) fq_store(&tree[1], e2_fq_inv(fq_load(&tree[1])));
+  __syncthreads();
+  for (int wdt = 1; wdt <= kE2Block / 2; wdt <<= 1) {
+    if (tid < wdt) {
+      const int j = wdt + tid;
+      const fq pi = fq_load(&tree[j]), l = fq_load(&tree[2 * j]), r = fq_load(&tree[2 * j + 1]);
+      fq_store(&tree[2 * j], e2_fqm(pi, r));
+      fq_store(&tree[2 * j + 1], e2_fqm(pi, l));
+    }
+    __syncthreads();
+  }
+  const fq inv = fq_load(&tree[kE2Block + tid]);
+  __syncthreads();  // the next call overwrites the leaves
+  return inv;
+}
 
 // sum of the workgroup's kE2Block points into sh[0]
 __device__ __forceinline__ void e2_block_tree(e2_jac* sh, const e2_jac& mine, const fq& a) {
