@@ -1,7 +1,8 @@
 """Python model of the reference client's exponential ElGamal on E2 (src/LeNet/Client.py: key generation :19-41, encrypt
 :121-132, decrypt and bsgs :182-243) on gadgets_model's e2_add / e2_mul, with the randomness explicit.  The baby-step table is
 the reference's dict {(x, y) of j * G: j} for 0 <= j < m with j = 0 the identity (keyed None here), and the walk is its two
-lock-step walks M - i (m G) and -M - i (m G)."""
+lock-step walks M - i (m G) and -M - i (m G).  It is checked against recorded runs of the reference's own client:
+tests/golden/layer_pins.json (tests/golden/make_layer_pins.py), compared in tests/test_layer_pins.py."""
 import gadgets_model as GM
 
 Q = GM.Q

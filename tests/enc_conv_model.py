@@ -1,6 +1,7 @@
 """Python model of the encrypted convolution layer and its random-linear-combination (RLC) check: the type-1 path of the
-reference service's myConv2d with rLCL / rLCR (src/convolution/Server.py, src/LeNet/Server.py), written from the layer's
-specification (include/vpin_hip.h, vpin_enc_conv2d) on gadgets_model.e2_add / e2_mul, hmac and hashlib.
+reference service's myConv2d with rLCL / rLCR (src/convolution/Server.py, src/LeNet/Server.py) on gadgets_model.e2_add / e2_mul,
+hmac and hashlib.  It is checked against recorded runs of the reference's own functions: tests/golden/layer_pins.json
+(tests/golden/make_layer_pins.py), compared in tests/test_layer_pins.py.
 
 The model is generic over the group it computes in:
   POINTS  the literal one: affine points of E2, None = the identity (one scalar multiplication costs ~10-17 ms)

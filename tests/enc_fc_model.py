@@ -1,6 +1,7 @@
 """Python model of the encrypted fully connected layer with its random-linear-combination (RLC) check and of the encrypted
 average-pooling layer: FCLayer (flag 1) with the type-1 branch of rLCL / rLCR, and myAvgPool2d (type1 = 1, flag = 1) of
-src/LeNet/Server.py, written from the layers' specification (include/vpin_hip.h, vpin_enc_fc and vpin_enc_avgpool2d).
+src/LeNet/Server.py.  Both are checked against recorded runs of the reference's own functions: tests/golden/layer_pins.json
+(tests/golden/make_layer_pins.py), compared in tests/test_layer_pins.py.
 Generic over the group it computes in, like enc_conv_model: POINTS (the literal one) or LOGS (discrete logarithms)."""
 import gadgets_model as GM
 from enc_conv_model import G, ORDER, POINTS, LOGS, ShapeError, VerifyError, log_point, prf, synthetic_logs  # noqa: F401
