@@ -41,6 +41,7 @@ def up_to_date():
 
 def build(force=False, verbose=False):
     if not force and up_to_date():
+        build_devtest(verbose=verbose)
         return LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)
     objs = []
@@ -66,6 +67,7 @@ def build(force=False, verbose=False):
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     build_cli(verbose)
+    build_devtest(force=True, verbose=verbose)
     return LIB_PATH
 
 
@@ -76,6 +78,37 @@ def build_cli(verbose=False):
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "vpin_prove")
     cmd = [hipcc(), "-O2", "-std=c++17", "-pthread", src, "-o", out, "-L", LIB_DIR, "-lvpin_hip", "-Wl,-rpath,$ORIGIN/../lib"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return out
+
+
+DEVTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "devarith", "devarith.hip")
+DEVTEST_LIB = os.path.join(LIB_DIR, "libvpin_devtest.so")
+
+
+def devtest_up_to_date():
+    if not os.path.exists(DEVTEST_LIB):
+        return False
+    t = os.path.getmtime(DEVTEST_LIB)
+    return all(os.path.getmtime(s) <= t for s in [DEVTEST_SRC] + glob.glob(os.path.join(CSRC, "*.h")))
+
+
+def build_devtest(force=False, verbose=False, out=None, csrc=None):
+    """vpin_amd/lib/libvpin_devtest.so: tests/devarith/devarith.hip, one kernel and one launcher per device function of the
+    arithmetic headers, compiled with the product's flags.  Test-only and a library of its own: nothing of it is in
+    libvpin_hip.so or include/vpin_hip.h; it refers to libvpin_hip.so for the host function make_fq_const alone.
+    out / csrc: another output file and another copy of the headers (a mutated copy, to see that the tests notice)."""
+    if out is None and csrc is None and not force and devtest_up_to_date():
+        return DEVTEST_LIB
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError("libvpin_hip.so comes first: the harness links to it for make_fq_const")
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = out or DEVTEST_LIB
+    cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", DEVTEST_SRC, "-o", out,
+           "-I", csrc or CSRC, "-L", LIB_DIR, "-lvpin_hip", "-Wl,-rpath,$ORIGIN"]
+    cmd += os.environ.get("VPIN_HIPCC_FLAGS", "").split()
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

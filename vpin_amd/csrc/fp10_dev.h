@@ -13,6 +13,11 @@
 // bits, odd limbs 25.  Bounds are tracked in units of "1x" = (even < 2^26, odd < 2^25 + 2^17):
 //   fe10_mul(f, g): f <= 4x, g <= 3x  ->  1x.   Column bound: 10 * 2^28 * (19 * 3 * 2^26) = 2^63.15 < 2^64.
 //   fe10_add: bounds add.   fe10_sub(a, b): b <= 1x (it is subtracted from the bias 2p, which is 2x)  ->  bound(a) + 2x.
+//   fe10_from_fp(a): limbs 0..8 are bit slices (1x), limb 9 is bits 230..255 of a, below 2^26: 1x only for a < 2^255.  That is
+//     a second factor of fe10_mul as it stands (<= 3x), but NOT a second operand of fe10_sub: the bias of limb 9 is 2^26 - 2, and
+//     2^26 - 1 taken from it wraps the limb.  fe10_from_fp_1x folds bit 255 into limb 0 (2^255 = 19): 1x for every a < 2^256.
+//     ge10_from_ext uses it, so a ge10 holds 1x coordinates whatever representatives it was made from.
+//   tests/test_gpu_dev_fp10.py pins these bounds on the device, limb by limb.
 #pragma once
 #include "fp_dev.h"
 
@@ -34,7 +39,8 @@ __device__ __forceinline__ fe10 fe10_one() {
   return r;
 }
 
-// any representative a < 2^256 (table entries are weakly reduced): limb 9 takes bits 230..255, up to 26 bits
+// any representative a < 2^256 (table entries are weakly reduced): limb 9 takes bits 230..255, up to 26 bits (2x on that limb:
+// good as a second factor of fe10_mul, too wide for the second operand of fe10_sub)
 __device__ __forceinline__ fe10 fe10_from_fp(const fp& a) {
   fe10 r;
   r.v[0] = a.v[0] & 0x3ffffffu;                                              // bits   0.. 25
@@ -47,6 +53,17 @@ __device__ __forceinline__ fe10 fe10_from_fp(const fp& a) {
   r.v[7] = __builtin_amdgcn_alignbit(a.v[6], a.v[5], 19) & 0x1ffffffu;       //      179..203
   r.v[8] = __builtin_amdgcn_alignbit(a.v[7], a.v[6], 12) & 0x3ffffffu;       //      204..229
   r.v[9] = a.v[7] >> 6;                                                      //      230..255
+  return r;
+}
+
+// the same for a point's coordinate, which fe10_sub may take as its second operand: bit 255 goes to limb 0 as 19, so every
+// limb is 1x (limb 0 < 2^26, limb 1 <= 2^25, limb 9 < 2^25)
+__device__ __forceinline__ fe10 fe10_from_fp_1x(const fp& a) {
+  fe10 r = fe10_from_fp(a);
+  r.v[0] += 19u * (r.v[9] >> 25);
+  r.v[9] &= 0x1ffffffu;
+  r.v[1] += r.v[0] >> 26;
+  r.v[0] &= 0x3ffffffu;
   return r;
 }
 
@@ -239,7 +256,7 @@ __device__ __forceinline__ ge10 ge10_double(const ge10& p) {
 
 __device__ __forceinline__ ge10 ge10_from_ext(const ge_ext& p) {
   ge10 r;
-  r.X = fe10_from_fp(p.X); r.Y = fe10_from_fp(p.Y); r.Z = fe10_from_fp(p.Z); r.T = fe10_from_fp(p.T);
+  r.X = fe10_from_fp_1x(p.X); r.Y = fe10_from_fp_1x(p.Y); r.Z = fe10_from_fp_1x(p.Z); r.T = fe10_from_fp_1x(p.T);
   return r;
 }
 

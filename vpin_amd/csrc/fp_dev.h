@@ -115,7 +115,8 @@ __device__ VPIN_FPMUL_INLINE fp fp_mul(fp a, fp b) {
 
 __device__ __forceinline__ fp fp_sqr(const fp& a) { return fp_mul(a, a); }
 
-// multiply by a small constant (< 2^31)
+// multiply by a small constant (< 2^31).  The carry out of limb 7 is below s, so 38 times it needs up to 37 bits: fp_fold's
+// 32-bit  c * 38u  holds it only below 2^26.7, and the fold is written out here over two limbs
 __device__ __forceinline__ fp fp_mul_small(const fp& a, uint32_t s) {
   fp r;
   uint64_t k = 0;
@@ -125,7 +126,13 @@ __device__ __forceinline__ fp fp_mul_small(const fp& a, uint32_t s) {
     r.v[i] = (uint32_t)k;
     k >>= 32;
   }
-  return fp_fold(r, (uint32_t)k);
+  const uint64_t f = k * 38u;
+  unsigned cy = 0;
+  r.v[0] = __builtin_addc(r.v[0], (uint32_t)f, 0u, &cy);
+  r.v[1] = __builtin_addc(r.v[1], (uint32_t)(f >> 32), cy, &cy);
+#pragma unroll
+  for (int i = 2; i < 8; i++) r.v[i] = __builtin_addc(r.v[i], 0u, cy, &cy);
+  return fp_fold(r, cy);  // a second wrap leaves a value below f: 38 more end it
 }
 
 // canonical representative in [0, p)
@@ -311,6 +318,25 @@ __device__ __noinline__ fp ge_compress(const ge_ext& p) {
   y = fp_select(fp_is_negative(fp_mul(x, z_inv)), fp_neg(y), y);
   fp s = fp_abs(fp_mul(den_inv, fp_sub(p.Z, y)));
   return fp_freeze(s);
+}
+
+// CompressedRistretto::decompress (RFC 9496 4.3.1); false for a non-canonical, negative or off-group encoding
+__device__ __noinline__ bool ge_decompress(const fp& s_in, ge_ext& out) {
+  const fp s = fp_freeze(s_in);
+  bool canonical = true;
+#pragma unroll
+  for (int i = 0; i < 8; i++) canonical = canonical && (s.v[i] == s_in.v[i]);
+  if (!canonical || (s.v[0] & 1u)) return false;
+  const fp one = fp_one();
+  const fp ss = fp_sqr(s), u1 = fp_sub(one, ss), u2 = fp_add(one, ss), u2s = fp_sqr(u2);
+  const fp v = fp_sub(fp_neg(fp_mul(FP_D(), fp_sqr(u1))), u2s);
+  bool sq;
+  const fp invsqrt = fp_invsqrt(fp_mul(v, u2s), &sq);
+  const fp den_x = fp_mul(invsqrt, u2), den_y = fp_mul(fp_mul(invsqrt, den_x), v);
+  const fp x = fp_abs(fp_mul(fp_add(s, s), den_x)), y = fp_mul(u1, den_y), t = fp_mul(x, y);
+  if (!sq || fp_is_negative(t) || fp_is_zero(y)) return false;
+  out.X = x; out.Y = y; out.Z = one; out.T = t;
+  return true;
 }
 
 }  // namespace vpin

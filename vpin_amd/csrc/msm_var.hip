@@ -21,25 +21,6 @@
 
 namespace vpin {
 
-// CompressedRistretto::decompress (RFC 9496 4.3.1); false for a non-canonical, negative or off-group encoding
-__device__ __noinline__ bool ge_decompress(const fp& s_in, ge_ext& out) {
-  const fp s = fp_freeze(s_in);
-  bool canonical = true;
-#pragma unroll
-  for (int i = 0; i < 8; i++) canonical = canonical && (s.v[i] == s_in.v[i]);
-  if (!canonical || (s.v[0] & 1u)) return false;
-  const fp one = fp_one();
-  const fp ss = fp_sqr(s), u1 = fp_sub(one, ss), u2 = fp_add(one, ss), u2s = fp_sqr(u2);
-  const fp v = fp_sub(fp_neg(fp_mul(FP_D(), fp_sqr(u1))), u2s);
-  bool sq;
-  const fp invsqrt = fp_invsqrt(fp_mul(v, u2s), &sq);
-  const fp den_x = fp_mul(invsqrt, u2), den_y = fp_mul(fp_mul(invsqrt, den_x), v);
-  const fp x = fp_abs(fp_mul(fp_add(s, s), den_x)), y = fp_mul(u1, den_y), t = fp_mul(x, y);
-  if (!sq || fp_is_negative(t) || fp_is_zero(y)) return false;
-  out.X = x; out.Y = y; out.Z = one; out.T = t;
-  return true;
-}
-
 constexpr int kVarBlock = 64;  // one wave per workgroup: 16384 points fill the chip
 
 // partial[b] = sum over the block's lanes of s_i * P_i; bad[0] != 0 when a point does not decode.
