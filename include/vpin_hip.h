@@ -473,7 +473,12 @@ size_t vpin_snark_proof_max_bytes(const vpin_r1cs* inst);
  * num_inputs, batch_size = 3, num_ops, num_mem_cells, comm_comb_ops, comm_comb_mem.
  * The generators are sized from the instance's own max nnz (the reference passes a hand-tuned
  * num_non_zero_entries, point_mult.rs:67 / point_addition.rs:70, which must round to the same
- * power of two or its commit asserts, commitments.rs:95). */
+ * power of two or its commit asserts, commitments.rs:95).
+ * Limits: with N = next_pow2(max nnz of A, B, C) and M = max(num_cons, 2 * num_vars), VPIN_ESHAPE when N < 4 or M < 4
+ * (so for every instance of fewer than 3 entries in its fullest matrix, the empty one included).  At N = 1 the reference's
+ * product circuit has no layer to prove; at N = 2 it does produce a proof, which this library does not: the round kernels
+ * start from tables of four.  VPIN_ESHAPE also for a row index >= num_cons or a column index >= 2 * num_vars in any triplet
+ * (Instance::new's InvalidIndex, lib.rs:171-178) and for num_inputs >= num_vars; the context stays usable after each. */
 int vpin_spark_encode(vpin_ctx* ctx, const vpin_r1cs* inst, vpin_spark_decomm** out, uint8_t* comm_out,
                       size_t comm_cap, size_t* comm_len);
 void vpin_spark_decomm_free(vpin_ctx* ctx, vpin_spark_decomm* d);
