@@ -762,6 +762,15 @@ int vpin_host_commit(const char* label, const uint8_t* v_mont, size_t n, const u
  * scalars in Montgomery form, points compressed; VPIN_EVERIFY when a point does not decode */
 int vpin_host_scalar_mul2(const uint8_t a_mont[32], const uint8_t P[32], const uint8_t b_mont[32], const uint8_t Q[32], uint8_t out[32]);
 
+/* self-test of the eq-factored sum-check round the product-circuit prover runs (EqRound, host/prover_common.h), replayed over
+ * given sums and challenges; all scalars in Montgomery form.  rand = the layer's k challenges rho_j, claims / coeffs = npc
+ * (+ 6 when with_dotp) scalars, res = per round 18 slots of 3 scalars: circuit t at slot t (lead != 0: t(0), the x^2
+ * coefficient of t, unused; lead == 0: the sums at x = 0, 2, 3), dot-product half i at slot 12 + i (its sums at x = 0, 2, 3),
+ * r = the k round challenges.  polys_out = per round the compressed cubic (coefficients 0, 2, 3), state_out = per round
+ * e, s, cn after the challenge.  VPIN_ESHAPE for lead != 0 with a zero rho_j. */
+int vpin_host_eq_round(const uint8_t* rand, int k, int npc, int with_dotp, int lead, const uint8_t* claims, const uint8_t* coeffs,
+                       const uint8_t* res, const uint8_t* r, uint8_t* polys_out, uint8_t* state_out);
+
 /* self-test of the pinned-memory mailbox framing used between resident kernels and the host (sequence number + checksum per
  * scalar; a torn or mixed publication is rejected and read again): 0 = as expected */
 int vpin_host_mailbox_selftest(void);

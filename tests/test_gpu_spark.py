@@ -141,10 +141,14 @@ def test_every_region_of_the_snark_is_checked(ctx):
 
 
 @pytest.mark.gpu
-def test_tail_from_8192_pairs_gives_the_same_bytes():
+@pytest.mark.parametrize("tail_pairs,keys", [("8192", ("3_32-mult", "A-add", "A-mult")), ("0", ("3_32-add", "3_32-mult"))],
+                         ids=["8192", "0"])
+def test_tail_from_8192_pairs_gives_the_same_bytes(tail_pairs, keys):
     """VPIN_SPARK_TAIL_PAIRS=8192: the resident tail kernel entered at up to 8192 pairs per circuit, one workgroup per circuit,
     on layers with dot-product halves too (read once per process, hence the child).  Whole SNARKs of conv f=3 and CNN A
-    (2^16 / 2^20 constraints) against the oracle's digests."""
+    (2^16 / 2^20 constraints) against the oracle's digests.
+    VPIN_SPARK_TAIL_PAIRS=0: no resident tail at all, every round one launch and every layer ended by the collect kernel
+    (also the fall-back for a zero challenge), on N = 2^8 and N = 2^17."""
     import json
     import os
     import subprocess
@@ -152,7 +156,6 @@ def test_tail_from_8192_pairs_gives_the_same_bytes():
     here = os.path.dirname(os.path.abspath(__file__))
     with open(os.path.join(here, "golden", "config_digests.json")) as f:
         gold = json.load(f)["cases"]
-    keys = ("3_32-mult", "A-add", "A-mult")
     code = ("import hashlib, sys; sys.path.insert(0, %r); import vpin_amd; from vpin_amd import gadgets as G\n"
             "c = vpin_amd.Context(0)\n"
             "for label, kind in %r:\n"
@@ -161,7 +164,7 @@ def test_tail_from_8192_pairs_gives_the_same_bytes():
             "    r = d.snark_prove(bytes(range(64)), bytes((7 * i + 3) %% 256 for i in range(64)))\n"
             "    print(hashlib.sha256(r['proof']).hexdigest()); d.free()\n"
             "c.close()\n" % (os.path.dirname(here), [(gold[k]["label"], gold[k]["kind"]) for k in keys]))
-    env = dict(os.environ, VPIN_SPARK_TAIL_PAIRS="8192")
+    env = dict(os.environ, VPIN_SPARK_TAIL_PAIRS=tail_pairs)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-len(keys):] == [gold[k]["snark_sha256"] for k in keys]

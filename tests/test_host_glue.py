@@ -65,6 +65,77 @@ def test_mailbox_framing_rejects_torn_and_stale_pieces():
     assert vpin_amd.lib().vpin_host_mailbox_selftest() == 0
 
 
+def test_eq_round_matches_direct_evaluation():
+    """host/prover_common.h EqRound (the round algebra of the product-circuit prover, through vpin_host_eq_round) against
+    direct evaluation in Python integers: per round the cubic it emits must be the interpolation of
+    s_j eq1(rho_j, x) sum_c coeff_c t_c(x) (+ sum_i coeff_i q_i(x) for six dot-product cubics) at x = 0..3, and cn after the
+    round must be sum_c coeff_c t_c(r_j).  Fed t_c(0) and the x^2 coefficient (lead) or the sums at 0, 2, 3 (three-sum).
+    Cases: rho_1 = 1 (1 - rho = 0), a circuit with t(inf) = 0, coeffs 0 and q - 1.  Everything exact."""
+    rng = np.random.default_rng(29)
+    rnd = lambda: int.from_bytes(rng.bytes(40), "little") % M.Q
+    ev = lambda cs, x: M.unipoly_eval(cs, x)
+    k, npc = 4, 3
+    rho = [rnd(), 1, rnd(), rnd()]
+    r = [rnd() for _ in range(k)]
+    coeffs = [0, M.Q - 1, rnd()] + [rnd(), 0, M.Q - 1, rnd(), rnd(), rnd()]
+    # consistent sum-check data: T_j = sum_c coeff_c t_c with (1 - rho_j) T_j(0) + rho_j T_j(1) = T_{j-1}(r_{j-1}) (circuit 1's
+    # linear coefficient is solved for), and sum_i coeff_i (q_i(0) + q_i(1)) = the halves' sum at r_{j-1} (half 5's constant)
+    t, q = [], []
+    for j in range(k):
+        tj = [[rnd(), rnd(), rnd()] for _ in range(npc)]
+        qj = [[rnd(), rnd(), rnd(), rnd()] for _ in range(6)]
+        if j == 2:
+            tj[2][2] = 0  # t(inf) = 0
+        if j > 0:
+            want = sum(coeffs[c] * ev(t[j - 1][c], r[j - 1]) for c in range(npc)) % M.Q
+            tj[1][1] = 0
+            have = sum(coeffs[c] * (tj[c][0] + rho[j] * (tj[c][1] + tj[c][2])) for c in range(npc)) % M.Q
+            tj[1][1] = (want - have) * pow(coeffs[1] * rho[j], -1, M.Q) % M.Q
+            want = sum(coeffs[npc + i] * ev(q[j - 1][i], r[j - 1]) for i in range(6)) % M.Q
+            qj[5][0] = 0
+            have = sum(coeffs[npc + i] * (ev(qj[i], 0) + ev(qj[i], 1)) for i in range(6)) % M.Q
+            qj[5][0] = (want - have) * pow(2 * coeffs[npc + 5], -1, M.Q) % M.Q
+        t.append(tj)
+        q.append(qj)
+    claims = [((1 - rho[0]) * ev(t[0][c], 0) + rho[0] * ev(t[0][c], 1)) % M.Q for c in range(npc)]
+    claims += [(ev(q[0][i], 0) + ev(q[0][i], 1)) % M.Q for i in range(6)]
+    L = vpin_amd.lib()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    for lead in (1, 0):
+        for with_dotp in (0, 1):
+            res = []
+            for j in range(k):
+                slots = [[0, 0, 0] for _ in range(18)]
+                for c in range(npc):
+                    slots[c] = [ev(t[j][c], 0), t[j][c][2], 0] if lead else [ev(t[j][c], x) for x in (0, 2, 3)]
+                for i in range(6):
+                    slots[12 + i] = [ev(q[j][i], x) for x in (0, 2, 3)]
+                res += [v for sl in slots for v in sl]
+            n = npc + 6 * with_dotp
+            a_rho, a_cl, a_co = M.ints_to_table(rho), M.ints_to_table(claims[:n]), M.ints_to_table(coeffs[:n])
+            a_res, a_r = M.ints_to_table(res), M.ints_to_table(r)
+            polys, state = np.zeros((3 * k, 4), dtype=np.uint64), np.zeros((3 * k, 4), dtype=np.uint64)
+            assert L.vpin_host_eq_round(vp(a_rho), k, npc, with_dotp, lead, vp(a_cl), vp(a_co), vp(a_res), vp(a_r), vp(polys), vp(state)) == 0
+            polys, state = M.table_to_ints(polys), M.table_to_ints(state)
+            s = 1
+            for j in range(k):
+                def P(x):
+                    T = sum(coeffs[c] * ev(t[j][c], x) for c in range(npc))
+                    D = sum(coeffs[npc + i] * ev(q[j][i], x) for i in range(6)) if with_dotp else 0
+                    return (s * ((1 - rho[j]) * (1 - x) + rho[j] * x) * T + D) % M.Q
+                cf = M.unipoly_from_evals([P(x) for x in range(4)])
+                assert polys[3 * j:3 * j + 3] == [cf[0], cf[2], cf[3]], (lead, with_dotp, j)
+                assert state[3 * j] == P(r[j]), (lead, with_dotp, j)
+                s = s * ((1 - rho[j]) * (1 - r[j]) + rho[j] * r[j]) % M.Q
+                assert state[3 * j + 1] == s, (lead, with_dotp, j)
+                if lead:
+                    assert state[3 * j + 2] == sum(coeffs[c] * ev(t[j][c], r[j]) for c in range(npc)) % M.Q, (with_dotp, j)
+    # a zero rho_j leaves only the three-sum form
+    a_rho = M.ints_to_table([rho[0], 0, rho[2], rho[3]])
+    out = np.zeros((6 * k, 4), dtype=np.uint64)
+    assert L.vpin_host_eq_round(vp(a_rho), k, npc, 0, 1, vp(a_cl), vp(a_co), vp(a_res), vp(a_r), vp(out[:3 * k]), vp(out[3 * k:])) == -5
+
+
 def test_host_scalar_mul2_matches_oracle():
     """host/curve.h: width-5 NAF scalar multiplication and the shared-doubling a*P + b*Q of the verifier, against the oracle's
     double-and-add on generator-stream points; edge scalars: 0, 1, q - 1, 2^252, runs of ones, a lone top window"""

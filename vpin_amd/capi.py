@@ -148,6 +148,7 @@ def lib():
     L.vpin_host_gens_derive.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.vpin_host_merlin_kat.argtypes = [C.c_char_p, C.c_char_p, vp, C.c_size_t, C.c_char_p, vp, C.c_size_t]
     L.vpin_host_commit.argtypes = [C.c_char_p, vp, C.c_size_t, vp, vp]
+    L.vpin_host_eq_round.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.vpin_gadget_point_add_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_gadget_point_mult_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_dev_instance_free.argtypes = [vp, vp]

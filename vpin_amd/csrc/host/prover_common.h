@@ -261,6 +261,101 @@ static Fq unipoly_eval(const Fq* coeffs, int n, const Fq& r) {
   return eval;
 }
 
+static void append_unipoly(Transcript& tr, const Fq* coeffs, int n) {
+  // AppendToTranscript for UniPoly (unipoly.rs:112-120)
+  tr.append_message("poly", "UniPoly_begin");
+  for (int i = 0; i < n; i++) tr.append_scalar("coeff", coeffs[i]);
+  tr.append_message("poly", "UniPoly_end");
+}
+
+// fold 2^k evaluations with bound_poly_var_bot in reverse challenge order (sparse_mlpoly.rs:104-109)
+static Fq combine_bot(std::vector<Fq> e, const std::vector<Fq>& ch) {
+  size_t n = e.size();
+  for (size_t ii = ch.size(); ii-- > 0;) {
+    n /= 2;
+    for (size_t i = 0; i < n; i++) e[i] = e[2 * i] + ch[ii] * (e[2 * i + 1] - e[2 * i]);
+  }
+  return e[0];
+}
+
+// Montgomery's trick: v[i] <- 1 / v[i] with one inversion.  Every v[i] must be non-zero (the callers test).
+static void fq_batch_invert(Fq* v, size_t n) {
+  if (n == 0) return;
+  std::vector<Fq> pre(n);
+  Fq acc = Fq::one();
+  for (size_t j = 0; j < n; j++) { pre[j] = acc; acc = acc * v[j]; }
+  acc = acc.invert();
+  for (size_t j = n; j-- > 0;) { Fq t = acc * v[j]; v[j] = acc * pre[j]; acc = t; }
+}
+
+// ---- the eq-factored round of prove_cubic_batched (sumcheck.rs:248-425), as spark.cpp's product-circuit prover runs it ----
+// poly_C = eq(rho, .) folded with r_0..r_{j-1} equals s_j * eq(rho_{j..}, .), s_j = prod_{i<j} eq1(rho_i, r_i); at the round's
+// evaluation point x it is s_j * ((1-rho_j) + x (2 rho_j - 1)) * E_{j+1}[i], and the kernels sum E_{j+1}[i] (A_x B_x)[i] only.
+// Leading-coefficient form (lead_ok): per circuit the round's sums are t(0) and the x^2 coefficient of
+// t(x) = sum_i E[i] (A_x B_x)[i]; t(1) follows from the circuit's claim, which the prover knows exactly (the claims are
+// evaluations of the trees it built): with cn = (sum_t coeff_t claim_t) / s the combined quadratic T satisfies
+// cn = (1-rho) T(0) + rho T(1), and cn becomes T(r_j) after the round.  Exact field identities: the same c0, c2, c3 as summing
+// at x = 0, 2, 3.  A zero rho_j (never, for a transcript challenge) takes the three-sum form on the whole layer.
+// Sums arrive in the single-GPU slot order: circuit t at res[3 t ..], dot-product half i at res[3 (kHalfSlot + i) ..], the
+// halves always as the three sums at x = 0, 2, 3 of their cubic.
+constexpr int kHalfSlot = 12;
+struct EqRound {
+  Fq s, cn;
+  std::vector<Fq> rho_inv;  // 1 / rho_j when lead_ok
+  bool lead_ok;
+  // the round in flight, from combine to advance
+  const Fq* rhos;
+  int j;
+  Fq S0, Sinf, T1, cf[4];
+
+  // rand: the layer's k challenges rho_j (they outlive the rounds); claims / coeffs: of the npc product circuits
+  void begin(const Fq* rand, int k, const Fq* claims, const Fq* coeffs, int npc) {
+    rhos = rand; j = 0;
+    s = Fq::one();
+    rho_inv.assign(rand, rand + k);
+    lead_ok = true;
+    for (auto& x : rho_inv) lead_ok = lead_ok && !x.is_zero();
+    if (lead_ok) fq_batch_invert(rho_inv.data(), rho_inv.size());  // one inversion per layer
+    cn = Fq::zero();
+    for (int t = 0; t < npc; t++) cn = cn + claims[t] * coeffs[t];
+  }
+  // the round's cubic (4 coefficients) from its sums; e = the combined claim, dotp: six halves ride along (coeffs[npc + i])
+  const Fq* combine(const Fq* res, const Fq* coeffs, int npc, bool dotp, const Fq& e) {
+    const Fq one = Fq::one(), rho = rhos[j], omr = one - rho;
+    Fq S2 = Fq::zero(), S3 = Fq::zero();
+    S0 = Sinf = T1 = Fq::zero();
+    if (lead_ok) {
+      for (int t = 0; t < npc; t++) { S0 = S0 + res[3 * t] * coeffs[t]; Sinf = Sinf + res[3 * t + 1] * coeffs[t]; }
+      T1 = (cn - omr * S0) * rho_inv[j];
+      const Fq two_inf = Sinf + Sinf, d10 = T1 - S0;
+      S2 = T1 + d10 + two_inf;                               // T(2) = 2 T(1) - T(0) + 2 Tinf
+      S3 = S2 + d10 + two_inf + two_inf;                     // T(3) = 3 T(1) - 2 T(0) + 6 Tinf
+    } else {
+      for (int t = 0; t < npc; t++) { S0 = S0 + res[3 * t] * coeffs[t]; S2 = S2 + res[3 * t + 1] * coeffs[t]; S3 = S3 + res[3 * t + 2] * coeffs[t]; }
+    }
+    const Fq two_rho = rho + rho;
+    Fq c0 = s * omr * S0;
+    Fq c2 = s * (two_rho + rho - one) * S2;                       // (1-rho) + 2(2rho-1) = 3rho - 1
+    Fq c3 = s * (two_rho + two_rho + rho - one - one) * S3;       // (1-rho) + 3(2rho-1) = 5rho - 2
+    if (dotp)
+      for (int i = 0; i < 6; i++) {
+        const Fq* q = res + 3 * (kHalfSlot + i);
+        c0 = c0 + q[0] * coeffs[npc + i]; c2 = c2 + q[1] * coeffs[npc + i]; c3 = c3 + q[2] * coeffs[npc + i];
+      }
+    const Fq evals[4] = {c0, e - c0, c2, c3};
+    unipoly_from_evals(evals, 4, cf);
+    return cf;
+  }
+  // after the challenge r_j: e = the cubic at r_j, cn = T(r_j), s_{j+1}
+  void advance(const Fq& rj, Fq& e) {
+    const Fq one = Fq::one(), rho = rhos[j], omr = one - rho;
+    e = unipoly_eval(cf, 4, rj);
+    if (lead_ok) cn = S0 + rj * ((T1 - S0 - Sinf) + rj * Sinf);   // T(r_j)
+    s = s * (rho * rj + omr * (one - rj));
+    j++;
+  }
+};
+
 // EqPolynomial::evals (dense_mlpoly.rs:78-94) on the host, for the short L / R vectors
 static void host_eq(const Fq* r, size_t ell, Fq* out) {
   out[0] = Fq::one();

@@ -173,13 +173,7 @@ static int zk_sumcheck(vpin_ctx* c, int K, vpin_table** tabs, const Fq& claim, c
   if (factored) {
     tau_inv.assign(tau->begin(), tau->begin() + rounds);
     for (auto& x : tau_inv) lead = lead && !x.is_zero();
-    if (lead) {
-      std::vector<Fq> pre(rounds);
-      Fq acc = f_one;
-      for (int j = 0; j < rounds; j++) { pre[j] = acc; acc = acc * tau_inv[j]; }
-      acc = acc.invert();
-      for (int j = rounds - 1; j >= 0; j--) { Fq t = acc * tau_inv[j]; tau_inv[j] = acc * pre[j]; acc = t; }
-    }
+    if (lead) fq_batch_invert(tau_inv.data(), tau_inv.size());
   }
   Fq cn = claim;  // claim_pr / s_eq: the claim on the quadratic t
   int rc = factored ? vpin::sc_cubic3_launch(c, tabs, pyramid, loc_rounds, 1, nullptr, lead) : vpin::sc_round_launch(c, K, tabs, nullptr);
@@ -406,6 +400,30 @@ int vpin_host_scalar_mul2(const uint8_t a_mont[32], const uint8_t P[32], const u
   const Point joint = Point::mul2(a, p, b, q), apart = p.mul(a) + q.mul(b);
   if (!joint.equals(apart)) return VPIN_EHIP;  // an arithmetic fault of this library, not of the input
   joint.compress(out);
+  return VPIN_OK;
+}
+
+// round-algebra self-test hook: EqRound (host/prover_common.h) replayed over given sums and given challenges
+int vpin_host_eq_round(const uint8_t* rand, int k, int npc, int with_dotp, int lead, const uint8_t* claims, const uint8_t* coeffs,
+                       const uint8_t* res, const uint8_t* r, uint8_t* polys_out, uint8_t* state_out) {
+  if (!rand || !claims || !coeffs || !res || !r || !polys_out || !state_out || k < 1 || npc < 1 || npc > kHalfSlot) return VPIN_EINVAL;
+  const int nclaims = npc + (with_dotp ? 6 : 0);
+  const Fq *rho = reinterpret_cast<const Fq*>(rand), *cl = reinterpret_cast<const Fq*>(claims), *co = reinterpret_cast<const Fq*>(coeffs);
+  const Fq *sums = reinterpret_cast<const Fq*>(res), *ch = reinterpret_cast<const Fq*>(r);
+  Fq* polys = reinterpret_cast<Fq*>(polys_out);
+  Fq* state = reinterpret_cast<Fq*>(state_out);
+  Fq e = Fq::zero();
+  for (int i = 0; i < nclaims; i++) e = e + cl[i] * co[i];
+  EqRound rd;
+  rd.begin(rho, k, cl, co, npc);
+  if (!lead) rd.lead_ok = false;
+  else if (!rd.lead_ok) return VPIN_ESHAPE;  // a zero rho_j: only the three-sum form applies
+  for (int j = 0; j < k; j++) {
+    const Fq* cf = rd.combine(sums + 3 * 18 * (size_t)j, co, npc, with_dotp != 0, e);
+    polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
+    rd.advance(ch[j], e);
+    state[3 * j] = e; state[3 * j + 1] = rd.s; state[3 * j + 2] = rd.cn;
+  }
   return VPIN_OK;
 }
 

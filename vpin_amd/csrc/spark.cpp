@@ -137,24 +137,7 @@ static void append_polycomm(Transcript& tr, const char* label, const std::vector
   tr.append_message(label, "poly_commitment_end");
 }
 
-static void append_unipoly(Transcript& tr, const Fq* coeffs, int n) {
-  // AppendToTranscript for UniPoly (unipoly.rs:112-120)
-  tr.append_message("poly", "UniPoly_begin");
-  for (int i = 0; i < n; i++) tr.append_scalar("coeff", coeffs[i]);
-  tr.append_message("poly", "UniPoly_end");
-}
-
 static void w_scalars(Writer& w, const Fq* v, size_t n) { w.u64(n); for (size_t i = 0; i < n; i++) w.scalar(v[i]); }
-
-// fold 2^k evaluations with bound_poly_var_bot in reverse challenge order (sparse_mlpoly.rs:104-109)
-static Fq combine_bot(std::vector<Fq> e, const std::vector<Fq>& ch) {
-  size_t n = e.size();
-  for (size_t ii = ch.size(); ii-- > 0;) {
-    n /= 2;
-    for (size_t i = 0; i < n; i++) e[i] = e[2 * i] + ch[ii] * (e[2 * i + 1] - e[2 * i]);
-  }
-  return e[0];
-}
 
 // PolyEvalProof::prove with blinds None, blind_Zr None (dense_mlpoly.rs:326-379)
 // z_rows (one proof over several GPUs, split by residue class): this rank's rows rank, rank + world, .. of Z stored densely; Z then
@@ -309,302 +292,16 @@ static void write_batched(Writer& w, const Batched& b) {
 
 static inline size_t pyramid_offset(int ell, int k) { return ((size_t)1 << ell) - ((size_t)2 << (ell - k)); }
 
-struct DotpCtx {  // the six DotProductCircuit halves ride along on layer 0 of the ops forest
-  const vpin_spark_decomm* d;
-  const vpin::fq* comb_derefs;
-  vpin::fq* scratch;
-  Fq claims[6];  // their evaluations (claim_eval_dotp_left/right per matrix)
-};
-
-// pl != nullptr (one proof over several GPUs): `f` holds this rank's circuits only (possibly none: f.ncirc == 0), npc_all is
-// the number of circuits of the whole forest (12 ops / 4 mem); the rounds run on the owned circuits and halves and every
-// per-round result is exchanged (dist_exchange), after which the transcript work below is the same on every rank.
-static int batched_prove(vpin_ctx* c, vpin::SparkForest& f, DotpCtx* dotp, Transcript& tr, Batched& out, std::vector<Fq>& rand,
-                         const DistPlan* pl = nullptr, int npc_all = 0) {
-  const int npc = pl ? npc_all : f.ncirc, ndotp = dotp ? 6 : 0;
-  const bool is_mem = pl && npc_all == 4;
-  const int nl = f.ncirc;                                             // circuits this rank runs
-  const std::vector<int> no_halves;
-  const std::vector<int>& my_halves = pl ? pl->dotp_of[pl->rank] : no_halves;
-  const int ndl = !dotp ? 0 : (pl ? (int)my_halves.size() : 6);       // dot-product halves this rank runs
-  const int* halves = pl ? my_halves.data() : nullptr;
-  static const bool fine = getenv("VPIN_SPARK_TRACE") && atoi(getenv("VPIN_SPARK_TRACE")) >= 2;
-  double t_setup = 0, t_first = 0, t_rounds = 0, t_epi = 0, t_host = 0;
-  auto tl0 = Clock::now();
-  const int num_layers = (int)log2z(f.n);
-  int rc;
-  // host copies of the small top levels
-  const size_t cnt = std::min<size_t>(2 * vpin::kSparkHostTop, f.stride());
-  if (nl && (rc = vpin::spark_fetch_tops(c, &f, cnt))) return rc;
-  std::vector<Fq> tops((size_t)npc * cnt);
-  if (!pl) memcpy(tops.data(), c->h_spark, tops.size() * 32);
-  else if ((rc = dist_exchange(c, *pl, is_mem, false, reinterpret_cast<const Fq*>(c->h_spark), (int)cnt, tops.data(), is_mem ? "mem_tops" : "ops_tops"))) return rc;
-  std::vector<Fq> res_all(3 * (size_t)vpin::kSparkMaxInst), fin_all(6 * (size_t)vpin::kSparkMaxInst), pack(6 * (size_t)vpin::kSparkMaxInst);
-
-  struct TailGuard { vpin_ctx* c; ~TailGuard() { vpin::spark_tail_abort(c); } } tail_guard{c};  // a no-op unless an error return leaves a tail resident
-  out.polys.assign(num_layers, {});
-  out.claims_left.assign(num_layers, {});
-  out.claims_right.assign(num_layers, {});
-  std::vector<Fq> claims(npc + ndotp), coeffs;
-  for (int t = 0; t < npc; t++) claims[t] = tops[(size_t)t * cnt + cnt - 2];  // the root: ProductCircuit::evaluate
-  rand.clear();
-  TableGuard tg(c);
-  const Fq one = Fq::one();
-
-  for (int layer_id = num_layers - 1, o = 0; layer_id >= 0; layer_id--, o++) {
-    const size_t h = f.n >> (layer_id + 1);  // entries of left_vec[layer_id]
-    const int k = (int)log2z(h);             // rounds; rand.size() == k
-    const bool with_dotp = (layer_id == 0 && ndotp > 0);
-    int nclaims = npc;
-    if (with_dotp) {
-      for (int i = 0; i < 6; i++) claims[npc + i] = dotp->claims[i];
-      nclaims += 6;
-    }
-    if (fine) tl0 = Clock::now();
-    coeffs = tr.challenge_vector("rand_coeffs_next_layer", nclaims);
-    Fq e = Fq::zero();
-    for (int i = 0; i < nclaims; i++) e = e + claims[i] * coeffs[i];
-    std::vector<Fq> r(k);
-    std::vector<Fq>& polys = out.polys[o];
-    polys.resize(3 * (size_t)k);
-    std::vector<Fq> cl(npc), cr(npc);
-    const bool on_host = (2 * h <= vpin::kSparkHostTop) && layer_id != 0;
-
-    if (on_host) {
-      // prove_cubic_batched (sumcheck.rs:248-425) as written, on <= 16-entry tables
-      std::vector<Fq> C(h), A((size_t)npc * h), Bv((size_t)npc * h);
-      host_eq(rand.data(), (size_t)k, C.data());
-      for (int t = 0; t < npc; t++) {
-        const Fq* lvl = &tops[(size_t)t * cnt + cnt - 4 * h];  // level of 2h entries
-        memcpy(&A[(size_t)t * h], lvl, h * 32);
-        memcpy(&Bv[(size_t)t * h], lvl + h, h * 32);
-      }
-      size_t len = h;
-      for (int j = 0; j < k; j++) {
-        const size_t half = len / 2;
-        Fq c0 = Fq::zero(), c2 = Fq::zero(), c3 = Fq::zero();
-        for (int t = 0; t < npc; t++) {
-          const Fq* a = &A[(size_t)t * h];
-          const Fq* b = &Bv[(size_t)t * h];
-          Fq e0 = Fq::zero(), e2 = Fq::zero(), e3 = Fq::zero();
-          for (size_t i = 0; i < half; i++) {
-            e0 = e0 + a[i] * b[i] * C[i];
-            Fq a2 = a[half + i] + a[half + i] - a[i], b2 = b[half + i] + b[half + i] - b[i], c2p = C[half + i] + C[half + i] - C[i];
-            e2 = e2 + a2 * b2 * c2p;
-            Fq a3 = a2 + a[half + i] - a[i], b3 = b2 + b[half + i] - b[i], c3p = c2p + C[half + i] - C[i];
-            e3 = e3 + a3 * b3 * c3p;
-          }
-          c0 = c0 + e0 * coeffs[t]; c2 = c2 + e2 * coeffs[t]; c3 = c3 + e3 * coeffs[t];
-        }
-        Fq evals[4] = {c0, e - c0, c2, c3}, cf[4];
-        unipoly_from_evals(evals, 4, cf);
-        append_unipoly(tr, cf, 4);
-        Fq rj = tr.challenge_scalar("challenge_nextround");
-        r[j] = rj;
-        for (int t = 0; t < npc; t++) {
-          Fq* a = &A[(size_t)t * h];
-          Fq* b = &Bv[(size_t)t * h];
-          for (size_t i = 0; i < half; i++) { a[i] = a[i] + rj * (a[half + i] - a[i]); b[i] = b[i] + rj * (b[half + i] - b[i]); }
-        }
-        for (size_t i = 0; i < half; i++) C[i] = C[i] + rj * (C[half + i] - C[i]);
-        e = unipoly_eval(cf, 4, rj);
-        polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
-        len = half;
-      }
-      for (int t = 0; t < npc; t++) { cl[t] = A[(size_t)t * h]; cr[t] = Bv[(size_t)t * h]; }
-    } else {
-      // eq-factored rounds on the device: poly_C = eq(rand, .) folded with r_0..r_{j-1} equals
-      // s_j * eq(rand_{j..}, .), s_j = prod_{i<j} eq1(rand_i, r_i); at the round's evaluation point x it is
-      // s_j*((1-rand_j) + x*(2 rand_j - 1)) * E_{j+1}[i].  The kernel returns sum_i E_{j+1}[i]*(A_x B_x)[i].
-      if (k < 1) return VPIN_ESHAPE;
-      const int ndl_here = with_dotp ? ndl : 0;          // halves this rank runs on this layer
-      const bool runs = nl > 0 || ndl_here > 0;          // a rank without circuits of this forest only follows the transcript
-      vpin_table* pyr = nullptr;
-      if (runs) {
-        if ((rc = vpin_eq_suffix_tables(c, B(rand.data()), k, &pyr))) return rc;
-        tg.add(pyr);
-      }
-      Fq s = one;
-      // Leading-coefficient rounds: per circuit the kernel returns t(0) and the x^2 coefficient of
-      // t(x) = sum_i E[i] (A_x B_x)[i]; t(1) follows from the circuit's claim, which the prover knows exactly
-      // (claims[] are evaluations of the trees it built): with cn = (sum_t coeff_t claim_t) / s the combined
-      // quadratic T satisfies cn = (1-rho) T(0) + rho T(1), and cn becomes T(r_j) after the round.  Exact field
-      // identities: same c0, c2, c3 as summing at x = 0, 2, 3.  A zero rho_j (never, for a transcript
-      // challenge) takes the three-sum kernel for that round.
-      std::vector<Fq> rho_inv(rand.begin(), rand.begin() + k);
-      bool lead_ok = true;
-      for (auto& x : rho_inv) lead_ok = lead_ok && !x.is_zero();
-      if (lead_ok) {  // Montgomery's trick: one inversion per layer
-        std::vector<Fq> pre(k);
-        Fq acc = one;
-        for (int j = 0; j < k; j++) { pre[j] = acc; acc = acc * rho_inv[j]; }
-        acc = acc.invert();
-        for (int j = k - 1; j >= 0; j--) { Fq t = acc * rho_inv[j]; rho_inv[j] = acc * pre[j]; acc = t; }
-      }
-      Fq cn = Fq::zero();
-      for (int t = 0; t < npc; t++) cn = cn + claims[t] * coeffs[t];
-      // Rounds with at most spark_tail_pairs() pairs per circuit are proven by ONE resident launch (spark.hip, persistent
-      // tail): the kernel publishes a round's sums to pinned memory and polls a pinned mailbox for the challenge this
-      // loop derives from the transcript.  Larger rounds take one launch each.
-      const size_t tail_pairs = lead_ok ? vpin::spark_tail_pairs() : 0;
-      if (pl && tail_pairs == 0) {  // the split rounds end in the persistent tail; a zero challenge (never) or VPIN_SPARK_TAIL_PAIRS=0 rules it out
-        vpin::set_last_error("one proof over several GPUs needs the persistent tail rounds", hipErrorUnknown);
-        return VPIN_ESHAPE;
-      }
-      bool tail_on = false;
-      int tail_j0 = 0;
-      const int ninst = nl + ndl_here;  // instances this rank's launches carry
-      if (fine) { auto t = Clock::now(); t_setup += secs(tl0, t); tl0 = t; }
-      for (int j = 0; j < k; j++) {
-        const size_t len = j == 0 ? h : (h >> (j - 1));  // live length before this round's launch
-        const vpin::fq* E = runs ? pyr->d + pyramid_offset(k, j + 1) : nullptr;
-        const uint8_t* rprev = j ? B(&r[j - 1]) : nullptr;
-        if (!tail_on && (h >> (j + 1)) <= tail_pairs) {
-          if (runs && (rc = vpin::spark_tail_launch(c, &f, layer_id, k, j, len, pyr->d, rprev, ndl_here ? dotp->d->N : 0,
-                                                    ndl_here ? dotp->d->vals : nullptr,
-                                                    ndl_here ? dotp->comb_derefs : nullptr, ndl_here ? dotp->scratch : nullptr,
-                                                    halves, ndl_here)))
-            return rc;
-          tail_on = true;
-          tail_j0 = j;
-        }
-        const Fq* res = nullptr;
-        if (tail_on) {
-          if (runs) {
-            if ((rc = vpin::spark_tail_wait(c, j - tail_j0, ninst, nl))) return rc;
-            res = reinterpret_cast<const Fq*>(vpin::spark_tail_sums(c));
-          }
-        } else if (runs) {
-          if ((rc = vpin::spark_prod_round(c, &f, layer_id, len, E, rprev, ndl_here, lead_ok))) return rc;
-          if (ndl_here && (rc = vpin::spark_dotp_round(c, dotp->d->N, dotp->d->vals, dotp->comb_derefs, dotp->scratch, len, j == 1, rprev, halves, ndl_here))) return rc;
-          if ((rc = vpin::spark_wait_flag(c))) return rc;
-          res = reinterpret_cast<const Fq*>(c->h_spark);
-        }
-        if (pl) {
-          // this rank's sums (circuits at slots 0.., halves at slots 12..) -> everyone's, in the single-GPU slot order
-          for (int t = 0; t < nl; t++) memcpy(&pack[3 * (size_t)t], res + 3 * (size_t)t, 96);
-          // (a launch group puts its halves at slots 12.., the persistent tail numbers its instances consecutively)
-          for (int i = 0; i < ndl_here; i++) memcpy(&pack[3 * (size_t)(nl + i)], res + 3 * (size_t)((tail_on ? nl : 12) + i), 96);
-          if ((rc = dist_exchange(c, *pl, is_mem, with_dotp, pack.data(), 3, res_all.data(),
-                                  is_mem ? (tail_on ? "mem_tail_round" : "mem_round") : (tail_on ? "ops_tail_round" : "ops_round"))))
-            return rc;
-          res = res_all.data();
-        }
-        if (fine) { auto t = Clock::now(); (j == 0 ? t_first : t_rounds) += secs(tl0, t); if (k >= 11) fprintf(stderr, " w%.1f", secs(tl0, t) * 1e6); tl0 = t; }
-        const Fq rho = rand[j], omr = one - rho;
-        Fq S0 = Fq::zero(), S2 = Fq::zero(), S3 = Fq::zero(), T1 = Fq::zero(), Sinf = Fq::zero();
-        if (lead_ok) {
-          for (int t = 0; t < npc; t++) { S0 = S0 + res[3 * t] * coeffs[t]; Sinf = Sinf + res[3 * t + 1] * coeffs[t]; }
-          T1 = (cn - omr * S0) * rho_inv[j];
-          const Fq two_inf = Sinf + Sinf, d10 = T1 - S0;
-          S2 = T1 + d10 + two_inf;                               // T(2) = 2 T(1) - T(0) + 2 Tinf
-          S3 = S2 + d10 + two_inf + two_inf;                     // T(3) = 3 T(1) - 2 T(0) + 6 Tinf
-        } else {
-          for (int t = 0; t < npc; t++) { S0 = S0 + res[3 * t] * coeffs[t]; S2 = S2 + res[3 * t + 1] * coeffs[t]; S3 = S3 + res[3 * t + 2] * coeffs[t]; }
-        }
-        const Fq two_rho = rho + rho;
-        Fq c0 = s * omr * S0;
-        Fq c2 = s * (two_rho + rho - one) * S2;                       // (1-rho) + 2(2rho-1) = 3rho - 1
-        Fq c3 = s * (two_rho + two_rho + rho - one - one) * S3;       // (1-rho) + 3(2rho-1) = 5rho - 2
-        if (with_dotp)
-          for (int i = 0; i < 6; i++) {
-            const Fq* q = res + 3 * (12 + i);
-            c0 = c0 + q[0] * coeffs[npc + i]; c2 = c2 + q[1] * coeffs[npc + i]; c3 = c3 + q[2] * coeffs[npc + i];
-          }
-        Fq evals[4] = {c0, e - c0, c2, c3}, cf[4];
-        unipoly_from_evals(evals, 4, cf);
-        append_unipoly(tr, cf, 4);
-        Fq rj = tr.challenge_scalar("challenge_nextround");
-        if (tail_on && runs && j + 1 < k) vpin::spark_tail_reply(c, j - tail_j0, B(&rj));  // the kernel folds while the host finishes the round
-        r[j] = rj;
-        e = unipoly_eval(cf, 4, rj);
-        if (lead_ok) cn = S0 + rj * ((T1 - S0 - Sinf) + rj * Sinf);   // T(r_j)
-        s = s * (rho * rj + omr * (one - rj));
-        polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
-        if (fine) { auto t = Clock::now(); t_host += secs(tl0, t); if (k >= 11) fprintf(stderr, " m%.1f", secs(tl0, t) * 1e6); tl0 = t; }
-      }
-      if (fine && k >= 11) fprintf(stderr, "\n");
-      // final fold of the two live entries per table with r_{k-1}
-      const Fq rl = r[k - 1];
-      if (tail_on) {
-        const Fq* fin = runs ? reinterpret_cast<const Fq*>(vpin::spark_tail_final(c)) : nullptr;
-        if (pl) {
-          for (int t = 0; t < ninst; t++) memcpy(&pack[6 * (size_t)t], fin + 6 * (size_t)t, 192);  // the tail numbers its instances 0..ninst-1
-          if ((rc = dist_exchange(c, *pl, is_mem, with_dotp, pack.data(), 6, fin_all.data(), is_mem ? "mem_finals" : "ops_finals"))) return rc;
-          fin = fin_all.data();  // halves at slots 12.. = npc + i (only the ops forest, npc == 12, carries them)
-        }
-        for (int t = 0; t < npc; t++) {
-          cl[t] = fin[6 * t] + rl * (fin[6 * t + 1] - fin[6 * t]);
-          cr[t] = fin[6 * t + 2] + rl * (fin[6 * t + 3] - fin[6 * t + 2]);
-        }
-        if (with_dotp) {
-          for (int t = 0; t < 3; t++) out.dotp[t].resize(6);
-          for (int i = 0; i < 6; i++)
-            for (int t = 0; t < 3; t++) {
-              const Fq* q = fin + 6 * (npc + i) + 2 * t;
-              out.dotp[t][i] = q[0] + rl * (q[1] - q[0]);
-            }
-        }
-        if (runs) vpin::spark_tail_end(c);
-      } else {
-        if (pl) return VPIN_ESHAPE;
-        if ((rc = vpin::spark_collect(c, &f, layer_id, with_dotp ? dotp->d : nullptr, with_dotp ? dotp->comb_derefs : nullptr,
-                                      with_dotp ? dotp->scratch : nullptr, with_dotp, k >= 2)))
-          return rc;
-        const Fq* res = reinterpret_cast<const Fq*>(c->h_spark);
-        for (int t = 0; t < npc; t++) {
-          cl[t] = res[4 * t] + rl * (res[4 * t + 1] - res[4 * t]);
-          cr[t] = res[4 * t + 2] + rl * (res[4 * t + 3] - res[4 * t + 2]);
-        }
-        if (with_dotp) {
-          const Fq* q = reinterpret_cast<const Fq*>(c->h_spark) + 64;
-          for (int t = 0; t < 3; t++) out.dotp[t].resize(6);
-          for (int i = 0; i < 6; i++)
-            for (int t = 0; t < 3; t++) out.dotp[t][i] = q[6 * i + 2 * t] + rl * (q[6 * i + 2 * t + 1] - q[6 * i + 2 * t]);
-        }
-      }
-    }
-
-    for (int t = 0; t < npc; t++) {
-      tr.append_scalar("claim_prod_left", cl[t]);
-      tr.append_scalar("claim_prod_right", cr[t]);
-    }
-    if (with_dotp)
-      for (int i = 0; i < 6; i++) {
-        tr.append_scalar("claim_dotp_left", out.dotp[0][i]);
-        tr.append_scalar("claim_dotp_right", out.dotp[1][i]);
-        tr.append_scalar("claim_dotp_weight", out.dotp[2][i]);
-      }
-    Fq r_layer = tr.challenge_scalar("challenge_r_layer");
-    for (int t = 0; t < npc; t++) claims[t] = cl[t] + r_layer * (cr[t] - cl[t]);
-    out.claims_left[o] = cl;
-    out.claims_right[o] = cr;
-    std::vector<Fq> ext;
-    ext.reserve(k + 1);
-    ext.push_back(r_layer);
-    ext.insert(ext.end(), r.begin(), r.end());
-    rand.swap(ext);
-    if (fine) { auto t = Clock::now(); t_epi += secs(tl0, t); tl0 = t; }
-  }
-  if (fine)
-    fprintf(stderr, "[spark]   forest of %d x 2^%d: setup %.3f  first result %.3f  later results %.3f  host per-round math %.3f  epilogue %.3f ms\n",
-            npc, num_layers, t_setup * 1e3, t_first * 1e3, t_rounds * 1e3, t_host * 1e3, t_epi * 1e3);
-  return VPIN_OK;
-}
-
-// ---- the same proof with every circuit split by RESIDUE CLASS over a power-of-two world (spark.hip) -----------------
-// `f` is this rank's local forest: all npc circuits, n / W leaves each (local index k <-> global index rank + k W).  A layer
-// of h = 2^k entries per half is h / W = 2^(k - lw) entries locally: the first k - lw rounds run on the device exactly as on
-// one GPU (same launches, same persistent tail, the suffix pyramid of the first k - lw challenges; the rank's eq-factored
-// sums are scaled by eq(rand_lo, rank)), each rank contributes its partial sums and all ranks derive the same challenge;
-// then every local table is one entry, the W entries of each table are gathered and the last lw rounds run on the host.
-// Layers of at most 32 entries are proven on the host from the gathered tree tops, as on one GPU.
-struct StridedDotp {
-  size_t Nloc;                    // N / W
-  const vpin::fq* vals_loc;       // 3 x Nloc: the val slices at the local entries
-  const vpin::fq* comb_loc;       // 6 x Nloc: the derefs slices at the local entries
-  vpin::fq* scratch;              // 18 x Nloc / 4
-  Fq claims[6];
+// The six DotProductCircuit halves ride along on layer 0 of the ops forest.  N leaves per half pair on this rank, vals = the
+// three val slices (3 x N), derefs = the six derefs slices (6 x N): the whole tables, or -- split by residue class -- the
+// rank's local entries.
+struct DotpCtx {
+  const vpin_spark_decomm* d;  // spark_collect reads the source tables through it (one GPU, launch-only end of a layer)
+  size_t N;
+  const vpin::fq* vals;
+  const vpin::fq* derefs;
+  vpin::fq* scratch;           // 18 x N / 4
+  Fq claims[6];                // their evaluations (claim_eval_dotp_left/right per matrix)
 };
 
 // sum over ranks of `cnt` scalars per rank
@@ -620,52 +317,229 @@ static int dist_sum(vpin_ctx* c, const DistPlan& pl, const Fq* mine, size_t cnt,
   return VPIN_OK;
 }
 
-static int batched_prove_strided(vpin_ctx* c, vpin::SparkForest& f, size_t n_global, StridedDotp* dotp, Transcript& tr, Batched& out,
-                                 std::vector<Fq>& rand, const DistPlan& pl, bool is_mem) {
-  const int npc = f.ncirc, ndotp = dotp ? 6 : 0, W = pl.world, lw = pl.lw;
-  const int num_layers = (int)log2z(n_global);
+// Split by residue class: the last cnt entries of every GLOBAL tree (levels of <= cnt / 2 entries) from the ranks' local tops
+static int residue_tops(vpin_ctx* c, vpin::SparkForest& f, const DistPlan& pl, int npc, size_t cnt, const char* tag, std::vector<Fq>& tops) {
+  const int W = pl.world;
+  const size_t cntl = cnt / (size_t)W;
   int rc;
-  const Fq one = Fq::one();
-  // ---- tree tops: the last cnt entries of every GLOBAL tree (levels of <= cnt / 2 entries) from the ranks' local tops ----
-  const size_t cnt = std::min<size_t>(2 * vpin::kSparkHostTop, 2 * n_global), cntl = cnt / (size_t)W;
   if (cntl < 2 || cntl > f.stride()) return VPIN_ESHAPE;
   if ((rc = vpin::spark_fetch_tops(c, &f, cntl))) return rc;
-  std::vector<Fq> tops((size_t)npc * cnt, Fq::zero());
-  {
-    std::vector<Fq> all((size_t)npc * cntl * W);
-    if ((rc = vpin::comm_allgather_ctx(c, c->h_spark, all.data(), (size_t)npc * cntl * 32, is_mem ? "mem_tops" : "ops_tops"))) return rc;
-    for (int t = 0; t < npc; t++) {
-      Fq* g = &tops[(size_t)t * cnt];
-      // levels of m >= W entries: global[i] = local_{i mod W}[i / W]; a level of m entries sits at offset cnt - 2m
-      for (size_t m = cnt / 2; m >= (size_t)W; m >>= 1) {
-        const size_t ml = m / W;
-        for (size_t i = 0; i < m; i++) g[cnt - 2 * m + i] = all[((size_t)(i % W) * npc + t) * cntl + (cntl - 2 * ml) + i / W];
-      }
-      // the levels above: products of the level below (product_tree.rs:18-35)
-      for (size_t m = (size_t)W / 2; m >= 1; m >>= 1)
-        for (size_t i = 0; i < m; i++) g[cnt - 2 * m + i] = g[cnt - 4 * m + i] * g[cnt - 4 * m + m + i];
+  std::vector<Fq> all((size_t)npc * cntl * W);
+  if ((rc = vpin::comm_allgather_ctx(c, c->h_spark, all.data(), (size_t)npc * cntl * 32, tag))) return rc;
+  for (int t = 0; t < npc; t++) {
+    Fq* g = &tops[(size_t)t * cnt];
+    // levels of m >= W entries: global[i] = local_{i mod W}[i / W]; a level of m entries sits at offset cnt - 2m
+    for (size_t m = cnt / 2; m >= (size_t)W; m >>= 1) {
+      const size_t ml = m / W;
+      for (size_t i = 0; i < m; i++) g[cnt - 2 * m + i] = all[((size_t)(i % W) * npc + t) * cntl + (cntl - 2 * ml) + i / W];
     }
+    // the levels above: products of the level below (product_tree.rs:18-35)
+    for (size_t m = (size_t)W / 2; m >= 1; m >>= 1)
+      for (size_t i = 0; i < m; i++) g[cnt - 2 * m + i] = g[cnt - 4 * m + i] * g[cnt - 4 * m + m + i];
   }
+  return VPIN_OK;
+}
+
+// Split by residue class: once every local table is one entry, the W entries of each table are gathered and the last
+// lw rounds of the layer run here.  A, B per product circuit; L, R, W (D[0..2]) per dot-product half.
+struct GatheredTables {
+  std::vector<std::vector<Fq>> A, B, D[3];
+
+  // fin: this rank's entry of every table, cl | cr per circuit and dp[3 i + tb] per half
+  int gather(vpin_ctx* c, int W, int npc, bool with_dotp, const Fq* cl, const Fq* cr, const Fq* dp, const char* tag) {
+    const size_t per_rank = 2 * (size_t)npc + (with_dotp ? 18 : 0);
+    std::vector<Fq> mine(per_rank), all(per_rank * (size_t)W);
+    for (int t = 0; t < npc; t++) { mine[2 * (size_t)t] = cl[t]; mine[2 * (size_t)t + 1] = cr[t]; }
+    if (with_dotp) for (int x = 0; x < 18; x++) mine[2 * (size_t)npc + x] = dp[x];
+    int rc = vpin::comm_allgather_ctx(c, mine.data(), all.data(), per_rank * 32, tag);
+    if (rc) return rc;
+    A.assign(npc, std::vector<Fq>(W)); B.assign(npc, std::vector<Fq>(W));
+    for (int t = 0; t < npc; t++)
+      for (int rk = 0; rk < W; rk++) { A[t][rk] = all[(size_t)rk * per_rank + 2 * t]; B[t][rk] = all[(size_t)rk * per_rank + 2 * t + 1]; }
+    if (with_dotp)
+      for (int tb = 0; tb < 3; tb++) {
+        D[tb].assign(6, std::vector<Fq>(W));
+        for (int i = 0; i < 6; i++)
+          for (int rk = 0; rk < W; rk++) D[tb][i][rk] = all[(size_t)rk * per_rank + 2 * (size_t)npc + 3 * (size_t)i + tb];
+      }
+    return VPIN_OK;
+  }
+  // a round's sums in the kernels' conventions, single-GPU slot order; E = eq(rho_{j+1..}, .), len / 2 entries
+  void round_sums(const Fq* rho_next, bool lead, bool with_dotp, Fq* res) const {
+    const size_t len = A[0].size(), half = len / 2;
+    std::vector<Fq> E(half);
+    host_eq(rho_next, log2z(half), E.data());
+    for (size_t t = 0; t < A.size(); t++) {
+      Fq a0 = Fq::zero(), a1 = Fq::zero(), a2 = Fq::zero();
+      for (size_t i = 0; i < half; i++) {
+        const Fq A0 = A[t][i], dA = A[t][i + half] - A0, B0 = B[t][i], dB = B[t][i + half] - B0;
+        if (lead) {
+          a0 = a0 + E[i] * (A0 * B0);
+          a1 = a1 + E[i] * (dA * dB);
+        } else {
+          const Fq A2 = A0 + dA + dA, B2 = B0 + dB + dB, A3 = A2 + dA, B3 = B2 + dB;
+          a0 = a0 + E[i] * (A0 * B0); a1 = a1 + E[i] * (A2 * B2); a2 = a2 + E[i] * (A3 * B3);
+        }
+      }
+      res[3 * t] = a0; res[3 * t + 1] = a1; res[3 * t + 2] = a2;
+    }
+    if (with_dotp)
+      for (int i = 0; i < 6; i++) {
+        Fq q0 = Fq::zero(), q2 = Fq::zero(), q3 = Fq::zero();
+        for (size_t x = 0; x < half; x++) {
+          Fq v0[3], v2[3], v3[3];
+          for (int tb = 0; tb < 3; tb++) {
+            const Fq p = D[tb][i][x], d = D[tb][i][x + half] - p;
+            v0[tb] = p; v2[tb] = p + d + d; v3[tb] = v2[tb] + d;
+          }
+          q0 = q0 + v0[0] * v0[1] * v0[2]; q2 = q2 + v2[0] * v2[1] * v2[2]; q3 = q3 + v3[0] * v3[1] * v3[2];
+        }
+        Fq* q = res + 3 * (size_t)(kHalfSlot + i);
+        q[0] = q0; q[1] = q2; q[2] = q3;
+      }
+  }
+  // bound_poly_var_top
+  void fold(const Fq& rj, bool with_dotp) {
+    auto f1 = [&](std::vector<Fq>& T) {
+      const size_t half = T.size() / 2;
+      for (size_t i = 0; i < half; i++) T[i] = T[i] + rj * (T[i + half] - T[i]);
+      T.resize(half);
+    };
+    for (size_t t = 0; t < A.size(); t++) { f1(A[t]); f1(B[t]); }
+    if (with_dotp) for (int tb = 0; tb < 3; tb++) for (int i = 0; i < 6; i++) f1(D[tb][i]);
+  }
+};
+
+// A layer of at most kSparkHostTop entries: prove_cubic_batched (sumcheck.rs:248-425) as written, on the tree tops.
+// (The residue-class prover once summed with cc = s * eq(rand_j.., .) instead of folding C: the same field elements, since
+// eq(rand, (x0, rest)) folded at r0 is eq1(rand_0, r0) * eq(rand_1.., rest).)
+static void host_layer(Transcript& tr, const std::vector<Fq>& tops, size_t cnt, int npc, size_t h, int k, const std::vector<Fq>& rand,
+                       const std::vector<Fq>& coeffs, Fq e, Fq* r, Fq* polys, Fq* cl, Fq* cr) {
+  std::vector<Fq> C(h), A((size_t)npc * h), Bv((size_t)npc * h);
+  host_eq(rand.data(), (size_t)k, C.data());
+  for (int t = 0; t < npc; t++) {
+    const Fq* lvl = &tops[(size_t)t * cnt + cnt - 4 * h];  // level of 2h entries
+    memcpy(&A[(size_t)t * h], lvl, h * 32);
+    memcpy(&Bv[(size_t)t * h], lvl + h, h * 32);
+  }
+  size_t len = h;
+  for (int j = 0; j < k; j++) {
+    const size_t half = len / 2;
+    Fq c0 = Fq::zero(), c2 = Fq::zero(), c3 = Fq::zero();
+    for (int t = 0; t < npc; t++) {
+      const Fq* a = &A[(size_t)t * h];
+      const Fq* b = &Bv[(size_t)t * h];
+      Fq e0 = Fq::zero(), e2 = Fq::zero(), e3 = Fq::zero();
+      for (size_t i = 0; i < half; i++) {
+        e0 = e0 + a[i] * b[i] * C[i];
+        Fq a2 = a[half + i] + a[half + i] - a[i], b2 = b[half + i] + b[half + i] - b[i], c2p = C[half + i] + C[half + i] - C[i];
+        e2 = e2 + a2 * b2 * c2p;
+        Fq a3 = a2 + a[half + i] - a[i], b3 = b2 + b[half + i] - b[i], c3p = c2p + C[half + i] - C[i];
+        e3 = e3 + a3 * b3 * c3p;
+      }
+      c0 = c0 + e0 * coeffs[t]; c2 = c2 + e2 * coeffs[t]; c3 = c3 + e3 * coeffs[t];
+    }
+    Fq evals[4] = {c0, e - c0, c2, c3}, cf[4];
+    unipoly_from_evals(evals, 4, cf);
+    append_unipoly(tr, cf, 4);
+    Fq rj = tr.challenge_scalar("challenge_nextround");
+    r[j] = rj;
+    for (int t = 0; t < npc; t++) {
+      Fq* a = &A[(size_t)t * h];
+      Fq* b = &Bv[(size_t)t * h];
+      for (size_t i = 0; i < half; i++) { a[i] = a[i] + rj * (a[half + i] - a[i]); b[i] = b[i] + rj * (b[half + i] - b[i]); }
+    }
+    for (size_t i = 0; i < half; i++) C[i] = C[i] + rj * (C[half + i] - C[i]);
+    e = unipoly_eval(cf, 4, rj);
+    polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
+    len = half;
+  }
+  for (int t = 0; t < npc; t++) { cl[t] = A[(size_t)t * h]; cr[t] = Bv[(size_t)t * h]; }
+}
+
+// The two live entries of every table after the last device round (spark_tail_final's layout: 6 scalars per instance, the
+// halves from instance `hs` on) bound with that round's challenge: cl | cr per circuit, dp[3 i + tb] per half
+static void bind_finals(const Fq* fin, const Fq& rl, int npc, bool with_dotp, int hs, Fq* cl, Fq* cr, Fq* dp) {
+  for (int t = 0; t < npc; t++) {
+    cl[t] = fin[6 * t] + rl * (fin[6 * t + 1] - fin[6 * t]);
+    cr[t] = fin[6 * t + 2] + rl * (fin[6 * t + 3] - fin[6 * t + 2]);
+  }
+  if (with_dotp)
+    for (int i = 0; i < 6; i++)
+      for (int tb = 0; tb < 3; tb++) {
+        const Fq* q = fin + 6 * (hs + i) + 2 * tb;
+        dp[3 * i + tb] = q[0] + rl * (q[1] - q[0]);
+      }
+}
+
+// One prover for the three ways a forest of npc circuits (12 ops / 4 mem) of n leaves each is held:
+//   one GPU (pl == nullptr): `f` is the whole forest.
+//   by circuit (pl, pl->lw == 0): `f` holds this rank's circuits only (possibly none: f.ncirc == 0) and the rank runs its own
+//     dot-product halves; every per-round result is exchanged (dist_exchange).  A rank without circuits of this forest
+//     only follows the transcript.
+//   by residue class (pl->lw > 0, a power-of-two world W): `f` is this rank's local forest, all npc circuits with n / W leaves
+//     each (local index i <-> global index rank + i W).  A layer of h = 2^k entries per half is 2^(k - lw) entries locally:
+//     the first k - lw rounds run on the device exactly as on one GPU (same launches, same persistent tail, the suffix
+//     pyramid of the first k - lw challenges), the rank's eq-factored sums are scaled by eq(rand_lo, rank) and added up over
+//     the ranks (dist_sum); then every local table is one entry, the W entries of each table are gathered and the last lw
+//     rounds run on the host (GatheredTables).
+// The modes differ only in where a round's sums and a layer's final entries come from; the transcript work is the same on
+// every rank.  Layers of at most kSparkHostTop entries are proven on the host from the tree tops (host_layer).
+//
+// Slot convention.  Everything the round algebra reads, and every exchanged or summed buffer, is in the single-GPU slot
+// order: circuit t at slot t, dot-product half i at slot kHalfSlot + i (3 scalars per slot for a round's sums, 6 for the
+// final entries).  A launch group (spark_prod_round + spark_dotp_round) writes h_spark in that order, a rank's own halves at
+// kHalfSlot, kHalfSlot + 1, ..; the persistent tail numbers the instances it runs consecutively, circuits 0..nl-1 and the
+// halves from nl on (the same thing on one GPU, where nl == 12 whenever halves ride along).  dist_exchange takes a rank's
+// instances packed consecutively (circuits, then halves) and returns the slot order; the residue split sums slot-ordered buffers.
+static int product_prove(vpin_ctx* c, vpin::SparkForest& f, int npc, DotpCtx* dotp, Transcript& tr, Batched& out, std::vector<Fq>& rand,
+                         const DistPlan* pl) {
+  const int ndotp = dotp ? 6 : 0, lw = pl ? pl->lw : 0;
+  const bool by_circuit = pl && lw == 0, by_residue = lw > 0, is_mem = npc == 4;
+  const size_t n = f.n << lw;                                         // leaves of a whole circuit
+  const int nl = f.ncirc;                                             // circuits this rank runs
+  const std::vector<int> no_halves;
+  const std::vector<int>& my_halves = by_circuit ? pl->dotp_of[pl->rank] : no_halves;
+  const int ndl = !dotp ? 0 : (by_circuit ? (int)my_halves.size() : 6);  // dot-product halves this rank runs
+  const int* halves = by_circuit ? my_halves.data() : nullptr;
+  static const bool fine = getenv("VPIN_SPARK_TRACE") && atoi(getenv("VPIN_SPARK_TRACE")) >= 2;
+  double t_setup = 0, t_first = 0, t_rounds = 0, t_epi = 0, t_host = 0;
+  auto tl0 = Clock::now();
+  const int num_layers = (int)log2z(n);
+  int rc;
+  // host copies of the small top levels: the last cnt entries of every tree
+  const size_t cnt = std::min<size_t>(2 * vpin::kSparkHostTop, 2 * n);
+  std::vector<Fq> tops((size_t)npc * cnt, Fq::zero());
+  const char* tops_tag = is_mem ? "mem_tops" : "ops_tops";
+  if (by_residue) {
+    if ((rc = residue_tops(c, f, *pl, npc, cnt, tops_tag, tops))) return rc;
+  } else {
+    if (nl && (rc = vpin::spark_fetch_tops(c, &f, cnt))) return rc;
+    if (!pl) memcpy(tops.data(), c->h_spark, tops.size() * 32);
+    else if ((rc = dist_exchange(c, *pl, is_mem, false, reinterpret_cast<const Fq*>(c->h_spark), (int)cnt, tops.data(), tops_tag))) return rc;
+  }
+  std::vector<Fq> res_all(3 * (size_t)vpin::kSparkMaxInst), fin_all(6 * (size_t)vpin::kSparkMaxInst), pack(6 * (size_t)vpin::kSparkMaxInst);
+
+  struct TailGuard { vpin_ctx* c; ~TailGuard() { vpin::spark_tail_abort(c); } } tail_guard{c};  // a no-op unless an error return leaves a tail resident
   out.polys.assign(num_layers, {});
   out.claims_left.assign(num_layers, {});
   out.claims_right.assign(num_layers, {});
   std::vector<Fq> claims(npc + ndotp), coeffs;
-  for (int t = 0; t < npc; t++) claims[t] = tops[(size_t)t * cnt + cnt - 2];
+  for (int t = 0; t < npc; t++) claims[t] = tops[(size_t)t * cnt + cnt - 2];  // the root: ProductCircuit::evaluate
   rand.clear();
   TableGuard tg(c);
-  struct TailGuard { vpin_ctx* c; ~TailGuard() { vpin::spark_tail_abort(c); } } tail_guard{c};
-  const int ninst = npc + ndotp;
-  std::vector<Fq> res((size_t)3 * vpin::kSparkMaxInst), mine((size_t)6 * vpin::kSparkMaxInst), fin((size_t)6 * vpin::kSparkMaxInst);
+  EqRound rd;
 
   for (int layer_id = num_layers - 1, o = 0; layer_id >= 0; layer_id--, o++) {
-    const size_t h = n_global >> (layer_id + 1);
-    const int k = (int)log2z(h);
+    const size_t h = n >> (layer_id + 1);    // entries of left_vec[layer_id]
+    const int k = (int)log2z(h);             // rounds; rand.size() == k
     const bool with_dotp = (layer_id == 0 && ndotp > 0);
     int nclaims = npc;
     if (with_dotp) {
       for (int i = 0; i < 6; i++) claims[npc + i] = dotp->claims[i];
       nclaims += 6;
     }
+    if (fine) tl0 = Clock::now();
     coeffs = tr.challenge_vector("rand_coeffs_next_layer", nclaims);
     Fq e = Fq::zero();
     for (int i = 0; i < nclaims; i++) e = e + claims[i] * coeffs[i];
@@ -673,237 +547,165 @@ static int batched_prove_strided(vpin_ctx* c, vpin::SparkForest& f, size_t n_glo
     std::vector<Fq>& polys = out.polys[o];
     polys.resize(3 * (size_t)k);
     std::vector<Fq> cl(npc), cr(npc);
+    Fq dp[18];  // the halves' final entries, dp[3 i + tb]
     const bool on_host = (2 * h <= vpin::kSparkHostTop) && layer_id != 0;
-    // host tables of the layer: product circuits A, B; dot-product halves L, R, W (filled from the tops or from the gather)
-    std::vector<std::vector<Fq>> HA(npc), HB(npc), HD[3];
-    int j_host = 0;  // first round that runs on the host tables
-    Fq s = one, cn = Fq::zero();
-    std::vector<Fq> rho_inv(rand.begin(), rand.begin() + k);
-    bool lead_ok = !on_host;
-    for (auto& x : rho_inv) lead_ok = lead_ok && !x.is_zero();
-    if (lead_ok && k > 0) {
-      std::vector<Fq> pre(k);
-      Fq acc = one;
-      for (int j = 0; j < k; j++) { pre[j] = acc; acc = acc * rho_inv[j]; }
-      acc = acc.invert();
-      for (int j = k - 1; j >= 0; j--) { Fq t = acc * rho_inv[j]; rho_inv[j] = acc * pre[j]; acc = t; }
-    }
-    for (int t = 0; t < npc; t++) cn = cn + claims[t] * coeffs[t];
 
-    vpin_table* pyr = nullptr;
-    int kl = 0;           // device rounds
-    bool tail_on = false;
-    int tail_j0 = 0;
-    Fq c_rank = one;
     if (on_host) {
-      for (int t = 0; t < npc; t++) {
-        const Fq* lvl = &tops[(size_t)t * cnt + cnt - 4 * h];
-        HA[t].assign(lvl, lvl + h);
-        HB[t].assign(lvl + h, lvl + 2 * h);
-      }
+      host_layer(tr, tops, cnt, npc, h, k, rand, coeffs, e, r.data(), polys.data(), cl.data(), cr.data());
     } else {
-      kl = k - lw;
-      if (kl < 1 || !lead_ok) {
+      const int kl = k - lw;                             // rounds on the device
+      const size_t hl = h >> lw;                         // entries per half on this rank
+      if (by_residue && kl < 1) {  // (a zero challenge is refused with the tail below)
         vpin::set_last_error("split by residue class: layer too small for the world, or a zero challenge", hipErrorUnknown);
         return VPIN_ESHAPE;
       }
-      j_host = kl;
-      if ((rc = vpin_eq_suffix_tables(c, B(rand.data()), kl, &pyr))) return rc;
-      tg.add(pyr);
-      std::vector<Fq> eq_lo((size_t)W);
-      host_eq(rand.data() + kl, (size_t)lw, eq_lo.data());
-      c_rank = eq_lo[pl.rank];
+      if (k < 1) return VPIN_ESHAPE;
+      const int ndl_here = with_dotp ? ndl : 0;          // halves this rank runs on this layer
+      const bool runs = nl > 0 || ndl_here > 0;          // a rank without circuits of this forest only follows the transcript
+      vpin_table* pyr = nullptr;
+      if (runs) {
+        if ((rc = vpin_eq_suffix_tables(c, B(rand.data()), kl, &pyr))) return rc;
+        tg.add(pyr);
+      }
+      rd.begin(rand.data(), k, claims.data(), coeffs.data(), npc);
+      Fq c_rank = Fq::one();  // by residue: eq(rand_lo, rank), the scale of this rank's eq-factored sums
+      if (by_residue) {
+        std::vector<Fq> eq_lo((size_t)pl->world);
+        host_eq(rand.data() + kl, (size_t)lw, eq_lo.data());
+        c_rank = eq_lo[pl->rank];
+      }
+      // Rounds with at most spark_tail_pairs() pairs per circuit are proven by ONE resident launch (spark.hip, persistent
+      // tail): the kernel publishes a round's sums to pinned memory and polls a pinned mailbox for the challenge this
+      // loop derives from the transcript.  Larger rounds take one launch each.
+      const size_t tail_pairs = rd.lead_ok ? vpin::spark_tail_pairs() : 0;
+      if (pl && tail_pairs == 0) {  // the split rounds end in the persistent tail; a zero challenge (never) or VPIN_SPARK_TAIL_PAIRS=0 rules it out
+        vpin::set_last_error("one proof over several GPUs needs the persistent tail rounds", hipErrorUnknown);
+        return VPIN_ESHAPE;
+      }
+      bool tail_on = false;
+      int tail_j0 = 0;
+      const int ninst = nl + ndl_here;  // instances this rank's launches carry
+      GatheredTables gt;
+      if (fine) { auto t = Clock::now(); t_setup += secs(tl0, t); tl0 = t; }
+      for (int j = 0; j < k; j++) {
+        const Fq* res = nullptr;
+        if (j < kl) {
+          // ---- a device round on this rank's tables ----
+          const size_t len = j == 0 ? hl : (hl >> (j - 1));  // live length before this round's launch
+          const uint8_t* rprev = j ? B(&r[j - 1]) : nullptr;
+          if (!tail_on && (hl >> (j + 1)) <= tail_pairs) {
+            if (runs && (rc = vpin::spark_tail_launch(c, &f, layer_id, kl, j, len, pyr->d, rprev, ndl_here ? dotp->N : 0,
+                                                      ndl_here ? dotp->vals : nullptr, ndl_here ? dotp->derefs : nullptr,
+                                                      ndl_here ? dotp->scratch : nullptr, halves, ndl_here)))
+              return rc;
+            tail_on = true;
+            tail_j0 = j;
+          }
+          if (tail_on) {
+            if (runs) {
+              if ((rc = vpin::spark_tail_wait(c, j - tail_j0, ninst, nl))) return rc;
+              res = reinterpret_cast<const Fq*>(vpin::spark_tail_sums(c));
+            }
+          } else if (runs) {
+            const vpin::fq* E = pyr->d + pyramid_offset(kl, j + 1);
+            if ((rc = vpin::spark_prod_round(c, &f, layer_id, len, E, rprev, ndl_here, rd.lead_ok))) return rc;
+            if (ndl_here && (rc = vpin::spark_dotp_round(c, dotp->N, dotp->vals, dotp->derefs, dotp->scratch, len, j == 1, rprev, halves, ndl_here))) return rc;
+            if ((rc = vpin::spark_wait_flag(c))) return rc;
+            res = reinterpret_cast<const Fq*>(c->h_spark);
+          }
+          const int hs = tail_on ? nl : kHalfSlot;  // where this rank's halves start in res
+          if (by_circuit) {
+            // this rank's sums, packed -> everyone's, in the slot order
+            for (int t = 0; t < nl; t++) memcpy(&pack[3 * (size_t)t], res + 3 * (size_t)t, 96);
+            for (int i = 0; i < ndl_here; i++) memcpy(&pack[3 * (size_t)(nl + i)], res + 3 * (size_t)(hs + i), 96);
+            if ((rc = dist_exchange(c, *pl, is_mem, with_dotp, pack.data(), 3, res_all.data(),
+                                    is_mem ? (tail_on ? "mem_tail_round" : "mem_round") : (tail_on ? "ops_tail_round" : "ops_round"))))
+              return rc;
+            res = res_all.data();
+          } else if (by_residue) {
+            // this rank's share of every sum: the circuits' scaled by c_rank, the halves' as they are (no eq factor)
+            for (int x = 0; x < 3 * npc; x++) pack[x] = res[x] * c_rank;
+            if (with_dotp) memcpy(&pack[3 * (size_t)kHalfSlot], res + 3 * (size_t)hs, 6 * 96);
+            if ((rc = dist_sum(c, *pl, pack.data(), with_dotp ? 3 * (size_t)vpin::kSparkMaxInst : 3 * (size_t)npc, res_all.data(),
+                               is_mem ? "mem_round" : "ops_round")))
+              return rc;
+            res = res_all.data();
+          }
+        } else {
+          // ---- by residue: a host round on the gathered tables ----
+          gt.round_sums(rand.data() + j + 1, rd.lead_ok, with_dotp, res_all.data());
+          res = res_all.data();
+        }
+        if (fine) { auto t = Clock::now(); (j == 0 ? t_first : t_rounds) += secs(tl0, t); if (k >= 11) fprintf(stderr, " w%.1f", secs(tl0, t) * 1e6); tl0 = t; }
+        const Fq* cf = rd.combine(res, coeffs.data(), npc, with_dotp, e);
+        append_unipoly(tr, cf, 4);
+        Fq rj = tr.challenge_scalar("challenge_nextround");
+        if (tail_on && runs && j + 1 < kl) vpin::spark_tail_reply(c, j - tail_j0, B(&rj));  // the kernel folds while the host finishes the round
+        r[j] = rj;
+        rd.advance(rj, e);
+        polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
+        if (j >= kl) {
+          gt.fold(rj, with_dotp);
+        } else if (by_residue && j + 1 == kl) {
+          // the device rounds are over: the two live entries of every local table, bound with r_j, are this rank's entry of
+          // the W-entry tables the remaining rounds run on
+          bind_finals(reinterpret_cast<const Fq*>(vpin::spark_tail_final(c)), rj, npc, with_dotp, nl, cl.data(), cr.data(), dp);
+          vpin::spark_tail_end(c);
+          if ((rc = gt.gather(c, pl->world, npc, with_dotp, cl.data(), cr.data(), dp, is_mem ? "mem_gather_tables" : "ops_gather_tables")))
+            return rc;
+        }
+        if (fine) { auto t = Clock::now(); t_host += secs(tl0, t); if (k >= 11) fprintf(stderr, " m%.1f", secs(tl0, t) * 1e6); tl0 = t; }
+      }
+      if (fine && k >= 11) fprintf(stderr, "\n");
+      // the layer's final entries: the two live entries per table folded with r_{k-1}
+      const Fq rl = r[k - 1];
+      if (by_residue) {
+        for (int t = 0; t < npc; t++) { cl[t] = gt.A[t][0]; cr[t] = gt.B[t][0]; }
+        if (with_dotp)
+          for (int i = 0; i < 6; i++)
+            for (int tb = 0; tb < 3; tb++) dp[3 * i + tb] = gt.D[tb][i][0];
+      } else if (tail_on) {
+        const Fq* fin = runs ? reinterpret_cast<const Fq*>(vpin::spark_tail_final(c)) : nullptr;
+        if (by_circuit) {
+          for (int t = 0; t < ninst; t++) memcpy(&pack[6 * (size_t)t], fin + 6 * (size_t)t, 192);  // the tail numbers its instances 0..ninst-1
+          if ((rc = dist_exchange(c, *pl, is_mem, with_dotp, pack.data(), 6, fin_all.data(), is_mem ? "mem_finals" : "ops_finals"))) return rc;
+          fin = fin_all.data();
+        }
+        bind_finals(fin, rl, npc, with_dotp, kHalfSlot, cl.data(), cr.data(), dp);  // (halves ride along only with npc == 12 == kHalfSlot)
+        if (runs) vpin::spark_tail_end(c);
+      } else {
+        // launch-only end of a layer (VPIN_SPARK_TAIL_PAIRS=0, or a zero challenge): one GPU only
+        if (pl) return VPIN_ESHAPE;
+        if ((rc = vpin::spark_collect(c, &f, layer_id, with_dotp ? dotp->d : nullptr, with_dotp ? dotp->derefs : nullptr,
+                                      with_dotp ? dotp->scratch : nullptr, with_dotp, k >= 2)))
+          return rc;
+        const Fq* res = reinterpret_cast<const Fq*>(c->h_spark);
+        for (int t = 0; t < npc; t++) {
+          cl[t] = res[4 * t] + rl * (res[4 * t + 1] - res[4 * t]);
+          cr[t] = res[4 * t + 2] + rl * (res[4 * t + 3] - res[4 * t + 2]);
+        }
+        if (with_dotp) {
+          const Fq* q = reinterpret_cast<const Fq*>(c->h_spark) + 64;
+          for (int i = 0; i < 6; i++)
+            for (int t = 0; t < 3; t++) dp[3 * i + t] = q[6 * i + 2 * t] + rl * (q[6 * i + 2 * t + 1] - q[6 * i + 2 * t]);
+        }
+      }
     }
 
-    for (int j = 0; j < k; j++) {
-      const Fq* rs = nullptr;
-      if (j < j_host) {
-        // ---- a device round on the local tables ----
-        const size_t hl = h >> lw;
-        const size_t len = j == 0 ? hl : (hl >> (j - 1));
-        const vpin::fq* E = pyr->d + pyramid_offset(kl, j + 1);
-        const uint8_t* rprev = j ? B(&r[j - 1]) : nullptr;
-        const size_t tail_pairs = vpin::spark_tail_pairs();
-        if (tail_pairs == 0) return VPIN_ESHAPE;
-        if (!tail_on && (hl >> (j + 1)) <= tail_pairs) {
-          if ((rc = vpin::spark_tail_launch(c, &f, layer_id, kl, j, len, pyr->d, rprev, with_dotp ? dotp->Nloc : 0,
-                                            with_dotp ? dotp->vals_loc : nullptr, with_dotp ? dotp->comb_loc : nullptr,
-                                            with_dotp ? dotp->scratch : nullptr, nullptr, with_dotp ? 6 : 0)))
-            return rc;
-          tail_on = true;
-          tail_j0 = j;
-        }
-        const Fq* loc;
-        if (tail_on) {
-          if ((rc = vpin::spark_tail_wait(c, j - tail_j0, with_dotp ? ninst : npc, npc))) return rc;
-          loc = reinterpret_cast<const Fq*>(vpin::spark_tail_sums(c));
-          for (int t = 0; t < npc; t++) for (int x = 0; x < 3; x++) mine[3 * (size_t)t + x] = loc[3 * (size_t)t + x] * c_rank;
-          if (with_dotp) memcpy(&mine[3 * (size_t)12], loc + 3 * (size_t)npc, 6 * 96);
-        } else {
-          if ((rc = vpin::spark_prod_round(c, &f, layer_id, len, E, rprev, with_dotp ? 6 : 0, true))) return rc;
-          if (with_dotp && (rc = vpin::spark_dotp_round(c, dotp->Nloc, dotp->vals_loc, dotp->comb_loc, dotp->scratch, len, j == 1, rprev)))
-            return rc;
-          if ((rc = vpin::spark_wait_flag(c))) return rc;
-          loc = reinterpret_cast<const Fq*>(c->h_spark);
-          for (int t = 0; t < npc; t++) for (int x = 0; x < 3; x++) mine[3 * (size_t)t + x] = loc[3 * (size_t)t + x] * c_rank;
-          if (with_dotp) memcpy(&mine[3 * (size_t)12], loc + 3 * (size_t)12, 6 * 96);
-        }
-        // slots: circuits 0.., halves 12.. (npc <= 12)
-        if (!with_dotp) { if ((rc = dist_sum(c, pl, mine.data(), 3 * (size_t)npc, res.data(), is_mem ? "mem_round" : "ops_round"))) return rc; }
-        else if ((rc = dist_sum(c, pl, mine.data(), 3 * (size_t)18, res.data(), "ops_round"))) return rc;
-        rs = res.data();
-      } else {
-        // ---- a host round on the gathered (or top-level) tables: the kernels' conventions ----
-        const size_t len = HA[0].size(), half = len / 2;
-        std::vector<Fq> E(half);
-        host_eq(rand.data() + j + 1, (size_t)(k - j - 1), E.data());
-        for (int t = 0; t < npc; t++) {
-          Fq a0 = Fq::zero(), a1 = Fq::zero(), a2 = Fq::zero();
-          for (size_t i = 0; i < half; i++) {
-            const Fq A0 = HA[t][i], dA = HA[t][i + half] - A0, B0 = HB[t][i], dB = HB[t][i + half] - B0;
-            if (lead_ok) {
-              a0 = a0 + E[i] * (A0 * B0);
-              a1 = a1 + E[i] * (dA * dB);
-            } else {
-              const Fq A2 = A0 + dA + dA, B2 = B0 + dB + dB, A3 = A2 + dA, B3 = B2 + dB;
-              a0 = a0 + E[i] * (A0 * B0); a1 = a1 + E[i] * (A2 * B2); a2 = a2 + E[i] * (A3 * B3);
-            }
-          }
-          res[3 * (size_t)t] = a0; res[3 * (size_t)t + 1] = a1; res[3 * (size_t)t + 2] = a2;
-        }
-        if (with_dotp)
-          for (int i = 0; i < 6; i++) {
-            Fq q0 = Fq::zero(), q2 = Fq::zero(), q3 = Fq::zero();
-            for (size_t x = 0; x < half; x++) {
-              Fq v0[3], v2[3], v3[3];
-              for (int tb = 0; tb < 3; tb++) {
-                const Fq p = HD[tb][i][x], d = HD[tb][i][x + half] - p;
-                v0[tb] = p; v2[tb] = p + d + d; v3[tb] = v2[tb] + d;
-              }
-              q0 = q0 + v0[0] * v0[1] * v0[2]; q2 = q2 + v2[0] * v2[1] * v2[2]; q3 = q3 + v3[0] * v3[1] * v3[2];
-            }
-            res[3 * (size_t)(12 + i)] = q0; res[3 * (size_t)(12 + i) + 1] = q2; res[3 * (size_t)(12 + i) + 2] = q3;
-          }
-        rs = res.data();
-      }
-      // ---- the round's polynomial and challenge (the same on every rank; identical to batched_prove) ----
-      Fq c0, c2, c3, T1 = Fq::zero(), S0 = Fq::zero(), Sinf = Fq::zero();
-      if (on_host) {
-        // prove_cubic_batched as written (sumcheck.rs:248-425): the host tables carry no eq factoring
-        const size_t len = HA[0].size(), half = len / 2;
-        std::vector<Fq> C(len);
-        // poly_C = eq(rand, .) folded with r_0..r_{j-1}: s * eq(rand_{j..}, .)
-        host_eq(rand.data() + j, (size_t)(k - j), C.data());
-        c0 = c2 = c3 = Fq::zero();
-        for (int t = 0; t < npc; t++) {
-          Fq e0 = Fq::zero(), e2 = Fq::zero(), e3 = Fq::zero();
-          for (size_t i = 0; i < half; i++) {
-            const Fq a = HA[t][i], a1 = HA[t][i + half], b = HB[t][i], b1 = HB[t][i + half], cc = s * C[i], cc1 = s * C[i + half];
-            e0 = e0 + a * b * cc;
-            const Fq a2 = a1 + a1 - a, b2 = b1 + b1 - b, c2p = cc1 + cc1 - cc;
-            e2 = e2 + a2 * b2 * c2p;
-            const Fq a3 = a2 + a1 - a, b3 = b2 + b1 - b, c3p = c2p + cc1 - cc;
-            e3 = e3 + a3 * b3 * c3p;
-          }
-          c0 = c0 + e0 * coeffs[t]; c2 = c2 + e2 * coeffs[t]; c3 = c3 + e3 * coeffs[t];
-        }
-      } else {
-        const Fq rho = rand[j], omr = one - rho;
-        Fq S2 = Fq::zero(), S3 = Fq::zero();
-        if (lead_ok) {
-          for (int t = 0; t < npc; t++) { S0 = S0 + rs[3 * t] * coeffs[t]; Sinf = Sinf + rs[3 * t + 1] * coeffs[t]; }
-          T1 = (cn - omr * S0) * rho_inv[j];
-          const Fq two_inf = Sinf + Sinf, d10 = T1 - S0;
-          S2 = T1 + d10 + two_inf;
-          S3 = S2 + d10 + two_inf + two_inf;
-        } else {
-          for (int t = 0; t < npc; t++) { S0 = S0 + rs[3 * t] * coeffs[t]; S2 = S2 + rs[3 * t + 1] * coeffs[t]; S3 = S3 + rs[3 * t + 2] * coeffs[t]; }
-        }
-        const Fq two_rho = rho + rho;
-        c0 = s * omr * S0;
-        c2 = s * (two_rho + rho - one) * S2;
-        c3 = s * (two_rho + two_rho + rho - one - one) * S3;
-        if (with_dotp)
-          for (int i = 0; i < 6; i++) {
-            const Fq* q = rs + 3 * (12 + i);
-            c0 = c0 + q[0] * coeffs[npc + i]; c2 = c2 + q[1] * coeffs[npc + i]; c3 = c3 + q[2] * coeffs[npc + i];
-          }
-      }
-      Fq evals[4] = {c0, e - c0, c2, c3}, cf[4];
-      unipoly_from_evals(evals, 4, cf);
-      append_unipoly(tr, cf, 4);
-      const Fq rj = tr.challenge_scalar("challenge_nextround");
-      if (j < j_host && tail_on && j + 1 < j_host) vpin::spark_tail_reply(c, j - tail_j0, B(&rj));
-      r[j] = rj;
-      e = unipoly_eval(cf, 4, rj);
-      if (!on_host) {
-        const Fq rho = rand[j], omr = one - rho;
-        if (lead_ok) cn = S0 + rj * ((T1 - S0 - Sinf) + rj * Sinf);
-        s = s * (rho * rj + omr * (one - rj));
-      } else {
-        s = s * (rand[j] * rj + (one - rand[j]) * (one - rj));
-      }
-      polys[3 * j] = cf[0]; polys[3 * j + 1] = cf[2]; polys[3 * j + 2] = cf[3];
-      if (j >= j_host) {
-        // bound_poly_var_top on the host tables
-        auto fold = [&](std::vector<Fq>& T) {
-          const size_t half = T.size() / 2;
-          for (size_t i = 0; i < half; i++) T[i] = T[i] + rj * (T[i + half] - T[i]);
-          T.resize(half);
-        };
-        for (int t = 0; t < npc; t++) { fold(HA[t]); fold(HB[t]); }
-        if (with_dotp) for (int tb = 0; tb < 3; tb++) for (int i = 0; i < 6; i++) fold(HD[tb][i]);
-      } else if (j + 1 == j_host) {
-        // the device rounds are over: the two live entries of every local table, bound with r_j, are this rank's entry of
-        // the W-entry tables the remaining rounds run on
-        const Fq* fl = reinterpret_cast<const Fq*>(vpin::spark_tail_final(c));
-        for (int t = 0; t < npc; t++) {
-          mine[2 * (size_t)t] = fl[6 * t] + rj * (fl[6 * t + 1] - fl[6 * t]);
-          mine[2 * (size_t)t + 1] = fl[6 * t + 2] + rj * (fl[6 * t + 3] - fl[6 * t + 2]);
-        }
-        size_t per_rank = 2 * (size_t)npc;
-        if (with_dotp) {
-          for (int i = 0; i < 6; i++)
-            for (int tb = 0; tb < 3; tb++) {
-              const Fq* q = fl + 6 * (npc + i) + 2 * tb;
-              mine[per_rank + 3 * (size_t)i + tb] = q[0] + rj * (q[1] - q[0]);
-            }
-          per_rank += 18;
-        }
-        vpin::spark_tail_end(c);
-        tail_on = false;
-        std::vector<Fq> all(per_rank * (size_t)W);
-        if ((rc = vpin::comm_allgather_ctx(c, mine.data(), all.data(), per_rank * 32, is_mem ? "mem_gather_tables" : "ops_gather_tables")))
-          return rc;
-        for (int t = 0; t < npc; t++) {
-          HA[t].resize(W); HB[t].resize(W);
-          for (int rk = 0; rk < W; rk++) { HA[t][rk] = all[(size_t)rk * per_rank + 2 * t]; HB[t][rk] = all[(size_t)rk * per_rank + 2 * t + 1]; }
-        }
-        if (with_dotp)
-          for (int tb = 0; tb < 3; tb++) {
-            HD[tb].assign(6, std::vector<Fq>(W));
-            for (int i = 0; i < 6; i++)
-              for (int rk = 0; rk < W; rk++) HD[tb][i][rk] = all[(size_t)rk * per_rank + 2 * (size_t)npc + 3 * (size_t)i + tb];
-          }
-      }
-    }
-    for (int t = 0; t < npc; t++) { cl[t] = HA[t][0]; cr[t] = HB[t][0]; }
-    if (with_dotp) {
-      for (int tb = 0; tb < 3; tb++) out.dotp[tb].resize(6);
-      for (int i = 0; i < 6; i++)
-        for (int tb = 0; tb < 3; tb++) out.dotp[tb][i] = HD[tb][i][0];
-    }
     for (int t = 0; t < npc; t++) {
       tr.append_scalar("claim_prod_left", cl[t]);
       tr.append_scalar("claim_prod_right", cr[t]);
     }
-    if (with_dotp)
+    if (with_dotp) {
+      for (int t = 0; t < 3; t++) out.dotp[t].resize(6);
       for (int i = 0; i < 6; i++) {
+        for (int t = 0; t < 3; t++) out.dotp[t][i] = dp[3 * i + t];
         tr.append_scalar("claim_dotp_left", out.dotp[0][i]);
         tr.append_scalar("claim_dotp_right", out.dotp[1][i]);
         tr.append_scalar("claim_dotp_weight", out.dotp[2][i]);
       }
-    const Fq r_layer = tr.challenge_scalar("challenge_r_layer");
+    }
+    Fq r_layer = tr.challenge_scalar("challenge_r_layer");
     for (int t = 0; t < npc; t++) claims[t] = cl[t] + r_layer * (cr[t] - cl[t]);
     out.claims_left[o] = cl;
     out.claims_right[o] = cr;
@@ -912,7 +714,11 @@ static int batched_prove_strided(vpin_ctx* c, vpin::SparkForest& f, size_t n_glo
     ext.push_back(r_layer);
     ext.insert(ext.end(), r.begin(), r.end());
     rand.swap(ext);
+    if (fine) { auto t = Clock::now(); t_epi += secs(tl0, t); tl0 = t; }
   }
+  if (fine)
+    fprintf(stderr, "[spark]   forest of %d x 2^%d: setup %.3f  first result %.3f  later results %.3f  host per-round math %.3f  epilogue %.3f ms\n",
+            npc, num_layers, t_setup * 1e3, t_first * 1e3, t_rounds * 1e3, t_host * 1e3, t_epi * 1e3);
   return VPIN_OK;
 }
 
@@ -940,7 +746,7 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
     if (c->comm->world > 12) return VPIN_EINVAL;  // every rank owns at least one of the 12 ops circuits
     plan_init(plan, c->comm);
     dz = &plan;
-    // a power-of-two world splits every circuit by residue class (batched_prove_strided: perfectly balanced, and the derefs
+    // a power-of-two world splits every circuit by residue class (product_prove: perfectly balanced, and the derefs
     // gather, the leaves and the slices shrink with the world too); otherwise the circuits are dealt out whole
     static const bool by_circuit = getenv("VPIN_DIST_BY_CIRCUIT") != nullptr;
     const size_t Wz = (size_t)plan.world;
@@ -1124,8 +930,7 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
     tr.append_scalars(lab[s][2], &pl[s][4], 3);
     tr.append_scalar(lab[s][3], pl[s][7]);
   }
-  DotpCtx dotp{d, comb->d, (vpin::fq*)b_scr.p, {}};
-  StridedDotp sdotp{Nf, vals_loc, comb_loc, (vpin::fq*)b_scr.p, {}};
+  DotpCtx dotp{d, Nf, st ? vals_loc : d->vals, st ? comb_loc : comb->d, (vpin::fq*)b_scr.p, {}};
   Fq dotp_left[3], dotp_right[3];
   {
     // DotProductCircuit::evaluate (product_tree.rs:87-91) of the six halves
@@ -1135,7 +940,6 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
       Fq mine6[6];
       for (int i = 0; i < 6; i++) mine6[i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
       if ((rc = dist_sum(c, *dz, mine6, 6, dotp.claims, "triple_sums"))) return rc;
-      for (int i = 0; i < 6; i++) sdotp.claims[i] = dotp.claims[i];
     } else if (!dz) {
       if ((rc = vpin::spark_triple_sums(c, d, comb->d))) return rc;
       for (int i = 0; i < 6; i++) dotp.claims[i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
@@ -1160,9 +964,7 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
   std::vector<Fq> rand_ops, rand_mem;
   {
     TraceSpan ts("product: ops forest");
-    if (st) rc = batched_prove_strided(c, f_ops, N, &sdotp, tr, pf_ops, rand_ops, *dz, false);
-    else rc = batched_prove(c, f_ops, &dotp, tr, pf_ops, rand_ops, dz, 12);
-    if (rc) return rc;
+    if ((rc = product_prove(c, f_ops, 12, &dotp, tr, pf_ops, rand_ops, dz))) return rc;
   }
   if (defer_mem) {
     TraceSpan ts("network: mem forest (deferred)");
@@ -1175,9 +977,7 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
   }
   {
     TraceSpan ts("product: mem forest");
-    if (st) rc = batched_prove_strided(c, f_mem, M, nullptr, tr, pf_mem, rand_mem, *dz, true);
-    else rc = batched_prove(c, f_mem, nullptr, tr, pf_mem, rand_mem, dz, 4);
-    if (rc) return rc;
+    if ((rc = product_prove(c, f_mem, 4, nullptr, tr, pf_mem, rand_mem, dz))) return rc;
   }
   g_spark_timings[3] = secs(t0, Clock::now());
 

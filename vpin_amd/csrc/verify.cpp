@@ -633,12 +633,6 @@ static bool sat_verify(vpin_ctx* c, Reader& r, size_t num_cons, size_t num_vars,
 
 // ---- SPARK -----------------------------------------------------------------------------------------
 
-static void append_unipoly(Transcript& tr, const Fq* coeffs, int n) {
-  tr.append_message("poly", "UniPoly_begin");
-  for (int i = 0; i < n; i++) tr.append_scalar("coeff", coeffs[i]);
-  tr.append_message("poly", "UniPoly_end");
-}
-
 struct BatchedP {
   int num_layers = 0, npc = 0, ndotp = 0;
   std::vector<std::vector<Fq>> polys, cl, cr;
@@ -724,15 +718,6 @@ static bool batched_verify(const BatchedP& b, const Fq* claims_prod, const Fq* c
   }
   claims_out = claims;
   return true;
-}
-
-static Fq combine_bot(std::vector<Fq> e, const std::vector<Fq>& ch) {
-  size_t n = e.size();
-  for (size_t ii = ch.size(); ii-- > 0;) {
-    n /= 2;
-    for (size_t i = 0; i < n; i++) e[i] = e[2 * i] + ch[ii] * (e[2 * i + 1] - e[2 * i]);
-  }
-  return e[0];
 }
 
 // HashLayerProof::verify_helper (sparse_mlpoly.rs:851-900)
