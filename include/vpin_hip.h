@@ -734,6 +734,118 @@ int vpin_e2_dlog_solve(vpin_ctx* ctx, const vpin_e2_dlog* t, const uint8_t* px, 
 int vpin_e2_decrypt(vpin_ctx* ctx, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y,
                     const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant,
                     int64_t* v_out, uint8_t* found_out);
+/* One round of the client between two layers: what main of src/LeNet/Client.py does with one message of the server
+ * (receive_decrypt, then relu and / or shifting, then encryptInputImage_send), as ONE launch chain on the context's stream with
+ * no host copy between the decryption and the encryption: sk * c1, the subtraction, the walk of vpin_e2_dlog_solve, the
+ * activation, the three fixed-base multiplications of vpin_e2_encrypt.
+ *   v_out[i]    the raw decryption
+ *   act_out[i]  a = v, then max(a, 0) when relu != 0, then, when shift_bits != 0, the reference's shifting(a, shift_bits) =
+ *               (float32(a) / 2^shift_bits * 2^16).astype(int32): a rounded to nearest-even into float32, an exact power-of-two
+ *               scale, truncation toward zero.  This is not the integer shift of a: the rounding into float32 comes first.
+ *   c1o / c2o   the encryption of act_out under r_le32 (cnt scalars, as for vpin_e2_encrypt); reencrypt = 0 is the last round:
+ *               nothing is encrypted and baseG, baseH, r_le32 and the six outputs may be NULL
+ * VPIN_ESHAPE, with the first such index named in vpin_last_error(): an element has no value within +-(max_giant * nb + nb - 1)
+ * (the activation needs every value), or its shifted value does not fit int32 (numpy's result is undefined there), or
+ * without a shift |act| >= 2^62.  v_out and act_out are written all the same (0 at such an element's act_out).
+ * VPIN_EINVAL as for vpin_e2_decrypt and vpin_e2_encrypt, and shift_bits outside 0 .. 62. */
+int vpin_e2_client_round(vpin_ctx* ctx, const vpin_e2_dlog* t, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                         const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x,
+                         const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int relu, int shift_bits, int reencrypt,
+                         const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf,
+                         uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+
+/* ---- the channel sums of the LeNet server loop ---------------------------------------------------------------------------
+ * secondConv and thirdConv of src/LeNet/Server.py add whole ciphertext planes pixel by pixel (np.sum(planes, axis=0)) before
+ * the convolution: out[o][p] = sum over the input planes j with connect[o][j] != 0 of in[j][p], for n_in planes of H x W points
+ * (plane-major, row-major inside a plane), a table of n_out x n_in bytes and n_out output planes.  thirdConv is the table of
+ * all ones.  The additions are complete: an identity pixel adds nothing, the same point in two planes doubles, P and -P
+ * cancel to a flagged identity (zeros, flag 1), which is not an error -- the convolution takes identity pixels.  These
+ * additions belong to no witness list (the reference does not prove them).
+ * VPIN_EINVAL: a null argument, a zero dimension, a row of the table that selects no plane, a coordinate >= q, a point off the
+ * curve; n_in or n_out above 65535, or 2^31 points or more on either side. */
+int vpin_e2_plane_sums(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n_in, size_t H, size_t W,
+                       const uint8_t* connect, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+
+/* ---- the whole encrypted LeNet inference ---------------------------------------------------------------------------------
+ * What inferenceCNN of src/LeNet/Server.py and main of src/LeNet/Client.py do together: the encrypted image goes in, the
+ * encrypted class scores come out, and with them the witness lists of the seven labels L1 .. L7 the prover takes.
+ *   L1 conv1: n1 kernels, each the one filter over the c1 image and then over the c2 image   R1: ReLU
+ *   L2 pool1 on each of the 2 n1 planes                                                       R2: shifting(., 26)
+ *   L3 conv2: per output the connected planes summed (vpin_e2_plane_sums), then the filter    R3: ReLU
+ *   L4 pool2                                                                                  R4: shifting(., 26)
+ *   L5 conv3: n3 times the sum of all n2 planes through the filter -> 1 x 1                   R5: ReLU, shifting(., 26)
+ *   L6 FC1 n3 -> N1: the bias encrypted by the server, FCLayer on the c1 row, then the c2 row R6: ReLU, shifting(., 33)
+ *   L7 FC2 N1 -> N2                                                                           R7: ReLU, the result
+ * A label's lists are those of its layer call (vpin_enc_conv2d, vpin_enc_avgpool2d, vpin_enc_fc) over the planes in the order
+ * (kernel 0, c1), (kernel 0, c2), (kernel 1, c1), ..; the plane additions of the channel sums enter no list (the reference does
+ * not prove them).  Keys and randomness are the caller's, consumed in the order the reference draws them: one 32-byte key per
+ * myConv2d / FCLayer call in call order (2 n1 + 2 n2 + 2 n3 + 4), one r per encrypt call of encryptBias (N1, then N2). */
+typedef struct vpin_lenet_cfg {
+  size_t H, W;                   /* the image (square) */
+  size_t n1, n2, n3;             /* kernels of the three convolutions */
+  const uint8_t* connect;        /* n2 x n1 bytes: conv2's output o takes input plane j when connect[o * n1 + j] != 0 (conv3: all) */
+  size_t f;                      /* the one f x f filter .. */
+  const uint8_t* filter_le16;    /* .. of u128 weights, row-major, 16 bytes little-endian each */
+  size_t pool_k, pool_stride;
+  uint8_t pool_scale_le16[16];   /* u128, the reference's 2^10 / k^2 */
+  int relu[7], shift_bits[7];    /* per round R1 .. R7: ReLU or not, the bits of shifting (0: none) */
+  uint64_t max_giant[7];         /* per round: the discrete-log range of the ready-made client */
+  int prf_bytes;
+  size_t N1, N2;
+  const int32_t *w1, *w2;        /* n3 x N1 and N1 x N2, row-major, non-negative: the 16-bit fixed point of the model's weights */
+  const int64_t *b1, *b2;        /* N1 and N2 bias values */
+} vpin_lenet_cfg;
+/* the reference's network: 32 x 32, 6 / 16 / 120 kernels, 5 x 5, pooling 2 / 2 with scale 256, the rounds of the table above,
+ * 13 PRF bytes, 84 and 10 outputs; max_giant for a table of 2^24 baby steps (2^11 giant steps, 2^15 for R6 and R7, whose values
+ * reach 2^38.4).  The connection table, the filter and the weights stay NULL: they are the caller's data */
+int vpin_lenet_cfg_default(vpin_lenet_cfg* cfg);
+/* what a run consumes: out[0..6] multiplications and out[7..13] additions of L1 .. L7, out[14..20] decryptions of R1 .. R7,
+ * out[21] decryptions in all, out[22] client encryptions (the image included), out[23] PRF keys, out[24] bias r.  VPIN_EINVAL for
+ * a zero dimension, a window that does not fit, a third convolution whose output is not 1 x 1, a connection row without a plane */
+int vpin_lenet_cfg_counts(const vpin_lenet_cfg* cfg, size_t out[32]);
+/* One interaction with the client (interactionClient / receiveEncryptedImage of Server.py): round = 0 .. 6, flags =
+ * VPIN_LENET_RELU | VPIN_LENET_REENCRYPT, cnt ciphertexts (c1, c2) out, the activated values encrypted again back (the six
+ * outputs are NULL in the last round, which has no VPIN_LENET_REENCRYPT).  Returns VPIN_OK or an error code; the error text is
+ * cleared before the call, and a callback that fails without setting one is reported as "the round callback failed" */
+#define VPIN_LENET_RELU 1
+#define VPIN_LENET_REENCRYPT 2
+typedef int (*vpin_lenet_round_fn)(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y,
+                                   const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
+                                   uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+typedef struct vpin_lenet_trace vpin_lenet_trace;
+/* The server loop.  The driver holds no secret key: baseG / baseH (the client's public key) are there because the server
+ * encrypts the bias itself.  What the client sends back is validated by the layer that takes it.  A failing layer or round
+ * frees everything, returns its code and names the label or round in vpin_last_error() ("vpin_lenet_infer: L3: ..").
+ * VPIN_EINVAL also for a negative weight and for n_keys / n_bias_r other than vpin_lenet_cfg_counts says */
+int vpin_lenet_infer(vpin_ctx* ctx, const vpin_lenet_cfg* cfg, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                     const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                     const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
+                     void* user, vpin_lenet_trace** out);
+void vpin_lenet_trace_free(vpin_lenet_trace* t);
+/* label 1 .. 7 as the trace of its layer call, borrowed until vpin_lenet_trace_free: vpin_conv_trace_dims / _output / _mults /
+ * _adds / _left read it (the pooling labels have no multiplications) */
+int vpin_lenet_trace_label(const vpin_lenet_trace* t, int label, const vpin_conv_trace** out);
+/* a label's two lists through vpin_gadget_point_mult_dev / _add_dev, as vpin_conv_trace_instances */
+int vpin_lenet_trace_instances(vpin_ctx* ctx, const vpin_lenet_trace* t, int label, vpin_dev_instance** mult_out,
+                               vpin_dev_instance** add_out);
+/* the last layer's ciphertext: 2 x n points, the c1 row and then the c2 row */
+int vpin_lenet_trace_result(const vpin_lenet_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf, size_t* n);
+/* host-clock milliseconds of the last vpin_lenet_infer on this thread: [0..6] L1 .. L7, [7..13] R1 .. R7, [14] the whole */
+void vpin_lenet_last_timings(double out[16]);
+/* The ready-made client: owns sk, the tables of G and H = sk * G, a discrete-log table of nb baby steps and the queue of n_r
+ * encryption randomness values (32 bytes each, one per encrypt call in order).  vpin_lenet_client_round is a
+ * vpin_lenet_round_fn over vpin_e2_client_round with user = the client; it keeps each round's raw decryptions and activated
+ * values (vpin_lenet_client_values, round 1 .. 7, borrowed).  VPIN_EINVAL when the queue runs out; a round that fails consumes no
+ * randomness, so the client can be used again */
+typedef struct vpin_lenet_client vpin_lenet_client;
+int vpin_lenet_client_create(vpin_ctx* ctx, const uint8_t sk_le32[32], uint64_t nb, const uint64_t max_giant[7], const uint8_t* r_le32,
+                             size_t n_r, vpin_lenet_client** out);
+void vpin_lenet_client_free(vpin_lenet_client* cl);
+int vpin_lenet_client_bases(const vpin_lenet_client* cl, const vpin_e2_base** baseG, const vpin_e2_base** baseH);
+int vpin_lenet_client_values(const vpin_lenet_client* cl, int round, const int64_t** v, const int64_t** act, size_t* cnt);
+int vpin_lenet_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
+                            uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's

@@ -46,6 +46,19 @@ def make_r1cs(inst):
     return r
 
 
+class LenetCfg(C.Structure):
+    """vpin_lenet_cfg of include/vpin_hip.h"""
+    _fields_ = [("H", C.c_size_t), ("W", C.c_size_t), ("n1", C.c_size_t), ("n2", C.c_size_t), ("n3", C.c_size_t),
+                ("connect", C.c_void_p), ("f", C.c_size_t), ("filter_le16", C.c_void_p), ("pool_k", C.c_size_t),
+                ("pool_stride", C.c_size_t), ("pool_scale_le16", C.c_uint8 * 16), ("relu", C.c_int * 7), ("shift_bits", C.c_int * 7),
+                ("max_giant", C.c_uint64 * 7), ("prf_bytes", C.c_int), ("N1", C.c_size_t), ("N2", C.c_size_t),
+                ("w1", C.c_void_p), ("w2", C.c_void_p), ("b1", C.c_void_p), ("b2", C.c_void_p)]
+
+
+# vpin_lenet_round_fn
+LENET_ROUND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, *([C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 6))
+
+
 class KStat(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("ms", C.c_double), ("alg_bytes", C.c_double), ("units", C.c_double)]
 
@@ -193,6 +206,23 @@ def lib():
     L.vpin_e2_dlog_info.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vpin_e2_dlog_solve.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, vp]
     L.vpin_e2_decrypt.argtypes = [vp, vp, vp] + [vp] * 6 + [C.c_size_t, C.c_uint64, vp, vp]
+    L.vpin_e2_client_round.argtypes = [vp] * 5 + [vp] * 6 + [C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, vp, vp, vp] + [vp] * 6
+    L.vpin_e2_plane_sums.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp, C.c_size_t, vp, vp, vp]
+    L.vpin_lenet_cfg_default.argtypes = [C.POINTER(LenetCfg)]
+    L.vpin_lenet_cfg_counts.argtypes = [C.POINTER(LenetCfg), C.POINTER(C.c_size_t)]
+    L.vpin_lenet_infer.argtypes = [vp, C.POINTER(LenetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.vpin_lenet_trace_free.argtypes = [vp]
+    L.vpin_lenet_trace_free.restype = None
+    L.vpin_lenet_trace_label.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.vpin_lenet_trace_instances.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.vpin_lenet_trace_result.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_lenet_last_timings.argtypes = [C.POINTER(C.c_double)]
+    L.vpin_lenet_last_timings.restype = None
+    L.vpin_lenet_client_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_lenet_client_free.argtypes = [vp]
+    L.vpin_lenet_client_free.restype = None
+    L.vpin_lenet_client_bases.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vpin_lenet_client_values.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]
@@ -1351,6 +1381,41 @@ class Context:
         _chk(lib().vpin_e2_decrypt(self.h, table, p(k), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), n, max_giant, p(v), p(found)),
              "vpin_e2_decrypt")
         return v, found
+
+    def e2_client_round(self, table, base_g, base_h, sk, c1, c2, max_giant, relu=False, shift_bits=0, rs=None):
+        """vpin_e2_client_round: decrypt, activate (ReLU, then the reference's float32 shifting when shift_bits != 0) and, when rs is
+        given, encrypt again under rs, in one launch chain.  -> (v, act, c1_out, c2_out); the ciphertexts are None for rs = None
+        (the last round)"""
+        x1, y1, f1 = self._points(*c1)
+        x2, y2, f2 = self._points(*c2)
+        n = x1.shape[0]
+        assert x2.shape[0] == n and (rs is None or len(rs) == n)
+        k = self._u256s([sk])
+        v, act = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        r, out = None, [None] * 6
+        if rs is not None:
+            r = self._u256s(rs)
+            out = [np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8),
+                   np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
+        rc = lib().vpin_e2_client_round(self.h, table, base_g, base_h, p(k), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), n, max_giant,
+                                        int(bool(relu)), int(shift_bits), int(rs is not None), p(r), p(v), p(act), *[p(a) for a in out])
+        _chk(rc, "vpin_e2_client_round")
+        if rs is None:
+            return v, act, None, None
+        return v, act, tuple(out[:3]), tuple(out[3:])
+
+    def e2_plane_sums(self, x, y, inf, n_in, H, W, connect):
+        """vpin_e2_plane_sums: n_in planes of H x W points and a table connect[o][j] -> (x, y, inf) of len(connect) planes, each the
+        pixel-wise sum of the planes its row selects"""
+        x, y, f = self._points(x, y, inf)
+        con = np.ascontiguousarray(np.asarray(connect, dtype=np.uint8))
+        assert x.shape[0] == n_in * H * W and con.ndim == 2 and con.shape[1] == n_in
+        n_out = con.shape[0]
+        ox, oy, oi = np.zeros((n_out, H, W, 32), np.uint8), np.zeros((n_out, H, W, 32), np.uint8), np.zeros((n_out, H, W), np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_plane_sums(self.h, p(x), p(y), p(f), n_in, H, W, p(con), n_out, p(ox), p(oy), p(oi)), "vpin_e2_plane_sums")
+        return ox, oy, oi
 
     # ---- profiling ----
     def prof_enable(self, on=True):

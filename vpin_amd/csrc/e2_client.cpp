@@ -2,6 +2,7 @@
 // the two device-resident tables.  The arithmetic runs on the device (e2_client.hip).  Restates the key generation, `encrypt`
 // and `decrypt` / `bsgs` of the reference's src/LeNet/Client.py with the randomness and the key as explicit inputs, and
 // with the baby-step table built on the device instead of read from a pickle.
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -133,6 +134,42 @@ int vpin_e2_decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32
     case 2: return fail(VPIN_EINVAL, "vpin_e2_decrypt: the key sk is zero");
   }
   return cl::decrypt(c, t, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, max_giant, v_out, found_out);
+}
+
+int vpin_e2_client_round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t sk_le32[32],
+                         const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y,
+                         const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int relu, int shift_bits, int reencrypt, const uint8_t* r_le32,
+                         int64_t* v_out, int64_t* act_out, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y,
+                         uint8_t* o2inf) {
+  if (!c || !t || !sk_le32 || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !v_out || !act_out)
+    return fail(VPIN_EINVAL, "vpin_e2_client_round: null argument");
+  if (reencrypt && (!baseG || !baseH || !r_le32 || !o1x || !o1y || !o1inf || !o2x || !o2y || !o2inf))
+    return fail(VPIN_EINVAL, "vpin_e2_client_round: null argument");
+  if (cnt == 0 || cnt >= ((size_t)1 << 30)) return fail(VPIN_EINVAL, "vpin_e2_client_round: cnt must be in 1 .. 2^30 - 1");
+  if (shift_bits < 0 || shift_bits > 62) return fail(VPIN_EINVAL, "vpin_e2_client_round: shift_bits must be 0 (no shifting) or in 1 .. 62");
+  if (!walk_fits(max_giant, t->nb)) return fail(VPIN_EINVAL, "vpin_e2_client_round: max_giant * nb is past 2^62");
+  switch (check_scalars(sk_le32, 1, true)) {
+    case 1: return fail(VPIN_EINVAL, "vpin_e2_client_round: the key sk is not below the group order");
+    case 2: return fail(VPIN_EINVAL, "vpin_e2_client_round: the key sk is zero");
+  }
+  if (reencrypt) switch (check_scalars(r_le32, cnt, true)) {
+    case 1: return fail(VPIN_EINVAL, "vpin_e2_client_round: a randomness r is not below the group order");
+    case 2: return fail(VPIN_EINVAL, "vpin_e2_client_round: a randomness r is zero");
+  }
+  std::vector<uint8_t> bad(cnt, 0);
+  const int rc = cl::round(c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, max_giant, relu != 0, shift_bits,
+                           reencrypt ? r_le32 : nullptr, v_out, act_out, bad.data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
+  if (rc) return rc;
+  for (size_t i = 0; i < cnt; i++) {
+    if (!bad[i]) continue;
+    char why[160];
+    if (bad[i] & 1)
+      snprintf(why, sizeof why, "vpin_e2_client_round: element %zu has no value within the walk's range", i);
+    else
+      snprintf(why, sizeof why, "vpin_e2_client_round: the activated value of element %zu (decrypted %lld) does not fit", i, (long long)v_out[i]);
+    return fail(VPIN_ESHAPE, why);
+  }
+  return VPIN_OK;
 }
 
 }  // extern "C"

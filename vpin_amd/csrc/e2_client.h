@@ -49,6 +49,14 @@ int dlog_solve(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t* px, const uint
 int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
             const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int64_t* v_out,
             uint8_t* found_out);
+// One round of the client between two layers as one launch chain: decrypt (as above), the activation (ReLU when relu, then
+// the reference's float32 `shifting` when shift_bits != 0) and, when r_le32 is not null, the encryption of the activated values
+// under r.  v_out: the raw decryptions; act_out: the activated values; bad_out: per element 0, or bit 0 = no value in the
+// walk's range, bit 1 = the activated value does not fit (int32 after a shift, |.| < 2^62 otherwise)
+int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
+          const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
+          uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
+          uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf);
 
 }  // namespace client
 }  // namespace vpin

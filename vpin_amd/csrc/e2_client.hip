@@ -13,6 +13,8 @@
 //                          inversion per step (e2_block_inverse); every step is looked up by x and confirmed on the stored
 //                          coordinates.  A point has up to 64 lanes, which take the giant steps in turn (the step's latency
 //                          is that one inversion, so a walk is as long as its deepest lane)
+//   e2_act_kernel          the client's activation between the walk and the next encryption: ReLU and the reference's
+//                          `shifting`, which goes through float32, one lane per element
 // e2_to_affine_kernel (enc_conv.hip) normalises every output and the baby steps.  As in the layers' kernels the accumulators
 // are named registers: no per-lane arrays.
 #include "e2_dev.h"
@@ -230,6 +232,39 @@ __global__ __launch_bounds__(kE2Block) void e2_dlog_walk_kernel(const fq* __rest
   }
 }
 
+// The client's activation (src/LeNet/Client.py relu :278-283, shifting :285-289) on the walk's value v, then the message of
+// the next encryption as cl::encrypt takes it: the magnitude as a 32-byte scalar and a sign byte.  shifting(v, bits) is
+// (float32(v) / 2^bits * 2^16).astype(int32): v rounded to nearest-even into float32, an exact power-of-two scale, truncation
+// toward zero.  An integer shift of v is NOT the same number (the rounding into 24 bits of mantissa comes first and can carry).
+// bad[i]: kActNotFound when the walk met no value, kActRange when the shifted value does not fit int32 (numpy's result is
+// undefined there) or the message is not below 2^62 in magnitude
+constexpr uint8_t kActNotFound = 1, kActRange = 2;
+
+__global__ __launch_bounds__(kE2Block) void e2_act_kernel(const long long* __restrict__ v, const uint8_t* __restrict__ found, size_t n, int relu,
+                                                          int shift_bits, uint32_t* __restrict__ m, uint8_t* __restrict__ neg,
+                                                          long long* __restrict__ act, uint8_t* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  long long a = v[i];
+  uint8_t b = found[i] ? 0 : kActNotFound;
+  if (relu && a < 0) a = 0;
+  if (shift_bits) {
+    const float s = truncf(ldexpf(__ll2float_rn(a), 16 - shift_bits));  // |a| < 2^63, 16 - bits >= -47: the scale is exact
+    if (s >= 2147483648.0f || s < -2147483648.0f) { b |= kActRange; a = 0; }
+    else a = (long long)s;
+  }
+  const unsigned long long mag = a < 0 ? 0ull - (unsigned long long)a : (unsigned long long)a;
+  if (mag >= (1ull << 62)) b |= kActRange;
+  if (b) a = 0;
+  const unsigned long long mg = b ? 0ull : mag;
+  uint4* mo = reinterpret_cast<uint4*>(m + 8 * i);
+  mo[0] = make_uint4((uint32_t)mg, (uint32_t)(mg >> 32), 0u, 0u);
+  mo[1] = make_uint4(0u, 0u, 0u, 0u);
+  neg[i] = a < 0 ? 1 : 0;
+  act[i] = a;
+  bad[i] = b;
+}
+
 using vpin_host::Fq;
 
 fq to_fq(const uint8_t* le32) {
@@ -275,18 +310,25 @@ int walk_lanes_log(size_t n, uint64_t max_giant) {
   return l;
 }
 
-// the walk over n points resident as Montgomery coordinates
+// the walk over n points resident as Montgomery coordinates into the device words v (n x 8 bytes) and f (n bytes), not synchronised
+int launch_walk(vpin_ctx* c, const vpin_e2_dlog* t, const fq* X, const fq* Y, const uint8_t* inf, size_t n, uint64_t max_giant, void* v, void* f) {
+  VPIN_HIP_TRY(hipMemsetAsync(v, 0, n * 8, c->stream));
+  VPIN_HIP_TRY(hipMemsetAsync(f, 0, n, c->stream));
+  const int ll = walk_lanes_log(n, max_giant);
+  hipLaunchKernelGGL(e2_dlog_walk_kernel, dim3(blocks_of(n << ll, kE2Block)), dim3(kE2Block), 0, c->stream, X, Y, inf, n, (const fq*)t->tx,
+                     (const uint8_t*)t->par, (const unsigned long long*)t->idx, t->slots - 1, t->nb, (const fq*)t->dmx, (const fq*)t->dmy, ll,
+                     max_giant, e2_curve_a(), (long long*)v, (uint8_t*)f);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+// the walk, its values and flags to the host; synchronises
 int run_walk(vpin_ctx* c, const vpin_e2_dlog* t, const fq* X, const fq* Y, const uint8_t* inf, size_t n, uint64_t max_giant, int64_t* v_out,
              uint8_t* found_out) {
   DevBuf v(c), f(c);
   if (v.alloc(n * 8) || f.alloc(n)) return VPIN_ENOMEM;
-  VPIN_HIP_TRY(hipMemsetAsync(v.p, 0, n * 8, c->stream));
-  VPIN_HIP_TRY(hipMemsetAsync(f.p, 0, n, c->stream));
-  const int ll = walk_lanes_log(n, max_giant);
-  hipLaunchKernelGGL(e2_dlog_walk_kernel, dim3(blocks_of(n << ll, kE2Block)), dim3(kE2Block), 0, c->stream, X, Y, inf, n, (const fq*)t->tx,
-                     (const uint8_t*)t->par, (const unsigned long long*)t->idx, t->slots - 1, t->nb, (const fq*)t->dmx, (const fq*)t->dmy, ll,
-                     max_giant, e2_curve_a(), (long long*)v.p, (uint8_t*)f.p);
-  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = launch_walk(c, t, X, Y, inf, n, max_giant, v.p, f.p);
+  if (rc) return rc;
   VPIN_HIP_TRY(hipMemcpyAsync(v_out, v.p, n * 8, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(found_out, f.p, n, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -349,26 +391,42 @@ int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, si
   return emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
 }
 
+// The device side of an encryption over cnt elements whose r (cnt x 32 bytes), message magnitudes (cnt x 32 bytes) and sign bytes
+// are resident: the three fixed-base multiplications, the last addition, one normalisation of c1 | c2 and the copies of the
+// canonical bytes to the host.  Not synchronised; the buffers live until the caller has synchronised
+struct EncryptChain {
+  DevBuf ct, rh, mg, mx, my, cx, cy, fl;  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
+  explicit EncryptChain(vpin_ctx* c) : ct(c), rh(c), mg(c), mx(c), my(c), cx(c), cy(c), fl(c) {}
+  int run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const void* d_r, const void* d_m, const void* d_neg, size_t cnt,
+          uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+};
+
 int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg,
             size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf) {
   (void)hipSetDevice(c->device);
-  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
-  DevBuf r(c), m(c), ng(c), ct(c), rh(c), mg(c);
-  if (r.alloc(cnt * 32) || m.alloc(cnt * 32) || ng.alloc(cnt) || ct.alloc(2 * cnt * sizeof(e2_jac)) || rh.alloc(cnt * sizeof(e2_jac)) ||
-      mg.alloc(cnt * sizeof(e2_jac)))
-    return VPIN_ENOMEM;
+  DevBuf r(c), m(c), ng(c);
+  if (r.alloc(cnt * 32) || m.alloc(cnt * 32) || ng.alloc(cnt)) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(m.p, m_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(ng.p, neg, cnt, hipMemcpyHostToDevice, c->stream));
+  EncryptChain e(c);
+  const int rc = e.run(c, g, h, r.p, m.p, ng.p, cnt, c1x, c1y, c1inf, c2x, c2y, c2inf);
+  if (rc) return rc;
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+int EncryptChain::run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const void* d_r, const void* d_m, const void* d_neg, size_t cnt,
+                      uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf) {
+  if (ct.alloc(2 * cnt * sizeof(e2_jac)) || rh.alloc(cnt * sizeof(e2_jac)) || mg.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
   e2_jac* c1 = (e2_jac*)ct.p;
-  int rc = launch_base_mul(c, g, (const uint32_t*)r.p, nullptr, cnt, c1);
-  if (!rc) rc = launch_base_mul(c, h, (const uint32_t*)r.p, nullptr, cnt, (e2_jac*)rh.p);
-  if (!rc) rc = launch_base_mul(c, g, (const uint32_t*)m.p, (const uint8_t*)ng.p, cnt, (e2_jac*)mg.p);
+  int rc = launch_base_mul(c, g, (const uint32_t*)d_r, nullptr, cnt, c1);
+  if (!rc) rc = launch_base_mul(c, h, (const uint32_t*)d_r, nullptr, cnt, (e2_jac*)rh.p);
+  if (!rc) rc = launch_base_mul(c, g, (const uint32_t*)d_m, (const uint8_t*)d_neg, cnt, (e2_jac*)mg.p);
   if (rc) return rc;
   hipLaunchKernelGGL(e2_add_pairs_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)mg.p, (const e2_jac*)rh.p,
                      cnt, e2_curve_a(), c1 + cnt);
   VPIN_HIP_TRY(hipGetLastError());
-  DevBuf mx(c), my(c), cx(c), cy(c), fl(c);
   if (mx.alloc(2 * cnt * 32) || my.alloc(2 * cnt * 32) || cx.alloc(2 * cnt * 32) || cy.alloc(2 * cnt * 32) || fl.alloc(2 * cnt)) return VPIN_ENOMEM;
   if ((rc = e2_to_affine(c, c1, 2 * cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
   VPIN_HIP_TRY(hipMemcpyAsync(c1x, cx.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
@@ -377,7 +435,6 @@ int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uin
   VPIN_HIP_TRY(hipMemcpyAsync(c2x, (const uint8_t*)cx.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(c2y, (const uint8_t*)cy.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(c2inf, (const uint8_t*)fl.p + cnt, cnt, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }
 
@@ -479,28 +536,67 @@ int dlog_solve(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t* px, const uint
   return run_walk(c, t, (const fq*)d.px.p, (const fq*)d.py.p, (const uint8_t*)d.pinf.p, cnt, max_giant, v_out, found_out);
 }
 
+// The device side of a decryption up to the walk's input: the two ciphertext halves through the range and curve checks (who: the
+// entry point the rejection names), T = sk * c1, M = c2 - T normalised into mx / my / fl.  Not synchronised past the checks
+struct DecryptChain {
+  EncConvDev d1, d2;
+  DevBuf s, T, M, mx, my, cx, cy, fl;
+  explicit DecryptChain(vpin_ctx* c) : d1(c), d2(c), s(c), T(c), M(c), mx(c), my(c), cx(c), cy(c), fl(c) {}
+  int run(vpin_ctx* c, const char* who, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+          const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt) {
+    uint32_t flags = 0;
+    int rc = d1.load(c1x, c1y, c1inf, cnt, &flags);
+    if (rc) return rc;
+    if ((rc = enc::check_flags(flags, who, "c1 point"))) return rc;
+    if ((rc = d2.load(c2x, c2y, c2inf, cnt, &flags))) return rc;
+    if ((rc = enc::check_flags(flags, who, "c2 point"))) return rc;
+    if (s.alloc(32) || T.alloc(cnt * sizeof(e2_jac)) || M.alloc(cnt * sizeof(e2_jac)) || mx.alloc(cnt * 32) || my.alloc(cnt * 32) ||
+        cx.alloc(cnt * 32) || cy.alloc(cnt * 32) || fl.alloc(cnt))
+      return VPIN_ENOMEM;
+    VPIN_HIP_TRY(hipMemcpyAsync(s.p, sk_le32, 32, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_mul256(c, d1, (const uint32_t*)s.p, true, cnt, (e2_jac*)T.p))) return rc;
+    hipLaunchKernelGGL(e2_sub_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)T.p, (const fq*)d2.px.p,
+                       (const fq*)d2.py.p, (const uint8_t*)d2.pinf.p, cnt, e2_curve_a(), (e2_jac*)M.p);
+    VPIN_HIP_TRY(hipGetLastError());
+    return e2_to_affine(c, (const e2_jac*)M.p, cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
+  }
+};
+
 int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
             const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int64_t* v_out,
             uint8_t* found_out) {
   (void)hipSetDevice(c->device);
-  EncConvDev d1(c), d2(c);
-  uint32_t flags = 0;
-  int rc = d1.load(c1x, c1y, c1inf, cnt, &flags);
+  DecryptChain d(c);
+  const int rc = d.run(c, "vpin_e2_decrypt", sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
   if (rc) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_decrypt", "c1 point"))) return rc;
-  if ((rc = d2.load(c2x, c2y, c2inf, cnt, &flags))) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_decrypt", "c2 point"))) return rc;
-  DevBuf s(c), T(c), M(c), mx(c), my(c), cx(c), cy(c), fl(c);
-  if (s.alloc(32) || T.alloc(cnt * sizeof(e2_jac)) || M.alloc(cnt * sizeof(e2_jac)) || mx.alloc(cnt * 32) || my.alloc(cnt * 32) ||
-      cx.alloc(cnt * 32) || cy.alloc(cnt * 32) || fl.alloc(cnt))
-    return VPIN_ENOMEM;
-  VPIN_HIP_TRY(hipMemcpyAsync(s.p, sk_le32, 32, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_mul256(c, d1, (const uint32_t*)s.p, true, cnt, (e2_jac*)T.p))) return rc;
-  hipLaunchKernelGGL(e2_sub_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)T.p, (const fq*)d2.px.p,
-                     (const fq*)d2.py.p, (const uint8_t*)d2.pinf.p, cnt, e2_curve_a(), (e2_jac*)M.p);
+  return run_walk(c, t, (const fq*)d.mx.p, (const fq*)d.my.p, (const uint8_t*)d.fl.p, cnt, max_giant, v_out, found_out);
+}
+
+int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
+          const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
+          uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
+          uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf) {
+  (void)hipSetDevice(c->device);
+  DevBuf r(c), v(c), f(c), m(c), ng(c), act(c), bad(c);
+  if (v.alloc(cnt * 8) || f.alloc(cnt) || m.alloc(cnt * 32) || ng.alloc(cnt) || act.alloc(cnt * 8) || bad.alloc(cnt)) return VPIN_ENOMEM;
+  if (r_le32) {
+    if (r.alloc(cnt * 32)) return VPIN_ENOMEM;
+    VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  DecryptChain d(c);
+  int rc = d.run(c, "vpin_e2_client_round", sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
+  if (!rc) rc = launch_walk(c, t, (const fq*)d.mx.p, (const fq*)d.my.p, (const uint8_t*)d.fl.p, cnt, max_giant, v.p, f.p);
+  if (rc) return rc;
+  hipLaunchKernelGGL(e2_act_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const long long*)v.p, (const uint8_t*)f.p, cnt,
+                     relu ? 1 : 0, shift_bits, (uint32_t*)m.p, (uint8_t*)ng.p, (long long*)act.p, (uint8_t*)bad.p);
   VPIN_HIP_TRY(hipGetLastError());
-  if ((rc = e2_to_affine(c, (const e2_jac*)M.p, cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
-  return run_walk(c, t, (const fq*)mx.p, (const fq*)my.p, (const uint8_t*)fl.p, cnt, max_giant, v_out, found_out);
+  EncryptChain e(c);
+  if (r_le32 && (rc = e.run(c, g, h, r.p, m.p, ng.p, cnt, o1x, o1y, o1inf, o2x, o2y, o2inf))) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(v_out, v.p, cnt * 8, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(act_out, act.p, cnt * 8, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(bad_out, bad.p, cnt, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
 }
 
 }  // namespace client
