@@ -86,6 +86,8 @@ int vpin_ctx_set_shared_device(vpin_ctx* ctx, int on);
 /* commitment rows this context has handed to the row-per-lane kernel (msm_strip_kernel) since it was created: lets a test
  * or a scheduler see that the path it asked for is the one that ran */
 unsigned long long vpin_ctx_strip_rows_taken(vpin_ctx* ctx);
+/* rows committed through the row-table kernels so far (tests: the path under test is the one that ran) */
+unsigned long long vpin_ctx_row_table_rows(vpin_ctx* ctx);
 /* row chunks the bucket method (vpin_hyrax_commit_pippenger, VPIN_MSM_PIPPENGER) has launched on this context: a commitment
  * whose digit buffer would pass 2 GiB takes its rows in several (the 2^14 x 2^15 polynomials of a 2^25-constraint instance: 15) */
 unsigned long long vpin_ctx_pip_row_chunks(vpin_ctx* ctx);
@@ -223,6 +225,17 @@ size_t vpin_gens_count(const vpin_gens* g);
  * windows (W per scalar), [split, bases) c_hi-bit ones (0 when the table has a single segment); `bases` counts the
  * nb generators plus the prefix-sum bases S_k = g_0 + ... + g_{2^k - 1} behind them. */
 int vpin_gens_layout(const vpin_gens* g, size_t out[6]);
+/* The row table beside it, if the table has one: out = {c_row, W_row, bases covered, columns per segment of the row kernel}.
+ * T1[j][k] = (k+1) g_j for one window of c_row bits per generator; the row commitments of 2^24 scalars and more accumulate one
+ * sum per window from it and apply the powers of two once per row.  All 0 for a table without one. */
+int vpin_gens_row_layout(const vpin_gens* g, size_t out[4]);
+/* TEST ENTRY POINT, not for callers: the provers reach this commitment through vpin_snark_prove*; it validates its indices on the
+ * host and copies synchronously.  The derefs commitment on its own: Z = 8N scalars as L rows of R = 8N / L, whose rows [3N/R, 6N/R) are the col-derefs
+ * vectors e_ry[col_idx[m][i]] of the three matrices; col_idx = 3 x N column indices on the host, hot[m] = the column of matrix m
+ * whose entries are added as hot[m]-multiples computed once (0xffffffff: none).  out_compressed: L x 32 bytes, the bytes of
+ * DensePolynomial::commit(gens, None). */
+int vpin_hyrax_commit_derefs(vpin_ctx* ctx, const vpin_gens* g, const vpin_table* Z, size_t L, size_t N, const uint32_t* col_idx,
+                             const uint32_t hot[3], const vpin_table* e_ry, uint8_t* out_compressed);
 /* bytes per window-table entry (affine Niels point, possibly padded to a cache line) */
 size_t vpin_gens_entry_bytes(void);
 /* DensePolynomial::commit_inner (Spartan/src/dense_mlpoly.rs:160-175): Z viewed as L rows

@@ -740,6 +740,13 @@ class Context:
         L.vpin_ctx_pip_row_chunks.restype = C.c_ulonglong
         return int(L.vpin_ctx_pip_row_chunks(self.h))
 
+    def row_table_rows(self):
+        """rows committed through the row-table kernels so far (vpin_ctx_row_table_rows)"""
+        L = lib()
+        L.vpin_ctx_row_table_rows.argtypes = [C.c_void_p]
+        L.vpin_ctx_row_table_rows.restype = C.c_ulonglong
+        return int(L.vpin_ctx_row_table_rows(self.h))
+
     def strip_rows_taken(self):
         """rows handed to the row-per-lane commitment kernel so far (vpin_ctx_strip_rows_taken)"""
         L = lib()
@@ -867,6 +874,18 @@ class Context:
         out = np.zeros((Ls, 32), dtype=np.uint8)
         _chk(lib().vpin_hyrax_commit(self.h, gens.h, Z.h, b.ctypes.data_as(C.c_void_p), Ls, blind_base,
                                      out.ctypes.data_as(C.c_void_p)), "vpin_hyrax_commit")
+        return out
+
+    def hyrax_commit_derefs(self, gens, Z, Ls, N, col_idx, hot, e_ry):
+        """vpin_hyrax_commit_derefs: the derefs commitment alone (col_idx: (3, N) uint32; hot: three columns, None for no hot column)"""
+        idx = np.ascontiguousarray(col_idx, dtype=np.uint32).reshape(3 * N)
+        h = (C.c_uint32 * 3)(*[0xFFFFFFFF if x is None else int(x) for x in hot])
+        out = np.zeros((Ls, 32), dtype=np.uint8)
+        L = lib()
+        L.vpin_hyrax_commit_derefs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
+        _chk(L.vpin_hyrax_commit_derefs(self.h, gens.h, Z.h, Ls, N, idx.ctypes.data_as(C.c_void_p), h, e_ry.h,
+                                        out.ctypes.data_as(C.c_void_p)), "vpin_hyrax_commit_derefs")
         return out
 
     def hyrax_commit_pippenger(self, gens, Z, blinds, blind_base, Ls=None, c_bits=0):

@@ -100,6 +100,7 @@ struct vpin_ctx {
   vpin::fq tail_sums[3 * 18];   // host copies of the current tail round's results (assembled from the mailbox pieces)
   vpin::fq tail_final[6 * 18];
   unsigned long long pip_row_chunks = 0;    // row chunks launched by the bucket method so far (vpin_ctx_pip_row_chunks: tests)
+  unsigned long long row_table_rows = 0;    // rows committed by msm_rows_win_kernel so far (vpin_ctx_row_table_rows: tests)
   unsigned long long strip_rows_taken = 0;  // rows handed to msm_strip_kernel so far (vpin_ctx_strip_rows_taken: tests)
   bool low_memory = false;     // vpin_ctx_set_low_memory: trade ~1 % of a large proof's time for a third less working set
   bool shared_device = false;  // other contexts prove on this device at the same time (vpin_ctx_set_shared_device)
@@ -197,6 +198,14 @@ int slices_combine(vpin_ctx* c, const fq* d_LZs, int S, size_t Rs, const uint8_t
 
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
+// vpin_gens_shared by the provers' policy (sat_prepare, the SPARK views): where the budget holds a row table of 13..16 bits
+// beside an 8-bit multi-window table, that pair is built; otherwise exactly vpin_gens_shared's table.  The registry is one: a
+// table the public entry point built serves a prover too; only a narrowed pair is never returned by the public entry point.
+// vpin_hyrax_commit for scalars the caller knows to be mostly short (SNARK::encode's combined polynomials: addresses, timestamps,
+// counters): always the multi-window walk, never the row-table kernels (measured 4x slower on such polynomials)
+int hyrax_commit_walk(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, const uint8_t* blinds, size_t L, size_t blind_base,
+                      uint8_t* out_compressed);
+int gens_shared_rows(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, size_t nb, size_t budget_gb, const vpin_gens** out);
 // few-row fixed-base MSM over device-resident scalars (msm.hip): rows x ncols Montgomery scalars ->
 // rows x vpin_gens_msm_parts_count(ncols) partial points (canonical X|Y|Z|T) in host memory; synchronises
 int gens_msm_parts_dev(vpin_ctx* c, const vpin_gens* g, const fq* d_scalars, size_t rows, size_t ncols, uint8_t* parts_xyzt);

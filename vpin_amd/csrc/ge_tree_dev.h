@@ -112,35 +112,52 @@ __device__ __forceinline__ fp fp_pick(bool c, const fp& a, const fp& b) {
 // split > 0 (a power of two below n): the entries alternate in runs of `split` between two sums (index & split); the
 // level that would mix them is skipped and the levels below it reduce both runs: sh[0] = sum of the entries with
 // (index & split) == 0, sh[split] = sum of the others.
-__device__ __forceinline__ void ge_tree_quad(ge_ext* sh, int n, int split = 0) {
-  const int role = threadIdx.x & 3, qbase = (threadIdx.x & 63) & ~3;
+// sh[i] += sh[j] by the four lanes of a quad (role = lane & 3, qbase = the quad's first lane in its wave); all four call it
+__device__ __forceinline__ void ge_quad_add_into(ge_ext* sh, int i, int j, int role, int qbase) {
   const fp* shf = reinterpret_cast<const fp*>(sh);
   fp* shw = reinterpret_cast<fp*>(sh);
+  // role 0: (Y1-X1)(Y2-X2)   role 1: (Y1+X1)(Y2+X2)   role 2: 2d T1 T2   role 3: 2 Z1 Z2
+  const int f0 = role < 2 ? 1 : (role == 2 ? 3 : 2);  // Y | T | Z
+  const fp p0 = shf[4 * i + f0], q0 = shf[4 * j + f0];
+  fp u = p0, v = q0;
+  if (role < 2) {  // uniform per quad pair: both take the same instructions, the select below is per lane
+    const fp p1 = shf[4 * i], q1 = shf[4 * j];
+    u = fp_pick(role == 0, fp_sub(p0, p1), fp_add(p0, p1));
+    v = fp_pick(role == 0, fp_sub(q0, q1), fp_add(q0, q1));
+  }
+  fp m = fp_mul(u, v);
+  m = fp_mul(m, fp_pick(role == 2, FP_D2(), fp_one()));
+  m = fp_pick(role == 3, fp_add(m, m), m);
+  const fp a = fp_shfl_from(m, qbase), b = fp_shfl_from(m, qbase + 1), c = fp_shfl_from(m, qbase + 2),
+           d = fp_shfl_from(m, qbase + 3);
+  const fp E = fp_sub(b, a), H = fp_add(b, a), F = fp_sub(d, c), G = fp_add(d, c);
+  // X3 = E F, Y3 = G H, Z3 = F G, T3 = E H
+  u = fp_pick(role == 0 || role == 3, E, fp_pick(role == 1, G, F));
+  v = fp_pick(role == 0, F, fp_pick(role == 2, G, H));
+  shw[4 * i + role] = fp_mul(u, v);
+}
+__device__ __forceinline__ void ge_tree_quad(ge_ext* sh, int n, int split = 0) {
+  const int role = threadIdx.x & 3, qbase = (threadIdx.x & 63) & ~3;
   for (int s = n / 2; s >= 1; s >>= 1) {
     if (s == split) continue;
     const int items = s < split ? 2 * s : s;
     for (int w = threadIdx.x >> 2; w < items; w += (int)(blockDim.x >> 2)) {
       const int i = w < s ? w : split + (w - s);
-      // role 0: (Y1-X1)(Y2-X2)   role 1: (Y1+X1)(Y2+X2)   role 2: 2d T1 T2   role 3: 2 Z1 Z2
-      const int f0 = role < 2 ? 1 : (role == 2 ? 3 : 2);  // Y | T | Z
-      const fp p0 = shf[4 * i + f0], q0 = shf[4 * (i + s) + f0];
-      fp u = p0, v = q0;
-      if (role < 2) {  // uniform per quad pair: both take the same instructions, the select below is per lane
-        const fp p1 = shf[4 * i], q1 = shf[4 * (i + s)];
-        u = fp_pick(role == 0, fp_sub(p0, p1), fp_add(p0, p1));
-        v = fp_pick(role == 0, fp_sub(q0, q1), fp_add(q0, q1));
-      }
-      fp m = fp_mul(u, v);
-      m = fp_mul(m, fp_pick(role == 2, FP_D2(), fp_one()));
-      m = fp_pick(role == 3, fp_add(m, m), m);
-      const fp a = fp_shfl_from(m, qbase), b = fp_shfl_from(m, qbase + 1), c = fp_shfl_from(m, qbase + 2),
-               d = fp_shfl_from(m, qbase + 3);
-      const fp E = fp_sub(b, a), H = fp_add(b, a), F = fp_sub(d, c), G = fp_add(d, c);
-      // X3 = E F, Y3 = G H, Z3 = F G, T3 = E H
-      u = fp_pick(role == 0 || role == 3, E, fp_pick(role == 1, G, F));
-      v = fp_pick(role == 0, F, fp_pick(role == 2, G, H));
-      shw[4 * i + role] = fp_mul(u, v);
+      ge_quad_add_into(sh, i, i + s, role, qbase);
     }
+    __syncthreads();
+  }
+}
+// The same tree over entries that belong to W interleaved sums, entry t to sum t mod W (the lanes of the row-table kernel:
+// lane t accumulates window t mod W): sh[w] = sum of sh[w], sh[w + W], sh[w + 2W], .. below n, for every w < W.  Any W >= 1.
+__device__ __forceinline__ void ge_tree_quad_strided(ge_ext* sh, int n, int W) {
+  const int role = threadIdx.x & 3, qbase = (threadIdx.x & 63) & ~3;
+  int P = 1;
+  while (P * W < n) P <<= 1;  // the entries of a sum: at most P
+  for (int s = P / 2; s >= 1; s >>= 1) {
+    const int items = s * W;  // entry i < s W takes entry i + s W (the live entries are those below 2 s W)
+    for (int i = threadIdx.x >> 2; i < items; i += (int)(blockDim.x >> 2))
+      if (i + items < n) ge_quad_add_into(sh, i, i + items, role, qbase);
     __syncthreads();
   }
 }

@@ -15,6 +15,15 @@
 // digits are skipped (the witness is ~40% zero padding and full of 0/1 bits), like dalek's
 // vartime MSM.  One 256-thread workgroup per row; per-thread partial sums are combined by
 // an LDS tree.  Integer-ALU bound (~8 field multiplies per table add); no MFMA.
+//
+// Beside it, where the provers' budget holds one, a ROW TABLE of a single window per generator: T1[j][k] = (k+1) * g_j with 13..16
+// bit windows (64 GiB for 16386 generators at 16 bits in 128-byte slots).  A row commitment is C_i = sum_w 2^(c w) A_iw with
+// A_iw = sum_j digit_w(s_ij) g_j, and the sums A_iw need the multiples of g_j alone: msm_rows_win_kernel keeps one accumulator per
+// lane and window, msm_rows_finish_kernel applies the powers of two once per ROW (c (W - 1) doublings against the 2^13..2^14
+// scalars x 16 additions of the row: free).  A folded scalar then costs 16 additions instead of 21, and the multi-window table,
+// narrowed to 8 bits, is left to the kernels that multiply one scalar by one base (bullet rounds, few-row MSMs, blind terms,
+// hot-column tables, constant rows).  Commitments below 2^24 scalars, a rank's share of a split commitment and tables built
+// through the public entry points keep the multi-window walk.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -58,6 +67,12 @@ struct vpin_gens {
   size_t split = 0;
   int c = 12, W = 22, E = 2048;     // window bits, windows, entries per window (= 2^(c-1)) of the first segment
   int c_hi = 8, W_hi = 32, E_hi = 128;
+  // Row table (optional): T1[j][k] = (k + 1) * g_j for the first n_row bases, k < E_row = 2^(c_row - 1), in the same slots.  The
+  // row commitments walk it (msm_rows_win_kernel); everything that multiplies ONE scalar by one base stays on the table above.
+  vpin::fp* table_row = nullptr;
+  size_t n_row = 0;
+  int c_row = 0, W_row = 0, E_row = 0;
+  bool narrowed = false;  // the multi-window table gave way to the row table (8-bit windows): not what the public entry points build
 };
 
 namespace vpin {
@@ -85,6 +100,19 @@ __device__ __forceinline__ TableSeg table_seg(const TableView& tv, size_t j) {
   if (j < tv.split) return TableSeg{tv.t, j, tv.split, tv.c, tv.W, tv.E, tv.s32};
   return TableSeg{tv.t_hi, j - tv.split, tv.nbt - tv.split, tv.c_hi, tv.W_hi, tv.E_hi, tv.s32};
 }
+
+// The row table: one window per generator.  A row commitment is sum_w 2^(c w) A_w with A_w = sum_j digit_w(s_j) g_j, and every
+// A_w needs the multiples of g_j itself only; the powers of two are applied once per row (msm_rows_finish_kernel).
+struct RowTable {
+  const fp* t;  // [n][E] slots
+  size_t n;     // bases [0, n)
+  int c, W, E, s32;
+  __device__ __forceinline__ const ge_niels* entry(size_t j, uint32_t d) const {  // multiple d + 1 of base j
+    return reinterpret_cast<const ge_niels*>(t + (j * (size_t)E + d) * (size_t)s32);
+  }
+};
+// windows of c bits for a sign-folded scalar (below 2^252): the top digit, carry included, must not exceed 2^(c-1), the last entry
+constexpr int row_windows(int c) { return (253 + c - 1) / c; }
 
 // ---- table construction ---------------------------------------------------------------
 
@@ -613,6 +641,197 @@ __global__ __launch_bounds__(64) void strip_combine_kernel(const ge_ext* __restr
   ge_store(o, a);
 }
 
+// ---- row commitment over the row table: one accumulator per lane and WINDOW ------------------------------------------------
+// Lane l of a workgroup owns window l mod W and accumulates A_w = sum_j digit_w(s_j) g_j over the workgroup's columns from the
+// one-window table T1[j][k] = (k+1) g_j; msm_rows_finish_kernel then forms sum_w 2^(c w) A_w per row (c (W-1) doublings per
+// ROW instead of a table of every shifted generator: 16-bit windows fit where the multi-window table stops at 12, and a folded
+// scalar is 16 additions instead of 21).  Per segment of `segn` columns:
+//   phase 1: every scalar is read, converted out of Montgomery form, sign-folded and recoded ONCE into W signed digits, which go
+//            to LDS as dig[w][column]: magnitude - 1 in bits 0..14, sign in bit 15, kNoDigit for a zero digit (and for every
+//            digit of a zero scalar or a hot-column entry);
+//   phase 2: the lanes of window w stride over dig[w][.]; a lane skips zero digits on its own (a short LDS scan, not an idle
+//            addition), and the entry of its next digit is requested before the current addition, as in table_mul_acc10.
+// The hot-column entries of a derefs row are added afterwards by ALL lanes (add_cached from T[m], as in msm_rows_hot_kernel)
+// and tree-summed into window 0; a constant row is s * S_k over the multi-window table, as before.  LDS: 48 KiB of digits,
+// which the two reductions at the end reuse -- what msm_rows_kernel takes, so msm_lds_pad keeps its meaning.
+constexpr int kRowLdsBytes = 48 * 1024;
+constexpr uint16_t kNoDigit = 0xffffu;  // never a digit: a negative digit's magnitude is below 2^(c-1), c <= 16
+// columns per segment for W windows (host and device agree on it)
+static inline int row_segment(int W) { return ((kRowLdsBytes / 2) / W) & ~3; }
+
+// One signed digit of a sign-folded canonical scalar, low end first: takes the low c bits of s and the carry of the window below,
+// shifts s right by c bits, and returns magnitude - 1 in bits 0..14 with the sign in bit 15, or kNoDigit for a zero digit.
+// flip: the scalar was folded (s -> q - s), every digit changes sign.  A digit of exactly 2^(c-1) is taken as +2^(c-1) without the
+// fold and as -2^(c-1) (carrying) with it, so that AFTER the flip the negative magnitudes stay below 2^(c-1): 16 bits hold a
+// 16-bit window's digits.  The top window is never negated (its value is at most 2^(c-1), see row_windows).
+__device__ __forceinline__ uint16_t row_digit(fq& s, uint32_t& carry, int c, bool flip, bool top) {
+  const uint32_t mask = (1u << c) - 1u, half = 1u << (c - 1);
+  const uint32_t v = (s.v[0] & mask) + carry;
+#pragma unroll
+  for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], c);
+  s.v[7] >>= c;
+  const bool neg = !top && (flip ? v >= half : v > half);
+  const uint32_t mag = neg ? (mask + 1u) - v : v;
+  carry = neg ? 1u : 0u;
+  return mag ? (uint16_t)((mag - 1u) | ((neg != flip) ? 0x8000u : 0u)) : kNoDigit;
+}
+
+__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
+                                                                     const fq* __restrict__ extra, int n_extra, size_t extra_base0,
+                                                                     TableView tv, RowTable rt, HotRows hr, int segn,
+                                                                     ge_ext* __restrict__ parts, size_t row_base, size_t row_step,
+                                                                     int z_compact) {
+  const size_t row = row_base + (size_t)blockIdx.x * row_step;  // row of the polynomial; parts[] is indexed by blockIdx.x
+  const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
+  const fq* xr = extra + (size_t)blockIdx.x * (size_t)n_extra;
+  const int W = rt.W;
+  ge_ext* o = parts + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (size_t)W;  // the W window sums of this (row, chunk)
+  __shared__ __align__(16) unsigned char lds[kRowLdsBytes];
+  __shared__ uint32_t n_hot;
+  // a row of one repeated scalar (padding tails): s * (g_0 + ... + g_{ncols-1}) into window 0, as in msm_rows_kernel
+  if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
+    const fq first = fq_load(zr);
+    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
+      int same = 1;
+      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
+      if (__syncthreads_and(same)) {
+        if (threadIdx.x == 0) {
+          RowAcc acc;
+          if (blockIdx.y == 0) {  // the first chunk owns the row, the others add nothing
+            if (!fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
+            for (int e = 0; e < n_extra; e++) {
+              const fq x = fq_load(xr + e);
+              if (!fq_is_zero(x)) acc.mul_acc(fq_from_mont(x), tv, extra_base0 + e);
+            }
+          }
+          ge_store(o, acc.ext());
+        } else if ((int)threadIdx.x < W) {
+          ge_store_identity(o + threadIdx.x);
+        }
+        return;
+      }
+    }
+  }
+  const uint32_t* idx = nullptr;
+  const ge_cached* T = nullptr;
+  uint32_t hot = 0xffffffffu;
+  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
+    const size_t m = (row - hr.row0) / hr.rows_per_vec;
+    if (hr.hot[m] != 0xffffffffu) {
+      hot = hr.hot[m];
+      T = hr.T[m];
+      idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols;
+    }
+  }
+  const size_t total = ncols + (size_t)n_extra;
+  const size_t per = (total + gridDim.y - 1) / gridDim.y;
+  const size_t j0 = (size_t)blockIdx.y * per, j1 = (j0 + per < total) ? j0 + per : total;
+  // this lane's window, its rank among the window's lanes and their number
+  const int w = (int)threadIdx.x % W, r = (int)threadIdx.x / W, nw = (kMsmBlock - 1 - w + W) / W;
+  uint16_t* dig = reinterpret_cast<uint16_t*>(lds);
+  ge10 acc = ge10_identity();
+  for (size_t seg = j0; seg < j1; seg += (size_t)segn) {
+    const uint32_t n = (uint32_t)((seg + (size_t)segn < j1) ? (size_t)segn : j1 - seg);
+    for (uint32_t jl = threadIdx.x; jl < n; jl += kMsmBlock) {
+      const size_t j = seg + jl;
+      fq s = fq_load(j < ncols ? zr + j : xr + (j - ncols));
+      const bool live = !fq_is_zero(s) && !(idx && j < ncols && idx[j] == hot);
+      bool flip = false;
+      if (live) {
+        s = fq_from_mont(s);
+        flip = fq_fold_sign(s);
+      }
+      uint32_t carry = 0;
+#pragma unroll 1
+      for (int ww = 0; ww < W; ww++) {
+        uint16_t d = kNoDigit;
+        if (live) d = row_digit(s, carry, rt.c, flip, ww == W - 1);
+        dig[(size_t)ww * segn + jl] = d;
+      }
+    }
+    __syncthreads();
+    const uint16_t* dg = dig + (size_t)w * segn;
+    uint32_t k = (uint32_t)r;
+    // the next non-zero digit of this lane's stride: its table entry is requested, false when the list is exhausted
+    auto fetch = [&](ge_niels& e, bool& neg) -> bool {
+      while (k < n) {
+        const uint32_t kk = k;
+        k += (uint32_t)nw;
+        const uint16_t d = dg[kk];
+        if (d != kNoDigit) {
+          const size_t j = seg + kk;
+          e = ge_load(rt.entry(j < ncols ? j : extra_base0 + (j - ncols), d & 0x7fffu));
+          neg = (d >> 15) != 0;
+          return true;
+        }
+      }
+      return false;
+    };
+    ge_niels e_cur;
+    bool neg_cur = false;
+    bool have_cur = fetch(e_cur, neg_cur);
+    while (have_cur) {
+      ge_niels e_next;
+      bool neg_next = false;
+      const bool have_next = fetch(e_next, neg_next);
+      acc = ge10_add_niels(acc, e_cur, neg_cur);
+      e_cur = e_next;
+      neg_cur = neg_next;
+      have_cur = have_next;
+    }
+    __syncthreads();
+  }
+  // the lanes of each window, summed: sh[w] = A_w of this workgroup
+  ge_ext* sh = reinterpret_cast<ge_ext*>(lds);
+  sh[threadIdx.x] = ge10_to_ext(acc);
+  __syncthreads();
+  ge_tree_quad_strided(sh, kMsmBlock, W);
+  ge_ext mine = ge_identity();
+  if ((int)threadIdx.x < W) mine = sh[threadIdx.x];
+  __syncthreads();
+  if (idx) {  // uniform over the workgroup: the hot entries of this chunk, all lanes, into window 0
+    uint16_t* list = reinterpret_cast<uint16_t*>(lds);
+    RowAcc hacc;
+    uint32_t any = 0;
+    const size_t c1 = j1 < ncols ? j1 : ncols;
+    for (size_t seg = j0; seg < c1; seg += kSeg) {
+      const size_t seg_end = (seg + kSeg < c1) ? seg + kSeg : c1;
+      if (threadIdx.x == 0) n_hot = 0;
+      __syncthreads();
+      for (size_t j = seg + threadIdx.x; j < seg_end; j += kMsmBlock)
+        if (idx[j] == hot && !fq_is_zero(fq_load(zr + j))) list[atomicAdd(&n_hot, 1u)] = (uint16_t)(j - seg);
+      __syncthreads();
+      const uint32_t nh = n_hot;
+      any |= nh;
+      for (uint32_t kk = threadIdx.x; kk < nh; kk += kMsmBlock) hacc.add_cached(ge_load(T + seg + list[kk]));
+      __syncthreads();
+    }
+    if (any) {  // n_hot is read by every lane between two barriers: uniform
+      sh[threadIdx.x] = hacc.ext();
+      __syncthreads();
+      ge_tree_quad(sh, kMsmBlock);
+      if (threadIdx.x == 0) mine = ge_add(mine, sh[0]);
+    }
+  }
+  if ((int)threadIdx.x < W) ge_store(o + threadIdx.x, mine);
+}
+
+// out[row] = sum_w 2^(c w) * (sum over the row's chunks of window w's partial point): one lane per row.  The chunk sums are
+// written over the first chunk's slots, then Horner runs from the top window down (ge10_horner_windows).
+__global__ __launch_bounds__(64) void msm_rows_finish_kernel(ge_ext* __restrict__ parts, size_t rows, int chunks, int W, int c,
+                                                             ge_ext* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  ge_ext* p = parts + i * (size_t)chunks * (size_t)W;
+  if (chunks > 1)
+    for (int w = 0; w < W; w++) {
+      ge_ext a = ge_load(p + w);
+      for (int k = 1; k < chunks; k++) a = ge_add(a, ge_load(p + (size_t)k * W + w));
+      ge_store(p + w, a);
+    }
+  ge_store(out + i, ge10_to_ext(ge10_horner_windows(p, W, [c](int) { return c; })));
+}
+
 // Profiling aid (vpin_prof_enable(ctx, 2)): the affine table additions msm_rows_kernel performs for the same
 // arguments -- non-zero signed digits of every non-zero scalar, one scalar for a constant row -- summed into *count.
 __device__ __forceinline__ uint32_t count_digits(fq s, const TableView& tv, size_t j) {
@@ -629,11 +848,19 @@ __device__ __forceinline__ uint32_t count_digits(fq s, const TableView& tv, size
   }
   return n;
 }
+// the same for a scalar that msm_rows_win_kernel recodes into W digits of c bits
+__device__ __forceinline__ uint32_t count_digits_row(fq s, int c, int W) {
+  const bool flip = fq_fold_sign(s);
+  uint32_t carry = 0, n = 0;
+  for (int w = 0; w < W; w++) n += row_digit(s, carry, c, flip, w == W - 1) != kNoDigit;
+  return n;
+}
+// c_row != 0: the launch goes to msm_rows_win_kernel with W_row windows of c_row bits (constant rows stay on the multi-window table)
 __global__ __launch_bounds__(kMsmBlock) void msm_count_adds_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
                                                                    const fq* __restrict__ extra, int n_extra, size_t extra_base0,
                                                                    TableView tv, unsigned long long* __restrict__ count,
                                                                    HotRows hr = HotRows{}, size_t row_base = 0, size_t row_step = 1,
-                                                                   int z_compact = 0) {
+                                                                   int z_compact = 0, int c_row = 0, int W_row = 0) {
   const size_t row = row_base + (size_t)blockIdx.x * row_step;
   const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
   // msm_rows_hot_kernel: the hot-column entries are not table additions
@@ -656,11 +883,11 @@ __global__ __launch_bounds__(kMsmBlock) void msm_count_adds_kernel(const fq* __r
   if (!constant)
     for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) {
       const fq s = fq_load(zr + j);
-      if (!fq_is_zero(s) && !(hidx && hidx[j] == hot)) n += count_digits(fq_from_mont(s), tv, j);
+      if (!fq_is_zero(s) && !(hidx && hidx[j] == hot)) n += c_row ? count_digits_row(fq_from_mont(s), c_row, W_row) : count_digits(fq_from_mont(s), tv, j);
     }
   for (int e = threadIdx.x; e < n_extra; e += kMsmBlock) {
     const fq x = fq_load(extra + row * (size_t)n_extra + e);
-    if (!fq_is_zero(x)) n += count_digits(fq_from_mont(x), tv, extra_base0 + e);
+    if (!fq_is_zero(x)) n += (c_row && !constant) ? count_digits_row(fq_from_mont(x), c_row, W_row) : count_digits(fq_from_mont(x), tv, extra_base0 + e);
   }
   __shared__ uint32_t sh[kMsmBlock];
   sh[threadIdx.x] = n;
@@ -979,12 +1206,12 @@ using namespace vpin;
 
 extern "C" {
 
-static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, int cmax, vpin_gens** out);
+static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, int cmax, bool row_policy, vpin_gens** out);
 
 // The table budget is a speed knob (every window bit saves ~8 % of a commitment), so it yields to what the device really has
 // at this moment: at most a third of the FREE memory (a co-tenant, another process's tables, a smaller part), and a failed
 // allocation halves it instead of failing the proof.  The instance, its decommitment and the proof temporaries need the rest.
-static int gens_build(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, vpin_gens** out) {
+static int gens_build(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, bool row_policy, vpin_gens** out) {
   (void)hipSetDevice(c->device);
   size_t free_b = 0, total_b = 0;
   // (not asked in a one-shot process: its tables are sized by use, and the first hipMemGetInfo of a process costs 35-50 ms)
@@ -1013,7 +1240,7 @@ static int gens_build(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t b
     }
   }
   for (;;) {
-    int rc = gens_build_once(c, gens_xyzt, nb, budget, cmax, out);
+    int rc = gens_build_once(c, gens_xyzt, nb, budget, cmax, row_policy, out);
     if (rc != VPIN_ENOMEM || budget <= floor_b) return rc;
     (void)hipGetLastError();
     budget /= 2;
@@ -1030,7 +1257,23 @@ static size_t table_slot_bytes() {
   return v == 128 ? 128 : v == 96 ? 96 : (size_t)VPIN_NIELS_SLOT;
 }
 
-static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, int cmax, vpin_gens** out) {
+// The row table of the NEXT table built, forced: VPIN_ROW_TABLE_C = c (4..16) builds one of c-bit windows beside whatever
+// multi-window table the build path chooses, whatever the budget (tests: several windows, segments and carries at tiny sizes);
+// VPIN_ROW_TABLE = 0 builds none (A/B runs: the layout and the kernels of before).  Read per build.
+static int row_table_forced_bits() {
+  const char* e = getenv("VPIN_ROW_TABLE_C");
+  const int v = e ? atoi(e) : 0;
+  return v >= 4 && v <= 16 ? v : 0;
+}
+static bool row_table_off() {
+  const char* e = getenv("VPIN_ROW_TABLE");
+  return e && atoi(e) == 0;
+}
+// generators below which a stream gets no row table by policy: the row-table kernels take commitments of 2^24 scalars and more
+// (row_table_min_scalars), and a stream this short commits no such polynomial
+constexpr size_t kRowTableMinBases = 4096;
+
+static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, int cmax, bool row_policy, vpin_gens** out) {
   if (!c || !gens_xyzt || !out || nb == 0) return VPIN_EINVAL;
   const size_t slot = table_slot_bytes();
   (void)hipSetDevice(c->device);
@@ -1073,9 +1316,33 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
       fit(nbt - kSplitBases, budget - lo_bytes, g->c, &g->c_hi, &g->W_hi, &g->E_hi);
     }
   }
+  // The row table (see RowTable): the widest windows of 13..16 bits that fit the budget beside an 8-bit multi-window table of the
+  // whole stream -- 16 bits for the 16386 generators the derefs commitment walks are 64 GiB in 128-byte slots, 16 additions per
+  // folded scalar where the 12-bit multi-window table needs 21 in 88 GiB.  The multi-window table then serves the kernels that
+  // multiply ONE scalar by one base (bullet rounds, few-row MSMs, blind terms, hot-column tables, constant rows), which spread
+  // a scalar's windows over eight lanes: 32 windows of 8 bits are four per lane, as 29 of 9 bits would be.
+  // By policy only for the provers' tables of a long-lived process (vpin::gens_shared_rows: sat_prepare and the SPARK views) and
+  // only for streams long enough to commit 2^24 scalars at once; when no such table fits, the geometry is exactly the one above.
+  const size_t n_row = std::min(nb, kSplitBases);
+  int c_row = row_table_forced_bits();
+  if (!c_row && row_policy && !row_table_off() && c->expected_proofs == 0 && nb >= kRowTableMinBases) {
+    const size_t mw8 = nbt * (size_t)32 * 128 * slot;
+    for (int cc = 16; cc >= 13 && !c_row; cc--)
+      if (n_row * ((size_t)1 << (cc - 1)) * slot + mw8 <= budget) c_row = cc;
+    if (c_row) {
+      g->split = nbt;
+      g->c = 8; g->W = 32; g->E = 128;
+      g->narrowed = true;
+    }
+  }
+  if (c_row) {
+    g->n_row = n_row;
+    g->c_row = c_row; g->W_row = row_windows(c_row); g->E_row = 1 << (c_row - 1);
+  }
+  const size_t entries_row = g->n_row * (size_t)g->E_row;
   const size_t n_hi = nbt - g->split;
   const size_t entries = g->split * (size_t)g->W * g->E, entries_hi = n_hi * (size_t)g->W_hi * g->E_hi;
-  const size_t max_entries = entries > entries_hi ? entries : entries_hi;
+  const size_t max_entries = std::max(std::max(entries, entries_hi), entries_row);
   const size_t max_shifts = std::max(g->split * (size_t)g->W, n_hi * (size_t)g->W_hi);
   TraceLap lap(c, "gens_build");
   // temporaries come from the context pool, so the blocks go on to serve proof temporaries instead of being
@@ -1083,9 +1350,11 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
   DevBuf raw(c), b_shifts(c), b_prefix(c);
   if (raw.alloc(nbt * 128) != VPIN_OK || b_shifts.alloc(max_shifts * sizeof(ge_ext)) != VPIN_OK ||
       b_prefix.alloc(max_entries * sizeof(fp)) != VPIN_OK || driver_malloc((void**)&g->table, entries * slot) != hipSuccess ||
-      (n_hi && driver_malloc((void**)&g->table_hi, entries_hi * slot) != hipSuccess)) {
+      (n_hi && driver_malloc((void**)&g->table_hi, entries_hi * slot) != hipSuccess) ||
+      (entries_row && driver_malloc((void**)&g->table_row, entries_row * slot) != hipSuccess)) {
     if (g->table) (void)hipFree(g->table);
     if (g->table_hi) (void)hipFree(g->table_hi);
+    if (g->table_row) (void)hipFree(g->table_row);
     delete g;
     return VPIN_ENOMEM;
   }
@@ -1106,6 +1375,10 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
       hipLaunchKernelGGL(gens_table_kernel, dim3((unsigned)((n_hi * g->W_hi + 63) / 64)), dim3(64), 0, c->stream, shifts, n_hi,
                          g->W_hi, g->E_hi, g->table_hi, g->s32, prefix);
     }
+    // the row table: the generators themselves are the "shifts" of its one window (X | Y | Z | T is a ge_ext)
+    if (entries_row)
+      hipLaunchKernelGGL(gens_table_kernel, dim3((unsigned)((g->n_row + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)raw.p, g->n_row, 1,
+                         g->E_row, g->table_row, g->s32, prefix);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1125,6 +1398,7 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
     set_last_error("vpin_gens_create", e);
     (void)hipFree(g->table);
     if (g->table_hi) (void)hipFree(g->table_hi);
+    if (g->table_row) (void)hipFree(g->table_row);
     delete g;
     return VPIN_EHIP;
   }
@@ -1142,7 +1416,7 @@ static size_t default_budget() {
 }
 
 int vpin_gens_create(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, vpin_gens** out) {
-  return gens_build(c, gens_xyzt, nb, default_budget(), out);
+  return gens_build(c, gens_xyzt, nb, default_budget(), false, out);
 }
 
 // The first nb generators of a label's stream from 64 x nb bytes of SHAKE256 output (the caller's: host/transcript.h), mapped
@@ -1165,21 +1439,25 @@ int vpin_gens_map_stream(vpin_ctx* c, const uint8_t* stream64, size_t nb, uint8_
 // far serves every context, stream and polynomial size of that label.  Tables are immutable once
 // built; superseded (shorter) ones stay alive because other contexts may still hold them.
 namespace {
-struct RegEntry { int device; std::string label; vpin_gens* g; };
-struct Building { int device; std::string label; size_t nb; };
+// rows: asked for by the provers' policy (vpin::gens_shared_rows).  ONE registry serves both kinds of request -- a prover finds and
+// uses whatever table of its label covers its generators, a public table included (it then walks the multi-window table as before)
+// -- with one exception: a table whose multi-window part was narrowed beside a row table is never returned by the public entry
+// point, whose geometry must not depend on what a prover built before.
+struct RegEntry { int device; std::string label; vpin_gens* g; bool rows; };
+struct Building { int device; std::string label; size_t nb; bool rows; };
 std::mutex g_reg_mu;
 std::condition_variable g_reg_cv;
 std::vector<RegEntry> g_reg;
 std::vector<Building> g_building;  // tables under construction (the registry is unlocked meanwhile)
 }  // namespace
 
-int vpin_gens_shared(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, size_t nb, size_t budget_gb,
-                     const vpin_gens** out) {
+static int gens_shared_impl(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, size_t nb, size_t budget_gb, bool rows,
+                            const vpin_gens** out) {
   if (!c || !label || !out || nb == 0) return VPIN_EINVAL;
   auto lookup = [&]() -> const vpin_gens* {
     const vpin_gens* best = nullptr;
     for (auto& e : g_reg)
-      if (e.device == c->device && e.label == label && e.g->nb >= nb && (!best || e.g->nb < best->nb)) best = e.g;
+      if (e.device == c->device && e.label == label && (rows || !e.g->narrowed) && e.g->nb >= nb && (!best || e.g->nb < best->nb)) best = e.g;
     return best;
   };
   {
@@ -1189,7 +1467,7 @@ int vpin_gens_shared(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, s
       // another thread is building a table that will cover this request: wait for it instead of building a second one
       // (tens of GB each); a shorter or different one under way does not help
       bool covered = false;
-      for (auto& b : g_building) covered = covered || (b.device == c->device && b.label == label && b.nb >= nb);
+      for (auto& b : g_building) covered = covered || (b.device == c->device && b.label == label && (rows || !b.rows) && b.nb >= nb);
       if (!covered) break;
       g_reg_cv.wait(lock);
     }
@@ -1201,21 +1479,26 @@ int vpin_gens_shared(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, s
       if (e.device == c->device && e.label == label && !said.exchange(true))
         fprintf(stderr, "vpin_gens_shared: a table of \"%s\" for %zu generators is built beside the one for %zu (both stay allocated): "
                         "call vpin_spark_prepare / vpin_sat_prepare with the largest shape first\n", label, nb, e.g->nb);
-    g_building.push_back(Building{c->device, label, nb});
+    g_building.push_back(Building{c->device, label, nb, rows});
   }
   // Built with the registry unlocked: other contexts of the process keep finding their tables, and building tables of other
   // labels, meanwhile.
   vpin_gens* g = nullptr;
-  const int rc = gens_build(c, gens_xyzt, nb, budget_gb ? (budget_gb << 30) : default_budget(), &g);
+  const int rc = gens_build(c, gens_xyzt, nb, budget_gb ? (budget_gb << 30) : default_budget(), rows, &g);
   std::lock_guard<std::mutex> lock(g_reg_mu);
   for (size_t i = 0; i < g_building.size(); i++)
-    if (g_building[i].device == c->device && g_building[i].label == label && g_building[i].nb == nb) { g_building.erase(g_building.begin() + (long)i); break; }
+    if (g_building[i].device == c->device && g_building[i].label == label && g_building[i].nb == nb && g_building[i].rows == rows) { g_building.erase(g_building.begin() + (long)i); break; }
   if (!rc) {
-    g_reg.push_back(RegEntry{c->device, label, g});
+    g_reg.push_back(RegEntry{c->device, label, g, rows});
     *out = g;
   }
   g_reg_cv.notify_all();  // also on failure: the waiters then build for themselves
   return rc;
+}
+
+int vpin_gens_shared(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, size_t nb, size_t budget_gb,
+                     const vpin_gens** out) {
+  return gens_shared_impl(c, label, gens_xyzt, nb, budget_gb, false, out);
 }
 
 size_t vpin_gens_shared_bytes(int device) {
@@ -1224,7 +1507,8 @@ size_t vpin_gens_shared_bytes(int device) {
   for (auto& e : g_reg)
     if (e.device == device)
       total += (size_t)32 * (size_t)e.g->s32 * ((size_t)e.g->W * e.g->split * (size_t)e.g->E +
-                                     (e.g->split < e.g->nbt ? (size_t)e.g->W_hi * (e.g->nbt - e.g->split) * (size_t)e.g->E_hi : 0));
+                                     (e.g->split < e.g->nbt ? (size_t)e.g->W_hi * (e.g->nbt - e.g->split) * (size_t)e.g->E_hi : 0) +
+                                     e.g->n_row * (size_t)e.g->E_row);
   return total;
 }
 
@@ -1235,6 +1519,7 @@ void vpin_gens_shared_clear(void) {
     (void)hipDeviceSynchronize();
     if (e.g->table) (void)hipFree(e.g->table);
     if (e.g->table_hi) (void)hipFree(e.g->table_hi);
+    if (e.g->table_row) (void)hipFree(e.g->table_row);
     delete e.g;
   }
   g_reg.clear();
@@ -1245,6 +1530,7 @@ void vpin_gens_free(vpin_ctx* c, vpin_gens* g) {
   if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }
   if (g->table) (void)hipFree(g->table);
   if (g->table_hi) (void)hipFree(g->table_hi);
+  if (g->table_row) (void)hipFree(g->table_row);
   delete g;
 }
 
@@ -1254,6 +1540,12 @@ int vpin_gens_layout(const vpin_gens* g, size_t out[6]) {
   if (!g || !out) return VPIN_EINVAL;
   out[0] = (size_t)g->c; out[1] = (size_t)g->W; out[2] = g->split;
   out[3] = g->split < g->nbt ? (size_t)g->c_hi : 0; out[4] = g->split < g->nbt ? (size_t)g->W_hi : 0; out[5] = g->nbt;
+  return VPIN_OK;
+}
+// the row table beside it: out = {c_row, W_row, bases covered, columns per LDS segment of the row kernel}; all 0 without one
+int vpin_gens_row_layout(const vpin_gens* g, size_t out[4]) {
+  if (!g || !out) return VPIN_EINVAL;
+  out[0] = (size_t)g->c_row; out[1] = (size_t)g->W_row; out[2] = g->n_row; out[3] = g->c_row ? (size_t)row_segment(g->W_row) : 0;
   return VPIN_OK;
 }
 size_t vpin_gens_entry_bytes(void) { return table_slot_bytes(); }  // of the next table built (VPIN_TABLE_SLOT)
@@ -1289,8 +1581,57 @@ static unsigned msm_lds_pad(const vpin_ctx* c) {
   return env_pad >= 0 ? (unsigned)env_pad : (c->shared_device ? kSharedPad : 0u);
 }
 
+static inline RowTable row_view(const vpin_gens* g) {
+  return RowTable{g->table_row, g->n_row, g->c_row, g->W_row, g->E_row, g->s32};
+}
+
+// Scalars from which a commitment goes to the row-table kernels.  Their finishing pass is one lane per row running c (W - 1) = 240
+// doublings and the chunk sums in sequence: 0.56 .. 1.54 ms, 0.73 ms on average (profiles/r12_kernel_trace_row_table.txt), whatever
+// the size, against 24 % of a walk that takes ~1 ms per 2^20 full-width scalars: at 2^24 scalars the pass costs a fifth of what the
+// table saves, at 2^22 most of it.  The threshold was set before that measurement, assuming 1.4 ms, and has not been swept.  VPIN_MSM_ROW_MIN = n overrides (tests: 0; read per call);
+// VPIN_MSM_ROW_TABLE = 0 keeps every commitment on the multi-window walk (A/B runs and parity tests; read per call).
+static size_t row_table_min_scalars() {
+  const char* e = getenv("VPIN_MSM_ROW_MIN");
+  return e ? (size_t)atoll(e) : (size_t)1 << 24;
+}
+static bool row_table_use(const vpin_ctx* c, const vpin_gens* g, size_t rows, size_t ncols, int n_extra, size_t extra_base0) {
+  if (!g->table_row || c->comm != nullptr) return false;  // a rank's share of a split commitment keeps the walk
+  const char* e = getenv("VPIN_MSM_ROW_TABLE");
+  if (e && atoi(e) == 0) return false;
+  if (ncols > g->n_row || (n_extra && extra_base0 + (size_t)n_extra > g->n_row)) return false;
+  return rows * (ncols + (size_t)n_extra) >= row_table_min_scalars();
+}
+
+// rows x (ncols + n_extra) scalars over the row table: msm_rows_win_kernel on `chunks` column chunks per row, then the finishing
+// pass into d_points[rows].  hr: the derefs commitment's hot columns (HotRows{} for plain rows).
+static int msm_rows_win(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols, const fq* d_extra,
+                        int n_extra, size_t extra_base0, const HotRows& hr, size_t row_base, size_t row_step, int z_compact,
+                        ge_ext* d_points) {
+  const RowTable rt = row_view(g);
+  const int segn = row_segment(rt.W);
+  c->row_table_rows += rows;
+  const size_t total = ncols + (size_t)n_extra;
+  // Column chunks: a workgroup ends with two LDS trees and W stores, so a chunk is worth several segments; enough of them to
+  // give a few-row commitment three workgroups per CU, at most 64.
+  const size_t most = std::max<size_t>(1, total / ((size_t)segn * 2));
+  size_t want = rows >= 768 ? 1 : (768 + rows - 1) / rows;
+  if (rows >= 768 && total > (size_t)kSeg) want = std::min<size_t>(8, (total + kSeg - 1) / kSeg);  // as msm_rows: short tails
+  const char* ec = getenv("VPIN_MSM_ROW_WIN_CHUNKS");  // tests and A/B runs; read per call
+  const int chunks = ec && atoi(ec) > 0 ? std::min(atoi(ec), 64) : (int)std::max<size_t>(1, std::min<size_t>(64, std::min(want, most)));
+  DevBuf parts(c);
+  if (parts.alloc(rows * (size_t)chunks * (size_t)rt.W * sizeof(ge_ext))) return VPIN_ENOMEM;
+  hipLaunchKernelGGL(msm_rows_win_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, dZ, stride,
+                     ncols, d_extra, n_extra, extra_base0, view(g), rt, hr, segn, (ge_ext*)parts.p, row_base, row_step, z_compact);
+  hipLaunchKernelGGL(msm_rows_finish_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (ge_ext*)parts.p, rows, chunks,
+                     rt.W, rt.c, d_points);
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+// walk_only: the caller knows its scalars to be mostly short (addresses, counters): the multi-window walk, where a lane skips a
+// short scalar's empty upper windows; in the row-table kernel those windows' lanes would idle
 static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols,
-                    const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points) {
+                    const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points, bool walk_only = false) {
   if (const int pm = pip_mode())
     if (n_extra <= 1 && ncols + (size_t)n_extra <= 32768)
       return msm_rows_pip(c, g, dZ, rows, stride, ncols, d_extra, n_extra, extra_base0, pm < 0 ? 0 : pm, d_points);
@@ -1313,15 +1654,21 @@ static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, 
     chunks = (int)(want < most ? want : most);
     if (chunks < 1) chunks = 1;
   }
+  const bool use_row = !walk_only && row_table_use(c, g, rows, ncols, n_extra, extra_base0);
   DevBuf parts(c);
   ge_ext* dst = d_points;
-  if (chunks > 1) {
+  if (chunks > 1 && !use_row) {
     if (parts.alloc(rows * (size_t)chunks * sizeof(ge_ext))) return VPIN_ENOMEM;
     dst = (ge_ext*)parts.p;
   }
   if (c->prof_count_adds && c->d_add_count && rows >= 128)
     hipLaunchKernelGGL(msm_count_adds_kernel, dim3((unsigned)rows), dim3(kMsmBlock), 0, c->stream, dZ, stride, ncols, d_extra,
-                       n_extra, extra_base0, view(g), c->d_add_count);
+                       n_extra, extra_base0, view(g), c->d_add_count, HotRows{}, (size_t)0, (size_t)1, 0, use_row ? g->c_row : 0,
+                       use_row ? g->W_row : 0);
+  if (use_row) {
+    ProfScope ps(c, VPIN_K_MSM, 32.0 * nz_est, rows >= 128 ? VPIN_K_MSM_ROWS : -1);
+    return msm_rows_win(c, g, dZ, rows, stride, ncols, d_extra, n_extra, extra_base0, HotRows{}, 0, 1, 0, d_points);
+  }
   {
     ProfScope ps(c, VPIN_K_MSM, 32.0 * nz_est, rows >= 128 ? VPIN_K_MSM_ROWS : -1);
     hipLaunchKernelGGL(msm_rows_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, dZ, stride, ncols,
@@ -1352,14 +1699,14 @@ static int compress_to_host(vpin_ctx* c, const ge_ext* d_pts, size_t n, uint8_t*
 // on generator blind_base.  buckets: by msm_pip.hip with windows of c_bits (0: its default) instead of the table walk.
 // The entry points below have checked the arguments.
 static int commit_rows(vpin_ctx* c, const vpin_gens* g, const fq* z, size_t rows, size_t stride, size_t R, const uint8_t* blinds,
-                       size_t blind_base, bool buckets, int c_bits, uint8_t* out_compressed) {
+                       size_t blind_base, bool buckets, int c_bits, uint8_t* out_compressed, bool walk_only = false) {
   (void)hipSetDevice(c->device);
   const int n_extra = blinds ? 1 : 0;
   DevBuf dbl(c), dpts(c);
   if ((blinds && dbl.alloc(rows * 32)) || dpts.alloc(rows * sizeof(ge_ext))) return VPIN_ENOMEM;
   if (blinds) VPIN_HIP_TRY(hipMemcpyAsync(dbl.p, blinds, rows * 32, hipMemcpyHostToDevice, c->stream));
   const int rc = buckets ? msm_rows_pip(c, g, z, rows, stride, R, (const fq*)dbl.p, n_extra, blind_base, c_bits, (ge_ext*)dpts.p)
-                         : msm_rows(c, g, z, rows, stride, R, (const fq*)dbl.p, n_extra, blind_base, (ge_ext*)dpts.p);
+                         : msm_rows(c, g, z, rows, stride, R, (const fq*)dbl.p, n_extra, blind_base, (ge_ext*)dpts.p, walk_only);
   if (rc) return rc;
   return compress_to_host(c, (const ge_ext*)dpts.p, rows, out_compressed);
 }
@@ -1474,9 +1821,23 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
     for (int m = 0; m < 3; m++)
       if (hot[m] == distinct[k]) hr.T[m] = Tk;
   }
+  // With a row table the whole commitment, regular rows included, goes to msm_rows_win_kernel.  Measured against the strip kernel
+  // forced (which then walks the 8-bit window table): step 345.5-347.1 against 431.6 ms, L5-mult alone 251.8 against 329.8 ms
+  // (profiles/r12_ab_row_table.txt).  An explicit VPIN_MSM_STRIP / VPIN_MSM_STRIP_MIN keeps its meaning: the
+  // strip and hot kernels over the multi-window table.
+  const char* es = getenv("VPIN_MSM_STRIP");
+  const char* em = getenv("VPIN_MSM_STRIP_MIN");
+  const bool use_row = !es && !em && row_table_use(c, g, nrows, R, 0, 0);
   if (c->prof_count_adds && c->d_add_count)
     hipLaunchKernelGGL(msm_count_adds_kernel, dim3((unsigned)nrows), dim3(kMsmBlock), 0, c->stream, zbase, R, R, (const fq*)nullptr, 0,
-                       (size_t)0, view(g), c->d_add_count, hr, row0, row_step, z_compact);
+                       (size_t)0, view(g), c->d_add_count, hr, row0, row_step, z_compact, use_row ? g->c_row : 0, use_row ? g->W_row : 0);
+  if (use_row) {
+    {
+      ProfScope ps(c, VPIN_K_MSM, 32.0 * (double)(nrows * R), VPIN_K_MSM_ROWS);
+      if (const int rc = msm_rows_win(c, g, zbase, nrows, R, R, nullptr, 0, 0, hr, row0, row_step, z_compact, (ge_ext*)dpts.p)) return rc;
+    }
+    return compress_to_host(c, (const ge_ext*)dpts.p, nrows, out_compressed);
+  }
   static const int env_chunks = [] { const char* e = getenv("VPIN_MSM_HOT_CHUNKS"); return e ? atoi(e) : 0; }();
   const int chunks = env_chunks > 0 ? env_chunks : (int)std::max<size_t>(1, std::min<size_t>(8, R / kSeg));
   DevBuf dparts(c);
@@ -1486,8 +1847,6 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
   // and a rank's share of a split commitment, stay with one workgroup per row.
   // VPIN_MSM_STRIP = 0: off, S: number of strips; VPIN_MSM_STRIP_MIN = n: take the path from n rows on (tests, A/B runs; read per
   // call so that a test can switch it)
-  const char* es = getenv("VPIN_MSM_STRIP");
-  const char* em = getenv("VPIN_MSM_STRIP_MIN");
   const int env_strip = es ? atoi(es) : -1;
   const size_t min_rows = em ? (size_t)atol(em) : 8192, min_list = em ? (size_t)1 : 4096, min_R = em ? (size_t)64 : 4096;
   int S = env_strip > 0 ? env_strip : 16;
@@ -1560,6 +1919,19 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
   return compress_to_host(c, (const ge_ext*)dpts.p, nrows, out_compressed);
 }
 
+int hyrax_commit_walk(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, const uint8_t* blinds, size_t L, size_t blind_base,
+                      uint8_t* out_compressed) {
+  if (!c || !g || !Z || !Z->d || !blinds || !out_compressed || L == 0) return VPIN_EINVAL;
+  if (Z->len % L != 0) return VPIN_ESHAPE;
+  const size_t R = Z->len / L;
+  if (R > g->nb || blind_base >= g->nb) return VPIN_ESHAPE;
+  return commit_rows(c, g, Z->d, L, R, R, blinds, blind_base, false, 0, out_compressed, true);
+}
+
+int gens_shared_rows(vpin_ctx* c, const char* label, const uint8_t* gens_xyzt, size_t nb, size_t budget_gb, const vpin_gens** out) {
+  return gens_shared_impl(c, label, gens_xyzt, nb, budget_gb, true, out);
+}
+
 int hyrax_commit_rows_strided(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, size_t L, size_t row0, size_t nrows, size_t row_step,
                               uint8_t* out_compressed, const fq* z_rows) {
   if (!c || !g || !Z || (!Z->d && !z_rows) || !out_compressed || L == 0 || row_step == 0) return VPIN_EINVAL;
@@ -1574,6 +1946,21 @@ int hyrax_commit_rows_strided(vpin_ctx* c, const vpin_gens* g, const vpin_table*
 }  // namespace vpin
 
 extern "C" {
+
+int vpin_hyrax_commit_derefs(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z, size_t L, size_t N, const uint32_t* col_idx,
+                             const uint32_t hot[3], const vpin_table* e_ry, uint8_t* out_compressed) {
+  if (!c || !g || !Z || !Z->d || !col_idx || !hot || !e_ry || !e_ry->d || !out_compressed || L == 0 || N == 0) return VPIN_EINVAL;
+  for (size_t i = 0; i < 3 * N; i++)
+    if (col_idx[i] >= e_ry->len) return VPIN_ESHAPE;
+  for (int m = 0; m < 3; m++)
+    if (hot[m] != 0xffffffffu && hot[m] >= e_ry->len) return VPIN_ESHAPE;
+  (void)hipSetDevice(c->device);
+  DevBuf didx(c);
+  if (didx.alloc(3 * N * sizeof(uint32_t))) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(didx.p, col_idx, 3 * N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  const uint32_t* const idx[3] = {(const uint32_t*)didx.p, (const uint32_t*)didx.p + N, (const uint32_t*)didx.p + 2 * N};
+  return vpin::hyrax_commit_derefs_hot(c, g, Z, L, N, idx, hot, (const fq*)e_ry->d, out_compressed);  // synchronises
+}
 
 int vpin_hyrax_commit_pair(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za, const vpin_table* Zb,
                            const uint8_t* blinds_a, const uint8_t* blinds_b, size_t L, size_t blind_base,

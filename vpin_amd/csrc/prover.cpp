@@ -67,12 +67,12 @@ static int get_gens(vpin_ctx* c, size_t num_vars, SatGens** out) {
   sg->gens_1 = sg->pc.gens_1;
   sg->gens_3 = Mcg{3, {&sg->fb[0], &sg->fb[1], &sg->fb[2], nullptr}, &sg->fb[3]};
   sg->gens_4 = Mcg{4, {&sg->fb[0], &sg->fb[1], &sg->fb[2], &sg->fb[3]}, &sg->fb[4]};
-  int rc = vpin_gens_shared(c, "gens_r1cs_sat", nullptr, sg->nb, 0, &sg->dev);
+  int rc = vpin::gens_shared_rows(c, "gens_r1cs_sat", nullptr, sg->nb, 0, &sg->dev);
   if (rc == VPIN_EINVAL) {  // no table of this label covers nb generators yet: build one
     std::vector<uint8_t> xyzt(128 * sg->nb);
     for (size_t i = 0; i < sg->nb; i++) sg->g[i].to_xyzt(xyzt.data() + 128 * i);
     c->gens_scalars_per_proof = (double)num_vars;  // the two halves of the assignment, about half of them full-size scalars
-    rc = vpin_gens_shared(c, "gens_r1cs_sat", xyzt.data(), sg->nb, 0, &sg->dev);
+    rc = vpin::gens_shared_rows(c, "gens_r1cs_sat", xyzt.data(), sg->nb, 0, &sg->dev);
   }
   if (rc) return rc;
   lap("fixed bases + table");

@@ -80,7 +80,7 @@ static int get_view(vpin_ctx* c, size_t ell, const PcGens** out) {
     lap("derive_gens (host)");
     std::unique_ptr<PcGens> v(new PcGens());
     v->ell = ell; v->L = (size_t)1 << left; v->R = R;
-    int rc = vpin_gens_shared(c, "gens_r1cs_eval", nullptr, nb, 0, &v->dev);
+    int rc = vpin::gens_shared_rows(c, "gens_r1cs_eval", nullptr, nb, 0, &v->dev);
     if (rc == VPIN_EINVAL) {
       std::vector<uint8_t> xyzt(128 * nb);
 #pragma omp parallel for schedule(static) num_threads(host_threads())
@@ -88,7 +88,7 @@ static int get_view(vpin_ctx* c, size_t ell, const PcGens** out) {
       // full-size scalars one proof commits under this table: the derefs polynomial's six non-zero slices, 6N of the 16N
       // entries of the largest view (the computation commitment's entries are addresses, counters and small constants)
       c->gens_scalars_per_proof = (double)((size_t)1 << ell) * 0.375;
-      rc = vpin_gens_shared(c, "gens_r1cs_eval", xyzt.data(), nb, spark_budget_gb(c), &v->dev);
+      rc = vpin::gens_shared_rows(c, "gens_r1cs_eval", xyzt.data(), nb, spark_budget_gb(c), &v->dev);
     }
     if (rc) return rc;
     lap("device table");
@@ -124,9 +124,11 @@ static Shape shape_of(size_t num_cons, size_t num_vars, const size_t nnz[3]) {
 }
 
 // DensePolynomial::commit(gens, None) (dense_mlpoly.rs:193-218): zero blinds
-static int commit_noblind(vpin_ctx* c, const PcGens* pc, const vpin_table* Z, std::vector<CG>& out) {
+// short_scalars: most of Z is addresses, timestamps and counters (see vpin::hyrax_commit_walk)
+static int commit_noblind(vpin_ctx* c, const PcGens* pc, const vpin_table* Z, std::vector<CG>& out, bool short_scalars = false) {
   std::vector<uint8_t> zeros(pc->L * 32, 0);
   out.resize(pc->L);
+  if (short_scalars) return vpin::hyrax_commit_walk(c, pc->dev, Z, zeros.data(), pc->L, pc->R + 1, out[0].b);
   return vpin_hyrax_commit(c, pc->dev, Z, zeros.data(), pc->L, pc->R + 1, out[0].b);
 }
 
@@ -1251,9 +1253,10 @@ static int encode_commit(vpin_ctx* c, const Shape& s, std::unique_ptr<vpin_spark
   std::vector<CG> c_ops, c_mem;
   if ((rc = vpin::spark_comb_tables(c, d.get()))) return fail(rc);
   lap("comb tables");
-  if ((rc = commit_noblind(c, g_ops, d->comb_ops, c_ops))) return fail(rc);
+  // 13 of comb_ops' 16 slices and all of comb_mem are addresses, timestamps and counters
+  if ((rc = commit_noblind(c, g_ops, d->comb_ops, c_ops, true))) return fail(rc);
   lap("commit ops");
-  if ((rc = commit_noblind(c, g_mem, d->comb_mem, c_mem))) return fail(rc);
+  if ((rc = commit_noblind(c, g_mem, d->comb_mem, c_mem, true))) return fail(rc);
   lap("commit mem");
   // (commit_noblind has synchronised the stream.)  The blocks go back to the context's POOL, never straight to the driver
   // (round 6): the proof that follows takes its 16N-scalar temporaries out of them, and a host that encodes per proof

@@ -456,7 +456,10 @@ struct SatGensV {  // R1CSGens (r1csproof.rs:49-89) for the verifier
 static int make_pc(vpin_ctx* c, const char* label, const std::vector<Point>& g, size_t ell, size_t budget_gb, PcGens& pc) {
   const size_t left = ell / 2, R = (size_t)1 << (ell - left), nb = R + 2;
   pc.ell = ell; pc.L = (size_t)1 << left; pc.R = R;
-  int rc = vpin_gens_shared(c, label, nullptr, nb, 0, &pc.dev);
+  // a prover's table of the label serves as well (the verifier multiplies single scalars: the multi-window part); it builds none
+  // of that kind itself
+  int rc = vpin::gens_shared_rows(c, label, nullptr, nb, 0, &pc.dev);
+  if (rc == VPIN_EINVAL) rc = vpin_gens_shared(c, label, nullptr, nb, 0, &pc.dev);
   if (rc == VPIN_EINVAL) {
     std::vector<uint8_t> xyzt(128 * nb);
     for (size_t i = 0; i < nb; i++) g[i].to_xyzt(xyzt.data() + 128 * i);
