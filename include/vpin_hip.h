@@ -632,6 +632,20 @@ int vpin_snark_prove_dev(vpin_ctx* ctx, const vpin_dev_instance* g, const uint8_
  * points included (one lane per term, double-and-add, complete additions in the reduction trees) */
 int vpin_e2_msm(vpin_ctx* ctx, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n,
                 uint8_t out_x[32], uint8_t out_y[32], uint8_t* out_inf);
+/* The tail of a layer's RLC check as a stage of its own (rLCR of src/LeNet/Server.py and of src/cnn_networks/Server.py: the
+ * products w[k] * B'[k], or s_k * X[k] in FCLayer, and the running sum the additions of the list come from): P chains of K
+ * terms, term (p, k) at index p * K + k, each a u128 scalar (16 bytes little-endian) and a point.
+ *   t[p][k]   = s[p][k] * X[p][k]
+ *   acc[p][k] = t[p][0] + .. + t[p][k], the inclusive prefixes
+ * Both as P * K affine points in canonical bytes, an identity written as zeros with flag 1.  Every addition is complete: an
+ * identity term (s = 0, or a flagged X) adds nothing, equal operands double, opposite operands give the identity, and a chain
+ * goes on from an identity prefix.  The prefixes are a workgroup scan, which associates differently from a left-to-right loop;
+ * the group elements and therefore the bytes are the same.  One shared inversion per 256 output points.  No VPIN_ESHAPE
+ * judgement is made here: the flags are reported and the layers decide.  VPIN_EINVAL: a null argument, P or K zero, P * K
+ * above 2^31 - 1, a coordinate >= q, a non-identity point off the curve. */
+int vpin_e2_mul_chain(vpin_ctx* ctx, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf,
+                      size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y,
+                      uint8_t* acc_inf);
 /* One plane of H x W points (row-major) under an fh x fw filter of u128 weights (row-major, 16 bytes little-endian each):
  * out[i][j] = sum_{ii,jj} w[ii][jj] * X[i*stride + ii][j*stride + jj], X = the plane padded with `pad` identities on every side;
  * oh = (H + 2 pad - fh) / stride + 1, ow likewise; out_* hold oh x ow points. */
@@ -859,6 +873,89 @@ int vpin_lenet_client_values(const vpin_lenet_client* cl, int round, const int64
 int vpin_lenet_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
                             const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
                             uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+
+/* ---- an encrypted inference as a list of layers: the CNN A .. E service ---------------------------------------------------
+ * What inferenceCNN of src/cnn_networks/Server.py and main of src/cnn_networks/Client.py do together, for any list of layers
+ * over C planes of H x W ciphertexts (c1 and c2 apart, C * H * W points each, plane-major):
+ *   VPIN_NET_CONV  one fh x fw filter of u128 weights with pad and stride over each of the C c1 planes and then each of the C c2
+ *                  planes, one PRF key per plane in that order: vpin_enc_conv2d with P = 2 C (callConv2_ciphertext on c1, then
+ *                  on c2).  This is not LeNet's order (kernel 0 c1, kernel 0 c2, ..), which is why LeNet keeps its own driver
+ *   VPIN_NET_POOL  k x k windows with a stride and a u128 scale: vpin_enc_avgpool2d over the c1 planes, then the c2 planes
+ *   VPIN_NET_FC    K = the incoming C * H * W, flattened channel-major (flatten), N outputs, int32 weights K x N row-major and
+ *                  non-negative, int64 bias: the server encrypts the bias under baseH with the caller's r, N values drawn
+ *                  before the layer (encryptBias), then vpin_enc_fc with P = 2, the c1 row and then the c2 row, one key each.
+ *                  After it C = 1, H = 1, W = N
+ * After a layer comes, when has_round != 0, one interaction with the client: relu, shift_bits (0: none) as in
+ * vpin_e2_client_round, reencrypt = 0 only on the last layer (the result stays with the client); max_giant is the range the
+ * ready-made client is to be given for that round.  A layer without a round hands its ciphertext straight to the next layer.
+ * Rounds are numbered 0, 1, .. over the layers that have one; layers 0, 1, .. in list order.
+ * In cnn_networks all layers append to the same four global lists (points_mult, weights_array, point_one_Add, point_two_Add),
+ * so a network has ONE label: the multiplication lists and the addition lists of its layers concatenated in layer order. */
+#define VPIN_NET_CONV 0
+#define VPIN_NET_POOL 1
+#define VPIN_NET_FC 2
+typedef struct vpin_net_layer {
+  int kind;
+  size_t fh, fw, pad;            /* CONV */
+  size_t stride;                 /* CONV and POOL */
+  const uint8_t* filter_le16;    /* CONV: fh x fw u128 weights, row-major, 16 bytes little-endian each */
+  size_t k;                      /* POOL: the window */
+  uint8_t scale_le16[16];        /* POOL: u128, the reference's 2^10 / k^2 */
+  size_t K, N;                   /* FC */
+  const int32_t* w;              /* FC: K x N, row-major, non-negative */
+  const int64_t* bias;           /* FC: N values */
+  int has_round, relu, shift_bits, reencrypt;
+  uint64_t max_giant;
+} vpin_net_layer;
+typedef struct vpin_net_cfg {
+  size_t C, H, W;                /* the encrypted input */
+  int prf_bytes;                 /* per network (cnn_networks: 14) */
+  size_t n_layers;
+  const vpin_net_layer* layers;
+} vpin_net_cfg;
+/* what a run consumes; cap >= 8 + 3 n_layers values: out[0] layers, out[1] rounds, out[2] multiplications and out[3] additions
+ * of the label, out[4] decryptions, out[5] client encryptions (the input included), out[6] PRF keys, out[7] bias r; then per
+ * layer i out[8 + 3 i] its multiplications, out[9 + 3 i] its additions, out[10 + 3 i] the decryptions of the round after it (0:
+ * none).  VPIN_EINVAL for a zero dimension, a window that does not fit, an FC whose K is not the incoming C * H * W, an unknown
+ * kind, shift_bits outside 0 .. 62, reencrypt = 0 before the last layer, prf_bytes outside 1 .. 16 */
+int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
+typedef struct vpin_net_trace vpin_net_trace;
+/* The server loop, as vpin_lenet_infer: the same callback type per round (round = the round's number), the caller's keys (one
+ * per convolution plane and FC row, in call order) and bias r (one per FC output, in layer order) with their counts checked
+ * against vpin_net_cfg_counts, baseG / baseH because the server encrypts the bias (may be NULL without an FC layer).  A failing
+ * layer or round frees everything, returns its code and names itself in vpin_last_error(): "vpin_net_infer: layer 2 (fc): .." /
+ * "vpin_net_infer: round 1: ..".  VPIN_EINVAL also for a negative weight and for a missing filter, weight or bias array */
+int vpin_net_infer(vpin_ctx* ctx, const vpin_net_cfg* cfg, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                   const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                   const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
+                   void* user, vpin_net_trace** out);
+void vpin_net_trace_free(vpin_net_trace* t);
+/* per layer: the trace of its layer call, borrowed until vpin_net_trace_free */
+int vpin_net_trace_layers(const vpin_net_trace* t, size_t* n);
+int vpin_net_trace_layer(const vpin_net_trace* t, size_t layer, const vpin_conv_trace** out);
+/* as one label, borrowed: a trace whose two lists are those of all layers in layer order -- what the reference holds in its four
+ * global lists at the end of inferenceCNN; its output and dims are the last layer's, it has no left sides */
+int vpin_net_trace_label(const vpin_net_trace* t, const vpin_conv_trace** out);
+/* the label through vpin_gadget_point_mult_dev / _add_dev: one pair of instances per network */
+int vpin_net_trace_instances(vpin_ctx* ctx, const vpin_net_trace* t, vpin_dev_instance** mult_out, vpin_dev_instance** add_out);
+/* the last layer's ciphertext: 2 x n points, the c1 half and then the c2 half */
+int vpin_net_trace_result(const vpin_net_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf, size_t* n);
+/* host-clock milliseconds of the last vpin_net_infer on this thread: out[0] the whole, out[1 + 2 i] layer i, out[2 + 2 i] the
+ * round after it; slots past 1 + 2 n_layers read 0 */
+int vpin_net_last_timings(double* out, size_t cap);
+/* The ready-made client for n_rounds rounds, over the same implementation as vpin_lenet_client (vpin_e2_client_round):
+ * max_giant holds one range per round, vpin_net_client_round is a vpin_lenet_round_fn with user = the client, and
+ * vpin_net_client_values reads round 0 .. n_rounds - 1 (borrowed).  VPIN_EINVAL when the queue of r runs out; a round that
+ * fails consumes no randomness, so the client can be used again */
+typedef struct vpin_net_client vpin_net_client;
+int vpin_net_client_create(vpin_ctx* ctx, const uint8_t sk_le32[32], uint64_t nb, size_t n_rounds, const uint64_t* max_giant,
+                           const uint8_t* r_le32, size_t n_r, vpin_net_client** out);
+void vpin_net_client_free(vpin_net_client* cl);
+int vpin_net_client_bases(const vpin_net_client* cl, const vpin_e2_base** baseG, const vpin_e2_base** baseH);
+int vpin_net_client_values(const vpin_net_client* cl, size_t round, const int64_t** v, const int64_t** act, size_t* cnt);
+int vpin_net_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                          const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
+                          uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's

@@ -6,8 +6,9 @@ Points are vpin_synthetic_points; the weights are 14-bit values (with the defaul
 128 bits, as in the reference's LeNet), the pooling scale is 2^10 / k^2.  One cold run, then R warm ones (default 11): per stage
 the median, the minimum and the maximum in ms -- validate (upload + range / curve checks, for fc the bias too), layer (fc: the
 matrix-vector product, its normalisation and out = C + bias; pool: the accumulators and the scaled outputs), PRF and RLC (fc
-only: HMAC-SHA256 on the host team, the left sum), host tail (fc: folded weights, the K multiplications on the device, the
-chain, the equation; pool: the second operands of the list), instance build (the vpin_gadget_point_*_dev calls)."""
+only: HMAC-SHA256 on the host team, the left sum), host tail (fc: folded weights, the K multiplications and the chain's prefixes
+on the device, the checks and the equation; pool: the second operands of the list), instance build (the vpin_gadget_point_*_dev
+calls)."""
 import os
 import statistics
 import sys

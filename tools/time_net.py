@@ -1,0 +1,99 @@
+"""The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
+the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E [--reps R] [--nb LOG2] [--no-proofs]
+It prints its fixed seeds, checks the scores and every round's values against the plaintext model (tests/net_model.py) and the
+label's counts against the model's, and then the median / minimum / maximum in ms over R warm runs (after one warm-up run) of
+every layer and every round (the library's host clock, vpin_net_last_timings), of the whole inference, and of the whole
+inference followed by the two proofs of its one label (vpin_snark_prove_dev on the trace's device instances).  The baby-step
+table has 2^nb entries (default 24)."""
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import vpin_amd  # noqa: E402
+from vpin_amd import net as VN  # noqa: E402
+import elgamal_model as EL  # noqa: E402
+import net_model as NM  # noqa: E402
+
+
+def opt(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+VERSION = sys.argv[1]
+REPS, NB_LOG = opt("--reps", 5), opt("--nb", 24)
+PROOFS = "--no-proofs" not in sys.argv
+SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
+SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
+SEED_C, SEED_P = bytes(range(64)), bytes((11 * i + 5) % 256 for i in range(64))
+KINDS = {VN.CONV: "conv", VN.POOL: "pool", VN.FC: "fc"}
+
+
+def stats(xs):
+    return "%9.2f %9.2f %9.2f" % (statistics.median(xs), min(xs), max(xs))
+
+
+def main():
+    assert VERSION in VN.VERSIONS, "time_net.py A|B|C|D|E"
+    print("network", VERSION, "seeds:", SEEDS, "sk: fixed", "nb = 2^%d" % NB_LOG, "reps =", REPS)
+    model = NM.cnn_config(VERSION)
+    image = NM.reference_image()
+    vs, acts = NM.plaintext(model, image)
+    ctx = vpin_amd.Context(0)
+    cfg = VN.cnn_config(VERSION, nb_log=NB_LOG)
+    counts, giants = cfg.counts(), cfg.max_giants()
+    assert counts == dict(NM.counts(model), rounds=len(giants))
+    keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
+    assert all(NM.keys_fit(model, keys)), "a folded weight does not fit 128 bits under these keys"
+    image_rs = EL.splitmix_scalars(SEEDS["image_r"], image.size)
+    bias_rs = EL.splitmix_scalars(SEEDS["bias_r"], counts["bias_r"])
+    client_rs = EL.splitmix_scalars(SEEDS["client_r"], counts["encryptions"] - image.size)
+    n = len(cfg.layers)
+    layers, rounds, whole, proved = [], [], [], []
+    for rep in range(REPS + 1):
+        client = VN.Client(ctx, SK, 1 << NB_LOG, giants, client_rs)
+        t0 = time.perf_counter()
+        scores, values, trace = VN.infer(ctx, cfg, client, image, image_rs, keys, bias_rs)
+        t1 = time.perf_counter()
+        if PROOFS:
+            for g in trace.instances():
+                if g is not None:
+                    g.snark_prove(SEED_C, SEED_P)
+                    g.free()
+        t2 = time.perf_counter()
+        if rep == 0:
+            for r in range(len(giants)):
+                assert [int(a) for a in values[r][0]] == vs[r] and [int(a) for a in values[r][1]] == acts[r], "round %d" % r
+            label = trace.label()
+            assert (label.n_mult, label.n_add) == (counts["n_mult"], counts["n_add"])
+            print("scores:", [int(a) for a in scores], "class", int(np.argmax(scores)), "(the plaintext model's, every round checked)")
+            print("label: %d multiplications, %d additions" % (label.n_mult, label.n_add))
+        else:
+            tm = VN.timings(n)
+            layers.append(tm["layers"])
+            rounds.append(tm["rounds"])
+            whole.append((t1 - t0) * 1e3)
+            proved.append((t2 - t0) * 1e3)
+        trace.free()
+        client.free()
+    print("%-34s %9s %9s %9s" % ("ms, warm", "median", "min", "max"))
+    rnd = 0
+    for i, l in enumerate(cfg.layers):
+        m, a = counts["layers"][i]
+        print("%-34s %s" % ("layer %d (%s, %d + %d ops)" % (i, KINDS[l.kind], m, a), stats([x[i] for x in layers])))
+        if l.has_round:
+            print("%-34s %s" % ("round %d (client, %d values)" % (rnd, counts["per_round"][rnd]), stats([x[i] for x in rounds])))
+            rnd += 1
+    print("%-34s %s" % ("inference (image encryption in)", stats(whole)))
+    if PROOFS:
+        print("%-34s %s" % ("inference + 2 proofs", stats(proved)))
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -55,6 +55,20 @@ class LenetCfg(C.Structure):
                 ("w1", C.c_void_p), ("w2", C.c_void_p), ("b1", C.c_void_p), ("b2", C.c_void_p)]
 
 
+class NetLayer(C.Structure):
+    """vpin_net_layer of include/vpin_hip.h"""
+    _fields_ = [("kind", C.c_int), ("fh", C.c_size_t), ("fw", C.c_size_t), ("pad", C.c_size_t), ("stride", C.c_size_t),
+                ("filter_le16", C.c_void_p), ("k", C.c_size_t), ("scale_le16", C.c_uint8 * 16), ("K", C.c_size_t), ("N", C.c_size_t),
+                ("w", C.c_void_p), ("bias", C.c_void_p), ("has_round", C.c_int), ("relu", C.c_int), ("shift_bits", C.c_int),
+                ("reencrypt", C.c_int), ("max_giant", C.c_uint64)]
+
+
+class NetCfg(C.Structure):
+    """vpin_net_cfg of include/vpin_hip.h"""
+    _fields_ = [("C", C.c_size_t), ("H", C.c_size_t), ("W", C.c_size_t), ("prf_bytes", C.c_int), ("n_layers", C.c_size_t),
+                ("layers", C.POINTER(NetLayer))]
+
+
 # vpin_lenet_round_fn
 LENET_ROUND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, *([C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 6))
 
@@ -179,6 +193,7 @@ def lib():
     L.vpin_spark_encode_dev.argtypes = [vp, vp, C.POINTER(vp), vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vpin_snark_prove_dev.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
     L.vpin_e2_msm.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_mul_chain.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t] + [vp] * 6
     L.vpin_e2_conv2d.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
     L.vpin_enc_conv2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_fc.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
@@ -223,6 +238,21 @@ def lib():
     L.vpin_lenet_client_free.restype = None
     L.vpin_lenet_client_bases.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_lenet_client_values.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_net_cfg_counts.argtypes = [C.POINTER(NetCfg), C.POINTER(C.c_size_t), C.c_size_t]
+    L.vpin_net_infer.argtypes = [vp, C.POINTER(NetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.vpin_net_trace_free.argtypes = [vp]
+    L.vpin_net_trace_free.restype = None
+    L.vpin_net_trace_layers.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.vpin_net_trace_layer.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_trace_label.argtypes = [vp, C.POINTER(vp)]
+    L.vpin_net_trace_instances.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vpin_net_trace_result.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_net_last_timings.argtypes = [C.POINTER(C.c_double), C.c_size_t]
+    L.vpin_net_client_create.argtypes = [vp, vp, C.c_uint64, C.c_size_t, C.POINTER(C.c_uint64), vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_client_free.argtypes = [vp]
+    L.vpin_net_client_free.restype = None
+    L.vpin_net_client_bases.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vpin_net_client_values.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]
@@ -1248,6 +1278,19 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _chk(lib().vpin_e2_msm(self.h, p(s), p(x), p(y), p(f), x.shape[0], p(ox), p(oy), p(oi)), "vpin_e2_msm")
         return None if oi[0] else (int.from_bytes(bytes(ox), "little"), int.from_bytes(bytes(oy), "little"))
+
+    def e2_mul_chain(self, scalars, x, y, inf, P, K):
+        """P chains of K terms (vpin_e2_mul_chain): scalars are P * K Python ints < 2^128, term (p, k) at index p * K + k.  Returns
+        ((tx, ty, tinf), (ax, ay, ainf)): the products s * X and the inclusive prefixes of every chain, P * K points each."""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == P * K == len(scalars)
+        s = self._u128s(scalars)
+        n = P * K
+        out = [np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
+        out += [np.zeros_like(a) for a in out]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_mul_chain(self.h, p(s), p(x), p(y), p(f), P, K, *[p(a) for a in out]), "vpin_e2_mul_chain")
+        return tuple(out[:3]), tuple(out[3:])
 
     def e2_conv2d(self, x, y, inf, H, W, filt, fh, fw, pad=0, stride=1):
         """one plane through vpin_e2_conv2d; filt: fh*fw Python ints row-major.  Returns (x, y, inf) of the oh x ow outputs."""

@@ -32,9 +32,12 @@ constexpr uint32_t kE2FlagOffCurve = 2u;  // a non-identity point that does not 
 //   matvec      C[p][j] = sum_k W[k][j] * X[p][k] for P rows of K points and u32 weights (K x N row-major, little-endian),
 //               normalised; C takes conv's place as the resident outputs (P planes of 1 x N, no taps), so rlc gives
 //               sum_j r[p][j] * C[p][j] per row
-//   scalar_mul  T_i = s_i * X_i (s: n x 16 LE bytes), normalised, canonical bytes
 //   pool_sums   per pooled output (geom: fh = fw = k, pad 0) its taps() - 1 accumulators e_0, e_0 + e_1, .. in the order of
 //               the addition list, normalised, canonical bytes; acc_identity: one byte per output, 1 = one of them is the identity
+// The tail of the fully connected layer's RLC check, also vpin_e2_mul_chain (enc_fc.hip: e2_scalar_mul_kernel,
+// e2_chain_scan_kernel, one e2_to_affine_kernel launch):
+//   mul_chain   P chains of K terms over the loaded points: T[p][k] = s[p][k] * X[p][k] and the inclusive prefixes
+//               acc[p][k] = T[p][0] + .. + T[p][k], both as canonical bytes with identity flags (P * K points each)
 struct EncConvDev {
   vpin_ctx* c;
   ConvGeom g;
@@ -45,8 +48,9 @@ struct EncConvDev {
   int rlc(const uint8_t* r_le16, uint8_t* sums_jac);
   int msm(const uint8_t* r_le16, size_t n, uint8_t sum_jac[96]);
   int matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf);
-  int scalar_mul(const uint8_t* s_le16, size_t n, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf);
   int pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity);
+  int mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y,
+                uint8_t* acc_inf);
 };
 
 // What enc_fc.hip takes from enc_conv.hip (types: fq_dev.h, e2_dev.h): the curve coefficient a in Montgomery form, the

@@ -1,8 +1,9 @@
 // enc_fc.cpp -- the encrypted fully connected layer with its random-linear-combination check, and the encrypted average
 // pooling, host side: input validation, the PRF scalars, the folded weights s_k = sum_j r_j * W[k][j] (exact, in 128 bits),
-// out = C + bias, the chains of additions, the equality test and the operation lists in the order the point-mult /
-// point-add gadgets prove them.  The matrix-vector product, the left sum, the K multiplications s_k * X[k], the pooling's
-// accumulators and its scaled outputs run on the device (enc_fc.hip, enc_conv.hip).  Restates FCLayer (flag 1) with the
+// out = C + bias, the checks over the chains of additions, the equality test and the operation lists in the order the
+// point-mult / point-add gadgets prove them.  The matrix-vector product, the left sum, the K multiplications s_k * X[k] with
+// the chain of their sums (mul_chain, also exposed as vpin_e2_mul_chain), the pooling's accumulators and its scaled outputs run
+// on the device (enc_fc.hip, enc_conv.hip).  Restates FCLayer (flag 1) with the
 // type-1 branch of rLCL / rLCR, and myAvgPool2d (type1 = 1, flag = 1), of the reference's src/LeNet/Server.py.
 #include <omp.h>
 
@@ -38,6 +39,20 @@ struct TraceGuard {
 }  // namespace
 
 extern "C" {
+
+int vpin_e2_mul_chain(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P,
+                      size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_inf) {
+  if (!c || !scalars_le16 || !px || !py || !pinf || !t_x || !t_y || !t_inf || !acc_x || !acc_y || !acc_inf)
+    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: null argument");
+  if (!P || !K || P >= ((size_t)1 << 31) || K >= ((size_t)1 << 31) || P * K >= ((size_t)1 << 31))
+    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: P and K must be at least 1 and P * K at most 2^31 - 1");
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, P * K, &flags);
+  if (rc) return rc;
+  if ((rc = check_flags(flags, "vpin_e2_mul_chain", "point"))) return rc;
+  return d.mul_chain(scalars_le16, P, K, t_x, t_y, t_inf, acc_x, acc_y, acc_inf);
+}
 
 int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const uint8_t* weights_le4,
                 size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
@@ -98,7 +113,7 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
   if ((rc = d.rlc(r.data(), sums.data()))) return rc;
   tm[3] = lap();
 
-  // host tail: the folded weights, T_k = s_k * X[k] (device), the chain of additions, the equation
+  // the tail: the folded weights here, T_k = s_k * X[k] and the prefixes of every row's chain on the device, then the equation
   for (size_t p = 0; p < P; p++)
     for (size_t k = 0; k < K; k++) {
       u128 s = 0;
@@ -115,22 +130,20 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
     if (pinf[i]) return fail(VPIN_ESHAPE, "vpin_enc_fc: a multiplication operand X[k] is the identity (the witness format has no flag for it)");
   memcpy(t->m_px.data(), px, n_in * 32);
   memcpy(t->m_py.data(), py, n_in * 32);
-  std::vector<uint8_t> tx(n_in * 32), ty(n_in * 32), tinf(n_in);
-  if ((rc = d.scalar_mul(t->m_w.data(), n_in, tx.data(), ty.data(), tinf.data()))) return rc;
+  std::vector<uint8_t> tx(n_in * 32), ty(n_in * 32), tinf(n_in), ax(n_in * 32), ay(n_in * 32), ainf(n_in);
+  if ((rc = d.mul_chain(t->m_w.data(), P, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
   bool equal = true;
   for (size_t p = 0; p < P; p++) {
-    Aff acc;
-    for (size_t k = 0; k < K; k++) {
+    for (size_t k = 1; k < K; k++) {
       const size_t m = p * K + k;
-      const Aff Tk = aff_from_bytes(&tx[32 * m], &ty[32 * m], tinf[m]);
-      if (k == 0) { acc = Tk; continue; }
-      if (acc.inf) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator is the identity (the witness format has no flag for it)");
+      if (ainf[m - 1]) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator is the identity (the witness format has no flag for it)");
       const size_t ai = p * adds_per_row + N + (k - 1);
-      put_point(acc, &t->a_px[32 * ai], &t->a_py[32 * ai]);
+      memcpy(&t->a_px[32 * ai], &ax[32 * (m - 1)], 32); memcpy(&t->a_py[32 * ai], &ay[32 * (m - 1)], 32);
       memcpy(&t->a_rx[32 * ai], &tx[32 * m], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * m], 32);
       t->a_rz[ai] = tinf[m];
-      acc = aff_add(acc, Tk);
     }
+    const size_t last = p * K + K - 1;  // the last accumulator may be the identity: it is only compared
+    const Aff acc = aff_from_bytes(&ax[32 * last], &ay[32 * last], ainf[last]);
     const Aff left = to_affine(jac_from_bytes(&sums[96 * p]));
     put_point(left, &t->left_x[32 * p], &t->left_y[32 * p]);
     t->left_inf[p] = left.inf ? 1 : 0;

@@ -7,6 +7,11 @@
 //   e2_scalar_mul_kernel  T_i = s_i * X_i, one lane per point, s_i a u128: the multiplications of the layer's RLC check
 //   e2_pool_sums_kernel   one lane per pooled output: the k*k - 1 accumulators e_0, e_0 + e_1, ... of its window (the first
 //                         operands of the pooling's additions) and a flag when one of them is the identity
+//   e2_chain_scan_kernel  one workgroup per chain of K Jacobian points: the inclusive prefixes T_0 + .. + T_k as a scan in LDS
+//                         with the complete addition, in tiles of kE2Block with a carried prefix; with e2_scalar_mul_kernel
+//                         before it and ONE e2_to_affine_kernel launch over products and prefixes after it, this is the tail
+//                         of the fully connected layer's RLC check (mul_chain): one shared inversion per 256 points instead of
+//                         one per addition
 // As in enc_conv.hip the accumulators are named registers (one e2_jac, the scalar as shifted words): no per-lane arrays.
 #include "e2_dev.h"
 #include "enc_conv.h"
@@ -61,6 +66,43 @@ __global__ __launch_bounds__(64) void e2_pool_sums_kernel(const fq* __restrict__
   acc_identity[o] = bad;
 }
 
+// grid: x = chain.  acc[p * K + k] = T[p * K] + .. + T[p * K + k].  A scan associates differently from a left-to-right loop;
+// the group elements are the same, and every addition is complete: an identity term or prefix adds nothing, equal segment sums
+// double, opposite ones give the identity, from which the chain goes on
+__global__ __launch_bounds__(kE2Block) void e2_chain_scan_kernel(const e2_jac* __restrict__ T, size_t K, fq a,
+                                                                 e2_jac* __restrict__ acc) {
+  __shared__ e2_jac sh[kE2Block];
+  const int tid = threadIdx.x;
+  const e2_jac* t = T + (size_t)blockIdx.x * K;
+  e2_jac* o = acc + (size_t)blockIdx.x * K;
+  e2_jac carry = e2_identity();
+  for (size_t base = 0; base < K; base += kE2Block) {
+    const size_t k = base + tid;
+    const int live = (int)(K - base < (size_t)kE2Block ? K - base : (size_t)kE2Block);  // a short tile is the last one
+    e2_jac v = e2_identity();
+    if (k < K) v = e2_load(t + k);
+    e2_store(&sh[tid], v);
+    __syncthreads();
+    for (int d = 1; d < live; d <<= 1) {
+      const bool on = tid >= d;
+      e2_jac left = e2_identity();
+      if (on) left = e2_load(&sh[tid - d]);
+      __syncthreads();
+      if (on) {
+        v = e2_add(left, v, a);
+        e2_store(&sh[tid], v);
+      }
+      __syncthreads();
+    }
+    v = e2_add(carry, v, a);
+    if (k < K) e2_store(o + k, v);
+    if (tid == kE2Block - 1) e2_store(&sh[tid], v);  // the next tile's carry; nobody reads this slot after the last step
+    __syncthreads();
+    carry = e2_load(&sh[kE2Block - 1]);
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 // C = X * W per row over the loaded points (P x K), normalised: canonical bytes to the host, Montgomery coordinates resident
@@ -92,22 +134,33 @@ int EncConvDev::matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4,
   return VPIN_OK;
 }
 
-// T_i = s_i * X_i over the n loaded points, normalised, as canonical bytes
-int EncConvDev::scalar_mul(const uint8_t* s_le16, size_t n, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf) {
+// the tail over the loaded points, P chains of K terms: T = s * X (Jacobian), the prefixes of every chain, and both normalised by
+// ONE launch over the 2 P K points; canonical bytes and flags to the host
+int EncConvDev::mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x,
+                          uint8_t* acc_y, uint8_t* acc_inf) {
   (void)hipSetDevice(c->device);
+  const size_t n = P * K;
   DevBuf s(c), jac(c), mx(c), my(c), cx(c), cy(c), ti(c);
-  if (s.alloc(n * 16) || jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) ||
-      ti.alloc(n))
+  if (s.alloc(n * 16) || jac.alloc(2 * n * sizeof(e2_jac)) || mx.alloc(2 * n * 32) || my.alloc(2 * n * 32) || cx.alloc(2 * n * 32) ||
+      cy.alloc(2 * n * 32) || ti.alloc(2 * n))
     return VPIN_ENOMEM;
+  const fq a = e2_curve_a();
+  e2_jac* prod = (e2_jac*)jac.p;
   VPIN_HIP_TRY(hipMemcpyAsync(s.p, s_le16, n * 16, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(e2_scalar_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
-                     (const uint8_t*)pinf.p, (const uint4*)s.p, n, e2_curve_a(), (e2_jac*)jac.p);
+                     (const uint8_t*)pinf.p, (const uint4*)s.p, n, a, prod);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ti.p);
+  hipLaunchKernelGGL(e2_chain_scan_kernel, dim3((unsigned)P), dim3(kE2Block), 0, c->stream, (const e2_jac*)prod, K, a, prod + n);
+  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_to_affine(c, prod, 2 * n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ti.p);
   if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(t_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(t_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(t_inf, ti.p, n, hipMemcpyDeviceToHost, c->stream));
+  const uint8_t *bx = (const uint8_t*)cx.p, *by = (const uint8_t*)cy.p, *bi = (const uint8_t*)ti.p;
+  VPIN_HIP_TRY(hipMemcpyAsync(t_x, bx, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(t_y, by, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(t_inf, bi, n, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_x, bx + n * 32, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_y, by + n * 32, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(acc_inf, bi + n, n, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }

@@ -1,0 +1,242 @@
+"""An encrypted inference as a list of layers over the C ABI (vpin_net_*): the server loop of the reference's CNN A .. E service
+(src/cnn_networks/Server.py inferenceCNN) over the encrypted layers, the client's rounds in between (the ready-made client of
+any number of rounds, or a Python callback), and the network's ONE label for the prover: the lists of all layers concatenated
+in layer order, as the reference leaves them in its four global lists.
+
+The networks' constants are data, not code: `cnn_config(version)` reads the filter, the pooling windows, the PRF bytes, the
+schedule of the rounds and the names of the weight files from the fixture recorded off runs of the reference
+(tests/golden/net_pins.json, written by tests/golden/make_net_pins.py) and the weights from the .npy files beside it."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+
+from .capi import ConvTrace, DevInstance, NetCfg, NetLayer, _chk, lib
+from .lenet import RELU, REENCRYPT, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
+
+CONV, POOL, FC = 0, 1, 2
+VERSIONS = ("A", "B", "C", "D", "E")
+_GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+
+
+class Config:
+    """A vpin_net_cfg, its layers and the arrays they point to.  Layers are added in order; `round` attaches the client's
+    round to the layer added last."""
+
+    def __init__(self, C_, H, W, prf_bytes):
+        self.dims = (C_, H, W)
+        self.prf_bytes = prf_bytes
+        self.layers, self._keep = [], []
+
+    def _add(self, kind):
+        l = NetLayer()
+        l.kind = kind
+        self.layers.append(l)
+        return l
+
+    def conv(self, filt, pad=0, stride=1):
+        """filt: fh x fw ints below 2^128"""
+        filt = [[int(v) for v in row] for row in filt]
+        buf = np.frombuffer(b"".join(v.to_bytes(16, "little") for row in filt for v in row), dtype=np.uint8).copy()
+        self._keep.append(buf)
+        l = self._add(CONV)
+        l.fh, l.fw, l.pad, l.stride, l.filter_le16 = len(filt), len(filt[0]), pad, stride, buf.ctypes.data
+        return self
+
+    def pool(self, k, stride, scale):
+        l = self._add(POOL)
+        l.k, l.stride = k, stride
+        l.scale_le16[:] = list(int(scale).to_bytes(16, "little"))
+        return self
+
+    def fc(self, w, bias):
+        """w: K x N ints (int32 range; a negative one is rejected by the driver), bias: N ints"""
+        w64 = np.asarray(w, dtype=np.int64)
+        w32 = np.ascontiguousarray(w64.astype(np.int32))
+        assert w32.ndim == 2 and np.array_equal(w32, w64)
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.int64))
+        assert b.shape == (w32.shape[1],)
+        self._keep += [w32, b]
+        l = self._add(FC)
+        l.K, l.N, l.w, l.bias = w32.shape[0], w32.shape[1], w32.ctypes.data, b.ctypes.data
+        return self
+
+    def round(self, relu=False, shift_bits=0, max_giant=1, reencrypt=True):
+        l = self.layers[-1]
+        l.has_round, l.relu, l.shift_bits, l.reencrypt, l.max_giant = 1, int(bool(relu)), shift_bits, int(bool(reencrypt)), int(max_giant)
+        return self
+
+    @property
+    def c(self):
+        cfg = NetCfg()
+        cfg.C, cfg.H, cfg.W = self.dims
+        cfg.prf_bytes, cfg.n_layers = self.prf_bytes, len(self.layers)
+        arr = (NetLayer * max(1, len(self.layers)))(*self.layers)
+        cfg.layers = C.cast(arr, C.POINTER(NetLayer)) if self.layers else None
+        cfg._arr = arr
+        return cfg
+
+    def max_giants(self):
+        return [int(l.max_giant) for l in self.layers if l.has_round]
+
+    def counts(self):
+        n = len(self.layers)
+        out = (C.c_size_t * (8 + 3 * n))()
+        cfg = self.c
+        _chk(lib().vpin_net_cfg_counts(C.byref(cfg), out, len(out)), "vpin_net_cfg_counts")
+        o = [int(v) for v in out]
+        per = [tuple(o[8 + 3 * i:11 + 3 * i]) for i in range(n)]
+        return dict(layers=[(m, a) for m, a, _ in per], per_round=[d for (_, _, d), l in zip(per, self.layers) if l.has_round], n_mult=o[2],
+                    n_add=o[3], decryptions=o[4], encryptions=o[5], prf_keys=o[6], bias_r=o[7], rounds=o[1])
+
+
+def cnn_config(version, nb_log=24, golden=None):
+    """the reference's network A .. E: the 3 x 3 filter with pad 1, pooling (4, 4) for A and B and (2, 2) for C, D and E with the
+    scale int(2^10 / k^2), 14 PRF bytes, the rounds ReLU / shifting(., 26) / ReLU and shifting(., 32) / ReLU without
+    re-encryption, the weights as 16-bit fixed point -- all read from `golden` (default: tests/golden of the source tree).
+    max_giant is set for a table of 2^nb_log baby steps: +-2^31 for the first two rounds (on the reference's image the values
+    reach 2^19.0 and 2^29.0) and +-2^38 for the rounds after the fully connected layers (up to 2^35.0 and 2^36.5, network E;
+    tests/test_net_model.py computes them with the plaintext model)"""
+    golden = golden or _GOLDEN
+    path = os.path.join(golden, "net_pins.json")
+    if not os.path.exists(path):
+        raise FileNotFoundError("cnn_config: %s not found; pass golden= (the directory of net_pins.json and the weight files)" % path)
+    with open(path) as f:
+        p = json.load(f)
+    net, v, rounds = p["network"], p["networks"][version], p["rounds"]
+    load = lambda key: fixed_point(np.load(os.path.join(golden, v[key])), net["weight_bits"])
+    conv, k = net["conv"], v["pool"][0]
+    giants = [max(1, (1 << bits) >> nb_log) for bits in (31, 31, 38, 38)]
+    rnd = lambda i: dict(relu=rounds[i]["relu"], shift_bits=rounds[i]["shift_bits"], max_giant=giants[i], reencrypt=i + 1 < len(rounds))
+    cfg = Config(1, net["H"], net["W"], net["prf_bytes"])
+    cfg.conv(np.array(conv["filter"], dtype=object).reshape(conv["fh"], conv["fw"]).tolist(), conv["pad"], conv["stride"]).round(**rnd(0))
+    cfg.pool(k, v["pool"][1], int(2**net["pool_scale_bits"] / k**2)).round(**rnd(1))
+    cfg.fc(load("weight_fc1"), load("bias_fc1")).round(**rnd(2))
+    cfg.fc(load("weight_fc2"), load("bias_fc2")).round(**rnd(3))
+    return cfg
+
+
+class Client:
+    """vpin_net_client: the key, the two base tables, the discrete-log table and the queue of randomness, for n rounds"""
+
+    def __init__(self, ctx, sk, nb, max_giant, rs):
+        self.ctx, self.n_rounds = ctx, len(max_giant)
+        h = C.c_void_p()
+        k = ctx._u256s([sk])
+        r = ctx._u256s(rs) if len(rs) else np.zeros(32, np.uint8)
+        mg = (C.c_uint64 * len(max_giant))(*[int(v) for v in max_giant])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_net_client_create(ctx.h, p(k), nb, len(max_giant), mg, p(r), len(rs), C.byref(h)), "vpin_net_client_create")
+        self.h = h
+        g, hh = C.c_void_p(), C.c_void_p()
+        _chk(lib().vpin_net_client_bases(h, C.byref(g), C.byref(hh)), "vpin_net_client_bases")
+        self.base_g, self.base_h = g, hh
+        self.round_fn = C.cast(lib().vpin_net_client_round, C.c_void_p)
+        self.user = h
+
+    def encrypt(self, msgs, rs):
+        """the input's encryption under the client's key -> (c1, c2), each (x, y, inf)"""
+        return self.ctx.e2_encrypt(self.base_g, self.base_h, msgs, rs)
+
+    def values(self, rnd):
+        """(v, act) of round 0 .. n_rounds - 1 as int64 arrays"""
+        v, a, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _chk(lib().vpin_net_client_values(self.h, rnd, C.byref(v), C.byref(a), C.byref(n)), "vpin_net_client_values")
+        get = lambda p: np.frombuffer((C.c_int64 * n.value).from_address(p.value), dtype=np.int64).copy() if n.value else np.zeros(0, np.int64)
+        return get(v), get(a)
+
+    def free(self):
+        if self.h:
+            lib().vpin_net_client_free(self.h)
+            self.h = None
+
+
+class Trace:
+    """vpin_net_trace: per layer the ConvTrace of its layer call, and the label, all borrowed"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        n = C.c_size_t()
+        _chk(lib().vpin_net_trace_layers(handle, C.byref(n)), "vpin_net_trace_layers")
+        self.n_layers = n.value
+
+    def _borrowed(self, h):
+        t = ConvTrace(self.ctx, h)
+        t.free = lambda: None  # borrowed: the Trace frees it
+        return t
+
+    def layer(self, i):
+        h = C.c_void_p()
+        _chk(lib().vpin_net_trace_layer(self.h, i, C.byref(h)), "vpin_net_trace_layer")
+        return self._borrowed(h)
+
+    def label(self):
+        """the network's one label: mults() and adds() are the lists of all layers in layer order"""
+        h = C.c_void_p()
+        _chk(lib().vpin_net_trace_label(self.h, C.byref(h)), "vpin_net_trace_label")
+        return self._borrowed(h)
+
+    def instances(self):
+        hm, ha = C.c_void_p(), C.c_void_p()
+        _chk(lib().vpin_net_trace_instances(self.ctx.h, self.h, C.byref(hm), C.byref(ha)), "vpin_net_trace_instances")
+        return (DevInstance(self.ctx, hm) if hm.value else None), (DevInstance(self.ctx, ha) if ha.value else None)
+
+    def result(self):
+        """the last layer's ciphertext -> (c1, c2), each (x, y, inf)"""
+        x, y, f, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _chk(lib().vpin_net_trace_result(self.h, C.byref(x), C.byref(y), C.byref(f), C.byref(n)), "vpin_net_trace_result")
+        n = n.value
+        get = lambda p, k: np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8).copy()
+        xs, ys, fs = get(x, 64 * n).reshape(2, n, 32), get(y, 64 * n).reshape(2, n, 32), get(f, 2 * n).reshape(2, n)
+        return (xs[0], ys[0], fs[0]), (xs[1], ys[1], fs[1])
+
+    def free(self):
+        if self.h:
+            lib().vpin_net_trace_free(self.h)
+            self.h = None
+
+
+def timings(n_layers):
+    """host-clock ms of the last run: dict(total, layers = [ms], rounds = [ms, 0 where a layer has no round])"""
+    out = (C.c_double * (1 + 2 * n_layers))()
+    _chk(lib().vpin_net_last_timings(out, len(out)), "vpin_net_last_timings")
+    return dict(total=float(out[0]), layers=[float(out[1 + 2 * i]) for i in range(n_layers)], rounds=[float(out[2 + 2 * i]) for i in range(n_layers)])
+
+
+def run(ctx, cfg, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user=None):
+    """vpin_net_infer -> Trace.  c1, c2: (x, y, inf) of the C * H * W input points; keys: 32-byte keys in call order; bias_rs:
+    ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer"""
+    x1, y1, f1 = ctx._points(*c1)
+    x2, y2, f2 = ctx._points(*c2)
+    k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
+    r = ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
+    h = C.c_void_p()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    fn = C.cast(round_fn, C.c_void_p)
+    c = cfg.c
+    rc = lib().vpin_net_infer(ctx.h, C.byref(c), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h, p(k), len(keys), p(r),
+                              len(bias_rs), fn, user, C.byref(h))
+    if rc:
+        assert not h.value
+        err, lib_text = getattr(round_fn, "error", None), lib().vpin_last_error().decode()
+        if err is not None:  # the Python callback's own exception, with the round the driver names
+            round_fn.error = None
+            raise RuntimeError("the round callback raised [%s]" % lib_text) from err
+        _chk(rc, "vpin_net_infer")
+    return Trace(ctx, h)
+
+
+def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
+    """image: C x H x W ints (see preprocess).  Encrypts it under the client's key, runs the server loop against the ready-made
+    client and returns (scores, rounds, trace): the last round's activated values, per round its (v, act), and the Trace"""
+    c1, c2 = client.encrypt(np.asarray(image, dtype=np.int64).reshape(-1), image_rs)
+    trace = run(ctx, cfg, c1, c2, client.base_g, client.base_h, keys, bias_rs, client.round_fn, client.user)
+    rounds = [client.values(r) for r in range(client.n_rounds)]
+    return rounds[-1][1], rounds, trace
+
+
+def write_witness_files(trace, root, label):
+    """the 8 JSON files the CLI reads for the network's one label, under root/rust_files/<label>"""
+    from . import enc_conv
+    enc_conv.write_witness_files(trace.label(), root, label)
