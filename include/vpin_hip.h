@@ -840,10 +840,12 @@ typedef int (*vpin_lenet_round_fn)(void* user, int round, int flags, int shift_b
                                    const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
                                    uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 typedef struct vpin_lenet_trace vpin_lenet_trace;
-/* The server loop.  The driver holds no secret key: baseG / baseH (the client's public key) are there because the server
- * encrypts the bias itself.  What the client sends back is validated by the layer that takes it.  A failing layer or round
- * frees everything, returns its code and names the label or round in vpin_last_error() ("vpin_lenet_infer: L3: ..").
- * VPIN_EINVAL also for a negative weight and for n_keys / n_bias_r other than vpin_lenet_cfg_counts says */
+/* The server loop: the table above as seven steps of the driver vpin_net_infer runs too, here with the planes interleaved, the
+ * plane sums before L3 and L5 and the repeats of L1 and L5.  The driver holds no secret key: baseG / baseH (the client's public
+ * key) are there because the server encrypts the bias itself.  What the client sends back is validated by the layer that takes
+ * it.  A failing layer or round frees everything, returns its code and names the label or round in vpin_last_error()
+ * ("vpin_lenet_infer: L3: ..", "vpin_lenet_infer: R6: ..").  VPIN_EINVAL also for a negative weight and for n_keys / n_bias_r
+ * other than vpin_lenet_cfg_counts says */
 int vpin_lenet_infer(vpin_ctx* ctx, const vpin_lenet_cfg* cfg, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
                      const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
                      const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
@@ -859,27 +861,14 @@ int vpin_lenet_trace_instances(vpin_ctx* ctx, const vpin_lenet_trace* t, int lab
 int vpin_lenet_trace_result(const vpin_lenet_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf, size_t* n);
 /* host-clock milliseconds of the last vpin_lenet_infer on this thread: [0..6] L1 .. L7, [7..13] R1 .. R7, [14] the whole */
 void vpin_lenet_last_timings(double out[16]);
-/* The ready-made client: owns sk, the tables of G and H = sk * G, a discrete-log table of nb baby steps and the queue of n_r
- * encryption randomness values (32 bytes each, one per encrypt call in order).  vpin_lenet_client_round is a
- * vpin_lenet_round_fn over vpin_e2_client_round with user = the client; it keeps each round's raw decryptions and activated
- * values (vpin_lenet_client_values, round 1 .. 7, borrowed).  VPIN_EINVAL when the queue runs out; a round that fails consumes no
- * randomness, so the client can be used again */
-typedef struct vpin_lenet_client vpin_lenet_client;
-int vpin_lenet_client_create(vpin_ctx* ctx, const uint8_t sk_le32[32], uint64_t nb, const uint64_t max_giant[7], const uint8_t* r_le32,
-                             size_t n_r, vpin_lenet_client** out);
-void vpin_lenet_client_free(vpin_lenet_client* cl);
-int vpin_lenet_client_bases(const vpin_lenet_client* cl, const vpin_e2_base** baseG, const vpin_e2_base** baseH);
-int vpin_lenet_client_values(const vpin_lenet_client* cl, int round, const int64_t** v, const int64_t** act, size_t* cnt);
-int vpin_lenet_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
-                            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
-                            uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+/* The ready-made client is vpin_net_client below, made for the seven rounds: vpin_net_client_create(.., n_rounds = 7, ..) */
 
 /* ---- an encrypted inference as a list of layers: the CNN A .. E service ---------------------------------------------------
  * What inferenceCNN of src/cnn_networks/Server.py and main of src/cnn_networks/Client.py do together, for any list of layers
  * over C planes of H x W ciphertexts (c1 and c2 apart, C * H * W points each, plane-major):
  *   VPIN_NET_CONV  one fh x fw filter of u128 weights with pad and stride over each of the C c1 planes and then each of the C c2
  *                  planes, one PRF key per plane in that order: vpin_enc_conv2d with P = 2 C (callConv2_ciphertext on c1, then
- *                  on c2).  This is not LeNet's order (kernel 0 c1, kernel 0 c2, ..), which is why LeNet keeps its own driver
+ *                  on c2).  LeNet's order is (kernel 0 c1, kernel 0 c2, ..): the one driver takes either
  *   VPIN_NET_POOL  k x k windows with a stride and a u128 scale: vpin_enc_avgpool2d over the c1 planes, then the c2 planes
  *   VPIN_NET_FC    K = the incoming C * H * W, flattened channel-major (flatten), N outputs, int32 weights K x N row-major and
  *                  non-negative, int64 bias: the server encrypts the bias under baseH with the caller's r, N values drawn
@@ -920,9 +909,10 @@ typedef struct vpin_net_cfg {
  * kind, shift_bits outside 0 .. 62, reencrypt = 0 before the last layer, prf_bytes outside 1 .. 16 */
 int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
 typedef struct vpin_net_trace vpin_net_trace;
-/* The server loop, as vpin_lenet_infer: the same callback type per round (round = the round's number), the caller's keys (one
- * per convolution plane and FC row, in call order) and bias r (one per FC output, in layer order) with their counts checked
- * against vpin_net_cfg_counts, baseG / baseH because the server encrypts the bias (may be NULL without an FC layer).  A failing
+/* The server loop, the same driver as vpin_lenet_infer with one step per layer, the planes blocked (all c1, then all c2): the
+ * same callback type per round (round = the round's number), the caller's keys (one per convolution plane and FC row, in call
+ * order) and bias r (one per FC output, in layer order) with their counts checked against vpin_net_cfg_counts, baseG / baseH
+ * because the server encrypts the bias (may be NULL without an FC layer; round_fn may be NULL without a round).  A failing
  * layer or round frees everything, returns its code and names itself in vpin_last_error(): "vpin_net_infer: layer 2 (fc): .." /
  * "vpin_net_infer: round 1: ..".  VPIN_EINVAL also for a negative weight and for a missing filter, weight or bias array */
 int vpin_net_infer(vpin_ctx* ctx, const vpin_net_cfg* cfg, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
@@ -943,10 +933,12 @@ int vpin_net_trace_result(const vpin_net_trace* t, const uint8_t** x, const uint
 /* host-clock milliseconds of the last vpin_net_infer on this thread: out[0] the whole, out[1 + 2 i] layer i, out[2 + 2 i] the
  * round after it; slots past 1 + 2 n_layers read 0 */
 int vpin_net_last_timings(double* out, size_t cap);
-/* The ready-made client for n_rounds rounds, over the same implementation as vpin_lenet_client (vpin_e2_client_round):
- * max_giant holds one range per round, vpin_net_client_round is a vpin_lenet_round_fn with user = the client, and
- * vpin_net_client_values reads round 0 .. n_rounds - 1 (borrowed).  VPIN_EINVAL when the queue of r runs out; a round that
- * fails consumes no randomness, so the client can be used again */
+/* The ready-made client of both drivers, for n_rounds rounds (LeNet: 7): owns sk, the tables of G and H = sk * G, a
+ * discrete-log table of nb baby steps, one range max_giant per round and the queue of n_r encryption randomness values (32 bytes
+ * each, one per encrypt call in order).  vpin_net_client_round is a vpin_lenet_round_fn over vpin_e2_client_round with user =
+ * the client; it keeps each round's raw decryptions and activated values (vpin_net_client_values, round 0 .. n_rounds - 1,
+ * borrowed).  VPIN_EINVAL when the queue of r runs out; a round that fails consumes no randomness, so the client can be used
+ * again */
 typedef struct vpin_net_client vpin_net_client;
 int vpin_net_client_create(vpin_ctx* ctx, const uint8_t sk_le32[32], uint64_t nb, size_t n_rounds, const uint64_t* max_giant,
                            const uint8_t* r_le32, size_t n_r, vpin_net_client** out);

@@ -1,4 +1,4 @@
-"""GPU tests of the whole encrypted LeNet inference (vpin_lenet_infer, vpin_lenet_client_*, vpin_amd.lenet) on the smallest
+"""GPU tests of the whole encrypted LeNet inference (vpin_lenet_infer, vpin_net_client_*, vpin_amd.lenet) on the smallest
 network the architecture allows: a 32 x 32 image of small signed integers, n1 = 2, n2 = 3 (rows [1,1], [0,1], [1,0]), n3 = 4,
 FC 4 -> 3 -> 2, the LeNet filter, pool scale 1 and shifts chosen so that every decrypted value stays within 2^16 * 64 (a table
 of 2^16 baby steps and 64 giant steps).  The scores and every round's values are compared with the plaintext model, every
@@ -162,6 +162,9 @@ def test_numpy_callback_gives_the_same_trace_and_scores(ctx, run, plain):
     c1, c2 = client.encrypt(np.array(IMAGE, dtype=np.int64).reshape(-1), IMAGE_RS)
     cb = VL.python_round(fn)
     other = VL.run(ctx, cfg, c1, c2, client.base_g, client.base_h, KEYS, BIAS_RS, cb)
+    tm = VL.timings()  # the layout: seven labels, seven rounds, the whole
+    assert len(tm["labels"]) == len(tm["rounds"]) == 7 and all(t > 0 for t in tm["labels"] + tm["rounds"]), tm
+    assert tm["total"] >= sum(tm["labels"]) + sum(tm["rounds"]), tm
     assert seen[6] == [int(a) for a in scores] and seen[6] == plain[1][6]
     for name in VL.LABELS:
         a, b = trace.label(name), other.label(name)

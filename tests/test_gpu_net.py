@@ -145,6 +145,9 @@ def test_python_callback_gives_the_same_trace(ctx, runs):
 
     c1, c2 = run.client.encrypt(np.array(run.image, dtype=np.int64), run.image_r)
     other = VN.run(ctx, run.cfg, c1, c2, run.client.base_g, run.client.base_h, run.keys, run.bias_r, VN.python_round(fn))
+    tm = VN.timings(4)  # the layout: the whole, then per layer the layer and the round after it
+    assert len(tm["layers"]) == len(tm["rounds"]) == 4 and all(t > 0 for t in tm["layers"] + tm["rounds"]), tm
+    assert tm["total"] >= sum(tm["layers"]) + sum(tm["rounds"]), tm
     assert seen == [r["act"] for r in run.case["rounds"]] and not queue
     a, b = run.trace.label(), other.label()
     assert a.mults()[0] == b.mults()[0]
@@ -176,13 +179,14 @@ def small(ctx):
     cfg = device_config(SMALL, [4, 4])
     client = VN.Client(ctx, SMALL_SK, NB, [4, 4], client_r)
     scores, rounds, trace = VN.infer(ctx, cfg, client, msgs, image_r, keys, bias_r)
+    timings = VN.timings(3)
     # the model on discrete logarithms
     c1, c2 = NM.log_encrypt(SMALL_SK, msgs, image_r)
     seen = []
     layers, label = NM.infer_model(EM.LOGS, SMALL, c1, c2, keys, [NM.log_encrypt(SMALL_SK, SMALL["layers"][2]["bias"], bias_r)],
                                    NM.log_client(SMALL_SK, client_r, seen))
     yield dict(cfg=cfg, client=client, trace=trace, rounds=rounds, scores=scores, plain=(vs, acts), layers=layers, label=label, seen=seen,
-               msgs=msgs, image_r=image_r, bias_r=bias_r, keys=keys)
+               msgs=msgs, image_r=image_r, bias_r=bias_r, keys=keys, timings=timings)
     trace.free()
     client.free()
 
@@ -192,6 +196,9 @@ def test_layer_without_a_round_hands_its_ciphertext_on(small):
     assert [([int(a) for a in v], [int(a) for a in act]) for v, act in small["rounds"]] == list(zip(vs, acts)) == [tuple(s) for s in small["seen"]]
     trace, conv = small["trace"], LM.logs_to_points
     assert trace.n_layers == 3
+    tm = small["timings"]  # of the fixture's run: the convolution's round slot stays exactly 0
+    assert all(t > 0 for t in tm["layers"]) and tm["rounds"][0] == 0 and tm["rounds"][1] > 0 and tm["rounds"][2] > 0, tm
+    assert tm["total"] >= sum(tm["layers"]) + sum(tm["rounds"]), tm
     for i, exp in enumerate(small["layers"]):
         t = trace.layer(i)
         assert points_of(*t.output()) == conv([v for plane in exp["out"] for v in plane]), "output of layer %d" % i

@@ -233,11 +233,6 @@ def lib():
     L.vpin_lenet_trace_result.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_lenet_last_timings.argtypes = [C.POINTER(C.c_double)]
     L.vpin_lenet_last_timings.restype = None
-    L.vpin_lenet_client_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_size_t, C.POINTER(vp)]
-    L.vpin_lenet_client_free.argtypes = [vp]
-    L.vpin_lenet_client_free.restype = None
-    L.vpin_lenet_client_bases.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.vpin_lenet_client_values.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_net_cfg_counts.argtypes = [C.POINTER(NetCfg), C.POINTER(C.c_size_t), C.c_size_t]
     L.vpin_net_infer.argtypes = [vp, C.POINTER(NetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.vpin_net_trace_free.argtypes = [vp]

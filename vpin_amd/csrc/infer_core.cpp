@@ -1,0 +1,159 @@
+// infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_avgpool2d,
+// vpin_enc_fc, vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
+// (lenet.cpp) and vpin_net_infer (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer validates
+// what it is given, the client's answers included.
+#include "infer_core.h"
+
+#include <utility>
+
+namespace vpin::infer {
+
+namespace {
+
+using enc::fail;
+
+struct Pts {
+  std::vector<uint8_t> x, y, inf;
+  size_t n() const { return inf.size(); }
+  void resize(size_t k) { x.resize(32 * k); y.resize(32 * k); inf.resize(k); }
+  void append(const uint8_t* px, const uint8_t* py, const uint8_t* pf, size_t k) {
+    x.insert(x.end(), px, px + 32 * k); y.insert(y.end(), py, py + 32 * k); inf.insert(inf.end(), pf, pf + k);
+  }
+  void append(const Pts& o, size_t from, size_t k) { append(o.x.data() + 32 * from, o.y.data() + 32 * from, o.inf.data() + from, k); }
+};
+
+// C planes of c1 and of c2, `times` over, in the order of the layer call
+Pts gather(Pts& c1, const Pts& c2, size_t C, size_t times, Step::Order order) {
+  Pts in;
+  if (order == Step::kInterleaved) {
+    const size_t per = c1.n() / C;
+    for (size_t p = 0; p < C * times; p++) {
+      in.append(c1, (p % C) * per, per);
+      in.append(c2, (p % C) * per, per);
+    }
+    return in;
+  }
+  if (times == 1) {  // c1, c2 are rebuilt from the layer's output
+    in = std::move(c1);
+    in.append(c2, 0, c2.n());
+    return in;
+  }
+  for (size_t t = 0; t < times; t++) in.append(c1, 0, c1.n());
+  for (size_t t = 0; t < times; t++) in.append(c2, 0, c2.n());
+  return in;
+}
+
+void split(const vpin_conv_trace& t, Step::Order order, Pts* c1, Pts* c2) {
+  const size_t per = t.oh * t.ow;
+  c1->resize(0); c2->resize(0);
+  for (size_t p = 0; p < t.P; p++)
+    ((order == Step::kInterleaved ? p % 2 : p >= t.P / 2) ? c2 : c1)
+        ->append(&t.out_x[32 * p * per], &t.out_y[32 * p * per], &t.out_inf[p * per], per);
+}
+
+// the bias under the client's key, N values encrypted with the caller's r before the layer (encryptBias), then the layer on the
+// c1 row and the c2 row
+int fc(const Call& a, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
+  Pts b, b2;
+  b.resize(s.N); b2.resize(s.N);
+  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, s.bias, r_le32, s.N, b.x.data(), b.y.data(), b.inf.data(), b2.x.data(), b2.y.data(),
+                                 b2.inf.data());
+  if (rc) return rc;
+  b.append(b2, 0, s.N);
+  std::vector<uint32_t> wu(s.K * s.N);
+  for (size_t i = 0; i < s.K * s.N; i++) wu[i] = (uint32_t)s.w[i];
+  return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(), b.inf.data(),
+                     key, a.prf_bytes, out);
+}
+
+// one interaction with the client: the step's output goes out, the activated and re-encrypted values come back into c1, c2
+int interact(const Call& a, const Step& s, Pts* c1, Pts* c2) {
+  const size_t n = c1->n();
+  Pts a1, a2;
+  uint8_t* o[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // no outputs when nothing is encrypted again
+  if (s.reencrypt) {
+    a1.resize(n); a2.resize(n);
+    o[0] = a1.x.data(); o[1] = a1.y.data(); o[2] = a1.inf.data(); o[3] = a2.x.data(); o[4] = a2.y.data(); o[5] = a2.inf.data();
+  }
+  const int flags = (s.relu ? VPIN_LENET_RELU : 0) | (s.reencrypt ? VPIN_LENET_REENCRYPT : 0);
+  set_last_error_text("");  // a foreign callback may fail without a text of its own: no stale one is quoted then
+  const int rc = a.round_fn(a.user, s.round, flags, s.shift_bits, c1->x.data(), c1->y.data(), c1->inf.data(), c2->x.data(), c2->y.data(),
+                            c2->inf.data(), n, o[0], o[1], o[2], o[3], o[4], o[5]);
+  if (rc && !*vpin_last_error()) set_last_error_text("the round callback failed");
+  if (!rc && s.reencrypt) { std::swap(*c1, a1); std::swap(*c2, a2); }
+  return rc;
+}
+
+}  // namespace
+
+bool any_negative(const int32_t* w, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (w[i] < 0) return true;
+  return false;
+}
+
+int run(const Call& a, const std::vector<Step>& steps, Result* out) {
+  const std::string who = std::string(a.who) + ": ";
+  // the failing call's own text behind the step or round it happened in
+  auto named = [&](int rc, const std::string& where) { return fail(rc, (who + where + ": " + vpin_last_error()).c_str()); };
+  size_t keys = 0, bias_r = 0;
+  bool any_round = false;
+  for (const Step& s : steps) { keys += s.keys; bias_r += s.kind == Step::kFc ? s.N : 0; any_round = any_round || s.has_round; }
+  if (a.n_keys != keys)
+    return fail(VPIN_EINVAL, (who + "the number of PRF keys is not one per convolution plane and fully connected row").c_str());
+  if (a.n_bias_r != bias_r)
+    return fail(VPIN_EINVAL, (who + "the number of bias randomness values is not one per fully connected output").c_str());
+  if ((keys && !a.keys32) || (bias_r && (!a.bias_r_le32 || !a.baseG || !a.baseH)) || (any_round && !a.round_fn))
+    return fail(VPIN_EINVAL, (who + "null argument").c_str());
+  out->step_ms.assign(steps.size(), 0.0);
+  out->round_ms.assign(steps.size(), 0.0);
+  enc::Lap total, lap;
+  const uint8_t* key = a.keys32;
+  const uint8_t* br = a.bias_r_le32;
+  size_t C = a.C, H = a.H, W = a.W;
+  Pts c1, c2;  // what the server holds
+  c1.append(a.c1x, a.c1y, a.c1inf, C * H * W);
+  c2.append(a.c2x, a.c2y, a.c2inf, C * H * W);
+  for (size_t i = 0; i < steps.size(); i++) {
+    const Step& s = steps[i];
+    int rc = VPIN_OK;
+    if (s.sum_table) {
+      for (Pts* p : {&c1, &c2}) {
+        Pts sum;
+        sum.resize(s.sum_out * H * W);
+        rc = vpin_e2_plane_sums(a.c, p->x.data(), p->y.data(), p->inf.data(), C, H, W, s.sum_table, s.sum_out, sum.x.data(), sum.y.data(),
+                                sum.inf.data());
+        if (rc) return named(rc, s.name);
+        std::swap(*p, sum);
+      }
+      C = s.sum_out;
+    }
+    if (s.kind == Step::kFc) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
+    const Pts in = gather(c1, c2, C, s.repeat, s.order);
+    C *= s.repeat;
+    vpin_conv_trace* tr = nullptr;
+    if (s.kind == Step::kConv) {
+      rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, key,
+                           a.prf_bytes, &tr);
+    } else if (s.kind == Step::kPool) {
+      rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
+    } else {
+      rc = fc(a, s, in, key, br, &tr);
+      br += 32 * s.N;
+    }
+    key += 32 * s.keys;
+    out->step_ms[i] = 1e3 * lap();
+    if (rc) return named(rc, s.name);
+    out->step.push_back(tr);
+    split(*tr, s.order, &c1, &c2);
+    C = tr->P / 2; H = tr->oh; W = tr->ow;
+    if (!s.has_round) continue;
+    rc = interact(a, s, &c1, &c2);
+    out->round_ms[i] = 1e3 * lap();
+    if (rc) return named(rc, s.round_name);
+  }
+  out->total_ms = 1e3 * total();
+  return VPIN_OK;
+}
+
+}  // namespace vpin::infer

@@ -1,0 +1,73 @@
+// infer_core.h -- the one server loop behind vpin_lenet_infer and vpin_net_infer (infer_core.cpp): a list of steps over the
+// server's (c1, c2) planes, each a layer call with the client's round after it.  Internal: the two entry points translate their
+// configuration into steps and keep their own trace types around the Result.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "../../include/vpin_hip.h"
+#include "enc_conv.h"
+
+namespace vpin::infer {
+
+struct Step {
+  enum Kind { kConv, kPool, kFc } kind = kConv;
+  // how c1 and c2 make up the layer call's P = 2 C planes, and how its output splits back: all c1 planes and then all c2 planes
+  // (first half, second half), or (0, c1), (0, c2), (1, c1), .. (even planes, odd planes).  For kFc, P = 2, they coincide
+  enum Order { kBlocked, kInterleaved } order = kBlocked;
+  const uint8_t* filter_le16 = nullptr;  // kConv
+  size_t fh = 0, fw = 0, pad = 0;
+  size_t stride = 1;                     // kConv and kPool
+  size_t k = 0;                          // kPool
+  const uint8_t* scale_le16 = nullptr;
+  size_t K = 0, N = 0;                   // kFc
+  const int32_t* w = nullptr;
+  const int64_t* bias = nullptr;
+  // before the call: vpin_e2_plane_sums by this table on c1 and on c2 (sum_out planes each), when there is one ..
+  const uint8_t* sum_table = nullptr;
+  size_t sum_out = 0;
+  size_t repeat = 1;  // .. and then the planes handed to the call this many times over
+  size_t keys = 0;    // PRF keys the call consumes
+  std::string name;   // in error texts: "<who>: <name>: .."
+  // the client's round after the call
+  bool has_round = false;
+  int round = 0, relu = 0, shift_bits = 0, reencrypt = 1;
+  std::string round_name;
+};
+
+// what both entry points are given, and the input's shape
+struct Call {
+  vpin_ctx* c;
+  const char* who;  // the entry point's name, in front of every error text
+  int prf_bytes;
+  size_t C, H, W;
+  const uint8_t *c1x, *c1y, *c1inf, *c2x, *c2y, *c2inf;
+  const vpin_e2_base *baseG, *baseH;
+  const uint8_t* keys32;
+  size_t n_keys;
+  const uint8_t* bias_r_le32;
+  size_t n_bias_r;
+  vpin_lenet_round_fn round_fn;
+  void* user;
+};
+
+// per step the trace of its layer call, owned; host-clock milliseconds per step (plane sums included), per round (0: none) and in all
+struct Result {
+  std::vector<vpin_conv_trace*> step;
+  std::vector<double> step_ms, round_ms;
+  double total_ms = 0.0;
+  Result() = default;
+  Result(const Result&) = delete;
+  Result& operator=(const Result&) = delete;
+  ~Result() {
+    for (vpin_conv_trace* t : step) vpin_conv_trace_free(t);
+  }
+};
+
+// VPIN_EINVAL when n_keys or n_bias_r is not what the steps consume, or an array they need is NULL; a failing step or round
+// returns its code behind "<who>: <name>: ".  The timings are filled as far as the run got; the caller drops `out` on failure
+int run(const Call& call, const std::vector<Step>& steps, Result* out);
+
+bool any_negative(const int32_t* w, size_t n);
+
+}  // namespace vpin::infer

@@ -10,27 +10,12 @@ import os
 
 import numpy as np
 
-from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, LenetCfg, _chk, lib
+from . import inference
+from .capi import LenetCfg, _chk, lib
+from .inference import RELU, REENCRYPT, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
-RELU, REENCRYPT = 1, 2
 LABELS = ("L1", "L2", "L3", "L4", "L5", "L6", "L7")
 _GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
-
-
-def min_max_scaling(image):
-    image = np.asarray(image)
-    lo, hi = np.min(image), np.max(image)
-    return np.clip((image - lo) / (hi - lo), a_min=0.001, a_max=0.9999999)
-
-
-def fixed_point(values, bits=16):
-    """real numbers -> the int32 fixed point the reference works on (truncation toward zero)"""
-    return (np.asarray(values) * 2**bits).astype(np.int32)
-
-
-def preprocess(image):
-    """the client's min_max_scaling and 16-bit fixed point: an H x W (or 1 x 1 x H x W) image of reals -> int32 of the same shape"""
-    return fixed_point(min_max_scaling(image))
 
 
 class Config:
@@ -94,96 +79,26 @@ def default_config(w1, b1, w2, b2, filt=None, connect=None):
     return Config(filt, connect, w1, b1, w2, b2)
 
 
-class Client:
-    """vpin_lenet_client: the key, the two base tables, the discrete-log table and the queue of randomness"""
+class Client(inference.Client):
+    """the ready-made client made for the seven rounds; `values(rnd)` counts them R1 .. R7, from 1"""
+    first_round = 1
 
     def __init__(self, ctx, sk, nb, max_giant, rs):
-        self.ctx = ctx
-        h = C.c_void_p()
-        k = ctx._u256s([sk])
-        r = ctx._u256s(rs) if len(rs) else np.zeros(32, np.uint8)
-        mg = (C.c_uint64 * 7)(*[int(v) for v in max_giant])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _chk(lib().vpin_lenet_client_create(ctx.h, p(k), nb, mg, p(r), len(rs), C.byref(h)), "vpin_lenet_client_create")
-        self.h = h
-        g, hh = C.c_void_p(), C.c_void_p()
-        _chk(lib().vpin_lenet_client_bases(h, C.byref(g), C.byref(hh)), "vpin_lenet_client_bases")
-        self.base_g, self.base_h = g, hh
-        self.round_fn = C.cast(lib().vpin_lenet_client_round, C.c_void_p)
-        self.user = h
-
-    def encrypt(self, msgs, rs):
-        """the image's encryption under the client's key -> (c1, c2), each (x, y, inf)"""
-        return self.ctx.e2_encrypt(self.base_g, self.base_h, msgs, rs)
-
-    def values(self, rnd):
-        """(v, act) of round 1 .. 7 as int64 arrays"""
-        v, a, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _chk(lib().vpin_lenet_client_values(self.h, rnd, C.byref(v), C.byref(a), C.byref(n)), "vpin_lenet_client_values")
-        get = lambda p: np.frombuffer((C.c_int64 * n.value).from_address(p.value), dtype=np.int64).copy() if n.value else np.zeros(0, np.int64)
-        return get(v), get(a)
-
-    def free(self):
-        if self.h:
-            lib().vpin_lenet_client_free(self.h)
-            self.h = None
+        assert len(max_giant) == 7
+        super().__init__(ctx, sk, nb, max_giant, rs)
 
 
-def python_round(fn):
-    """a vpin_lenet_round_fn around fn(round, relu, reencrypt, shift_bits, c1, c2) -> (c1_out, c2_out) or None, the ciphertexts
-    as (x, y, inf) numpy triples.  An exception must not unwind through the C frames: the callback returns VPIN_EINVAL, keeps
-    the exception in `.error`, and `run` raises it again once vpin_lenet_infer has returned"""
-
-    def cb(user, rnd, flags, bits, x1, y1, f1, x2, y2, f2, cnt, ox1, oy1, of1, ox2, oy2, of2):
-        view = lambda p, n: np.frombuffer((C.c_uint8 * n).from_address(p), dtype=np.uint8)
-        try:
-            c1 = (view(x1, 32 * cnt).reshape(cnt, 32).copy(), view(y1, 32 * cnt).reshape(cnt, 32).copy(), view(f1, cnt).copy())
-            c2 = (view(x2, 32 * cnt).reshape(cnt, 32).copy(), view(y2, 32 * cnt).reshape(cnt, 32).copy(), view(f2, cnt).copy())
-            out = fn(rnd, bool(flags & RELU), bool(flags & REENCRYPT), bits, c1, c2)
-            if flags & REENCRYPT:
-                for dst, src, n in zip((ox1, oy1, of1, ox2, oy2, of2), tuple(out[0]) + tuple(out[1]), (32 * cnt, 32 * cnt, cnt) * 2):
-                    C.memmove(dst, np.ascontiguousarray(src, dtype=np.uint8).ctypes.data, n)
-            return 0
-        except Exception as e:  # noqa: BLE001
-            wrapped.error = e
-            return -1
-
-    wrapped = LENET_ROUND_FN(cb)
-    wrapped.error = None
-    return wrapped
-
-
-class Trace:
+class Trace(inference.Trace):
     """vpin_lenet_trace: per label the ConvTrace of its layer call (borrowed)"""
-
-    def __init__(self, ctx, handle):
-        self.ctx, self.h = ctx, handle
+    prefix = "vpin_lenet_trace"
 
     def label(self, name):
         h = C.c_void_p()
         _chk(lib().vpin_lenet_trace_label(self.h, LABELS.index(name) + 1, C.byref(h)), "vpin_lenet_trace_label")
-        t = ConvTrace(self.ctx, h)
-        t.free = lambda: None  # borrowed: the Trace frees it
-        return t
+        return self._borrowed(h)
 
     def instances(self, name):
-        hm, ha = C.c_void_p(), C.c_void_p()
-        _chk(lib().vpin_lenet_trace_instances(self.ctx.h, self.h, LABELS.index(name) + 1, C.byref(hm), C.byref(ha)), "vpin_lenet_trace_instances")
-        return (DevInstance(self.ctx, hm) if hm.value else None), (DevInstance(self.ctx, ha) if ha.value else None)
-
-    def result(self):
-        """the last layer's ciphertext -> (c1, c2), each (x, y, inf)"""
-        x, y, f, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _chk(lib().vpin_lenet_trace_result(self.h, C.byref(x), C.byref(y), C.byref(f), C.byref(n)), "vpin_lenet_trace_result")
-        n = n.value
-        get = lambda p, k: np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8).copy()
-        xs, ys, fs = get(x, 64 * n).reshape(2, n, 32), get(y, 64 * n).reshape(2, n, 32), get(f, 2 * n).reshape(2, n)
-        return (xs[0], ys[0], fs[0]), (xs[1], ys[1], fs[1])
-
-    def free(self):
-        if self.h:
-            lib().vpin_lenet_trace_free(self.h)
-            self.h = None
+        return self._instances(LABELS.index(name) + 1)
 
 
 def timings():
@@ -194,32 +109,13 @@ def timings():
 
 def run(ctx, cfg, image_c1, image_c2, base_g, base_h, keys, bias_rs, round_fn, user=None):
     """vpin_lenet_infer -> Trace.  keys: 32-byte keys in call order; bias_rs: ints; round_fn: a LENET_ROUND_FN or a pointer"""
-    x1, y1, f1 = ctx._points(*image_c1)
-    x2, y2, f2 = ctx._points(*image_c2)
-    k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
-    r = ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
-    h = C.c_void_p()
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    fn = C.cast(round_fn, C.c_void_p)
-    rc = lib().vpin_lenet_infer(ctx.h, C.byref(cfg.c), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h, p(k), len(keys), p(r),
-                                len(bias_rs), fn, user, C.byref(h))
-    if rc:
-        assert not h.value
-        err, lib_text = getattr(round_fn, "error", None), lib().vpin_last_error().decode()
-        if err is not None:  # the Python callback's own exception, with the round the driver names
-            round_fn.error = None
-            raise RuntimeError("the round callback raised [%s]" % lib_text) from err
-        _chk(rc, "vpin_lenet_infer")
-    return Trace(ctx, h)
+    return Trace(ctx, inference.run_infer("vpin_lenet_infer", ctx, cfg.c, image_c1, image_c2, base_g, base_h, keys, bias_rs, round_fn, user))
 
 
 def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
     """image: H x W ints (see preprocess).  Encrypts it under the client's key, runs the server loop against the ready-made
     client and returns (scores, rounds, trace): the N2 class scores, per round R1 .. R7 its (v, act), and the Trace"""
-    c1, c2 = client.encrypt(np.asarray(image, dtype=np.int64).reshape(-1), image_rs)
-    trace = run(ctx, cfg, c1, c2, client.base_g, client.base_h, keys, bias_rs, client.round_fn, client.user)
-    rounds = [client.values(r) for r in range(1, 8)]
-    return rounds[6][1], rounds, trace
+    return inference.infer(run, ctx, cfg, client, image, image_rs, keys, bias_rs)
 
 
 def write_witness_files(trace, root):

@@ -12,8 +12,9 @@ import os
 
 import numpy as np
 
-from .capi import ConvTrace, DevInstance, NetCfg, NetLayer, _chk, lib
-from .lenet import RELU, REENCRYPT, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
+from . import inference
+from .capi import NetCfg, NetLayer, _chk, lib
+from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
 CONV, POOL, FC = 0, 1, 2
 VERSIONS = ("A", "B", "C", "D", "E")
@@ -117,54 +118,15 @@ def cnn_config(version, nb_log=24, golden=None):
     return cfg
 
 
-class Client:
-    """vpin_net_client: the key, the two base tables, the discrete-log table and the queue of randomness, for n rounds"""
-
-    def __init__(self, ctx, sk, nb, max_giant, rs):
-        self.ctx, self.n_rounds = ctx, len(max_giant)
-        h = C.c_void_p()
-        k = ctx._u256s([sk])
-        r = ctx._u256s(rs) if len(rs) else np.zeros(32, np.uint8)
-        mg = (C.c_uint64 * len(max_giant))(*[int(v) for v in max_giant])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _chk(lib().vpin_net_client_create(ctx.h, p(k), nb, len(max_giant), mg, p(r), len(rs), C.byref(h)), "vpin_net_client_create")
-        self.h = h
-        g, hh = C.c_void_p(), C.c_void_p()
-        _chk(lib().vpin_net_client_bases(h, C.byref(g), C.byref(hh)), "vpin_net_client_bases")
-        self.base_g, self.base_h = g, hh
-        self.round_fn = C.cast(lib().vpin_net_client_round, C.c_void_p)
-        self.user = h
-
-    def encrypt(self, msgs, rs):
-        """the input's encryption under the client's key -> (c1, c2), each (x, y, inf)"""
-        return self.ctx.e2_encrypt(self.base_g, self.base_h, msgs, rs)
-
-    def values(self, rnd):
-        """(v, act) of round 0 .. n_rounds - 1 as int64 arrays"""
-        v, a, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _chk(lib().vpin_net_client_values(self.h, rnd, C.byref(v), C.byref(a), C.byref(n)), "vpin_net_client_values")
-        get = lambda p: np.frombuffer((C.c_int64 * n.value).from_address(p.value), dtype=np.int64).copy() if n.value else np.zeros(0, np.int64)
-        return get(v), get(a)
-
-    def free(self):
-        if self.h:
-            lib().vpin_net_client_free(self.h)
-            self.h = None
-
-
-class Trace:
+class Trace(inference.Trace):
     """vpin_net_trace: per layer the ConvTrace of its layer call, and the label, all borrowed"""
+    prefix = "vpin_net_trace"
 
     def __init__(self, ctx, handle):
-        self.ctx, self.h = ctx, handle
+        super().__init__(ctx, handle)
         n = C.c_size_t()
         _chk(lib().vpin_net_trace_layers(handle, C.byref(n)), "vpin_net_trace_layers")
         self.n_layers = n.value
-
-    def _borrowed(self, h):
-        t = ConvTrace(self.ctx, h)
-        t.free = lambda: None  # borrowed: the Trace frees it
-        return t
 
     def layer(self, i):
         h = C.c_void_p()
@@ -178,23 +140,7 @@ class Trace:
         return self._borrowed(h)
 
     def instances(self):
-        hm, ha = C.c_void_p(), C.c_void_p()
-        _chk(lib().vpin_net_trace_instances(self.ctx.h, self.h, C.byref(hm), C.byref(ha)), "vpin_net_trace_instances")
-        return (DevInstance(self.ctx, hm) if hm.value else None), (DevInstance(self.ctx, ha) if ha.value else None)
-
-    def result(self):
-        """the last layer's ciphertext -> (c1, c2), each (x, y, inf)"""
-        x, y, f, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-        _chk(lib().vpin_net_trace_result(self.h, C.byref(x), C.byref(y), C.byref(f), C.byref(n)), "vpin_net_trace_result")
-        n = n.value
-        get = lambda p, k: np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8).copy()
-        xs, ys, fs = get(x, 64 * n).reshape(2, n, 32), get(y, 64 * n).reshape(2, n, 32), get(f, 2 * n).reshape(2, n)
-        return (xs[0], ys[0], fs[0]), (xs[1], ys[1], fs[1])
-
-    def free(self):
-        if self.h:
-            lib().vpin_net_trace_free(self.h)
-            self.h = None
+        return self._instances()
 
 
 def timings(n_layers):
@@ -207,33 +153,13 @@ def timings(n_layers):
 def run(ctx, cfg, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user=None):
     """vpin_net_infer -> Trace.  c1, c2: (x, y, inf) of the C * H * W input points; keys: 32-byte keys in call order; bias_rs:
     ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer"""
-    x1, y1, f1 = ctx._points(*c1)
-    x2, y2, f2 = ctx._points(*c2)
-    k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
-    r = ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
-    h = C.c_void_p()
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    fn = C.cast(round_fn, C.c_void_p)
-    c = cfg.c
-    rc = lib().vpin_net_infer(ctx.h, C.byref(c), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h, p(k), len(keys), p(r),
-                              len(bias_rs), fn, user, C.byref(h))
-    if rc:
-        assert not h.value
-        err, lib_text = getattr(round_fn, "error", None), lib().vpin_last_error().decode()
-        if err is not None:  # the Python callback's own exception, with the round the driver names
-            round_fn.error = None
-            raise RuntimeError("the round callback raised [%s]" % lib_text) from err
-        _chk(rc, "vpin_net_infer")
-    return Trace(ctx, h)
+    return Trace(ctx, inference.run_infer("vpin_net_infer", ctx, cfg.c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user))
 
 
 def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
     """image: C x H x W ints (see preprocess).  Encrypts it under the client's key, runs the server loop against the ready-made
     client and returns (scores, rounds, trace): the last round's activated values, per round its (v, act), and the Trace"""
-    c1, c2 = client.encrypt(np.asarray(image, dtype=np.int64).reshape(-1), image_rs)
-    trace = run(ctx, cfg, c1, c2, client.base_g, client.base_h, keys, bias_rs, client.round_fn, client.user)
-    rounds = [client.values(r) for r in range(client.n_rounds)]
-    return rounds[-1][1], rounds, trace
+    return inference.infer(run, ctx, cfg, client, image, image_rs, keys, bias_rs)
 
 
 def write_witness_files(trace, root, label):
