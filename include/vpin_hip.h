@@ -716,6 +716,34 @@ int vpin_enc_fc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8
 int vpin_enc_avgpool2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
                        size_t k, size_t stride, const uint8_t scale_le16[16], vpin_conv_trace** out);
 
+/* The trained convolution layer: one filter per (output channel, input channel), signed weights, the channel mixing inside the
+ * proven check.  The reference's convolution is one non-negative filter for all planes with the channels summed beforehand and
+ * unproven (vpin_e2_plane_sums); this is its own check -- myConv2d type 1 with rLCL / rLCR type 0 -- per output plane with one
+ * chain over all (channel, tap) terms.  groups x C planes of H x W points, group-major (a group: the c1 or the c2 image, or a batch
+ * element); weights W[o][c][ii][jj] as n_out * C * fh * fw int32, row-major; connect[o][c], n_out * C bytes, non-zero = connected,
+ * NULL = all connected (the table is architecture, public; weights of unconnected pairs are not read).
+ *   out[g][o][i][j] = sum_{c connected to o} sum_{ii,jj} W[o][c][ii][jj] * X[g][c][i*stride + ii][j*stride + jj]
+ * X padded with identities; the output planes are group-major, then o.  One key per (g, o), group-major: keys32 = groups * n_out
+ * x 32 bytes.  The check per (g, o), with r_t the PRF of vpin_enc_conv2d under that pair's key:
+ *   left = sum_t r_t * out[g][o][t];  B'[c][k] = sum_t r_t * window_t(X[g][c])[k] for the connected c ascending, the taps k row-major.
+ *   Term m = (c, k) in that order records the multiplication (|w_m|, S_m), S_m = B'[c][k] for w_m >= 0 and -B'[c][k] = (x, q - y)
+ *   for w_m < 0: the gadget's weights are u128, so the sign goes into the point.  T_m = |w_m| * S_m; acc = T_0 and every later
+ *   term records the addition (acc, T_m), an identity T_m as rz = 1; acc == left at the end.
+ * VPIN_ESHAPE when a B'[c][k] is the identity or the accumulator is the identity before a step (as in vpin_enc_conv2d: a zero
+ * FIRST weight of a pair's chain, an all-identity connected channel, terms that cancel before the last step; the accumulator
+ * after the last step may be the identity, it is only compared).  VPIN_EVERIFY when the two sides differ.  VPIN_EINVAL as for
+ * vpin_enc_conv2d, and for groups, C or n_out zero and a row of connect that selects no channel.
+ * The trace's dims are {groups * n_out, oh, ow, M, M - groups * n_out} with M = groups * fh * fw * (connected pairs); with
+ * C = n_out = 1, groups = P and non-negative weights it is vpin_enc_conv2d's trace byte for byte. */
+int vpin_enc_conv2d_mc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
+                       size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
+                       const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out);
+/* the bare stage beside vpin_e2_conv2d: the output ciphertext only (groups * n_out * oh * ow points), no check; a cancelled
+ * output is the flagged identity */
+int vpin_e2_conv2d_mc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
+                      size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
+                      uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+
 /* ---- the client side: exponential ElGamal on E2 (key generation, encryption, decryption with a discrete-log table) ------
  * What the reference's client does around every layer (src/LeNet/Client.py: encrypt, decrypt, bsgs): with the generator G of
  * prime order n, a key sk and H = sk * G, a signed message m is (c1, c2) = (r * G, m * G + r * H), and
@@ -883,6 +911,10 @@ void vpin_lenet_last_timings(double out[16]);
 #define VPIN_NET_CONV 0
 #define VPIN_NET_POOL 1
 #define VPIN_NET_FC 2
+/*   VPIN_NET_CONVMC  the trained convolution: vpin_enc_conv2d_mc with groups = 2 (the C c1 planes, then the C c2 planes) under
+ *                  n_out x C filters of fh x fw int32 weights (w_mc) and the optional table connect; 2 n_out keys, (c1, o) first;
+ *                  n_out planes go on.  Its fields stand at the END of vpin_net_layer (ABI 3); the other kinds read none of them */
+#define VPIN_NET_CONVMC 3
 typedef struct vpin_net_layer {
   int kind;
   size_t fh, fw, pad;            /* CONV */
@@ -895,6 +927,9 @@ typedef struct vpin_net_layer {
   const int64_t* bias;           /* FC: N values */
   int has_round, relu, shift_bits, reencrypt;
   uint64_t max_giant;
+  size_t n_out;                  /* CONVMC (with fh, fw, pad, stride): the output channels */
+  const int32_t* w_mc;           /* CONVMC: n_out x C x fh x fw, row-major, signed */
+  const uint8_t* connect;        /* CONVMC: n_out x C bytes, non-zero = connected; NULL: all */
 } vpin_net_layer;
 typedef struct vpin_net_cfg {
   size_t C, H, W;                /* the encrypted input */
@@ -906,7 +941,8 @@ typedef struct vpin_net_cfg {
  * of the label, out[4] decryptions, out[5] client encryptions (the input included), out[6] PRF keys, out[7] bias r; then per
  * layer i out[8 + 3 i] its multiplications, out[9 + 3 i] its additions, out[10 + 3 i] the decryptions of the round after it (0:
  * none).  VPIN_EINVAL for a zero dimension, a window that does not fit, an FC whose K is not the incoming C * H * W, an unknown
- * kind, shift_bits outside 0 .. 62, reencrypt = 0 before the last layer, prf_bytes outside 1 .. 16 */
+ * kind, shift_bits outside 0 .. 62, reencrypt = 0 before the last layer, prf_bytes outside 1 .. 16, a CONVMC layer with n_out = 0
+ * or a row of connect that selects no channel (the table is read here: the counts depend on it; the weights are not) */
 int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
 typedef struct vpin_net_trace vpin_net_trace;
 /* The server loop, the same driver as vpin_lenet_infer with one step per layer, the planes blocked (all c1, then all c2): the

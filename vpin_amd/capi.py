@@ -60,7 +60,7 @@ class NetLayer(C.Structure):
     _fields_ = [("kind", C.c_int), ("fh", C.c_size_t), ("fw", C.c_size_t), ("pad", C.c_size_t), ("stride", C.c_size_t),
                 ("filter_le16", C.c_void_p), ("k", C.c_size_t), ("scale_le16", C.c_uint8 * 16), ("K", C.c_size_t), ("N", C.c_size_t),
                 ("w", C.c_void_p), ("bias", C.c_void_p), ("has_round", C.c_int), ("relu", C.c_int), ("shift_bits", C.c_int),
-                ("reencrypt", C.c_int), ("max_giant", C.c_uint64)]
+                ("reencrypt", C.c_int), ("max_giant", C.c_uint64), ("n_out", C.c_size_t), ("w_mc", C.c_void_p), ("connect", C.c_void_p)]
 
 
 class NetCfg(C.Structure):
@@ -196,6 +196,8 @@ def lib():
     L.vpin_e2_mul_chain.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t] + [vp] * 6
     L.vpin_e2_conv2d.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
     L.vpin_enc_conv2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
+    L.vpin_e2_conv2d_mc.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
+    L.vpin_enc_conv2d_mc.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_fc.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_avgpool2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, C.POINTER(vp)]
     L.vpin_conv_trace_free.argtypes = [vp]
@@ -1310,6 +1312,43 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         rc = lib().vpin_enc_conv2d(self.h, p(x), p(y), p(f), P, H, W, p(w), fh, fw, pad, stride, p(k), prf_bytes, C.byref(h))
         return self._trace(rc, h, "vpin_enc_conv2d")
+
+    @staticmethod
+    def _mc_args(weights, connect, groups, C_, n_out, fh, fw):
+        """W[o][c][ii][jj] as contiguous int32 and the optional table as bytes, with the pointers the C ABI takes"""
+        w64 = np.asarray(weights, dtype=np.int64).reshape(n_out, C_, fh, fw)
+        w = np.ascontiguousarray(w64.astype("<i4"))
+        assert np.array_equal(w, w64), "a weight does not fit int32"
+        t = None if connect is None else np.ascontiguousarray(np.asarray(connect).reshape(n_out, C_) != 0, dtype=np.uint8)
+        return w, t, w.ctypes.data_as(C.c_void_p), (None if t is None else t.ctypes.data_as(C.c_void_p))
+
+    def e2_conv2d_mc(self, x, y, inf, groups, C_, n_out, H, W, weights, connect, fh, fw, pad=0, stride=1):
+        """the bare stage (vpin_e2_conv2d_mc): groups x C_ planes of H x W points under n_out x C_ signed filters.  Returns
+        (x, y, inf) of the groups * n_out output planes, shaped (groups, n_out, oh, ow[, 32])"""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == groups * C_ * H * W
+        w, t, pw, pt = self._mc_args(weights, connect, groups, C_, n_out, fh, fw)
+        oh, ow = (H + 2 * pad - fh) // stride + 1, (W + 2 * pad - fw) // stride + 1
+        n = groups * n_out * max(oh, 0) * max(ow, 0)
+        ox, oy, oi = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_conv2d_mc(self.h, p(x), p(y), p(f), groups, C_, n_out, H, W, pw, pt, fh, fw, pad, stride, p(ox), p(oy), p(oi)),
+             "vpin_e2_conv2d_mc")
+        s = (groups, n_out, oh, ow)
+        return ox.reshape(s + (32,)), oy.reshape(s + (32,)), oi.reshape(s)
+
+    def enc_conv2d_mc(self, x, y, inf, groups, C_, n_out, H, W, weights, connect, fh, fw, pad, stride, keys, prf_bytes=16):
+        """the trained convolution layer (vpin_enc_conv2d_mc): weights[o][c][ii][jj] signed ints (int32 range), connect: n_out x C_
+        (None: all connected), one 32-byte key per (group, o), group-major -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        assert x.shape[0] == groups * C_ * H * W
+        w, t, pw, pt = self._mc_args(weights, connect, groups, C_, n_out, fh, fw)
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy()
+        assert k.size == 32 * groups * n_out
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_conv2d_mc(self.h, p(x), p(y), p(f), groups, C_, n_out, H, W, pw, pt, fh, fw, pad, stride, p(k), prf_bytes, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_conv2d_mc")
 
     def _trace(self, rc, h, where):
         if rc:

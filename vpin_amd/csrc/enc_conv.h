@@ -38,6 +38,16 @@ constexpr uint32_t kE2FlagOffCurve = 2u;  // a non-identity point that does not 
 // e2_chain_scan_kernel, one e2_to_affine_kernel launch):
 //   mul_chain   P chains of K terms over the loaded points: T[p][k] = s[p][k] * X[p][k] and the inclusive prefixes
 //               acc[p][k] = T[p][0] + .. + T[p][k], both as canonical bytes with identity flags (P * K points each)
+// The convolution with one signed filter per (output channel, input channel) and its sums (enc_convmc.hip), over the loaded
+// points as groups x C planes (this->g after conv_mc: P = groups * C):
+//   conv_mc     out[g][o][t] = sum over the connected c and the taps k of w[o][c][k] * window_t(X[g][c])[k] (e2_convmc_kernel),
+//               normalised; the groups * n_out output planes stay resident for rlc_mc and go to the host as canonical bytes.
+//               w: n_out * C * taps() int32, connect: n_out * C bytes (never NULL here), top_bit: per o the top set bit of its
+//               largest |w| over the connected channels, -1 when all are zero
+//   rlc_mc      n_sums sums, one descriptor of four ints each: {plane, tap, pair, 0}.  plane >= 0: sum_t r[pair][t] *
+//               window_t(X[plane])[tap]; plane = -1: sum_t r[pair][t] * out[pair][t]; plane = -2: no terms (the padding of a
+//               chain).  neg[i] != 0 negates sum i (e2_negate_kernel).  All sums are normalised by one launch: canonical bytes and
+//               flags to the host, and the Montgomery coordinates become tail's loaded points, ready for tail->mul_chain
 struct EncConvDev {
   vpin_ctx* c;
   ConvGeom g;
@@ -51,6 +61,10 @@ struct EncConvDev {
   int pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity);
   int mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y,
                 uint8_t* acc_inf);
+  int conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_out, const int32_t* w, const uint8_t* connect, const int32_t* top_bit,
+              uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+  int rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, EncConvDev* tail, uint8_t* s_x,
+             uint8_t* s_y, uint8_t* s_inf);
 };
 
 // What enc_fc.hip takes from enc_conv.hip (types: fq_dev.h, e2_dev.h): the curve coefficient a in Montgomery form, the
@@ -116,7 +130,7 @@ struct Lap {
 
 }  // namespace vpin
 
-// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_fc, vpin_enc_avgpool2d)
+// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_conv2d_mc, vpin_enc_fc, vpin_enc_avgpool2d)
 struct vpin_conv_trace {
   size_t P = 0, oh = 0, ow = 0, n_mult = 0, n_add = 0;
   std::vector<uint8_t> out_x, out_y, out_inf;        // P * oh * ow

@@ -1,5 +1,5 @@
-// infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_avgpool2d,
-// vpin_enc_fc, vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
+// infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc,
+// vpin_enc_avgpool2d, vpin_enc_fc, vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
 // (lenet.cpp) and vpin_net_infer (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer validates
 // what it is given, the client's answers included.
 #include "infer_core.h"
@@ -135,6 +135,9 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
     if (s.kind == Step::kConv) {
       rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, key,
                            a.prf_bytes, &tr);
+    } else if (s.kind == Step::kConvMc) {
+      rc = vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad, s.stride,
+                              key, a.prf_bytes, &tr);
     } else if (s.kind == Step::kPool) {
       rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
     } else {

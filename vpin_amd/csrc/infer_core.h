@@ -11,7 +11,7 @@
 namespace vpin::infer {
 
 struct Step {
-  enum Kind { kConv, kPool, kFc } kind = kConv;
+  enum Kind { kConv, kPool, kFc, kConvMc } kind = kConv;
   // how c1 and c2 make up the layer call's P = 2 C planes, and how its output splits back: all c1 planes and then all c2 planes
   // (first half, second half), or (0, c1), (0, c2), (1, c1), .. (even planes, odd planes).  For kFc, P = 2, they coincide
   enum Order { kBlocked, kInterleaved } order = kBlocked;
@@ -23,6 +23,9 @@ struct Step {
   size_t K = 0, N = 0;                   // kFc
   const int32_t* w = nullptr;
   const int64_t* bias = nullptr;
+  size_t n_out = 0;                      // kConvMc (with fh, fw, pad, stride): vpin_enc_conv2d_mc with groups = 2, kBlocked
+  const int32_t* w_mc = nullptr;
+  const uint8_t* connect = nullptr;
   // before the call: vpin_e2_plane_sums by this table on c1 and on c2 (sum_out planes each), when there is one ..
   const uint8_t* sum_table = nullptr;
   size_t sum_out = 0;

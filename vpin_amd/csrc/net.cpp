@@ -15,7 +15,9 @@ using vpin::infer::Step;
 
 namespace {
 
-const char* kind_name(int kind) { return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : "fc"; }
+const char* kind_name(int kind) {
+  return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : kind == VPIN_NET_CONVMC ? "convmc" : "fc";
+}
 
 // per layer what it consumes and leaves; the walk that vpin_net_cfg_counts and vpin_net_infer share
 struct LayerPlan {
@@ -48,6 +50,25 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.mult = 2 * C * l.fh * l.fw;
       p.add = 2 * C * (l.fh * l.fw - 1);
       p.keys = 2 * C;
+    } else if (l.kind == VPIN_NET_CONVMC) {
+      if (!l.fh || !l.fw || !l.stride || !l.n_out) return fail(VPIN_EINVAL, "vpin_net: a dimension is zero");
+      if (l.fh > kMaxSide || l.fw > kMaxSide || l.pad > kMaxSide || l.stride > kMaxSide || l.n_out > kMaxPlanes)
+        return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
+      if (H + 2 * l.pad < l.fh || W + 2 * l.pad < l.fw) return fail(VPIN_EINVAL, fit);
+      if (weights && !l.w_mc) return fail(VPIN_EINVAL, "vpin_net: a trained convolution has no weights");
+      size_t pairs = 0;  // the table is architecture: the counts need it, the weights they do not
+      for (size_t o = 0; o < l.n_out; o++) {
+        size_t row = 0;
+        for (size_t ch = 0; ch < C; ch++) row += !l.connect || l.connect[o * C + ch];
+        if (!row) return fail(VPIN_EINVAL, "vpin_net: a row of a trained convolution's connect selects no channel");
+        pairs += row;
+      }
+      p.oC = l.n_out;
+      p.oH = (H + 2 * l.pad - l.fh) / l.stride + 1;
+      p.oW = (W + 2 * l.pad - l.fw) / l.stride + 1;
+      p.mult = 2 * l.fh * l.fw * pairs;
+      p.add = p.mult - 2 * l.n_out;
+      p.keys = 2 * l.n_out;
     } else if (l.kind == VPIN_NET_POOL) {
       if (!l.k || !l.stride) return fail(VPIN_EINVAL, "vpin_net: a dimension is zero");
       if (l.stride > kMaxSide) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
@@ -69,7 +90,7 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.keys = 2;
       p.bias_r = l.N;
     } else {
-      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc");
+      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc, convmc");
     }
     if (l.has_round) {
       if (l.shift_bits < 0 || l.shift_bits > 62) return fail(VPIN_EINVAL, "vpin_net: a round's shift_bits is outside 0 .. 62");
@@ -126,8 +147,9 @@ int vpin_net_infer(vpin_ctx* c, const vpin_net_cfg* g, const uint8_t* c1x, const
   for (size_t i = 0; i < pl.size(); i++) {
     const vpin_net_layer& l = g->layers[i];
     Step& s = steps[i];
-    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : Step::kFc;
+    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc : Step::kFc;
     s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
+    if (l.kind == VPIN_NET_CONVMC) { s.n_out = l.n_out; s.w_mc = l.w_mc; s.connect = l.connect; }  // no other kind reads them
     s.k = l.k; s.scale_le16 = l.scale_le16;
     s.K = l.K; s.N = l.N; s.w = l.w; s.bias = l.bias;
     s.keys = pl[i].keys;

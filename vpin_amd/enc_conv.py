@@ -1,4 +1,4 @@
-"""The encrypted layers of vPIN's inference server over the C ABI (vpin_enc_conv2d, vpin_enc_fc, vpin_enc_avgpool2d):
+"""The encrypted layers of vPIN's inference server over the C ABI (vpin_enc_conv2d, vpin_enc_conv2d_mc, vpin_enc_fc, vpin_enc_avgpool2d):
 ciphertext planes and a filter (or rows and a weight matrix, or a pooling window) in, the output ciphertext and the two gadget
 operation lists out -- as device instances for vpin_snark_prove_dev, or as the witness files the reference's Python service
 writes, so that the unchanged CLI proves a real layer."""
@@ -26,6 +26,21 @@ def conv_layer(ctx, c1, c2, filt, pad, stride, keys, prf_bytes=16):
     rows = [list(r) for r in filt]
     fh, fw = len(rows), len(rows[0])
     return ctx.enc_conv2d(x, y, inf, x.shape[0] // (H * W), H, W, [int(v) for r in rows for v in r], fh, fw, pad, stride, keys, prf_bytes)
+
+
+def convmc_layer(ctx, groups, weights, connect, pad, stride, keys, prf_bytes=16):
+    """The trained convolution layer (vpin_enc_conv2d_mc).  groups: a list of ciphertext images (the c1 and the c2 image, or batch
+    elements), each (x, y, inf) with x, y of shape (C, H, W, 32) and inf of shape (C, H, W) or None; weights: n_out x C x fh x fw
+    signed ints; connect: n_out x C (None: all connected); keys: one 32-byte key per (group, output channel), group-major.
+    Returns the ConvTrace: groups * n_out output planes, group-major."""
+    w = np.asarray(weights, dtype=np.int64)
+    assert w.ndim == 4, "weights[o][c][ii][jj]"
+    n_out, C_, fh, fw = w.shape
+    parts = [_flat(g) for g in groups]
+    shape = np.asarray(groups[0][0]).shape
+    assert len(shape) == 4 and shape[0] == C_ and all(np.asarray(g[0]).shape == shape for g in groups), "groups of C planes of one H x W"
+    x, y, inf = (np.concatenate([p[i] for p in parts]) for i in range(3))
+    return ctx.enc_conv2d_mc(x, y, inf, len(groups), C_, n_out, shape[1], shape[2], w, connect, fh, fw, pad, stride, keys, prf_bytes)
 
 
 def _flat(img):

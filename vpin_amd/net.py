@@ -1,7 +1,8 @@
 """An encrypted inference as a list of layers over the C ABI (vpin_net_*): the server loop of the reference's CNN A .. E service
 (src/cnn_networks/Server.py inferenceCNN) over the encrypted layers, the client's rounds in between (the ready-made client of
 any number of rounds, or a Python callback), and the network's ONE label for the prover: the lists of all layers concatenated
-in layer order, as the reference leaves them in its four global lists.
+in layer order, as the reference leaves them in its four global lists.  Beside the reference's three layer kinds there is CONVMC,
+the convolution of a trained model (vpin_enc_conv2d_mc: a signed filter per channel pair, an optional connection table).
 
 The networks' constants are data, not code: `cnn_config(version)` reads the filter, the pooling windows, the PRF bytes, the
 schedule of the rounds and the names of the weight files from the fixture recorded off runs of the reference
@@ -16,7 +17,7 @@ from . import inference
 from .capi import NetCfg, NetLayer, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
-CONV, POOL, FC = 0, 1, 2
+CONV, POOL, FC, CONVMC = 0, 1, 2, 3
 VERSIONS = ("A", "B", "C", "D", "E")
 _GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
@@ -43,6 +44,22 @@ class Config:
         self._keep.append(buf)
         l = self._add(CONV)
         l.fh, l.fw, l.pad, l.stride, l.filter_le16 = len(filt), len(filt[0]), pad, stride, buf.ctypes.data
+        return self
+
+    def convmc(self, w, connect=None, pad=0, stride=1):
+        """the trained convolution (VPIN_NET_CONVMC): w[o][c][ii][jj] signed ints (int32 range), n_out x C x fh x fw with C the
+        planes that reach the layer; connect: n_out x C, non-zero = connected (None: all)"""
+        w64 = np.asarray(w, dtype=np.int64)
+        w32 = np.ascontiguousarray(w64.astype(np.int32))
+        assert w32.ndim == 4 and np.array_equal(w32, w64)
+        self._keep.append(w32)
+        l = self._add(CONVMC)
+        l.n_out, l.fh, l.fw, l.pad, l.stride, l.w_mc = w32.shape[0], w32.shape[2], w32.shape[3], pad, stride, w32.ctypes.data
+        if connect is not None:
+            t = np.ascontiguousarray(np.asarray(connect) != 0, dtype=np.uint8)
+            assert t.shape == w32.shape[:2]
+            self._keep.append(t)
+            l.connect = t.ctypes.data
         return self
 
     def pool(self, k, stride, scale):
