@@ -705,6 +705,19 @@ void vpin_enc_conv_last_timings(double out[8]);
 int vpin_enc_fc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K,
                 const uint8_t* weights_le4, size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf,
                 const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out);
+/* The fully connected layer of a trained model: vpin_enc_fc over int32 weights (K x N row-major, signed).  The same arguments,
+ * trace, dims and rules; what the signs change, per row:
+ *   1. C[j] = sum_k W[k][j] * X[k] with a negative weight adding |w| times -X[k].  A C[j] that is the identity (VPIN_ESHAPE) is
+ *      now reachable by plain inputs: X[0] = X[1] under the weights w, -w.
+ *   3. s_k = sum_j r_j * W[k][j] = pos_k - neg_k, two unsigned sums over the positive and the negative weights (|INT32_MIN| =
+ *      2^31); VPIN_ESHAPE if either leaves 128 bits.
+ *   4. the multiplication is (|s_k|, S_k), S_k = X[k] for s_k >= 0 and -X[k] = (x, q - y) for s_k < 0: the gadget's weight is a
+ *      u128 bit string, so the sign goes into the point (as in vpin_enc_conv2d_mc).  s_k = 0 records (0, X[k]).
+ *   5. T_k = |s_k| * S_k, and the chain as before.
+ * With every weight non-negative the trace is vpin_enc_fc's byte for byte. */
+int vpin_enc_fc_signed(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K,
+                       const int32_t* weights, size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf,
+                       const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out);
 /* The average pooling: myAvgPool2d (type1 = 1, flag = 1) of src/LeNet/Server.py over P planes of H x W points with a k x k
  * window.  oh = (H - k) / stride + 1, ow likewise, outputs row-major.  Per output, with the window's elements e_0 .. e_{k*k-1}
  * taken row-major: acc = e_0 and, for m >= 1, the addition (acc, e_m), then acc += e_m; out = scale * acc (scale: u128
@@ -738,6 +751,19 @@ int vpin_enc_avgpool2d(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, cons
 int vpin_enc_conv2d_mc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
                        size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
                        const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out);
+/* The trained convolution with a bias per output channel (nn.Conv2d's): vpin_enc_conv2d_mc plus bx, by, binf, groups * n_out
+ * encrypted bias points, group-major then o; an identity bias is allowed and flagged.  C is what vpin_enc_conv2d_mc calls out;
+ *   out[g][o][t] = C[g][o][t] + bias[g][o]
+ * and the check runs over C, not out (as in vpin_enc_fc).  The multiplication list and the left sides are those of
+ * vpin_enc_conv2d_mc on the same inputs and keys, byte for byte.  The addition list per (g, o) is first the oh * ow additions
+ * (C[t], bias[g][o]), t row-major, an identity bias as rz = 1, rx = ry = 0, then that pair's chain additions as before.  out =
+ * identity (bias = -C[t]) and C[t] = bias (a doubling) are cases of the addition, not errors.  Dims: {groups * n_out, oh, ow, M,
+ * M - groups * n_out + groups * n_out * oh * ow}.  VPIN_ESHAPE also when a C[t] is the identity: it is the first operand of an
+ * addition, which has no flag.  VPIN_EINVAL also for a null bias array, a bias coordinate >= q or a bias point off the curve. */
+int vpin_enc_conv2d_mc_bias(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C,
+                            size_t n_out, size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw,
+                            size_t pad, size_t stride, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32,
+                            int prf_bytes, vpin_conv_trace** out);
 /* the bare stage beside vpin_e2_conv2d: the output ciphertext only (groups * n_out * oh * ow points), no check; a cancelled
  * output is the flagged identity */
 int vpin_e2_conv2d_mc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
@@ -915,6 +941,12 @@ void vpin_lenet_last_timings(double out[16]);
  *                  n_out x C filters of fh x fw int32 weights (w_mc) and the optional table connect; 2 n_out keys, (c1, o) first;
  *                  n_out planes go on.  Its fields stand at the END of vpin_net_layer (ABI 3); the other kinds read none of them */
 #define VPIN_NET_CONVMC 3
+/*   (ABI 4) A CONVMC layer reads `bias`: NULL is the layer without one; otherwise n_out int64 values, which the server encrypts as
+ *                  for FC (n_out of the caller's r, drawn before the layer) and hands to vpin_enc_conv2d_mc_bias, the c1 halves for
+ *                  group 0 and the c2 halves for group 1: n_out more bias r and 2 n_out oh ow more additions
+ *   VPIN_NET_FCS   VPIN_NET_FC over signed weights: K, N, w, bias as there, vpin_enc_fc_signed with P = 2; the same counts.
+ *                  VPIN_NET_FC itself still answers VPIN_EINVAL for a negative weight */
+#define VPIN_NET_FCS 4
 typedef struct vpin_net_layer {
   int kind;
   size_t fh, fw, pad;            /* CONV */
@@ -923,8 +955,8 @@ typedef struct vpin_net_layer {
   size_t k;                      /* POOL: the window */
   uint8_t scale_le16[16];        /* POOL: u128, the reference's 2^10 / k^2 */
   size_t K, N;                   /* FC */
-  const int32_t* w;              /* FC: K x N, row-major, non-negative */
-  const int64_t* bias;           /* FC: N values */
+  const int32_t* w;              /* FC: K x N, row-major, non-negative; FCS: signed */
+  const int64_t* bias;           /* FC, FCS: N values; CONVMC: NULL or n_out values */
   int has_round, relu, shift_bits, reencrypt;
   uint64_t max_giant;
   size_t n_out;                  /* CONVMC (with fh, fw, pad, stride): the output channels */

@@ -1,6 +1,8 @@
 """Time per stage of the trained convolution layer (vpin_enc_conv2d_mc + vpin_conv_trace_instances), warm:
 python tools/time_enc_convmc.py groups C n_out H W f pad stride [--runs N] [--prf-bytes B] [--bits K] [--plane-sum-route]
                                 [--no-instances]   (leave the instance build out: 2 * 120 * 16 * 25 multiplications are a 10 GB witness)
+                                [--bias]           (vpin_enc_conv2d_mc_bias under groups * n_out synthetic bias points: the bias
+                                                    addition is part of the conv stage)
 Pixels are vpin_synthetic_points; the weights are signed pseudo-random values of up to K bits (default 16: the reference's
 fixed point), every pair connected, the first weight of every chain non-zero.  One cold run, then N warm ones (default 11): per
 stage the median, the minimum and the maximum in ms -- validate (upload + range / curve checks), conv (+ normalisation, outputs
@@ -31,7 +33,7 @@ skip = False
 for a in sys.argv[1:]:
     if skip:
         skip = False
-    elif a in ("--plane-sum-route", "--no-instances"):
+    elif a in ("--plane-sum-route", "--no-instances", "--bias"):
         pass
     elif a.startswith("--"):
         skip = True
@@ -39,7 +41,8 @@ for a in sys.argv[1:]:
         pos.append(int(a))
 groups, C, n_out, H, W, f, pad, stride = pos
 runs, prf_bytes, bits = opt("--runs", 11), opt("--prf-bytes", 16), opt("--bits", 16)
-no_inst = "--no-instances" in sys.argv
+no_inst, with_bias = "--no-instances" in sys.argv, "--bias" in sys.argv
+bx, by = G.synthetic_points(G.SEED + 8, groups * n_out)
 rng = np.random.default_rng(0x4D43)
 w = rng.integers(-(1 << bits) + 1, 1 << bits, size=(n_out, C, f, f), dtype=np.int64)
 w[:, 0, 0, 0] = np.where(w[:, 0, 0, 0] == 0, 1, w[:, 0, 0, 0])
@@ -58,14 +61,17 @@ def report(samples, names):
 samples = {s: [] for s in STAGES}
 with vpin_amd.Context(0) as ctx:
     for it in range(runs + 1):
-        tr = ctx.enc_conv2d_mc(x, y, None, groups, C, n_out, H, W, w, None, f, f, pad, stride, keys, prf_bytes)
+        if with_bias:
+            tr = ctx.enc_conv2d_mc_bias(x, y, None, groups, C, n_out, H, W, w, None, f, f, pad, stride, bx, by, None, keys, prf_bytes)
+        else:
+            tr = ctx.enc_conv2d_mc(x, y, None, groups, C, n_out, H, W, w, None, f, f, pad, stride, keys, prf_bytes)
         tm = ctx.enc_conv_timings()
         t0 = time.perf_counter()
         gm, ga = (None, None) if no_inst else tr.instances()
         ctx.sync()
         tm["instances"] = time.perf_counter() - t0
         if it == 0:
-            print(f"convmc groups={groups} C={C} n_out={n_out} {H}x{W} f={f} pad={pad} stride={stride} prf_bytes={prf_bytes} |w| < 2^{bits}: "
+            print(f"convmc{' + bias' if with_bias else ''} groups={groups} C={C} n_out={n_out} {H}x{W} f={f} pad={pad} stride={stride} prf_bytes={prf_bytes} |w| < 2^{bits}: "
                   f"outputs {tr.P}x{tr.oh}x{tr.ow}, {tr.n_mult} multiplications, {tr.n_add} additions; cold run {tm['total'] * 1e3:.1f} ms "
                   f"+ instances {tm['instances'] * 1e3:.1f} ms")
         else:

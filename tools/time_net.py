@@ -1,5 +1,8 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
-the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E [--reps R] [--nb LOG2] [--no-proofs]
+the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs]
+lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
+three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
+weights exist here.
 It prints its fixed seeds, checks the scores and every round's values against the plaintext model (tests/net_model.py) and the
 label's counts against the model's, and then the median / minimum / maximum in ms over R warm runs (after one warm-up run) of
 every layer and every round (the library's host clock, vpin_net_last_timings), of the whole inference, and of the whole
@@ -18,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import vpin_amd  # noqa: E402
 from vpin_amd import net as VN  # noqa: E402
 import elgamal_model as EL  # noqa: E402
+import fcs_model as TM  # noqa: E402
 import net_model as NM  # noqa: E402
 
 
@@ -31,7 +35,7 @@ PROOFS = "--no-proofs" not in sys.argv
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
 SEED_C, SEED_P = bytes(range(64)), bytes((11 * i + 5) % 256 for i in range(64))
-KINDS = {VN.CONV: "conv", VN.POOL: "pool", VN.FC: "fc"}
+KINDS = {VN.CONV: "conv", VN.POOL: "pool", VN.FC: "fc", VN.CONVMC: "convmc", VN.FCS: "fcs"}
 
 
 def stats(xs):
@@ -39,17 +43,30 @@ def stats(xs):
 
 
 def main():
-    assert VERSION in VN.VERSIONS, "time_net.py A|B|C|D|E"
+    assert VERSION in VN.VERSIONS + ("lenet5",), "time_net.py A|B|C|D|E|lenet5"
     print("network", VERSION, "seeds:", SEEDS, "sk: fixed", "nb = 2^%d" % NB_LOG, "reps =", REPS)
-    model = NM.cnn_config(VERSION)
     image = NM.reference_image()
-    vs, acts = NM.plaintext(model, image)
+    if VERSION == "lenet5":
+        model = TM.lenet5_model_config()
+        vs, acts = TM.net_plaintext(model, image)
+        giant = max(1, (1 << 31) >> NB_LOG)  # the client's range per round: +-2^31
+        assert all(abs(v) < giant << NB_LOG for r in vs for v in r), "the shifts do not keep a round inside the client's range"
+        cfg = TM.lenet5_device_config([giant] * 7)
+        want = TM.net_counts(model)
+    else:
+        model = NM.cnn_config(VERSION)
+        vs, acts = NM.plaintext(model, image)
+        cfg = VN.cnn_config(VERSION, nb_log=NB_LOG)
+        want = NM.counts(model)
     ctx = vpin_amd.Context(0)
-    cfg = VN.cnn_config(VERSION, nb_log=NB_LOG)
     counts, giants = cfg.counts(), cfg.max_giants()
-    assert counts == dict(NM.counts(model), rounds=len(giants))
+    assert counts == dict(want, rounds=len(giants))
     keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
-    assert all(NM.keys_fit(model, keys)), "a folded weight does not fit 128 bits under these keys"
+    if VERSION == "lenet5":
+        fcs = [l for l in model["layers"] if l["kind"] == "fcs"]
+        assert all(TM.folded_fit_signed(l["w"], l["N"], keys[44 + 2 * j + i], model["prf_bytes"]) for j, l in enumerate(fcs) for i in range(2))
+    else:
+        assert all(NM.keys_fit(model, keys)), "a folded weight does not fit 128 bits under these keys"
     image_rs = EL.splitmix_scalars(SEEDS["image_r"], image.size)
     bias_rs = EL.splitmix_scalars(SEEDS["bias_r"], counts["bias_r"])
     client_rs = EL.splitmix_scalars(SEEDS["client_r"], counts["encryptions"] - image.size)

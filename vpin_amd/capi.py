@@ -199,6 +199,8 @@ def lib():
     L.vpin_e2_conv2d_mc.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
     L.vpin_enc_conv2d_mc.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_fc.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.vpin_enc_fc_signed.argtypes = L.vpin_enc_fc.argtypes
+    L.vpin_enc_conv2d_mc_bias.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_avgpool2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, C.POINTER(vp)]
     L.vpin_conv_trace_free.argtypes = [vp]
     L.vpin_conv_trace_free.restype = None
@@ -1350,6 +1352,21 @@ class Context:
         rc = lib().vpin_enc_conv2d_mc(self.h, p(x), p(y), p(f), groups, C_, n_out, H, W, pw, pt, fh, fw, pad, stride, p(k), prf_bytes, C.byref(h))
         return self._trace(rc, h, "vpin_enc_conv2d_mc")
 
+    def enc_conv2d_mc_bias(self, x, y, inf, groups, C_, n_out, H, W, weights, connect, fh, fw, pad, stride, bx, by, binf, keys, prf_bytes=16):
+        """the trained convolution with a bias (vpin_enc_conv2d_mc_bias): enc_conv2d_mc's arguments and groups * n_out bias points,
+        group-major then o -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        bx, by, bf = self._points(bx, by, binf)
+        assert x.shape[0] == groups * C_ * H * W and bx.shape[0] == groups * n_out
+        w, t, pw, pt = self._mc_args(weights, connect, groups, C_, n_out, fh, fw)
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy()
+        assert k.size == 32 * groups * n_out
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_conv2d_mc_bias(self.h, p(x), p(y), p(f), groups, C_, n_out, H, W, pw, pt, fh, fw, pad, stride, p(bx), p(by), p(bf),
+                                           p(k), prf_bytes, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_conv2d_mc_bias")
+
     def _trace(self, rc, h, where):
         if rc:
             assert not h.value, where + " returned a handle with an error"
@@ -1370,6 +1387,20 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         rc = lib().vpin_enc_fc(self.h, p(x), p(y), p(f), P, K, p(w), N, p(bx), p(by), p(bf), p(k), prf_bytes, C.byref(h))
         return self._trace(rc, h, "vpin_enc_fc")
+
+    def enc_fc_signed(self, x, y, inf, P, K, weights, N, bx, by, binf, keys, prf_bytes=16):
+        """the fully connected layer over signed weights (vpin_enc_fc_signed): enc_fc's arguments, weights[k][j] in the int32 range"""
+        x, y, f = self._points(x, y, inf)
+        bx, by, bf = self._points(bx, by, binf)
+        w64 = np.asarray(weights, dtype=np.int64).reshape(-1)
+        w = np.ascontiguousarray(w64.astype("<i4"))
+        assert x.shape[0] == P * K and bx.shape[0] == P * N and w.size == K * N and np.array_equal(w, w64), "a weight does not fit int32"
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy()
+        assert k.size == 32 * P
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_fc_signed(self.h, p(x), p(y), p(f), P, K, p(w), N, p(bx), p(by), p(bf), p(k), prf_bytes, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_fc_signed")
 
     def enc_avgpool2d(self, x, y, inf, P, H, W, k, stride, scale):
         """the average pooling (vpin_enc_avgpool2d): P planes of H x W points, a k x k window, scale a Python int < 2^128 -> ConvTrace"""

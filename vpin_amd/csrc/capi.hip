@@ -293,7 +293,7 @@ const char* vpin_strerror(int code) {
 
 const char* vpin_last_error(void) { return g_last_error.c_str(); }
 
-int vpin_abi_version(void) { return 3; }  // 3: vpin_net_layer grew n_out, w_mc, connect at its end (VPIN_NET_CONVMC)
+int vpin_abi_version(void) { return 4; }  // 3: vpin_net_layer grew n_out, w_mc, connect at its end (VPIN_NET_CONVMC); 4: VPIN_NET_FCS, CONVMC reads bias
 
 static int ctx_create(int device, int priority, const uint32_t* cu_mask, uint32_t n_words, vpin_ctx** out);
 

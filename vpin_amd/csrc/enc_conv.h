@@ -32,6 +32,7 @@ constexpr uint32_t kE2FlagOffCurve = 2u;  // a non-identity point that does not 
 //   matvec      C[p][j] = sum_k W[k][j] * X[p][k] for P rows of K points and u32 weights (K x N row-major, little-endian),
 //               normalised; C takes conv's place as the resident outputs (P planes of 1 x N, no taps), so rlc gives
 //               sum_j r[p][j] * C[p][j] per row
+//   matvec_signed  matvec over int32 weights (e2_matvec_signed_kernel): a negative weight adds |w| times the negated point
 //   pool_sums   per pooled output (geom: fh = fw = k, pad 0) its taps() - 1 accumulators e_0, e_0 + e_1, .. in the order of
 //               the addition list, normalised, canonical bytes; acc_identity: one byte per output, 1 = one of them is the identity
 // The tail of the fully connected layer's RLC check, also vpin_e2_mul_chain (enc_fc.hip: e2_scalar_mul_kernel,
@@ -44,6 +45,9 @@ constexpr uint32_t kE2FlagOffCurve = 2u;  // a non-identity point that does not 
 //               normalised; the groups * n_out output planes stay resident for rlc_mc and go to the host as canonical bytes.
 //               w: n_out * C * taps() int32, connect: n_out * C bytes (never NULL here), top_bit: per o the top set bit of its
 //               largest |w| over the connected channels, -1 when all are zero
+//   add_bias    after conv_mc, with `bias` holding the groups * n_out loaded bias points: out[plane][t] = C[plane][t] +
+//               bias[plane] (e2_bias_add_kernel, the complete addition), normalised, canonical bytes to the host.  The resident
+//               outputs stay C: the check runs over C, not out
 //   rlc_mc      n_sums sums, one descriptor of four ints each: {plane, tap, pair, 0}.  plane >= 0: sum_t r[pair][t] *
 //               window_t(X[plane])[tap]; plane = -1: sum_t r[pair][t] * out[pair][t]; plane = -2: no terms (the padding of a
 //               chain).  neg[i] != 0 negates sum i (e2_negate_kernel).  All sums are normalised by one launch: canonical bytes and
@@ -58,11 +62,14 @@ struct EncConvDev {
   int rlc(const uint8_t* r_le16, uint8_t* sums_jac);
   int msm(const uint8_t* r_le16, size_t n, uint8_t sum_jac[96]);
   int matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf);
+  int matvec_signed(size_t P, size_t K, size_t N, const int32_t* weights, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf);
+  int matvec_any(size_t P, size_t K, size_t N, const void* weights, bool is_signed, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf);
   int pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity);
   int mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y,
                 uint8_t* acc_inf);
   int conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_out, const int32_t* w, const uint8_t* connect, const int32_t* top_bit,
               uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+  int add_bias(const EncConvDev& bias, size_t groups, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
   int rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, EncConvDev* tail, uint8_t* s_x,
              uint8_t* s_y, uint8_t* s_inf);
 };
@@ -130,7 +137,7 @@ struct Lap {
 
 }  // namespace vpin
 
-// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_conv2d_mc, vpin_enc_fc, vpin_enc_avgpool2d)
+// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias], vpin_enc_fc[_signed], vpin_enc_avgpool2d)
 struct vpin_conv_trace {
   size_t P = 0, oh = 0, ow = 0, n_mult = 0, n_add = 0;
   std::vector<uint8_t> out_x, out_y, out_inf;        // P * oh * ow

@@ -5,6 +5,7 @@
 // the negation S = -B' for a negative weight and the chain T_m = |w_m| * S_m with its prefixes (mul_chain) run on the device
 // (enc_convmc.hip, enc_conv.hip, enc_fc.hip).  Generalises the type-1 path of the reference's myConv2d with rLCL / rLCR
 // (src/LeNet/Server.py), which has one non-negative filter and sums the channels outside the check; enc_conv.cpp restates that one.
+// vpin_enc_conv2d_mc_bias adds one encrypted bias point per output plane on the device (e2_bias_add_kernel) and records the additions.
 #include <omp.h>
 
 #include <algorithm>
@@ -68,37 +69,23 @@ struct TraceGuard {
   ~TraceGuard() { delete t; }
 };
 
-}  // namespace
-
-extern "C" {
-
-int vpin_e2_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out, size_t H,
-                      size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride, uint8_t* out_x,
-                      uint8_t* out_y, uint8_t* out_inf) {
-  if (!c || !px || !py || !pinf || !weights || !out_x || !out_y || !out_inf) return fail(VPIN_EINVAL, "vpin_e2_conv2d_mc: null argument");
-  McPlan p;
-  int rc = make_plan("vpin_e2_conv2d_mc", groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, &p);
-  if (rc) return rc;
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, p.g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags, "vpin_e2_conv2d_mc", "pixel"))) return rc;
-  return d.conv_mc(p.g, groups, C, n_out, weights, p.connect.data(), p.top_bit.data(), out_x, out_y, out_inf);
-}
-
-int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out, size_t H,
-                       size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
-                       const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out) {
+// vpin_enc_conv2d_mc (no bias: bx = by = binf = NULL) and vpin_enc_conv2d_mc_bias.  With a bias the convolution's result is C,
+// the output is C + bias, every pair's additions begin with its oh * ow pairs (C[t], bias), and the check still runs over C
+int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C,
+             size_t n_out, size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
+             const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out) {
+  const std::string name(who);
+  auto failed = [&](int code, const char* why) { return fail(code, (name + ": " + why).c_str()); };
   if (out) *out = nullptr;
-  if (!c || !px || !py || !pinf || !weights || !keys32 || !out) return fail(VPIN_EINVAL, "vpin_enc_conv2d_mc: null argument");
-  if (prf_bytes < 1 || prf_bytes > 16) return fail(VPIN_EINVAL, "vpin_enc_conv2d_mc: prf_bytes must be in 1 .. 16");
+  if (!c || !px || !py || !pinf || !weights || !keys32 || !out || (with_bias && (!bx || !by || !binf))) return failed(VPIN_EINVAL, "null argument");
+  if (prf_bytes < 1 || prf_bytes > 16) return failed(VPIN_EINVAL, "prf_bytes must be in 1 .. 16");
   McPlan p;
-  int rc = make_plan("vpin_enc_conv2d_mc", groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, &p);
+  int rc = make_plan(who, groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, &p);
   if (rc) return rc;
   const ConvGeom& g = p.g;
   const size_t taps = g.taps(), per_plane = g.oh * g.ow, n_pairs = groups * n_out, n_o = n_pairs * per_plane, K = p.k_max;
   const size_t n_chain = n_pairs * K, n_sums = n_chain + n_pairs;  // the chains, padded to K terms each, then the left sides
-  if (n_sums * ((per_plane + 255) / 256) >= ((size_t)1 << 31)) return fail(VPIN_EINVAL, "vpin_enc_conv2d_mc: a dimension is out of range");
+  if (n_sums * ((per_plane + 255) / 256) >= ((size_t)1 << 31)) return failed(VPIN_EINVAL, "a dimension is out of range");
   double* tm = last_timings();
   for (int i = 0; i < 8; i++) tm[i] = 0.0;
   Lap total, lap;
@@ -107,19 +94,30 @@ int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   TraceGuard guard{t};
   t->P = n_pairs; t->oh = g.oh; t->ow = g.ow;
   t->n_mult = groups * taps * p.pairs;
-  t->n_add = t->n_mult - n_pairs;
+  t->n_add = t->n_mult - n_pairs + (with_bias ? n_o : 0);
 
   // validate: upload, range and curve checks on the device
-  EncConvDev d(c), tail(c);
+  EncConvDev d(c), tail(c), b(c);
   uint32_t flags = 0;
   if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags, "vpin_enc_conv2d_mc", "pixel"))) return rc;
+  if ((rc = check_flags(flags, who, "pixel"))) return rc;
+  if (with_bias) {
+    if ((rc = b.load(bx, by, binf, n_pairs, &flags))) return rc;
+    if ((rc = check_flags(flags, who, "bias point"))) return rc;
+  }
   tm[0] = lap();
 
   // the convolution
   t->out_x.resize(n_o * 32); t->out_y.resize(n_o * 32); t->out_inf.resize(n_o);
   if ((rc = d.conv_mc(g, groups, C, n_out, weights, p.connect.data(), p.top_bit.data(), t->out_x.data(), t->out_y.data(), t->out_inf.data())))
     return rc;
+  std::vector<uint8_t> cx, cy;  // C, the first operands of the bias additions; the trace's output becomes C + bias
+  if (with_bias) {
+    for (size_t i = 0; i < n_o; i++)
+      if (t->out_inf[i]) return failed(VPIN_ESHAPE, "an addition accumulator C[t] is the identity (the witness format has no flag for it)");
+    cx = t->out_x; cy = t->out_y;
+    if ((rc = d.add_bias(b, groups, n_out, t->out_x.data(), t->out_y.data(), t->out_inf.data()))) return rc;
+  }
   tm[1] = lap();
 
   // the PRF scalars: one key per (g, o), the index restarts at 0 for every pair
@@ -157,7 +155,7 @@ int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   for (size_t q = 0; q < n_pairs; q++)
     for (size_t m = 0; m < p.chan[q % n_out].size() * taps; m++)
       if (sinf[q * K + m])
-        return fail(VPIN_ESHAPE, "vpin_enc_conv2d_mc: a multiplication operand B'[c][k] is the identity (the witness format has no flag for it)");
+        return failed(VPIN_ESHAPE, "a multiplication operand B'[c][k] is the identity (the witness format has no flag for it)");
   std::vector<uint8_t> tx(n_chain * 32), ty(n_chain * 32), tinf(n_chain), ax(n_chain * 32), ay(n_chain * 32), ainf(n_chain);
   if ((rc = tail.mul_chain(s.data(), n_pairs, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
   t->resize_lists();
@@ -166,12 +164,18 @@ int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   size_t mi = 0, ai = 0;
   for (size_t q = 0; q < n_pairs; q++) {
     const size_t len = p.chan[q % n_out].size() * taps;
+    for (size_t tt = 0; with_bias && tt < per_plane; tt++, ai++) {
+      const size_t i = q * per_plane + tt;
+      memcpy(&t->a_px[32 * ai], &cx[32 * i], 32); memcpy(&t->a_py[32 * ai], &cy[32 * i], 32);
+      if (binf[q]) { t->a_rz[ai] = 1; continue; }  // rx, ry stay zero
+      memcpy(&t->a_rx[32 * ai], bx + 32 * q, 32); memcpy(&t->a_ry[32 * ai], by + 32 * q, 32);
+    }
     for (size_t m = 0; m < len; m++, mi++) {
       const size_t i = q * K + m;
       memcpy(&t->m_w[16 * mi], &s[16 * i], 16);
       memcpy(&t->m_px[32 * mi], &sx[32 * i], 32); memcpy(&t->m_py[32 * mi], &sy[32 * i], 32);
       if (m == 0) continue;
-      if (ainf[i - 1]) return fail(VPIN_ESHAPE, "vpin_enc_conv2d_mc: an addition accumulator is the identity (the witness format has no flag for it)");
+      if (ainf[i - 1]) return failed(VPIN_ESHAPE, "an addition accumulator is the identity (the witness format has no flag for it)");
       memcpy(&t->a_px[32 * ai], &ax[32 * (i - 1)], 32); memcpy(&t->a_py[32 * ai], &ay[32 * (i - 1)], 32);
       memcpy(&t->a_rx[32 * ai], &tx[32 * i], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * i], 32);
       t->a_rz[ai] = tinf[i];
@@ -185,10 +189,43 @@ int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   }
   tm[4] = lap();
   tm[5] = total();
-  if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_conv2d_mc: the two sides of the random linear combination differ");
+  if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");
   guard.t = nullptr;
   *out = t;
   return VPIN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpin_e2_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out, size_t H,
+                      size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride, uint8_t* out_x,
+                      uint8_t* out_y, uint8_t* out_inf) {
+  if (!c || !px || !py || !pinf || !weights || !out_x || !out_y || !out_inf) return fail(VPIN_EINVAL, "vpin_e2_conv2d_mc: null argument");
+  McPlan p;
+  int rc = make_plan("vpin_e2_conv2d_mc", groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, &p);
+  if (rc) return rc;
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  if ((rc = d.load(px, py, pinf, p.g.pixels(), &flags))) return rc;
+  if ((rc = check_flags(flags, "vpin_e2_conv2d_mc", "pixel"))) return rc;
+  return d.conv_mc(p.g, groups, C, n_out, weights, p.connect.data(), p.top_bit.data(), out_x, out_y, out_inf);
+}
+
+int vpin_enc_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out, size_t H,
+                       size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
+                       const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out) {
+  return mc_layer("vpin_enc_conv2d_mc", false, c, px, py, pinf, groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, nullptr, nullptr,
+                  nullptr, keys32, prf_bytes, out);
+}
+
+int vpin_enc_conv2d_mc_bias(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
+                            size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw, size_t pad, size_t stride,
+                            const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
+                            vpin_conv_trace** out) {
+  return mc_layer("vpin_enc_conv2d_mc_bias", true, c, px, py, pinf, groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, bx, by, binf,
+                  keys32, prf_bytes, out);
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 //   e2_rlc_mc_kernel   e2_rlc_kernel with a descriptor per sum: the term's plane (or the outputs), its tap and the pair (g, o)
 //                      whose r vector weighs it; one lane per (sum, term), S lanes a sum: a sum of 256 terms or more takes whole
 //                      workgroups (e2_reduce_kernel adds their partials), shorter sums share one
+//   e2_bias_add_kernel out[g][o][t] = C[g][o][t] + bias[g][o] (vpin_enc_conv2d_mc_bias): one lane per output over the resident,
+//                      normalised C, one mixed addition each, complete by case; one e2_to_affine launch follows
 //   e2_negate_kernel   S = -B' where the weight is negative: Y -> q - Y on the Jacobian sums, before the one normalisation
 // Exactness: every addition is complete by case (e2_dev.h): two channels that hold the same pixel under the same weight double
 // in the tree, a pixel and its negative cancel to the flagged identity.  The accumulators are named registers: no per-lane arrays.
@@ -24,6 +26,7 @@ namespace vpin {
 namespace {
 
 constexpr int kMcMaxSlots = 16;
+constexpr int kBiasBlock = 64;  // one wave: a lane is one mixed addition
 
 // grid: x = blocks of px output pixels, y = output channel, z = group; block = slots * px <= kE2Block lanes
 __global__ __launch_bounds__(kE2Block) void e2_convmc_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
@@ -111,7 +114,41 @@ __global__ __launch_bounds__(kE2Block) void e2_negate_kernel(e2_jac* __restrict_
   fq_store(&p[i].Y, fq_neg(fq_load(&p[i].Y)));  // the identity (Z = 0) stays the identity
 }
 
+// grid: x = blocks of kBiasBlock output pixels, y = output channel, z = group: the plane's bias is uniform per workgroup.
+// out = C + bias with the complete addition: C[t] = bias doubles, bias = -C[t] gives the identity, a flagged operand adds nothing
+__global__ __launch_bounds__(kBiasBlock) void e2_bias_add_kernel(const fq* __restrict__ CX, const fq* __restrict__ CY,
+                                                               const uint8_t* __restrict__ cinf, const fq* __restrict__ BX,
+                                                               const fq* __restrict__ BY, const uint8_t* __restrict__ binf, size_t n_pix,
+                                                               fq a, e2_jac* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * kBiasBlock + threadIdx.x, plane = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
+  if (t >= n_pix) return;
+  const size_t i = plane * n_pix + t;
+  e2_jac acc = e2_identity();
+  if (!binf[plane]) { acc.X = fq_load(BX + plane); acc.Y = fq_load(BY + plane); acc.Z = fq_one(); }
+  if (!cinf[i]) acc = e2_add_mixed(acc, fq_load(CX + i), fq_load(CY + i), a);
+  e2_store(out + i, acc);
+}
+
 }  // namespace
+
+int EncConvDev::add_bias(const EncConvDev& bias, size_t groups, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {
+  (void)hipSetDevice(c->device);
+  const size_t per_plane = g.oh * g.ow, n = groups * n_out * per_plane;
+  DevBuf jac(c), mx(c), my(c), cx(c), cy(c), fi(c);
+  if (jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || fi.alloc(n))
+    return VPIN_ENOMEM;
+  hipLaunchKernelGGL(e2_bias_add_kernel, dim3(blocks_of(per_plane, kBiasBlock), (unsigned)n_out, (unsigned)groups), dim3(kBiasBlock), 0, c->stream,
+                     (const fq*)ox.p, (const fq*)oy.p, (const uint8_t*)oinf.p, (const fq*)bias.px.p, (const fq*)bias.py.p,
+                     (const uint8_t*)bias.pinf.p, per_plane, e2_curve_a(), (e2_jac*)jac.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fi.p);
+  if (rc) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, fi.p, n, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
 
 int EncConvDev::conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_out, const int32_t* w, const uint8_t* connect,
                         const int32_t* top_bit, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {

@@ -4,11 +4,13 @@
 // point-mult / point-add gadgets prove them.  The matrix-vector product, the left sum, the K multiplications s_k * X[k] with
 // the chain of their sums (mul_chain, also exposed as vpin_e2_mul_chain), the pooling's accumulators and its scaled outputs run
 // on the device (enc_fc.hip, enc_conv.hip).  Restates FCLayer (flag 1) with the
-// type-1 branch of rLCL / rLCR, and myAvgPool2d (type1 = 1, flag = 1), of the reference's src/LeNet/Server.py.
+// type-1 branch of rLCL / rLCR, and myAvgPool2d (type1 = 1, flag = 1), of the reference's src/LeNet/Server.py.  vpin_enc_fc_signed is
+// the same layer over int32 weights: s_k is a signed integer, and a negative one multiplies the negated point.
 #include <omp.h>
 
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/vpin_hip.h"
@@ -36,32 +38,18 @@ struct TraceGuard {
   ~TraceGuard() { delete t; }
 };
 
-}  // namespace
-
-extern "C" {
-
-int vpin_e2_mul_chain(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P,
-                      size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_inf) {
-  if (!c || !scalars_le16 || !px || !py || !pinf || !t_x || !t_y || !t_inf || !acc_x || !acc_y || !acc_inf)
-    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: null argument");
-  if (!P || !K || P >= ((size_t)1 << 31) || K >= ((size_t)1 << 31) || P * K >= ((size_t)1 << 31))
-    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: P and K must be at least 1 and P * K at most 2^31 - 1");
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, P * K, &flags);
-  if (rc) return rc;
-  if ((rc = check_flags(flags, "vpin_e2_mul_chain", "point"))) return rc;
-  return d.mul_chain(scalars_le16, P, K, t_x, t_y, t_inf, acc_x, acc_y, acc_inf);
-}
-
-int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const uint8_t* weights_le4,
-                size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
-                vpin_conv_trace** out) {
+// vpin_enc_fc (weights: u32) and vpin_enc_fc_signed (is_signed, weights: int32) are one layer: without a negative weight every
+// neg_k below is zero, no point is negated, and the two kernels of the product compute the same points
+int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const void* weights,
+             bool is_signed, size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
+             vpin_conv_trace** out) {
+  const std::string name(who);
+  auto failed = [&](int code, const char* why) { return fail(code, (name + ": " + why).c_str()); };
   if (out) *out = nullptr;
-  if (!c || !px || !py || !pinf || !weights_le4 || !bx || !by || !binf || !keys32 || !out) return fail(VPIN_EINVAL, "vpin_enc_fc: null argument");
-  if (prf_bytes < 1 || prf_bytes > 16) return fail(VPIN_EINVAL, "vpin_enc_fc: prf_bytes must be in 1 .. 16");
-  if (!P || !K || !N) return fail(VPIN_EINVAL, "vpin_enc_fc: a dimension is zero");
-  if (P > 65535 || N > 65535 || K > kMaxDim) return fail(VPIN_EINVAL, "vpin_enc_fc: a dimension is out of range");
+  if (!c || !px || !py || !pinf || !weights || !bx || !by || !binf || !keys32 || !out) return failed(VPIN_EINVAL, "null argument");
+  if (prf_bytes < 1 || prf_bytes > 16) return failed(VPIN_EINVAL, "prf_bytes must be in 1 .. 16");
+  if (!P || !K || !N) return failed(VPIN_EINVAL, "a dimension is zero");
+  if (P > 65535 || N > 65535 || K > kMaxDim) return failed(VPIN_EINVAL, "a dimension is out of range");
   double* tm = last_timings();
   for (int i = 0; i < 8; i++) tm[i] = 0.0;
   Lap total, lap;
@@ -72,13 +60,13 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
   t->P = P; t->oh = 1; t->ow = N; t->n_mult = n_in; t->n_add = P * adds_per_row;
 
   // validate: upload, range and curve checks on the device, for the inputs and the bias
-  EncConvDev d(c), b(c);
+  EncConvDev d(c), b(c), flipped(c);
   uint32_t flags = 0;
   int rc = d.load(px, py, pinf, n_in, &flags);
   if (rc) return rc;
-  if ((rc = check_flags(flags, "vpin_enc_fc", "input point"))) return rc;
+  if ((rc = check_flags(flags, who, "input point"))) return rc;
   if ((rc = b.load(bx, by, binf, n_out, &flags))) return rc;
-  if ((rc = check_flags(flags, "vpin_enc_fc", "bias point"))) return rc;
+  if ((rc = check_flags(flags, who, "bias point"))) return rc;
   tm[0] = lap();
 
   // C = X * W on the device, out = C + bias here; the first N additions of every row
@@ -86,9 +74,11 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
   t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
   t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
   std::vector<uint8_t> cx(n_out * 32), cy(n_out * 32), cinf(n_out);
-  if ((rc = d.matvec(P, K, N, weights_le4, cx.data(), cy.data(), cinf.data()))) return rc;
+  rc = is_signed ? d.matvec_signed(P, K, N, (const int32_t*)weights, cx.data(), cy.data(), cinf.data())
+                 : d.matvec(P, K, N, (const uint8_t*)weights, cx.data(), cy.data(), cinf.data());
+  if (rc) return rc;
   for (size_t i = 0; i < n_out; i++)
-    if (cinf[i]) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator C[j] is the identity (the witness format has no flag for it)");
+    if (cinf[i]) return failed(VPIN_ESHAPE, "an addition accumulator C[j] is the identity (the witness format has no flag for it)");
 #pragma omp parallel for schedule(static) num_threads(team_size())
   for (long li = 0; li < (long)n_out; li++) {
     const size_t i = (size_t)li, ai = (i / N) * adds_per_row + i % N;
@@ -113,30 +103,49 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
   if ((rc = d.rlc(r.data(), sums.data()))) return rc;
   tm[3] = lap();
 
-  // the tail: the folded weights here, T_k = s_k * X[k] and the prefixes of every row's chain on the device, then the equation
+  // the tail: the folded weights here, T_k = |s_k| * S_k and the prefixes of every row's chain on the device, then the equation.
+  // s_k = pos_k - neg_k over the positive and the negative weights; the gadget's weight is a u128, so the sign goes into the
+  // point: S_k = X[k] for s_k >= 0 and -X[k] = (x, q - y) for s_k < 0
+  std::vector<size_t> minus_s;  // the m = p * K + k with s_k < 0
   for (size_t p = 0; p < P; p++)
     for (size_t k = 0; k < K; k++) {
-      u128 s = 0;
+      u128 pos = 0, neg = 0;
       for (size_t j = 0; j < N; j++) {
         u128 rj;
         uint32_t w;
         memcpy(&rj, &r[16 * (p * N + j)], 16);
-        memcpy(&w, weights_le4 + 4 * (k * N + j), 4);
-        if (!mul_add_u128(s, rj, w)) return fail(VPIN_ESHAPE, "vpin_enc_fc: a folded weight sum_j r_j * W[k][j] does not fit 128 bits");
+        memcpy(&w, (const uint8_t*)weights + 4 * (k * N + j), 4);
+        const bool minus = is_signed && (w >> 31);  // |INT32_MIN| = 2^31 as 0 - w in unsigned arithmetic
+        if (!mul_add_u128(minus ? neg : pos, rj, minus ? 0u - w : w))
+          return failed(VPIN_ESHAPE, "a folded weight sum_j r_j * W[k][j] does not fit 128 bits");
       }
-      memcpy(&t->m_w[16 * (p * K + k)], &s, 16);
+      const size_t m = p * K + k;
+      const u128 s = pos >= neg ? pos - neg : neg - pos;
+      memcpy(&t->m_w[16 * m], &s, 16);
+      if (pos < neg) minus_s.push_back(m);
     }
   for (size_t i = 0; i < n_in; i++)
-    if (pinf[i]) return fail(VPIN_ESHAPE, "vpin_enc_fc: a multiplication operand X[k] is the identity (the witness format has no flag for it)");
+    if (pinf[i]) return failed(VPIN_ESHAPE, "a multiplication operand X[k] is the identity (the witness format has no flag for it)");
   memcpy(t->m_px.data(), px, n_in * 32);
   memcpy(t->m_py.data(), py, n_in * 32);
+  for (const size_t m : minus_s) {
+    Aff x = aff_from_bytes(px + 32 * m, py + 32 * m, 0);
+    x.y = x.y.neg();
+    put_point(x, &t->m_px[32 * m], &t->m_py[32 * m]);
+  }
+  EncConvDev* tail = &d;
+  if (!minus_s.empty()) {  // the chain runs over S: the recorded points, validated again as they are loaded
+    if ((rc = flipped.load(t->m_px.data(), t->m_py.data(), pinf, n_in, &flags))) return rc;
+    if ((rc = check_flags(flags, who, "input point"))) return rc;
+    tail = &flipped;
+  }
   std::vector<uint8_t> tx(n_in * 32), ty(n_in * 32), tinf(n_in), ax(n_in * 32), ay(n_in * 32), ainf(n_in);
-  if ((rc = d.mul_chain(t->m_w.data(), P, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
+  if ((rc = tail->mul_chain(t->m_w.data(), P, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
   bool equal = true;
   for (size_t p = 0; p < P; p++) {
     for (size_t k = 1; k < K; k++) {
       const size_t m = p * K + k;
-      if (ainf[m - 1]) return fail(VPIN_ESHAPE, "vpin_enc_fc: an addition accumulator is the identity (the witness format has no flag for it)");
+      if (ainf[m - 1]) return failed(VPIN_ESHAPE, "an addition accumulator is the identity (the witness format has no flag for it)");
       const size_t ai = p * adds_per_row + N + (k - 1);
       memcpy(&t->a_px[32 * ai], &ax[32 * (m - 1)], 32); memcpy(&t->a_py[32 * ai], &ay[32 * (m - 1)], 32);
       memcpy(&t->a_rx[32 * ai], &tx[32 * m], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * m], 32);
@@ -151,10 +160,40 @@ int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t
   }
   tm[4] = lap();
   tm[5] = total();
-  if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_fc: the two sides of the random linear combination differ");
+  if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");
   guard.t = nullptr;
   *out = t;
   return VPIN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpin_e2_mul_chain(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P,
+                      size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_inf) {
+  if (!c || !scalars_le16 || !px || !py || !pinf || !t_x || !t_y || !t_inf || !acc_x || !acc_y || !acc_inf)
+    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: null argument");
+  if (!P || !K || P >= ((size_t)1 << 31) || K >= ((size_t)1 << 31) || P * K >= ((size_t)1 << 31))
+    return fail(VPIN_EINVAL, "vpin_e2_mul_chain: P and K must be at least 1 and P * K at most 2^31 - 1");
+  EncConvDev d(c);
+  uint32_t flags = 0;
+  int rc = d.load(px, py, pinf, P * K, &flags);
+  if (rc) return rc;
+  if ((rc = check_flags(flags, "vpin_e2_mul_chain", "point"))) return rc;
+  return d.mul_chain(scalars_le16, P, K, t_x, t_y, t_inf, acc_x, acc_y, acc_inf);
+}
+
+int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const uint8_t* weights_le4,
+                size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
+                vpin_conv_trace** out) {
+  return fc_layer("vpin_enc_fc", c, px, py, pinf, P, K, weights_le4, false, N, bx, by, binf, keys32, prf_bytes, out);
+}
+
+int vpin_enc_fc_signed(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const int32_t* weights,
+                       size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
+                       vpin_conv_trace** out) {
+  return fc_layer("vpin_enc_fc_signed", c, px, py, pinf, P, K, weights, true, N, bx, by, binf, keys32, prf_bytes, out);
 }
 
 int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W, size_t k,

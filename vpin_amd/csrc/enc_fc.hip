@@ -4,6 +4,8 @@
 //   e2_matvec_kernel      C[p][j] = sum_k W[k][j] * X[p][k]: one lane per (k, j) term on grid (blocks of k, N, P), double-and-add
 //                         over the lane's own 32-bit weight (mixed addition), then the workgroup's LDS tree with the complete
 //                         addition; e2_reduce_kernel sums over the blocks of k
+//   e2_matvec_signed_kernel  its sibling over int32 weights (vpin_enc_fc_signed): the lane multiplies by |w| and takes the negated
+//                         point (x, q - y) for w < 0; the same tree, so X[k] under w and -w cancels to the flagged identity
 //   e2_scalar_mul_kernel  T_i = s_i * X_i, one lane per point, s_i a u128: the multiplications of the layer's RLC check
 //   e2_pool_sums_kernel   one lane per pooled output: the k*k - 1 accumulators e_0, e_0 + e_1, ... of its window (the first
 //                         operands of the pooling's additions) and a flag when one of them is the identity
@@ -29,6 +31,23 @@ __global__ __launch_bounds__(kE2Block) void e2_matvec_kernel(const fq* __restric
   e2_jac acc = e2_identity();
   if (k < K && !inf[p * K + k])  // a zero weight gives the identity inside e2_mul_affine
     acc = e2_mul_affine(fq_load(X + p * K + k), fq_load(Y + p * K + k), 0u, 0u, 0u, W[k * N + j], 32, a);
+  e2_block_tree(sh, acc, a);
+  if (threadIdx.x == 0) e2_store(parts + ((p * N + j) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
+}
+
+// the same grid; |INT32_MIN| = 2^31 is taken in unsigned arithmetic
+__global__ __launch_bounds__(kE2Block) void e2_matvec_signed_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
+                                                                    const uint8_t* __restrict__ inf, const int32_t* __restrict__ W,
+                                                                    size_t K, size_t N, fq a, e2_jac* __restrict__ parts) {
+  __shared__ e2_jac sh[kE2Block];
+  const size_t k = (size_t)blockIdx.x * kE2Block + threadIdx.x, j = blockIdx.y, p = blockIdx.z;
+  e2_jac acc = e2_identity();
+  if (k < K && !inf[p * K + k]) {
+    const int32_t w = W[k * N + j];
+    const uint32_t m = w < 0 ? 0u - (uint32_t)w : (uint32_t)w;
+    const fq y = fq_load(Y + p * K + k);
+    acc = e2_mul_affine(fq_load(X + p * K + k), w < 0 ? fq_neg(y) : y, 0u, 0u, 0u, m, 32, a);
+  }
   e2_block_tree(sh, acc, a);
   if (threadIdx.x == 0) e2_store(parts + ((p * N + j) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
 }
@@ -108,6 +127,15 @@ __global__ __launch_bounds__(kE2Block) void e2_chain_scan_kernel(const e2_jac* _
 // C = X * W per row over the loaded points (P x K), normalised: canonical bytes to the host, Montgomery coordinates resident
 // as this object's outputs with the geometry "P planes of 1 x N and no taps", so that rlc() returns sum_j r[p][j] * C[p][j]
 int EncConvDev::matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
+  return matvec_any(P, K, N, weights_le4, false, c_x, c_y, c_inf);
+}
+
+int EncConvDev::matvec_signed(size_t P, size_t K, size_t N, const int32_t* weights, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
+  return matvec_any(P, K, N, weights, true, c_x, c_y, c_inf);
+}
+
+// weights: K * N words of four bytes, u32 or (is_signed) int32
+int EncConvDev::matvec_any(size_t P, size_t K, size_t N, const void* weights, bool is_signed, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
   (void)hipSetDevice(c->device);
   g = ConvGeom();
   g.P = P; g.oh = 1; g.ow = N;
@@ -120,9 +148,14 @@ int EncConvDev::matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4,
   VPIN_EC_ALLOC(oy, n_out * 32);
   VPIN_EC_ALLOC(oinf, n_out);
   const fq a = e2_curve_a();
-  VPIN_HIP_TRY(hipMemcpyAsync(w.p, weights_le4, K * N * 4, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_matvec_kernel, dim3((unsigned)nblk, (unsigned)N, (unsigned)P), dim3(kE2Block), 0, c->stream, (const fq*)px.p,
-                     (const fq*)py.p, (const uint8_t*)pinf.p, (const uint32_t*)w.p, K, N, a, (e2_jac*)parts.p);
+  VPIN_HIP_TRY(hipMemcpyAsync(w.p, weights, K * N * 4, hipMemcpyHostToDevice, c->stream));
+  const dim3 grid((unsigned)nblk, (unsigned)N, (unsigned)P);
+  if (is_signed)
+    hipLaunchKernelGGL(e2_matvec_signed_kernel, grid, dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
+                       (const uint8_t*)pinf.p, (const int32_t*)w.p, K, N, a, (e2_jac*)parts.p);
+  else
+    hipLaunchKernelGGL(e2_matvec_kernel, grid, dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
+                       (const uint8_t*)pinf.p, (const uint32_t*)w.p, K, N, a, (e2_jac*)parts.p);
   VPIN_HIP_TRY(hipGetLastError());
   int rc = e2_reduce(c, (const e2_jac*)parts.p, n_out, nblk, (e2_jac*)jac.p);
   if (rc) return rc;

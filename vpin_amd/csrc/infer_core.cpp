@@ -1,5 +1,5 @@
-// infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc,
-// vpin_enc_avgpool2d, vpin_enc_fc, vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
+// infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias],
+// vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
 // (lenet.cpp) and vpin_net_infer (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer validates
 // what it is given, the client's answers included.
 #include "infer_core.h"
@@ -51,19 +51,47 @@ void split(const vpin_conv_trace& t, Step::Order order, Pts* c1, Pts* c2) {
         ->append(&t.out_x[32 * p * per], &t.out_y[32 * p * per], &t.out_inf[p * per], per);
 }
 
-// the bias under the client's key, N values encrypted with the caller's r before the layer (encryptBias), then the layer on the
-// c1 row and the c2 row
-int fc(const Call& a, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
-  Pts b, b2;
-  b.resize(s.N); b2.resize(s.N);
-  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, s.bias, r_le32, s.N, b.x.data(), b.y.data(), b.inf.data(), b2.x.data(), b2.y.data(),
+// bias values the step encrypts, one r each
+size_t bias_values(const Step& s) {
+  return s.kind == Step::kFc || s.kind == Step::kFcs ? s.N : s.kind == Step::kConvMc && s.bias ? s.n_out : 0;
+}
+
+// n bias values under the client's key, encrypted with the caller's r before the layer (encryptBias): the n c1 halves, then the
+// n c2 halves
+int encrypt_bias(const Call& a, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* b) {
+  Pts b2;
+  b->resize(n); b2.resize(n);
+  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, bias, r_le32, n, b->x.data(), b->y.data(), b->inf.data(), b2.x.data(), b2.y.data(),
                                  b2.inf.data());
+  if (!rc) b->append(b2, 0, n);
+  return rc;
+}
+
+// the encrypted bias, then the layer on the c1 row and the c2 row
+int fc(const Call& a, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
+  Pts b;
+  const int rc = encrypt_bias(a, s.bias, r_le32, s.N, &b);
   if (rc) return rc;
-  b.append(b2, 0, s.N);
+  if (s.kind == Step::kFcs)
+    return vpin_enc_fc_signed(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, s.K, s.w, s.N, b.x.data(), b.y.data(), b.inf.data(), key,
+                              a.prf_bytes, out);
   std::vector<uint32_t> wu(s.K * s.N);
   for (size_t i = 0; i < s.K * s.N; i++) wu[i] = (uint32_t)s.w[i];
   return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(), b.inf.data(),
                      key, a.prf_bytes, out);
+}
+
+// the trained convolution; with a bias, n_out values encrypted as for fc: the c1 halves go to group 0, the c2 halves to group 1
+int conv_mc(const Call& a, const Step& s, const Pts& in, size_t C, size_t H, size_t W, const uint8_t* key, const uint8_t* r_le32,
+            vpin_conv_trace** out) {
+  if (!s.bias)
+    return vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad, s.stride,
+                              key, a.prf_bytes, out);
+  Pts b;
+  const int rc = encrypt_bias(a, s.bias, r_le32, s.n_out, &b);
+  if (rc) return rc;
+  return vpin_enc_conv2d_mc_bias(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
+                                 s.stride, b.x.data(), b.y.data(), b.inf.data(), key, a.prf_bytes, out);
 }
 
 // one interaction with the client: the step's output goes out, the activated and re-encrypted values come back into c1, c2
@@ -98,11 +126,11 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   auto named = [&](int rc, const std::string& where) { return fail(rc, (who + where + ": " + vpin_last_error()).c_str()); };
   size_t keys = 0, bias_r = 0;
   bool any_round = false;
-  for (const Step& s : steps) { keys += s.keys; bias_r += s.kind == Step::kFc ? s.N : 0; any_round = any_round || s.has_round; }
+  for (const Step& s : steps) { keys += s.keys; bias_r += bias_values(s); any_round = any_round || s.has_round; }
   if (a.n_keys != keys)
     return fail(VPIN_EINVAL, (who + "the number of PRF keys is not one per convolution plane and fully connected row").c_str());
   if (a.n_bias_r != bias_r)
-    return fail(VPIN_EINVAL, (who + "the number of bias randomness values is not one per fully connected output").c_str());
+    return fail(VPIN_EINVAL, (who + "the number of bias randomness values is not one per fully connected output and biased output channel").c_str());
   if ((keys && !a.keys32) || (bias_r && (!a.bias_r_le32 || !a.baseG || !a.baseH)) || (any_round && !a.round_fn))
     return fail(VPIN_EINVAL, (who + "null argument").c_str());
   out->step_ms.assign(steps.size(), 0.0);
@@ -128,7 +156,7 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
       }
       C = s.sum_out;
     }
-    if (s.kind == Step::kFc) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
+    if (s.kind == Step::kFc || s.kind == Step::kFcs) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
     const Pts in = gather(c1, c2, C, s.repeat, s.order);
     C *= s.repeat;
     vpin_conv_trace* tr = nullptr;
@@ -136,14 +164,13 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
       rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, key,
                            a.prf_bytes, &tr);
     } else if (s.kind == Step::kConvMc) {
-      rc = vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad, s.stride,
-                              key, a.prf_bytes, &tr);
+      rc = conv_mc(a, s, in, C, H, W, key, br, &tr);
     } else if (s.kind == Step::kPool) {
       rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
     } else {
       rc = fc(a, s, in, key, br, &tr);
-      br += 32 * s.N;
     }
+    br += 32 * bias_values(s);
     key += 32 * s.keys;
     out->step_ms[i] = 1e3 * lap();
     if (rc) return named(rc, s.name);

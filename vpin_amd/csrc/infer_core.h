@@ -11,18 +11,18 @@
 namespace vpin::infer {
 
 struct Step {
-  enum Kind { kConv, kPool, kFc, kConvMc } kind = kConv;
+  enum Kind { kConv, kPool, kFc, kConvMc, kFcs } kind = kConv;
   // how c1 and c2 make up the layer call's P = 2 C planes, and how its output splits back: all c1 planes and then all c2 planes
-  // (first half, second half), or (0, c1), (0, c2), (1, c1), .. (even planes, odd planes).  For kFc, P = 2, they coincide
+  // (first half, second half), or (0, c1), (0, c2), (1, c1), .. (even planes, odd planes).  For kFc and kFcs, P = 2, they coincide
   enum Order { kBlocked, kInterleaved } order = kBlocked;
   const uint8_t* filter_le16 = nullptr;  // kConv
   size_t fh = 0, fw = 0, pad = 0;
   size_t stride = 1;                     // kConv and kPool
   size_t k = 0;                          // kPool
   const uint8_t* scale_le16 = nullptr;
-  size_t K = 0, N = 0;                   // kFc
+  size_t K = 0, N = 0;                   // kFc, and kFcs: vpin_enc_fc_signed, w signed
   const int32_t* w = nullptr;
-  const int64_t* bias = nullptr;
+  const int64_t* bias = nullptr;         // kFc, kFcs: N values; kConvMc: NULL or n_out values (vpin_enc_conv2d_mc_bias)
   size_t n_out = 0;                      // kConvMc (with fh, fw, pad, stride): vpin_enc_conv2d_mc with groups = 2, kBlocked
   const int32_t* w_mc = nullptr;
   const uint8_t* connect = nullptr;

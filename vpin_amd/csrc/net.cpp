@@ -16,7 +16,7 @@ using vpin::infer::Step;
 namespace {
 
 const char* kind_name(int kind) {
-  return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : kind == VPIN_NET_CONVMC ? "convmc" : "fc";
+  return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : kind == VPIN_NET_CONVMC ? "convmc" : kind == VPIN_NET_FCS ? "fcs" : "fc";
 }
 
 // per layer what it consumes and leaves; the walk that vpin_net_cfg_counts and vpin_net_infer share
@@ -69,6 +69,10 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.mult = 2 * l.fh * l.fw * pairs;
       p.add = p.mult - 2 * l.n_out;
       p.keys = 2 * l.n_out;
+      if (l.bias) {  // like the table, whether there is a bias is architecture: n_out values, an addition per output
+        p.bias_r = l.n_out;
+        p.add += 2 * l.n_out * p.oH * p.oW;
+      }
     } else if (l.kind == VPIN_NET_POOL) {
       if (!l.k || !l.stride) return fail(VPIN_EINVAL, "vpin_net: a dimension is zero");
       if (l.stride > kMaxSide) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
@@ -76,13 +80,13 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.oH = (H - l.k) / l.stride + 1;
       p.oW = (W - l.k) / l.stride + 1;
       p.add = 2 * C * p.oH * p.oW * (l.k * l.k - 1);
-    } else if (l.kind == VPIN_NET_FC) {
+    } else if (l.kind == VPIN_NET_FC || l.kind == VPIN_NET_FCS) {
       if (!l.N || !l.K) return fail(VPIN_EINVAL, "vpin_net: a dimension is zero");
       if (l.N > 65535) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
       if (l.K != C * H * W) return fail(VPIN_EINVAL, "vpin_net: a fully connected layer's K is not the C * H * W that reaches it");
       if (weights) {
         if (!l.w || !l.bias) return fail(VPIN_EINVAL, "vpin_net: a fully connected layer has no weights or no bias");
-        if (vpin::infer::any_negative(l.w, l.K * l.N)) return fail(VPIN_EINVAL, "vpin_net: a weight of a fully connected layer is negative");
+        if (l.kind == VPIN_NET_FC && vpin::infer::any_negative(l.w, l.K * l.N)) return fail(VPIN_EINVAL, "vpin_net: a weight of a fully connected layer is negative");
       }
       p.oC = 1; p.oH = 1; p.oW = l.N;
       p.mult = 2 * l.K;
@@ -90,7 +94,7 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.keys = 2;
       p.bias_r = l.N;
     } else {
-      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc, convmc");
+      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc, convmc, fcs");
     }
     if (l.has_round) {
       if (l.shift_bits < 0 || l.shift_bits > 62) return fail(VPIN_EINVAL, "vpin_net: a round's shift_bits is outside 0 .. 62");
@@ -147,7 +151,8 @@ int vpin_net_infer(vpin_ctx* c, const vpin_net_cfg* g, const uint8_t* c1x, const
   for (size_t i = 0; i < pl.size(); i++) {
     const vpin_net_layer& l = g->layers[i];
     Step& s = steps[i];
-    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc : Step::kFc;
+    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc
+             : l.kind == VPIN_NET_FCS ? Step::kFcs : Step::kFc;
     s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
     if (l.kind == VPIN_NET_CONVMC) { s.n_out = l.n_out; s.w_mc = l.w_mc; s.connect = l.connect; }  // no other kind reads them
     s.k = l.k; s.scale_le16 = l.scale_le16;

@@ -2,7 +2,8 @@
 (src/cnn_networks/Server.py inferenceCNN) over the encrypted layers, the client's rounds in between (the ready-made client of
 any number of rounds, or a Python callback), and the network's ONE label for the prover: the lists of all layers concatenated
 in layer order, as the reference leaves them in its four global lists.  Beside the reference's three layer kinds there is CONVMC,
-the convolution of a trained model (vpin_enc_conv2d_mc: a signed filter per channel pair, an optional connection table).
+the convolution of a trained model (vpin_enc_conv2d_mc: a signed filter per channel pair, an optional connection table, and with a
+bias vpin_enc_conv2d_mc_bias), and FCS, the fully connected layer over signed weights (vpin_enc_fc_signed).
 
 The networks' constants are data, not code: `cnn_config(version)` reads the filter, the pooling windows, the PRF bytes, the
 schedule of the rounds and the names of the weight files from the fixture recorded off runs of the reference
@@ -17,7 +18,7 @@ from . import inference
 from .capi import NetCfg, NetLayer, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
-CONV, POOL, FC, CONVMC = 0, 1, 2, 3
+CONV, POOL, FC, CONVMC, FCS = 0, 1, 2, 3, 4
 VERSIONS = ("A", "B", "C", "D", "E")
 _GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
@@ -46,9 +47,9 @@ class Config:
         l.fh, l.fw, l.pad, l.stride, l.filter_le16 = len(filt), len(filt[0]), pad, stride, buf.ctypes.data
         return self
 
-    def convmc(self, w, connect=None, pad=0, stride=1):
+    def convmc(self, w, connect=None, pad=0, stride=1, bias=None):
         """the trained convolution (VPIN_NET_CONVMC): w[o][c][ii][jj] signed ints (int32 range), n_out x C x fh x fw with C the
-        planes that reach the layer; connect: n_out x C, non-zero = connected (None: all)"""
+        planes that reach the layer; connect: n_out x C, non-zero = connected (None: all); bias: n_out ints (None: no bias)"""
         w64 = np.asarray(w, dtype=np.int64)
         w32 = np.ascontiguousarray(w64.astype(np.int32))
         assert w32.ndim == 4 and np.array_equal(w32, w64)
@@ -60,6 +61,11 @@ class Config:
             assert t.shape == w32.shape[:2]
             self._keep.append(t)
             l.connect = t.ctypes.data
+        if bias is not None:
+            b = np.ascontiguousarray(np.asarray(bias, dtype=np.int64))
+            assert b.shape == (w32.shape[0],)
+            self._keep.append(b)
+            l.bias = b.ctypes.data
         return self
 
     def pool(self, k, stride, scale):
@@ -68,7 +74,7 @@ class Config:
         l.scale_le16[:] = list(int(scale).to_bytes(16, "little"))
         return self
 
-    def fc(self, w, bias):
+    def fc(self, w, bias, kind=FC):
         """w: K x N ints (int32 range; a negative one is rejected by the driver), bias: N ints"""
         w64 = np.asarray(w, dtype=np.int64)
         w32 = np.ascontiguousarray(w64.astype(np.int32))
@@ -76,9 +82,13 @@ class Config:
         b = np.ascontiguousarray(np.asarray(bias, dtype=np.int64))
         assert b.shape == (w32.shape[1],)
         self._keep += [w32, b]
-        l = self._add(FC)
+        l = self._add(kind)
         l.K, l.N, l.w, l.bias = w32.shape[0], w32.shape[1], w32.ctypes.data, b.ctypes.data
         return self
+
+    def fcs(self, w, bias):
+        """the fully connected layer of a trained model (VPIN_NET_FCS): fc with signed weights"""
+        return self.fc(w, bias, FCS)
 
     def round(self, relu=False, shift_bits=0, max_giant=1, reencrypt=True):
         l = self.layers[-1]
@@ -132,6 +142,26 @@ def cnn_config(version, nb_log=24, golden=None):
     cfg.pool(k, v["pool"][1], int(2**net["pool_scale_bits"] / k**2)).round(**rnd(1))
     cfg.fc(load("weight_fc1"), load("bias_fc1")).round(**rnd(2))
     cfg.fc(load("weight_fc2"), load("bias_fc2")).round(**rnd(3))
+    return cfg
+
+
+def lenet5_config(conv1, b1, conv2, b2, fc, bfc, fc1, bfc1, fc2, bfc2, rounds, prf_bytes=13):
+    """the architecture of the reference's src/accuracy/train_test_lenet5.py over a 1 x 32 x 32 input, every weight signed and every
+    weighted layer biased: CONVMC 1 -> 6 (f 5), pool 2 / 2, CONVMC 6 -> 16 (f 5), pool 2 / 2, FCS 400 -> 120, FCS 120 -> 84,
+    FCS 84 -> 10.  conv1: 6 x 1 x 5 x 5, conv2: 16 x 6 x 5 x 5, the fc matrices K x N (a Linear's weight transposed), all as
+    fixed-point ints; rounds: seven dicts for Config.round, one per layer in order (the pooling's scale is 1: the division by
+    4 goes into its round's shift_bits)"""
+    conv1, conv2 = np.asarray(conv1, dtype=np.int64), np.asarray(conv2, dtype=np.int64)
+    assert conv1.shape == (6, 1, 5, 5) and conv2.shape == (16, 6, 5, 5) and len(rounds) == 7
+    assert [np.shape(w) for w in (fc, fc1, fc2)] == [(400, 120), (120, 84), (84, 10)]
+    cfg = Config(1, 32, 32, prf_bytes)
+    cfg.convmc(conv1, bias=b1).round(**rounds[0])
+    cfg.pool(2, 2, 1).round(**rounds[1])
+    cfg.convmc(conv2, bias=b2).round(**rounds[2])
+    cfg.pool(2, 2, 1).round(**rounds[3])
+    cfg.fcs(fc, bfc).round(**rounds[4])
+    cfg.fcs(fc1, bfc1).round(**rounds[5])
+    cfg.fcs(fc2, bfc2).round(**rounds[6])
     return cfg
 
 
