@@ -1017,6 +1017,112 @@ int vpin_net_client_round(void* user, int round, int flags, int shift_bits, cons
                           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
                           uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 
+/* ---- the inference between two processes over a byte stream (ABI 5) ----------------------------------------------------------
+ * The reference's Server.py / Client.py are two processes (send_data_in_chunks / receive_data_in_chunks); here the server loop
+ * (vpin_net_serve) and the client (vpin_net_client_run) meet over any byte stream the caller has: vpin_wire_round is the round
+ * callback of vpin_net_infer on the server's side, vpin_net_client_round is called in a loop on the client's.  The library opens,
+ * listens on and connects nothing, and sends no proofs; there is no authentication.
+ *
+ * A packed point is one 256-bit little-endian integer (E2's group order is prime and the only multiple of itself inside the Hasse
+ * interval: every point of the curve is in the group, so x and a sign say it all):
+ *   bits 0 .. 252  the canonical x, x < q        bit 254  the identity; all other bits are zero then
+ *   bit 253        zero                          bit 255  bit 0 of the canonical y in [0, q)
+ * The point (0, sqrt(b)) with even y is 32 zero bytes, a valid point; the identity is 00 .. 00 40.
+ * vpin_e2_pack: points as in vpin_e2_msm -> cnt x 32 bytes.  VPIN_EINVAL: a null argument, cnt = 0 or >= 2^31, and, named with the
+ * first such index ("vpin_e2_pack: point 3: the point is not on the curve E2"), a coordinate >= q or a point off the curve.
+ * vpin_e2_unpack: cnt x 32 bytes -> points as every layer takes them (an identity as zeros with flag 1).  One square root in
+ * F_q per point on the device (one fixed exponentiation; the root is checked, never trusted).  VPIN_EINVAL: a null argument,
+ * cnt = 0 or >= 2^31, and, named with the first such index and its rule: "x is not below q" (x is never reduced: x = q is not
+ * x = 0), "bit 253 is set", "the identity bit is set together with other bits", "x is not on the curve E2" (x^3 + a x + b is
+ * not a square), "the parity bit is set over y = 0". */
+int vpin_e2_pack(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt, uint8_t* out32);
+int vpin_e2_unpack(vpin_ctx* ctx, const uint8_t* in32, size_t cnt, uint8_t* px, uint8_t* py, uint8_t* pinf);
+
+/* A frame is a header of 24 bytes, little-endian, and a payload:
+ *   magic "VPW1" | type u8 | flags u8 | shift_bits u8 | reserved u8 = 0 | round u32 | cnt u32 | payload_len u64
+ *   HELLO  client -> server  cnt = 1           the packed public key H
+ *   INPUT  client -> server  cnt = C H W       cnt packed c1, then cnt packed c2
+ *   ROUND  server -> client  the round's cnt   as INPUT, with round, flags (VPIN_LENET_RELU | VPIN_LENET_REENCRYPT), shift_bits
+ *   REPLY  client -> server  cnt, or 0         as INPUT; cnt = 0 without a payload acknowledges a round that encrypts nothing
+ *   DONE   server -> client  cnt = 0           no payload
+ *   ERROR  either way        cnt = 0           an int32 code and at most VPIN_WIRE_MAX_TEXT bytes of text
+ * vpin_wire_header_decode answers VPIN_EINVAL and names the rule for a wrong magic, an unknown type, a reserved byte that is
+ * not zero, cnt above VPIN_WIRE_MAX_CNT and a payload_len that is not exactly what the type and cnt imply; the cap bounds what
+ * a hostile header can make a receiver allocate, and no receiver allocates before decode has accepted the header.
+ * vpin_wire_header_encode applies the same rules to what it is given. */
+#define VPIN_WIRE_HELLO 1
+#define VPIN_WIRE_INPUT 2
+#define VPIN_WIRE_ROUND 3
+#define VPIN_WIRE_REPLY 4
+#define VPIN_WIRE_DONE 5
+#define VPIN_WIRE_ERROR 6
+#define VPIN_WIRE_HEADER_LEN 24
+#define VPIN_WIRE_MAX_CNT ((uint32_t)1 << 24)
+#define VPIN_WIRE_MAX_TEXT 1024
+typedef struct vpin_wire_header {
+  uint8_t type, flags, shift_bits;
+  uint32_t round, cnt;
+  uint64_t payload_len;
+} vpin_wire_header;
+int vpin_wire_header_encode(const vpin_wire_header* h, uint8_t out24[VPIN_WIRE_HEADER_LEN]);
+int vpin_wire_header_decode(const uint8_t in24[VPIN_WIRE_HEADER_LEN], vpin_wire_header* h);
+
+/* The stream: frames over a transport of the caller's.  send / recv move exactly n bytes and return 0, or fail with a negative
+ * code.  The descriptor form serves pipes, socketpairs and connected sockets and closes nothing: every wait is a poll of at most
+ * timeout_ms (> 0), EINTR is retried, and end-of-file, a time-out and a write error are VPIN_ECOMM with a text such as
+ * "vpin_wire: the peer closed the stream after 17 of 24 bytes"; a closed peer is never SIGPIPE (MSG_NOSIGNAL on sockets, the
+ * signal masked around the write elsewhere).  A vpin_wire needs no context and no GPU; one thread drives it.
+ * vpin_wire_send / vpin_wire_recv move one frame: recv decodes the header first and answers VPIN_EINVAL, reading no payload,
+ * when payload_len is above cap.  vpin_wire_send_error sends ERROR(code, text) best effort and keeps the caller's error text.
+ * vpin_wire_stats: bytes sent, bytes received, frames sent, frames received.  vpin_wire_timings: host-clock ms of slot 0 (HELLO
+ * and INPUT) or 1 + r (round r) spent by this side in pack, unpack, send and the receive of payloads; VPIN_EINVAL for a slot
+ * this wire has not seen. */
+typedef struct vpin_wire vpin_wire;
+typedef struct vpin_wire_io {
+  int (*send)(void* user, const void* p, size_t n);
+  int (*recv)(void* user, void* p, size_t n);
+  void* user;
+} vpin_wire_io;
+int vpin_wire_create(const vpin_wire_io* io, vpin_wire** out);
+int vpin_wire_fd_create(int rfd, int wfd, int timeout_ms, vpin_wire** out);
+void vpin_wire_free(vpin_wire* w);
+int vpin_wire_stats(const vpin_wire* w, uint64_t out[4]);
+int vpin_wire_timings(const vpin_wire* w, size_t slot, double out[4]);
+int vpin_wire_send(vpin_wire* w, const vpin_wire_header* h, const uint8_t* payload);
+int vpin_wire_recv(vpin_wire* w, vpin_wire_header* h, uint8_t* payload, size_t cap);
+int vpin_wire_send_error(vpin_wire* w, int code, const char* text);
+
+/* The server's endpoint.  vpin_wire_round is a vpin_lenet_round_fn with user = a vpin_wire bound to a context
+ * (vpin_wire_bind_ctx; vpin_net_serve binds its own): it packs the round's c1 and c2, sends ROUND, reads REPLY, checks its round
+ * and cnt (VPIN_ESHAPE, "vpin_wire_round: round 2: the reply is for round 3"), unpacks (VPIN_EINVAL naming the index, as
+ * vpin_e2_unpack) and returns the points in the callback's outputs.  An ERROR frame from the peer is VPIN_ECOMM quoting the
+ * peer's code and text.  vpin_lenet_infer takes it as well.
+ * vpin_net_serve reads HELLO, unpacks H and builds the tables of G and H, reads INPUT (cnt must be the configuration's C H W:
+ * VPIN_ESHAPE), runs vpin_net_infer with vpin_wire_round and sends DONE.  On any failure of its own it sends ERROR(code, text)
+ * best effort, frees everything and returns the code with the text; the server never holds a secret key.  VPIN_EINVAL before
+ * anything is read for a configuration whose last layer has no round: its result would never reach the client. */
+int vpin_wire_bind_ctx(vpin_wire* w, vpin_ctx* ctx);
+int vpin_wire_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                    const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf,
+                    uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+int vpin_net_serve(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* keys32, size_t n_keys,
+                   const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out);
+
+/* The client's endpoint: encrypts the image (n_input ints under n_input r, as vpin_e2_encrypt) under its own tables, sends HELLO
+ * and INPUT, then serves frames.  A client that performs whatever round the server asks for is a decryption oracle, so the
+ * schedule is the CLIENT's: ROUND must carry the next round number and exactly that round's flags, shift_bits and cnt, else the
+ * client sends ERROR and returns VPIN_ESHAPE ("vpin_net_client_run: round 2: the server asks for shift_bits 20, the schedule
+ * says 21") before anything is decrypted.  On a match: unpack, vpin_net_client_round, pack, REPLY.  DONE is VPIN_OK only after
+ * all n_rounds rounds (VPIN_ESHAPE otherwise); ERROR is VPIN_ECOMM with the peer's text.  n_rounds is at most the rounds the
+ * client was created for.  The values are read with vpin_net_client_values. */
+typedef struct vpin_wire_round_spec {
+  int flags;
+  int shift_bits;
+  size_t cnt;
+} vpin_wire_round_spec;
+int vpin_net_client_run(vpin_net_client* cl, vpin_wire* w, const int64_t* image, const uint8_t* image_r_le32, size_t n_input,
+                        const vpin_wire_round_spec* schedule, size_t n_rounds);
+
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's
  * c*Q and blind*H terms are host work: nizk/mod.rs:447-531).  x = the vector being reduced (a in bullet.rs), a = the

@@ -1,5 +1,5 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
-the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs]
+the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
@@ -7,10 +7,17 @@ It prints its fixed seeds, checks the scores and every round's values against th
 label's counts against the model's, and then the median / minimum / maximum in ms over R warm runs (after one warm-up run) of
 every layer and every round (the library's host clock, vpin_net_last_timings), of the whole inference, and of the whole
 inference followed by the two proofs of its one label (vpin_snark_prove_dev on the trace's device instances).  The baby-step
-table has 2^nb entries (default 24)."""
+table has 2^nb entries (default 24).
+--wire: the same inference in process and between two endpoints over a socketpair (vpin_net_serve in a thread on a context of
+its own, vpin_net_client_run here), the two modes alternating in this one process, R = 11 warm runs by default after one warm-up
+pair.  Per round it prints the bytes on the wire each way and the ms of pack, unpack and socket (send and the receive of
+payloads), both sides added up (vpin_wire_timings), beside that round's own time in process and over the wire (the server's host
+clock: the round as the driver sees it, the client's work and the wire included)."""
 import os
+import socket
 import statistics
 import sys
+import threading
 import time
 
 import numpy as np
@@ -30,7 +37,8 @@ def opt(name, default):
 
 
 VERSION = sys.argv[1]
-REPS, NB_LOG = opt("--reps", 5), opt("--nb", 24)
+WIRE = "--wire" in sys.argv
+REPS, NB_LOG = opt("--reps", 11 if WIRE else 5), opt("--nb", 24)
 PROOFS = "--no-proofs" not in sys.argv
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
@@ -71,6 +79,10 @@ def main():
     bias_rs = EL.splitmix_scalars(SEEDS["bias_r"], counts["bias_r"])
     client_rs = EL.splitmix_scalars(SEEDS["client_r"], counts["encryptions"] - image.size)
     n = len(cfg.layers)
+    if WIRE:
+        wire_mode(ctx, cfg, counts, giants, image, image_rs, keys, bias_rs, client_rs, vs, acts)
+        ctx.close()
+        return
     layers, rounds, whole, proved = [], [], [], []
     for rep in range(REPS + 1):
         client = VN.Client(ctx, SK, 1 << NB_LOG, giants, client_rs)
@@ -110,6 +122,89 @@ def main():
     if PROOFS:
         print("%-34s %s" % ("inference + 2 proofs", stats(proved)))
     ctx.close()
+
+
+def wire_mode(ctx, cfg, counts, giants, image, image_rs, keys, bias_rs, client_rs, vs, acts):
+    from vpin_amd import wire as W
+    ctx2 = vpin_amd.Context(0)  # the client's
+    sched, n, nr = VN.schedule(cfg), len(cfg.layers), len(giants)
+    at = [i for i, l in enumerate(cfg.layers) if l.has_round]  # the layer each round follows
+    inproc, wired, whole_in, whole_wire, infer_in, infer_wire = [], [], [], [], [], []
+    parts = []  # per run, per slot (0: HELLO and INPUT, 1 + r: round r): pack, unpack, socket ms, both sides added
+    stats = None
+    for rep in range(REPS + 1):
+        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs)
+        t0 = time.perf_counter()
+        scores, values, trace = VN.infer(ctx, cfg, client, image, image_rs, keys, bias_rs)
+        t1 = time.perf_counter()
+        tm = VN.timings(n)
+        trace.free()
+        client.free()
+        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs)
+        a, b = socket.socketpair()
+        ws, wc = W.Wire.from_fds(a.fileno(), a.fileno(), 600000), W.Wire.from_fds(b.fileno(), b.fileno(), 600000)
+        out = {}
+
+        def server():
+            try:
+                tr = VN.serve(ctx, cfg, ws, keys, bias_rs)
+                out["tm"] = VN.timings(n)  # this thread's
+                tr.free()
+            except BaseException as e:  # noqa: BLE001
+                out["error"] = e
+
+        th = threading.Thread(target=server)
+        t2 = time.perf_counter()
+        th.start()
+        wscores, wvalues = client.run(wc, image, image_rs, sched)
+        th.join()
+        t3 = time.perf_counter()
+        assert "error" not in out, out.get("error")
+        for r in range(nr):
+            assert np.array_equal(wvalues[r][0], values[r][0]) and np.array_equal(wvalues[r][1], values[r][1]), "round %d over the wire" % r
+        if rep == 0:
+            for r in range(nr):
+                assert [int(v) for v in values[r][0]] == vs[r] and [int(v) for v in values[r][1]] == acts[r], "round %d" % r
+            print("scores:", [int(v) for v in wscores], "class", int(np.argmax(wscores)), "(over the wire; the plaintext model's, every round checked in both modes)")
+            stats = (wc.stats(), ws.stats())
+        else:
+            inproc.append([tm["rounds"][i] for i in at])
+            wired.append([out["tm"]["rounds"][i] for i in at])
+            whole_in.append((t1 - t0) * 1e3)
+            whole_wire.append((t3 - t2) * 1e3)
+            infer_in.append(tm["total"])
+            infer_wire.append(out["tm"]["total"])
+            run = []
+            for slot in range(nr + 1):
+                s, c = ws.timings(slot), wc.timings(slot)
+                run.append((s["pack"] + c["pack"], s["unpack"] + c["unpack"], s["send"] + c["send"] + s["recv"] + c["recv"]))
+            parts.append(run)
+        ws.free(); wc.free()
+        a.close(); b.close()
+        client.free()
+    med = lambda xs: statistics.median(xs)
+    rng = lambda xs: "%8.2f (%7.2f .. %7.2f)" % (med(xs), min(xs), max(xs))
+    print("bytes on the wire: client -> server %d in %d frames, server -> client %d in %d frames" %
+          (stats[0]["bytes_sent"], stats[0]["frames_sent"], stats[1]["bytes_sent"], stats[1]["frames_sent"]))
+    print("ms, warm, median (min .. max) over %d runs, the two modes alternating" % REPS)
+    print("%-26s %9s %9s  %-28s %-28s %-28s %-28s %-28s" % ("", "B down", "B up", "round in process", "round over the wire", "pack", "unpack", "socket"))
+    col = lambda k, slot: rng([p[slot][k] for p in parts])
+    print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % ("HELLO and INPUT", 0, 2 * 24 + 32 + 64 * image.size, "", "", col(0, 0), col(1, 0), col(2, 0)))
+    for r, (flags, _, cnt) in enumerate(sched):
+        print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % (
+            "round %d (%d values)" % (r, cnt), 24 + 64 * cnt, 24 + (64 * cnt if flags & VN.REENCRYPT else 0), rng([x[r] for x in inproc]),
+            rng([x[r] for x in wired]), col(0, 1 + r), col(1, 1 + r), col(2, 1 + r)))
+    tot = lambda k: [sum(p[slot][k] for slot in range(nr + 1)) for p in parts]
+    print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % ("in all", stats[1]["bytes_sent"], stats[0]["bytes_sent"], rng(whole_in), rng(whole_wire),
+                                                             rng(tot(0)), rng(tot(1)), rng(tot(2))))
+    print("%-26s %9s %9s  %-28s %-28s" % ("vpin_net_infer alone", "", "", rng(infer_in), rng(infer_wire)))
+    print("(in all: from the image's encryption to the last value; over the wire it also holds the connection's set-up, the server's two "
+          "window tables of G and H built by vpin_e2_base_create, which the run in process takes ready-made from its client)")
+    share = [100.0 * (a + b + c) / w for a, b, c, w in zip(tot(0), tot(1), tot(2), whole_wire)]
+    print("pack + unpack + socket are %.2f %% of an inference over the wire (median; %.2f .. %.2f); unpack alone %.2f %%" %
+          (med(share), min(share), max(share), med([100.0 * b / w for b, w in zip(tot(1), whole_wire)])))
+    print("the inference over the wire takes %.3f x the inference in process (medians)" % (med(whole_wire) / med(whole_in)))
+    ctx2.close()
 
 
 if __name__ == "__main__":

@@ -69,6 +69,17 @@ class NetCfg(C.Structure):
                 ("layers", C.POINTER(NetLayer))]
 
 
+class WireHeader(C.Structure):
+    """vpin_wire_header of include/vpin_hip.h"""
+    _fields_ = [("type", C.c_uint8), ("flags", C.c_uint8), ("shift_bits", C.c_uint8), ("round", C.c_uint32), ("cnt", C.c_uint32),
+                ("payload_len", C.c_uint64)]
+
+
+class WireRoundSpec(C.Structure):
+    """vpin_wire_round_spec of include/vpin_hip.h"""
+    _fields_ = [("flags", C.c_int), ("shift_bits", C.c_int), ("cnt", C.c_size_t)]
+
+
 # vpin_lenet_round_fn
 LENET_ROUND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, *([C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 6))
 
@@ -252,6 +263,22 @@ def lib():
     L.vpin_net_client_free.restype = None
     L.vpin_net_client_bases.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_net_client_values.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_e2_pack.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.vpin_e2_unpack.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_wire_header_encode.argtypes = [C.POINTER(WireHeader), vp]
+    L.vpin_wire_header_decode.argtypes = [vp, C.POINTER(WireHeader)]
+    L.vpin_wire_create.argtypes = [vp, C.POINTER(vp)]
+    L.vpin_wire_fd_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.vpin_wire_free.argtypes = [vp]
+    L.vpin_wire_free.restype = None
+    L.vpin_wire_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vpin_wire_timings.argtypes = [vp, C.c_size_t, C.POINTER(C.c_double)]
+    L.vpin_wire_send.argtypes = [vp, C.POINTER(WireHeader), vp]
+    L.vpin_wire_recv.argtypes = [vp, C.POINTER(WireHeader), vp, C.c_size_t]
+    L.vpin_wire_send_error.argtypes = [vp, C.c_int, C.c_char_p]
+    L.vpin_wire_bind_ctx.argtypes = [vp, vp]
+    L.vpin_net_serve.argtypes = [vp, C.POINTER(NetCfg), vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_client_run.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(WireRoundSpec), C.c_size_t]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]
@@ -1531,6 +1558,25 @@ class Context:
         if rs is None:
             return v, act, None, None
         return v, act, tuple(out[:3]), tuple(out[3:])
+
+    def e2_pack(self, x, y, inf=None):
+        """vpin_e2_pack: points -> (n, 32) bytes, one packed point per row (x, the parity of y, an identity bit)"""
+        x, y, f = self._points(x, y, inf)
+        n = x.shape[0]
+        out = np.zeros((n, 32), np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_pack(self.h, p(x), p(y), p(f), n, p(out)), "vpin_e2_pack")
+        return out
+
+    def e2_unpack(self, packed):
+        """vpin_e2_unpack: n packed points -> (x, y, inf) arrays as every layer takes them"""
+        b = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if isinstance(packed, (bytes, bytearray)) else packed,
+                                 dtype=np.uint8).reshape(-1, 32)
+        n = b.shape[0]
+        ox, oy, oi = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_unpack(self.h, p(b), n, p(ox), p(oy), p(oi)), "vpin_e2_unpack")
+        return ox, oy, oi
 
     def e2_plane_sums(self, x, y, inf, n_in, H, W, connect):
         """vpin_e2_plane_sums: n_in planes of H x W points and a table connect[o][j] -> (x, y, inf) of len(connect) planes, each the

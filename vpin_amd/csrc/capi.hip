@@ -286,14 +286,16 @@ const char* vpin_strerror(int code) {
     case VPIN_EHIP: return "HIP runtime error";
     case VPIN_ESHAPE: return "operand shapes do not match";
     case VPIN_EVERIFY: return "proof rejected by the verifier";
-    case VPIN_ECOMM: return "a peer rank failed or timed out";
+    case VPIN_ECOMM: return "a peer rank failed or timed out";  // a rank of a group, or the peer of a vpin_wire
     default: return "unknown error";
   }
 }
 
 const char* vpin_last_error(void) { return g_last_error.c_str(); }
 
-int vpin_abi_version(void) { return 4; }  // 3: vpin_net_layer grew n_out, w_mc, connect at its end (VPIN_NET_CONVMC); 4: VPIN_NET_FCS, CONVMC reads bias
+// 3: vpin_net_layer grew n_out, w_mc, connect at its end (VPIN_NET_CONVMC); 4: VPIN_NET_FCS, CONVMC reads bias; 5: the wire (vpin_e2_pack,
+// vpin_wire_*, vpin_net_serve, vpin_net_client_run), new symbols only
+int vpin_abi_version(void) { return 5; }
 
 static int ctx_create(int device, int priority, const uint32_t* cu_mask, uint32_t n_words, vpin_ctx** out);
 

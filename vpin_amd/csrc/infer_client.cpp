@@ -1,12 +1,15 @@
 // infer_client.cpp -- the ready-made client of an encrypted inference, for any number of rounds: a vpin_lenet_round_fn over
 // vpin_e2_client_round (what main of the reference's Client.py does between two layers) around an object that owns the key, the
 // two base tables, the discrete-log table and the queue of encryption randomness, and keeps every round's values.
+#include <cstdio>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/vpin_hip.h"
 #include "enc_conv.h"
+#include "wire.h"
 
 using vpin::enc::fail;
 
@@ -86,6 +89,99 @@ int vpin_net_client_round(void* user, int round, int flags, int shift_bits, cons
                                       cl->v[round].data(), cl->act[round].data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
   if (re && rc == VPIN_OK) cl->r_pos += cnt;  // a failed round consumes nothing: the client can be used again
   return rc;
+}
+
+// The client's endpoint over a byte stream (wire.h): HELLO and INPUT, then one vpin_net_client_round per ROUND frame that is
+// exactly what the client's own schedule says comes next.  A mismatch is answered with ERROR before anything is decrypted
+int vpin_net_client_run(vpin_net_client* cl, vpin_wire* w, const int64_t* image, const uint8_t* image_r_le32, size_t n_input,
+                        const vpin_wire_round_spec* schedule, size_t n_rounds) {
+  namespace wr = vpin::wire;
+  const char* who = "vpin_net_client_run";
+  if (!cl || !w || !image || !image_r_le32 || !schedule) return fail(VPIN_EINVAL, "vpin_net_client_run: null argument");
+  if (n_input == 0 || n_input > VPIN_WIRE_MAX_CNT) return fail(VPIN_EINVAL, "vpin_net_client_run: n_input must be in 1 .. VPIN_WIRE_MAX_CNT");
+  if (n_rounds == 0 || n_rounds > cl->v.size()) return fail(VPIN_EINVAL, "vpin_net_client_run: n_rounds must be in 1 .. the rounds the client was made for");
+  char why[240];
+  // the failing call's text behind this endpoint's name; told: the peer hears of it too
+  auto failed = [&](int rc, const std::string& where, bool told) {
+    const std::string text = std::string(who) + ": " + where + vpin_last_error();
+    if (told) wr::send_error(w, rc, text.c_str());
+    return fail(rc, text.c_str());
+  };
+  vpin_wire_header h;
+  std::vector<uint8_t> p;
+  // HELLO: H = sk * G
+  uint8_t hx[32], hy[32], hinf = 0;
+  int rc = vpin_e2_base_mul(cl->ctx, cl->g, cl->sk, 1, hx, hy, &hinf);
+  if (rc) return failed(rc, "", false);
+  p.resize(32);
+  wr::Lap lap;
+  rc = vpin_e2_pack(cl->ctx, hx, hy, &hinf, 1, p.data());
+  wr::add_ms(w, 0, wr::kPack, lap());
+  if (rc) return failed(rc, "", false);
+  memset(&h, 0, sizeof h);
+  h.type = VPIN_WIRE_HELLO; h.cnt = 1; h.payload_len = 32;
+  if ((rc = wr::send_frame_timed(w, 0, h, p.data()))) return failed(rc, "", false);
+  // INPUT: the image under the client's key
+  {
+    std::vector<uint8_t> x1(32 * n_input), y1(32 * n_input), f1(n_input), x2(32 * n_input), y2(32 * n_input), f2(n_input);
+    rc = vpin_e2_encrypt(cl->ctx, cl->g, cl->h, image, image_r_le32, n_input, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data());
+    if (!rc) rc = wr::pack_pair_timed(w, 0, cl->ctx, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data(), n_input, &p);
+    if (rc) return failed(rc, "the input: ", true);
+  }
+  h.type = VPIN_WIRE_INPUT; h.cnt = (uint32_t)n_input; h.payload_len = 64 * (uint64_t)n_input;
+  if ((rc = wr::send_frame_timed(w, 0, h, p.data()))) return failed(rc, "", false);
+  for (size_t done = 0;;) {
+    if ((rc = wr::recv_header(w, &h))) return failed(rc, "", rc != VPIN_ECOMM);
+    if (h.type == VPIN_WIRE_ERROR) return wr::peer_error(w, h, who);
+    if (h.type == VPIN_WIRE_DONE) {
+      if (done == n_rounds) return VPIN_OK;
+      snprintf(why, sizeof why, "%s: the server is done after %zu of %zu rounds", who, done, n_rounds);
+      return fail(VPIN_ESHAPE, why);
+    }
+    why[0] = 0;
+    if (h.type != VPIN_WIRE_ROUND) {
+      snprintf(why, sizeof why, "%s: expected ROUND or DONE, the server sent type %u", who, (unsigned)h.type);
+    } else if (done == n_rounds) {
+      snprintf(why, sizeof why, "%s: the server asks for round %u, the schedule ends after %zu rounds", who, (unsigned)h.round, n_rounds);
+    } else {
+      const vpin_wire_round_spec& s = schedule[done];
+      if (h.round != done)
+        snprintf(why, sizeof why, "%s: the server asks for round %u, the schedule says round %zu comes next", who, (unsigned)h.round, done);
+      else if ((int)h.flags != s.flags)
+        snprintf(why, sizeof why, "%s: round %zu: the server asks for flags %d (relu %d, reencrypt %d), the schedule says %d", who, done,
+                 (int)h.flags, (h.flags & VPIN_LENET_RELU) != 0, (h.flags & VPIN_LENET_REENCRYPT) != 0, s.flags);
+      else if ((int)h.shift_bits != s.shift_bits)
+        snprintf(why, sizeof why, "%s: round %zu: the server asks for shift_bits %d, the schedule says %d", who, done, (int)h.shift_bits, s.shift_bits);
+      else if ((size_t)h.cnt != s.cnt)
+        snprintf(why, sizeof why, "%s: round %zu: the server sends %u ciphertexts, the schedule says %zu", who, done, (unsigned)h.cnt, s.cnt);
+    }
+    if (why[0]) {  // nothing is decrypted: the payload is read into nothing, so that the peer is not left writing, and refused
+      const std::string text = why;
+      if (wr::discard_payload(w, h) == VPIN_OK) wr::send_error(w, VPIN_ESHAPE, text.c_str());
+      return fail(VPIN_ESHAPE, text.c_str());
+    }
+    const size_t slot = 1 + done, cnt = h.cnt;
+    const int flags = h.flags, bits = h.shift_bits;
+    const bool re = (flags & VPIN_LENET_REENCRYPT) != 0;
+    snprintf(why, sizeof why, "round %zu: ", done);
+    if ((rc = wr::recv_payload_timed(w, slot, h, &p))) return failed(rc, why, false);
+    std::vector<uint8_t> x1(32 * cnt), y1(32 * cnt), f1(cnt), x2(32 * cnt), y2(32 * cnt), f2(cnt);
+    if ((rc = wr::unpack_pair_timed(w, slot, cl->ctx, p, cnt, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data())))
+      return failed(rc, why, true);
+    std::vector<uint8_t> o1x, o1y, o1f, o2x, o2y, o2f;
+    if (re) { o1x.resize(32 * cnt); o1y.resize(32 * cnt); o1f.resize(cnt); o2x.resize(32 * cnt); o2y.resize(32 * cnt); o2f.resize(cnt); }
+    rc = vpin_net_client_round(cl, (int)done, flags, bits, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data(), cnt,
+                               re ? o1x.data() : nullptr, re ? o1y.data() : nullptr, re ? o1f.data() : nullptr, re ? o2x.data() : nullptr,
+                               re ? o2y.data() : nullptr, re ? o2f.data() : nullptr);
+    if (rc) return failed(rc, why, true);
+    p.clear();
+    if (re && (rc = wr::pack_pair_timed(w, slot, cl->ctx, o1x.data(), o1y.data(), o1f.data(), o2x.data(), o2y.data(), o2f.data(), cnt, &p)))
+      return failed(rc, why, true);
+    memset(&h, 0, sizeof h);
+    h.type = VPIN_WIRE_REPLY; h.round = (uint32_t)done; h.cnt = re ? (uint32_t)cnt : 0; h.payload_len = re ? 64 * (uint64_t)cnt : 0;
+    if ((rc = wr::send_frame_timed(w, slot, h, p.data()))) return failed(rc, why, false);
+    done++;
+  }
 }
 
 }  // extern "C"

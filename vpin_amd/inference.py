@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, _chk, lib
+from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, WireRoundSpec, _chk, lib
 
 RELU, REENCRYPT = 1, 2
 
@@ -49,6 +49,19 @@ class Client:
     def encrypt(self, msgs, rs):
         """the input's encryption under the client's key -> (c1, c2), each (x, y, inf)"""
         return self.ctx.e2_encrypt(self.base_g, self.base_h, msgs, rs)
+
+    def run(self, wire, image, image_rs, schedule):
+        """vpin_net_client_run: the client's endpoint over a vpin_amd.wire.Wire.  Encrypts the image (ints) under image_rs, sends
+        HELLO and INPUT and serves the rounds of `schedule` ([(flags, shift_bits, cnt)], net.schedule) and no others -> (scores,
+        rounds) as `infer` returns them"""
+        m = np.ascontiguousarray(np.array([int(v) for v in np.asarray(image).reshape(-1)], dtype=np.int64))
+        r = self.ctx._u256s(image_rs)
+        assert len(image_rs) == m.shape[0]
+        spec = (WireRoundSpec * max(1, len(schedule)))(*[WireRoundSpec(int(f), int(b), int(n)) for f, b, n in schedule])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_net_client_run(self.h, wire.h, p(m), p(r), m.shape[0], spec, len(schedule)), "vpin_net_client_run")
+        rounds = [self.values(self.first_round + i) for i in range(len(schedule))]
+        return rounds[-1][1], rounds
 
     def values(self, rnd):
         """(v, act) of round first_round .. first_round + n_rounds - 1 as int64 arrays"""

@@ -209,6 +209,26 @@ def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
     return inference.infer(run, ctx, cfg, client, image, image_rs, keys, bias_rs)
 
 
+def schedule(cfg):
+    """what the client of `cfg` agrees to: per round (flags, shift_bits, cnt) from the layers' rounds and vpin_net_cfg_counts.  The
+    client holds its own copy and answers no round that differs (Client.run)"""
+    per = cfg.counts()["per_round"]
+    rounds = [l for l in cfg.layers if l.has_round]
+    return [((RELU if l.relu else 0) | (REENCRYPT if l.reencrypt else 0), int(l.shift_bits), int(n)) for l, n in zip(rounds, per)]
+
+
+def serve(ctx, cfg, wire, keys, bias_rs):
+    """vpin_net_serve -> Trace: the server's endpoint over a vpin_amd.wire.Wire.  Reads the client's public key and encrypted input
+    off the wire, runs the layers with every round sent to the peer, sends DONE; a failure goes to the peer as ERROR and is raised"""
+    k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
+    r = ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
+    h = C.c_void_p()
+    cfg_c = cfg.c
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _chk(lib().vpin_net_serve(ctx.h, C.byref(cfg_c), wire.h, p(k), len(keys), p(r), len(bias_rs), C.byref(h)), "vpin_net_serve")
+    return Trace(ctx, h)
+
+
 def write_witness_files(trace, root, label):
     """the 8 JSON files the CLI reads for the network's one label, under root/rust_files/<label>"""
     from . import enc_conv
