@@ -1,5 +1,5 @@
 // e2_client.h -- the client side of vPIN's exponential ElGamal on E2, device stages (e2_client.hip) as the entry points of
-// e2_client.cpp drive them.  Every stage validates its points on the device (EncConvDev::load: range and curve equation),
+// e2_client.cpp drive them.  Every stage validates its points on the device (E2Points::load: range and curve equation),
 // works on the context's stream and synchronises it before it returns.
 #pragma once
 #include <cstddef>
@@ -31,7 +31,7 @@ constexpr int kDefaultWindow = 10;  // measured against 4, 6, 8 and 12: DESIGN.m
 // the walk gives a point up to this many lanes: lane l visits the giant steps l, l + L, l + 2 L, .. (strides of L * D)
 constexpr int kDlogLanes = 64;
 
-// x, y: the base point, canonical little-endian.  VPIN_EINVAL (through enc::check_flags) when it is not on the curve
+// x, y: the base point, canonical little-endian.  VPIN_EINVAL (E2Points::load) when it is not on the curve
 int base_build(vpin_ctx* c, const uint8_t x[32], const uint8_t y[32], int w, vpin_e2_base** out);
 void base_free(vpin_e2_base* b);
 // out[i] = s_i * B (scalars: cnt x 32 bytes little-endian, already checked to be below the group order)

@@ -15,7 +15,8 @@
 //                          is that one inversion, so a walk is as long as its deepest lane)
 //   e2_act_kernel          the client's activation between the walk and the next encryption: ReLU and the reference's
 //                          `shifting`, which goes through float32, one lane per element
-// e2_to_affine_kernel (enc_conv.hip) normalises every output and the baby steps.  As in the layers' kernels the accumulators
+// Points come in through E2Points::load and results go out through E2Affine / e2_emit (enc_conv.h): e2_to_affine_kernel
+// normalises every output and the baby steps.  As in the layers' kernels the accumulators
 // are named registers: no per-lane arrays.
 #include "e2_dev.h"
 #include "e2_client.h"
@@ -23,8 +24,6 @@
 
 #include <cstring>
 #include <new>
-
-#include "host/field.h"
 
 namespace vpin {
 
@@ -265,35 +264,11 @@ __global__ __launch_bounds__(kE2Block) void e2_act_kernel(const long long* __res
   bad[i] = b;
 }
 
-using vpin_host::Fq;
-
-fq to_fq(const uint8_t* le32) {
-  Fq t;
-  memcpy(t.l, le32, 32);
-  t = t * Fq::r2();
-  fq r;
-  memcpy(r.v, t.l, 32);
-  return r;
-}
-
 // the generator G of E2, canonical little-endian
 const uint8_t kGx[32] = {0x74, 0xa7, 0xeb, 0x7c, 0x9d, 0xce, 0x1e, 0x21, 0x93, 0x6a, 0x35, 0x97, 0x79, 0x50, 0x40, 0x24,
                          0x72, 0x67, 0xcd, 0xa5, 0x3c, 0xba, 0x65, 0xf5, 0x70, 0xab, 0xb3, 0x3b, 0x6b, 0xfd, 0x15, 0x0a};
 const uint8_t kGy[32] = {0x96, 0xbb, 0x87, 0x62, 0x3d, 0xaf, 0x8a, 0x1f, 0xbe, 0xfd, 0x07, 0xa8, 0x82, 0x88, 0x01, 0x59,
                          0xc5, 0x7c, 0x0a, 0x85, 0x5b, 0x90, 0x8f, 0xb3, 0x7f, 0x29, 0x12, 0x66, 0xc7, 0x32, 0x83, 0x01};
-
-// Jacobian points -> canonical bytes on the host; synchronises
-int emit(vpin_ctx* c, const e2_jac* jac, size_t n, uint8_t* ox, uint8_t* oy, uint8_t* oinf) {
-  DevBuf mx(c), my(c), cx(c), cy(c), fl(c);
-  if (mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || fl.alloc(n)) return VPIN_ENOMEM;
-  const int rc = e2_to_affine(c, jac, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
-  if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(ox, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(oy, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(oinf, fl.p, n, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
-}
 
 int launch_base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint32_t* d_s, const uint8_t* d_neg, size_t n, e2_jac* out) {
   hipLaunchKernelGGL(e2_base_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)b->tx, (const fq*)b->ty, b->w,
@@ -350,12 +325,10 @@ int base_build(vpin_ctx* c, const uint8_t x[32], const uint8_t y[32], int w, vpi
   (void)hipSetDevice(c->device);
   const uint8_t* bx = x ? x : kGx;
   const uint8_t* by = x ? y : kGy;
-  EncConvDev d(c);  // the range and curve checks of every loaded point
-  uint32_t flags = 0;
+  E2Points base(c);  // the range and curve checks of every loaded point
   const uint8_t not_inf = 0;
-  int rc = d.load(bx, by, &not_inf, 1, &flags);
+  int rc = base.load(c, bx, by, &not_inf, 1, "vpin_e2_base_create", "base point");
   if (rc) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_base_create", "base point"))) return rc;
   vpin_e2_base* b = new (std::nothrow) vpin_e2_base();
   if (!b) return VPIN_ENOMEM;
   b->owner = c;
@@ -368,7 +341,7 @@ int base_build(vpin_ctx* c, const uint8_t x[32], const uint8_t y[32], int w, vpi
     base_free(b);
     return VPIN_ENOMEM;
   }
-  hipLaunchKernelGGL(e2_base_rows_kernel, dim3(1), dim3(64), 0, c->stream, to_fq(bx), to_fq(by), w, b->nwin, e2_curve_a(), (e2_jac*)jac.p);
+  hipLaunchKernelGGL(e2_base_rows_kernel, dim3(1), dim3(64), 0, c->stream, fq_of_le32(bx), fq_of_le32(by), w, b->nwin, e2_curve_a(), (e2_jac*)jac.p);
   rc = hipGetLastError() == hipSuccess ? VPIN_OK : VPIN_EHIP;
   // no entry is the identity: the group order is prime and d * 2^(w k) is not a multiple of it
   if (!rc) rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)b->tx, (fq*)b->ty, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
@@ -388,15 +361,16 @@ int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, si
   VPIN_HIP_TRY(hipMemcpyAsync(s.p, scalars_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
   const int rc = launch_base_mul(c, b, (const uint32_t*)s.p, nullptr, cnt, (e2_jac*)jac.p);
   if (rc) return rc;
-  return emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
+  return e2_emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
 }
 
 // The device side of an encryption over cnt elements whose r (cnt x 32 bytes), message magnitudes (cnt x 32 bytes) and sign bytes
 // are resident: the three fixed-base multiplications, the last addition, one normalisation of c1 | c2 and the copies of the
 // canonical bytes to the host.  Not synchronised; the buffers live until the caller has synchronised
 struct EncryptChain {
-  DevBuf ct, rh, mg, mx, my, cx, cy, fl;  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
-  explicit EncryptChain(vpin_ctx* c) : ct(c), rh(c), mg(c), mx(c), my(c), cx(c), cy(c), fl(c) {}
+  DevBuf ct, rh, mg;  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
+  E2Affine aff;
+  explicit EncryptChain(vpin_ctx* c) : ct(c), rh(c), mg(c), aff(c) {}
   int run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const void* d_r, const void* d_m, const void* d_neg, size_t cnt,
           uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
 };
@@ -427,21 +401,15 @@ int EncryptChain::run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h,
   hipLaunchKernelGGL(e2_add_pairs_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)mg.p, (const e2_jac*)rh.p,
                      cnt, e2_curve_a(), c1 + cnt);
   VPIN_HIP_TRY(hipGetLastError());
-  if (mx.alloc(2 * cnt * 32) || my.alloc(2 * cnt * 32) || cx.alloc(2 * cnt * 32) || cy.alloc(2 * cnt * 32) || fl.alloc(2 * cnt)) return VPIN_ENOMEM;
-  if ((rc = e2_to_affine(c, c1, 2 * cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(c1x, cx.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c1y, cy.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c1inf, fl.p, cnt, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c2x, (const uint8_t*)cx.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c2y, (const uint8_t*)cy.p + cnt * 32, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c2inf, (const uint8_t*)fl.p + cnt, cnt, hipMemcpyDeviceToHost, c->stream));
-  return VPIN_OK;
+  if ((rc = aff.normalise(c, c1, 2 * cnt))) return rc;
+  if ((rc = aff.copy_out(c, 0, cnt, c1x, c1y, c1inf))) return rc;
+  return aff.copy_out(c, cnt, cnt, c2x, c2y, c2inf);
 }
 
-// T_i = s * P_i over the points loaded in d, Jacobian, not synchronised
-static int launch_mul256(vpin_ctx* c, const EncConvDev& d, const uint32_t* d_s, bool one_scalar, size_t cnt, e2_jac* out) {
-  hipLaunchKernelGGL(e2_mul256_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)d.px.p, (const fq*)d.py.p,
-                     (const uint8_t*)d.pinf.p, d_s, (size_t)(one_scalar ? 0 : 8), cnt, e2_curve_a(), out);
+// T_i = s * P_i over the loaded points, Jacobian, not synchronised
+static int launch_mul256(vpin_ctx* c, const E2Points& pts, const uint32_t* d_s, bool one_scalar, size_t cnt, e2_jac* out) {
+  hipLaunchKernelGGL(e2_mul256_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, pts.X(), pts.Y(), pts.F(), d_s,
+                     (size_t)(one_scalar ? 0 : 8), cnt, e2_curve_a(), out);
   VPIN_HIP_TRY(hipGetLastError());
   return VPIN_OK;
 }
@@ -449,17 +417,15 @@ static int launch_mul256(vpin_ctx* c, const EncConvDev& d, const uint32_t* d_s, 
 int mul256(vpin_ctx* c, const uint8_t* scalars_le32, bool one_scalar, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
            uint8_t* ox, uint8_t* oy, uint8_t* oinf) {
   (void)hipSetDevice(c->device);
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, cnt, &flags);
+  E2Points pts(c);
+  int rc = pts.load(c, px, py, pinf, cnt, "vpin_e2_mul256", "point");
   if (rc) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_mul256", "point"))) return rc;
   const size_t ns = one_scalar ? 1 : cnt;
   DevBuf s(c), jac(c);
   if (s.alloc(ns * 32) || jac.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(s.p, scalars_le32, ns * 32, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_mul256(c, d, (const uint32_t*)s.p, one_scalar, cnt, (e2_jac*)jac.p))) return rc;
-  return emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
+  if ((rc = launch_mul256(c, pts, (const uint32_t*)s.p, one_scalar, cnt, (e2_jac*)jac.p))) return rc;
+  return e2_emit(c, (const e2_jac*)jac.p, cnt, ox, oy, oinf);
 }
 
 void dlog_free(vpin_e2_dlog* t) {
@@ -499,7 +465,7 @@ int dlog_build(vpin_ctx* c, uint64_t nb, vpin_e2_dlog** out) {
   }
   VPIN_HIP_TRY(hipMemsetAsync(t->idx, 0, t->slots * 8, c->stream));
   VPIN_HIP_TRY(hipMemsetAsync(t->par, 0, nb, c->stream));
-  const fq a = e2_curve_a(), gx = to_fq(kGx), gy = to_fq(kGy);
+  const fq a = e2_curve_a(), gx = fq_of_le32(kGx), gy = fq_of_le32(kGy);
   for (uint64_t j0 = 0; j0 < nb; j0 += tile) {
     const size_t count = (size_t)(nb - j0 < tile ? nb - j0 : tile), lanes = (count + kStepsChunk - 1) / kStepsChunk;
     hipLaunchKernelGGL(e2_dlog_steps_kernel, dim3(blocks_of(lanes, kStepsBlock)), dim3(kStepsBlock), 0, c->stream, (const fq*)g->tx,
@@ -528,37 +494,31 @@ int dlog_build(vpin_ctx* c, uint64_t nb, vpin_e2_dlog** out) {
 int dlog_solve(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt, uint64_t max_giant,
                int64_t* v_out, uint8_t* found_out) {
   (void)hipSetDevice(c->device);
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, cnt, &flags);
+  E2Points pts(c);
+  const int rc = pts.load(c, px, py, pinf, cnt, "vpin_e2_dlog_solve", "point");
   if (rc) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_dlog_solve", "point"))) return rc;
-  return run_walk(c, t, (const fq*)d.px.p, (const fq*)d.py.p, (const uint8_t*)d.pinf.p, cnt, max_giant, v_out, found_out);
+  return run_walk(c, t, pts.X(), pts.Y(), pts.F(), cnt, max_giant, v_out, found_out);
 }
 
 // The device side of a decryption up to the walk's input: the two ciphertext halves through the range and curve checks (who: the
-// entry point the rejection names), T = sk * c1, M = c2 - T normalised into mx / my / fl.  Not synchronised past the checks
+// entry point the rejection names), T = sk * c1, M = c2 - T normalised into m.  Not synchronised past the checks
 struct DecryptChain {
-  EncConvDev d1, d2;
-  DevBuf s, T, M, mx, my, cx, cy, fl;
-  explicit DecryptChain(vpin_ctx* c) : d1(c), d2(c), s(c), T(c), M(c), mx(c), my(c), cx(c), cy(c), fl(c) {}
+  E2Points c1, c2, m;
+  DevBuf s, T, M;
+  E2Affine aff;
+  explicit DecryptChain(vpin_ctx* c) : c1(c), c2(c), m(c), s(c), T(c), M(c), aff(c) {}
   int run(vpin_ctx* c, const char* who, const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt) {
-    uint32_t flags = 0;
-    int rc = d1.load(c1x, c1y, c1inf, cnt, &flags);
+    int rc = c1.load(c, c1x, c1y, c1inf, cnt, who, "c1 point");
+    if (!rc) rc = c2.load(c, c2x, c2y, c2inf, cnt, who, "c2 point");
     if (rc) return rc;
-    if ((rc = enc::check_flags(flags, who, "c1 point"))) return rc;
-    if ((rc = d2.load(c2x, c2y, c2inf, cnt, &flags))) return rc;
-    if ((rc = enc::check_flags(flags, who, "c2 point"))) return rc;
-    if (s.alloc(32) || T.alloc(cnt * sizeof(e2_jac)) || M.alloc(cnt * sizeof(e2_jac)) || mx.alloc(cnt * 32) || my.alloc(cnt * 32) ||
-        cx.alloc(cnt * 32) || cy.alloc(cnt * 32) || fl.alloc(cnt))
-      return VPIN_ENOMEM;
+    if (s.alloc(32) || T.alloc(cnt * sizeof(e2_jac)) || M.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
     VPIN_HIP_TRY(hipMemcpyAsync(s.p, sk_le32, 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_mul256(c, d1, (const uint32_t*)s.p, true, cnt, (e2_jac*)T.p))) return rc;
-    hipLaunchKernelGGL(e2_sub_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)T.p, (const fq*)d2.px.p,
-                       (const fq*)d2.py.p, (const uint8_t*)d2.pinf.p, cnt, e2_curve_a(), (e2_jac*)M.p);
+    if ((rc = launch_mul256(c, c1, (const uint32_t*)s.p, true, cnt, (e2_jac*)T.p))) return rc;
+    hipLaunchKernelGGL(e2_sub_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)T.p, c2.X(), c2.Y(), c2.F(),
+                       cnt, e2_curve_a(), (e2_jac*)M.p);
     VPIN_HIP_TRY(hipGetLastError());
-    return e2_to_affine(c, (const e2_jac*)M.p, cnt, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p);
+    return aff.normalise(c, (const e2_jac*)M.p, cnt, &m);
   }
 };
 
@@ -569,7 +529,7 @@ int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const
   DecryptChain d(c);
   const int rc = d.run(c, "vpin_e2_decrypt", sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
   if (rc) return rc;
-  return run_walk(c, t, (const fq*)d.mx.p, (const fq*)d.my.p, (const uint8_t*)d.fl.p, cnt, max_giant, v_out, found_out);
+  return run_walk(c, t, d.m.X(), d.m.Y(), d.m.F(), cnt, max_giant, v_out, found_out);
 }
 
 int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
@@ -585,7 +545,7 @@ int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_
   }
   DecryptChain d(c);
   int rc = d.run(c, "vpin_e2_client_round", sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
-  if (!rc) rc = launch_walk(c, t, (const fq*)d.mx.p, (const fq*)d.my.p, (const uint8_t*)d.fl.p, cnt, max_giant, v.p, f.p);
+  if (!rc) rc = launch_walk(c, t, d.m.X(), d.m.Y(), d.m.F(), cnt, max_giant, v.p, f.p);
   if (rc) return rc;
   hipLaunchKernelGGL(e2_act_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const long long*)v.p, (const uint8_t*)f.p, cnt,
                      relu ? 1 : 0, shift_bits, (uint32_t*)m.p, (uint8_t*)ng.p, (long long*)act.p, (uint8_t*)bad.p);

@@ -13,10 +13,7 @@
 #include "enc_conv.h"
 
 #include <cstdio>
-#include <cstring>
 #include <vector>
-
-#include "host/field.h"
 
 namespace vpin {
 
@@ -89,17 +86,6 @@ __global__ __launch_bounds__(kE2Block) void e2_unpack_kernel(const fq* __restric
   bad[i] = f;
 }
 
-using vpin_host::Fq;
-
-fq wire_fq(const uint8_t* le32) {
-  Fq t;
-  memcpy(t.l, le32, 32);
-  t = t * Fq::r2();
-  fq r;
-  memcpy(r.v, t.l, 32);
-  return r;
-}
-
 // the coefficient b of E2, canonical little-endian
 const uint8_t kBBytes[32] = {86, 83, 202, 68, 110, 236, 64, 249, 56, 118, 236, 1, 191, 143, 126, 100,
                              4, 149, 41, 137, 111, 171, 93, 146, 250, 112, 171, 90, 44, 184, 8, 8};
@@ -143,7 +129,7 @@ int vpin_e2_pack(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_
   VPIN_HIP_TRY(hipMemcpyAsync(y.p, py, cnt * 32, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(f.p, pinf, cnt, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(e2_pack_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)x.p, (const fq*)y.p,
-                     (const uint8_t*)f.p, cnt, e2_curve_a(), wire_fq(kBBytes), (fq*)o.p, (uint8_t*)b.p);
+                     (const uint8_t*)f.p, cnt, e2_curve_a(), fq_of_le32(kBBytes), (fq*)o.p, (uint8_t*)b.p);
   VPIN_HIP_TRY(hipGetLastError());
   VPIN_HIP_TRY(hipMemcpyAsync(out32, o.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(bad.data(), b.p, cnt, hipMemcpyDeviceToHost, c->stream));
@@ -160,7 +146,7 @@ int vpin_e2_unpack(vpin_ctx* c, const uint8_t* in32, size_t cnt, uint8_t* px, ui
   std::vector<uint8_t> bad(cnt);
   VPIN_HIP_TRY(hipMemcpyAsync(in.p, in32, cnt * 32, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(e2_unpack_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)in.p, cnt, e2_curve_a(),
-                     wire_fq(kBBytes), (fq*)x.p, (fq*)y.p, (uint8_t*)f.p, (uint8_t*)b.p);
+                     fq_of_le32(kBBytes), (fq*)x.p, (fq*)y.p, (uint8_t*)f.p, (uint8_t*)b.p);
   VPIN_HIP_TRY(hipGetLastError());
   VPIN_HIP_TRY(hipMemcpyAsync(px, x.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(py, y.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));

@@ -4,13 +4,15 @@
 // point-mult / point-add gadgets prove them.  The convolution itself and the f^2 + 1 sums of the check run on the device
 // (enc_conv.hip).  Restates the type-1 path of the reference's convolution service (src/convolution/Server.py,
 // src/LeNet/Server.py: myConv2d, rLCL, rLCR).  The E2 host code, the PRF and the trace accessors here also serve the fully
-// connected and pooling layers (enc_fc.cpp) through namespace vpin::enc of enc_conv.h.
+// connected and pooling layers (enc_fc.cpp) and the trained convolution (enc_convmc.cpp) through namespace vpin::enc of
+// enc_conv.h, as do the frame of a layer driver (reset_timings, prf_rows) and the tail that writes one chain (emit_chain).
 #include <omp.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -95,8 +97,6 @@ static Aff aff_mul(u128 w, const Aff& p) {
   return to_affine(acc);
 }
 
-bool aff_eq(const Aff& p, const Aff& q) { return p.inf == q.inf && (p.inf || (p.x == q.x && p.y == q.y)); }
-
 Aff aff_from_bytes(const uint8_t* x, const uint8_t* y, uint8_t inf) {
   Aff r;
   if (inf) return r;
@@ -126,7 +126,7 @@ static void hmac_sha256_key32(const uint8_t key[32], const uint8_t* msg, size_t 
 }
 
 // r_t = int.from_bytes(HMAC(key, ascii_decimal(t))[:prf_bytes], "big") as a little-endian u128
-void prf_scalar(const uint8_t key[32], size_t t, int prf_bytes, uint8_t out_le16[16]) {
+static void prf_scalar(const uint8_t key[32], size_t t, int prf_bytes, uint8_t out_le16[16]) {
   char msg[32];
   const int n = snprintf(msg, sizeof(msg), "%zu", t);
   uint8_t mac[32];
@@ -153,12 +153,6 @@ int make_geom(size_t P, size_t H, size_t W, size_t fh, size_t fw, size_t pad, si
   return VPIN_OK;
 }
 
-int check_flags(uint32_t flags, const char* who, const char* what) {
-  if (flags & vpin::kE2FlagRange) return fail(VPIN_EINVAL, (std::string(who) + ": a coordinate is not below q").c_str());
-  if (flags & vpin::kE2FlagOffCurve) return fail(VPIN_EINVAL, (std::string(who) + ": a " + what + " is not on the curve E2").c_str());
-  return VPIN_OK;
-}
-
 Jac jac_from_bytes(const uint8_t* p) {
   Jac r;
   memcpy(r.X.l, p, 32); memcpy(r.Y.l, p + 32, 32); memcpy(r.Z.l, p + 64, 32);
@@ -167,7 +161,31 @@ Jac jac_from_bytes(const uint8_t* p) {
 
 static thread_local double g_timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-double* last_timings() { return g_timings; }
+double* reset_timings() {
+  for (double& v : g_timings) v = 0.0;
+  return g_timings;
+}
+
+std::vector<uint8_t> prf_rows(const uint8_t* keys32, size_t rows, size_t per_row, int prf_bytes) {
+  std::vector<uint8_t> r(rows * per_row * 16);
+#pragma omp parallel for schedule(static) num_threads(team_size())
+  for (long i = 0; i < (long)(rows * per_row); i++)
+    prf_scalar(keys32 + 32 * ((size_t)i / per_row), (size_t)i % per_row, prf_bytes, &r[16 * (size_t)i]);
+  return r;
+}
+
+int emit_chain(const char* who, vpin_conv_trace* t, size_t* ai, PointBytes prod, PointBytes prefix, size_t len, PointBytes left, bool* closes) {
+  for (size_t k = 1; k < len; k++, ++*ai) {
+    if (prefix.inf[k - 1])
+      return fail(VPIN_ESHAPE, (std::string(who) + ": an addition accumulator is the identity (the witness format has no flag for it)").c_str());
+    memcpy(&t->a_px[32 * *ai], prefix.x + 32 * (k - 1), 32); memcpy(&t->a_py[32 * *ai], prefix.y + 32 * (k - 1), 32);
+    memcpy(&t->a_rx[32 * *ai], prod.x + 32 * k, 32); memcpy(&t->a_ry[32 * *ai], prod.y + 32 * k, 32);
+    t->a_rz[*ai] = prod.inf[k];
+  }
+  const PointBytes last = prefix.at(len - 1);  // both sides are canonical, the identity zeros
+  *closes = *last.inf == *left.inf && !memcmp(last.x, left.x, 32) && !memcmp(last.y, left.y, 32);
+  return VPIN_OK;
+}
 
 int team_size() { return (int)std::max(1.0, std::min(16.0, vpin::host_cpu_quota())); }
 
@@ -183,10 +201,8 @@ int vpin_e2_msm(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* px, con
   if (!c || !scalars_le16 || !px || !py || !pinf || !out_x || !out_y || !out_inf) return fail(VPIN_EINVAL, "vpin_e2_msm: null argument");
   if (n == 0 || n >= ((size_t)1 << 31)) return fail(VPIN_EINVAL, "vpin_e2_msm: n must be in 1 .. 2^31 - 1");
   EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, n, &flags);
+  int rc = d.in.load(c, px, py, pinf, n);
   if (rc) return rc;
-  if ((rc = check_flags(flags))) return rc;
   uint8_t sum[96];
   if ((rc = d.msm(scalars_le16, n, sum))) return rc;
   const Aff r = to_affine(jac_from_bytes(sum));
@@ -203,9 +219,7 @@ int vpin_e2_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint
   int rc = make_geom(1, H, W, fh, fw, pad, stride, &g);
   if (rc) return rc;
   EncConvDev d(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags))) return rc;
+  if ((rc = d.in.load(c, px, py, pinf, g.pixels()))) return rc;
   return d.conv(g, filter_le16, out_x, out_y, out_inf);
 }
 
@@ -218,39 +232,33 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
   ConvGeom g;
   int rc = make_geom(P, H, W, fh, fw, pad, stride, &g);
   if (rc) return rc;
-  for (double& v : g_timings) v = 0.0;
+  double* tm = reset_timings();
   Lap total, lap;
-  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  std::unique_ptr<vpin_conv_trace> t(new (std::nothrow) vpin_conv_trace());
   if (!t) return VPIN_ENOMEM;
-  struct Guard { vpin_conv_trace* t; ~Guard() { delete t; } } guard{t};
   const size_t taps = g.taps(), nsum = taps + 1, per_plane = g.oh * g.ow, n_out = g.outputs();
   t->P = P; t->oh = g.oh; t->ow = g.ow;
 
   // validate: upload, range and curve checks on the device
   EncConvDev d(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags))) return rc;
-  g_timings[0] = lap();
+  if ((rc = d.in.load(c, px, py, pinf, g.pixels()))) return rc;
+  tm[0] = lap();
 
   // the convolution
   t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
   if ((rc = d.conv(g, filter_le16, t->out_x.data(), t->out_y.data(), t->out_inf.data()))) return rc;
-  g_timings[1] = lap();
+  tm[1] = lap();
 
   // the PRF scalars: the index restarts at 0 for every plane
-  std::vector<uint8_t> r(n_out * 16);
-#pragma omp parallel for schedule(static) num_threads(team_size())
-  for (long i = 0; i < (long)n_out; i++)
-    prf_scalar(keys32 + 32 * ((size_t)i / per_plane), (size_t)i % per_plane, prf_bytes, &r[16 * (size_t)i]);
-  g_timings[2] = lap();
+  const std::vector<uint8_t> r = prf_rows(keys32, P, per_plane, prf_bytes);
+  tm[2] = lap();
 
   // the f^2 + 1 sums of every plane
   std::vector<uint8_t> sums(P * nsum * 96);
   if ((rc = d.rlc(r.data(), sums.data()))) return rc;
-  g_timings[3] = lap();
+  tm[3] = lap();
 
-  // host tail: T_k = w[k] * B'[k], the chain of additions, the equation, the two lists
+  // host tail: T_k = w[k] * B'[k] on the team, the prefixes of every plane's chain, the two lists, the equation
   std::vector<Aff> B(P * nsum), T(P * taps);
   std::vector<u128> w(taps);
   for (size_t k = 0; k < taps; k++) memcpy(&w[k], filter_le16 + 16 * k, 16);
@@ -268,32 +276,34 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
   t->n_add = P * (taps - 1);
   t->resize_lists();
   t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
+  std::vector<uint8_t> tx(taps * 32), ty(taps * 32), tinf(taps), ax(taps * 32), ay(taps * 32), ainf(taps);  // one plane's chain
+  const PointBytes prod{tx.data(), ty.data(), tinf.data()}, prefix{ax.data(), ay.data(), ainf.data()};
+  const PointBytes left{t->left_x.data(), t->left_y.data(), t->left_inf.data()};
   bool equal = true;
+  size_t ai = 0;
   for (size_t p = 0; p < P; p++) {
     Aff acc;
     for (size_t k = 0; k < taps; k++) {
       const size_t m = p * taps + k;
       memcpy(&t->m_w[16 * m], filter_le16 + 16 * k, 16);
       put_point(B[p * nsum + k], &t->m_px[32 * m], &t->m_py[32 * m]);
-      const Aff& Tk = T[m];
-      if (k == 0) { acc = Tk; continue; }
-      if (acc.inf) return fail(VPIN_ESHAPE, "vpin_enc_conv2d: an addition accumulator is the identity (the witness format has no flag for it)");
-      const size_t ai = p * (taps - 1) + (k - 1);
-      put_point(acc, &t->a_px[32 * ai], &t->a_py[32 * ai]);
-      put_point(Tk, &t->a_rx[32 * ai], &t->a_ry[32 * ai]);
-      t->a_rz[ai] = Tk.inf ? 1 : 0;
-      acc = aff_add(acc, Tk);
+      acc = aff_add(acc, T[m]);  // complete: an identity prefix is emit_chain's to reject
+      put_point(T[m], &tx[32 * k], &ty[32 * k]);
+      tinf[k] = T[m].inf ? 1 : 0;
+      put_point(acc, &ax[32 * k], &ay[32 * k]);
+      ainf[k] = acc.inf ? 1 : 0;
     }
-    const Aff& left = B[p * nsum + taps];
-    put_point(left, &t->left_x[32 * p], &t->left_y[32 * p]);
-    t->left_inf[p] = left.inf ? 1 : 0;
-    if (!aff_eq(acc, left)) equal = false;
+    const Aff& l = B[p * nsum + taps];
+    put_point(l, &t->left_x[32 * p], &t->left_y[32 * p]);
+    t->left_inf[p] = l.inf ? 1 : 0;
+    bool closes = false;
+    if ((rc = emit_chain("vpin_enc_conv2d", t.get(), &ai, prod, prefix, taps, left.at(p), &closes))) return rc;
+    if (!closes) equal = false;
   }
-  g_timings[4] = lap();
-  g_timings[5] = total();
+  tm[4] = lap();
+  tm[5] = total();
   if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_conv2d: the two sides of the random linear combination differ");
-  guard.t = nullptr;
-  *out = t;
+  *out = t.release();
   return VPIN_OK;
 }
 

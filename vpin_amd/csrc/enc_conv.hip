@@ -9,12 +9,15 @@
 //   e2_rlc_kernel        one lane per (sum, term): 128-step double-and-add of r_t times the term's point (mixed addition:
 //                        window pixels and normalised outputs are affine), then an LDS tree with the complete addition
 //   e2_reduce_kernel     the second launch: one workgroup per sum over the partials of the first
+// Also the plumbing every E2 stage of the library uses (enc_conv.h): E2Points::load around e2_load_kernel, and E2Affine /
+// e2_emit around e2_to_affine_kernel, the one place where normalised points are copied to the host.
 // Exactness: every addition is complete by case (e2_dev.h), so repeated pixels, P / -P pairs and identities are summed
 // correctly.  The accumulators are named registers (e2_jac locals, the scalar as four shifted words): no per-lane arrays.
 #include "e2_dev.h"
 #include "enc_conv.h"
 
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "host/field.h"
@@ -157,15 +160,6 @@ __global__ __launch_bounds__(kE2Block) void e2_reduce_kernel(const e2_jac* __res
 
 using vpin_host::Fq;
 
-fq fq_of_le32(const uint8_t* b) {
-  Fq t;
-  memcpy(t.l, b, 32);
-  t = t * Fq::r2();
-  fq r;
-  memcpy(r.v, t.l, 32);
-  return r;
-}
-
 // the curve coefficient b of E2, little-endian (a: host/gadget_ops.h kAPdBytes)
 const uint8_t kE2BBytes[32] = {86, 83, 202, 68, 110, 236, 64, 249, 56, 118, 236, 1, 191, 143, 126, 100,
                                4, 149, 41, 137, 111, 171, 93, 146, 250, 112, 171, 90, 44, 184, 8, 8};
@@ -195,6 +189,15 @@ E2Geom e2_geom(const ConvGeom& g) {
   return E2Geom{(int)g.H, (int)g.W, (int)g.fh, (int)g.fw, (int)g.pad, (int)g.stride, (int)g.oh, (int)g.ow};
 }
 
+fq fq_of_le32(const uint8_t* le32) {
+  Fq t;
+  memcpy(t.l, le32, 32);
+  t = t * Fq::r2();
+  fq r;
+  memcpy(r.v, t.l, 32);
+  return r;
+}
+
 fq e2_curve_a() { return fq_of_le32(vpin_gadgets::kAPdBytes); }
 
 int e2_to_affine(vpin_ctx* c, const e2_jac* in, size_t n, fq* mx, fq* my, fq* cx, fq* cy, uint8_t* oinf) {
@@ -209,22 +212,59 @@ int e2_reduce(vpin_ctx* c, const e2_jac* parts, size_t n_sums, size_t n_parts, e
   return VPIN_OK;
 }
 
-int EncConvDev::load(const uint8_t* x, const uint8_t* y, const uint8_t* inf, size_t n, uint32_t* flags) {
+int E2Points::resize(size_t count) {
+  n = count;
+  VPIN_EC_ALLOC(x, n * 32);
+  VPIN_EC_ALLOC(y, n * 32);
+  VPIN_EC_ALLOC(inf, n);
+  return VPIN_OK;
+}
+
+int E2Points::load(vpin_ctx* c, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, size_t count, const char* who, const char* what) {
   (void)hipSetDevice(c->device);
   DevBuf rx(c), ry(c), fl(c);
-  if (rx.alloc(n * 32) || ry.alloc(n * 32) || fl.alloc(16)) return VPIN_ENOMEM;
-  VPIN_EC_ALLOC(px, n * 32);
-  VPIN_EC_ALLOC(py, n * 32);
-  VPIN_EC_ALLOC(pinf, n);
-  VPIN_HIP_TRY(hipMemcpyAsync(rx.p, x, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(ry.p, y, n * 32, hipMemcpyHostToDevice, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(pinf.p, inf, n, hipMemcpyHostToDevice, c->stream));
+  if (rx.alloc(count * 32) || ry.alloc(count * 32) || fl.alloc(16)) return VPIN_ENOMEM;
+  const int rc = resize(count);
+  if (rc) return rc;
+  uint32_t flags = 0;
+  VPIN_HIP_TRY(hipMemcpyAsync(rx.p, bx, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(ry.p, by, n * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(inf.p, binf, n, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemsetAsync(fl.p, 0, 4, c->stream));
-  hipLaunchKernelGGL(e2_load_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)rx.p, (const fq*)ry.p,
-                     (const uint8_t*)pinf.p, n, e2_curve_a(), fq_of_le32(kE2BBytes), (fq*)px.p, (fq*)py.p,
-                     (uint32_t*)fl.p);
+  hipLaunchKernelGGL(e2_load_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)rx.p, (const fq*)ry.p, F(), n,
+                     e2_curve_a(), fq_of_le32(kE2BBytes), (fq*)x.p, (fq*)y.p, (uint32_t*)fl.p);
   VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(flags, fl.p, 4, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(&flags, fl.p, 4, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (flags & kE2FlagRange) return enc::fail(VPIN_EINVAL, (std::string(who) + ": a coordinate is not below q").c_str());
+  if (flags & kE2FlagOffCurve) return enc::fail(VPIN_EINVAL, (std::string(who) + ": a " + what + " is not on the curve E2").c_str());
+  return VPIN_OK;
+}
+
+int E2Affine::normalise(vpin_ctx* c, const e2_jac* jac, size_t n, E2Points* keep) {
+  if (cx.alloc(n * 32) || cy.alloc(n * 32)) return VPIN_ENOMEM;
+  if (keep) {
+    const int rc = keep->resize(n);
+    if (rc) return rc;
+  } else if (mx.alloc(n * 32) || my.alloc(n * 32) || fl.alloc(n)) {
+    return VPIN_ENOMEM;
+  }
+  flags = keep ? keep->F() : (const uint8_t*)fl.p;
+  return e2_to_affine(c, jac, n, (fq*)(keep ? keep->x.p : mx.p), (fq*)(keep ? keep->y.p : my.p), (fq*)cx.p, (fq*)cy.p, (uint8_t*)flags);
+}
+
+int E2Affine::copy_out(vpin_ctx* c, size_t first, size_t count, uint8_t* ox, uint8_t* oy, uint8_t* oinf) const {
+  VPIN_HIP_TRY(hipMemcpyAsync(ox, (const uint8_t*)cx.p + first * 32, count * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(oy, (const uint8_t*)cy.p + first * 32, count * 32, hipMemcpyDeviceToHost, c->stream));
+  if (oinf) VPIN_HIP_TRY(hipMemcpyAsync(oinf, flags + first, count, hipMemcpyDeviceToHost, c->stream));
+  return VPIN_OK;
+}
+
+int e2_emit(vpin_ctx* c, const e2_jac* jac, size_t n, uint8_t* ox, uint8_t* oy, uint8_t* oinf, E2Points* keep) {
+  E2Affine aff(c);
+  int rc = aff.normalise(c, jac, n, keep);
+  if (!rc) rc = aff.copy_out(c, 0, n, ox, oy, oinf);
+  if (rc) return rc;
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }
@@ -237,36 +277,24 @@ int EncConvDev::conv(const ConvGeom& geom, const uint8_t* filter_le16, uint8_t* 
   for (size_t k = 0; k < taps; k++)
     for (int b = 127; b > top_bit; b--)
       if ((filter_le16[16 * k + (b >> 3)] >> (b & 7)) & 1) { top_bit = b; break; }
-  DevBuf jac(c), cx(c), cy(c);
-  if (jac.alloc(n_out * sizeof(e2_jac)) || cx.alloc(n_out * 32) || cy.alloc(n_out * 32)) return VPIN_ENOMEM;
-  VPIN_EC_ALLOC(filt, taps * 16);
-  VPIN_EC_ALLOC(ox, n_out * 32);
-  VPIN_EC_ALLOC(oy, n_out * 32);
-  VPIN_EC_ALLOC(oinf, n_out);
+  DevBuf jac(c), filt(c);
+  if (jac.alloc(n_out * sizeof(e2_jac)) || filt.alloc(taps * 16)) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(filt.p, filter_le16, taps * 16, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_conv_kernel, dim3(blocks_of(per_plane, 64), (unsigned)g.P), dim3(64), 0, c->stream, (const fq*)px.p,
-                     (const fq*)py.p, (const uint8_t*)pinf.p, e2_geom(g), (const uint32_t*)filt.p, top_bit,
-                     e2_curve_a(), (e2_jac*)jac.p);
+  hipLaunchKernelGGL(e2_conv_kernel, dim3(blocks_of(per_plane, 64), (unsigned)g.P), dim3(64), 0, c->stream, in.X(), in.Y(), in.F(),
+                     e2_geom(g), (const uint32_t*)filt.p, top_bit, e2_curve_a(), (e2_jac*)jac.p);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n_out, (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p);
-  if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, oinf.p, n_out, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)jac.p, n_out, out_x, out_y, out_inf, &out);
 }
 
 int EncConvDev::rlc(const uint8_t* r_le16, uint8_t* sums_jac) {
   (void)hipSetDevice(c->device);
-  return run_rlc(c, (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, (const fq*)ox.p, (const fq*)oy.p,
-                 (const uint8_t*)oinf.p, g, g.oh * g.ow, r_le16, sums_jac);
+  return run_rlc(c, in.X(), in.Y(), in.F(), out.X(), out.Y(), out.F(), g, g.oh * g.ow, r_le16, sums_jac);
 }
 
 int EncConvDev::msm(const uint8_t* r_le16, size_t n, uint8_t sum_jac[96]) {
   (void)hipSetDevice(c->device);
   ConvGeom one;  // no taps: the single sum runs over the loaded points themselves
-  return run_rlc(c, nullptr, nullptr, nullptr, (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, one, n, r_le16, sum_jac);
+  return run_rlc(c, nullptr, nullptr, nullptr, in.X(), in.Y(), in.F(), one, n, r_le16, sum_jac);
 }
 
 }  // namespace vpin

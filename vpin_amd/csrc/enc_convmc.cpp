@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -19,6 +20,7 @@
 
 using namespace vpin::enc;
 using vpin::ConvGeom;
+using vpin::E2Points;
 using vpin::EncConvDev;
 
 namespace {
@@ -64,11 +66,6 @@ int make_plan(const char* who, size_t groups, size_t C, size_t n_out, size_t H, 
   return VPIN_OK;
 }
 
-struct TraceGuard {
-  vpin_conv_trace* t;
-  ~TraceGuard() { delete t; }
-};
-
 // vpin_enc_conv2d_mc (no bias: bx = by = binf = NULL) and vpin_enc_conv2d_mc_bias.  With a bias the convolution's result is C,
 // the output is C + bias, every pair's additions begin with its oh * ow pairs (C[t], bias), and the check still runs over C
 int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C,
@@ -86,25 +83,19 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
   const size_t taps = g.taps(), per_plane = g.oh * g.ow, n_pairs = groups * n_out, n_o = n_pairs * per_plane, K = p.k_max;
   const size_t n_chain = n_pairs * K, n_sums = n_chain + n_pairs;  // the chains, padded to K terms each, then the left sides
   if (n_sums * ((per_plane + 255) / 256) >= ((size_t)1 << 31)) return failed(VPIN_EINVAL, "a dimension is out of range");
-  double* tm = last_timings();
-  for (int i = 0; i < 8; i++) tm[i] = 0.0;
+  double* tm = reset_timings();
   Lap total, lap;
-  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  std::unique_ptr<vpin_conv_trace> t(new (std::nothrow) vpin_conv_trace());
   if (!t) return VPIN_ENOMEM;
-  TraceGuard guard{t};
   t->P = n_pairs; t->oh = g.oh; t->ow = g.ow;
   t->n_mult = groups * taps * p.pairs;
   t->n_add = t->n_mult - n_pairs + (with_bias ? n_o : 0);
 
   // validate: upload, range and curve checks on the device
-  EncConvDev d(c), tail(c), b(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags, who, "pixel"))) return rc;
-  if (with_bias) {
-    if ((rc = b.load(bx, by, binf, n_pairs, &flags))) return rc;
-    if ((rc = check_flags(flags, who, "bias point"))) return rc;
-  }
+  EncConvDev d(c);
+  E2Points tail(c), b(c);
+  if ((rc = d.in.load(c, px, py, pinf, g.pixels(), who, "pixel"))) return rc;
+  if (with_bias && (rc = b.load(c, bx, by, binf, n_pairs, who, "bias point"))) return rc;
   tm[0] = lap();
 
   // the convolution
@@ -121,10 +112,7 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
   tm[1] = lap();
 
   // the PRF scalars: one key per (g, o), the index restarts at 0 for every pair
-  std::vector<uint8_t> r(n_o * 16);
-#pragma omp parallel for schedule(static) num_threads(team_size())
-  for (long i = 0; i < (long)n_o; i++)
-    prf_scalar(keys32 + 32 * ((size_t)i / per_plane), (size_t)i % per_plane, prf_bytes, &r[16 * (size_t)i]);
+  const std::vector<uint8_t> r = prf_rows(keys32, n_pairs, per_plane, prf_bytes);
   tm[2] = lap();
 
   // the sums: per pair q = (g, o) its terms m = (c, k) over the connected c ascending, padded to K; then the left sides.  The
@@ -157,41 +145,34 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
       if (sinf[q * K + m])
         return failed(VPIN_ESHAPE, "a multiplication operand B'[c][k] is the identity (the witness format has no flag for it)");
   std::vector<uint8_t> tx(n_chain * 32), ty(n_chain * 32), tinf(n_chain), ax(n_chain * 32), ay(n_chain * 32), ainf(n_chain);
-  if ((rc = tail.mul_chain(s.data(), n_pairs, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
+  if ((rc = vpin::mul_chain(c, tail, s.data(), n_pairs, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
   t->resize_lists();
   t->left_x.resize(n_pairs * 32); t->left_y.resize(n_pairs * 32); t->left_inf.resize(n_pairs);
+  const PointBytes sum{sx.data(), sy.data(), sinf.data()}, prod{tx.data(), ty.data(), tinf.data()}, prefix{ax.data(), ay.data(), ainf.data()};
   bool equal = true;
   size_t mi = 0, ai = 0;
   for (size_t q = 0; q < n_pairs; q++) {
-    const size_t len = p.chan[q % n_out].size() * taps;
+    const size_t len = p.chan[q % n_out].size() * taps;  // the chain without its padding
     for (size_t tt = 0; with_bias && tt < per_plane; tt++, ai++) {
       const size_t i = q * per_plane + tt;
       memcpy(&t->a_px[32 * ai], &cx[32 * i], 32); memcpy(&t->a_py[32 * ai], &cy[32 * i], 32);
       if (binf[q]) { t->a_rz[ai] = 1; continue; }  // rx, ry stay zero
       memcpy(&t->a_rx[32 * ai], bx + 32 * q, 32); memcpy(&t->a_ry[32 * ai], by + 32 * q, 32);
     }
-    for (size_t m = 0; m < len; m++, mi++) {
-      const size_t i = q * K + m;
-      memcpy(&t->m_w[16 * mi], &s[16 * i], 16);
-      memcpy(&t->m_px[32 * mi], &sx[32 * i], 32); memcpy(&t->m_py[32 * mi], &sy[32 * i], 32);
-      if (m == 0) continue;
-      if (ainf[i - 1]) return failed(VPIN_ESHAPE, "an addition accumulator is the identity (the witness format has no flag for it)");
-      memcpy(&t->a_px[32 * ai], &ax[32 * (i - 1)], 32); memcpy(&t->a_py[32 * ai], &ay[32 * (i - 1)], 32);
-      memcpy(&t->a_rx[32 * ai], &tx[32 * i], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * i], 32);
-      t->a_rz[ai] = tinf[i];
-      ai++;
-    }
-    // the last accumulator may be the identity: it is only compared.  Both sides are canonical bytes, an identity zeros and a flag
-    const size_t last = q * K + len - 1, li = n_chain + q;
-    memcpy(&t->left_x[32 * q], &sx[32 * li], 32); memcpy(&t->left_y[32 * q], &sy[32 * li], 32);
-    t->left_inf[q] = sinf[li];
-    if (ainf[last] != sinf[li] || memcmp(&ax[32 * last], &sx[32 * li], 32) || memcmp(&ay[32 * last], &sy[32 * li], 32)) equal = false;
+    memcpy(&t->m_w[16 * mi], &s[16 * q * K], 16 * len);
+    memcpy(&t->m_px[32 * mi], &sx[32 * q * K], 32 * len); memcpy(&t->m_py[32 * mi], &sy[32 * q * K], 32 * len);
+    mi += len;
+    const PointBytes left = sum.at(n_chain + q);
+    memcpy(&t->left_x[32 * q], left.x, 32); memcpy(&t->left_y[32 * q], left.y, 32);
+    t->left_inf[q] = *left.inf;
+    bool closes = false;
+    if ((rc = emit_chain(who, t.get(), &ai, prod.at(q * K), prefix.at(q * K), len, left, &closes))) return rc;
+    if (!closes) equal = false;
   }
   tm[4] = lap();
   tm[5] = total();
   if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");
-  guard.t = nullptr;
-  *out = t;
+  *out = t.release();
   return VPIN_OK;
 }
 
@@ -207,9 +188,7 @@ int vpin_e2_conv2d_mc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const u
   int rc = make_plan("vpin_e2_conv2d_mc", groups, C, n_out, H, W, weights, connect, fh, fw, pad, stride, &p);
   if (rc) return rc;
   EncConvDev d(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, p.g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags, "vpin_e2_conv2d_mc", "pixel"))) return rc;
+  if ((rc = d.in.load(c, px, py, pinf, p.g.pixels(), "vpin_e2_conv2d_mc", "pixel"))) return rc;
   return d.conv_mc(p.g, groups, C, n_out, weights, p.connect.data(), p.top_bit.data(), out_x, out_y, out_inf);
 }
 

@@ -1,6 +1,7 @@
 // enc_convmc.hip -- the device stages of the trained convolution layer (driven by enc_convmc.cpp): one signed filter per
 // (output channel, input channel) over groups x C ciphertext planes on E2, and the sums of its random-linear-combination check.
-// Beside enc_conv.hip and enc_fc.hip, whose load, normalisation, reduce, scalar-multiplication and chain-scan kernels it reuses.
+// Beside enc_conv.hip and enc_fc.hip, whose load, normalisation (e2_emit), reduce, scalar-multiplication and chain-scan kernels it
+// reuses.
 //
 //   e2_convmc_kernel   one workgroup per (block of output pixels, output channel o, group): the weights of one o are uniform
 //                      per workgroup.  A workgroup is slots x px lanes, lane = slot * px + pixel: slot s walks the input
@@ -14,7 +15,7 @@
 //                      whose r vector weighs it; one lane per (sum, term), S lanes a sum: a sum of 256 terms or more takes whole
 //                      workgroups (e2_reduce_kernel adds their partials), shorter sums share one
 //   e2_bias_add_kernel out[g][o][t] = C[g][o][t] + bias[g][o] (vpin_enc_conv2d_mc_bias): one lane per output over the resident,
-//                      normalised C, one mixed addition each, complete by case; one e2_to_affine launch follows
+//                      normalised C (EncConvDev::out), one mixed addition each, complete by case; one normalisation follows
 //   e2_negate_kernel   S = -B' where the weight is negative: Y -> q - Y on the Jacobian sums, before the one normalisation
 // Exactness: every addition is complete by case (e2_dev.h): two channels that hold the same pixel under the same weight double
 // in the tree, a pixel and its negative cancel to the flagged identity.  The accumulators are named registers: no per-lane arrays.
@@ -131,23 +132,15 @@ __global__ __launch_bounds__(kBiasBlock) void e2_bias_add_kernel(const fq* __res
 
 }  // namespace
 
-int EncConvDev::add_bias(const EncConvDev& bias, size_t groups, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {
+int EncConvDev::add_bias(const E2Points& bias, size_t groups, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {
   (void)hipSetDevice(c->device);
   const size_t per_plane = g.oh * g.ow, n = groups * n_out * per_plane;
-  DevBuf jac(c), mx(c), my(c), cx(c), cy(c), fi(c);
-  if (jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || fi.alloc(n))
-    return VPIN_ENOMEM;
+  DevBuf jac(c);
+  if (jac.alloc(n * sizeof(e2_jac))) return VPIN_ENOMEM;
   hipLaunchKernelGGL(e2_bias_add_kernel, dim3(blocks_of(per_plane, kBiasBlock), (unsigned)n_out, (unsigned)groups), dim3(kBiasBlock), 0, c->stream,
-                     (const fq*)ox.p, (const fq*)oy.p, (const uint8_t*)oinf.p, (const fq*)bias.px.p, (const fq*)bias.py.p,
-                     (const uint8_t*)bias.pinf.p, per_plane, e2_curve_a(), (e2_jac*)jac.p);
+                     out.X(), out.Y(), out.F(), bias.X(), bias.Y(), bias.F(), per_plane, e2_curve_a(), (e2_jac*)jac.p);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fi.p);
-  if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, fi.p, n, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)jac.p, n, out_x, out_y, out_inf);
 }
 
 int EncConvDev::conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_out, const int32_t* w, const uint8_t* connect,
@@ -156,63 +149,42 @@ int EncConvDev::conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_
   g = geom;
   const size_t taps = g.taps(), per_plane = g.oh * g.ow, n = groups * n_out * per_plane;
   const int slots = (int)(C < (size_t)kMcMaxSlots ? C : (size_t)kMcMaxSlots), lanes = kE2Block / slots < 64 ? kE2Block / slots : 64;
-  DevBuf jac(c), cx(c), cy(c), wd(c), cn(c), tb(c);
-  if (jac.alloc(n * sizeof(e2_jac)) || cx.alloc(n * 32) || cy.alloc(n * 32) || wd.alloc(n_out * C * taps * 4) || cn.alloc(n_out * C) ||
-      tb.alloc(n_out * 4))
-    return VPIN_ENOMEM;
-  VPIN_EC_ALLOC(ox, n * 32);
-  VPIN_EC_ALLOC(oy, n * 32);
-  VPIN_EC_ALLOC(oinf, n);
+  DevBuf jac(c), wd(c), cn(c), tb(c);
+  if (jac.alloc(n * sizeof(e2_jac)) || wd.alloc(n_out * C * taps * 4) || cn.alloc(n_out * C) || tb.alloc(n_out * 4)) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(wd.p, w, n_out * C * taps * 4, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(cn.p, connect, n_out * C, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(tb.p, top_bit, n_out * 4, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(e2_convmc_kernel, dim3(blocks_of(per_plane, lanes), (unsigned)n_out, (unsigned)groups), dim3(slots * lanes), 0, c->stream,
-                     (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, e2_geom(g), (int)C, slots, lanes, (const int32_t*)wd.p,
-                     (const uint8_t*)cn.p, (const int32_t*)tb.p, e2_curve_a(), (e2_jac*)jac.p);
+                     in.X(), in.Y(), in.F(), e2_geom(g), (int)C, slots, lanes, (const int32_t*)wd.p, (const uint8_t*)cn.p,
+                     (const int32_t*)tb.p, e2_curve_a(), (e2_jac*)jac.p);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p);
-  if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, oinf.p, n, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)jac.p, n, out_x, out_y, out_inf, &out);
 }
 
-int EncConvDev::rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, EncConvDev* tail,
+int EncConvDev::rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, E2Points* sums_out,
                        uint8_t* s_x, uint8_t* s_y, uint8_t* s_inf) {
   (void)hipSetDevice(c->device);
   const size_t n_terms = g.oh * g.ow, total = n_pairs * n_terms;
   int S = kE2Block;  // lanes per sum
   while (S / 2 >= 1 && (size_t)(S / 2) >= n_terms) S /= 2;
   const size_t nblk = blocks_of(n_terms, S);  // 1 below kE2Block terms
-  DevBuf r(c), ds(c), ng(c), parts(c), sums(c), cx(c), cy(c);
+  DevBuf r(c), ds(c), ng(c), parts(c), sums(c);
   if (r.alloc(total * 16) || ds.alloc(n_sums * 16) || ng.alloc(n_sums) || parts.alloc(n_sums * nblk * sizeof(e2_jac)) ||
-      sums.alloc(n_sums * sizeof(e2_jac)) || cx.alloc(n_sums * 32) || cy.alloc(n_sums * 32))
+      sums.alloc(n_sums * sizeof(e2_jac)))
     return VPIN_ENOMEM;
-  VPIN_EC_ALLOC(tail->px, n_sums * 32);
-  VPIN_EC_ALLOC(tail->py, n_sums * 32);
-  VPIN_EC_ALLOC(tail->pinf, n_sums);
-  const fq a = e2_curve_a();
   VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le16, total * 16, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(ds.p, desc, n_sums * 16, hipMemcpyHostToDevice, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(ng.p, neg, n_sums, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_rlc_mc_kernel, dim3((unsigned)(blocks_of(n_sums, kE2Block / S) * nblk)), dim3(kE2Block), 0, c->stream, (const fq*)px.p,
-                     (const fq*)py.p, (const uint8_t*)pinf.p, (const fq*)ox.p, (const fq*)oy.p, (const uint8_t*)oinf.p, e2_geom(g),
-                     (const int4*)ds.p, n_sums, (unsigned)nblk, S, n_terms, (const uint4*)r.p, a, (e2_jac*)parts.p);
+  hipLaunchKernelGGL(e2_rlc_mc_kernel, dim3((unsigned)(blocks_of(n_sums, kE2Block / S) * nblk)), dim3(kE2Block), 0, c->stream, in.X(), in.Y(),
+                     in.F(), out.X(), out.Y(), out.F(), e2_geom(g), (const int4*)ds.p, n_sums, (unsigned)nblk, S, n_terms, (const uint4*)r.p,
+                     e2_curve_a(), (e2_jac*)parts.p);
   VPIN_HIP_TRY(hipGetLastError());
-  int rc = e2_reduce(c, (const e2_jac*)parts.p, n_sums, nblk, (e2_jac*)sums.p);
+  const int rc = e2_reduce(c, (const e2_jac*)parts.p, n_sums, nblk, (e2_jac*)sums.p);
   if (rc) return rc;
   hipLaunchKernelGGL(e2_negate_kernel, dim3(blocks_of(n_sums, kE2Block)), dim3(kE2Block), 0, c->stream, (e2_jac*)sums.p, (const uint8_t*)ng.p,
                      n_sums);
   VPIN_HIP_TRY(hipGetLastError());
-  if ((rc = e2_to_affine(c, (const e2_jac*)sums.p, n_sums, (fq*)tail->px.p, (fq*)tail->py.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)tail->pinf.p)))
-    return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(s_x, cx.p, n_sums * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(s_y, cy.p, n_sums * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(s_inf, tail->pinf.p, n_sums, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)sums.p, n_sums, s_x, s_y, s_inf, sums_out);
 }
 
 }  // namespace vpin

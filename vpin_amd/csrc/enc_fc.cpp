@@ -9,6 +9,7 @@
 #include <omp.h>
 
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -18,6 +19,7 @@
 
 using namespace vpin::enc;
 using vpin::ConvGeom;
+using vpin::E2Points;
 using vpin::EncConvDev;
 typedef unsigned __int128 u128;
 
@@ -33,13 +35,8 @@ bool mul_add_u128(u128& acc, u128 r, uint32_t w) {
   return acc >= prod;
 }
 
-struct TraceGuard {
-  vpin_conv_trace* t;
-  ~TraceGuard() { delete t; }
-};
-
 // vpin_enc_fc (weights: u32) and vpin_enc_fc_signed (is_signed, weights: int32) are one layer: without a negative weight every
-// neg_k below is zero, no point is negated, and the two kernels of the product compute the same points
+// neg_k below is zero, no point is negated, and the two instances of e2_matvec_kernel compute the same points
 int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const void* weights,
              bool is_signed, size_t N, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes,
              vpin_conv_trace** out) {
@@ -50,23 +47,19 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
   if (prf_bytes < 1 || prf_bytes > 16) return failed(VPIN_EINVAL, "prf_bytes must be in 1 .. 16");
   if (!P || !K || !N) return failed(VPIN_EINVAL, "a dimension is zero");
   if (P > 65535 || N > 65535 || K > kMaxDim) return failed(VPIN_EINVAL, "a dimension is out of range");
-  double* tm = last_timings();
-  for (int i = 0; i < 8; i++) tm[i] = 0.0;
+  double* tm = reset_timings();
   Lap total, lap;
-  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  std::unique_ptr<vpin_conv_trace> t(new (std::nothrow) vpin_conv_trace());
   if (!t) return VPIN_ENOMEM;
-  TraceGuard guard{t};
   const size_t n_in = P * K, n_out = P * N, adds_per_row = N + K - 1;
   t->P = P; t->oh = 1; t->ow = N; t->n_mult = n_in; t->n_add = P * adds_per_row;
 
   // validate: upload, range and curve checks on the device, for the inputs and the bias
-  EncConvDev d(c), b(c), flipped(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, n_in, &flags);
+  EncConvDev d(c);
+  E2Points b(c), flipped(c);
+  int rc = d.in.load(c, px, py, pinf, n_in, who, "input point");
+  if (!rc) rc = b.load(c, bx, by, binf, n_out, who, "bias point");
   if (rc) return rc;
-  if ((rc = check_flags(flags, who, "input point"))) return rc;
-  if ((rc = b.load(bx, by, binf, n_out, &flags))) return rc;
-  if ((rc = check_flags(flags, who, "bias point"))) return rc;
   tm[0] = lap();
 
   // C = X * W on the device, out = C + bias here; the first N additions of every row
@@ -74,9 +67,7 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
   t->out_x.resize(n_out * 32); t->out_y.resize(n_out * 32); t->out_inf.resize(n_out);
   t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
   std::vector<uint8_t> cx(n_out * 32), cy(n_out * 32), cinf(n_out);
-  rc = is_signed ? d.matvec_signed(P, K, N, (const int32_t*)weights, cx.data(), cy.data(), cinf.data())
-                 : d.matvec(P, K, N, (const uint8_t*)weights, cx.data(), cy.data(), cinf.data());
-  if (rc) return rc;
+  if ((rc = d.matvec(P, K, N, weights, is_signed, cx.data(), cy.data(), cinf.data()))) return rc;
   for (size_t i = 0; i < n_out; i++)
     if (cinf[i]) return failed(VPIN_ESHAPE, "an addition accumulator C[j] is the identity (the witness format has no flag for it)");
 #pragma omp parallel for schedule(static) num_threads(team_size())
@@ -93,9 +84,7 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
   tm[1] = lap();
 
   // the PRF scalars: the index restarts at 0 for every row
-  std::vector<uint8_t> r(n_out * 16);
-#pragma omp parallel for schedule(static) num_threads(team_size())
-  for (long i = 0; i < (long)n_out; i++) prf_scalar(keys32 + 32 * ((size_t)i / N), (size_t)i % N, prf_bytes, &r[16 * (size_t)i]);
+  const std::vector<uint8_t> r = prf_rows(keys32, P, N, prf_bytes);
   tm[2] = lap();
 
   // left = sum_j r_j * C[j] of every row, over the resident C
@@ -133,36 +122,29 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
     x.y = x.y.neg();
     put_point(x, &t->m_px[32 * m], &t->m_py[32 * m]);
   }
-  EncConvDev* tail = &d;
+  const E2Points* tail = &d.in;
   if (!minus_s.empty()) {  // the chain runs over S: the recorded points, validated again as they are loaded
-    if ((rc = flipped.load(t->m_px.data(), t->m_py.data(), pinf, n_in, &flags))) return rc;
-    if ((rc = check_flags(flags, who, "input point"))) return rc;
+    if ((rc = flipped.load(c, t->m_px.data(), t->m_py.data(), pinf, n_in, who, "input point"))) return rc;
     tail = &flipped;
   }
   std::vector<uint8_t> tx(n_in * 32), ty(n_in * 32), tinf(n_in), ax(n_in * 32), ay(n_in * 32), ainf(n_in);
-  if ((rc = tail->mul_chain(t->m_w.data(), P, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
+  if ((rc = vpin::mul_chain(c, *tail, t->m_w.data(), P, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
+  const PointBytes prod{tx.data(), ty.data(), tinf.data()}, prefix{ax.data(), ay.data(), ainf.data()};
+  const PointBytes left{t->left_x.data(), t->left_y.data(), t->left_inf.data()};
   bool equal = true;
   for (size_t p = 0; p < P; p++) {
-    for (size_t k = 1; k < K; k++) {
-      const size_t m = p * K + k;
-      if (ainf[m - 1]) return failed(VPIN_ESHAPE, "an addition accumulator is the identity (the witness format has no flag for it)");
-      const size_t ai = p * adds_per_row + N + (k - 1);
-      memcpy(&t->a_px[32 * ai], &ax[32 * (m - 1)], 32); memcpy(&t->a_py[32 * ai], &ay[32 * (m - 1)], 32);
-      memcpy(&t->a_rx[32 * ai], &tx[32 * m], 32); memcpy(&t->a_ry[32 * ai], &ty[32 * m], 32);
-      t->a_rz[ai] = tinf[m];
-    }
-    const size_t last = p * K + K - 1;  // the last accumulator may be the identity: it is only compared
-    const Aff acc = aff_from_bytes(&ax[32 * last], &ay[32 * last], ainf[last]);
-    const Aff left = to_affine(jac_from_bytes(&sums[96 * p]));
-    put_point(left, &t->left_x[32 * p], &t->left_y[32 * p]);
-    t->left_inf[p] = left.inf ? 1 : 0;
-    if (!aff_eq(acc, left)) equal = false;
+    const Aff l = to_affine(jac_from_bytes(&sums[96 * p]));
+    put_point(l, &t->left_x[32 * p], &t->left_y[32 * p]);
+    t->left_inf[p] = l.inf ? 1 : 0;
+    size_t ai = p * adds_per_row + N;  // after the row's bias additions
+    bool closes = false;
+    if ((rc = emit_chain(who, t.get(), &ai, prod.at(p * K), prefix.at(p * K), K, left.at(p), &closes))) return rc;
+    if (!closes) equal = false;
   }
   tm[4] = lap();
   tm[5] = total();
   if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");
-  guard.t = nullptr;
-  *out = t;
+  *out = t.release();
   return VPIN_OK;
 }
 
@@ -176,12 +158,10 @@ int vpin_e2_mul_chain(vpin_ctx* c, const uint8_t* scalars_le16, const uint8_t* p
     return fail(VPIN_EINVAL, "vpin_e2_mul_chain: null argument");
   if (!P || !K || P >= ((size_t)1 << 31) || K >= ((size_t)1 << 31) || P * K >= ((size_t)1 << 31))
     return fail(VPIN_EINVAL, "vpin_e2_mul_chain: P and K must be at least 1 and P * K at most 2^31 - 1");
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, P * K, &flags);
+  E2Points pts(c);
+  const int rc = pts.load(c, px, py, pinf, P * K, "vpin_e2_mul_chain", "point");
   if (rc) return rc;
-  if ((rc = check_flags(flags, "vpin_e2_mul_chain", "point"))) return rc;
-  return d.mul_chain(scalars_le16, P, K, t_x, t_y, t_inf, acc_x, acc_y, acc_inf);
+  return vpin::mul_chain(c, pts, scalars_le16, P, K, t_x, t_y, t_inf, acc_x, acc_y, acc_inf);
 }
 
 int vpin_enc_fc(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t K, const uint8_t* weights_le4,
@@ -203,19 +183,15 @@ int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   ConvGeom g;
   int rc = make_geom(P, H, W, k, k, 0, stride, &g);  // zero dimensions, k > H, k > W
   if (rc) return rc;
-  double* tm = last_timings();
-  for (int i = 0; i < 8; i++) tm[i] = 0.0;
+  double* tm = reset_timings();
   Lap total, lap;
-  vpin_conv_trace* t = new (std::nothrow) vpin_conv_trace();
+  std::unique_ptr<vpin_conv_trace> t(new (std::nothrow) vpin_conv_trace());
   if (!t) return VPIN_ENOMEM;
-  TraceGuard guard{t};
   const size_t taps = g.taps(), n_out = g.outputs(), per_plane = g.oh * g.ow;
   t->P = P; t->oh = g.oh; t->ow = g.ow; t->n_add = n_out * (taps - 1);
 
   EncConvDev d(c);
-  uint32_t flags = 0;
-  if ((rc = d.load(px, py, pinf, g.pixels(), &flags))) return rc;
-  if ((rc = check_flags(flags, "vpin_enc_avgpool2d", "pixel"))) return rc;
+  if ((rc = d.in.load(c, px, py, pinf, g.pixels(), "vpin_enc_avgpool2d", "pixel"))) return rc;
   tm[0] = lap();
 
   // the accumulators of the additions, then out = scale * (window sum) as the convolution under a constant filter
@@ -247,8 +223,7 @@ int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   }
   tm[4] = lap();
   tm[5] = total();
-  guard.t = nullptr;
-  *out = t;
+  *out = t.release();
   return VPIN_OK;
 }
 

@@ -3,8 +3,8 @@
 //
 //   e2_matvec_kernel      C[p][j] = sum_k W[k][j] * X[p][k]: one lane per (k, j) term on grid (blocks of k, N, P), double-and-add
 //                         over the lane's own 32-bit weight (mixed addition), then the workgroup's LDS tree with the complete
-//                         addition; e2_reduce_kernel sums over the blocks of k
-//   e2_matvec_signed_kernel  its sibling over int32 weights (vpin_enc_fc_signed): the lane multiplies by |w| and takes the negated
+//                         addition; e2_reduce_kernel sums over the blocks of k.  A template over the weights' type: <false> takes
+//                         u32 words, <true> int32 words (vpin_enc_fc_signed): the lane multiplies by |w| and takes the negated
 //                         point (x, q - y) for w < 0; the same tree, so X[k] under w and -w cancels to the flagged identity
 //   e2_scalar_mul_kernel  T_i = s_i * X_i, one lane per point, s_i a u128: the multiplications of the layer's RLC check
 //   e2_pool_sums_kernel   one lane per pooled output: the k*k - 1 accumulators e_0, e_0 + e_1, ... of its window (the first
@@ -12,7 +12,7 @@
 //   e2_chain_scan_kernel  one workgroup per chain of K Jacobian points: the inclusive prefixes T_0 + .. + T_k as a scan in LDS
 //                         with the complete addition, in tiles of kE2Block with a carried prefix; with e2_scalar_mul_kernel
 //                         before it and ONE e2_to_affine_kernel launch over products and prefixes after it, this is the tail
-//                         of the fully connected layer's RLC check (mul_chain): one shared inversion per 256 points instead of
+//                         of a layer's RLC check (mul_chain, over any E2Points): one shared inversion per 256 points instead of
 //                         one per addition
 // As in enc_conv.hip the accumulators are named registers (one e2_jac, the scalar as shifted words): no per-lane arrays.
 #include "e2_dev.h"
@@ -22,31 +22,21 @@ namespace vpin {
 
 namespace {
 
-// grid: x = blocks of k, y = output j, z = row p; W is K x N row-major
+// grid: x = blocks of k, y = output j, z = row p; W is K x N row-major, u32 or (Signed) int32 words: a negative weight
+// multiplies the negated point by |w|, and |INT32_MIN| = 2^31 is taken in unsigned arithmetic
+template <bool Signed>
 __global__ __launch_bounds__(kE2Block) void e2_matvec_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
                                                              const uint8_t* __restrict__ inf, const uint32_t* __restrict__ W,
                                                              size_t K, size_t N, fq a, e2_jac* __restrict__ parts) {
   __shared__ e2_jac sh[kE2Block];
   const size_t k = (size_t)blockIdx.x * kE2Block + threadIdx.x, j = blockIdx.y, p = blockIdx.z;
   e2_jac acc = e2_identity();
-  if (k < K && !inf[p * K + k])  // a zero weight gives the identity inside e2_mul_affine
-    acc = e2_mul_affine(fq_load(X + p * K + k), fq_load(Y + p * K + k), 0u, 0u, 0u, W[k * N + j], 32, a);
-  e2_block_tree(sh, acc, a);
-  if (threadIdx.x == 0) e2_store(parts + ((p * N + j) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
-}
-
-// the same grid; |INT32_MIN| = 2^31 is taken in unsigned arithmetic
-__global__ __launch_bounds__(kE2Block) void e2_matvec_signed_kernel(const fq* __restrict__ X, const fq* __restrict__ Y,
-                                                                    const uint8_t* __restrict__ inf, const int32_t* __restrict__ W,
-                                                                    size_t K, size_t N, fq a, e2_jac* __restrict__ parts) {
-  __shared__ e2_jac sh[kE2Block];
-  const size_t k = (size_t)blockIdx.x * kE2Block + threadIdx.x, j = blockIdx.y, p = blockIdx.z;
-  e2_jac acc = e2_identity();
-  if (k < K && !inf[p * K + k]) {
-    const int32_t w = W[k * N + j];
-    const uint32_t m = w < 0 ? 0u - (uint32_t)w : (uint32_t)w;
+  if (k < K && !inf[p * K + k]) {  // a zero weight gives the identity inside e2_mul_affine
+    const uint32_t w = W[k * N + j];
+    const bool minus = Signed && (int32_t)w < 0;
+    const uint32_t m = minus ? 0u - w : w;
     const fq y = fq_load(Y + p * K + k);
-    acc = e2_mul_affine(fq_load(X + p * K + k), w < 0 ? fq_neg(y) : y, 0u, 0u, 0u, m, 32, a);
+    acc = e2_mul_affine(fq_load(X + p * K + k), minus ? fq_neg(y) : y, 0u, 0u, 0u, m, 32, a);
   }
   e2_block_tree(sh, acc, a);
   if (threadIdx.x == 0) e2_store(parts + ((p * N + j) * gridDim.x + blockIdx.x), e2_load(&sh[0]));
@@ -125,75 +115,44 @@ __global__ __launch_bounds__(kE2Block) void e2_chain_scan_kernel(const e2_jac* _
 }  // namespace
 
 // C = X * W per row over the loaded points (P x K), normalised: canonical bytes to the host, Montgomery coordinates resident
-// as this object's outputs with the geometry "P planes of 1 x N and no taps", so that rlc() returns sum_j r[p][j] * C[p][j]
-int EncConvDev::matvec(size_t P, size_t K, size_t N, const uint8_t* weights_le4, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
-  return matvec_any(P, K, N, weights_le4, false, c_x, c_y, c_inf);
-}
-
-int EncConvDev::matvec_signed(size_t P, size_t K, size_t N, const int32_t* weights, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
-  return matvec_any(P, K, N, weights, true, c_x, c_y, c_inf);
-}
-
-// weights: K * N words of four bytes, u32 or (is_signed) int32
-int EncConvDev::matvec_any(size_t P, size_t K, size_t N, const void* weights, bool is_signed, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
+// as `out` with the geometry "P planes of 1 x N and no taps", so that rlc() returns sum_j r[p][j] * C[p][j]
+int EncConvDev::matvec(size_t P, size_t K, size_t N, const void* weights, bool is_signed, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf) {
   (void)hipSetDevice(c->device);
   g = ConvGeom();
   g.P = P; g.oh = 1; g.ow = N;
   const size_t nblk = blocks_of(K, kE2Block), n_out = P * N;
-  DevBuf w(c), parts(c), jac(c), cx(c), cy(c);
-  if (w.alloc(K * N * 4) || parts.alloc(n_out * nblk * sizeof(e2_jac)) || jac.alloc(n_out * sizeof(e2_jac)) || cx.alloc(n_out * 32) ||
-      cy.alloc(n_out * 32))
-    return VPIN_ENOMEM;
-  VPIN_EC_ALLOC(ox, n_out * 32);
-  VPIN_EC_ALLOC(oy, n_out * 32);
-  VPIN_EC_ALLOC(oinf, n_out);
-  const fq a = e2_curve_a();
+  DevBuf w(c), parts(c), jac(c);
+  if (w.alloc(K * N * 4) || parts.alloc(n_out * nblk * sizeof(e2_jac)) || jac.alloc(n_out * sizeof(e2_jac))) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(w.p, weights, K * N * 4, hipMemcpyHostToDevice, c->stream));
-  const dim3 grid((unsigned)nblk, (unsigned)N, (unsigned)P);
-  if (is_signed)
-    hipLaunchKernelGGL(e2_matvec_signed_kernel, grid, dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
-                       (const uint8_t*)pinf.p, (const int32_t*)w.p, K, N, a, (e2_jac*)parts.p);
-  else
-    hipLaunchKernelGGL(e2_matvec_kernel, grid, dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
-                       (const uint8_t*)pinf.p, (const uint32_t*)w.p, K, N, a, (e2_jac*)parts.p);
+  hipLaunchKernelGGL(is_signed ? e2_matvec_kernel<true> : e2_matvec_kernel<false>, dim3((unsigned)nblk, (unsigned)N, (unsigned)P),
+                     dim3(kE2Block), 0, c->stream, in.X(), in.Y(), in.F(), (const uint32_t*)w.p, K, N, e2_curve_a(), (e2_jac*)parts.p);
   VPIN_HIP_TRY(hipGetLastError());
-  int rc = e2_reduce(c, (const e2_jac*)parts.p, n_out, nblk, (e2_jac*)jac.p);
+  const int rc = e2_reduce(c, (const e2_jac*)parts.p, n_out, nblk, (e2_jac*)jac.p);
   if (rc) return rc;
-  if ((rc = e2_to_affine(c, (const e2_jac*)jac.p, n_out, (fq*)ox.p, (fq*)oy.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)oinf.p))) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(c_x, cx.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c_y, cy.p, n_out * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(c_inf, oinf.p, n_out, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)jac.p, n_out, c_x, c_y, c_inf, &out);
 }
 
-// the tail over the loaded points, P chains of K terms: T = s * X (Jacobian), the prefixes of every chain, and both normalised by
-// ONE launch over the 2 P K points; canonical bytes and flags to the host
-int EncConvDev::mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf, uint8_t* acc_x,
-                          uint8_t* acc_y, uint8_t* acc_inf) {
+// the tail over pts, P chains of K terms: T = s * X (Jacobian), the prefixes of every chain, and both normalised by ONE launch
+// over the 2 P K points; canonical bytes and flags to the host
+int mul_chain(vpin_ctx* c, const E2Points& pts, const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf,
+              uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_inf) {
   (void)hipSetDevice(c->device);
   const size_t n = P * K;
-  DevBuf s(c), jac(c), mx(c), my(c), cx(c), cy(c), ti(c);
-  if (s.alloc(n * 16) || jac.alloc(2 * n * sizeof(e2_jac)) || mx.alloc(2 * n * 32) || my.alloc(2 * n * 32) || cx.alloc(2 * n * 32) ||
-      cy.alloc(2 * n * 32) || ti.alloc(2 * n))
-    return VPIN_ENOMEM;
+  DevBuf s(c), jac(c);
+  if (s.alloc(n * 16) || jac.alloc(2 * n * sizeof(e2_jac))) return VPIN_ENOMEM;
   const fq a = e2_curve_a();
   e2_jac* prod = (e2_jac*)jac.p;
   VPIN_HIP_TRY(hipMemcpyAsync(s.p, s_le16, n * 16, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_scalar_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)px.p, (const fq*)py.p,
-                     (const uint8_t*)pinf.p, (const uint4*)s.p, n, a, prod);
+  hipLaunchKernelGGL(e2_scalar_mul_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, pts.X(), pts.Y(), pts.F(),
+                     (const uint4*)s.p, n, a, prod);
   VPIN_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(e2_chain_scan_kernel, dim3((unsigned)P), dim3(kE2Block), 0, c->stream, (const e2_jac*)prod, K, a, prod + n);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, prod, 2 * n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ti.p);
+  E2Affine aff(c);
+  int rc = aff.normalise(c, prod, 2 * n);
+  if (!rc) rc = aff.copy_out(c, 0, n, t_x, t_y, t_inf);
+  if (!rc) rc = aff.copy_out(c, n, n, acc_x, acc_y, acc_inf);
   if (rc) return rc;
-  const uint8_t *bx = (const uint8_t*)cx.p, *by = (const uint8_t*)cy.p, *bi = (const uint8_t*)ti.p;
-  VPIN_HIP_TRY(hipMemcpyAsync(t_x, bx, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(t_y, by, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(t_inf, bi, n, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(acc_x, bx + n * 32, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(acc_y, by + n * 32, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(acc_inf, bi + n, n, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;
 }
@@ -203,18 +162,15 @@ int EncConvDev::mul_chain(const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_
 int EncConvDev::pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity) {
   (void)hipSetDevice(c->device);
   const size_t n_out = geom.outputs(), n = n_out * (geom.taps() - 1);
-  DevBuf jac(c), mx(c), my(c), cx(c), cy(c), ai(c), bad(c);
-  if (jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) || cy.alloc(n * 32) || ai.alloc(n) ||
-      bad.alloc(n_out))
-    return VPIN_ENOMEM;
-  hipLaunchKernelGGL(e2_pool_sums_kernel, dim3(blocks_of(geom.oh * geom.ow, 64), (unsigned)geom.P), dim3(64), 0, c->stream,
-                     (const fq*)px.p, (const fq*)py.p, (const uint8_t*)pinf.p, e2_geom(geom), e2_curve_a(), (e2_jac*)jac.p,
-                     (uint8_t*)bad.p);
+  DevBuf jac(c), bad(c);
+  if (jac.alloc(n * sizeof(e2_jac)) || bad.alloc(n_out)) return VPIN_ENOMEM;
+  hipLaunchKernelGGL(e2_pool_sums_kernel, dim3(blocks_of(geom.oh * geom.ow, 64), (unsigned)geom.P), dim3(64), 0, c->stream, in.X(), in.Y(),
+                     in.F(), e2_geom(geom), e2_curve_a(), (e2_jac*)jac.p, (uint8_t*)bad.p);
   VPIN_HIP_TRY(hipGetLastError());
-  const int rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)ai.p);
+  E2Affine aff(c);  // the flags that matter are the kernel's, per output: the points' own are not copied
+  int rc = aff.normalise(c, (const e2_jac*)jac.p, n);
+  if (!rc) rc = aff.copy_out(c, 0, n, acc_x, acc_y, nullptr);
   if (rc) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(acc_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(acc_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipMemcpyAsync(acc_identity, bad.p, n_out, hipMemcpyDeviceToHost, c->stream));
   VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
   return VPIN_OK;

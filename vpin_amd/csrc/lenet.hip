@@ -5,7 +5,8 @@
 //   e2_plane_sum_kernel  one lane per (output plane, pixel): a Jacobian accumulator over the connected input planes with the
 //                        mixed addition, complete by case (e2_dev.h): an identity pixel is skipped, the same point in two planes
 //                        falls to the doubling, P and -P cancel to the identity
-// e2_load_kernel (range and curve checks) comes before it and e2_to_affine_kernel after it, both of enc_conv.hip.  The plane
+// E2Points::load (e2_load_kernel: range and curve checks) comes before it and e2_emit (e2_to_affine_kernel) after it, both of
+// enc_conv.hip.  The plane
 // additions are not part of any witness list: the reference does not prove them.
 #include "e2_dev.h"
 #include "enc_conv.h"
@@ -37,26 +38,17 @@ __global__ __launch_bounds__(kE2Block) void e2_plane_sum_kernel(const fq* __rest
 int plane_sums(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n_in, size_t hw, const uint8_t* connect,
                size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf) {
   (void)hipSetDevice(c->device);
-  EncConvDev d(c);
-  uint32_t flags = 0;
-  int rc = d.load(px, py, pinf, n_in * hw, &flags);
+  E2Points pts(c);
+  const int rc = pts.load(c, px, py, pinf, n_in * hw, "vpin_e2_plane_sums", "pixel");
   if (rc) return rc;
-  if ((rc = enc::check_flags(flags, "vpin_e2_plane_sums", "pixel"))) return rc;
   const size_t n = n_out * hw;
-  DevBuf con(c), jac(c), mx(c), my(c), cx(c), cy(c), fl(c);
-  if (con.alloc(n_out * n_in) || jac.alloc(n * sizeof(e2_jac)) || mx.alloc(n * 32) || my.alloc(n * 32) || cx.alloc(n * 32) ||
-      cy.alloc(n * 32) || fl.alloc(n))
-    return VPIN_ENOMEM;
+  DevBuf con(c), jac(c);
+  if (con.alloc(n_out * n_in) || jac.alloc(n * sizeof(e2_jac))) return VPIN_ENOMEM;
   VPIN_HIP_TRY(hipMemcpyAsync(con.p, connect, n_out * n_in, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_plane_sum_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)d.px.p, (const fq*)d.py.p,
-                     (const uint8_t*)d.pinf.p, n_in, hw, (const uint8_t*)con.p, n_out, e2_curve_a(), (e2_jac*)jac.p);
+  hipLaunchKernelGGL(e2_plane_sum_kernel, dim3(blocks_of(n, kE2Block)), dim3(kE2Block), 0, c->stream, pts.X(), pts.Y(), pts.F(), n_in, hw,
+                     (const uint8_t*)con.p, n_out, e2_curve_a(), (e2_jac*)jac.p);
   VPIN_HIP_TRY(hipGetLastError());
-  if ((rc = e2_to_affine(c, (const e2_jac*)jac.p, n, (fq*)mx.p, (fq*)my.p, (fq*)cx.p, (fq*)cy.p, (uint8_t*)fl.p))) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(out_x, cx.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_y, cy.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(out_inf, fl.p, n, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return e2_emit(c, (const e2_jac*)jac.p, n, out_x, out_y, out_inf);
 }
 
 }  // namespace
