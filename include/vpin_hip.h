@@ -1001,6 +1001,41 @@ int vpin_net_trace_result(const vpin_net_trace* t, const uint8_t** x, const uint
 /* host-clock milliseconds of the last vpin_net_infer on this thread: out[0] the whole, out[1 + 2 i] layer i, out[2 + 2 i] the
  * round after it; slots past 1 + 2 n_layers read 0 */
 int vpin_net_last_timings(double* out, size_t cap);
+/* ---- a batch of B images through one inference (ABI 6) ---------------------------------------------------------------------
+ * vpin_net_infer over B images at once; a batch is byte for byte B single inferences, everything image-major:
+ *   c1, c2       B * C * H * W points each, [b][C][H][W]
+ *   keys32       B * k keys, k = out[6] of vpin_net_cfg_counts; image b owns keys [b k, (b + 1) k) in the order a single run
+ *                consumes them.  bias_r_le32: B * r values (out[7]) likewise: every image has its own bias encryption
+ *   a layer      ONE call of its entry point over the planes [b][half][plane], half = c1, then c2: CONV and POOL with P = B * 2 C,
+ *                CONVMC with groups = 2 B (g = 2 b + half), FC and FCS with P = 2 B rows (row 2 b: image b's c1 row); the biases
+ *                of all images by one vpin_e2_encrypt of B * N values.  Every layer emits its lists plane by plane (row by row,
+ *                group by group), so a layer's output, lists and left sides are those of the single runs, image after image
+ *   a round      ONE callback with cnt = B * n, the values image-major; round, flags and shift_bits as in a single run.  The
+ *                ready-made client consumes its queue of r in order: the input of all images, round 0 of all images, ..
+ * B = 1 is vpin_net_infer: both are the same driver.  VPIN_EINVAL before anything runs: B = 0, B > VPIN_NET_MAX_BATCH, n_keys !=
+ * B * k, n_bias_r != B * r, and a layer whose planes, groups or rows at this B are more than its kernels' grids take (65535:
+ * "vpin_net_infer_batch: layer 2 (convmc): 2 B * C = 73728 planes are more than the 65535 a layer call takes").  A failing layer
+ * or round fails the whole batch with the single run's texts; an index in such a text counts over the whole batch: image = index /
+ * the per-image count.  A layer says that an input point is not on the curve, not which one; when the first layer refuses the
+ * caller's input so, a batch's text goes on with the first such point as vpin_e2_pack names it (found by packing the input, on
+ * this path only): ".. a pixel is not on the curve E2; the input's c1: vpin_e2_pack: point 250: the point is not on the curve E2".
+ * On a batch's trace the accessors above keep their meaning over the whole batch: vpin_net_trace_layer is the one layer call (P
+ * = B x the single P), vpin_net_trace_label holds the images' labels one after the other in image order (its output and dims are
+ * the last layer call's), vpin_net_trace_instances builds from that label, vpin_net_trace_result gives B x (2 x n) points
+ * image-major with *n = n. */
+#define VPIN_NET_MAX_BATCH 1024
+int vpin_net_infer_batch(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                         const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                         const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
+                         void* user, vpin_net_trace** out);
+/* the images of a trace (1 for vpin_net_infer's) */
+int vpin_net_trace_images(const vpin_net_trace* t, size_t* B);
+/* image b's label, borrowed until vpin_net_trace_free: byte for byte what vpin_net_trace_label gives for image b run alone
+ * (lists, output, dims).  Built when first asked for and kept; one thread reads a trace at a time */
+int vpin_net_trace_image_label(const vpin_net_trace* t, size_t b, const vpin_conv_trace** out);
+/* image b's label as vpin_net_trace_instances */
+int vpin_net_trace_image_instances(vpin_ctx* ctx, const vpin_net_trace* t, size_t b, vpin_dev_instance** mult_out,
+                                   vpin_dev_instance** add_out);
 /* The ready-made client of both drivers, for n_rounds rounds (LeNet: 7): owns sk, the tables of G and H = sk * G, a
  * discrete-log table of nb baby steps, one range max_giant per round and the queue of n_r encryption randomness values (32 bytes
  * each, one per encrypt call in order).  vpin_net_client_round is a vpin_lenet_round_fn over vpin_e2_client_round with user =
@@ -1107,6 +1142,15 @@ int vpin_wire_round(void* user, int round, int flags, int shift_bits, const uint
                     uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 int vpin_net_serve(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* keys32, size_t n_keys,
                    const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out);
+/* (ABI 6) vpin_net_serve for a batch of up to max_batch images, run by vpin_net_infer_batch: n_keys = max_batch * k and n_bias_r =
+ * max_batch * r (VPIN_EINVAL otherwise, and for max_batch outside 1 .. VPIN_NET_MAX_BATCH, before anything is read).  The server
+ * reads B off the INPUT frame, B = cnt / (C H W); a cnt that is no multiple of C H W or a B outside 1 .. max_batch is VPIN_ESHAPE
+ * with an ERROR frame to the peer, as for vpin_net_serve's wrong count.  The first B * k keys and B * r values are used.  No
+ * frame changes: INPUT and every ROUND and REPLY carry B times the single run's cnt, image-major.  vpin_net_serve itself is as it
+ * was: one image, its own texts.  The client's side needs nothing new: vpin_net_client_run takes n_input and the schedule's cnt
+ * from its caller */
+int vpin_net_serve_batch(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, size_t max_batch, const uint8_t* keys32, size_t n_keys,
+                         const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out);
 
 /* The client's endpoint: encrypts the image (n_input ints under n_input r, as vpin_e2_encrypt) under its own tables, sends HELLO
  * and INPUT, then serves frames.  A client that performs whatever round the server asks for is a decryption oracle, so the

@@ -1,5 +1,6 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
 the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
+[--batch 1,2,4,..]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
@@ -12,7 +13,12 @@ table has 2^nb entries (default 24).
 its own, vpin_net_client_run here), the two modes alternating in this one process, R = 11 warm runs by default after one warm-up
 pair.  Per round it prints the bytes on the wire each way and the ms of pack, unpack and socket (send and the receive of
 payloads), both sides added up (vpin_wire_timings), beside that round's own time in process and over the wire (the server's host
-clock: the round as the driver sees it, the client's work and the wire included)."""
+clock: the round as the driver sees it, the client's work and the wire included).
+--batch 1,2,4,..: per B a batch of B images through ONE inference (vpin_net_infer_batch; image b is the reference's image rolled by
+b % 8 rows and b // 8 columns, under keys and r of its own), every B warmed as a shape of its own by one run and then timed over
+R = 11 warm runs by default: ms per inference and per image, and per layer and per round the median (minimum .. maximum).  The
+first run of every B is checked against the plaintext model, image by image.  With --wire every B also runs between two endpoints
+over a socketpair (vpin_net_serve_batch, vpin_net_client_run), the two modes alternating.  No proofs in this mode."""
 import os
 import socket
 import statistics
@@ -38,7 +44,8 @@ def opt(name, default):
 
 VERSION = sys.argv[1]
 WIRE = "--wire" in sys.argv
-REPS, NB_LOG = opt("--reps", 11 if WIRE else 5), opt("--nb", 24)
+BATCH = [int(b) for b in sys.argv[sys.argv.index("--batch") + 1].split(",")] if "--batch" in sys.argv else None
+REPS, NB_LOG = opt("--reps", 11 if WIRE or BATCH else 5), opt("--nb", 24)
 PROOFS = "--no-proofs" not in sys.argv
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
@@ -69,6 +76,11 @@ def main():
     ctx = vpin_amd.Context(0)
     counts, giants = cfg.counts(), cfg.max_giants()
     assert counts == dict(want, rounds=len(giants))
+    if BATCH:
+        plain = TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
+        batch_mode(ctx, cfg, model, counts, giants, image, plain)
+        ctx.close()
+        return
     keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
     if VERSION == "lenet5":
         fcs = [l for l in model["layers"] if l["kind"] == "fcs"]
@@ -205,6 +217,107 @@ def wire_mode(ctx, cfg, counts, giants, image, image_rs, keys, bias_rs, client_r
           (med(share), min(share), max(share), med([100.0 * b / w for b, w in zip(tot(1), whole_wire)])))
     print("the inference over the wire takes %.3f x the inference in process (medians)" % (med(whole_wire) / med(whole_in)))
     ctx2.close()
+
+
+def batch_mode(ctx, cfg, model, counts, giants, image, plain):
+    from vpin_amd import wire as W
+    ctx2 = vpin_amd.Context(0) if WIRE else ctx  # the client's
+    n, nr, size = len(cfg.layers), len(giants), image.size
+    at = [i for i, l in enumerate(cfg.layers) if l.has_round]
+    k, r_bias, r_client = counts["prf_keys"], counts["bias_r"], counts["encryptions"] - size
+    top = max(BATCH)
+    images = [np.roll(image, (b % 8, b // 8), axis=(0, 1)) for b in range(top)]
+    expect = [plain(model, im) for im in images]
+    bound = max(g << NB_LOG for g in giants)
+    assert all(abs(v) < bound for vs, _ in expect for r in vs for v in r), "an image leaves the client's range"
+    keys = [[NM.net_key(k * b + i) for i in range(k)] for b in range(top)]
+    image_rs = [EL.splitmix_scalars(SEEDS["image_r"] + 0x1000 * b, size) for b in range(top)]
+    bias_rs = [EL.splitmix_scalars(SEEDS["bias_r"] + 0x1000 * b, r_bias) for b in range(top)]
+    client_rs = [EL.splitmix_scalars(SEEDS["client_r"] + 0x1000 * b, r_client) for b in range(top)]
+    stage = [c for c, l in zip(counts["per_round"], [cfg.layers[i] for i in at]) if l.reencrypt]  # per image, per round that encrypts again
+    med = statistics.median
+    rng = lambda xs, d=1: "%9.2f (%8.2f .. %8.2f)" % (med(xs) / d, min(xs) / d, max(xs) / d)
+    summary = []
+    for B in BATCH:
+        queue, pos = [], 0
+        for c in stage:  # stage after stage the r of all images
+            for b in range(B):
+                queue += client_rs[b][pos:pos + c]
+            pos += c
+        flat = lambda per: [v for one in per[:B] for v in one]
+        sched = VN.schedule(cfg, batch=B)
+        layers, rounds, whole, wired_rounds, wired_whole = [], [], [], [], []
+        for rep in range(REPS + 1):
+            client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue)
+            t0 = time.perf_counter()
+            scores, values, trace = VN.infer_batch(ctx, cfg, client, images[:B], image_rs[:B], keys[:B], bias_rs[:B])
+            t1 = time.perf_counter()
+            tm = VN.timings(n)
+            if rep == 0:
+                for r in range(nr):
+                    for i in range(2):
+                        assert [int(a) for a in values[r][i]] == [v for e in expect[:B] for v in e[i][r]], "B = %d round %d" % (B, r)
+                label = trace.label()
+                assert (label.n_mult, label.n_add) == (B * counts["n_mult"], B * counts["n_add"]) and trace.images == B
+                assert all(trace.layer(i).n_add == B * counts["layers"][i][1] for i in range(n)), "every layer is one call over the batch"
+            trace.free()
+            client.free()
+            if WIRE:
+                client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue)
+                a, b = socket.socketpair()
+                ws, wc = W.Wire.from_fds(a.fileno(), a.fileno(), 600000), W.Wire.from_fds(b.fileno(), b.fileno(), 600000)
+                out = {}
+
+                def server():
+                    try:
+                        tr = VN.serve(ctx, cfg, ws, flat(keys), flat(bias_rs), max_batch=None if B == 1 else B)
+                        out["tm"] = VN.timings(n)  # this thread's
+                        tr.free()
+                    except BaseException as e:  # noqa: BLE001
+                        out["error"] = e
+
+                th = threading.Thread(target=server)
+                t2 = time.perf_counter()
+                th.start()
+                _, wvalues = client.run(wc, np.concatenate([im.reshape(-1) for im in images[:B]]), flat(image_rs), sched)
+                th.join()
+                t3 = time.perf_counter()
+                assert "error" not in out, out.get("error")
+                for r in range(nr):
+                    assert np.array_equal(wvalues[r][0], values[r][0]) and np.array_equal(wvalues[r][1], values[r][1]), "round %d over the wire" % r
+                ws.free(); wc.free()
+                a.close(); b.close()
+                client.free()
+            if rep:
+                layers.append(tm["layers"])
+                rounds.append([tm["rounds"][i] for i in at])
+                whole.append((t1 - t0) * 1e3)
+                if WIRE:
+                    wired_rounds.append([out["tm"]["rounds"][i] for i in at])
+                    wired_whole.append((t3 - t2) * 1e3)
+        print("B = %d: every round of every image is the plaintext model's; ms, warm, median (min .. max) over %d runs" % (B, REPS))
+        print("%-40s %-32s %12s" % ("", "the batch", "per image"))
+        rnd = 0
+        for i, l in enumerate(cfg.layers):
+            m, a = counts["layers"][i]
+            xs = [x[i] for x in layers]
+            print("%-40s %-32s %12.3f" % ("layer %d (%s, %d + %d ops)" % (i, KINDS[l.kind], B * m, B * a), rng(xs), med(xs) / B))
+            if l.has_round:
+                xs = [x[rnd] for x in rounds]
+                print("%-40s %-32s %12.3f" % ("round %d (client, %d values)" % (rnd, sched[rnd][2]), rng(xs), med(xs) / B))
+                if WIRE:
+                    xs = [x[rnd] for x in wired_rounds]
+                    print("%-40s %-32s %12.3f" % ("round %d over the wire" % rnd, rng(xs), med(xs) / B))
+                rnd += 1
+        print("%-40s %-32s %12.3f" % ("inference (image encryption in)", rng(whole), med(whole) / B))
+        if WIRE:
+            print("%-40s %-32s %12.3f" % ("inference over the wire (set-up in)", rng(wired_whole), med(wired_whole) / B))
+        summary.append((B, med(whole), med([sum(x) for x in layers]), med([sum(x) for x in rounds]), med(wired_whole) if WIRE else 0.0))
+    print("ms per image (medians): the whole inference, the layers, the rounds" + (", the whole inference over the wire" if WIRE else ""))
+    for B, w, ls, rs, ww in summary:
+        print("B = %-4d %10.3f %10.3f %10.3f" % (B, w / B, ls / B, rs / B) + ("%10.3f" % (ww / B) if WIRE else ""))
+    if WIRE:
+        ctx2.close()
 
 
 if __name__ == "__main__":

@@ -258,6 +258,10 @@ def lib():
     L.vpin_net_trace_instances.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_net_trace_result.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_net_last_timings.argtypes = [C.POINTER(C.c_double), C.c_size_t]
+    L.vpin_net_infer_batch.argtypes = [vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.vpin_net_trace_images.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.vpin_net_trace_image_label.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_trace_image_instances.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_net_client_create.argtypes = [vp, vp, C.c_uint64, C.c_size_t, C.POINTER(C.c_uint64), vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_client_free.argtypes = [vp]
     L.vpin_net_client_free.restype = None
@@ -278,6 +282,7 @@ def lib():
     L.vpin_wire_send_error.argtypes = [vp, C.c_int, C.c_char_p]
     L.vpin_wire_bind_ctx.argtypes = [vp, vp]
     L.vpin_net_serve.argtypes = [vp, C.POINTER(NetCfg), vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_serve_batch.argtypes = [vp, C.POINTER(NetCfg), vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_client_run.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(WireRoundSpec), C.c_size_t]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]

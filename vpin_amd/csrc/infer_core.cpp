@@ -1,9 +1,11 @@
 // infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias],
 // vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
-// (lenet.cpp) and vpin_net_infer (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer validates
-// what it is given, the client's answers included.
+// (lenet.cpp) and vpin_net_infer[_batch] (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer
+// validates what it is given, the client's answers included.  A batch of B images is the same loop: every layer call and every
+// round takes the planes of all images at once, image after image (infer_core.h, Call).
 #include "infer_core.h"
 
+#include <cstring>
 #include <utility>
 
 namespace vpin::infer {
@@ -22,75 +24,98 @@ struct Pts {
   void append(const Pts& o, size_t from, size_t k) { append(o.x.data() + 32 * from, o.y.data() + 32 * from, o.inf.data() + from, k); }
 };
 
-// C planes of c1 and of c2, `times` over, in the order of the layer call
-Pts gather(Pts& c1, const Pts& c2, size_t C, size_t times, Step::Order order) {
+// the planes of the layer call: image after image, the image's C planes of c1 and of c2, `times` over, in the step's order
+Pts gather(Pts& c1, const Pts& c2, size_t B, size_t C, size_t times, Step::Order order) {
   Pts in;
-  if (order == Step::kInterleaved) {
-    const size_t per = c1.n() / C;
-    for (size_t p = 0; p < C * times; p++) {
-      in.append(c1, (p % C) * per, per);
-      in.append(c2, (p % C) * per, per);
-    }
-    return in;
-  }
-  if (times == 1) {  // c1, c2 are rebuilt from the layer's output
+  if (B == 1 && times == 1 && order == Step::kBlocked) {  // c1, c2 are rebuilt from the layer's output
     in = std::move(c1);
     in.append(c2, 0, c2.n());
     return in;
   }
-  for (size_t t = 0; t < times; t++) in.append(c1, 0, c1.n());
-  for (size_t t = 0; t < times; t++) in.append(c2, 0, c2.n());
+  const size_t img = c1.n() / B, per = img / C, n = 2 * times * c1.n();
+  in.x.reserve(32 * n); in.y.reserve(32 * n); in.inf.reserve(n);
+  for (size_t b = 0; b < B; b++) {
+    if (order == Step::kInterleaved) {
+      for (size_t p = 0; p < C * times; p++) {
+        in.append(c1, b * img + (p % C) * per, per);
+        in.append(c2, b * img + (p % C) * per, per);
+      }
+      continue;
+    }
+    for (size_t t = 0; t < times; t++) in.append(c1, b * img, img);
+    for (size_t t = 0; t < times; t++) in.append(c2, b * img, img);
+  }
   return in;
 }
 
-void split(const vpin_conv_trace& t, Step::Order order, Pts* c1, Pts* c2) {
-  const size_t per = t.oh * t.ow;
+// the output's planes back into c1 and c2, both image-major: an image's planes are the first and the second half of its P / B
+// (blocked) or the even and the odd ones
+void split(const vpin_conv_trace& t, size_t B, Step::Order order, Pts* c1, Pts* c2) {
+  const size_t per = t.oh * t.ow, planes = t.P / B;
   c1->resize(0); c2->resize(0);
+  if (order == Step::kBlocked) {  // one run of planes / 2 planes per image and half
+    const size_t run = planes / 2 * per;
+    for (size_t h = 0; h < 2 * B; h++) (h % 2 ? c2 : c1)->append(&t.out_x[32 * h * run], &t.out_y[32 * h * run], &t.out_inf[h * run], run);
+    return;
+  }
   for (size_t p = 0; p < t.P; p++)
-    ((order == Step::kInterleaved ? p % 2 : p >= t.P / 2) ? c2 : c1)
-        ->append(&t.out_x[32 * p * per], &t.out_y[32 * p * per], &t.out_inf[p * per], per);
+    (p % planes % 2 ? c2 : c1)->append(&t.out_x[32 * p * per], &t.out_y[32 * p * per], &t.out_inf[p * per], per);
 }
 
-// bias values the step encrypts, one r each
+// bias values the step encrypts per image, one r each
 size_t bias_values(const Step& s) {
   return s.kind == Step::kFc || s.kind == Step::kFcs ? s.N : s.kind == Step::kConvMc && s.bias ? s.n_out : 0;
 }
 
-// n bias values under the client's key, encrypted with the caller's r before the layer (encryptBias): the n c1 halves, then the
-// n c2 halves
-int encrypt_bias(const Call& a, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* b) {
-  Pts b2;
-  b->resize(n); b2.resize(n);
-  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, bias, r_le32, n, b->x.data(), b->y.data(), b->inf.data(), b2.x.data(), b2.y.data(),
-                                 b2.inf.data());
-  if (!rc) b->append(b2, 0, n);
-  return rc;
+// a step's n 32-byte items (PRF keys, bias r) of all B images, image after image: image b's stand at base + 32 (b * stride + ..);
+// `own` holds them when they have to be put together
+const uint8_t* of_all_images(const uint8_t* at, size_t stride, size_t n, size_t B, std::vector<uint8_t>* own) {
+  if (B == 1 || !n) return at;
+  own->resize(32 * n * B);
+  for (size_t b = 0; b < B; b++) memcpy(own->data() + 32 * n * b, at + 32 * stride * b, 32 * n);
+  return own->data();
 }
 
-// the encrypted bias, then the layer on the c1 row and the c2 row
+// every image's n bias values under the client's key, encrypted with the caller's r before the layer (encryptBias) by ONE call,
+// then per image its n c1 halves and its n c2 halves: the layer's rows 2 b and 2 b + 1, or its groups
+int encrypt_bias(const Call& a, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* out) {
+  Pts b1, b2;
+  b1.resize(a.B * n); b2.resize(a.B * n);
+  std::vector<int64_t> msgs(a.B * n);
+  for (size_t i = 0; i < a.B * n; i++) msgs[i] = bias[i % n];
+  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(), b1.inf.data(), b2.x.data(),
+                                 b2.y.data(), b2.inf.data());
+  if (rc) return rc;
+  out->resize(0);
+  for (size_t b = 0; b < a.B; b++) { out->append(b1, b * n, n); out->append(b2, b * n, n); }
+  return VPIN_OK;
+}
+
+// the encrypted bias, then the layer on every image's c1 row and c2 row
 int fc(const Call& a, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
   Pts b;
   const int rc = encrypt_bias(a, s.bias, r_le32, s.N, &b);
   if (rc) return rc;
   if (s.kind == Step::kFcs)
-    return vpin_enc_fc_signed(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, s.K, s.w, s.N, b.x.data(), b.y.data(), b.inf.data(), key,
+    return vpin_enc_fc_signed(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, s.K, s.w, s.N, b.x.data(), b.y.data(), b.inf.data(), key,
                               a.prf_bytes, out);
   std::vector<uint32_t> wu(s.K * s.N);
   for (size_t i = 0; i < s.K * s.N; i++) wu[i] = (uint32_t)s.w[i];
-  return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(), b.inf.data(),
-                     key, a.prf_bytes, out);
+  return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(),
+                     b.inf.data(), key, a.prf_bytes, out);
 }
 
-// the trained convolution; with a bias, n_out values encrypted as for fc: the c1 halves go to group 0, the c2 halves to group 1
+// the trained convolution over the groups g = 2 b + half; with a bias, n_out values per image encrypted as for fc: an image's c1
+// halves go to its first group, its c2 halves to its second
 int conv_mc(const Call& a, const Step& s, const Pts& in, size_t C, size_t H, size_t W, const uint8_t* key, const uint8_t* r_le32,
             vpin_conv_trace** out) {
   if (!s.bias)
-    return vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad, s.stride,
-                              key, a.prf_bytes, out);
+    return vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
+                              s.stride, key, a.prf_bytes, out);
   Pts b;
   const int rc = encrypt_bias(a, s.bias, r_le32, s.n_out, &b);
   if (rc) return rc;
-  return vpin_enc_conv2d_mc_bias(a.c, in.x.data(), in.y.data(), in.inf.data(), 2, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
+  return vpin_enc_conv2d_mc_bias(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
                                  s.stride, b.x.data(), b.y.data(), b.inf.data(), key, a.prf_bytes, out);
 }
 
@@ -127,25 +152,28 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   size_t keys = 0, bias_r = 0;
   bool any_round = false;
   for (const Step& s : steps) { keys += s.keys; bias_r += bias_values(s); any_round = any_round || s.has_round; }
-  if (a.n_keys != keys)
+  if (!a.B) return fail(VPIN_EINVAL, (who + "no image").c_str());
+  if (a.n_keys != a.B * keys)
     return fail(VPIN_EINVAL, (who + "the number of PRF keys is not one per convolution plane and fully connected row").c_str());
-  if (a.n_bias_r != bias_r)
+  if (a.n_bias_r != a.B * bias_r)
     return fail(VPIN_EINVAL, (who + "the number of bias randomness values is not one per fully connected output and biased output channel").c_str());
   if ((keys && !a.keys32) || (bias_r && (!a.bias_r_le32 || !a.baseG || !a.baseH)) || (any_round && !a.round_fn))
     return fail(VPIN_EINVAL, (who + "null argument").c_str());
   out->step_ms.assign(steps.size(), 0.0);
   out->round_ms.assign(steps.size(), 0.0);
   enc::Lap total, lap;
-  const uint8_t* key = a.keys32;
+  const size_t B = a.B;
+  const uint8_t* key = a.keys32;  // image 0's, of the step at hand; image b's stand b * keys (b * bias_r) items on
   const uint8_t* br = a.bias_r_le32;
   size_t C = a.C, H = a.H, W = a.W;
-  Pts c1, c2;  // what the server holds
-  c1.append(a.c1x, a.c1y, a.c1inf, C * H * W);
-  c2.append(a.c2x, a.c2y, a.c2inf, C * H * W);
+  Pts c1, c2;  // what the server holds: [b][C][H][W] each
+  c1.append(a.c1x, a.c1y, a.c1inf, B * C * H * W);
+  c2.append(a.c2x, a.c2y, a.c2inf, B * C * H * W);
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     int rc = VPIN_OK;
     if (s.sum_table) {
+      if (B != 1) return fail(VPIN_EINVAL, (who + s.name + ": the plane sums take one image").c_str());
       for (Pts* p : {&c1, &c2}) {
         Pts sum;
         sum.resize(s.sum_out * H * W);
@@ -157,26 +185,29 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
       C = s.sum_out;
     }
     if (s.kind == Step::kFc || s.kind == Step::kFcs) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
-    const Pts in = gather(c1, c2, C, s.repeat, s.order);
+    const Pts in = gather(c1, c2, B, C, s.repeat, s.order);
     C *= s.repeat;
+    std::vector<uint8_t> own_keys, own_r;
+    const uint8_t* k = of_all_images(key, keys, s.keys, B, &own_keys);
+    const uint8_t* r = of_all_images(br, bias_r, bias_values(s), B, &own_r);
     vpin_conv_trace* tr = nullptr;
     if (s.kind == Step::kConv) {
-      rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, key,
+      rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), B * 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, k,
                            a.prf_bytes, &tr);
     } else if (s.kind == Step::kConvMc) {
-      rc = conv_mc(a, s, in, C, H, W, key, br, &tr);
+      rc = conv_mc(a, s, in, C, H, W, k, r, &tr);
     } else if (s.kind == Step::kPool) {
-      rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
+      rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), B * 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
     } else {
-      rc = fc(a, s, in, key, br, &tr);
+      rc = fc(a, s, in, k, r, &tr);
     }
     br += 32 * bias_values(s);
     key += 32 * s.keys;
     out->step_ms[i] = 1e3 * lap();
     if (rc) return named(rc, s.name);
     out->step.push_back(tr);
-    split(*tr, s.order, &c1, &c2);
-    C = tr->P / 2; H = tr->oh; W = tr->ow;
+    split(*tr, B, s.order, &c1, &c2);
+    C = tr->P / (2 * B); H = tr->oh; W = tr->ow;
     if (!s.has_round) continue;
     rc = interact(a, s, &c1, &c2);
     out->round_ms[i] = 1e3 * lap();

@@ -38,7 +38,10 @@ struct Step {
   std::string round_name;
 };
 
-// what both entry points are given, and the input's shape
+// what both entry points are given, and the input's shape.  B images go through every step in ONE layer call and every round in
+// ONE callback: c1 and c2 hold [b][C][H][W], a layer call's planes are [b] of what Step::Order says for one image, keys32 and
+// bias_r_le32 are image-major (n_keys, n_bias_r: B times what the steps consume), and each step is handed its keys and bias r of
+// all images, image after image.  A step with a sum_table is for B = 1 (vpin_lenet_infer)
 struct Call {
   vpin_ctx* c;
   const char* who;  // the entry point's name, in front of every error text
@@ -52,6 +55,7 @@ struct Call {
   size_t n_bias_r;
   vpin_lenet_round_fn round_fn;
   void* user;
+  size_t B = 1;  // the images; last, so that a caller of one image names none
 };
 
 // per step the trace of its layer call, owned; host-clock milliseconds per step (plane sums included), per round (0: none) and in all
@@ -67,7 +71,7 @@ struct Result {
   }
 };
 
-// VPIN_EINVAL when n_keys or n_bias_r is not what the steps consume, or an array they need is NULL; a failing step or round
+// VPIN_EINVAL when n_keys or n_bias_r is not B times what the steps consume, or an array they need is NULL; a failing step or round
 // returns its code behind "<who>: <name>: ".  The timings are filled as far as the run got; the caller drops `out` on failure
 int run(const Call& call, const std::vector<Step>& steps, Result* out);
 

@@ -3,6 +3,9 @@
 // driver (infer_core.cpp).  The planes go through a layer as all c1 planes and then all c2 planes, the order of
 // callConv2_ciphertext on c1 and then on c2; that service appends every layer's operations to the same four global lists, so
 // the trace offers, beside each layer's own trace, the lists of all layers concatenated in layer order: the network's ONE label.
+// vpin_net_infer_batch is the same function over B images (vpin_net_infer: B = 1): every layer one call and every round one
+// callback over the planes of all images, image after image; the label is then the images' labels one after the other, and
+// vpin_net_trace_image_label cuts image b's own out of the layer calls' traces.
 #include <memory>
 #include <new>
 #include <string>
@@ -109,14 +112,115 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
 
 thread_local std::vector<double> g_ms;  // [0] the whole, then per layer: the layer, the round after it
 
-void append(std::vector<uint8_t>* to, const std::vector<uint8_t>& from) { to->insert(to->end(), from.begin(), from.end()); }
+// image b's share of a layer call's lists behind L's.  Every layer kind emits its lists plane by plane (row by row, pair by pair)
+// and an image's planes stand together, so the share is the b-th of B equal parts
+void append_image(vpin_conv_trace* L, const vpin_conv_trace& tr, size_t b, size_t B) {
+  auto part = [&](std::vector<uint8_t>* to, const std::vector<uint8_t>& from) {
+    const size_t n = from.size() / B;
+    to->insert(to->end(), from.begin() + b * n, from.begin() + (b + 1) * n);
+  };
+  L->n_mult += tr.n_mult / B; L->n_add += tr.n_add / B;
+  part(&L->m_w, tr.m_w); part(&L->m_px, tr.m_px); part(&L->m_py, tr.m_py);
+  part(&L->a_px, tr.a_px); part(&L->a_py, tr.a_py); part(&L->a_rx, tr.a_rx); part(&L->a_ry, tr.a_ry); part(&L->a_rz, tr.a_rz);
+}
+
+// what a layer call at B images must not exceed: its planes, groups or rows are a grid axis of its kernels (65535), its chains'
+// terms and its outputs an int.  At B = 1 the layer itself says so, with its own text
+int fits(const char* who, const vpin_net_cfg* g, const std::vector<LayerPlan>& pl, size_t B) {
+  size_t C = g->C;
+  for (size_t i = 0; i < pl.size(); i++) {
+    const vpin_net_layer& l = g->layers[i];
+    const std::string name = std::string(who) + ": layer " + std::to_string(i) + " (" + kind_name(l.kind) + "): ";
+    const bool fc = l.kind == VPIN_NET_FC || l.kind == VPIN_NET_FCS;
+    const size_t planes = fc ? 2 * B : 2 * B * C;
+    if (planes > 65535)
+      return fail(VPIN_EINVAL, (name + "2 B * C = " + std::to_string(planes) + " planes are more than the 65535 a layer call takes").c_str());
+    if (fc && 2 * B * l.K >= ((size_t)1 << 31))
+      return fail(VPIN_EINVAL, (name + "2 B * K = " + std::to_string(2 * B * l.K) + " chain terms are 2^31 or more").c_str());
+    if (2 * B * pl[i].oC * pl[i].oH * pl[i].oW >= ((size_t)1 << 31))
+      return fail(VPIN_EINVAL, (name + "the outputs of all images are 2^31 or more").c_str());
+    C = pl[i].oC;
+  }
+  return VPIN_OK;
+}
 
 }  // namespace
 
 struct vpin_net_trace {
-  vpin::infer::Result run;  // per layer the trace of its layer call
-  vpin_conv_trace label;    // the lists of all layers in layer order; the output and dims of the last layer
+  vpin::infer::Result run;  // per layer the trace of its layer call over all images
+  vpin_conv_trace label;    // per image, in image order, the lists of all layers in layer order; the output and dims of the last layer
+  size_t B = 1;
+  mutable std::vector<std::unique_ptr<vpin_conv_trace>> image;  // B > 1: image b's label once it has been asked for
 };
+
+namespace {
+
+// vpin_net_infer (B = 1) and vpin_net_infer_batch: the steps of the one driver and the label
+int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+          const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t* keys32,
+          size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out) {
+  if (out) *out = nullptr;
+  if (!c || !g || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !out) return fail(VPIN_EINVAL, (std::string(who) + ": null argument").c_str());
+  if (!B || B > VPIN_NET_MAX_BATCH)
+    return fail(VPIN_EINVAL, (std::string(who) + ": B = " + std::to_string(B) + " is outside 1 .. VPIN_NET_MAX_BATCH (" +
+                              std::to_string(VPIN_NET_MAX_BATCH) + ")").c_str());
+  std::vector<LayerPlan> pl;
+  int bad = plan(g, true, &pl);
+  if (!bad && B > 1) bad = fits(who, g, pl, B);
+  if (bad) return bad;
+  std::vector<Step> steps(pl.size());
+  for (size_t i = 0; i < pl.size(); i++) {
+    const vpin_net_layer& l = g->layers[i];
+    Step& s = steps[i];
+    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc
+             : l.kind == VPIN_NET_FCS ? Step::kFcs : Step::kFc;
+    s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
+    if (l.kind == VPIN_NET_CONVMC) { s.n_out = l.n_out; s.w_mc = l.w_mc; s.connect = l.connect; }  // no other kind reads them
+    s.k = l.k; s.scale_le16 = l.scale_le16;
+    s.K = l.K; s.N = l.N; s.w = l.w; s.bias = l.bias;
+    s.keys = pl[i].keys;
+    s.name = "layer " + std::to_string(i) + " (" + kind_name(l.kind) + ")";
+    s.has_round = pl[i].round >= 0;
+    s.round = pl[i].round; s.relu = l.relu; s.shift_bits = l.shift_bits; s.reencrypt = l.reencrypt;
+    s.round_name = "round " + std::to_string(pl[i].round);
+  }
+  std::unique_ptr<vpin_net_trace> t(new (std::nothrow) vpin_net_trace());
+  if (!t) return VPIN_ENOMEM;
+  t->B = B;
+  const vpin::infer::Call call{c, who, g->prf_bytes, g->C, g->H, g->W, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH,
+                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, B};
+  const vpin::infer::Result& res = t->run;
+  const int rc = vpin::infer::run(call, steps, &t->run);
+  g_ms.assign(1 + 2 * pl.size(), 0.0);
+  for (size_t i = 0; i < res.step_ms.size(); i++) { g_ms[1 + 2 * i] = res.step_ms[i]; g_ms[2 + 2 * i] = res.round_ms[i]; }
+  if (rc == VPIN_EINVAL && B > 1 && res.step.empty() && !res.step_ms.empty() && res.step_ms[0] > 0.0) {  // layer 0 ran and failed
+    // the first layer refuses the caller's input without saying which point: of a batch the caller wants to know whose.  The
+    // packing names the first point that is not a point of E2, counted over the whole batch (image = index / (C H W))
+    const std::string text = vpin_last_error();
+    const size_t n = B * g->C * g->H * g->W;
+    std::vector<uint8_t> packed(32 * n);
+    for (int half = 0; half < 2; half++)
+      if (vpin_e2_pack(c, half ? c2x : c1x, half ? c2y : c1y, half ? c2inf : c1inf, n, packed.data()) == VPIN_EINVAL)
+        return fail(rc, (text + "; the input's " + (half ? "c2" : "c1") + ": " + vpin_last_error()).c_str());
+    return fail(rc, text.c_str());
+  }
+  if (rc) return rc;
+
+  // the one label: what the reference leaves in points_mult, weights_array, point_one_Add and point_two_Add, image after image
+  vpin::enc::Lap lap;
+  vpin_conv_trace& L = t->label;
+  const vpin_conv_trace* last = res.step.back();
+  L.P = last->P; L.oh = last->oh; L.ow = last->ow;
+  L.out_x = last->out_x; L.out_y = last->out_y; L.out_inf = last->out_inf;
+  for (size_t b = 0; b < B; b++)
+    for (const vpin_conv_trace* tr : res.step) append_image(&L, *tr, b, B);
+  t->image.resize(B);
+  g_ms[0] = res.total_ms + 1e3 * lap();  // the whole, the label included
+  *out = t.release();
+  return VPIN_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -142,51 +246,50 @@ void vpin_net_trace_free(vpin_net_trace* t) { delete t; }
 int vpin_net_infer(vpin_ctx* c, const vpin_net_cfg* g, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x,
                    const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t* keys32,
                    size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out) {
-  if (out) *out = nullptr;
-  if (!c || !g || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !out) return fail(VPIN_EINVAL, "vpin_net_infer: null argument");
-  std::vector<LayerPlan> pl;
-  const int bad = plan(g, true, &pl);
-  if (bad) return bad;
-  std::vector<Step> steps(pl.size());
-  for (size_t i = 0; i < pl.size(); i++) {
-    const vpin_net_layer& l = g->layers[i];
-    Step& s = steps[i];
-    s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc
-             : l.kind == VPIN_NET_FCS ? Step::kFcs : Step::kFc;
-    s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
-    if (l.kind == VPIN_NET_CONVMC) { s.n_out = l.n_out; s.w_mc = l.w_mc; s.connect = l.connect; }  // no other kind reads them
-    s.k = l.k; s.scale_le16 = l.scale_le16;
-    s.K = l.K; s.N = l.N; s.w = l.w; s.bias = l.bias;
-    s.keys = pl[i].keys;
-    s.name = "layer " + std::to_string(i) + " (" + kind_name(l.kind) + ")";
-    s.has_round = pl[i].round >= 0;
-    s.round = pl[i].round; s.relu = l.relu; s.shift_bits = l.shift_bits; s.reencrypt = l.reencrypt;
-    s.round_name = "round " + std::to_string(pl[i].round);
-  }
-  std::unique_ptr<vpin_net_trace> t(new (std::nothrow) vpin_net_trace());
-  if (!t) return VPIN_ENOMEM;
-  const vpin::infer::Call call{c, "vpin_net_infer", g->prf_bytes, g->C, g->H, g->W, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH,
-                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user};
-  const vpin::infer::Result& res = t->run;
-  const int rc = vpin::infer::run(call, steps, &t->run);
-  g_ms.assign(1 + 2 * pl.size(), 0.0);
-  for (size_t i = 0; i < res.step_ms.size(); i++) { g_ms[1 + 2 * i] = res.step_ms[i]; g_ms[2 + 2 * i] = res.round_ms[i]; }
-  if (rc) return rc;
+  return infer("vpin_net_infer", c, g, 1, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH, keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, out);
+}
 
-  // the one label: what the reference leaves in points_mult, weights_array, point_one_Add and point_two_Add
-  vpin::enc::Lap lap;
-  vpin_conv_trace& L = t->label;
-  const vpin_conv_trace* last = res.step.back();
-  L.P = last->P; L.oh = last->oh; L.ow = last->ow;
-  L.out_x = last->out_x; L.out_y = last->out_y; L.out_inf = last->out_inf;
-  for (const vpin_conv_trace* tr : res.step) {
-    L.n_mult += tr->n_mult; L.n_add += tr->n_add;
-    append(&L.m_w, tr->m_w); append(&L.m_px, tr->m_px); append(&L.m_py, tr->m_py);
-    append(&L.a_px, tr->a_px); append(&L.a_py, tr->a_py); append(&L.a_rx, tr->a_rx); append(&L.a_ry, tr->a_ry); append(&L.a_rz, tr->a_rz);
-  }
-  g_ms[0] = res.total_ms + 1e3 * lap();  // the whole, the label included
-  *out = t.release();
+int vpin_net_infer_batch(vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                         const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                         const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
+                         void* user, vpin_net_trace** out) {
+  return infer("vpin_net_infer_batch", c, g, B, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH, keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user,
+               out);
+}
+
+int vpin_net_trace_images(const vpin_net_trace* t, size_t* B) {
+  if (!t || !B) return fail(VPIN_EINVAL, "vpin_net_trace_images: null argument");
+  *B = t->B;
   return VPIN_OK;
+}
+
+int vpin_net_trace_image_label(const vpin_net_trace* t, size_t b, const vpin_conv_trace** out) {
+  if (out) *out = nullptr;
+  if (!t || !out || b >= t->B) return fail(VPIN_EINVAL, "vpin_net_trace_image_label: null argument or no such image");
+  if (t->B == 1) { *out = &t->label; return VPIN_OK; }
+  if (!t->image[b]) {
+    std::unique_ptr<vpin_conv_trace> L(new (std::nothrow) vpin_conv_trace());
+    if (!L) return VPIN_ENOMEM;
+    const vpin_conv_trace& all = t->label;  // its output is the last layer call's: image b's planes are the b-th part
+    const size_t n = all.out_inf.size() / t->B;
+    L->P = all.P / t->B; L->oh = all.oh; L->ow = all.ow;
+    L->out_x.assign(all.out_x.begin() + 32 * b * n, all.out_x.begin() + 32 * (b + 1) * n);
+    L->out_y.assign(all.out_y.begin() + 32 * b * n, all.out_y.begin() + 32 * (b + 1) * n);
+    L->out_inf.assign(all.out_inf.begin() + b * n, all.out_inf.begin() + (b + 1) * n);
+    for (const vpin_conv_trace* tr : t->run.step) append_image(L.get(), *tr, b, t->B);
+    t->image[b] = std::move(L);
+  }
+  *out = t->image[b].get();
+  return VPIN_OK;
+}
+
+int vpin_net_trace_image_instances(vpin_ctx* c, const vpin_net_trace* t, size_t b, vpin_dev_instance** mult_out, vpin_dev_instance** add_out) {
+  if (mult_out) *mult_out = nullptr;
+  if (add_out) *add_out = nullptr;
+  if (!c || !t || !mult_out || !add_out) return fail(VPIN_EINVAL, "vpin_net_trace_image_instances: null argument");
+  const vpin_conv_trace* L = nullptr;
+  const int rc = vpin_net_trace_image_label(t, b, &L);
+  return rc ? rc : vpin_conv_trace_instances(c, L, mult_out, add_out);
 }
 
 int vpin_net_trace_layers(const vpin_net_trace* t, size_t* n) {
@@ -218,7 +321,7 @@ int vpin_net_trace_instances(vpin_ctx* c, const vpin_net_trace* t, vpin_dev_inst
 
 int vpin_net_trace_result(const vpin_net_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf, size_t* n) {
   if (!t || !x || !y || !inf || !n) return fail(VPIN_EINVAL, "vpin_net_trace_result: null argument");
-  *n = t->label.out_inf.size() / 2;
+  *n = t->label.out_inf.size() / (2 * t->B);
   return vpin_conv_trace_output(&t->label, x, y, inf);
 }
 

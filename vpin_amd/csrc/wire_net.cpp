@@ -2,6 +2,8 @@
 // (infer_core.cpp interact) over a byte stream, and vpin_net_serve, which reads the client's public key and encrypted input off the
 // stream, runs vpin_net_infer with that callback and reports the end, or its failure, to the peer.  The server holds no secret
 // key.  Everything that arrives is unpacked on the device (e2_wire.hip) and so validated before a layer sees it.
+// vpin_net_serve_batch is the same endpoint for up to max_batch images: it reads B off INPUT's cnt and runs vpin_net_infer_batch;
+// every frame is as it was, with B times the single run's cnt.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -81,10 +83,11 @@ struct Bases {
   ~Bases() { vpin_e2_base_free(h); vpin_e2_base_free(g); }
 };
 
-int serve(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r,
-          vpin_net_trace** out) {
-  const char* who = "vpin_net_serve";
-  char why[200];
+// max_batch = 0: vpin_net_serve, one image and its own texts; otherwise vpin_net_serve_batch, B read off INPUT, k and r the
+// configuration's keys and bias r per image
+int serve(const char* who, vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, size_t max_batch, size_t k, size_t r, const uint8_t* keys32,
+          size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out) {
+  char why[240];
   vpin_wire_header h;
   std::vector<uint8_t> p;
   int rc = recv_header(w, &h);
@@ -99,24 +102,34 @@ int serve(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* key
   Lap lap;
   rc = vpin_e2_unpack(c, p.data(), 1, hx, hy, &hinf);
   add_ms(w, 0, kUnpack, lap());
-  if (rc) return named(rc, "vpin_net_serve: HELLO");
-  if (hinf) return fail(VPIN_EINVAL, "vpin_net_serve: HELLO: the public key is the identity");
+  if (rc) return named(rc, (std::string(who) + ": HELLO").c_str());
+  if (hinf) return fail(VPIN_EINVAL, (std::string(who) + ": HELLO: the public key is the identity").c_str());
   Bases b;
   if ((rc = vpin_e2_base_create(c, nullptr, nullptr, &b.g)) || (rc = vpin_e2_base_create(c, hx, hy, &b.h))) return named(rc, who);
   if ((rc = recv_header(w, &h))) return named(rc, who);
   if (h.type == VPIN_WIRE_ERROR) return peer_error(w, h, who);
-  const size_t n = cfg->C * cfg->H * cfg->W;
-  if (h.type != VPIN_WIRE_INPUT || h.cnt != n) {
-    snprintf(why, sizeof why, "%s: expected INPUT of %zu ciphertexts, the peer sent type %u with cnt %u", who, n, (unsigned)h.type, (unsigned)h.cnt);
+  const size_t per = cfg->C * cfg->H * cfg->W;
+  if (h.type != VPIN_WIRE_INPUT || (!max_batch && h.cnt != per)) {
+    snprintf(why, sizeof why, "%s: expected INPUT of %zu ciphertexts, the peer sent type %u with cnt %u", who, per, (unsigned)h.type, (unsigned)h.cnt);
+    return fail(VPIN_ESHAPE, why);
+  }
+  const size_t n = h.cnt, B = n / per;
+  if (max_batch && (n % per || B < 1 || B > max_batch)) {
+    snprintf(why, sizeof why, "%s: expected INPUT of 1 .. %zu images of %zu ciphertexts, the peer sent cnt %u", who, max_batch, per, (unsigned)h.cnt);
     return fail(VPIN_ESHAPE, why);
   }
   if ((rc = recv_payload_timed(w, 0, h, &p))) return named(rc, who);
   std::vector<uint8_t> x1(32 * n), y1(32 * n), f1(n), x2(32 * n), y2(32 * n), f2(n);
-  if ((rc = unpack_pair_timed(w, 0, c, p, n, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data()))) return named(rc, "vpin_net_serve: INPUT");
+  if ((rc = unpack_pair_timed(w, 0, c, p, n, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data())))
+    return named(rc, (std::string(who) + ": INPUT").c_str());
   p.clear();
   w->ctx = c;
-  rc = vpin_net_infer(c, cfg, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data(), b.g, b.h, keys32, n_keys, bias_r_le32, n_bias_r,
-                      vpin_wire_round, w, out);
+  if (!max_batch)
+    rc = vpin_net_infer(c, cfg, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data(), b.g, b.h, keys32, n_keys, bias_r_le32, n_bias_r,
+                        vpin_wire_round, w, out);
+  else  // the first B * k keys and B * r values
+    rc = vpin_net_infer_batch(c, cfg, B, x1.data(), y1.data(), f1.data(), x2.data(), y2.data(), f2.data(), b.g, b.h, keys32, B * k, bias_r_le32,
+                              B * r, vpin_wire_round, w, out);
   if (rc) return rc;
   memset(&h, 0, sizeof h);
   h.type = VPIN_WIRE_DONE;
@@ -182,21 +195,45 @@ int vpin_wire_round(void* user, int round, int flags, int shift_bits, const uint
   return VPIN_OK;
 }
 
-int vpin_net_serve(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32,
-                   size_t n_bias_r, vpin_net_trace** out) {
+namespace {
+
+int serve_checked(const char* who, vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, size_t max_batch, const uint8_t* keys32, size_t n_keys,
+                  const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out) {
+  const std::string name(who);
   if (out) *out = nullptr;
-  if (!c || !cfg || !w || !out) return fail(VPIN_EINVAL, "vpin_net_serve: null argument");
+  if (!c || !cfg || !w || !out) return fail(VPIN_EINVAL, (name + ": null argument").c_str());
   std::vector<size_t> counts(8 + 3 * cfg->n_layers);
   int rc = vpin_net_cfg_counts(cfg, counts.data(), counts.size());  // the configuration's own rules, before anything is read
   if (!rc && (!cfg->n_layers || !cfg->layers[cfg->n_layers - 1].has_round))
-    rc = fail(VPIN_EINVAL, "vpin_net_serve: the last layer has no round: its result would never reach the client");
+    rc = fail(VPIN_EINVAL, (name + ": the last layer has no round: its result would never reach the client").c_str());
+  if (!rc && max_batch > VPIN_NET_MAX_BATCH) rc = fail(VPIN_EINVAL, (name + ": max_batch is outside 1 .. VPIN_NET_MAX_BATCH").c_str());
+  if (!rc && max_batch && (n_keys != max_batch * counts[6] || n_bias_r != max_batch * counts[7]))
+    rc = fail(VPIN_EINVAL, (name + ": n_keys or n_bias_r is not max_batch times what one image consumes").c_str());
   if (!rc) {
     vpin_ctx* bound = w->ctx;
-    rc = serve(c, cfg, w, keys32, n_keys, bias_r_le32, n_bias_r, out);
+    rc = serve(who, c, cfg, w, max_batch, counts[6], counts[7], keys32, n_keys, bias_r_le32, n_bias_r, out);
     w->ctx = bound;
   }
   if (rc && rc != VPIN_ECOMM) send_error(w, rc, vpin_last_error());  // the peer is gone or has said so itself otherwise
   return rc;
+}
+
+}  // namespace
+
+int vpin_net_serve(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32,
+                   size_t n_bias_r, vpin_net_trace** out) {
+  return serve_checked("vpin_net_serve", c, cfg, w, 0, keys32, n_keys, bias_r_le32, n_bias_r, out);
+}
+
+int vpin_net_serve_batch(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, size_t max_batch, const uint8_t* keys32, size_t n_keys,
+                         const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out) {
+  if (!max_batch) {
+    if (out) *out = nullptr;
+    const int rc = fail(VPIN_EINVAL, "vpin_net_serve_batch: max_batch is outside 1 .. VPIN_NET_MAX_BATCH");
+    if (w) send_error(w, rc, vpin_last_error());
+    return rc;
+  }
+  return serve_checked("vpin_net_serve_batch", c, cfg, w, max_batch, keys32, n_keys, bias_r_le32, n_bias_r, out);
 }
 
 }  // extern "C"

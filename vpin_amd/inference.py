@@ -118,14 +118,19 @@ class Trace:
         _chk(getattr(lib(), name)(self.ctx.h, self.h, *label, C.byref(hm), C.byref(ha)), name)
         return (DevInstance(self.ctx, hm) if hm.value else None), (DevInstance(self.ctx, ha) if ha.value else None)
 
+    images = 1
+
     def result(self):
-        """the last layer's ciphertext -> (c1, c2), each (x, y, inf)"""
+        """the last layer's ciphertext -> (c1, c2), each (x, y, inf); of a batch, every array with the image in front"""
         x, y, f, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
         _chk(getattr(lib(), self.prefix + "_result")(self.h, C.byref(x), C.byref(y), C.byref(f), C.byref(n)), self.prefix + "_result")
-        n = n.value
+        n, b = n.value, self.images
         get = lambda p, k: np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8).copy()
-        xs, ys, fs = get(x, 64 * n).reshape(2, n, 32), get(y, 64 * n).reshape(2, n, 32), get(f, 2 * n).reshape(2, n)
-        return (xs[0], ys[0], fs[0]), (xs[1], ys[1], fs[1])
+        xs, ys, fs = get(x, 64 * n * b).reshape(b, 2, n, 32), get(y, 64 * n * b).reshape(b, 2, n, 32), get(f, 2 * n * b).reshape(b, 2, n)
+        if b == 1:
+            xs, ys, fs = xs[0], ys[0], fs[0]
+            return (xs[0], ys[0], fs[0]), (xs[1], ys[1], fs[1])
+        return (xs[:, 0], ys[:, 0], fs[:, 0]), (xs[:, 1], ys[:, 1], fs[:, 1])
 
     def free(self):
         if self.h:
@@ -133,9 +138,10 @@ class Trace:
             self.h = None
 
 
-def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user):
+def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user, batch=None):
     """`name` = vpin_lenet_infer or vpin_net_infer over the C configuration cfg_c -> the trace's handle.  c1, c2: (x, y, inf) of
-    the input points; keys: 32-byte keys in call order; bias_rs: ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer"""
+    the input points; keys: 32-byte keys in call order; bias_rs: ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer.
+    batch: the B of vpin_net_infer_batch, which takes it behind the configuration; everything is then image-major"""
     x1, y1, f1 = ctx._points(*c1)
     x2, y2, f2 = ctx._points(*c2)
     k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
@@ -143,8 +149,8 @@ def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn,
     h = C.c_void_p()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     fn = C.cast(round_fn, C.c_void_p)
-    rc = getattr(lib(), name)(ctx.h, C.byref(cfg_c), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h, p(k), len(keys), p(r),
-                              len(bias_rs), fn, user, C.byref(h))
+    rc = getattr(lib(), name)(ctx.h, C.byref(cfg_c), *([] if batch is None else [batch]), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h,
+                              p(k), len(keys), p(r), len(bias_rs), fn, user, C.byref(h))
     if rc:
         assert not h.value
         err, lib_text = getattr(round_fn, "error", None), lib().vpin_last_error().decode()

@@ -108,12 +108,13 @@ class Config:
     def max_giants(self):
         return [int(l.max_giant) for l in self.layers if l.has_round]
 
-    def counts(self):
+    def counts(self, batch=1):
+        """what a run consumes (vpin_net_cfg_counts); of a batch, B times as much of everything but the layers and the rounds"""
         n = len(self.layers)
         out = (C.c_size_t * (8 + 3 * n))()
         cfg = self.c
         _chk(lib().vpin_net_cfg_counts(C.byref(cfg), out, len(out)), "vpin_net_cfg_counts")
-        o = [int(v) for v in out]
+        o = [int(v) if i < 2 else batch * int(v) for i, v in enumerate(out)]  # out[0], out[1]: the layers and the rounds
         per = [tuple(o[8 + 3 * i:11 + 3 * i]) for i in range(n)]
         return dict(layers=[(m, a) for m, a, _ in per], per_round=[d for (_, _, d), l in zip(per, self.layers) if l.has_round], n_mult=o[2],
                     n_add=o[3], decryptions=o[4], encryptions=o[5], prf_keys=o[6], bias_r=o[7], rounds=o[1])
@@ -166,7 +167,8 @@ def lenet5_config(conv1, b1, conv2, b2, fc, bfc, fc1, bfc1, fc2, bfc2, rounds, p
 
 
 class Trace(inference.Trace):
-    """vpin_net_trace: per layer the ConvTrace of its layer call, and the label, all borrowed"""
+    """vpin_net_trace: per layer the ConvTrace of its layer call, and the label, all borrowed.  Of a batch (images > 1) a layer
+    is the one call over all images, the label the images' labels in image order; image_label(b) is image b's own"""
     prefix = "vpin_net_trace"
 
     def __init__(self, ctx, handle):
@@ -174,6 +176,8 @@ class Trace(inference.Trace):
         n = C.c_size_t()
         _chk(lib().vpin_net_trace_layers(handle, C.byref(n)), "vpin_net_trace_layers")
         self.n_layers = n.value
+        _chk(lib().vpin_net_trace_images(handle, C.byref(n)), "vpin_net_trace_images")
+        self.images = n.value
 
     def layer(self, i):
         h = C.c_void_p()
@@ -189,6 +193,17 @@ class Trace(inference.Trace):
     def instances(self):
         return self._instances()
 
+    def image_label(self, b):
+        """image b's label: what label() is for that image run alone"""
+        h = C.c_void_p()
+        _chk(lib().vpin_net_trace_image_label(self.h, b, C.byref(h)), "vpin_net_trace_image_label")
+        return self._borrowed(h)
+
+    def image_instances(self, b):
+        hm, ha = C.c_void_p(), C.c_void_p()
+        _chk(lib().vpin_net_trace_image_instances(self.ctx.h, self.h, b, C.byref(hm), C.byref(ha)), "vpin_net_trace_image_instances")
+        return (inference.DevInstance(self.ctx, hm) if hm.value else None), (inference.DevInstance(self.ctx, ha) if ha.value else None)
+
 
 def timings(n_layers):
     """host-clock ms of the last run: dict(total, layers = [ms], rounds = [ms, 0 where a layer has no round])"""
@@ -197,10 +212,14 @@ def timings(n_layers):
     return dict(total=float(out[0]), layers=[float(out[1 + 2 * i]) for i in range(n_layers)], rounds=[float(out[2 + 2 * i]) for i in range(n_layers)])
 
 
-def run(ctx, cfg, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user=None):
+def run(ctx, cfg, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user=None, batch=1):
     """vpin_net_infer -> Trace.  c1, c2: (x, y, inf) of the C * H * W input points; keys: 32-byte keys in call order; bias_rs:
-    ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer"""
-    return Trace(ctx, inference.run_infer("vpin_net_infer", ctx, cfg.c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user))
+    ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer.  batch != 1 (or None for vpin_net_infer_batch with B = 1):
+    vpin_net_infer_batch over B times the points, keys and bias_rs, all image-major"""
+    if batch == 1:
+        return Trace(ctx, inference.run_infer("vpin_net_infer", ctx, cfg.c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user))
+    return Trace(ctx, inference.run_infer("vpin_net_infer_batch", ctx, cfg.c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user,
+                                          batch=1 if batch is None else batch))
 
 
 def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
@@ -209,23 +228,43 @@ def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
     return inference.infer(run, ctx, cfg, client, image, image_rs, keys, bias_rs)
 
 
-def schedule(cfg):
-    """what the client of `cfg` agrees to: per round (flags, shift_bits, cnt) from the layers' rounds and vpin_net_cfg_counts.  The
-    client holds its own copy and answers no round that differs (Client.run)"""
-    per = cfg.counts()["per_round"]
+def infer_batch(ctx, cfg, client, images, image_rs, keys, bias_rs):
+    """infer over B images at once (vpin_net_infer_batch).  images: B x (C x H x W) ints; image_rs: B x (C H W) ints; keys: B x k
+    keys and bias_rs: B x r ints, per image what a single run takes; the client's queue of r holds, stage after stage (the input,
+    round 0, round 1, ..), the r of all images.  Returns (scores[B][n], rounds, trace): per round its (v, act) over the whole batch,
+    image-major"""
+    imgs = [np.asarray(im, dtype=np.int64).reshape(-1) for im in images]
+    b = len(imgs)
+    c1, c2 = client.encrypt(np.concatenate(imgs), [r for rs in image_rs for r in rs])
+    trace = run(ctx, cfg, c1, c2, client.base_g, client.base_h, [k for ks in keys for k in ks], [r for rs in bias_rs for r in rs],
+                client.round_fn, client.user, batch=None if b == 1 else b)
+    rounds = [client.values(client.first_round + r) for r in range(client.n_rounds)]
+    return rounds[-1][1].reshape(b, -1), rounds, trace
+
+
+def schedule(cfg, batch=1):
+    """what the client of `cfg` agrees to: per round (flags, shift_bits, cnt) from the layers' rounds and vpin_net_cfg_counts, cnt
+    times the images of a batch.  The client holds its own copy and answers no round that differs (Client.run)"""
+    per = cfg.counts(batch)["per_round"]
     rounds = [l for l in cfg.layers if l.has_round]
     return [((RELU if l.relu else 0) | (REENCRYPT if l.reencrypt else 0), int(l.shift_bits), int(n)) for l, n in zip(rounds, per)]
 
 
-def serve(ctx, cfg, wire, keys, bias_rs):
+def serve(ctx, cfg, wire, keys, bias_rs, max_batch=1):
     """vpin_net_serve -> Trace: the server's endpoint over a vpin_amd.wire.Wire.  Reads the client's public key and encrypted input
-    off the wire, runs the layers with every round sent to the peer, sends DONE; a failure goes to the peer as ERROR and is raised"""
+    off the wire, runs the layers with every round sent to the peer, sends DONE; a failure goes to the peer as ERROR and is raised.
+    max_batch != 1 (or None for vpin_net_serve_batch with max_batch = 1): vpin_net_serve_batch, which reads the number of images off
+    the input; keys and bias_rs are then flat, max_batch times one image's"""
     k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
     r = ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
     h = C.c_void_p()
     cfg_c = cfg.c
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    _chk(lib().vpin_net_serve(ctx.h, C.byref(cfg_c), wire.h, p(k), len(keys), p(r), len(bias_rs), C.byref(h)), "vpin_net_serve")
+    if max_batch == 1:
+        _chk(lib().vpin_net_serve(ctx.h, C.byref(cfg_c), wire.h, p(k), len(keys), p(r), len(bias_rs), C.byref(h)), "vpin_net_serve")
+    else:
+        _chk(lib().vpin_net_serve_batch(ctx.h, C.byref(cfg_c), wire.h, 1 if max_batch is None else max_batch, p(k), len(keys), p(r), len(bias_rs),
+                                        C.byref(h)), "vpin_net_serve_batch")
     return Trace(ctx, h)
 
 
