@@ -726,70 +726,116 @@ static int product_prove(vpin_ctx* c, vpin::SparkForest& f, int npc, DotpCtx* do
 
 static thread_local double g_spark_timings[8];
 
-// SparseMatPolyEvalProof::prove (sparse_mlpoly.rs:1466-1533) -> bincode(R1CSEvalProof) appended to w
-static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vector<Fq>& rx, const std::vector<Fq>& ry,
-                       const Fq evals[3], Transcript& tr, Transcript& tape, Writer& w) {
-  const size_t N = d->N, M = d->M, lgN = log2z(N), lgM = log2z(M);
-  if (N < 4 || M < 4 || rx.size() != d->nx || ry.size() != d->ny) return VPIN_ESHAPE;
-  int rc;
-  const Shape sh{d->nx, d->ny, N, M, lgN + 4, std::max(d->nx, d->ny) + 1, lgN + 3};
-  const PcGens *g_ops = nullptr, *g_mem = nullptr, *g_derefs = nullptr;
-  // the longest stream first: a later, longer request would rebuild the table and drop earlier views
-  if ((rc = get_view(c, std::max(sh.v_ops, sh.v_mem), &g_ops)) || (rc = get_view(c, sh.v_ops, &g_ops)) ||
-      (rc = get_view(c, sh.v_mem, &g_mem)) || (rc = get_view(c, sh.v_derefs, &g_derefs)))
-    return rc;
-  TableGuard tg(c);
-  auto t0 = Clock::now();
+// split by whole circuits: each of `cnt` scalars comes from the one rank that computed it (owner[i]; the others send zero)
+static int dist_pick(vpin_ctx* c, const DistPlan& pl, const Fq* mine, size_t cnt, const int* owner, Fq* out, const char* tag) {
+  std::vector<Fq> all(cnt * (size_t)pl.world);
+  int rc = vpin::comm_allgather_ctx(c, mine, all.data(), cnt * 32, tag);
+  if (rc) return rc;
+  for (size_t i = 0; i < cnt; i++) out[i] = all[cnt * (size_t)owner[i] + i];
+  return VPIN_OK;
+}
 
+// One SparseMatPolyEvalProof::prove in flight: what the stages below (one per timing slot) hand to each other.  The three
+// configurations -- one GPU (!dz), split by whole circuits (dz && !st), split by residue class (st) -- are plain branches
+// inside the stages.
+struct SparkProof {
+  vpin_ctx* c;
+  const vpin_spark_decomm* d;
+  const std::vector<Fq>&rx, &ry;
+  const Fq* evals;
+  Transcript &tr, &tape;
+  const size_t N, M, lgN, lgM;
+  const PcGens *g_ops = nullptr, *g_mem = nullptr, *g_derefs = nullptr;
+  TableGuard tg;
   // one proof over several GPUs (vpin_ctx_set_comm): every rank is here with the same transcript state
   DistPlan plan;
   const DistPlan* dz = nullptr;
-  if (c->comm && c->comm->world > 1) {
-    if (c->comm->world > 12) return VPIN_EINVAL;  // every rank owns at least one of the 12 ops circuits
-    plan_init(plan, c->comm);
-    dz = &plan;
-    // a power-of-two world splits every circuit by residue class (product_prove: perfectly balanced, and the derefs
-    // gather, the leaves and the slices shrink with the world too); otherwise the circuits are dealt out whole
-    static const bool by_circuit = getenv("VPIN_DIST_BY_CIRCUIT") != nullptr;
-    const size_t Wz = (size_t)plan.world;
-    if (!by_circuit && (Wz & (Wz - 1)) == 0 && Wz <= 16 && N / Wz >= 4096 && M / Wz >= 4096 && g_derefs->L >= Wz)
-      plan.lw = (int)log2z(Wz);
-  }
-  const bool st = dz && dz->lw > 0;                       // split by residue class
-  const size_t Wz = dz ? (size_t)dz->world : 1, rk = dz ? (size_t)dz->rank : 0;
-  tr.append_protocol_name("Sparse polynomial evaluation proof");
+  bool st = false;                  // split by residue class
+  vpin::SparkLeaves leaves;         // the entries this rank holds of every circuit and committed polynomial: all, or (rank, world)
+  size_t Nf = 0, Mf = 0;            // leaves per tree on this rank
+  bool defer_mem = false;
+  // derefs: the whole polynomial (comb), or -- split by residue class -- the local views (spark.hip) and a shape-only handle
+  vpin_table *mem_rx = nullptr, *mem_ry = nullptr, *comb = nullptr;
+  vpin_table comb_shape;
+  vpin::DevBuf b_cloc, b_crows, b_vloc, b_ops, b_mem, b_scr;
+  vpin::fq* comb_rows = nullptr;
+  const vpin::fq *derefs = nullptr, *vals = nullptr;  // the six derefs slices and the three val slices over `leaves`
+  std::vector<CG> comm_derefs;
+  vpin::HashParams hash;
+  vpin::SparkForest f_ops, f_mem;
+  Fq pl[2][8];  // roots per side: init, read[3], write[3], audit
+  DotpCtx dotp;
+  Fq dotp_left[3], dotp_right[3];
+  Batched pf_ops, pf_mem;
+  std::vector<Fq> rand_ops, rand_mem;
+  Fq ev_derefs[6], ev_ops[15], ev_mem[2];
+  DpLog pe_derefs, pe_ops, pe_mem;
+
+  SparkProof(vpin_ctx* c_, const vpin_spark_decomm* d_, const std::vector<Fq>& rx_, const std::vector<Fq>& ry_, const Fq* evals_,
+             Transcript& tr_, Transcript& tape_)
+      : c(c_), d(d_), rx(rx_), ry(ry_), evals(evals_), tr(tr_), tape(tape_), N(d_->N), M(d_->M), lgN(log2z(d_->N)), lgM(log2z(d_->M)),
+        tg(c_), b_cloc(c_), b_crows(c_), b_vloc(c_), b_ops(c_), b_mem(c_), b_scr(c_) {}
+  bool by_circuit() const { return dz && !st; }
+};
+
+static int split_plan(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  if (!(c->comm && c->comm->world > 1)) return VPIN_OK;
+  if (c->comm->world > 12) return VPIN_EINVAL;  // every rank owns at least one of the 12 ops circuits
+  plan_init(S.plan, c->comm);
+  S.dz = &S.plan;
+  // a power-of-two world splits every circuit by residue class (product_prove: perfectly balanced, and the derefs
+  // gather, the leaves and the slices shrink with the world too); otherwise the circuits are dealt out whole
+  static const bool by_circuit = getenv("VPIN_DIST_BY_CIRCUIT") != nullptr;
+  const size_t Wz = (size_t)S.plan.world;
+  if (!by_circuit && (Wz & (Wz - 1)) == 0 && Wz <= 16 && S.N / Wz >= 4096 && S.M / Wz >= 4096 && S.g_derefs->L >= Wz)
+    S.plan.lw = (int)log2z(Wz);
+  S.st = S.plan.lw > 0;
+  if (S.st) { S.leaves.r0 = (size_t)S.plan.rank; S.leaves.step = Wz; }
+  return VPIN_OK;
+}
+
+// Derefs (sparse_mlpoly.rs:525-531,56-71) and their commitment
+static int stage_derefs(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const vpin_spark_decomm* d = S.d;
+  const DistPlan* dz = S.dz;
+  const PcGens* g_derefs = S.g_derefs;
+  const size_t N = S.N;
+  int rc;
+  S.tr.append_protocol_name("Sparse polynomial evaluation proof");
   // equalize (sparse_mlpoly.rs:1448-1465) + the two memories eq(rx_ext, .), eq(ry_ext, .)
   const size_t nm = std::max(d->nx, d->ny);
   std::vector<Fq> rx_ext(nm, Fq::zero()), ry_ext(nm, Fq::zero());
-  std::copy(rx.begin(), rx.end(), rx_ext.begin() + (nm - d->nx));
-  std::copy(ry.begin(), ry.end(), ry_ext.begin() + (nm - d->ny));
-  vpin_table *mem_rx = nullptr, *mem_ry = nullptr, *comb = nullptr;
-  if ((rc = vpin_eq_table(c, B(rx_ext.data()), (int)nm, &mem_rx))) return rc;
-  tg.add(mem_rx);
-  if ((rc = vpin_eq_table(c, B(ry_ext.data()), (int)nm, &mem_ry))) return rc;
-  tg.add(mem_ry);
-  // Derefs (sparse_mlpoly.rs:525-531,56-71) and their commitment
-  vpin::DevBuf b_cloc(c), b_crows(c), b_vloc(c);          // split by residue class: the local views (spark.hip)
-  vpin::fq *comb_loc = nullptr, *comb_rows = nullptr, *vals_loc = nullptr;
-  vpin_table comb_shape;                                  // shape-only handle of the (never materialised) derefs polynomial
-  comb_shape.d = nullptr; comb_shape.len = comb_shape.cap = 8 * N; comb_shape.owned = false;
-  const size_t nrows_loc = st ? vpin::comm_strided_count(g_derefs->L, dz->rank, dz->world) : 0;
-  if (st) {
-    const size_t Nl = N / Wz;
-    if (b_cloc.alloc(6 * Nl * 32) || b_crows.alloc(std::max<size_t>(1, nrows_loc) * g_derefs->R * 32) || b_vloc.alloc(3 * Nl * 32)) return VPIN_ENOMEM;
-    comb_loc = (vpin::fq*)b_cloc.p; comb_rows = (vpin::fq*)b_crows.p; vals_loc = (vpin::fq*)b_vloc.p;
-    if ((rc = vpin::spark_gather_derefs_strided(c, d, mem_rx->d, mem_ry->d, rk, Wz, comb_loc, comb_rows, g_derefs->R, nrows_loc))) return rc;
+  std::copy(S.rx.begin(), S.rx.end(), rx_ext.begin() + (nm - d->nx));
+  std::copy(S.ry.begin(), S.ry.end(), ry_ext.begin() + (nm - d->ny));
+  if ((rc = vpin_eq_table(c, B(rx_ext.data()), (int)nm, &S.mem_rx))) return rc;
+  S.tg.add(S.mem_rx);
+  if ((rc = vpin_eq_table(c, B(ry_ext.data()), (int)nm, &S.mem_ry))) return rc;
+  S.tg.add(S.mem_ry);
+  const vpin::fq *mem_rx = S.mem_rx->d, *mem_ry = S.mem_ry->d;
+  S.Nf = N / S.leaves.step; S.Mf = S.M / S.leaves.step;
+  if (S.st) {
+    S.comb_shape.d = nullptr; S.comb_shape.len = S.comb_shape.cap = 8 * N; S.comb_shape.owned = false;
+    S.comb = &S.comb_shape;  // never materialised
+    const size_t Nl = S.Nf, nrows_loc = vpin::comm_strided_count(g_derefs->L, dz->rank, dz->world);
+    if (S.b_cloc.alloc(6 * Nl * 32) || S.b_crows.alloc(std::max<size_t>(1, nrows_loc) * g_derefs->R * 32) || S.b_vloc.alloc(3 * Nl * 32)) return VPIN_ENOMEM;
+    S.comb_rows = (vpin::fq*)S.b_crows.p;
+    if ((rc = vpin::spark_gather_derefs(c, d, S.leaves, mem_rx, mem_ry, (vpin::fq*)S.b_cloc.p, S.comb_rows, g_derefs->R, nrows_loc))) return rc;
     for (int m = 0; m < 3; m++)
-      if ((rc = vpin::spark_take_strided(c, d->vals + (size_t)m * N, Nl, rk, Wz, vals_loc + (size_t)m * Nl))) return rc;
-    comb = &comb_shape;
+      if ((rc = vpin::spark_take_strided(c, d->vals + (size_t)m * N, Nl, S.leaves.r0, S.leaves.step, (vpin::fq*)S.b_vloc.p + (size_t)m * Nl))) return rc;
+    S.derefs = (const vpin::fq*)S.b_cloc.p; S.vals = (const vpin::fq*)S.b_vloc.p;
   } else {
-    if ((rc = vpin::table_alloc_uninit(c, 8 * N, &comb))) return rc;
-    tg.add(comb);
-    if ((rc = vpin::spark_gather_derefs(c, d, mem_rx->d, mem_ry->d, comb->d))) return rc;
+    if ((rc = vpin::table_alloc_uninit(c, 8 * N, &S.comb))) return rc;
+    S.tg.add(S.comb);
+    if ((rc = vpin::spark_gather_derefs(c, d, S.leaves, mem_rx, mem_ry, S.comb->d))) return rc;
+    S.derefs = S.comb->d; S.vals = d->vals;
   }
   if ((rc = vpin::comm_mark(c, "derefs_gather"))) return rc;
-  std::vector<CG> comm_derefs;
+  std::vector<CG>& comm_derefs = S.comm_derefs;
+  // the entries of each matrix's hot column hold one scalar, E_ry[hot]: one addition each instead of a table walk
   const bool hot = d->hot_col[0] != 0xffffffffu || d->hot_col[1] != 0xffffffffu || d->hot_col[2] != 0xffffffffu;
+  const uint32_t* col_idx[3] = {d->idx + 6 * N, d->idx + 7 * N, d->idx + 8 * N};
   if (dz) {
     // the L row commitments are independent MSMs over shared generators: rank r commits rows r, r + world, .. (the rows
     // differ in cost: two of the polynomial's eight slices are zero padding, the col slices carry the hot columns), 32
@@ -798,14 +844,11 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
     const size_t nrows = vpin::comm_strided_count(L, dz->rank, dz->world);  // rows rank, rank + world, ..
     std::vector<uint8_t> mine(pmax * 32, 0), all(pmax * 32 * (size_t)dz->world);
     if (nrows) {
-      if (hot) {
-        const uint32_t* col_idx[3] = {d->idx + 6 * d->N, d->idx + 7 * d->N, d->idx + 8 * d->N};
-        rc = vpin::hyrax_commit_derefs_hot(c, g_derefs->dev, comb, L, d->N, col_idx, d->hot_col, mem_ry->d, mine.data(), (size_t)dz->rank,
-                                           nrows, (size_t)dz->world, st ? comb_rows : nullptr);
-      } else {
-        rc = vpin::hyrax_commit_rows_strided(c, g_derefs->dev, comb, L, (size_t)dz->rank, nrows, (size_t)dz->world, mine.data(),
-                                             st ? comb_rows : nullptr);
-      }
+      if (hot)
+        rc = vpin::hyrax_commit_derefs_hot(c, g_derefs->dev, S.comb, L, N, col_idx, d->hot_col, mem_ry, mine.data(), (size_t)dz->rank,
+                                           nrows, (size_t)dz->world, S.comb_rows);
+      else
+        rc = vpin::hyrax_commit_rows_strided(c, g_derefs->dev, S.comb, L, (size_t)dz->rank, nrows, (size_t)dz->world, mine.data(), S.comb_rows);
       if (rc) return rc;
     }
     if ((rc = vpin::comm_allgather_ctx(c, mine.data(), all.data(), mine.size(), "derefs_commit"))) return rc;
@@ -814,81 +857,83 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
       const size_t n = vpin::comm_strided_count(L, r, dz->world);
       for (size_t k = 0; k < n; k++) memcpy(comm_derefs[(size_t)r + k * (size_t)dz->world].b, all.data() + ((size_t)r * pmax + k) * 32, 32);
     }
-  } else if (d->hot_col[0] != 0xffffffffu || d->hot_col[1] != 0xffffffffu || d->hot_col[2] != 0xffffffffu) {
-    // the entries of each matrix's hot column hold one scalar, E_ry[hot]: one addition each instead of a table walk
-    const uint32_t* col_idx[3] = {d->idx + 6 * d->N, d->idx + 7 * d->N, d->idx + 8 * d->N};
+  } else if (hot) {
     comm_derefs.resize(g_derefs->L);
-    if ((rc = vpin::hyrax_commit_derefs_hot(c, g_derefs->dev, comb, g_derefs->L, d->N, col_idx, d->hot_col, mem_ry->d,
-                                            comm_derefs[0].b)))
-      return rc;
-  } else if ((rc = commit_noblind(c, g_derefs, comb, comm_derefs))) {
+    if ((rc = vpin::hyrax_commit_derefs_hot(c, g_derefs->dev, S.comb, g_derefs->L, N, col_idx, d->hot_col, mem_ry, comm_derefs[0].b))) return rc;
+  } else if ((rc = commit_noblind(c, g_derefs, S.comb, comm_derefs))) {
     return rc;
   }
-  tr.append_message("derefs_commitment", "begin_derefs_commitment");  // DerefsCommitment::append_to_transcript (:216-222)
-  append_polycomm(tr, "comm_poly_row_col_ops_val", comm_derefs);
-  tr.append_message("derefs_commitment", "end_derefs_commitment");
-  g_spark_timings[1] = secs(t0, Clock::now());
-  if (c->progress_flag) *c->progress_flag = 2;  // the proof's largest MSM is done (a scheduler may let other streams in now)
+  S.tr.append_message("derefs_commitment", "begin_derefs_commitment");  // DerefsCommitment::append_to_transcript (:216-222)
+  append_polycomm(S.tr, "comm_poly_row_col_ops_val", comm_derefs);
+  S.tr.append_message("derefs_commitment", "end_derefs_commitment");
+  return VPIN_OK;
+}
 
-  // ---- PolyEvalNetwork::new (sparse_mlpoly.rs:681-696) ----
-  t0 = Clock::now();
-  std::vector<Fq> r_mem_check = tr.challenge_vector("challenge_r_hash", 2);
-  const Fq r_hash = r_mem_check[0], gamma = r_mem_check[1], r_hash_sqr = r_hash * r_hash, r2_boost = r_hash_sqr * Fq::r2();
-  vpin::SparkForest f_ops, f_mem;
-  vpin::DevBuf b_ops(c), b_mem(c), b_scr(c);
-  const int nl_ops = (dz && !st) ? (int)dz->ops_of[dz->rank].size() : 12, nl_mem = (dz && !st) ? (int)dz->mem_of[dz->rank].size() : 4;
-  const size_t nl_dotp = (dz && !st) ? dz->dotp_of[dz->rank].size() : 6;  // the first-fold scratch is numbered by the local half
-  const size_t Nf = st ? N / Wz : N, Mf = st ? M / Wz : M;               // leaves per tree on this rank
+static vpin::HashParams make_hash(const Fq& r_hash, const Fq& gamma) {
+  const Fq r2 = r_hash * r_hash, r2_boost = r2 * Fq::r2();
+  vpin::HashParams hp;
+  memcpy(hp.r.v, B(&r_hash), 32); memcpy(hp.r2.v, B(&r2), 32); memcpy(hp.r2_boost.v, B(&r2_boost), 32); memcpy(hp.gamma.v, B(&gamma), 32);
+  return hp;
+}
+
+// PolyEvalNetwork::new (sparse_mlpoly.rs:681-696)
+static int stage_network(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const DistPlan* dz = S.dz;
+  int rc;
+  std::vector<Fq> r_mem_check = S.tr.challenge_vector("challenge_r_hash", 2);
+  S.hash = make_hash(r_mem_check[0], r_mem_check[1]);
+  // which leaves this rank builds: S.leaves of all 12 + 4 circuits, or -- split by whole circuits -- every leaf of its own
+  vpin::SparkLeaves lv_ops = S.leaves, lv_mem = S.leaves;
+  int nl_ops = 12, nl_mem = 4;
+  size_t nl_dotp = 6;  // the first-fold scratch is numbered by the local half
+  if (S.by_circuit()) {
+    const auto &ops = dz->ops_of[dz->rank], &mem = dz->mem_of[dz->rank];
+    lv_ops.ncirc = nl_ops = (int)ops.size(); lv_mem.ncirc = nl_mem = (int)mem.size();
+    std::copy(ops.begin(), ops.end(), lv_ops.ids);
+    std::copy(mem.begin(), mem.end(), lv_mem.ids);
+    nl_dotp = dz->dotp_of[dz->rank].size();
+  }
   // Single GPU, a context in low-memory mode (vpin_ctx_set_low_memory, or VPIN_MEM_FOREST_LATE=1; round 5): the mem forest is
   // built AFTER the ops forest has been proven, into the memory it frees (-16 GiB of working set for the 2^25 instance, the
   // LeNet step's HBM 197 -> 181 GiB); the four mem roots the transcript wants first come from a product reduction over the
   // leaves (spark_mem_roots).  It costs 1 % of the 2^25 proof and 1.6 % of the four-lane step, so it is not the default.
-  const bool defer_mem = !dz && (c->low_memory || getenv("VPIN_MEM_FOREST_LATE") != nullptr);
-  if (b_ops.alloc((size_t)nl_ops * 2 * Nf * 32) || (nl_mem && !defer_mem && b_mem.alloc((size_t)nl_mem * 2 * Mf * 32)) ||
-      b_scr.alloc(std::max<size_t>(256, 3 * nl_dotp * (Nf / 4) * 32)))
+  S.defer_mem = !dz && (c->low_memory || getenv("VPIN_MEM_FOREST_LATE") != nullptr);
+  if (S.b_ops.alloc((size_t)nl_ops * 2 * S.Nf * 32) || (nl_mem && !S.defer_mem && S.b_mem.alloc((size_t)nl_mem * 2 * S.Mf * 32)) ||
+      S.b_scr.alloc(std::max<size_t>(256, 3 * nl_dotp * (S.Nf / 4) * 32)))
     return VPIN_ENOMEM;
   if ((rc = vpin::comm_mark(c, "network_alloc"))) return rc;
-  f_ops.base = (vpin::fq*)b_ops.p; f_ops.n = Nf; f_ops.ncirc = nl_ops;
-  f_mem.base = (vpin::fq*)b_mem.p; f_mem.n = Mf; f_mem.ncirc = nl_mem;
-  if (st) {
-    if ((rc = vpin::spark_build_forests_strided(c, d, comb_loc, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma),
-                                                &f_ops, &f_mem, rk, Wz)))
-      return rc;
-  } else if (defer_mem) {
-    if ((rc = vpin::spark_build_forest_ops(c, d, comb->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma), &f_ops))) return rc;
-  } else if (!dz) {
-    if ((rc = vpin::spark_build_forests(c, d, comb->d, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma),
-                                        &f_ops, &f_mem)))
-      return rc;
+  S.f_ops.base = (vpin::fq*)S.b_ops.p; S.f_ops.n = S.Nf; S.f_ops.ncirc = nl_ops;
+  S.f_mem.base = (vpin::fq*)S.b_mem.p; S.f_mem.n = S.Mf; S.f_mem.ncirc = nl_mem;
+  const vpin::SparkInputs in{S.derefs, S.mem_rx->d, S.mem_ry->d};
+  if (!S.by_circuit() && !S.defer_mem) {
+    rc = vpin::spark_build_forests(c, S.d, S.hash, S.leaves, in, &S.f_ops, &S.f_mem);
   } else {
-    // leaves and trees of this rank's circuits only
-    if ((rc = vpin::spark_build_forest_sub(c, d, comb->d, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma),
-                                           &f_ops, dz->ops_of[dz->rank].data(), false)))
-      return rc;
-    if (nl_mem && (rc = vpin::spark_build_forest_sub(c, d, comb->d, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost),
-                                                     B(&gamma), &f_mem, dz->mem_of[dz->rank].data(), true)))
-      return rc;
+    rc = vpin::spark_build_forest(c, S.d, S.hash, lv_ops, in, &S.f_ops, false);
+    if (!rc && !S.defer_mem && nl_mem) rc = vpin::spark_build_forest(c, S.d, S.hash, lv_mem, in, &S.f_mem, true);
   }
-  if ((rc = vpin::spark_wait(c))) return rc;
-  if ((rc = vpin::comm_mark(c, "network_build"))) return rc;
-  g_spark_timings[2] = secs(t0, Clock::now());
+  if (rc || (rc = vpin::spark_wait(c))) return rc;
+  return vpin::comm_mark(c, "network_build");
+}
 
-  // ---- PolyEvalNetworkProof::prove / ProductLayerProof::prove (:1336-1370, :1049-1227) ----
-  t0 = Clock::now();
-  tr.append_protocol_name("Sparse polynomial evaluation proof");
-  tr.append_protocol_name("Sparse polynomial product layer proof");
-  // roots of the 16 circuits
-  Fq pl[2][8];  // per side: init, read[3], write[3], audit
+// roots of the 16 circuits -> S.pl and the transcript
+static int product_roots(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const DistPlan* dz = S.dz;
+  const bool st = S.st;
+  const size_t Wz = S.leaves.step;
+  auto& pl = S.pl;
+  int rc;
   {
     std::vector<Fq> roots(2 * (size_t)vpin::kSparkMaxInst);
-    if ((rc = vpin::spark_fetch_tops(c, &f_ops, 2))) return rc;
+    if ((rc = vpin::spark_fetch_tops(c, &S.f_ops, 2))) return rc;
     const Fq* t = reinterpret_cast<const Fq*>(c->h_spark);
     std::vector<Fq> st_roots(2 * 16);
     if (st) {
       // a circuit's root is the product of its leaves = the product over the ranks of their local roots
       std::vector<Fq> mine16(16), all16(16 * Wz);
       for (int i = 0; i < 12; i++) mine16[i] = t[2 * i];
-      if ((rc = vpin::spark_fetch_tops(c, &f_mem, 2))) return rc;
+      if ((rc = vpin::spark_fetch_tops(c, &S.f_mem, 2))) return rc;
       for (int i = 0; i < 4; i++) mine16[12 + i] = t[2 * i];
       if ((rc = vpin::comm_allgather_ctx(c, mine16.data(), all16.data(), 16 * 32, "roots"))) return rc;
       for (int i = 0; i < 16; i++) {
@@ -908,9 +953,9 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
       for (int i = 0; i < 4; i++) roots[2 * i] = st_roots[2 * (12 + i)];
       t = roots.data();
     } else {
-      if (defer_mem) {
-        if ((rc = vpin::spark_mem_roots(c, d, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma)))) return rc;
-      } else if (nl_mem && (rc = vpin::spark_fetch_tops(c, &f_mem, 2))) {
+      if (S.defer_mem) {
+        if ((rc = vpin::spark_mem_roots(c, S.d, S.hash, S.mem_rx->d, S.mem_ry->d))) return rc;
+      } else if (S.f_mem.ncirc && (rc = vpin::spark_fetch_tops(c, &S.f_mem, 2))) {
         return rc;
       }
       t = reinterpret_cast<const Fq*>(c->h_spark);
@@ -927,69 +972,157 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
     Fq ws = Fq::one(), rs = Fq::one();
     for (int m = 0; m < 3; m++) { rs = rs * pl[s][1 + m]; ws = ws * pl[s][4 + m]; }
     if (!(pl[s][0] * ws == rs * pl[s][7])) return VPIN_ESHAPE;  // assert_eq!(row_eval_init * ws, rs * row_eval_audit)
-    tr.append_scalar(lab[s][0], pl[s][0]);
-    tr.append_scalars(lab[s][1], &pl[s][1], 3);
-    tr.append_scalars(lab[s][2], &pl[s][4], 3);
-    tr.append_scalar(lab[s][3], pl[s][7]);
+    S.tr.append_scalar(lab[s][0], pl[s][0]);
+    S.tr.append_scalars(lab[s][1], &pl[s][1], 3);
+    S.tr.append_scalars(lab[s][2], &pl[s][4], 3);
+    S.tr.append_scalar(lab[s][3], pl[s][7]);
   }
-  DotpCtx dotp{d, Nf, st ? vals_loc : d->vals, st ? comb_loc : comb->d, (vpin::fq*)b_scr.p, {}};
-  Fq dotp_left[3], dotp_right[3];
-  {
-    // DotProductCircuit::evaluate (product_tree.rs:87-91) of the six halves
-    if (st) {
-      // every rank sums its residue class of all six halves; the partial sums are added up
-      if ((rc = vpin::spark_triple_sums_raw(c, comb_loc, vals_loc, Nf))) return rc;
-      Fq mine6[6];
-      for (int i = 0; i < 6; i++) mine6[i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
-      if ((rc = dist_sum(c, *dz, mine6, 6, dotp.claims, "triple_sums"))) return rc;
-    } else if (!dz) {
-      if ((rc = vpin::spark_triple_sums(c, d, comb->d))) return rc;
-      for (int i = 0; i < 6; i++) dotp.claims[i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
-    } else {
-      // every rank sums the halves it will prove; one scalar per half is exchanged
-      const auto& hv = dz->dotp_of[dz->rank];
-      if (!hv.empty() && (rc = vpin::spark_triple_sums(c, d, comb->d, hv.data(), (int)hv.size()))) return rc;
-      std::vector<Fq> mine6(6, Fq::zero()), all6(6 * (size_t)dz->world);
-      for (size_t i = 0; i < hv.size(); i++) mine6[hv[i]] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
-      if ((rc = vpin::comm_allgather_ctx(c, mine6.data(), all6.data(), 6 * 32, "triple_sums"))) return rc;
-      for (int k = 0; k < 6; k++) dotp.claims[k] = all6[6 * (size_t)dz->owner_dotp[k] + k];
-    }
-    for (int m = 0; m < 3; m++) {
-      dotp_left[m] = dotp.claims[2 * m];
-      dotp_right[m] = dotp.claims[2 * m + 1];
-      tr.append_scalar("claim_eval_dotp_left", dotp_left[m]);
-      tr.append_scalar("claim_eval_dotp_right", dotp_right[m]);
-      if (!(dotp_left[m] + dotp_right[m] == evals[m])) return VPIN_ESHAPE;  // assert_eq!(left + right, eval[i])
-    }
+  return VPIN_OK;
+}
+
+// DotProductCircuit::evaluate (product_tree.rs:87-91) of the six halves -> S.dotp.claims and the transcript
+static int dotp_claims(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const DistPlan* dz = S.dz;
+  int rc;
+  // one GPU: all six halves.  Split by residue class: every rank sums its residue class of all six, the partial sums are added
+  // up.  Split by whole circuits: every rank sums the halves it will prove, one scalar per half is exchanged.
+  const std::vector<int>* hv = S.by_circuit() ? &dz->dotp_of[dz->rank] : nullptr;
+  const size_t nh = hv ? hv->size() : 6;
+  if (nh && (rc = vpin::spark_triple_sums(c, S.derefs, S.vals, S.Nf, hv ? hv->data() : nullptr, (int)nh))) return rc;
+  Fq mine6[6] = {};
+  for (size_t i = 0; i < nh; i++) mine6[hv ? (*hv)[i] : i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
+  if (S.st) rc = dist_sum(c, *dz, mine6, 6, S.dotp.claims, "triple_sums");
+  else if (dz) rc = dist_pick(c, *dz, mine6, 6, dz->owner_dotp, S.dotp.claims, "triple_sums");
+  else std::copy(mine6, mine6 + 6, S.dotp.claims);
+  if (rc) return rc;
+  for (int m = 0; m < 3; m++) {
+    S.dotp_left[m] = S.dotp.claims[2 * m];
+    S.dotp_right[m] = S.dotp.claims[2 * m + 1];
+    S.tr.append_scalar("claim_eval_dotp_left", S.dotp_left[m]);
+    S.tr.append_scalar("claim_eval_dotp_right", S.dotp_right[m]);
+    if (!(S.dotp_left[m] + S.dotp_right[m] == S.evals[m])) return VPIN_ESHAPE;  // assert_eq!(left + right, eval[i])
   }
-  Batched pf_ops, pf_mem;
-  std::vector<Fq> rand_ops, rand_mem;
+  return VPIN_OK;
+}
+
+// PolyEvalNetworkProof::prove / ProductLayerProof::prove (:1336-1370, :1049-1227)
+static int stage_product(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  int rc;
+  S.tr.append_protocol_name("Sparse polynomial evaluation proof");
+  S.tr.append_protocol_name("Sparse polynomial product layer proof");
+  if ((rc = product_roots(S))) return rc;
+  S.dotp = DotpCtx{S.d, S.Nf, S.vals, S.derefs, (vpin::fq*)S.b_scr.p, {}};
+  if ((rc = dotp_claims(S))) return rc;
   {
     TraceSpan ts("product: ops forest");
-    if ((rc = product_prove(c, f_ops, 12, &dotp, tr, pf_ops, rand_ops, dz))) return rc;
+    if ((rc = product_prove(c, S.f_ops, 12, &S.dotp, S.tr, S.pf_ops, S.rand_ops, S.dz))) return rc;
   }
-  if (defer_mem) {
+  if (S.defer_mem) {
     TraceSpan ts("network: mem forest (deferred)");
-    b_ops.release();   // every level of the ops forest has been folded away: its memory takes the mem forest
-    b_scr.release();
-    if (b_mem.alloc((size_t)4 * 2 * M * 32)) return VPIN_ENOMEM;
-    f_mem.base = (vpin::fq*)b_mem.p;
-    if ((rc = vpin::spark_build_forest_mem(c, d, mem_rx->d, mem_ry->d, B(&r_hash), B(&r_hash_sqr), B(&r2_boost), B(&gamma), &f_mem))) return rc;
+    S.b_ops.release();   // every level of the ops forest has been folded away: its memory takes the mem forest
+    S.b_scr.release();
+    if (S.b_mem.alloc((size_t)4 * 2 * S.M * 32)) return VPIN_ENOMEM;
+    S.f_mem.base = (vpin::fq*)S.b_mem.p;
+    if ((rc = vpin::spark_build_forest(c, S.d, S.hash, S.leaves, {nullptr, S.mem_rx->d, S.mem_ry->d}, &S.f_mem, true))) return rc;
     if ((rc = vpin::spark_wait(c))) return rc;
   }
-  {
-    TraceSpan ts("product: mem forest");
-    if ((rc = product_prove(c, f_mem, 4, nullptr, tr, pf_mem, rand_mem, dz))) return rc;
-  }
-  g_spark_timings[3] = secs(t0, Clock::now());
+  TraceSpan ts("product: mem forest");
+  return product_prove(c, S.f_mem, 4, nullptr, S.tr, S.pf_mem, S.rand_mem, S.dz);
+}
 
-  // ---- HashLayerProof::prove (:740-849) ----
-  t0 = Clock::now();
-  tr.append_protocol_name("Sparse polynomial hash layer proof");
+// One proof over several GPUs: the 23 DensePolynomial::evaluate of the hash layer (6 derefs + 15 ops slices against
+// eq(rand_ops), 2 mem slices against eq(rand_mem)) -> S.ev_derefs | S.ev_ops | S.ev_mem.  They depend on nothing the
+// transcript produces in between.
+static int hash_slice_evals_dist(SparkProof& S, const vpin_table* comb_ops, const vpin_table* comb_mem, const vpin_table* eq_ops,
+                                 const vpin_table* eq_mem) {
+  vpin_ctx* c = S.c;
+  const DistPlan* dz = S.dz;
+  const size_t N = S.N, M = S.M;
+  const Fq* hs = reinterpret_cast<const Fq*>(c->h_spark);
+  const int cnts[3] = {6, 15, 2};
+  const vpin::fq* tabs[3] = {S.derefs, comb_ops->d, comb_mem->d};
+  const vpin::fq* eqs[3] = {eq_ops->d, eq_ops->d, eq_mem->d};
+  Fq mine23[23] = {}, all23[23];
+  int rc, base = 0;
+  if (S.st) {
+    // every rank evaluates its residue class of all 23 slices; the partial sums (scaled by eq(rand_lo, rank)) are added up
+    const size_t rk = S.leaves.r0, Wz = S.leaves.step;
+    std::vector<Fq> lo_ops(Wz), lo_mem(Wz);
+    host_eq(S.rand_ops.data() + (S.lgN - dz->lw), (size_t)dz->lw, lo_ops.data());
+    host_eq(S.rand_mem.data() + (S.lgM - dz->lw), (size_t)dz->lw, lo_mem.data());
+    const Fq scale[3] = {lo_ops[rk], lo_ops[rk], lo_mem[rk]};
+    for (int g = 0; g < 3; g++) {
+      // the derefs slices are this rank's local view already; the combined polynomials are whole
+      if (g == 0) rc = vpin::spark_slice_evals(c, tabs[g], S.Nf, cnts[g], eqs[g]);
+      else rc = vpin::spark_slice_evals(c, tabs[g], g == 1 ? N : M, cnts[g], eqs[g], rk, Wz);
+      if (rc) return rc;
+      for (int i = 0; i < cnts[g]; i++) mine23[base + i] = hs[3 * i] * scale[g];
+      base += cnts[g];
+    }
+    if ((rc = dist_sum(c, *dz, mine23, 23, all23, "hash_slice_evals"))) return rc;
+  } else {
+    // deal them out in contiguous runs of equal cost (a slice costs its length), evaluate, exchange 23 scalars
+    const size_t cost[3] = {N, N, M};
+    size_t total = 0, cum = 0;
+    for (int g = 0; g < 3; g++) total += cost[g] * (size_t)cnts[g];
+    int owner[23];
+    for (int g = 0, sidx = 0; g < 3; g++)
+      for (int i = 0; i < cnts[g]; i++, sidx++) {
+        owner[sidx] = (int)std::min<size_t>((size_t)dz->world - 1, (cum + cost[g] / 2) * (size_t)dz->world / total);
+        cum += cost[g];
+      }
+    for (int g = 0; g < 3; g++) {
+      int first = -1, cnt = 0;
+      for (int i = 0; i < cnts[g]; i++)
+        if (owner[base + i] == dz->rank) { if (first < 0) first = i; cnt++; }
+      if (cnt) {  // a rank's slices of one table are contiguous
+        if ((rc = vpin::spark_slice_evals(c, tabs[g] + (size_t)first * cost[g], cost[g], cnt, eqs[g]))) return rc;
+        for (int i = 0; i < cnt; i++) mine23[base + first + i] = hs[3 * i];
+      }
+      base += cnts[g];
+    }
+    if ((rc = dist_pick(c, *dz, mine23, 23, owner, all23, "hash_slice_evals"))) return rc;
+  }
+  std::copy(all23, all23 + 6, S.ev_derefs);
+  std::copy(all23 + 6, all23 + 21, S.ev_ops);
+  std::copy(all23 + 21, all23 + 23, S.ev_mem);
+  return VPIN_OK;
+}
+
+// the joint evaluation proof of one combined polynomial Z (DerefsEvalProof::prove :137-158, :90-135; HashLayerProof::prove
+// :803-849): its slices' evaluations e (padded to a power of two) at `rand`, combined with nch challenges
+struct JointLabels { const char *evals, *challenge, *joint, *span; };
+static int prove_joint(SparkProof& S, const PcGens& g, const vpin_table* Z, SlicePass& sp, const std::vector<Fq>& e, int nch,
+                       const std::vector<Fq>& rand, const JointLabels& lab, const vpin::fq* z_rows, DpLog& out) {
+  int rc;
+  S.tr.append_scalars(lab.evals, e.data(), e.size());
+  std::vector<Fq> ch = S.tr.challenge_vector(lab.challenge, nch);
+  Fq joint = combine_bot(e, ch);
+  std::vector<Fq> rj(ch);
+  rj.insert(rj.end(), rand.begin(), rand.end());
+  S.tr.append_scalar(lab.joint, joint);
+  TraceSpan ts(lab.span);
+  std::vector<Fq> lz;
+  if (sp.on && (rc = sp.combine(S.c, g, ch, lz))) return rc;
+  if ((rc = polyeval_prove_plain(S.c, g, Z, rj, joint, S.tr, S.tape, out, z_rows, sp.on ? &lz : nullptr, sp.on ? &sp.Rv : nullptr))) return rc;
+  return vpin::comm_mark(S.c, "hash_bullet");
+}
+
+// HashLayerProof::prove (:740-849)
+static int stage_hash(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const vpin_spark_decomm* d = S.d;
+  const DistPlan* dz = S.dz;
+  const size_t N = S.N, M = S.M;
+  const std::vector<Fq>&rand_ops = S.rand_ops, &rand_mem = S.rand_mem;
+  int rc;
+  S.tr.append_protocol_name("Sparse polynomial hash layer proof");
   vpin_table *eq_ops = nullptr, *eq_mem = nullptr;
   // single GPU: slice evaluations and the evaluation proofs' LZ vectors from one pass per combined polynomial (SlicePass)
-  const bool one_pass = !dz && SlicePass::fits(*g_derefs, 3, rand_ops) && SlicePass::fits(*g_ops, 4, rand_ops) &&
-                        SlicePass::fits(*g_mem, 1, rand_mem);
+  const bool one_pass = !dz && SlicePass::fits(*S.g_derefs, 3, rand_ops) && SlicePass::fits(*S.g_ops, 4, rand_ops) &&
+                        SlicePass::fits(*S.g_mem, 1, rand_mem);
   SlicePass sp_derefs(c), sp_ops(c), sp_mem(c);
   // the combined polynomials as whole field tables: only the two-pass and the multi-GPU paths read them (this proof's own
   // copies: the decommitment is shared with other contexts)
@@ -1003,160 +1136,99 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
     comb_ops = dm->comb_ops; comb_mem = dm->comb_mem;
   } else if (!one_pass) {
     if ((rc = vpin::spark_comb_make(c, d, &comb_ops, &comb_mem))) return rc;
-    tg.add(comb_ops); tg.add(comb_mem);
+    S.tg.add(comb_ops); S.tg.add(comb_mem);
   }
   if (!one_pass) {
     TraceSpan ts("hash: eq tables");
     // split by residue class: eq(rand, rank + k W) = eq(rand_hi, k) * eq(rand_lo, rank), so the local table is the table of
     // the first lg - lw challenges and the rank's sums are scaled by one constant
-    const int lwz = st ? dz->lw : 0;
-    if ((rc = vpin_eq_table(c, B(rand_ops.data()), (int)lgN - lwz, &eq_ops))) return rc;
-    tg.add(eq_ops);
-    if ((rc = vpin_eq_table(c, B(rand_mem.data()), (int)lgM - lwz, &eq_mem))) return rc;
-    tg.add(eq_mem);
+    const int lwz = S.st ? dz->lw : 0;
+    if ((rc = vpin_eq_table(c, B(rand_ops.data()), (int)S.lgN - lwz, &eq_ops))) return rc;
+    S.tg.add(eq_ops);
+    if ((rc = vpin_eq_table(c, B(rand_mem.data()), (int)S.lgM - lwz, &eq_mem))) return rc;
+    S.tg.add(eq_mem);
   }
   if ((rc = vpin::comm_mark(c, "hash_eq_tables"))) return rc;
-  Fq ev_derefs[6], ev_ops[15], ev_mem[2];
   const Fq* hs = reinterpret_cast<const Fq*>(c->h_spark);
-  if (st) {
-    // every rank evaluates its residue class of all 23 slices; the partial sums (scaled by eq(rand_lo, rank)) are added up
-    std::vector<Fq> lo_ops(Wz), lo_mem(Wz);
-    host_eq(rand_ops.data() + (lgN - dz->lw), (size_t)dz->lw, lo_ops.data());
-    host_eq(rand_mem.data() + (lgM - dz->lw), (size_t)dz->lw, lo_mem.data());
-    Fq mine23[23], all23[23];
-    if ((rc = vpin::spark_slice_evals(c, comb_loc, Nf, 6, eq_ops->d))) return rc;
-    for (int i = 0; i < 6; i++) mine23[i] = hs[3 * i] * lo_ops[rk];
-    if ((rc = vpin::spark_slice_evals(c, comb_ops->d, N, 15, eq_ops->d, rk, Wz))) return rc;
-    for (int i = 0; i < 15; i++) mine23[6 + i] = hs[3 * i] * lo_ops[rk];
-    if ((rc = vpin::spark_slice_evals(c, comb_mem->d, M, 2, eq_mem->d, rk, Wz))) return rc;
-    for (int i = 0; i < 2; i++) mine23[21 + i] = hs[3 * i] * lo_mem[rk];
-    if ((rc = dist_sum(c, *dz, mine23, 23, all23, "hash_slice_evals"))) return rc;
-    for (int i = 0; i < 6; i++) ev_derefs[i] = all23[i];
-    for (int i = 0; i < 15; i++) ev_ops[i] = all23[6 + i];
-    for (int i = 0; i < 2; i++) ev_mem[i] = all23[21 + i];
-  } else if (dz) {
-    // The 23 DensePolynomial::evaluate of the hash layer (6 derefs + 15 ops slices against eq(rand_ops), 2 mem slices
-    // against eq(rand_mem)) depend on nothing the transcript produces in between: deal them out in contiguous runs of
-    // equal cost (a slice costs its length), evaluate, exchange 23 scalars.
-    const size_t cost[3] = {N, N, M};
-    const int cnts[3] = {6, 15, 2};
-    const vpin::fq* tabs[3] = {comb->d, comb_ops->d, comb_mem->d};
-    const vpin::fq* eqs[3] = {eq_ops->d, eq_ops->d, eq_mem->d};
-    size_t total = 0;
-    for (int g = 0; g < 3; g++) total += cost[g] * (size_t)cnts[g];
-    int owner[23];
-    {
-      size_t cum = 0;
-      int sidx = 0;
-      for (int g = 0; g < 3; g++)
-        for (int i = 0; i < cnts[g]; i++, sidx++) {
-          owner[sidx] = (int)std::min<size_t>((size_t)dz->world - 1, (cum + cost[g] / 2) * (size_t)dz->world / total);
-          cum += cost[g];
-        }
-    }
-    std::vector<Fq> mine23(23, Fq::zero()), all23(23 * (size_t)dz->world);
-    int base = 0;
-    for (int g = 0; g < 3; g++) {
-      int first = -1, cnt = 0;
-      for (int i = 0; i < cnts[g]; i++)
-        if (owner[base + i] == dz->rank) { if (first < 0) first = i; cnt++; }
-      if (cnt) {  // a rank's slices of one table are contiguous
-        if ((rc = vpin::spark_slice_evals(c, tabs[g] + (size_t)first * cost[g], cost[g], cnt, eqs[g]))) return rc;
-        for (int i = 0; i < cnt; i++) mine23[base + first + i] = hs[3 * i];
-      }
-      base += cnts[g];
-    }
-    if ((rc = vpin::comm_allgather_ctx(c, mine23.data(), all23.data(), 23 * 32, "hash_slice_evals"))) return rc;
-    auto pick = [&](int sidx) { return all23[23 * (size_t)owner[sidx] + sidx]; };
-    for (int i = 0; i < 6; i++) ev_derefs[i] = pick(i);
-    for (int i = 0; i < 15; i++) ev_ops[i] = pick(6 + i);
-    for (int i = 0; i < 2; i++) ev_mem[i] = pick(21 + i);
+  if (dz) {
+    if ((rc = hash_slice_evals_dist(S, comb_ops, comb_mem, eq_ops, eq_mem))) return rc;
   } else if (one_pass) {
     TraceSpan ts("hash: derefs slices (one pass)");
-    if ((rc = sp_derefs.run(c, *g_derefs, nullptr, 0, comb->d, 3, 6, rand_ops, ev_derefs))) return rc;
+    if ((rc = sp_derefs.run(c, *S.g_derefs, nullptr, 0, S.derefs, 3, 6, rand_ops, S.ev_derefs))) return rc;
   } else {
     TraceSpan ts("hash: derefs slice evals");
-    if ((rc = vpin::spark_slice_evals(c, comb->d, N, 6, eq_ops->d))) return rc;
-    for (int i = 0; i < 6; i++) ev_derefs[i] = hs[3 * i];
+    if ((rc = vpin::spark_slice_evals(c, S.derefs, N, 6, eq_ops->d))) return rc;
+    for (int i = 0; i < 6; i++) S.ev_derefs[i] = hs[3 * i];
   }
-  DpLog pe_derefs, pe_ops, pe_mem;
-  {
-    // DerefsEvalProof::prove (:137-158, :90-135)
-    tr.append_protocol_name("Derefs evaluation proof");
-    std::vector<Fq> e8(8, Fq::zero());
-    for (int i = 0; i < 6; i++) e8[i] = ev_derefs[i];
-    tr.append_scalars("evals_ops_val", e8.data(), 8);
-    std::vector<Fq> ch = tr.challenge_vector("challenge_combine_n_to_one", 3);
-    Fq joint = combine_bot(e8, ch);
-    std::vector<Fq> rj(ch);
-    rj.insert(rj.end(), rand_ops.begin(), rand_ops.end());
-    tr.append_scalar("joint_claim_eval", joint);
-    TraceSpan ts("hash: polyeval derefs");
-    std::vector<Fq> lz;
-    if (sp_derefs.on && (rc = sp_derefs.combine(c, *g_derefs, ch, lz))) return rc;
-    if ((rc = polyeval_prove_plain(c, *g_derefs, comb, rj, joint, tr, tape, pe_derefs, st ? comb_rows : nullptr,
-                                   sp_derefs.on ? &lz : nullptr, sp_derefs.on ? &sp_derefs.Rv : nullptr))) return rc;
-    if ((rc = vpin::comm_mark(c, "hash_bullet"))) return rc;
-  }
+  S.tr.append_protocol_name("Derefs evaluation proof");
+  std::vector<Fq> e8(8, Fq::zero());
+  std::copy(S.ev_derefs, S.ev_derefs + 6, e8.begin());
+  if ((rc = prove_joint(S, *S.g_derefs, S.comb, sp_derefs, e8, 3, rand_ops,
+                        {"evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", "hash: polyeval derefs"}, S.comb_rows, S.pe_derefs)))
+    return rc;
   if (one_pass) {
     TraceSpan ts("hash: ops+mem slices (one pass)");
-    if ((rc = sp_ops.run(c, *g_ops, d->idx, 12, d->vals, 4, 15, rand_ops, ev_ops))) return rc;
-    if ((rc = sp_mem.run(c, *g_mem, d->idx + 12 * N, 2, nullptr, 1, 2, rand_mem, ev_mem))) return rc;
+    if ((rc = sp_ops.run(c, *S.g_ops, d->idx, 12, d->vals, 4, 15, rand_ops, S.ev_ops))) return rc;
+    if ((rc = sp_mem.run(c, *S.g_mem, d->idx + 12 * N, 2, nullptr, 1, 2, rand_mem, S.ev_mem))) return rc;
   } else if (!dz) {
     TraceSpan ts("hash: ops+mem slice evals");
     if ((rc = vpin::spark_slice_evals(c, comb_ops->d, N, 15, eq_ops->d))) return rc;
-    for (int i = 0; i < 15; i++) ev_ops[i] = hs[3 * i];
+    for (int i = 0; i < 15; i++) S.ev_ops[i] = hs[3 * i];
     if ((rc = vpin::spark_slice_evals(c, comb_mem->d, M, 2, eq_mem->d))) return rc;
-    for (int i = 0; i < 2; i++) ev_mem[i] = hs[3 * i];
+    for (int i = 0; i < 2; i++) S.ev_mem[i] = hs[3 * i];
   }
-  {
-    std::vector<Fq> e16(16, Fq::zero());
-    for (int i = 0; i < 15; i++) e16[i] = ev_ops[i];  // row addr, row read_ts, col addr, col read_ts, val (comb_ops order)
-    tr.append_scalars("claim_evals_ops", e16.data(), 16);
-    std::vector<Fq> ch = tr.challenge_vector("challenge_combine_n_to_one", 4);
-    Fq joint = combine_bot(e16, ch);
-    std::vector<Fq> rj(ch);
-    rj.insert(rj.end(), rand_ops.begin(), rand_ops.end());
-    tr.append_scalar("joint_claim_eval_ops", joint);
-    TraceSpan ts("hash: polyeval ops");
-    std::vector<Fq> lz;
-    if (sp_ops.on && (rc = sp_ops.combine(c, *g_ops, ch, lz))) return rc;
-    if ((rc = polyeval_prove_plain(c, *g_ops, comb_ops, rj, joint, tr, tape, pe_ops, nullptr, sp_ops.on ? &lz : nullptr,
-                                   sp_ops.on ? &sp_ops.Rv : nullptr))) return rc;
-    if ((rc = vpin::comm_mark(c, "hash_bullet"))) return rc;
-  }
-  {
-    std::vector<Fq> e2 = {ev_mem[0], ev_mem[1]};
-    tr.append_scalars("claim_evals_mem", e2.data(), 2);
-    std::vector<Fq> ch = tr.challenge_vector("challenge_combine_two_to_one", 1);
-    Fq joint = combine_bot(e2, ch);
-    std::vector<Fq> rj(ch);
-    rj.insert(rj.end(), rand_mem.begin(), rand_mem.end());
-    tr.append_scalar("joint_claim_eval_mem", joint);
-    TraceSpan ts("hash: polyeval mem");
-    std::vector<Fq> lz;
-    if (sp_mem.on && (rc = sp_mem.combine(c, *g_mem, ch, lz))) return rc;
-    if ((rc = polyeval_prove_plain(c, *g_mem, comb_mem, rj, joint, tr, tape, pe_mem, nullptr, sp_mem.on ? &lz : nullptr,
-                                   sp_mem.on ? &sp_mem.Rv : nullptr))) return rc;
-    if ((rc = vpin::comm_mark(c, "hash_bullet"))) return rc;
-  }
-  g_spark_timings[4] = secs(t0, Clock::now());
+  std::vector<Fq> e16(16, Fq::zero());
+  std::copy(S.ev_ops, S.ev_ops + 15, e16.begin());  // row addr, row read_ts, col addr, col read_ts, val (comb_ops order)
+  if ((rc = prove_joint(S, *S.g_ops, comb_ops, sp_ops, e16, 4, rand_ops,
+                        {"claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops", "hash: polyeval ops"}, nullptr, S.pe_ops)))
+    return rc;
+  return prove_joint(S, *S.g_mem, comb_mem, sp_mem, {S.ev_mem[0], S.ev_mem[1]}, 1, rand_mem,
+                     {"claim_evals_mem", "challenge_combine_two_to_one", "joint_claim_eval_mem", "hash: polyeval mem"}, nullptr, S.pe_mem);
+}
 
-  // ---- bincode(R1CSEvalProof) (r1csinstance.rs:326-328; sparse_mlpoly.rs:1438-1441,1326-1329,1036-1042,698-707) ----
-  w.u64(comm_derefs.size());
-  for (auto& p : comm_derefs) w.point(p);
+// bincode(R1CSEvalProof) (r1csinstance.rs:326-328; sparse_mlpoly.rs:1438-1441,1326-1329,1036-1042,698-707)
+static void write_proof(const SparkProof& S, Writer& w) {
+  const auto& pl = S.pl;
+  w.u64(S.comm_derefs.size());
+  for (auto& p : S.comm_derefs) w.point(p);
   for (int s = 0; s < 2; s++) { w.scalar(pl[s][0]); w_scalars(w, &pl[s][1], 3); w_scalars(w, &pl[s][4], 3); w.scalar(pl[s][7]); }
-  w_scalars(w, dotp_left, 3);
-  w_scalars(w, dotp_right, 3);
-  write_batched(w, pf_mem);
-  write_batched(w, pf_ops);
-  w_scalars(w, &ev_ops[0], 3); w_scalars(w, &ev_ops[3], 3); w.scalar(ev_mem[0]);  // eval_row: addr, read_ts, audit_ts
-  w_scalars(w, &ev_ops[6], 3); w_scalars(w, &ev_ops[9], 3); w.scalar(ev_mem[1]);  // eval_col
-  w_scalars(w, &ev_ops[12], 3);                                                   // eval_val
-  w_scalars(w, &ev_derefs[0], 3); w_scalars(w, &ev_derefs[3], 3);                 // eval_derefs
-  write_dplog(w, pe_ops);
-  write_dplog(w, pe_mem);
-  write_dplog(w, pe_derefs);
+  w_scalars(w, S.dotp_left, 3);
+  w_scalars(w, S.dotp_right, 3);
+  write_batched(w, S.pf_mem);
+  write_batched(w, S.pf_ops);
+  w_scalars(w, &S.ev_ops[0], 3); w_scalars(w, &S.ev_ops[3], 3); w.scalar(S.ev_mem[0]);  // eval_row: addr, read_ts, audit_ts
+  w_scalars(w, &S.ev_ops[6], 3); w_scalars(w, &S.ev_ops[9], 3); w.scalar(S.ev_mem[1]);  // eval_col
+  w_scalars(w, &S.ev_ops[12], 3);                                                       // eval_val
+  w_scalars(w, &S.ev_derefs[0], 3); w_scalars(w, &S.ev_derefs[3], 3);                   // eval_derefs
+  write_dplog(w, S.pe_ops);
+  write_dplog(w, S.pe_mem);
+  write_dplog(w, S.pe_derefs);
+}
+
+// SparseMatPolyEvalProof::prove (sparse_mlpoly.rs:1466-1533) -> bincode(R1CSEvalProof) appended to w
+static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vector<Fq>& rx, const std::vector<Fq>& ry,
+                       const Fq evals[3], Transcript& tr, Transcript& tape, Writer& w) {
+  if (d->N < 4 || d->M < 4 || rx.size() != d->nx || ry.size() != d->ny) return VPIN_ESHAPE;
+  int rc;
+  SparkProof S(c, d, rx, ry, evals, tr, tape);
+  const Shape sh{d->nx, d->ny, S.N, S.M, S.lgN + 4, std::max(d->nx, d->ny) + 1, S.lgN + 3};
+  // the longest stream first: a later, longer request would rebuild the table and drop earlier views
+  if ((rc = get_view(c, std::max(sh.v_ops, sh.v_mem), &S.g_ops)) || (rc = get_view(c, sh.v_ops, &S.g_ops)) ||
+      (rc = get_view(c, sh.v_mem, &S.g_mem)) || (rc = get_view(c, sh.v_derefs, &S.g_derefs)))
+    return rc;
+  // one stage per timing slot of vpin_spark_last_timings
+  auto t0 = Clock::now();
+  auto lap = [&](int slot) { g_spark_timings[slot] = secs(t0, Clock::now()); t0 = Clock::now(); };
+  if ((rc = split_plan(S)) || (rc = stage_derefs(S))) return rc;
+  lap(1);
+  if (c->progress_flag) *c->progress_flag = 2;  // the proof's largest MSM is done (a scheduler may let other streams in now)
+  if ((rc = stage_network(S))) return rc;
+  lap(2);
+  if ((rc = stage_product(S))) return rc;
+  lap(3);
+  if ((rc = stage_hash(S))) return rc;
+  lap(4);
+  write_proof(S, w);
   return VPIN_OK;
 }
 

@@ -50,103 +50,122 @@ __global__ __launch_bounds__(kBlock) void u32_to_fq_kernel(const uint32_t* __res
   }
 }
 
-// blockIdx.y = slice 0..7: 0..2 row derefs of A,B,C, 3..5 col derefs, 6..7 zero padding
+// Which leaves (or derefs entries) a launch produces.  kStrided: the residue class lv.r0 (mod lv.step) of every slice, local
+// index k <-> global index lv.r0 + k*lv.step, n = the local length.  Otherwise every entry, with the index arithmetic of the
+// single-GPU kernels: lv is not read.
+template <bool kStrided>
+__device__ __forceinline__ size_t leaf_index(const SparkLeaves& lv, size_t k) {
+  if constexpr (kStrided) return lv.r0 + k * lv.step;
+  return k;
+}
+
+// comb[s*n + k] = Derefs slice s at entry leaf_index(k).  blockIdx.y = slice: 0..2 row derefs of A,B,C, 3..5 col derefs, and on
+// one GPU (gridDim.y = 8) 6..7 zero padding
+template <bool kStrided>
 __global__ __launch_bounds__(kBlock) void gather_derefs_kernel(const uint32_t* __restrict__ idx, size_t N,
                                                                const fq* __restrict__ mem_rx, const fq* __restrict__ mem_ry,
-                                                               fq* __restrict__ comb) {
+                                                               fq* __restrict__ comb, SparkLeaves lv) {
   const int s = blockIdx.y;
-  fq* dst = comb + (size_t)s * N;
-  if (s >= 6) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (size_t)gridDim.x * kBlock) fq_store(dst + i, fq_zero());
+  const size_t n = kStrided ? N / lv.step : N;
+  fq* dst = comb + (size_t)s * n;
+  if (!kStrided && s >= 6) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) fq_store(dst + i, fq_zero());
     return;
   }
   const uint32_t* a = idx + (size_t)(s < 3 ? s : 3 + s) * N;  // idx slices 0..2 = row, 6..8 = col
   const fq* mem = s < 3 ? mem_rx : mem_ry;
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (size_t)gridDim.x * kBlock)
-    fq_store(dst + i, fq_load(mem + a[i]));
+  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock)
+    fq_store(dst + k, fq_load(mem + a[leaf_index<kStrided>(lv, k)]));
 }
 
-// hash_func(addr, val, ts) - r_multiset_check = ts*r^2 + val*r + addr - gamma  (sparse_mlpoly.rs:557-560).
-// r2_boost = r^2 * R (Montgomery form of the Montgomery image), so fq_mul(raw ts, r2_boost) is ts*r^2
-// in Montgomery form without a separate conversion of ts.
-struct HashParams { fq r, r2, r2_boost, gamma; };
-struct CircIds { int v[12]; };  // global circuit (or dot-product half) of each local one
+// hash_func(addr, val, ts) - r_multiset_check = ts*r^2 + val*r + addr - gamma  (sparse_mlpoly.rs:557-560), written once per
+// forest.  hp.r2_boost = r^2 * R (Montgomery form of the Montgomery image), so fq_mul(raw ts, r2_boost) is ts*r^2 in
+// Montgomery form without a separate conversion of ts.
+// ops: the leaf of a read circuit; its write circuit's leaf is ops_leaf_write of it.
+__device__ __forceinline__ fq ops_leaf(const HashParams& hp, const fq& val, uint32_t addr, uint32_t ts) {
+  fq h = fq_sub(fq_mul(val, hp.r), hp.gamma);
+  if (addr) h = fq_add(h, fq_mul(fq_raw_u32(addr), fq_r2()));
+  if (ts) h = fq_add(h, fq_mul(fq_raw_u32(ts), hp.r2_boost));
+  return h;
+}
+__device__ __forceinline__ fq ops_leaf_write(const HashParams& hp, const fq& read) { return fq_add(read, hp.r2); }  // write ts = read ts + 1
+// mem: the leaf of an init circuit (timestamp 0) and, from it, the leaf of the audit circuit
+__device__ __forceinline__ fq mem_leaf_init(const HashParams& hp, const fq& val, size_t addr) {
+  fq h = fq_sub(fq_mul(val, hp.r), hp.gamma);
+  if (addr) h = fq_add(h, fq_mul(fq_raw_u32((uint32_t)addr), fq_r2()));
+  return h;
+}
+__device__ __forceinline__ fq mem_leaf_audit(const HashParams& hp, fq init, uint32_t ts) {
+  if (ts) init = fq_add(init, fq_mul(fq_raw_u32(ts), hp.r2_boost));
+  return init;
+}
 
-// blockIdx.y = side*3 + m.  Writes level 0 of read circuit (side*6 + m) and write circuit (side*6 + 3 + m).
+// Level 0 of all 12 ops circuits over n = f.n leaves each.  blockIdx.y = side*3 + m: one hash is computed and stored to the
+// read circuit (side*6 + m) and the write circuit (side*6 + 3 + m).  derefs: 6 slices of n (the rank's local view when kStrided).
+template <bool kStrided>
 __global__ __launch_bounds__(kBlock) void hash_ops_kernel(const uint32_t* __restrict__ idx, const fq* __restrict__ derefs, size_t N,
-                                                          HashParams hp, fq* __restrict__ forest) {
+                                                          HashParams hp, fq* __restrict__ forest, SparkLeaves lv) {
   const int side = blockIdx.y / 3, m = blockIdx.y % 3;
+  const size_t n = kStrided ? N / lv.step : N;
   const uint32_t* addr = idx + (size_t)(side * 6 + m) * N;
   const uint32_t* ts = idx + (size_t)(side * 6 + 3 + m) * N;
-  const fq* val = derefs + (size_t)(side * 3 + m) * N;
-  fq* rd = forest + (size_t)(side * 6 + m) * 2 * N;
-  fq* wr = forest + (size_t)(side * 6 + 3 + m) * 2 * N;
-  const fq r2c = fq_r2();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (size_t)gridDim.x * kBlock) {
-    fq h = fq_sub(fq_mul(fq_load(val + i), hp.r), hp.gamma);
-    uint32_t a = addr[i], t = ts[i];
-    if (a) h = fq_add(h, fq_mul(fq_raw_u32(a), r2c));
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    fq_store(rd + i, h);
-    fq_store(wr + i, fq_add(h, hp.r2));  // write timestamp = read timestamp + 1
+  const fq* val = derefs + (size_t)(side * 3 + m) * n;
+  fq* rd = forest + (size_t)(side * 6 + m) * 2 * n;
+  fq* wr = forest + (size_t)(side * 6 + 3 + m) * 2 * n;
+  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
+    const size_t i = leaf_index<kStrided>(lv, k);
+    const fq h = ops_leaf(hp, fq_load(val + k), addr[i], ts[i]);
+    fq_store(rd + k, h);
+    fq_store(wr + k, ops_leaf_write(hp, h));
   }
 }
 
-// blockIdx.y = side.  Level 0 of init circuit (2*side) and audit circuit (2*side + 1).
+// Level 0 of all 4 mem circuits.  blockIdx.y = side: init circuit (2*side) and audit circuit (2*side + 1).
+template <bool kStrided>
 __global__ __launch_bounds__(kBlock) void hash_mem_kernel(const uint32_t* __restrict__ audit_ts, const fq* __restrict__ mem_rx,
                                                           const fq* __restrict__ mem_ry, size_t M, HashParams hp,
-                                                          fq* __restrict__ forest) {
+                                                          fq* __restrict__ forest, SparkLeaves lv) {
   const int side = blockIdx.y;
+  const size_t n = kStrided ? M / lv.step : M;
   const fq* mem = side ? mem_ry : mem_rx;
   const uint32_t* ts = audit_ts + (size_t)side * M;
-  fq* init = forest + (size_t)(2 * side) * 2 * M;
-  fq* audit = forest + (size_t)(2 * side + 1) * 2 * M;
-  const fq r2c = fq_r2();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (size_t)gridDim.x * kBlock) {
-    fq h = fq_sub(fq_mul(fq_load(mem + i), hp.r), hp.gamma);
-    if (i) h = fq_add(h, fq_mul(fq_raw_u32((uint32_t)i), r2c));
-    fq_store(init + i, h);
-    uint32_t t = ts[i];
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    fq_store(audit + i, h);
+  fq* init = forest + (size_t)(2 * side) * 2 * n;
+  fq* audit = forest + (size_t)(2 * side + 1) * 2 * n;
+  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
+    const size_t i = leaf_index<kStrided>(lv, k);
+    const fq h = mem_leaf_init(hp, fq_load(mem + i), i);
+    fq_store(init + k, h);
+    fq_store(audit + k, mem_leaf_audit(hp, h, ts[i]));
   }
 }
 
-// The same leaves for a SUBSET of the circuits (one proof over several GPUs: a rank builds the trees of the circuits it
-// owns and nothing else).  ids.v[j] = global circuit of local tree j, in the numbering of the two kernels above:
-// ops: side*6 + kind*3 + m (kind 0 = read, 1 = write); mem: side*2 + kind (kind 0 = init, 1 = audit).
+// The same leaves for a SUBSET of the circuits (one proof over several GPUs, split by whole circuits: a rank builds the trees
+// of the circuits it owns and nothing else), one tree per blockIdx.y.  lv.ids[j] = global circuit of local tree j, in the
+// numbering of the two kernels above: ops: side*6 + kind*3 + m (kind 0 = read, 1 = write); mem: side*2 + kind (kind 0 = init,
+// 1 = audit).
 __global__ __launch_bounds__(kBlock) void hash_ops_sub_kernel(const uint32_t* __restrict__ idx, const fq* __restrict__ derefs, size_t N,
-                                                              HashParams hp, fq* __restrict__ forest, CircIds ids) {
-  const int g = ids.v[blockIdx.y], side = g / 6, kind = (g % 6) / 3, m = g % 3;
+                                                              HashParams hp, fq* __restrict__ forest, SparkLeaves lv) {
+  const int g = lv.ids[blockIdx.y], side = g / 6, kind = (g % 6) / 3, m = g % 3;
   const uint32_t* addr = idx + (size_t)(side * 6 + m) * N;
   const uint32_t* ts = idx + (size_t)(side * 6 + 3 + m) * N;
   const fq* val = derefs + (size_t)(side * 3 + m) * N;
   fq* leaf = forest + (size_t)blockIdx.y * 2 * N;
-  const fq r2c = fq_r2();
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (size_t)gridDim.x * kBlock) {
-    fq h = fq_sub(fq_mul(fq_load(val + i), hp.r), hp.gamma);
-    uint32_t a = addr[i], t = ts[i];
-    if (a) h = fq_add(h, fq_mul(fq_raw_u32(a), r2c));
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    fq_store(leaf + i, kind ? fq_add(h, hp.r2) : h);
+    const fq h = ops_leaf(hp, fq_load(val + i), addr[i], ts[i]);
+    fq_store(leaf + i, kind ? ops_leaf_write(hp, h) : h);
   }
 }
 
 __global__ __launch_bounds__(kBlock) void hash_mem_sub_kernel(const uint32_t* __restrict__ audit_ts, const fq* __restrict__ mem_rx,
                                                               const fq* __restrict__ mem_ry, size_t M, HashParams hp,
-                                                              fq* __restrict__ forest, CircIds ids) {
-  const int g = ids.v[blockIdx.y], side = g / 2, kind = g % 2;
+                                                              fq* __restrict__ forest, SparkLeaves lv) {
+  const int g = lv.ids[blockIdx.y], side = g / 2, kind = g % 2;
   const fq* mem = side ? mem_ry : mem_rx;
   const uint32_t* ts = audit_ts + (size_t)side * M;
   fq* leaf = forest + (size_t)blockIdx.y * 2 * M;
-  const fq r2c = fq_r2();
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (size_t)gridDim.x * kBlock) {
-    fq h = fq_sub(fq_mul(fq_load(mem + i), hp.r), hp.gamma);
-    if (i) h = fq_add(h, fq_mul(fq_raw_u32((uint32_t)i), r2c));
-    if (kind) {
-      uint32_t t = ts[i];
-      if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    }
+    fq h = mem_leaf_init(hp, fq_load(mem + i), i);
+    if (kind) h = mem_leaf_audit(hp, h, ts[i]);
     fq_store(leaf + i, h);
   }
 }
@@ -156,21 +175,8 @@ __global__ __launch_bounds__(kBlock) void hash_mem_sub_kernel(const uint32_t* __
 // sum-checks over it (dense_mlpoly.rs:229-236): while len/2 is a multiple of the world size both members of a pair lie in
 // the same residue class.  Rank r0 therefore owns the leaves i = r0 (mod step) of EVERY circuit; its local arrays (local
 // index k <-> global index r0 + k*step) are product trees over n/step leaves in their own right, built and proven by the
-// unchanged kernels, and no table entry ever moves.  The kernels below produce those local leaves and the local views of
-// the committed polynomials directly from the decommitment.
-
-// comb_loc[s*(N/step) + k] = Derefs slice s (0..2 row A,B,C; 3..5 col A,B,C) at entry r0 + k*step
-__global__ __launch_bounds__(kBlock) void gather_derefs_loc_kernel(const uint32_t* __restrict__ idx, size_t N, const fq* __restrict__ mem_rx,
-                                                                   const fq* __restrict__ mem_ry, fq* __restrict__ comb_loc, size_t r0,
-                                                                   size_t step) {
-  const int s = blockIdx.y;
-  const size_t nloc = N / step;
-  const uint32_t* a = idx + (size_t)(s < 3 ? s : 3 + s) * N;
-  const fq* mem = s < 3 ? mem_rx : mem_ry;
-  fq* dst = comb_loc + (size_t)s * nloc;
-  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < nloc; k += (size_t)gridDim.x * kBlock)
-    fq_store(dst + k, fq_load(mem + a[r0 + k * step]));
-}
+// unchanged kernels, and no table entry ever moves.  The kStrided instantiations above produce those local leaves and the
+// local view of the derefs slices directly from the decommitment; the two kernels below, the other local views.
 
 // rows_out[jl*R + c] = entry (r0 + jl*step)*R + c of the derefs polynomial (8 slices of N, the last two zero): the rows
 // r0, r0 + step, .. of its commitment matrix, stored densely
@@ -186,51 +192,6 @@ __global__ __launch_bounds__(kBlock) void gather_derefs_rows_kernel(const uint32
     if (sl < 3) v = fq_load(mem_rx + idx[sl * N + i]);
     else if (sl < 6) v = fq_load(mem_ry + idx[(3 + sl) * N + i]);
     fq_store(rows_out + t, v);
-  }
-}
-
-// local leaves of the 12 ops circuits: blockIdx.y = side*3 + m writes the read circuit (side*6 + m) and the write circuit
-// (side*6 + 3 + m) of the LOCAL forest (n/step leaves each)
-__global__ __launch_bounds__(kBlock) void hash_ops_strided_kernel(const uint32_t* __restrict__ idx, const fq* __restrict__ comb_loc, size_t N,
-                                                                  HashParams hp, fq* __restrict__ forest, size_t r0, size_t step) {
-  const int side = blockIdx.y / 3, m = blockIdx.y % 3;
-  const size_t nloc = N / step;
-  const uint32_t* addr = idx + (size_t)(side * 6 + m) * N;
-  const uint32_t* ts = idx + (size_t)(side * 6 + 3 + m) * N;
-  const fq* val = comb_loc + (size_t)(side * 3 + m) * nloc;
-  fq* rd = forest + (size_t)(side * 6 + m) * 2 * nloc;
-  fq* wr = forest + (size_t)(side * 6 + 3 + m) * 2 * nloc;
-  const fq r2c = fq_r2();
-  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < nloc; k += (size_t)gridDim.x * kBlock) {
-    const size_t i = r0 + k * step;
-    fq h = fq_sub(fq_mul(fq_load(val + k), hp.r), hp.gamma);
-    uint32_t a = addr[i], t = ts[i];
-    if (a) h = fq_add(h, fq_mul(fq_raw_u32(a), r2c));
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    fq_store(rd + k, h);
-    fq_store(wr + k, fq_add(h, hp.r2));
-  }
-}
-
-// local leaves of the 4 mem circuits: blockIdx.y = side
-__global__ __launch_bounds__(kBlock) void hash_mem_strided_kernel(const uint32_t* __restrict__ audit_ts, const fq* __restrict__ mem_rx,
-                                                                  const fq* __restrict__ mem_ry, size_t M, HashParams hp,
-                                                                  fq* __restrict__ forest, size_t r0, size_t step) {
-  const int side = blockIdx.y;
-  const size_t nloc = M / step;
-  const fq* mem = side ? mem_ry : mem_rx;
-  const uint32_t* ts = audit_ts + (size_t)side * M;
-  fq* init = forest + (size_t)(2 * side) * 2 * nloc;
-  fq* audit = forest + (size_t)(2 * side + 1) * 2 * nloc;
-  const fq r2c = fq_r2();
-  for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < nloc; k += (size_t)gridDim.x * kBlock) {
-    const size_t i = r0 + k * step;
-    fq h = fq_sub(fq_mul(fq_load(mem + i), hp.r), hp.gamma);
-    if (i) h = fq_add(h, fq_mul(fq_raw_u32((uint32_t)i), r2c));
-    fq_store(init + k, h);
-    uint32_t t = ts[i];
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    fq_store(audit + k, h);
   }
 }
 
@@ -417,6 +378,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void prod_round_kernel(fq* __res
 }
 
 struct DotpPtrs { const fq* src[3]; fq* dst[3]; size_t src_stride[3]; };
+struct CircIds { int v[12]; };  // global dot-product half of each local one
 
 // MODE 0: evaluate src as is; 1: fold src -> dst, evaluate; (dst == src for the in-place rounds)
 template <bool BIND>
@@ -754,10 +716,21 @@ int spark_find_hot_cols(vpin_ctx* c, vpin_spark_decomm* d) {
   return VPIN_OK;
 }
 
-int spark_gather_derefs(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, fq* comb) {
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)d->N * (6 * 68.0 + 2 * 32.0));
-  hipLaunchKernelGGL(gather_derefs_kernel, dim3(grid_for(d->N), 8), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N,
-                     mem_rx, mem_ry, comb);
+int spark_gather_derefs(vpin_ctx* c, const vpin_spark_decomm* d, const SparkLeaves& lv, const fq* mem_rx, const fq* mem_ry, fq* comb,
+                        fq* comb_rows, size_t R, size_t nrows_loc) {
+  const bool strided = lv.step > 1;
+  if (!c || !d || !mem_rx || !mem_ry || !comb || lv.ncirc || lv.step == 0 || lv.r0 >= lv.step || d->N % lv.step) return VPIN_EINVAL;
+  if (strided && (!comb_rows || R == 0 || d->N % R)) return VPIN_EINVAL;
+  (void)hipSetDevice(c->device);
+  ProfScope ps(c, VPIN_K_SPARK_BUILD, strided ? (double)d->N * 6 * 68.0 + (double)nrows_loc * R * 68.0 : (double)d->N * (6 * 68.0 + 2 * 32.0));
+  const dim3 grid(grid_for(d->N / lv.step), strided ? 6 : 8);
+  if (strided)
+    hipLaunchKernelGGL(gather_derefs_kernel<true>, grid, dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N, mem_rx, mem_ry, comb, lv);
+  else
+    hipLaunchKernelGGL(gather_derefs_kernel<false>, grid, dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N, mem_rx, mem_ry, comb, lv);
+  if (strided && nrows_loc)
+    hipLaunchKernelGGL(gather_derefs_rows_kernel, dim3(grid_for(nrows_loc * R)), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N,
+                       R, mem_rx, mem_ry, comb_rows, lv.r0, lv.step, nrows_loc);
   VPIN_HIP_TRY(hipGetLastError());
   return VPIN_OK;
 }
@@ -784,32 +757,69 @@ static int build_levels(vpin_ctx* c, SparkForest* f) {
   return VPIN_OK;
 }
 
-int spark_build_forests(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const fq* mem_rx, const fq* mem_ry,
-                        const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                        const uint8_t gamma[32], SparkForest* ops, SparkForest* mem) {
-  if (!c || !d || !ops || !mem || !ops->base || !mem->base) return VPIN_EINVAL;
-  if (ops->n != d->N || mem->n != d->M || ops->ncirc != 12 || mem->ncirc != 4 || d->N < 2 || d->M < 2) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  HashParams hp;
-  hp.r = load_host_fq(r_hash);
-  hp.r2 = load_host_fq(r_hash_sqr);
-  hp.r2_boost = load_host_fq(r_hash_sqr_boost);
-  hp.gamma = load_host_fq(gamma);
-  {
-    // leaves: 6 gathers of (addr, ts, val) -> 12 N leaves; 2 x (ts, mem) -> 4 M leaves; then 1 product per inner node
-    ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)d->N * (6 * (8.0 + 32.0) + 12 * 32.0 + 12 * 64.0) + (double)d->M * (2 * 36.0 + 4 * 32.0 + 4 * 64.0));
-    // (leaves and the first three levels in ONE pass -- eight strided leaves per thread -- were measured and dropped: 21.2 ms
-    // against 18.7 ms for the 2^25 instance with the leaf kernels below and three tree levels per pass after them)
-    hipLaunchKernelGGL(hash_ops_kernel, dim3(grid_for(d->N), 6), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, comb_derefs,
-                       d->N, hp, ops->base);
-    hipLaunchKernelGGL(hash_mem_kernel, dim3(grid_for(d->M), 2), dim3(kBlock), 0, c->stream,
-                       (const uint32_t*)(d->idx + 12 * d->N), mem_rx, mem_ry, d->M, hp, mem->base);
-    VPIN_HIP_TRY(hipGetLastError());
-    int rc = build_levels(c, ops);
-    if (!rc) rc = build_levels(c, mem);
-    if (rc) return rc;
-  }
+// ---- one forest: leaves from the decommitment, then every upper level ---------------------------------------------------
+static int check_forest(const vpin_ctx* c, const vpin_spark_decomm* d, const SparkLeaves& lv, const SparkInputs& in, const SparkForest* f,
+                        bool is_mem) {
+  const int all = is_mem ? 4 : 12;
+  if (!c || !d || !f || !f->base || lv.step == 0 || lv.r0 >= lv.step || (lv.ncirc && lv.step > 1)) return VPIN_EINVAL;
+  if (is_mem ? (!in.mem_rx || !in.mem_ry) : !in.derefs) return VPIN_EINVAL;
+  if (lv.ncirc < 0 || lv.ncirc > all) return VPIN_EINVAL;
+  for (int j = 0; j < lv.ncirc; j++)
+    if (lv.ids[j] < 0 || lv.ids[j] >= all) return VPIN_EINVAL;
+  if (f->n * lv.step != (is_mem ? d->M : d->N) || f->ncirc != (lv.ncirc ? lv.ncirc : all) || f->n < 2) return VPIN_ESHAPE;
   return VPIN_OK;
+}
+
+// algorithmic bytes of one forest.  All circuits: 6 gathers of (addr, ts, val) -> 12 n leaves, or 2 x (ts, mem) -> 4 n leaves,
+// each hash stored twice; a subset: every tree reads its own inputs.  Then 1 product per inner node.
+static double forest_bytes(const SparkLeaves& lv, const SparkForest* f, bool is_mem) {
+  if (lv.ncirc) return (double)f->n * f->ncirc * (is_mem ? (36.0 + 32.0 + 64.0) : (8.0 + 32.0 + 32.0 + 64.0));
+  return (double)f->n * (is_mem ? (2 * 36.0 + 4 * 32.0 + 4 * 64.0) : (6 * (8.0 + 32.0) + 12 * 32.0 + 12 * 64.0));
+}
+
+// (leaves and the first three levels in ONE pass -- eight strided leaves per thread -- were measured and dropped: 21.2 ms
+// against 18.7 ms for the 2^25 instance with the leaf kernels and three tree levels per pass after them)
+static void launch_leaves(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const SparkLeaves& lv, const SparkInputs& in,
+                          SparkForest* f, bool is_mem) {
+  const uint32_t* idx = d->idx;
+  const uint32_t* audit_ts = d->idx + 12 * d->N;
+  const dim3 paired(grid_for(f->n), is_mem ? 2 : 6), each(grid_for(f->n), f->ncirc), block(kBlock);
+  if (is_mem) {
+    if (lv.ncirc) hipLaunchKernelGGL(hash_mem_sub_kernel, each, block, 0, c->stream, audit_ts, in.mem_rx, in.mem_ry, d->M, hp, f->base, lv);
+    else if (lv.step > 1) hipLaunchKernelGGL(hash_mem_kernel<true>, paired, block, 0, c->stream, audit_ts, in.mem_rx, in.mem_ry, d->M, hp, f->base, lv);
+    else hipLaunchKernelGGL(hash_mem_kernel<false>, paired, block, 0, c->stream, audit_ts, in.mem_rx, in.mem_ry, d->M, hp, f->base, lv);
+  } else {
+    if (lv.ncirc) hipLaunchKernelGGL(hash_ops_sub_kernel, each, block, 0, c->stream, idx, in.derefs, d->N, hp, f->base, lv);
+    else if (lv.step > 1) hipLaunchKernelGGL(hash_ops_kernel<true>, paired, block, 0, c->stream, idx, in.derefs, d->N, hp, f->base, lv);
+    else hipLaunchKernelGGL(hash_ops_kernel<false>, paired, block, 0, c->stream, idx, in.derefs, d->N, hp, f->base, lv);
+  }
+}
+
+int spark_build_forest(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const SparkLeaves& lv, const SparkInputs& in,
+                       SparkForest* f, bool is_mem) {
+  int rc = check_forest(c, d, lv, in, f, is_mem);
+  if (rc) return rc;
+  (void)hipSetDevice(c->device);
+  ProfScope ps(c, VPIN_K_SPARK_BUILD, forest_bytes(lv, f, is_mem));
+  launch_leaves(c, d, hp, lv, in, f, is_mem);
+  VPIN_HIP_TRY(hipGetLastError());
+  return build_levels(c, f);
+}
+
+// both forests as one launch group: the leaves of both, then the levels of both
+int spark_build_forests(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const SparkLeaves& lv, const SparkInputs& in,
+                        SparkForest* ops, SparkForest* mem) {
+  int rc = check_forest(c, d, lv, in, ops, false);
+  if (!rc) rc = check_forest(c, d, lv, in, mem, true);
+  if (rc) return rc;
+  (void)hipSetDevice(c->device);
+  ProfScope ps(c, VPIN_K_SPARK_BUILD, forest_bytes(lv, ops, false) + forest_bytes(lv, mem, true));
+  launch_leaves(c, d, hp, lv, in, ops, false);
+  launch_leaves(c, d, hp, lv, in, mem, true);
+  VPIN_HIP_TRY(hipGetLastError());
+  rc = build_levels(c, ops);
+  if (!rc) rc = build_levels(c, mem);
+  return rc;
 }
 
 // ---- the mem circuits' roots without their trees (round 5) --------------------------------------------------------------
@@ -829,15 +839,11 @@ __global__ __launch_bounds__(kBlock) void hash_mem_roots_kernel(const uint32_t* 
   const int side = blockIdx.y;
   const fq* mem = side ? mem_ry : mem_rx;
   const uint32_t* ts = audit_ts + (size_t)side * M;
-  const fq r2c = fq_r2();
   fq pi = fq_one(), pa = fq_one();
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (size_t)gridDim.x * kBlock) {
-    fq h = fq_sub(fq_mul(fq_load(mem + i), hp.r), hp.gamma);
-    if (i) h = fq_add(h, fq_mul(fq_raw_u32((uint32_t)i), r2c));
+    const fq h = mem_leaf_init(hp, fq_load(mem + i), i);
     pi = fq_mul(pi, h);
-    const uint32_t t = ts[i];
-    if (t) h = fq_add(h, fq_mul(fq_raw_u32(t), hp.r2_boost));
-    pa = fq_mul(pa, h);
+    pa = fq_mul(pa, mem_leaf_audit(hp, h, ts[i]));
   }
   pi = fq_wave_prod(pi);
   pa = fq_wave_prod(pa);
@@ -866,19 +872,8 @@ __global__ __launch_bounds__(kBlock) void roots_finish_kernel(const fq* __restri
   }
 }
 
-static HashParams hash_params(const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                              const uint8_t gamma[32]) {
-  HashParams hp;
-  hp.r = load_host_fq(r_hash);
-  hp.r2 = load_host_fq(r_hash_sqr);
-  hp.r2_boost = load_host_fq(r_hash_sqr_boost);
-  hp.gamma = load_host_fq(gamma);
-  return hp;
-}
-
 // roots of the four mem circuits (init / audit per side) -> c->h_spark[2 * circuit], as spark_fetch_tops(&mem_forest, 2) leaves them
-int spark_mem_roots(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, const uint8_t r_hash[32],
-                    const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32]) {
+int spark_mem_roots(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const fq* mem_rx, const fq* mem_ry) {
   if (!c || !d || !mem_rx || !mem_ry || d->M < 2) return VPIN_EINVAL;
   int rc = spark_pinned(c);
   if (rc) return rc;
@@ -889,78 +884,11 @@ int spark_mem_roots(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, c
   {
     ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)d->M * 2 * 36.0);
     hipLaunchKernelGGL(hash_mem_roots_kernel, dim3((unsigned)np, 2), dim3(kBlock), 0, c->stream, (const uint32_t*)(d->idx + 12 * d->N), mem_rx,
-                       mem_ry, d->M, hash_params(r_hash, r_hash_sqr, r_hash_sqr_boost, gamma), (fq*)parts.p);
+                       mem_ry, d->M, hp, (fq*)parts.p);
   }
   hipLaunchKernelGGL(roots_finish_kernel, dim3(4), dim3(kBlock), 0, c->stream, (const fq*)parts.p, np, c->h_spark);
   VPIN_HIP_TRY(hipGetLastError());
   return spark_wait(c);
-}
-
-// the ops forest alone / the mem forest alone (spark_build_forests below does both)
-int spark_build_forest_ops(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const uint8_t r_hash[32],
-                           const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32], SparkForest* ops) {
-  if (!c || !d || !ops || !ops->base || !comb_derefs) return VPIN_EINVAL;
-  if (ops->n != d->N || ops->ncirc != 12 || d->N < 2) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)d->N * (6 * (8.0 + 32.0) + 12 * 32.0 + 12 * 64.0));
-  hipLaunchKernelGGL(hash_ops_kernel, dim3(grid_for(d->N), 6), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, comb_derefs, d->N,
-                     hash_params(r_hash, r_hash_sqr, r_hash_sqr_boost, gamma), ops->base);
-  VPIN_HIP_TRY(hipGetLastError());
-  return build_levels(c, ops);
-}
-int spark_build_forest_mem(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, const uint8_t r_hash[32],
-                           const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32], SparkForest* mem) {
-  if (!c || !d || !mem || !mem->base || !mem_rx || !mem_ry) return VPIN_EINVAL;
-  if (mem->n != d->M || mem->ncirc != 4 || d->M < 2) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)d->M * (2 * 36.0 + 4 * 32.0 + 4 * 64.0));
-  hipLaunchKernelGGL(hash_mem_kernel, dim3(grid_for(d->M), 2), dim3(kBlock), 0, c->stream, (const uint32_t*)(d->idx + 12 * d->N), mem_rx,
-                     mem_ry, d->M, hash_params(r_hash, r_hash_sqr, r_hash_sqr_boost, gamma), mem->base);
-  VPIN_HIP_TRY(hipGetLastError());
-  return build_levels(c, mem);
-}
-
-int spark_build_forest_sub(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const fq* mem_rx, const fq* mem_ry,
-                           const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                           const uint8_t gamma[32], SparkForest* f, const int* ids, bool is_mem) {
-  if (!c || !d || !f || !f->base || !ids || f->ncirc < 1 || f->ncirc > (is_mem ? 4 : 12)) return VPIN_EINVAL;
-  if (f->n != (is_mem ? d->M : d->N) || f->n < 2) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  HashParams hp;
-  hp.r = load_host_fq(r_hash);
-  hp.r2 = load_host_fq(r_hash_sqr);
-  hp.r2_boost = load_host_fq(r_hash_sqr_boost);
-  hp.gamma = load_host_fq(gamma);
-  CircIds cid{};
-  for (int j = 0; j < f->ncirc; j++) {
-    if (ids[j] < 0 || ids[j] >= (is_mem ? 4 : 12)) return VPIN_EINVAL;
-    cid.v[j] = ids[j];
-  }
-  const double per = is_mem ? (36.0 + 32.0 + 64.0) : (8.0 + 32.0 + 32.0 + 64.0);
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, (double)f->n * f->ncirc * per);
-  if (is_mem)
-    hipLaunchKernelGGL(hash_mem_sub_kernel, dim3(grid_for(d->M), f->ncirc), dim3(kBlock), 0, c->stream,
-                       (const uint32_t*)(d->idx + 12 * d->N), mem_rx, mem_ry, d->M, hp, f->base, cid);
-  else
-    hipLaunchKernelGGL(hash_ops_sub_kernel, dim3(grid_for(d->N), f->ncirc), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx,
-                       comb_derefs, d->N, hp, f->base, cid);
-  VPIN_HIP_TRY(hipGetLastError());
-  return build_levels(c, f);
-}
-
-int spark_gather_derefs_strided(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, size_t r0, size_t step,
-                                fq* comb_loc, fq* comb_rows, size_t R, size_t nrows_loc) {
-  if (!c || !d || !mem_rx || !mem_ry || !comb_loc || !comb_rows || step == 0 || r0 >= step || d->N % step || R == 0 || d->N % R)
-    return VPIN_EINVAL;
-  (void)hipSetDevice(c->device);
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, ((double)d->N * 6 * 68.0 + (double)nrows_loc * R * 68.0) / 1.0);
-  hipLaunchKernelGGL(gather_derefs_loc_kernel, dim3(grid_for(d->N / step), 6), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N,
-                     mem_rx, mem_ry, comb_loc, r0, step);
-  if (nrows_loc)
-    hipLaunchKernelGGL(gather_derefs_rows_kernel, dim3(grid_for(nrows_loc * R)), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, d->N,
-                       R, mem_rx, mem_ry, comb_rows, r0, step, nrows_loc);
-  VPIN_HIP_TRY(hipGetLastError());
-  return VPIN_OK;
 }
 
 int spark_take_strided(vpin_ctx* c, const fq* src, size_t nloc, size_t r0, size_t step, fq* dst) {
@@ -969,29 +897,6 @@ int spark_take_strided(vpin_ctx* c, const fq* src, size_t nloc, size_t r0, size_
   hipLaunchKernelGGL(take_strided_kernel, dim3(grid_for(nloc)), dim3(kBlock), 0, c->stream, src, nloc, r0, step, dst);
   VPIN_HIP_TRY(hipGetLastError());
   return VPIN_OK;
-}
-
-// local forests of rank r0 of `step`: ops over N/step leaves, mem over M/step leaves, all 12 / 4 circuits
-int spark_build_forests_strided(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_loc, const fq* mem_rx, const fq* mem_ry,
-                                const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                                const uint8_t gamma[32], SparkForest* ops, SparkForest* mem, size_t r0, size_t step) {
-  if (!c || !d || !ops || !mem || !ops->base || !mem->base || step == 0 || r0 >= step) return VPIN_EINVAL;
-  if (ops->n * step != d->N || mem->n * step != d->M || ops->ncirc != 12 || mem->ncirc != 4 || ops->n < 2 || mem->n < 2) return VPIN_ESHAPE;
-  (void)hipSetDevice(c->device);
-  HashParams hp;
-  hp.r = load_host_fq(r_hash);
-  hp.r2 = load_host_fq(r_hash_sqr);
-  hp.r2_boost = load_host_fq(r_hash_sqr_boost);
-  hp.gamma = load_host_fq(gamma);
-  ProfScope ps(c, VPIN_K_SPARK_BUILD, ((double)d->N * (6 * (8.0 + 32.0) + 12 * 32.0 + 12 * 64.0) + (double)d->M * (2 * 36.0 + 4 * 32.0 + 4 * 64.0)) / (double)step);
-  hipLaunchKernelGGL(hash_ops_strided_kernel, dim3(grid_for(ops->n), 6), dim3(kBlock), 0, c->stream, (const uint32_t*)d->idx, comb_loc, d->N, hp,
-                     ops->base, r0, step);
-  hipLaunchKernelGGL(hash_mem_strided_kernel, dim3(grid_for(mem->n), 2), dim3(kBlock), 0, c->stream,
-                     (const uint32_t*)(d->idx + 12 * d->N), mem_rx, mem_ry, d->M, hp, mem->base, r0, step);
-  VPIN_HIP_TRY(hipGetLastError());
-  int rc = build_levels(c, ops);
-  if (!rc) rc = build_levels(c, mem);
-  return rc;
 }
 
 int spark_fetch_tops(vpin_ctx* c, const SparkForest* f, size_t cnt) {
@@ -1162,12 +1067,7 @@ int spark_collect(vpin_ctx* c, const SparkForest* f, int level, const vpin_spark
   return spark_wait_flag(c);
 }
 
-int spark_triple_sums(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const int* halves, int nh) {
-  if (!d) return VPIN_EINVAL;
-  return spark_triple_sums_raw(c, comb_derefs, d->vals, d->N, halves, nh);
-}
-
-int spark_triple_sums_raw(vpin_ctx* c, const fq* comb_derefs, const fq* vals, size_t N, const int* halves, int nh) {
+int spark_triple_sums(vpin_ctx* c, const fq* comb_derefs, const fq* vals, size_t N, const int* halves, int nh) {
   if (!c || !comb_derefs || !vals || N < 2 || nh < 1 || nh > 6) return VPIN_EINVAL;
   CircIds kmap{};
   for (int i = 0; i < nh; i++) kmap.v[i] = halves ? halves[i] : i;

@@ -49,9 +49,25 @@ int spark_comb_tables(vpin_ctx* c, vpin_spark_decomm* d);
 int spark_comb_make(vpin_ctx* c, const vpin_spark_decomm* d, vpin_table** ops, vpin_table** mem, bool pooled = true);
 void spark_comb_release(vpin_ctx* c, vpin_spark_decomm* d, bool to_driver = false);
 
+// Which leaves of the product circuits (and which entries of the committed polynomials) a launch produces: one description
+// for one GPU and both splits of a proof over several.
+//   one GPU:                {}                  every entry of every circuit
+//   split by residue class: {r0, step}          the entries r0, r0 + step, .. of every circuit (local index k <-> r0 + k*step)
+//   split by whole circuits: ncirc, ids         every entry of the circuits ids[0..ncirc) (ops: side*6 + kind*3 + m, kind
+//                                               0 read / 1 write; mem: side*2 + kind, kind 0 init / 1 audit), one tree each
+// Passed to the kernels by value.
+struct SparkLeaves {
+  size_t r0 = 0, step = 1;
+  int ncirc = 0;
+  int ids[12] = {};
+};
+
 // Derefs (sparse_mlpoly.rs:267-283,525-531): comb[m*N+i] = mem_rx[row_m[i]], comb[(3+m)*N+i] =
-// mem_ry[col_m[i]], comb[6N..8N) = 0
-int spark_gather_derefs(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, fq* comb);
+// mem_ry[col_m[i]], comb[6N..8N) = 0.
+// Split by residue class (lv.step > 1): comb = 6 x N/step, the six slices at the entries r0 + k*step, without the zero
+// padding; and comb_rows = nrows_loc x R, the rows r0, r0 + step, .. of the derefs polynomial's commitment matrix, dense.
+int spark_gather_derefs(vpin_ctx* c, const vpin_spark_decomm* d, const SparkLeaves& lv, const fq* mem_rx, const fq* mem_ry, fq* comb,
+                        fq* comb_rows = nullptr, size_t R = 0, size_t nrows_loc = 0);
 // fills d->hot_col: candidates are the constant-1 column (num_vars) and the first input (num_vars + 1)
 int spark_find_hot_cols(vpin_ctx* c, vpin_spark_decomm* d);
 
@@ -66,29 +82,25 @@ struct SparkForest {
   size_t level_off(int l) const { return 2 * n - ((2 * n) >> l); }
 };
 
-// Layers::build_hash_layer (sparse_mlpoly.rs:547-622) for both sides, written as level 0 of the
-// forests: ops = [row read A,B,C | row write A,B,C | col read A,B,C | col write A,B,C] (n = N),
-// mem = [row init, row audit, col init, col audit] (n = M); then every upper level.
-// r_hash_sqr = r_hash^2; r_hash_sqr_boost = r_hash^2 * R (its Montgomery image taken to Montgomery form
-// once more), which lets the kernel multiply RAW u32 timestamps straight into Montgomery form.
-int spark_build_forests(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const fq* mem_rx, const fq* mem_ry,
-                        const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                        const uint8_t gamma[32], SparkForest* ops, SparkForest* mem);
+// The multiset hash's challenge (sparse_mlpoly.rs:557-560), Montgomery form: r2 = r^2; r2_boost = r^2 * R (its Montgomery
+// image taken to Montgomery form once more), which lets a kernel multiply RAW u32 timestamps straight into Montgomery form.
+struct HashParams { fq r, r2, r2_boost, gamma; };
+// what the leaves are hashed from, next to the decommitment: derefs = the six derefs slices over the entries `lv` names
+// (ops forests), mem_rx / mem_ry = the two memories eq(rx, .), eq(ry, .) (mem forests)
+struct SparkInputs { const fq* derefs; const fq* mem_rx; const fq* mem_ry; };
 
-// Round 5: the ops forest alone, the mem circuits' roots without their trees (-> c->h_spark[2 * circuit], the layout of
-// spark_fetch_tops(&mem, 2)), and the mem forest alone -- built after the ops forest is proven, into the memory it frees
-int spark_build_forest_ops(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const uint8_t r_hash[32],
-                           const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32], SparkForest* ops);
-int spark_mem_roots(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, const uint8_t r_hash[32],
-                    const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32]);
-int spark_build_forest_mem(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, const uint8_t r_hash[32],
-                           const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32], const uint8_t gamma[32], SparkForest* mem);
-
-// The same for a subset of the circuits: f holds ncirc trees, ids[j] = global circuit of tree j (ops: side*6 + kind*3 + m,
-// kind 0 read / 1 write; mem: side*2 + kind, kind 0 init / 1 audit).  One proof over several GPUs: a rank's own circuits.
-int spark_build_forest_sub(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const fq* mem_rx, const fq* mem_ry,
-                           const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                           const uint8_t gamma[32], SparkForest* f, const int* ids, bool is_mem);
+// Layers::build_hash_layer (sparse_mlpoly.rs:547-622) for both sides, written as level 0 of a forest, then every upper level.
+// All circuits: ops = [row read A,B,C | row write A,B,C | col read A,B,C | col write A,B,C] (12 trees of N/step leaves),
+// mem = [row init, row audit, col init, col audit] (4 trees of M/step leaves); split by whole circuits: the lv.ncirc trees
+// of lv.ids.  f's n and ncirc must say the same.  One launch group.
+int spark_build_forest(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const SparkLeaves& lv, const SparkInputs& in,
+                       SparkForest* f, bool is_mem);
+// the ops and the mem forest of all circuits as ONE launch group
+int spark_build_forests(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const SparkLeaves& lv, const SparkInputs& in,
+                        SparkForest* ops, SparkForest* mem);
+// Round 5: the mem circuits' roots without their trees (-> c->h_spark[2 * circuit], the layout of spark_fetch_tops(&mem, 2));
+// the mem forest itself is then built after the ops forest is proven, into the memory it frees
+int spark_mem_roots(vpin_ctx* c, const vpin_spark_decomm* d, const HashParams& hp, const fq* mem_rx, const fq* mem_ry);
 
 // the last `cnt` entries of every tree (the levels of <= cnt/2 entries), to ctx->h_spark
 // [tree][cnt]; synchronises
@@ -129,11 +141,9 @@ int spark_collect(vpin_ctx* c, const SparkForest* f, int level, const vpin_spark
                   const fq* scratch, bool with_dotp, bool folded);
 
 // DotProductCircuit::evaluate (product_tree.rs:87-91) of the six halves: h_spark[3*k] = sum_i L[i]*R[i]*W[i]
-// over the N/2 entries of half k; synchronises
+// over the N/2 entries of half k, from the derefs slices (6 x N) and the val slices (3 x N); synchronises
 // halves / nh: a subset of the halves (results at h_spark[3*i] in that order); nullptr / 6 = all
-int spark_triple_sums(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_derefs, const int* halves = nullptr, int nh = 6);
-// the same over explicit arrays: derefs slices (6 x N) and val slices (3 x N)
-int spark_triple_sums_raw(vpin_ctx* c, const fq* comb_derefs, const fq* vals, size_t N, const int* halves = nullptr, int nh = 6);
+int spark_triple_sums(vpin_ctx* c, const fq* comb_derefs, const fq* vals, size_t N, const int* halves = nullptr, int nh = 6);
 
 // Persistent tail (spark.hip): rounds j0..k-1 of forest level `level` (h = 2^k entries per half) in ONE launch, one workgroup per
 // circuit (+ the six dot-product halves when vals != nullptr), leading-coefficient form.  The host keeps the transcript:
@@ -157,14 +167,7 @@ int spark_wait(vpin_ctx* c);  // stream sync
 // r0 / step: only the entries r0, r0 + step, .. of every slice, against eq[0 .. len/step) (split by residue class)
 int spark_slice_evals(vpin_ctx* c, const fq* table, size_t len, int nslices, const fq* eq, size_t r0 = 0, size_t step = 1);
 
-// ---- split by residue class (spark.hip): the local views of rank r0 of `step` ----
-// comb_loc: 6 x N/step (the derefs slices at the entries r0 + k*step); comb_rows: nrows_loc x R (rows r0, r0 + step, .. of the
-// derefs polynomial's commitment matrix, dense)
-int spark_gather_derefs_strided(vpin_ctx* c, const vpin_spark_decomm* d, const fq* mem_rx, const fq* mem_ry, size_t r0, size_t step,
-                                fq* comb_loc, fq* comb_rows, size_t R, size_t nrows_loc);
+// split by residue class: dst[k] = src[r0 + k*step], k < nloc (the local view of a table no kernel above produces)
 int spark_take_strided(vpin_ctx* c, const fq* src, size_t nloc, size_t r0, size_t step, fq* dst);
-int spark_build_forests_strided(vpin_ctx* c, const vpin_spark_decomm* d, const fq* comb_loc, const fq* mem_rx, const fq* mem_ry,
-                                const uint8_t r_hash[32], const uint8_t r_hash_sqr[32], const uint8_t r_hash_sqr_boost[32],
-                                const uint8_t gamma[32], SparkForest* ops, SparkForest* mem, size_t r0, size_t step);
 
 }  // namespace vpin
