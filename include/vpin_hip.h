@@ -798,6 +798,18 @@ int vpin_e2_mul256(vpin_ctx* ctx, const uint8_t* scalars_le32, const uint8_t* px
  * for all cnt elements */
 int vpin_e2_encrypt(vpin_ctx* ctx, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const int64_t* msgs, const uint8_t* r_le32,
                     size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+/* (ABI 7) vpin_e2_encrypt with one public key per element and no table of any H: c1[i] = r_i * G, c2[i] = msg_i * G + r_i *
+ * H[key_of[i]].  hx, hy: n_pub public keys, canonical little-endian, n_pub x 32 bytes each.  r * G and msg * G come from G's
+ * table as in vpin_e2_encrypt; r * H is a double-and-add over the key's affine coordinates, one lane per element, a launch of
+ * its own in the same chain.  The results are canonical, so they are byte for byte those of vpin_e2_encrypt under a table of
+ * the same H.  For many elements under few keys a table per key is faster; this form is for a server that
+ * encrypts a few hundred values under each of many clients' keys.
+ * VPIN_EINVAL, each with its rule in vpin_last_error(): a null argument, cnt = 0, n_pub = 0, a key_of[i] >= n_pub (the first
+ * such i is named), a public key that is the identity, has a coordinate >= q or is off the curve (the key's index is named),
+ * and, as in vpin_e2_encrypt, r_i = 0, r_i >= n, |msg_i| >= 2^62 */
+int vpin_e2_encrypt_keyed(vpin_ctx* ctx, const vpin_e2_base* baseG, const uint8_t* hx, const uint8_t* hy, size_t n_pub, const uint32_t* key_of,
+                          const int64_t* msgs, const uint8_t* r_le32, size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x,
+                          uint8_t* c2y, uint8_t* c2inf);
 /* the baby steps j * G, 0 <= j < nb, device-resident: 32 bytes of x and a parity byte per entry and an open-addressing index
  * of 2^ceil(log2(2 nb)) 64-bit slots (49 to 65 bytes per entry in all; 2^24 entries: 0.8 GB).  2 <= nb <= 2^28 */
 typedef struct vpin_e2_dlog vpin_e2_dlog;
@@ -1028,6 +1040,17 @@ int vpin_net_infer_batch(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t B, const
                          const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
                          const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn,
                          void* user, vpin_net_trace** out);
+/* (ABI 7) vpin_net_infer_batch over the images of several clients, each under its own key: n_pub public keys (hx, hy: canonical
+ * little-endian, n_pub x 32 bytes each) and per image the index of its client's, key_of_image[B].  No table of any H: the biases
+ * of all images are still ONE encryption, vpin_e2_encrypt_keyed with image b's values under key key_of_image[b].  Everything else
+ * is vpin_net_infer_batch: layers, keys, bias r, the trace and all its accessors.  The round callback sees the whole batch,
+ * image-major; who decrypts which images is the caller's business.  With n_pub = 1 the run is byte for byte vpin_net_infer_batch
+ * under a table of that key.  VPIN_EINVAL in addition: hx, hy or key_of_image NULL, n_pub = 0, a key_of_image[b] >= n_pub (b is
+ * named), and, from the first layer with a bias, a public key that vpin_e2_encrypt_keyed refuses */
+int vpin_net_infer_multi(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                         const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const uint8_t* hx,
+                         const uint8_t* hy, size_t n_pub, const uint32_t* key_of_image, const uint8_t* keys32, size_t n_keys,
+                         const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out);
 /* the images of a trace (1 for vpin_net_infer's) */
 int vpin_net_trace_images(const vpin_net_trace* t, size_t* B);
 /* image b's label, borrowed until vpin_net_trace_free: byte for byte what vpin_net_trace_label gives for image b run alone
@@ -1151,6 +1174,59 @@ int vpin_net_serve(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, const u
  * from its caller */
 int vpin_net_serve_batch(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, size_t max_batch, const uint8_t* keys32, size_t n_keys,
                          const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_trace** out);
+
+/* ---- several clients in one batched inference (ABI 7) -------------------------------------------------------------------------
+ * A service has many clients with an image or two each, every one with its own key.  vpin_net_serve_multi runs ONE inference
+ * (vpin_net_infer_multi) over the images of all the wires it is given, every round one exchange with all of them, and drops a
+ * client that disappears or misbehaves on the wire while the others finish.  No frame changes and the client's side needs nothing
+ * new (vpin_net_client_run): each wire sees exactly the frames vpin_net_serve_batch would send it alone.
+ * A vpin_net_server holds what outlives a call: the checked configuration (borrowed: it and what it points to live until
+ * vpin_net_server_free) and the table of G, built ONCE; no table of any client's H is ever built (vpin_e2_encrypt_keyed).
+ * vpin_net_server_create: VPIN_EINVAL as vpin_net_serve_batch for the configuration and max_batch.  vpin_net_server_stats:
+ * out = {calls, clients admitted, clients served to DONE, images run, base tables built}.  One thread drives a server.
+ *
+ * vpin_net_serve_multi, n_keys = max_batch * k and n_bias_r = max_batch * r as for vpin_net_serve_batch:
+ *   admission   in wire order: HELLO, then INPUT, B_i = cnt / (C H W).  A wire is answered with ERROR where it can be and is not
+ *               admitted when HELLO or INPUT is another type, its key is the identity or does not unpack, its cnt is 0 or no
+ *               multiple of C H W, its B_i does not fit into what is left of max_batch (what the wires before it asked for,
+ *               whether or not their points then unpack), or one of its input points does not unpack.  The keys and inputs of
+ *               all wires are unpacked by ONE launch.  Admitted clients take image slots in wire order: first_image = the sum of
+ *               B_j over the clients admitted before; slot s uses the keys [s k, (s + 1) k) and the bias r [s r, (s + 1) r), so
+ *               which keys a client is served with depends only on who was admitted before it.  Nobody admitted: VPIN_ESHAPE,
+ *               "vpin_net_serve_multi: no client was admitted", *out = NULL, nothing runs
+ *   a round     one pack launch over the batch's c1 | c2; every live client gets ROUND with cnt = B_i * n and its slice, c1 part
+ *               then c2 part; all ROUNDs are sent first, then the REPLYs are read in wire order (the clients decrypt at the same
+ *               time); one unpack launch over all replies
+ *   a drop      a client whose stream fails or times out, who sends ERROR, a REPLY for another round or with another cnt, or a
+ *               REPLY with a point that does not unpack is dropped from that round on: ERROR to it best effort and nothing more (a
+ *               silent client costs its wire's timeout_ms once).  Its images stay in the batch: for that round and every later
+ *               one their reply is the ciphertexts the server sent, so the layer calls keep their shape and the other images are
+ *               untouched; its part of the trace means nothing.  The last live client gone: VPIN_ECOMM, *out = NULL
+ *   the end     DONE to every live client.  VPIN_OK when at least one client got DONE
+ *   the server's own failure (a layer's refusal, VPIN_EHIP, VPIN_ENOMEM): ERROR to every live client, the code into their
+ *               status, and returned
+ * status[i], for wire i: code VPIN_OK and stage VPIN_NET_STAGE_DONE for a client served to DONE; otherwise the code, the text and
+ * the stage it left at: VPIN_NET_STAGE_ADMISSION, the round's number, or VPIN_NET_STAGE_SERVER for the server's own failure.
+ * first_image and n_images are its slots (0, 0 when it was not admitted).
+ * NOT isolated: a client whose well-formed ciphertexts drive a layer into a refusal (an accumulator that is the identity, an s_k
+ * that does not fit) still fails the whole batch; that needs isolation per image inside the layers.
+ * VPIN_EINVAL before anything is read: a null argument, n_wires = 0 or > max_batch, the same wire twice, n_keys != max_batch * k,
+ * n_bias_r != max_batch * r.  All waits are the wires' own timeout_ms; admission reads the wires one after another. */
+typedef struct vpin_net_server vpin_net_server;
+int vpin_net_server_create(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t max_batch, vpin_net_server** out);
+void vpin_net_server_free(vpin_net_server* s);
+int vpin_net_server_stats(const vpin_net_server* s, uint64_t out[5]);
+#define VPIN_NET_STAGE_DONE (-1)
+#define VPIN_NET_STAGE_ADMISSION (-2)
+#define VPIN_NET_STAGE_SERVER (-3)
+typedef struct vpin_net_peer_status {
+  int code;
+  int stage;
+  uint32_t first_image, n_images;
+  char text[256];
+} vpin_net_peer_status;
+int vpin_net_serve_multi(vpin_net_server* s, vpin_wire* const* wires, size_t n_wires, const uint8_t* keys32, size_t n_keys,
+                         const uint8_t* bias_r_le32, size_t n_bias_r, vpin_net_peer_status* status, vpin_net_trace** out);
 
 /* The client's endpoint: encrypts the image (n_input ints under n_input r, as vpin_e2_encrypt) under its own tables, sends HELLO
  * and INPUT, then serves frames.  A client that performs whatever round the server asks for is a decryption oracle, so the

@@ -1,6 +1,6 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
 the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
-[--batch 1,2,4,..]
+[--batch 1,2,4,..] [--clients 1,2,4,..]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
@@ -18,7 +18,15 @@ clock: the round as the driver sees it, the client's work and the wire included)
 b % 8 rows and b // 8 columns, under keys and r of its own), every B warmed as a shape of its own by one run and then timed over
 R = 11 warm runs by default: ms per inference and per image, and per layer and per round the median (minimum .. maximum).  The
 first run of every B is checked against the plaintext model, image by image.  With --wire every B also runs between two endpoints
-over a socketpair (vpin_net_serve_batch, vpin_net_client_run), the two modes alternating.  No proofs in this mode."""
+over a socketpair (vpin_net_serve_batch, vpin_net_client_run), the two modes alternating.  No proofs in this mode.
+--clients 1,2,4,..: per K, K clients of one image each, every one with a key and a context of its own, as threads of this one
+process over socketpairs (at most 8 clients: 9 contexts), three ways that alternate run by run: (a) ONE inference over all of them
+(vpin_net_serve_multi on a vpin_net_server that keeps its table of G), (b) one client with K images through vpin_net_serve_batch,
+(c) K times vpin_net_serve, one connection after the other.  Per way the ms per image of the whole exchange (from the first
+endpoint's start to the last one's return: the connection's set-up in, the clients' own tables and the server object out) and of
+every layer and every round (the server's host clock): median (minimum .. maximum) of R = 11 warm runs by default.  Every client's
+values of the first run are checked against the plaintext model.  Then two side timings: vpin_e2_base_create of G and of an H,
+and vpin_e2_encrypt_keyed against vpin_e2_encrypt with a ready table at cnt = 236, 944 and 7552.  No proofs in this mode."""
 import os
 import socket
 import statistics
@@ -45,7 +53,8 @@ def opt(name, default):
 VERSION = sys.argv[1]
 WIRE = "--wire" in sys.argv
 BATCH = [int(b) for b in sys.argv[sys.argv.index("--batch") + 1].split(",")] if "--batch" in sys.argv else None
-REPS, NB_LOG = opt("--reps", 11 if WIRE or BATCH else 5), opt("--nb", 24)
+CLIENTS = [int(b) for b in sys.argv[sys.argv.index("--clients") + 1].split(",")] if "--clients" in sys.argv else None
+REPS, NB_LOG = opt("--reps", 11 if WIRE or BATCH or CLIENTS else 5), opt("--nb", 24)
 PROOFS = "--no-proofs" not in sys.argv
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
@@ -76,9 +85,9 @@ def main():
     ctx = vpin_amd.Context(0)
     counts, giants = cfg.counts(), cfg.max_giants()
     assert counts == dict(want, rounds=len(giants))
-    if BATCH:
+    if BATCH or CLIENTS:
         plain = TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
-        batch_mode(ctx, cfg, model, counts, giants, image, plain)
+        (clients_mode if CLIENTS else batch_mode)(ctx, cfg, model, counts, giants, image, plain)
         ctx.close()
         return
     keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
@@ -318,6 +327,174 @@ def batch_mode(ctx, cfg, model, counts, giants, image, plain):
         print("B = %-4d %10.3f %10.3f %10.3f" % (B, w / B, ls / B, rs / B) + ("%10.3f" % (ww / B) if WIRE else ""))
     if WIRE:
         ctx2.close()
+
+
+def threads(fns):
+    """every fn in a thread of its own -> their results in order; the first exception is raised here"""
+    out = [None] * len(fns)
+
+    def body(i):
+        try:
+            out[i] = fns[i]()
+        except BaseException as e:  # noqa: BLE001
+            out[i] = e
+
+    ts = [threading.Thread(target=body, args=(i,)) for i in range(len(fns))]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    for o in out:
+        if isinstance(o, BaseException):
+            raise o
+    return out
+
+
+def clients_mode(ctx, cfg, model, counts, giants, image, plain):
+    from vpin_amd import elgamal as E
+    from vpin_amd import wire as W
+    top = max(CLIENTS)
+    assert top <= 8, "at most 8 clients: a context each beside the server's"
+    cctx = [vpin_amd.Context(0) for _ in range(top)]
+    sks = [(SK + 977 * k) % EL.ORDER for k in range(top)]
+    n, nr, size = len(cfg.layers), len(giants), image.size
+    at = [i for i, l in enumerate(cfg.layers) if l.has_round]
+    k_keys, r_bias, r_client = counts["prf_keys"], counts["bias_r"], counts["encryptions"] - size
+    images = [np.roll(image, (b % 8, b // 8), axis=(0, 1)) for b in range(top)]
+    expect = [plain(model, im) for im in images]
+    bound = max(g << NB_LOG for g in giants)
+    assert all(abs(v) < bound for vs, _ in expect for r in vs for v in r), "an image leaves the client's range"
+    keys = [[NM.net_key(k_keys * b + i) for i in range(k_keys)] for b in range(top)]
+    image_rs = [EL.splitmix_scalars(SEEDS["image_r"] + 0x1000 * b, size) for b in range(top)]
+    bias_rs = [EL.splitmix_scalars(SEEDS["bias_r"] + 0x1000 * b, r_bias) for b in range(top)]
+    client_rs = [EL.splitmix_scalars(SEEDS["client_r"] + 0x1000 * b, r_client) for b in range(top)]
+    stage = [c for c, l in zip(counts["per_round"], [cfg.layers[i] for i in at]) if l.reencrypt]
+    sched1 = VN.schedule(cfg)
+    med = statistics.median
+    rng = lambda xs, d: "%8.2f (%7.2f .. %7.2f)" % (med(xs) / d, min(xs) / d, max(xs) / d)
+
+    class Conn:
+        def __init__(self):
+            self.a, self.b = socket.socketpair()
+            self.ws, self.wc = W.Wire.from_fds(self.a.fileno(), self.a.fileno(), 600000), W.Wire.from_fds(self.b.fileno(), self.b.fileno(), 600000)
+
+        def close(self):
+            self.ws.free(); self.wc.free()
+            self.a.close(); self.b.close()
+
+    def checked(values, who):  # per client k its rounds
+        for k, vals in enumerate(values):
+            for r in range(nr):
+                for i in range(2):
+                    assert [int(a) for a in vals[r][i]] == expect[who[k]][i][r], "client %d round %d" % (who[k], r)
+
+    summary = []
+    for K in CLIENTS:
+        flat = lambda per: [v for one in per[:K] for v in one]
+        queue, pos = [], 0
+        for c in stage:  # one client with K images: stage after stage the r of all images
+            for b in range(K):
+                queue += client_rs[b][pos:pos + c]
+            pos += c
+        schedK = VN.schedule(cfg, batch=K)
+        server = VN.Server(ctx, cfg, K)
+        ways = {w: dict(whole=[], layers=[], rounds=[]) for w in "abc"}
+        for rep in range(REPS + 1):
+            # (a) one inference over K clients
+            cl = [VN.Client(cctx[k], sks[k], 1 << NB_LOG, giants, client_rs[k]) for k in range(K)]
+            conns = [Conn() for _ in range(K)]
+            t0 = time.perf_counter()
+            res = threads([lambda: (server.serve([c.ws for c in conns], flat(keys), flat(bias_rs)), VN.timings(n))] +
+                          [lambda k=k: cl[k].run(conns[k].wc, images[k].reshape(-1), image_rs[k], sched1) for k in range(K)])
+            ta = (time.perf_counter() - t0) * 1e3
+            (trace, statuses), tma = res[0]
+            assert all(s["code"] == 0 and s["stage"] == VN.STAGE_DONE for s in statuses) and trace.images == K
+            if rep == 0:
+                checked([r[1] for r in res[1:]], list(range(K)))
+            trace.free()
+            for c in cl + conns:
+                c.free() if hasattr(c, "free") else c.close()
+            # (b) one client with K images
+            client = VN.Client(cctx[0], sks[0], 1 << NB_LOG, giants, queue)
+            conn = Conn()
+            t0 = time.perf_counter()
+            res = threads([lambda: (VN.serve(ctx, cfg, conn.ws, flat(keys), flat(bias_rs), max_batch=None if K == 1 else K), VN.timings(n)),
+                           lambda: client.run(conn.wc, np.concatenate([im.reshape(-1) for im in images[:K]]), flat(image_rs), schedK)])
+            tb = (time.perf_counter() - t0) * 1e3
+            res[0][0].free()
+            tmb = res[0][1]
+            client.free()
+            conn.close()
+            # (c) K connections, one after the other
+            cl = [VN.Client(cctx[k], sks[k], 1 << NB_LOG, giants, client_rs[k]) for k in range(K)]
+            conns = [Conn() for _ in range(K)]
+            tmc = dict(layers=[0.0] * n, rounds=[0.0] * n)
+            t0 = time.perf_counter()
+            for k in range(K):
+                res = threads([lambda: (VN.serve(ctx, cfg, conns[k].ws, keys[k], bias_rs[k]), VN.timings(n)),
+                               lambda: cl[k].run(conns[k].wc, images[k].reshape(-1), image_rs[k], sched1)])
+                res[0][0].free()
+                for key in ("layers", "rounds"):
+                    tmc[key] = [x + y for x, y in zip(tmc[key], res[0][1][key])]
+                if rep == 0:
+                    checked([res[1][1]], [k])
+            tc = (time.perf_counter() - t0) * 1e3
+            for c in cl + conns:
+                c.free() if hasattr(c, "free") else c.close()
+            if rep:
+                for w, whole, tm in (("a", ta, tma), ("b", tb, tmb), ("c", tc, tmc)):
+                    ways[w]["whole"].append(whole)
+                    ways[w]["layers"].append(tm["layers"])
+                    ways[w]["rounds"].append([tm["rounds"][i] for i in at])
+        assert server.stats()["base_tables_built"] == 1 and server.stats()["calls"] == REPS + 1
+        server.free()
+        print("K = %d clients of one image each; ms PER IMAGE, warm, median (min .. max) over %d runs, the three ways alternating" % (K, REPS))
+        print("%-34s %-30s %-30s %-30s" % ("", "(a) vpin_net_serve_multi", "(b) one client, serve_batch", "(c) K x vpin_net_serve"))
+        rnd = 0
+        for i, l in enumerate(cfg.layers):
+            print("%-34s %-30s %-30s %-30s" % (("layer %d (%s)" % (i, KINDS[l.kind]),) + tuple(rng([x[i] for x in ways[w]["layers"]], K) for w in "abc")))
+            if l.has_round:
+                print("%-34s %-30s %-30s %-30s" % (("round %d (%d values per image)" % (rnd, sched1[rnd][2]),) +
+                                                   tuple(rng([x[rnd] for x in ways[w]["rounds"]], K) for w in "abc")))
+                rnd += 1
+        print("%-34s %-30s %-30s %-30s" % (("the whole exchange",) + tuple(rng(ways[w]["whole"], K) for w in "abc")))
+        summary.append((K,) + tuple(med(ways[w]["whole"]) / K for w in "abc"))
+    print("ms per image (medians) of the whole exchange: (a), (b), (c)")
+    for row in summary:
+        print("K = %-3d %10.3f %10.3f %10.3f" % row)
+    # the side timings: the table builds, and the keyed encryption against the table form
+    base_g = E.BaseTable(ctx)
+    H = E.keygen(base_g, SK)
+    pubs = [E.keygen(base_g, sk) for sk in sks]
+    tg, th = [], []
+    for rep in range(REPS + 1):
+        for xs, point in ((tg, None), (th, H)):
+            t0 = time.perf_counter()
+            b = E.BaseTable(ctx, point)
+            xs.append((time.perf_counter() - t0) * 1e3)
+            b.free()
+    print("vpin_e2_base_create, ms: of G %s, of an H %s" % (rng(tg[1:], 1), rng(th[1:], 1)))
+    base_h = E.BaseTable(ctx, H)
+    for cnt in (236, 944, 7552):
+        msgs = [int(v) % (1 << 30) - (1 << 29) for v in EL.splitmix_scalars(0xCB1, cnt)]
+        rs = EL.splitmix_scalars(0xCB2, cnt)
+        key_of = [i * len(pubs) // cnt for i in range(cnt)]  # runs of elements under one key, as the images of a batch
+        tt, tk, t1 = [], [], []
+        for rep in range(REPS + 1):
+            for xs, fn in ((tt, lambda: E.encrypt(base_g, base_h, msgs, rs)), (tk, lambda: E.encrypt_keyed(base_g, pubs, key_of, msgs, rs)),
+                           (t1, lambda: E.encrypt_keyed(base_g, [H], [0] * cnt, msgs, rs))):
+                t0 = time.perf_counter()
+                out = fn()
+                xs.append((time.perf_counter() - t0) * 1e3)
+            if rep == 0:
+                ref = E.encrypt(base_g, base_h, msgs, rs)
+                assert all(np.array_equal(u, v) for a, b in zip(out, ref) for u, v in zip(a, b)), "keyed under H is the table form"
+        print("cnt = %-5d ms (with the Python marshalling): vpin_e2_encrypt with a ready table %s, vpin_e2_encrypt_keyed under %d keys %s, under one key %s" %
+              (cnt, rng(tt[1:], 1), len(pubs), rng(tk[1:], 1), rng(t1[1:], 1)))
+    base_h.free()
+    base_g.free()
+    for c in cctx:
+        c.close()
 
 
 if __name__ == "__main__":

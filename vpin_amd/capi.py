@@ -80,6 +80,11 @@ class WireRoundSpec(C.Structure):
     _fields_ = [("flags", C.c_int), ("shift_bits", C.c_int), ("cnt", C.c_size_t)]
 
 
+class NetPeerStatus(C.Structure):
+    """vpin_net_peer_status of include/vpin_hip.h"""
+    _fields_ = [("code", C.c_int), ("stage", C.c_int), ("first_image", C.c_uint32), ("n_images", C.c_uint32), ("text", C.c_char * 256)]
+
+
 # vpin_lenet_round_fn
 LENET_ROUND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, *([C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 6))
 
@@ -230,6 +235,7 @@ def lib():
     L.vpin_e2_base_mul.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_mul256.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_encrypt.argtypes = [vp, vp, vp, vp, vp, C.c_size_t] + [vp] * 6
+    L.vpin_e2_encrypt_keyed.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t] + [vp] * 6
     L.vpin_e2_dlog_create.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.vpin_e2_dlog_free.argtypes = [vp]
     L.vpin_e2_dlog_free.restype = None
@@ -259,6 +265,8 @@ def lib():
     L.vpin_net_trace_result.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_net_last_timings.argtypes = [C.POINTER(C.c_double), C.c_size_t]
     L.vpin_net_infer_batch.argtypes = [vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.vpin_net_infer_multi.argtypes = ([vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp] +
+                                       [vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)])
     L.vpin_net_trace_images.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.vpin_net_trace_image_label.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_trace_image_instances.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
@@ -283,6 +291,11 @@ def lib():
     L.vpin_wire_bind_ctx.argtypes = [vp, vp]
     L.vpin_net_serve.argtypes = [vp, C.POINTER(NetCfg), vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_serve_batch.argtypes = [vp, C.POINTER(NetCfg), vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_server_create.argtypes = [vp, C.POINTER(NetCfg), C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_server_free.argtypes = [vp]
+    L.vpin_net_server_free.restype = None
+    L.vpin_net_server_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vpin_net_serve_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(NetPeerStatus), C.POINTER(vp)]
     L.vpin_net_client_run.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(WireRoundSpec), C.c_size_t]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
@@ -1502,6 +1515,22 @@ class Context:
                np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _chk(lib().vpin_e2_encrypt(self.h, base_g, base_h, p(m), p(r), n, *[p(a) for a in out]), "vpin_e2_encrypt")
+        return tuple(out[:3]), tuple(out[3:])
+
+    def e2_encrypt_keyed(self, base_g, pubs, key_of, msgs, rs):
+        """e2_encrypt with a public key per element and no table of any H: pubs = [(x, y)] as Python ints, element i under
+        pubs[key_of[i]] (vpin_e2_encrypt_keyed)"""
+        m = np.ascontiguousarray(np.array([int(v) for v in msgs], dtype=np.int64))
+        r = self._u256s(rs)
+        ko = np.ascontiguousarray(np.array([int(k) for k in key_of], dtype=np.uint32))
+        hx, hy = self._u256s([x for x, _ in pubs]), self._u256s([y for _, y in pubs])
+        n = m.shape[0]
+        assert len(rs) == n and ko.shape[0] == n
+        out = [np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8),
+               np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_encrypt_keyed(self.h, base_g, p(hx), p(hy), len(pubs), p(ko), p(m), p(r), n, *[p(a) for a in out]),
+             "vpin_e2_encrypt_keyed")
         return tuple(out[:3]), tuple(out[3:])
 
     def e2_dlog_create(self, nb):

@@ -4,6 +4,7 @@
 // with the baby-step table built on the device instead of read from a pickle.
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/vpin_hip.h"
@@ -43,6 +44,19 @@ int check_scalars(const uint8_t* s, size_t cnt, bool nonzero) {
 // max_giant * nb <= 2^62, so that every value of the walk fits an int64
 bool walk_fits(uint64_t max_giant, uint64_t nb) {
   return (unsigned __int128)max_giant * nb <= ((unsigned __int128)1 << 62);
+}
+
+// the messages as the device takes them: the magnitude as a 32-byte scalar and a sign byte.  false when one is 2^62 or more
+bool split_messages(const int64_t* msgs, size_t cnt, std::vector<uint8_t>* m, std::vector<uint8_t>* neg) {
+  m->assign(cnt * 32, 0);
+  neg->assign(cnt, 0);
+  for (size_t i = 0; i < cnt; i++) {
+    const uint64_t mag = msgs[i] < 0 ? 0 - (uint64_t)msgs[i] : (uint64_t)msgs[i];
+    if (mag >= ((uint64_t)1 << 62)) return false;
+    memcpy(&(*m)[32 * i], &mag, 8);
+    (*neg)[i] = msgs[i] < 0 ? 1 : 0;
+  }
+  return true;
 }
 
 }  // namespace
@@ -88,14 +102,42 @@ int vpin_e2_encrypt(vpin_ctx* c, const vpin_e2_base* baseG, const vpin_e2_base* 
     case 1: return fail(VPIN_EINVAL, "vpin_e2_encrypt: a randomness r is not below the group order");
     case 2: return fail(VPIN_EINVAL, "vpin_e2_encrypt: a randomness r is zero");
   }
-  std::vector<uint8_t> m(cnt * 32, 0), neg(cnt, 0);
-  for (size_t i = 0; i < cnt; i++) {
-    const uint64_t mag = msgs[i] < 0 ? 0 - (uint64_t)msgs[i] : (uint64_t)msgs[i];
-    if (mag >= ((uint64_t)1 << 62)) return fail(VPIN_EINVAL, "vpin_e2_encrypt: a message is not in -(2^62) < msg < 2^62");
-    memcpy(&m[32 * i], &mag, 8);
-    neg[i] = msgs[i] < 0 ? 1 : 0;
-  }
+  std::vector<uint8_t> m, neg;
+  if (!split_messages(msgs, cnt, &m, &neg)) return fail(VPIN_EINVAL, "vpin_e2_encrypt: a message is not in -(2^62) < msg < 2^62");
   return cl::encrypt(c, baseG, baseH, r_le32, m.data(), neg.data(), cnt, c1x, c1y, c1inf, c2x, c2y, c2inf);
+}
+
+int vpin_e2_encrypt_keyed(vpin_ctx* c, const vpin_e2_base* baseG, const uint8_t* hx, const uint8_t* hy, size_t n_pub, const uint32_t* key_of,
+                          const int64_t* msgs, const uint8_t* r_le32, size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x,
+                          uint8_t* c2y, uint8_t* c2inf) {
+  if (!c || !baseG || !hx || !hy || !key_of || !msgs || !r_le32 || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf)
+    return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: null argument");
+  if (cnt == 0 || cnt >= ((size_t)1 << 30)) return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: cnt must be in 1 .. 2^30 - 1");
+  if (n_pub == 0 || n_pub >= ((size_t)1 << 30)) return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: n_pub must be in 1 .. 2^30 - 1");
+  char why[160];
+  for (size_t i = 0; i < cnt; i++)
+    if (key_of[i] >= n_pub) {
+      snprintf(why, sizeof why, "vpin_e2_encrypt_keyed: key_of[%zu] = %u is not below n_pub = %zu", i, (unsigned)key_of[i], n_pub);
+      return fail(VPIN_EINVAL, why);
+    }
+  for (size_t k = 0; k < n_pub; k++)
+    if (is_zero32(hx + 32 * k) && is_zero32(hy + 32 * k)) {
+      snprintf(why, sizeof why, "vpin_e2_encrypt_keyed: public key %zu is the identity", k);
+      return fail(VPIN_EINVAL, why);
+    }
+  switch (check_scalars(r_le32, cnt, true)) {
+    case 1: return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: a randomness r is not below the group order");
+    case 2: return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: a randomness r is zero");
+  }
+  std::vector<uint8_t> m, neg;
+  if (!split_messages(msgs, cnt, &m, &neg)) return fail(VPIN_EINVAL, "vpin_e2_encrypt_keyed: a message is not in -(2^62) < msg < 2^62");
+  size_t bad_key = n_pub;
+  const int rc = cl::encrypt_keyed(c, baseG, hx, hy, n_pub, key_of, r_le32, m.data(), neg.data(), cnt, &bad_key, c1x, c1y, c1inf, c2x, c2y, c2inf);
+  if (rc == VPIN_EINVAL && bad_key < n_pub) {  // "vpin_e2_encrypt_keyed: <rule>" with the key's index behind it
+    const std::string text = std::string(vpin_last_error()) + " (public key " + std::to_string(bad_key) + ")";
+    return fail(rc, text.c_str());
+  }
+  return rc;
 }
 
 int vpin_e2_dlog_create(vpin_ctx* c, uint64_t nb, vpin_e2_dlog** out) {

@@ -39,6 +39,12 @@ int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, si
 // c1[i] = r_i * G, c2[i] = (+-)m_i * G + r_i * H with m_i = |msg_i| as a 32-byte scalar and neg[i] = 1 for a negative message
 int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg,
             size_t cnt, uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+// encrypt with one public key per element and no table of any H: c2[i] = (+-)m_i * G + r_i * (hx, hy)[key_of[i]], the n_pub keys
+// canonical little-endian and none the identity, every key_of[i] < n_pub (both checked by the caller).  The keys go through
+// E2Points::load; when it rejects one, *bad_key is the first such key's index (n_pub otherwise) and the text that key's own rule
+int encrypt_keyed(vpin_ctx* c, const vpin_e2_base* g, const uint8_t* hx, const uint8_t* hy, size_t n_pub, const uint32_t* key_of,
+                  const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg, size_t cnt, size_t* bad_key, uint8_t* c1x, uint8_t* c1y,
+                  uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
 // out[i] = s_i * P_i, or s_0 * P_i for every i when one_scalar
 int mul256(vpin_ctx* c, const uint8_t* scalars_le32, bool one_scalar, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t cnt,
            uint8_t* ox, uint8_t* oy, uint8_t* oinf);

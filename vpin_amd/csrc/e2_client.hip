@@ -6,6 +6,7 @@
 //   e2_base_mul_kernel     s_i * B, one lane per scalar: a mixed addition per non-zero digit, no doubling; optional negation
 //   e2_add_pairs_kernel    A_i + B_i, complete (the last addition of a ciphertext's c2)
 //   e2_mul256_kernel       s_i * P_i (or one s for all): double-and-add over eight shifted words
+//   e2_mul_keyed_kernel    s_i * H[key_of[i]] over a few resident points H: the r * H of an encryption under a key per element
 //   e2_sub_kernel          C_i - T_i, complete (M = c2 - sk * c1)
 //   e2_dlog_steps_kernel   baby steps: lane l starts at (j0 + l * chunk) * G from G's window table and steps by + G
 //   e2_dlog_insert_kernel  parity of y and the open-addressing index keyed on x (64-bit compare-and-swap)
@@ -24,6 +25,7 @@
 
 #include <cstring>
 #include <new>
+#include <vector>
 
 namespace vpin {
 
@@ -74,6 +76,16 @@ __global__ __launch_bounds__(kE2Block) void e2_mul256_kernel(const fq* __restric
   e2_jac acc = e2_identity();
   if (!inf[i]) acc = e2_mul_affine256(fq_load(X + i), fq_load(Y + i), e2_scalar256_load(s + stride * i), a);
   e2_store(out + i, acc);
+}
+
+// out_i = s_i * (HX, HY)[key_of[i]]: every key_of[i] indexes a loaded point that is not the identity (checked by the host)
+__global__ __launch_bounds__(kE2Block) void e2_mul_keyed_kernel(const fq* __restrict__ HX, const fq* __restrict__ HY,
+                                                                const uint32_t* __restrict__ key_of, const uint32_t* __restrict__ s, size_t n, fq a,
+                                                                e2_jac* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t k = key_of[i];
+  e2_store(out + i, e2_mul_affine256(fq_load(HX + k), fq_load(HY + k), e2_scalar256_load(s + 8 * i), a));
 }
 
 // out_i = (X_i, Y_i) - T_i
@@ -365,14 +377,16 @@ int base_mul(vpin_ctx* c, const vpin_e2_base* b, const uint8_t* scalars_le32, si
 }
 
 // The device side of an encryption over cnt elements whose r (cnt x 32 bytes), message magnitudes (cnt x 32 bytes) and sign bytes
-// are resident: the three fixed-base multiplications, the last addition, one normalisation of c1 | c2 and the copies of the
-// canonical bytes to the host.  Not synchronised; the buffers live until the caller has synchronised
+// are resident: the three multiplications, the last addition, one normalisation of c1 | c2 and the copies of the canonical bytes
+// to the host.  r * H comes from h's table, or, with pub, from the loaded public keys by double-and-add: element i under pub's
+// point d_key_of[i] (h is then not read).  Not synchronised; the buffers live until the caller has synchronised
 struct EncryptChain {
   DevBuf ct, rh, mg;  // ct = c1 | c2 (one normalisation for both); rh = r * H, mg = msg * G
   E2Affine aff;
   explicit EncryptChain(vpin_ctx* c) : ct(c), rh(c), mg(c), aff(c) {}
   int run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const void* d_r, const void* d_m, const void* d_neg, size_t cnt,
-          uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf);
+          uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf, const E2Points* pub = nullptr,
+          const void* d_key_of = nullptr);
 };
 
 int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg,
@@ -391,11 +405,17 @@ int encrypt(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const uin
 }
 
 int EncryptChain::run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h, const void* d_r, const void* d_m, const void* d_neg, size_t cnt,
-                      uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf) {
+                      uint8_t* c1x, uint8_t* c1y, uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf, const E2Points* pub,
+                      const void* d_key_of) {
   if (ct.alloc(2 * cnt * sizeof(e2_jac)) || rh.alloc(cnt * sizeof(e2_jac)) || mg.alloc(cnt * sizeof(e2_jac))) return VPIN_ENOMEM;
   e2_jac* c1 = (e2_jac*)ct.p;
   int rc = launch_base_mul(c, g, (const uint32_t*)d_r, nullptr, cnt, c1);
-  if (!rc) rc = launch_base_mul(c, h, (const uint32_t*)d_r, nullptr, cnt, (e2_jac*)rh.p);
+  if (!rc && !pub) rc = launch_base_mul(c, h, (const uint32_t*)d_r, nullptr, cnt, (e2_jac*)rh.p);
+  if (!rc && pub) {
+    hipLaunchKernelGGL(e2_mul_keyed_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, pub->X(), pub->Y(),
+                       (const uint32_t*)d_key_of, (const uint32_t*)d_r, cnt, e2_curve_a(), (e2_jac*)rh.p);
+    VPIN_HIP_TRY(hipGetLastError());
+  }
   if (!rc) rc = launch_base_mul(c, g, (const uint32_t*)d_m, (const uint8_t*)d_neg, cnt, (e2_jac*)mg.p);
   if (rc) return rc;
   hipLaunchKernelGGL(e2_add_pairs_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const e2_jac*)mg.p, (const e2_jac*)rh.p,
@@ -404,6 +424,35 @@ int EncryptChain::run(vpin_ctx* c, const vpin_e2_base* g, const vpin_e2_base* h,
   if ((rc = aff.normalise(c, c1, 2 * cnt))) return rc;
   if ((rc = aff.copy_out(c, 0, cnt, c1x, c1y, c1inf))) return rc;
   return aff.copy_out(c, cnt, cnt, c2x, c2y, c2inf);
+}
+
+int encrypt_keyed(vpin_ctx* c, const vpin_e2_base* g, const uint8_t* hx, const uint8_t* hy, size_t n_pub, const uint32_t* key_of,
+                  const uint8_t* r_le32, const uint8_t* m_le32, const uint8_t* neg, size_t cnt, size_t* bad_key, uint8_t* c1x, uint8_t* c1y,
+                  uint8_t* c1inf, uint8_t* c2x, uint8_t* c2y, uint8_t* c2inf) {
+  (void)hipSetDevice(c->device);
+  *bad_key = n_pub;
+  E2Points pub(c);
+  const std::vector<uint8_t> not_inf(n_pub, 0);
+  int rc = pub.load(c, hx, hy, not_inf.data(), n_pub, "vpin_e2_encrypt_keyed", "public key");
+  if (rc == VPIN_EINVAL) {
+    // which key: the rejection does not say, so on this path the keys go through the checks again one at a time; the first one
+    // refused is named, and its own rule is the text
+    for (size_t k = 0; k < n_pub && *bad_key == n_pub; k++) {
+      E2Points one(c);
+      if (one.load(c, hx + 32 * k, hy + 32 * k, not_inf.data(), 1, "vpin_e2_encrypt_keyed", "public key") == VPIN_EINVAL) *bad_key = k;
+    }
+  }
+  if (rc) return rc;
+  DevBuf r(c), m(c), ng(c), ko(c);
+  if (r.alloc(cnt * 32) || m.alloc(cnt * 32) || ng.alloc(cnt) || ko.alloc(cnt * 4)) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(m.p, m_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(ng.p, neg, cnt, hipMemcpyHostToDevice, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(ko.p, key_of, cnt * 4, hipMemcpyHostToDevice, c->stream));
+  EncryptChain e(c);
+  if ((rc = e.run(c, g, nullptr, r.p, m.p, ng.p, cnt, c1x, c1y, c1inf, c2x, c2y, c2inf, &pub, ko.p))) return rc;
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
 }
 
 // T_i = s * P_i over the loaded points, Jacobian, not synchronised

@@ -8,9 +8,11 @@
 //   e2_unpack_kernel  one lane per point: x to Montgomery form, rhs = x^3 + a x + b, y = fq_sqrt(rhs) by one fixed exponentiation
 //                     (e2_wire_dev.h), the check y^2 == rhs, y to canonical form, y or q - y by bit 255.  A lane with a bad
 //                     encoding writes its rule into `bad` and stays on the common path: the chain is the same for every lane
-// Both write one rule byte per point; the host names the first bad index (as vpin_e2_client_round names its first element).
+// Both write one rule byte per point; the host names the first bad index (as vpin_e2_client_round names its first element), or,
+// for the replies of several clients in one launch (wire::unpack_rules), finds whose point it is.
 #include "e2_wire_dev.h"
 #include "enc_conv.h"
+#include "wire.h"
 
 #include <cstdio>
 #include <vector>
@@ -112,6 +114,28 @@ int first_bad(const std::vector<uint8_t>& bad, const char* who, bool pack) {
 
 }  // namespace
 
+namespace wire {
+
+const char* unpack_rule_text(uint8_t rule) { return rule_text(rule, false); }
+
+int unpack_rules(vpin_ctx* c, const uint8_t* in32, size_t cnt, uint8_t* px, uint8_t* py, uint8_t* pinf, uint8_t* bad) {
+  (void)hipSetDevice(c->device);
+  DevBuf in(c), x(c), y(c), f(c), b(c);
+  if (in.alloc(cnt * 32) || x.alloc(cnt * 32) || y.alloc(cnt * 32) || f.alloc(cnt) || b.alloc(cnt)) return VPIN_ENOMEM;
+  VPIN_HIP_TRY(hipMemcpyAsync(in.p, in32, cnt * 32, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(e2_unpack_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)in.p, cnt, e2_curve_a(),
+                     fq_of_le32(kBBytes), (fq*)x.p, (fq*)y.p, (uint8_t*)f.p, (uint8_t*)b.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  VPIN_HIP_TRY(hipMemcpyAsync(px, x.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(py, y.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(pinf, f.p, cnt, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(bad, b.p, cnt, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return VPIN_OK;
+}
+
+}  // namespace wire
+
 }  // namespace vpin
 
 using namespace vpin;
@@ -140,19 +164,9 @@ int vpin_e2_pack(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_
 int vpin_e2_unpack(vpin_ctx* c, const uint8_t* in32, size_t cnt, uint8_t* px, uint8_t* py, uint8_t* pinf) {
   if (!c || !in32 || !px || !py || !pinf) return enc::fail(VPIN_EINVAL, "vpin_e2_unpack: null argument");
   if (cnt == 0 || cnt >= ((size_t)1 << 31)) return enc::fail(VPIN_EINVAL, "vpin_e2_unpack: cnt must be in 1 .. 2^31 - 1");
-  (void)hipSetDevice(c->device);
-  DevBuf in(c), x(c), y(c), f(c), b(c);
-  if (in.alloc(cnt * 32) || x.alloc(cnt * 32) || y.alloc(cnt * 32) || f.alloc(cnt) || b.alloc(cnt)) return VPIN_ENOMEM;
   std::vector<uint8_t> bad(cnt);
-  VPIN_HIP_TRY(hipMemcpyAsync(in.p, in32, cnt * 32, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(e2_unpack_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const fq*)in.p, cnt, e2_curve_a(),
-                     fq_of_le32(kBBytes), (fq*)x.p, (fq*)y.p, (uint8_t*)f.p, (uint8_t*)b.p);
-  VPIN_HIP_TRY(hipGetLastError());
-  VPIN_HIP_TRY(hipMemcpyAsync(px, x.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(py, y.p, cnt * 32, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(pinf, f.p, cnt, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(bad.data(), b.p, cnt, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  const int rc = wire::unpack_rules(c, in32, cnt, px, py, pinf, bad.data());
+  if (rc) return rc;
   return first_bad(bad, "vpin_e2_unpack", false);
 }
 

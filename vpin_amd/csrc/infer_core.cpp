@@ -76,15 +76,24 @@ const uint8_t* of_all_images(const uint8_t* at, size_t stride, size_t n, size_t 
   return own->data();
 }
 
-// every image's n bias values under the client's key, encrypted with the caller's r before the layer (encryptBias) by ONE call,
-// then per image its n c1 halves and its n c2 halves: the layer's rows 2 b and 2 b + 1, or its groups
+// every image's n bias values under the client's key (with public keys in the call: under the key of the image's own client),
+// encrypted with the caller's r before the layer (encryptBias) by ONE call, then per image its n c1 halves and its n c2 halves:
+// the layer's rows 2 b and 2 b + 1, or its groups
 int encrypt_bias(const Call& a, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* out) {
   Pts b1, b2;
   b1.resize(a.B * n); b2.resize(a.B * n);
   std::vector<int64_t> msgs(a.B * n);
   for (size_t i = 0; i < a.B * n; i++) msgs[i] = bias[i % n];
-  const int rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(), b1.inf.data(), b2.x.data(),
-                                 b2.y.data(), b2.inf.data());
+  int rc;
+  if (a.n_pub) {
+    std::vector<uint32_t> key_of(a.B * n);
+    for (size_t i = 0; i < a.B * n; i++) key_of[i] = a.key_of_image[i / n];
+    rc = vpin_e2_encrypt_keyed(a.c, a.baseG, a.hx, a.hy, a.n_pub, key_of.data(), msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(),
+                               b1.inf.data(), b2.x.data(), b2.y.data(), b2.inf.data());
+  } else {
+    rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(), b1.inf.data(), b2.x.data(),
+                         b2.y.data(), b2.inf.data());
+  }
   if (rc) return rc;
   out->resize(0);
   for (size_t b = 0; b < a.B; b++) { out->append(b1, b * n, n); out->append(b2, b * n, n); }
@@ -157,7 +166,8 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
     return fail(VPIN_EINVAL, (who + "the number of PRF keys is not one per convolution plane and fully connected row").c_str());
   if (a.n_bias_r != a.B * bias_r)
     return fail(VPIN_EINVAL, (who + "the number of bias randomness values is not one per fully connected output and biased output channel").c_str());
-  if ((keys && !a.keys32) || (bias_r && (!a.bias_r_le32 || !a.baseG || !a.baseH)) || (any_round && !a.round_fn))
+  if ((keys && !a.keys32) || (bias_r && (!a.bias_r_le32 || !a.baseG || (!a.n_pub && !a.baseH))) ||
+      (a.n_pub && (!a.hx || !a.hy || !a.key_of_image)) || (any_round && !a.round_fn))
     return fail(VPIN_EINVAL, (who + "null argument").c_str());
   out->step_ms.assign(steps.size(), 0.0);
   out->round_ms.assign(steps.size(), 0.0);

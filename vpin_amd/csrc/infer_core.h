@@ -55,7 +55,13 @@ struct Call {
   size_t n_bias_r;
   vpin_lenet_round_fn round_fn;
   void* user;
-  size_t B = 1;  // the images; last, so that a caller of one image names none
+  size_t B = 1;  // the images; behind everything a caller of one image names
+  // the images of several clients: n_pub public keys (canonical little-endian, n_pub x 32 bytes each) and per image the index
+  // of its client's.  n_pub = 0: every image is under baseH's key.  Otherwise baseH is not read and the bias of image b is
+  // encrypted under key key_of_image[b] (vpin_e2_encrypt_keyed)
+  const uint8_t *hx = nullptr, *hy = nullptr;
+  size_t n_pub = 0;
+  const uint32_t* key_of_image = nullptr;
 };
 
 // per step the trace of its layer call, owned; host-clock milliseconds per step (plane sums included), per round (0: none) and in all

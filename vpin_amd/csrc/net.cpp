@@ -6,6 +6,7 @@
 // vpin_net_infer_batch is the same function over B images (vpin_net_infer: B = 1): every layer one call and every round one
 // callback over the planes of all images, image after image; the label is then the images' labels one after the other, and
 // vpin_net_trace_image_label cuts image b's own out of the layer calls' traces.
+// vpin_net_infer_multi is the batch with the images of several clients: a public key per image instead of one table of H.
 #include <memory>
 #include <new>
 #include <string>
@@ -155,10 +156,18 @@ struct vpin_net_trace {
 
 namespace {
 
-// vpin_net_infer (B = 1) and vpin_net_infer_batch: the steps of the one driver and the label
+// the public keys of vpin_net_infer_multi; none (n_pub = 0) for the other two
+struct PubKeys {
+  const uint8_t *hx = nullptr, *hy = nullptr;
+  size_t n_pub = 0;
+  const uint32_t* key_of_image = nullptr;
+};
+
+// vpin_net_infer (B = 1), vpin_net_infer_batch and vpin_net_infer_multi: the steps of the one driver and the label
 int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t* keys32,
-          size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out) {
+          size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out,
+          const PubKeys& pub = PubKeys()) {
   if (out) *out = nullptr;
   if (!c || !g || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !out) return fail(VPIN_EINVAL, (std::string(who) + ": null argument").c_str());
   if (!B || B > VPIN_NET_MAX_BATCH)
@@ -188,7 +197,7 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
   if (!t) return VPIN_ENOMEM;
   t->B = B;
   const vpin::infer::Call call{c, who, g->prf_bytes, g->C, g->H, g->W, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH,
-                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, B};
+                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, B, pub.hx, pub.hy, pub.n_pub, pub.key_of_image};
   const vpin::infer::Result& res = t->run;
   const int rc = vpin::infer::run(call, steps, &t->run);
   g_ms.assign(1 + 2 * pl.size(), 0.0);
@@ -255,6 +264,21 @@ int vpin_net_infer_batch(vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uin
                          void* user, vpin_net_trace** out) {
   return infer("vpin_net_infer_batch", c, g, B, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH, keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user,
                out);
+}
+
+int vpin_net_infer_multi(vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                         const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const uint8_t* hx, const uint8_t* hy,
+                         size_t n_pub, const uint32_t* key_of_image, const uint8_t* keys32, size_t n_keys, const uint8_t* bias_r_le32,
+                         size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out) {
+  if (out) *out = nullptr;
+  if (!hx || !hy || !key_of_image) return fail(VPIN_EINVAL, "vpin_net_infer_multi: null argument");
+  if (!n_pub) return fail(VPIN_EINVAL, "vpin_net_infer_multi: n_pub = 0: no public key");
+  for (size_t b = 0; b < B && b < VPIN_NET_MAX_BATCH; b++)
+    if (key_of_image[b] >= n_pub)
+      return fail(VPIN_EINVAL, ("vpin_net_infer_multi: key_of_image[" + std::to_string(b) + "] = " + std::to_string(key_of_image[b]) +
+                                " is not below n_pub = " + std::to_string(n_pub)).c_str());
+  return infer("vpin_net_infer_multi", c, g, B, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, nullptr, keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user,
+               out, PubKeys{hx, hy, n_pub, key_of_image});
 }
 
 int vpin_net_trace_images(const vpin_net_trace* t, size_t* B) {

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/vpin_hip.h"
@@ -55,8 +56,53 @@ void send_error(vpin_wire* w, int code, const char* text);
 int peer_error(vpin_wire* w, const vpin_wire_header& h, const char* who);
 
 
+// ---- the roster of several clients in one batch (wire_roster.cpp: plain C++ like the codec and the stream) -----------------
+// Who gets which bytes.  A packed batch is c1 | c2 of all its images: 2 * images * per packed points of 32 bytes, each half
+// image-major, `per` the ciphertexts of one image.  A client's frame holds the c1 part of its images and then their c2 part.
+struct Peer {
+  vpin_wire* w = nullptr;
+  size_t wire = 0;           // its index among the caller's wires, and into the status
+  size_t first = 0, n = 0;   // its image slots [first, first + n)
+  bool live = true;
+};
+struct Roster {
+  const char* who = "";      // the entry point's name, in front of every text
+  size_t max_batch = 0, images = 0;
+  std::vector<Peer> peers;   // the admitted clients, in wire order
+  vpin_net_peer_status* status = nullptr;  // one per wire of the caller's
+  size_t live() const;
+  // the next admitted client: its slots are the n_images after those taken (the caller has seen that they fit)
+  void admit(vpin_wire* w, size_t wire, size_t n_images);
+  // wire's status: code, stage and "<who>: <text>"; the slots stay as they are
+  void report(size_t wire, int code, int stage, const std::string& text);
+  // peer p leaves at `stage`: report, and ERROR to it best effort, unless it has said ERROR itself (tell = false)
+  void drop(size_t p, int code, int stage, const std::string& text, bool tell = true);
+};
+// peer's frame out of a packed batch, and a frame's points into their places in one
+void slice(const Roster& r, const Peer& p, const uint8_t* packed, size_t per, std::vector<uint8_t>* frame);
+void place(const Roster& r, const Peer& p, const uint8_t* frame, size_t per, uint8_t* packed);
+// the images of peer p out of an image-major array of `elem` bytes per ciphertext into the same places of another
+void copy_images(const Peer& p, size_t per, size_t elem, const uint8_t* from, uint8_t* to);
+// HELLO and INPUT off one wire that may ask for at most `room` images: the packed key, the packed input (c1 part, then c2 part)
+// and its images.  *told: the peer has sent ERROR itself
+int read_client(vpin_wire* w, size_t per, size_t room, std::vector<uint8_t>* hello, std::vector<uint8_t>* input,
+                size_t* n_images, bool* told);
+// One round with every live client: ROUND with its slice to each, all sent first; then the REPLYs in wire order into *reply,
+// which is laid out as `packed` (left empty when the round encrypts nothing).  A client whose stream fails, who sends ERROR or
+// a REPLY for another round or with another cnt is dropped; the places of every client that is not live hold what the server
+// sent.  VPIN_ECOMM when no client is left
+int exchange(Roster* r, int round, int flags, int shift_bits, const uint8_t* packed, size_t per, std::vector<uint8_t>* reply);
+// DONE to every live client: VPIN_OK and VPIN_NET_STAGE_DONE into its status; one that cannot be told is dropped.  The clients told
+size_t finish(Roster* r);
+
 // what the endpoints share (wire_net.cpp; these reach the device through vpin_e2_pack / vpin_e2_unpack): c1 | c2 as one run of
 // 2 cnt packed points and back, and a frame's send and payload receive, each timed into the wire's slot
+int pack_pair(vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y,
+              const uint8_t* c2inf, size_t cnt, std::vector<uint8_t>* out);
+// vpin_e2_unpack (e2_wire.hip) with the rule byte of every point in bad[cnt] instead of a failure on the first: 0, or what
+// unpack_rule_text says.  A bad point comes out as zeros
+int unpack_rules(vpin_ctx* c, const uint8_t* in32, size_t cnt, uint8_t* px, uint8_t* py, uint8_t* pinf, uint8_t* bad);
+const char* unpack_rule_text(uint8_t rule);
 int pack_pair_timed(vpin_wire* w, size_t slot, vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x,
                     const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, std::vector<uint8_t>* out);
 int unpack_pair_timed(vpin_wire* w, size_t slot, vpin_ctx* c, const std::vector<uint8_t>& in, size_t cnt, uint8_t* c1x, uint8_t* c1y,

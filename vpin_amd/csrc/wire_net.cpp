@@ -16,8 +16,6 @@ namespace vpin::wire {
 
 void set_error(const char* text) { set_last_error_text(text); }
 
-namespace {
-
 // c1 | c2 as one run of 2 cnt packed points, one launch
 int pack_pair(vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y,
               const uint8_t* c2inf, size_t cnt, std::vector<uint8_t>* out) {
@@ -28,8 +26,6 @@ int pack_pair(vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t
   out->resize(64 * cnt);
   return vpin_e2_pack(c, x.data(), y.data(), f.data(), 2 * cnt, out->data());
 }
-
-}  // namespace
 
 int pack_pair_timed(vpin_wire* w, size_t slot, vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x,
                     const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, std::vector<uint8_t>* out) {

@@ -1,4 +1,4 @@
-"""The client side of vPIN's exponential ElGamal on E2 over the C ABI (vpin_e2_base_*, vpin_e2_encrypt, vpin_e2_dlog_*,
+"""The client side of vPIN's exponential ElGamal on E2 over the C ABI (vpin_e2_base_*, vpin_e2_encrypt[_keyed], vpin_e2_dlog_*,
 vpin_e2_decrypt): key generation, batched encryption of signed integers and batched decryption with a discrete-log table that
 stays in device memory.  Ciphertexts are the (x, y, inf) numpy triples the encrypted layers of vpin_amd.enc_conv take and
 return, so a layer's output decrypts, goes through the caller's activation in numpy and is encrypted again for the next layer.
@@ -79,6 +79,15 @@ def encrypt(base_g, base_h, msgs, rs):
     msgs.shape + (32,)"""
     m = np.asarray(msgs, dtype=np.int64)
     c1, c2 = base_g.ctx.e2_encrypt(base_g.h, base_h.h, m.reshape(-1), list(rs))
+    shaped = lambda t: (t[0].reshape(m.shape + (32,)), t[1].reshape(m.shape + (32,)), t[2].reshape(m.shape))
+    return shaped(c1), shaped(c2)
+
+
+def encrypt_keyed(base_g, pubs, key_of, msgs, rs):
+    """encrypt with a public key per element and no table of any H (vpin_e2_encrypt_keyed): pubs = [(x, y)] as Python ints (keygen),
+    element i under pubs[key_of[i]]; msgs, rs and the result as for encrypt, key_of of msgs' shape"""
+    m = np.asarray(msgs, dtype=np.int64)
+    c1, c2 = base_g.ctx.e2_encrypt_keyed(base_g.h, list(pubs), np.asarray(key_of).reshape(-1), m.reshape(-1), list(rs))
     shaped = lambda t: (t[0].reshape(m.shape + (32,)), t[1].reshape(m.shape + (32,)), t[2].reshape(m.shape))
     return shaped(c1), shaped(c2)
 

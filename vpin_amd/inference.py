@@ -138,10 +138,11 @@ class Trace:
             self.h = None
 
 
-def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user, batch=None):
+def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user, batch=None, pubs=None, key_of_image=None):
     """`name` = vpin_lenet_infer or vpin_net_infer over the C configuration cfg_c -> the trace's handle.  c1, c2: (x, y, inf) of
     the input points; keys: 32-byte keys in call order; bias_rs: ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer.
-    batch: the B of vpin_net_infer_batch, which takes it behind the configuration; everything is then image-major"""
+    batch: the B of vpin_net_infer_batch, which takes it behind the configuration; everything is then image-major.
+    pubs: for vpin_net_infer_multi, which takes public keys [(x, y)] as Python ints and key_of_image[B] where the others take base_h"""
     x1, y1, f1 = ctx._points(*c1)
     x2, y2, f2 = ctx._points(*c2)
     k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
@@ -149,7 +150,13 @@ def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn,
     h = C.c_void_p()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     fn = C.cast(round_fn, C.c_void_p)
-    rc = getattr(lib(), name)(ctx.h, C.byref(cfg_c), *([] if batch is None else [batch]), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, base_h,
+    under = [base_h]
+    if pubs is not None:
+        hx, hy = ctx._u256s([x for x, _ in pubs]), ctx._u256s([y for _, y in pubs])
+        ko = np.ascontiguousarray(np.array([int(v) for v in key_of_image], dtype=np.uint32))
+        assert ko.shape[0] == batch
+        under = [p(hx), p(hy), len(pubs), p(ko)]
+    rc = getattr(lib(), name)(ctx.h, C.byref(cfg_c), *([] if batch is None else [batch]), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, *under,
                               p(k), len(keys), p(r), len(bias_rs), fn, user, C.byref(h))
     if rc:
         assert not h.value

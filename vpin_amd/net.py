@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from . import inference
-from .capi import NetCfg, NetLayer, _chk, lib
+from .capi import NetCfg, NetLayer, NetPeerStatus, VpinError, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
 CONV, POOL, FC, CONVMC, FCS = 0, 1, 2, 3, 4
@@ -242,6 +242,15 @@ def infer_batch(ctx, cfg, client, images, image_rs, keys, bias_rs):
     return rounds[-1][1].reshape(b, -1), rounds, trace
 
 
+def infer_multi(ctx, cfg, base_g, pubs, key_of_image, c1, c2, keys, bias_rs, round_fn, user=None):
+    """vpin_net_infer_multi -> Trace: run over the images of several clients, each under its own key.  pubs: the clients' public
+    keys [(x, y)] as Python ints; key_of_image: per image the index of its client's; c1, c2: (x, y, inf) of all images' input
+    points, image-major, each image encrypted under its client's key; keys, bias_rs: flat, image-major, per image what a single run
+    takes.  The round function sees the whole batch and hands every image to whoever holds its key"""
+    return Trace(ctx, inference.run_infer("vpin_net_infer_multi", ctx, cfg.c, c1, c2, base_g, None, keys, bias_rs, round_fn, user,
+                                          batch=len(key_of_image), pubs=list(pubs), key_of_image=key_of_image))
+
+
 def schedule(cfg, batch=1):
     """what the client of `cfg` agrees to: per round (flags, shift_bits, cnt) from the layers' rounds and vpin_net_cfg_counts, cnt
     times the images of a batch.  The client holds its own copy and answers no round that differs (Client.run)"""
@@ -266,6 +275,52 @@ def serve(ctx, cfg, wire, keys, bias_rs, max_batch=1):
         _chk(lib().vpin_net_serve_batch(ctx.h, C.byref(cfg_c), wire.h, 1 if max_batch is None else max_batch, p(k), len(keys), p(r), len(bias_rs),
                                         C.byref(h)), "vpin_net_serve_batch")
     return Trace(ctx, h)
+
+
+STAGE_DONE, STAGE_ADMISSION, STAGE_SERVER = -1, -2, -3
+
+
+class Server:
+    """vpin_net_server: the server's endpoint for several clients in one batched inference.  Checks `cfg` and builds the table of G
+    once; every `serve` is then one inference over the images of all the wires it is given, each client under its own key, with no
+    table of any client's H"""
+
+    def __init__(self, ctx, cfg, max_batch):
+        self.ctx, self.cfg, self.max_batch = ctx, cfg, max_batch
+        self._cfg_c = cfg.c  # the server borrows it until free
+        h = C.c_void_p()
+        _chk(lib().vpin_net_server_create(ctx.h, C.byref(self._cfg_c), max_batch, C.byref(h)), "vpin_net_server_create")
+        self.h = h
+
+    def serve(self, wires, keys, bias_rs):
+        """vpin_net_serve_multi over vpin_amd.wire.Wire objects -> (Trace, statuses).  keys, bias_rs: flat, max_batch times one
+        image's.  statuses: per wire dict(code, stage, first_image, n_images, text), stage STAGE_DONE for a client served to the end,
+        else where it left: STAGE_ADMISSION, the round's number or STAGE_SERVER.  Raises VpinError, with the statuses in its
+        `.statuses`, when nobody was served"""
+        k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
+        r = self.ctx._u256s(bias_rs) if len(bias_rs) else np.zeros(32, np.uint8)
+        ws = (C.c_void_p * max(1, len(wires)))(*[w.h for w in wires])
+        st = (NetPeerStatus * max(1, len(wires)))()
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_net_serve_multi(self.h, ws, len(wires), p(k), len(keys), p(r), len(bias_rs), st, C.byref(h))
+        statuses = [dict(code=s.code, stage=s.stage, first_image=s.first_image, n_images=s.n_images, text=s.text.decode(errors="replace"))
+                    for s in st[:len(wires)]]
+        if rc:
+            e = VpinError(rc, "vpin_net_serve_multi")
+            e.statuses = statuses
+            raise e
+        return Trace(self.ctx, h), statuses
+
+    def stats(self):
+        out = (C.c_uint64 * 5)()
+        _chk(lib().vpin_net_server_stats(self.h, out), "vpin_net_server_stats")
+        return dict(zip(("calls", "clients_admitted", "clients_served", "images", "base_tables_built"), (int(v) for v in out)))
+
+    def free(self):
+        if self.h:
+            lib().vpin_net_server_free(self.h)
+            self.h = None
 
 
 def write_witness_files(trace, root, label):
