@@ -858,6 +858,13 @@ int vpin_e2_client_round(vpin_ctx* ctx, const vpin_e2_dlog* t, const vpin_e2_bas
  * curve; n_in or n_out above 65535, or 2^31 points or more on either side. */
 int vpin_e2_plane_sums(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n_in, size_t H, size_t W,
                        const uint8_t* connect, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
+/* (ABI 8) vpin_e2_plane_sums over `groups` sets of planes under the one table, by one upload, one kernel launch and one copy
+ * back: groups x n_in planes in, group-major, groups x n_out planes out; group g's output is byte for byte what
+ * vpin_e2_plane_sums gives on group g's planes alone.  A batch of B images hands its 2 B halves (image b's c1 planes, then its c2
+ * planes) as the groups.  VPIN_EINVAL as there, naming vpin_e2_plane_sums_batch: a point off the curve fails the whole call;
+ * groups above 65535, or 2^31 points or more on either side over all groups */
+int vpin_e2_plane_sums_batch(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t n_in,
+                             size_t H, size_t W, const uint8_t* connect, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
 
 /* ---- the whole encrypted LeNet inference ---------------------------------------------------------------------------------
  * What inferenceCNN of src/LeNet/Server.py and main of src/LeNet/Client.py do together: the encrypted image goes in, the
@@ -959,6 +966,16 @@ void vpin_lenet_last_timings(double out[16]);
  *   VPIN_NET_FCS   VPIN_NET_FC over signed weights: K, N, w, bias as there, vpin_enc_fc_signed with P = 2; the same counts.
  *                  VPIN_NET_FC itself still answers VPIN_EINVAL for a negative weight */
 #define VPIN_NET_FCS 4
+/*   (ABI 8) What the reference's LeNet needs of a layer, again at the END of vpin_net_layer and all zero for today's behaviour:
+ *   sum_table, sum_out  CONV: before the layer the channel sums (vpin_e2_plane_sums_batch over the 2 B halves) by a table of
+ *                  sum_out x C bytes, C the planes that reach the layer; the layer then sees C = sum_out.  They enter no list
+ *   repeat         CONV: the planes are handed to the call `repeat` times over (0 or 1: once), every one of the 2 C repeat
+ *                  planes under a key of its own; C repeat planes go on
+ *   plane_order    CONV and POOL: 0 the blocked order above, VPIN_NET_ORDER_INTERLEAVED LeNet's (0, c1), (0, c2), (1, c1), ..
+ *                  for the call's planes, its keys and its output.  With a repeat the blocked order is the image's c1 planes
+ *                  `repeat` times, then its c2 planes
+ * vpin_lenet_as_net writes the reference's LeNet as such a list */
+#define VPIN_NET_ORDER_INTERLEAVED 1
 typedef struct vpin_net_layer {
   int kind;
   size_t fh, fw, pad;            /* CONV */
@@ -974,6 +991,10 @@ typedef struct vpin_net_layer {
   size_t n_out;                  /* CONVMC (with fh, fw, pad, stride): the output channels */
   const int32_t* w_mc;           /* CONVMC: n_out x C x fh x fw, row-major, signed */
   const uint8_t* connect;        /* CONVMC: n_out x C bytes, non-zero = connected; NULL: all */
+  const uint8_t* sum_table;      /* CONV: NULL, or sum_out x C bytes: the channel sums in front of the layer */
+  size_t sum_out;
+  size_t repeat;                 /* CONV: 0 or 1: once */
+  int plane_order;               /* CONV and POOL: 0, or VPIN_NET_ORDER_INTERLEAVED */
 } vpin_net_layer;
 typedef struct vpin_net_cfg {
   size_t C, H, W;                /* the encrypted input */
@@ -986,8 +1007,18 @@ typedef struct vpin_net_cfg {
  * layer i out[8 + 3 i] its multiplications, out[9 + 3 i] its additions, out[10 + 3 i] the decryptions of the round after it (0:
  * none).  VPIN_EINVAL for a zero dimension, a window that does not fit, an FC whose K is not the incoming C * H * W, an unknown
  * kind, shift_bits outside 0 .. 62, reencrypt = 0 before the last layer, prf_bytes outside 1 .. 16, a CONVMC layer with n_out = 0
- * or a row of connect that selects no channel (the table is read here: the counts depend on it; the weights are not) */
+ * or a row of connect that selects no channel (the table is read here: the counts depend on it; the weights are not); (ABI 8) a
+ * sum_table or a repeat > 1 on a layer that is no CONV, a sum_table with sum_out = 0 or with a row that selects no plane (read
+ * here likewise), a plane_order that is neither 0 nor VPIN_NET_ORDER_INTERLEAVED.  A CONV behind sums and repeat counts 2 C'
+ * planes, keys and C' planes out, C' = (sum_out, or the incoming C) * repeat */
 int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
+/* (ABI 8) the reference's LeNet as a layer list: the seven layers vpin_lenet_infer runs (CONV with repeat = n1; POOL; CONV behind
+ * the sums by cfg->connect; POOL; CONV behind the sum of all planes with repeat = n3; FC; FC), the convolutions and poolings
+ * interleaved, every layer with its round R1 .. R7 (relu, shift_bits, max_giant, reencrypt = 0 on the last).  `layers` and `ones`
+ * (n2 bytes, filled with 1: the table of the third convolution) are the caller's and *out borrows them and cfg's arrays; layer i is
+ * label L(i + 1).  What vpin_lenet_infer computes on cfg, vpin_net_infer computes on *out byte for byte, with the same keys and
+ * bias r; and so a batch, the wire and several clients take LeNet.  The codes and texts of vpin_lenet_infer for a bad cfg */
+int vpin_lenet_as_net(const vpin_lenet_cfg* cfg, vpin_net_layer layers[7], uint8_t* ones, vpin_net_cfg* out);
 typedef struct vpin_net_trace vpin_net_trace;
 /* The server loop, the same driver as vpin_lenet_infer with one step per layer, the planes blocked (all c1, then all c2): the
  * same callback type per round (round = the round's number), the caller's keys (one per convolution plane and FC row, in call
@@ -1056,6 +1087,9 @@ int vpin_net_trace_images(const vpin_net_trace* t, size_t* B);
 /* image b's label, borrowed until vpin_net_trace_free: byte for byte what vpin_net_trace_label gives for image b run alone
  * (lists, output, dims).  Built when first asked for and kept; one thread reads a trace at a time */
 int vpin_net_trace_image_label(const vpin_net_trace* t, size_t b, const vpin_conv_trace** out);
+/* (ABI 8) image b's share of ONE layer call, borrowed likewise: its lists, its left sides and its output, byte for byte
+ * vpin_net_trace_layer of that image run alone.  For a network whose layers are labels of their own (LeNet: seven) */
+int vpin_net_trace_image_layer(const vpin_net_trace* t, size_t b, size_t layer, const vpin_conv_trace** out);
 /* image b's label as vpin_net_trace_instances */
 int vpin_net_trace_image_instances(vpin_ctx* ctx, const vpin_net_trace* t, size_t b, vpin_dev_instance** mult_out,
                                    vpin_dev_instance** add_out);

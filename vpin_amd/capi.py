@@ -56,17 +56,23 @@ class LenetCfg(C.Structure):
 
 
 class NetLayer(C.Structure):
-    """vpin_net_layer of include/vpin_hip.h"""
+    """vpin_net_layer of include/vpin_hip.h as ABI 3 to 7 had it: the struct's prefix, ending in CONVMC's fields"""
     _fields_ = [("kind", C.c_int), ("fh", C.c_size_t), ("fw", C.c_size_t), ("pad", C.c_size_t), ("stride", C.c_size_t),
                 ("filter_le16", C.c_void_p), ("k", C.c_size_t), ("scale_le16", C.c_uint8 * 16), ("K", C.c_size_t), ("N", C.c_size_t),
                 ("w", C.c_void_p), ("bias", C.c_void_p), ("has_round", C.c_int), ("relu", C.c_int), ("shift_bits", C.c_int),
                 ("reencrypt", C.c_int), ("max_giant", C.c_uint64), ("n_out", C.c_size_t), ("w_mc", C.c_void_p), ("connect", C.c_void_p)]
 
 
+class NetLayer8(NetLayer):
+    """the whole vpin_net_layer: behind NetLayer's fields what ABI 8 appended at its end, all zero for a layer as before.  This is
+    the struct the library reads: a vpin_net_cfg points to an array of these"""
+    _fields_ = [("sum_table", C.c_void_p), ("sum_out", C.c_size_t), ("repeat", C.c_size_t), ("plane_order", C.c_int)]
+
+
 class NetCfg(C.Structure):
     """vpin_net_cfg of include/vpin_hip.h"""
     _fields_ = [("C", C.c_size_t), ("H", C.c_size_t), ("W", C.c_size_t), ("prf_bytes", C.c_int), ("n_layers", C.c_size_t),
-                ("layers", C.POINTER(NetLayer))]
+                ("layers", C.POINTER(NetLayer8))]
 
 
 class WireHeader(C.Structure):
@@ -244,7 +250,9 @@ def lib():
     L.vpin_e2_decrypt.argtypes = [vp, vp, vp] + [vp] * 6 + [C.c_size_t, C.c_uint64, vp, vp]
     L.vpin_e2_client_round.argtypes = [vp] * 5 + [vp] * 6 + [C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, vp, vp, vp] + [vp] * 6
     L.vpin_e2_plane_sums.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_plane_sums_batch.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 4 + [vp, C.c_size_t, vp, vp, vp]
     L.vpin_lenet_cfg_default.argtypes = [C.POINTER(LenetCfg)]
+    L.vpin_lenet_as_net.argtypes = [C.POINTER(LenetCfg), C.POINTER(NetLayer8), vp, C.POINTER(NetCfg)]
     L.vpin_lenet_cfg_counts.argtypes = [C.POINTER(LenetCfg), C.POINTER(C.c_size_t)]
     L.vpin_lenet_infer.argtypes = [vp, C.POINTER(LenetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.vpin_lenet_trace_free.argtypes = [vp]
@@ -269,6 +277,7 @@ def lib():
                                        [vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)])
     L.vpin_net_trace_images.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.vpin_net_trace_image_label.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.vpin_net_trace_image_layer.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_trace_image_instances.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
     L.vpin_net_client_create.argtypes = [vp, vp, C.c_uint64, C.c_size_t, C.POINTER(C.c_uint64), vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_client_free.argtypes = [vp]
@@ -1622,6 +1631,20 @@ class Context:
         ox, oy, oi = np.zeros((n_out, H, W, 32), np.uint8), np.zeros((n_out, H, W, 32), np.uint8), np.zeros((n_out, H, W), np.uint8)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _chk(lib().vpin_e2_plane_sums(self.h, p(x), p(y), p(f), n_in, H, W, p(con), n_out, p(ox), p(oy), p(oi)), "vpin_e2_plane_sums")
+        return ox, oy, oi
+
+    def e2_plane_sums_batch(self, x, y, inf, groups, n_in, H, W, connect):
+        """vpin_e2_plane_sums_batch: e2_plane_sums over `groups` sets of n_in planes (group-major) under the one table, in one call
+        -> (x, y, inf) of groups x len(connect) planes"""
+        x, y, f = self._points(x, y, inf)
+        con = np.ascontiguousarray(np.asarray(connect, dtype=np.uint8))
+        assert x.shape[0] == groups * n_in * H * W and con.ndim == 2 and con.shape[1] == n_in
+        n_out = con.shape[0]
+        shape = (groups, n_out, H, W)
+        ox, oy, oi = np.zeros(shape + (32,), np.uint8), np.zeros(shape + (32,), np.uint8), np.zeros(shape, np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_plane_sums_batch(self.h, p(x), p(y), p(f), groups, n_in, H, W, p(con), n_out, p(ox), p(oy), p(oi)),
+             "vpin_e2_plane_sums_batch")
         return ox, oy, oi
 
     # ---- profiling ----

@@ -1,5 +1,5 @@
 // infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias],
-// vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums) and the interaction with the client as a callback per round: what vpin_lenet_infer
+// vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums_batch) and the interaction with the client as a callback per round: what vpin_lenet_infer
 // (lenet.cpp) and vpin_net_infer[_batch] (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer
 // validates what it is given, the client's answers included.  A batch of B images is the same loop: every layer call and every
 // round takes the planes of all images at once, image after image (infer_core.h, Call).
@@ -182,16 +182,16 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     int rc = VPIN_OK;
-    if (s.sum_table) {
-      if (B != 1) return fail(VPIN_EINVAL, (who + s.name + ": the plane sums take one image").c_str());
-      for (Pts* p : {&c1, &c2}) {
-        Pts sum;
-        sum.resize(s.sum_out * H * W);
-        rc = vpin_e2_plane_sums(a.c, p->x.data(), p->y.data(), p->inf.data(), C, H, W, s.sum_table, s.sum_out, sum.x.data(), sum.y.data(),
-                                sum.inf.data());
-        if (rc) return named(rc, s.name);
-        std::swap(*p, sum);
-      }
+    if (s.sum_table) {  // ONE call over the groups g = 2 b + half, then the sums back into c1 and c2
+      const size_t img = C * H * W, out_img = s.sum_out * H * W;
+      Pts in, sum;
+      for (size_t b = 0; b < B; b++) { in.append(c1, b * img, img); in.append(c2, b * img, img); }
+      sum.resize(2 * B * out_img);
+      rc = vpin_e2_plane_sums_batch(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * B, C, H, W, s.sum_table, s.sum_out, sum.x.data(),
+                                    sum.y.data(), sum.inf.data());
+      if (rc) return named(rc, s.name);
+      c1.resize(0); c2.resize(0);
+      for (size_t h = 0; h < 2 * B; h++) (h % 2 ? c2 : c1).append(sum, h * out_img, out_img);
       C = s.sum_out;
     }
     if (s.kind == Step::kFc || s.kind == Step::kFcs) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row

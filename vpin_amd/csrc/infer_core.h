@@ -26,7 +26,7 @@ struct Step {
   size_t n_out = 0;                      // kConvMc (with fh, fw, pad, stride): vpin_enc_conv2d_mc with groups = 2, kBlocked
   const int32_t* w_mc = nullptr;
   const uint8_t* connect = nullptr;
-  // before the call: vpin_e2_plane_sums by this table on c1 and on c2 (sum_out planes each), when there is one ..
+  // before the call: vpin_e2_plane_sums_batch by this table on every image's c1 and c2 (sum_out planes each), when there is one ..
   const uint8_t* sum_table = nullptr;
   size_t sum_out = 0;
   size_t repeat = 1;  // .. and then the planes handed to the call this many times over
@@ -41,7 +41,7 @@ struct Step {
 // what both entry points are given, and the input's shape.  B images go through every step in ONE layer call and every round in
 // ONE callback: c1 and c2 hold [b][C][H][W], a layer call's planes are [b] of what Step::Order says for one image, keys32 and
 // bias_r_le32 are image-major (n_keys, n_bias_r: B times what the steps consume), and each step is handed its keys and bias r of
-// all images, image after image.  A step with a sum_table is for B = 1 (vpin_lenet_infer)
+// all images, image after image; the sums of a step with a sum_table are one call over the groups [b][half]
 struct Call {
   vpin_ctx* c;
   const char* who;  // the entry point's name, in front of every error text

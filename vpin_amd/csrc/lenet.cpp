@@ -1,7 +1,8 @@
 // lenet.cpp -- the whole encrypted LeNet inference behind the C ABI: the server loop of the reference's src/LeNet/Server.py
 // inferenceCNN as seven steps of the one driver (infer_core.cpp), planes in the order (kernel 0, c1), (kernel 0, c2), ..  Per
 // label L1 .. L7 the trace keeps the layer's own trace, so the witness lists are the layers' lists in call order; the plane
-// additions of the channel sums enter no list (the reference does not prove them).
+// additions of the channel sums enter no list (the reference does not prove them).  vpin_lenet_as_net says the same seven steps
+// as a vpin_net_cfg, for the batched, wired and multi-client paths of net.cpp.
 #include <cstring>
 #include <memory>
 #include <new>
@@ -106,6 +107,34 @@ int vpin_lenet_cfg_counts(const vpin_lenet_cfg* g, size_t out[32]) {
   out[23] = 2 * (g->n1 + g->n2 + g->n3) + 4;    // PRF keys
   out[24] = g->N1 + g->N2;                      // bias randomness
   for (int i = 25; i < 32; i++) out[i] = 0;
+  return VPIN_OK;
+}
+
+int vpin_lenet_as_net(const vpin_lenet_cfg* g, vpin_net_layer layers[7], uint8_t* ones, vpin_net_cfg* out) {
+  if (!g || !layers || !ones || !out) return fail(VPIN_EINVAL, "vpin_lenet_as_net: null argument");
+  Dims d;
+  const int bad = check_cfg(g, &d, true);
+  if (bad) return bad;
+  memset(ones, 1, g->n2);
+  memset(layers, 0, 7 * sizeof *layers);
+  const int kinds[7] = {VPIN_NET_CONV, VPIN_NET_POOL, VPIN_NET_CONV, VPIN_NET_POOL, VPIN_NET_CONV, VPIN_NET_FC, VPIN_NET_FC};
+  for (int l = 0; l < 7; l++) {  // the steps of vpin_lenet_infer below, said as layers
+    vpin_net_layer& y = layers[l];
+    y.kind = kinds[l];
+    y.has_round = 1; y.relu = g->relu[l]; y.shift_bits = g->shift_bits[l]; y.reencrypt = l < 6; y.max_giant = g->max_giant[l];
+    if (y.kind == VPIN_NET_CONV) { y.filter_le16 = g->filter_le16; y.fh = y.fw = g->f; y.stride = 1; }
+    if (y.kind == VPIN_NET_POOL) { y.k = g->pool_k; y.stride = g->pool_stride; memcpy(y.scale_le16, g->pool_scale_le16, 16); }
+    if (y.kind != VPIN_NET_FC) y.plane_order = VPIN_NET_ORDER_INTERLEAVED;
+  }
+  layers[0].repeat = g->n1;
+  layers[2].sum_table = g->connect; layers[2].sum_out = g->n2;
+  layers[4].sum_table = ones; layers[4].sum_out = 1; layers[4].repeat = g->n3;
+  layers[5].K = g->n3; layers[5].N = g->N1; layers[5].w = g->w1; layers[5].bias = g->b1;
+  layers[6].K = g->N1; layers[6].N = g->N2; layers[6].w = g->w2; layers[6].bias = g->b2;
+  out->C = 1; out->H = g->H; out->W = g->W;
+  out->prf_bytes = g->prf_bytes;
+  out->n_layers = 7;
+  out->layers = layers;
   return VPIN_OK;
 }
 

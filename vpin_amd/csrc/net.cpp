@@ -7,6 +7,9 @@
 // callback over the planes of all images, image after image; the label is then the images' labels one after the other, and
 // vpin_net_trace_image_label cuts image b's own out of the layer calls' traces.
 // vpin_net_infer_multi is the batch with the images of several clients: a public key per image instead of one table of H.
+// A CONV layer may say what the reference's LeNet needs (channel sums in front of it, its planes handed over several times, the
+// interleaved plane order: the driver's own Step fields), and vpin_lenet_as_net (lenet.cpp) writes that network as such a list;
+// its labels are single layers: vpin_net_trace_image_layer.
 #include <memory>
 #include <new>
 #include <string>
@@ -26,6 +29,7 @@ const char* kind_name(int kind) {
 // per layer what it consumes and leaves; the walk that vpin_net_cfg_counts and vpin_net_infer share
 struct LayerPlan {
   size_t oC, oH, oW;     // what goes out
+  size_t sumC, inC;      // the planes per half that reach the channel sums, and the layer call behind sums and repeat
   size_t mult, add, keys, bias_r;
   int round;             // index of the round after the layer, or -1
 };
@@ -42,9 +46,25 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
   out->clear();
   for (size_t i = 0; i < g->n_layers; i++) {
     const vpin_net_layer& l = g->layers[i];
-    LayerPlan p{C, H, W, 0, 0, 0, 0, -1};
+    LayerPlan p{C, H, W, C, C, 0, 0, 0, 0, -1};
     const char* fit = "vpin_net: a window does not fit its plane";
+    if (l.kind != VPIN_NET_CONV && (l.sum_table || l.repeat > 1)) return fail(VPIN_EINVAL, "vpin_net: only a convolution takes a sum_table or a repeat");
+    if (l.plane_order != 0 && l.plane_order != VPIN_NET_ORDER_INTERLEAVED)
+      return fail(VPIN_EINVAL, "vpin_net: a layer's plane_order is neither 0 nor VPIN_NET_ORDER_INTERLEAVED");
     if (l.kind == VPIN_NET_CONV) {
+      if (l.sum_table) {  // like a trained convolution's table, architecture: read here
+        if (!l.sum_out) return fail(VPIN_EINVAL, "vpin_net: a convolution has a sum_table and sum_out = 0");
+        if (l.sum_out > kMaxPlanes) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
+        for (size_t o = 0; o < l.sum_out; o++) {
+          bool any = false;
+          for (size_t ch = 0; ch < C; ch++) any = any || l.sum_table[o * C + ch] != 0;
+          if (!any) return fail(VPIN_EINVAL, "vpin_net: a row of a convolution's sum_table selects no plane");
+        }
+        C = l.sum_out;
+      }
+      if (l.repeat > kMaxPlanes || C * (l.repeat ? l.repeat : 1) > kMaxPlanes) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
+      C *= l.repeat ? l.repeat : 1;
+      p.oC = p.inC = C;
       if (!l.fh || !l.fw || !l.stride) return fail(VPIN_EINVAL, "vpin_net: a dimension is zero");
       if (l.fh > kMaxSide || l.fw > kMaxSide || l.pad > kMaxSide || l.stride > kMaxSide) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
       if (H + 2 * l.pad < l.fh || W + 2 * l.pad < l.fw) return fail(VPIN_EINVAL, fit);
@@ -125,22 +145,26 @@ void append_image(vpin_conv_trace* L, const vpin_conv_trace& tr, size_t b, size_
   part(&L->a_px, tr.a_px); part(&L->a_py, tr.a_py); part(&L->a_rx, tr.a_rx); part(&L->a_ry, tr.a_ry); part(&L->a_rz, tr.a_rz);
 }
 
-// what a layer call at B images must not exceed: its planes, groups or rows are a grid axis of its kernels (65535), its chains'
-// terms and its outputs an int.  At B = 1 the layer itself says so, with its own text
+// what a layer call at B images must not exceed: its planes (behind the channel sums and the repeat), groups or rows are a grid
+// axis of its kernels (65535), its chains' terms, its outputs and the points around its channel sums an int.  At B = 1 the layer
+// itself says so, with its own text
 int fits(const char* who, const vpin_net_cfg* g, const std::vector<LayerPlan>& pl, size_t B) {
-  size_t C = g->C;
   for (size_t i = 0; i < pl.size(); i++) {
     const vpin_net_layer& l = g->layers[i];
     const std::string name = std::string(who) + ": layer " + std::to_string(i) + " (" + kind_name(l.kind) + "): ";
     const bool fc = l.kind == VPIN_NET_FC || l.kind == VPIN_NET_FCS;
-    const size_t planes = fc ? 2 * B : 2 * B * C;
+    const size_t planes = fc ? 2 * B : 2 * B * pl[i].inC;
+    if (l.sum_table) {  // H, W of what reaches the layer: the previous layer's output
+      const size_t hw = i ? pl[i - 1].oH * pl[i - 1].oW : g->H * g->W, most = pl[i].sumC > l.sum_out ? pl[i].sumC : l.sum_out;
+      if (2 * B * most * hw >= ((size_t)1 << 31))
+        return fail(VPIN_EINVAL, (name + "the planes of all images around the channel sums are 2^31 points or more").c_str());
+    }
     if (planes > 65535)
       return fail(VPIN_EINVAL, (name + "2 B * C = " + std::to_string(planes) + " planes are more than the 65535 a layer call takes").c_str());
     if (fc && 2 * B * l.K >= ((size_t)1 << 31))
       return fail(VPIN_EINVAL, (name + "2 B * K = " + std::to_string(2 * B * l.K) + " chain terms are 2^31 or more").c_str());
     if (2 * B * pl[i].oC * pl[i].oH * pl[i].oW >= ((size_t)1 << 31))
       return fail(VPIN_EINVAL, (name + "the outputs of all images are 2^31 or more").c_str());
-    C = pl[i].oC;
   }
   return VPIN_OK;
 }
@@ -152,6 +176,7 @@ struct vpin_net_trace {
   vpin_conv_trace label;    // per image, in image order, the lists of all layers in layer order; the output and dims of the last layer
   size_t B = 1;
   mutable std::vector<std::unique_ptr<vpin_conv_trace>> image;  // B > 1: image b's label once it has been asked for
+  mutable std::vector<std::unique_ptr<vpin_conv_trace>> image_layer;  // B > 1: [layer][b], image b's share of a layer call likewise
 };
 
 namespace {
@@ -184,6 +209,8 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
     s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc
              : l.kind == VPIN_NET_FCS ? Step::kFcs : Step::kFc;
     s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
+    if (l.kind == VPIN_NET_CONV) { s.sum_table = l.sum_table; s.sum_out = l.sum_out; s.repeat = l.repeat ? l.repeat : 1; }
+    if ((l.kind == VPIN_NET_CONV || l.kind == VPIN_NET_POOL) && l.plane_order == VPIN_NET_ORDER_INTERLEAVED) s.order = Step::kInterleaved;
     if (l.kind == VPIN_NET_CONVMC) { s.n_out = l.n_out; s.w_mc = l.w_mc; s.connect = l.connect; }  // no other kind reads them
     s.k = l.k; s.scale_le16 = l.scale_le16;
     s.K = l.K; s.N = l.N; s.w = l.w; s.bias = l.bias;
@@ -224,6 +251,7 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
   for (size_t b = 0; b < B; b++)
     for (const vpin_conv_trace* tr : res.step) append_image(&L, *tr, b, B);
   t->image.resize(B);
+  t->image_layer.resize(B * res.step.size());
   g_ms[0] = res.total_ms + 1e3 * lap();  // the whole, the label included
   *out = t.release();
   return VPIN_OK;
@@ -304,6 +332,30 @@ int vpin_net_trace_image_label(const vpin_net_trace* t, size_t b, const vpin_con
     t->image[b] = std::move(L);
   }
   *out = t->image[b].get();
+  return VPIN_OK;
+}
+
+int vpin_net_trace_image_layer(const vpin_net_trace* t, size_t b, size_t layer, const vpin_conv_trace** out) {
+  if (out) *out = nullptr;
+  if (!t || !out || b >= t->B || layer >= t->run.step.size())
+    return fail(VPIN_EINVAL, "vpin_net_trace_image_layer: null argument, no such image or no such layer");
+  if (t->B == 1) { *out = t->run.step[layer]; return VPIN_OK; }
+  std::unique_ptr<vpin_conv_trace>& slot = t->image_layer[layer * t->B + b];
+  if (!slot) {
+    std::unique_ptr<vpin_conv_trace> L(new (std::nothrow) vpin_conv_trace());
+    if (!L) return VPIN_ENOMEM;
+    const vpin_conv_trace& all = *t->run.step[layer];  // an image's planes stand together: every array's b-th part
+    auto part = [&](std::vector<uint8_t>* to, const std::vector<uint8_t>& from) {
+      const size_t n = from.size() / t->B;
+      to->assign(from.begin() + b * n, from.begin() + (b + 1) * n);
+    };
+    L->P = all.P / t->B; L->oh = all.oh; L->ow = all.ow;
+    part(&L->out_x, all.out_x); part(&L->out_y, all.out_y); part(&L->out_inf, all.out_inf);
+    part(&L->left_x, all.left_x); part(&L->left_y, all.left_y); part(&L->left_inf, all.left_inf);
+    append_image(L.get(), all, b, t->B);
+    slot = std::move(L);
+  }
+  *out = slot.get();
   return VPIN_OK;
 }
 

@@ -118,6 +118,13 @@ def infer(ctx, cfg, client, image, image_rs, keys, bias_rs):
     return inference.infer(run, ctx, cfg, client, image, image_rs, keys, bias_rs)
 
 
+def infer_batch(ctx, cfg, client, images, image_rs, keys, bias_rs):
+    """infer over B images at once: the layer list of `cfg` (net.from_lenet) through net.infer_batch, arguments and results as
+    there.  The trace is a net.Trace: image b's label L(i + 1) is trace.image_layer(b, i)"""
+    from . import net
+    return net.infer_batch(ctx, net.from_lenet(cfg), client, images, image_rs, keys, bias_rs)
+
+
 def write_witness_files(trace, root):
     """the 7 x 8 JSON files the CLI reads, under root/rust_files/L1 .. L7"""
     from . import enc_conv

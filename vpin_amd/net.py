@@ -15,10 +15,11 @@ import os
 import numpy as np
 
 from . import inference
-from .capi import NetCfg, NetLayer, NetPeerStatus, VpinError, _chk, lib
+from .capi import NetCfg, NetLayer8 as NetLayer, NetPeerStatus, VpinError, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
 CONV, POOL, FC, CONVMC, FCS = 0, 1, 2, 3, 4
+ORDER_INTERLEAVED = 1  # VPIN_NET_ORDER_INTERLEAVED
 VERSIONS = ("A", "B", "C", "D", "E")
 _GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
@@ -38,13 +39,21 @@ class Config:
         self.layers.append(l)
         return l
 
-    def conv(self, filt, pad=0, stride=1):
-        """filt: fh x fw ints below 2^128"""
+    def conv(self, filt, pad=0, stride=1, sum_table=None, repeat=1, interleaved=False):
+        """filt: fh x fw ints below 2^128.  What the reference's LeNet adds: sum_table, sum_out x C bytes (non-zero = connected): the
+        channel sums in front of the layer; repeat: the planes handed to the call that many times over, each under its own key;
+        interleaved: the planes as (0, c1), (0, c2), (1, c1), .. instead of all c1 and then all c2"""
         filt = [[int(v) for v in row] for row in filt]
         buf = np.frombuffer(b"".join(v.to_bytes(16, "little") for row in filt for v in row), dtype=np.uint8).copy()
         self._keep.append(buf)
         l = self._add(CONV)
         l.fh, l.fw, l.pad, l.stride, l.filter_le16 = len(filt), len(filt[0]), pad, stride, buf.ctypes.data
+        l.repeat, l.plane_order = 0 if repeat == 1 else repeat, ORDER_INTERLEAVED if interleaved else 0  # all zero: a layer as before
+        if sum_table is not None:
+            t = np.ascontiguousarray(np.asarray(sum_table) != 0, dtype=np.uint8)
+            assert t.ndim == 2
+            self._keep.append(t)
+            l.sum_table, l.sum_out = t.ctypes.data, t.shape[0]
         return self
 
     def convmc(self, w, connect=None, pad=0, stride=1, bias=None):
@@ -68,9 +77,9 @@ class Config:
             l.bias = b.ctypes.data
         return self
 
-    def pool(self, k, stride, scale):
+    def pool(self, k, stride, scale, interleaved=False):
         l = self._add(POOL)
-        l.k, l.stride = k, stride
+        l.k, l.stride, l.plane_order = k, stride, ORDER_INTERLEAVED if interleaved else 0
         l.scale_le16[:] = list(int(scale).to_bytes(16, "little"))
         return self
 
@@ -146,6 +155,20 @@ def cnn_config(version, nb_log=24, golden=None):
     return cfg
 
 
+def from_lenet(lenet_cfg):
+    """the reference's LeNet (a vpin_amd.lenet.Config) as a layer list (vpin_lenet_as_net): seven layers, layer i is label L(i + 1),
+    with the rounds R1 .. R7 and their max_giant.  What lenet.run computes on lenet_cfg, run computes on the result byte for byte
+    with the same keys and bias r -- and so do run(batch=..), serve and Server.  The arrays stay lenet_cfg's, which is kept alive"""
+    layers = (NetLayer * 7)()
+    ones = np.zeros(max(1, int(lenet_cfg.c.n2)), np.uint8)
+    out = NetCfg()
+    _chk(lib().vpin_lenet_as_net(C.byref(lenet_cfg.c), layers, ones.ctypes.data_as(C.c_void_p), C.byref(out)), "vpin_lenet_as_net")
+    cfg = Config(out.C, out.H, out.W, out.prf_bytes)
+    cfg.layers = [NetLayer.from_buffer_copy(l) for l in layers]
+    cfg._keep += [lenet_cfg, ones]
+    return cfg
+
+
 def lenet5_config(conv1, b1, conv2, b2, fc, bfc, fc1, bfc1, fc2, bfc2, rounds, prf_bytes=13):
     """the architecture of the reference's src/accuracy/train_test_lenet5.py over a 1 x 32 x 32 input, every weight signed and every
     weighted layer biased: CONVMC 1 -> 6 (f 5), pool 2 / 2, CONVMC 6 -> 16 (f 5), pool 2 / 2, FCS 400 -> 120, FCS 120 -> 84,
@@ -197,6 +220,12 @@ class Trace(inference.Trace):
         """image b's label: what label() is for that image run alone"""
         h = C.c_void_p()
         _chk(lib().vpin_net_trace_image_label(self.h, b, C.byref(h)), "vpin_net_trace_image_label")
+        return self._borrowed(h)
+
+    def image_layer(self, b, i):
+        """image b's share of layer i's call: what layer(i) is for that image run alone (LeNet: its label L(i + 1))"""
+        h = C.c_void_p()
+        _chk(lib().vpin_net_trace_image_layer(self.h, b, i, C.byref(h)), "vpin_net_trace_image_layer")
         return self._borrowed(h)
 
     def image_instances(self, b):
