@@ -91,6 +91,10 @@ unsigned long long vpin_ctx_row_table_rows(vpin_ctx* ctx);
 /* row chunks the bucket method (vpin_hyrax_commit_pippenger, VPIN_MSM_PIPPENGER) has launched on this context: a commitment
  * whose digit buffer would pass 2 GiB takes its rows in several (the 2^14 x 2^15 polynomials of a 2^25-constraint instance: 15) */
 unsigned long long vpin_ctx_pip_row_chunks(vpin_ctx* ctx);
+/* operations of the last vpin_gadget_point_mult_dev call on this context whose witness the step-by-step kernel wrote
+ * (gd_mult_witness_kernel): those the batched-inversion kernel flagged because a denominator or a Z vanished, or all N
+ * under VPIN_WITNESS_LITERAL.  0 for a batch of honest inputs: lets a test see which kernel produced a witness. */
+unsigned long long vpin_ctx_witness_redo_ops(vpin_ctx* ctx);
 /* the context's device memory pool: out = {bytes obtained from the driver and still held (handles + temporaries + cached
  * blocks), bytes of those sitting in the free lists (reusable by the next proof), blocks}.  What bench.py's hbm_breakdown and a
  * service's admission control are made of. */

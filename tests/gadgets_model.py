@@ -26,7 +26,8 @@ assert int.from_bytes(bytes(A_PD_BYTES), "little") == E2_A
 
 def inv(x):
     """dalek Scalar::invert: x^(q-2); 0 -> 0"""
-    return pow(x % Q, Q - 2, Q)
+    x %= Q
+    return pow(x, -1, Q) if x else 0  # q is prime: the same value as pow(x, Q - 2, Q), at a tenth of the time
 
 
 def e2_add(P1, P2):
@@ -75,6 +76,25 @@ def synthetic_points(seed, count):
 
 # ------------------------------------------------------------------------------------------------
 
+def point_add_assignment(ops):
+    """(vars_para, vars_input, vars) of build_point_add alone: point_addition.rs:207-222, no matrices."""
+    num_vars = 15 * len(ops) + 1
+    vars_input = [0] * num_vars
+    for i, (px, py, rx, ry, rz) in enumerate(ops):
+        c = inv(rx - px)
+        s1 = (ry - py) * c % Q
+        s2 = s1 * s1 % Q
+        t1 = (s2 - px - rx) * (1 - rz) % Q
+        t2 = px * rz % Q
+        x3 = (t1 + t2) % Q
+        s3 = s1 * (px - x3) % Q
+        t3 = (s3 - py) * (1 - rz) % Q
+        t4 = py * rz % Q
+        y3 = (t3 + t4) % Q
+        vars_input[15 * i:15 * i + 15] = [c, rx % Q, px % Q, ry % Q, py % Q, rz % Q, s1, s2, s3, t1, t2, t3, t4, x3, y3]
+    return [0] * num_vars, vars_input, list(vars_input)
+
+
 def build_point_add(ops):
     """ops: list of (px, py, rx, ry, rz) ints.  point_addition.rs:67-327."""
     N = len(ops)
@@ -96,22 +116,9 @@ def build_point_add(ops):
         C.append((r + 7, v + 11, one))
         A.append((r + 8, v + 4, one)); B.append((r + 8, v + 5, one)); C.append((r + 8, v + 12, one))
         A.append((r + 9, v + 11, one)); A.append((r + 9, v + 12, one)); B.append((r + 9, nv, one)); C.append((r + 9, v + 14, one))
-    vars_input = [0] * num_vars
-    for i, (px, py, rx, ry, rz) in enumerate(ops):
-        c = inv(rx - px)
-        s1 = (ry - py) * c % Q
-        s2 = s1 * s1 % Q
-        t1 = (s2 - px - rx) * (1 - rz) % Q
-        t2 = px * rz % Q
-        x3 = (t1 + t2) % Q
-        s3 = s1 * (px - x3) % Q
-        t3 = (s3 - py) * (1 - rz) % Q
-        t4 = py * rz % Q
-        y3 = (t3 + t4) % Q
-        vars_input[15 * i:15 * i + 15] = [c, rx % Q, px % Q, ry % Q, py % Q, rz % Q, s1, s2, s3, t1, t2, t3, t4, x3, y3]
-    vars_para = [0] * num_vars
+    vars_para, vars_input, vars_all = point_add_assignment(ops)
     return dict(num_cons=num_cons, num_vars=num_vars, num_inputs=num_inputs, A=A, B=B, C=C,
-                vars_para=vars_para, vars_input=vars_input, vars=list(vars_input), inputs=[])
+                vars_para=vars_para, vars_input=vars_input, vars=vars_all, inputs=[])
 
 
 def _pa(bx, by, bz, ax, ay):
@@ -137,6 +144,46 @@ def _pd(ax, ay, a):
     t2 = s1 * (ax - dx) % Q
     dy = (t2 - ay) % Q
     return dx, dy, t1, t2, s1, s2, c
+
+
+def point_mult_assignment(ops, n=128):
+    """(vars_para, vars_input, vars) of build_point_mult alone: point_mult.rs:414-500, no matrices."""
+    ov = n + 10 + n * 26
+    num_vars = ov * len(ops) + 1
+    vars_para, vars_input = [0] * num_vars, [0] * num_vars
+    for j, (w, px, py) in enumerate(ops):
+        v0 = ov * j
+        w &= (1 << 128) - 1
+        bits = [(w >> i) & 1 for i in range(n)]
+        ax_prev, ay_prev = px % Q, py % Q
+        bx_prev, by_prev, bz_prev = 0, 0, 1
+        vars_para[v0 + n] = w % Q
+        vi = vars_input
+        vi[v0 + n + 1] = ax_prev; vi[v0 + 2 * n + 2] = ay_prev
+        vi[v0 + 3 * n + 3] = 0; vi[v0 + 4 * n + 4] = 0; vi[v0 + 5 * n + 5] = 1
+        vi[v0 + 10 * n + 8] = px % Q; vi[v0 + 10 * n + 9] = py % Q
+        for i in range(n):
+            cx, cy, c_pa, s1_pa, s2_pa, s3_pa, t1_pa, t2_pa, t3_pa, t4_pa = _pa(bx_prev, by_prev, bz_prev, ax_prev, ay_prev)
+            dx, dy, t1_pd, t2_pd, s1_pd, s2_pd, c_pd = _pd(ax_prev, ay_prev, E2_A)
+            b = bits[i]
+            z1 = cx * b % Q; z2 = bx_prev * (1 - b) % Q; bx = (z1 + z2) % Q
+            z3 = cy * b % Q; z4 = by_prev * (1 - b) % Q; by = (z3 + z4) % Q
+            bz = bz_prev * (1 - b) % Q
+            vi[v0 + i] = b
+            vi[v0 + n + 2 + i] = dx; vi[v0 + 2 * n + 3 + i] = dy
+            vi[v0 + 3 * n + 4 + i] = bx; vi[v0 + 4 * n + 5 + i] = by; vi[v0 + 5 * n + 6 + i] = bz
+            vi[v0 + 6 * n + 6 + i] = cx; vi[v0 + 7 * n + 6 + i] = cy
+            vi[v0 + 8 * n + 6 + i] = dx; vi[v0 + 9 * n + 6 + i] = dy
+            vi[v0 + 10 * n + 10 + i] = c_pa; vi[v0 + 11 * n + 10 + i] = s1_pa; vi[v0 + 12 * n + 10 + i] = s2_pa
+            vi[v0 + 13 * n + 10 + i] = s3_pa; vi[v0 + 14 * n + 10 + i] = t1_pa; vi[v0 + 15 * n + 10 + i] = t2_pa
+            vi[v0 + 16 * n + 10 + i] = t3_pa; vi[v0 + 17 * n + 10 + i] = t4_pa
+            vi[v0 + 18 * n + 10 + i] = c_pd; vi[v0 + 19 * n + 10 + i] = t1_pd; vi[v0 + 20 * n + 10 + i] = s1_pd
+            vi[v0 + 21 * n + 10 + i] = s2_pd; vi[v0 + 22 * n + 10 + i] = t2_pd
+            vi[v0 + 23 * n + 10 + i] = z1; vi[v0 + 24 * n + 10 + i] = z2
+            vi[v0 + 25 * n + 10 + i] = z3; vi[v0 + 26 * n + 10 + i] = z4
+            ax_prev, ay_prev, bx_prev, by_prev, bz_prev = dx, dy, bx, by, bz
+        vi[v0 + 10 * n + 6] = bx_prev; vi[v0 + 10 * n + 7] = by_prev
+    return vars_para, vars_input, [(a + b) % Q for a, b in zip(vars_para, vars_input)]
 
 
 def build_point_mult(ops, n=128):
@@ -197,40 +244,7 @@ def build_point_mult(ops, n=128):
         A.append((r0 + oc - 2, v0 + 10 * n + 6, one)); A.append((r0 + oc - 2, v0 + 3 * n + 3 + n, m1)); B.append((r0 + oc - 2, nv, one))
         A.append((r0 + oc - 1, v0 + 10 * n + 7, one)); A.append((r0 + oc - 1, v0 + 4 * n + 4 + n, m1)); B.append((r0 + oc - 1, nv, one))
 
-    vars_para, vars_input = [0] * num_vars, [0] * num_vars
-    for j, (w, px, py) in enumerate(ops):
-        v0 = ov * j
-        w &= (1 << 128) - 1
-        bits = [(w >> i) & 1 for i in range(n)]
-        ax_prev, ay_prev = px % Q, py % Q
-        bx_prev, by_prev, bz_prev = 0, 0, 1
-        vars_para[v0 + n] = w % Q
-        vi = vars_input
-        vi[v0 + n + 1] = ax_prev; vi[v0 + 2 * n + 2] = ay_prev
-        vi[v0 + 3 * n + 3] = 0; vi[v0 + 4 * n + 4] = 0; vi[v0 + 5 * n + 5] = 1
-        vi[v0 + 10 * n + 8] = px % Q; vi[v0 + 10 * n + 9] = py % Q
-        for i in range(n):
-            cx, cy, c_pa, s1_pa, s2_pa, s3_pa, t1_pa, t2_pa, t3_pa, t4_pa = _pa(bx_prev, by_prev, bz_prev, ax_prev, ay_prev)
-            dx, dy, t1_pd, t2_pd, s1_pd, s2_pd, c_pd = _pd(ax_prev, ay_prev, E2_A)
-            b = bits[i]
-            z1 = cx * b % Q; z2 = bx_prev * (1 - b) % Q; bx = (z1 + z2) % Q
-            z3 = cy * b % Q; z4 = by_prev * (1 - b) % Q; by = (z3 + z4) % Q
-            bz = bz_prev * (1 - b) % Q
-            vi[v0 + i] = b
-            vi[v0 + n + 2 + i] = dx; vi[v0 + 2 * n + 3 + i] = dy
-            vi[v0 + 3 * n + 4 + i] = bx; vi[v0 + 4 * n + 5 + i] = by; vi[v0 + 5 * n + 6 + i] = bz
-            vi[v0 + 6 * n + 6 + i] = cx; vi[v0 + 7 * n + 6 + i] = cy
-            vi[v0 + 8 * n + 6 + i] = dx; vi[v0 + 9 * n + 6 + i] = dy
-            vi[v0 + 10 * n + 10 + i] = c_pa; vi[v0 + 11 * n + 10 + i] = s1_pa; vi[v0 + 12 * n + 10 + i] = s2_pa
-            vi[v0 + 13 * n + 10 + i] = s3_pa; vi[v0 + 14 * n + 10 + i] = t1_pa; vi[v0 + 15 * n + 10 + i] = t2_pa
-            vi[v0 + 16 * n + 10 + i] = t3_pa; vi[v0 + 17 * n + 10 + i] = t4_pa
-            vi[v0 + 18 * n + 10 + i] = c_pd; vi[v0 + 19 * n + 10 + i] = t1_pd; vi[v0 + 20 * n + 10 + i] = s1_pd
-            vi[v0 + 21 * n + 10 + i] = s2_pd; vi[v0 + 22 * n + 10 + i] = t2_pd
-            vi[v0 + 23 * n + 10 + i] = z1; vi[v0 + 24 * n + 10 + i] = z2
-            vi[v0 + 25 * n + 10 + i] = z3; vi[v0 + 26 * n + 10 + i] = z4
-            ax_prev, ay_prev, bx_prev, by_prev, bz_prev = dx, dy, bx, by, bz
-        vi[v0 + 10 * n + 6] = bx_prev; vi[v0 + 10 * n + 7] = by_prev
-    vars_all = [(a + b) % Q for a, b in zip(vars_para, vars_input)]
+    vars_para, vars_input, vars_all = point_mult_assignment(ops, n)
     return dict(num_cons=num_cons, num_vars=num_vars, num_inputs=num_inputs, A=A, B=B, C=C,
                 vars_para=vars_para, vars_input=vars_input, vars=vars_all, inputs=[E2_A])
 

@@ -837,6 +837,13 @@ class Context:
         L.vpin_ctx_strip_rows_taken.restype = C.c_ulonglong
         return int(L.vpin_ctx_strip_rows_taken(self.h))
 
+    def witness_redo_ops(self):
+        """operations of the last gadget_point_mult_dev call that the step-by-step witness kernel wrote (vpin_ctx_witness_redo_ops)"""
+        L = lib()
+        L.vpin_ctx_witness_redo_ops.argtypes = [C.c_void_p]
+        L.vpin_ctx_witness_redo_ops.restype = C.c_ulonglong
+        return int(L.vpin_ctx_witness_redo_ops(self.h))
+
     def set_shared_device(self, on=True):
         """other contexts prove on this device concurrently: leave them a share of every CU"""
         _chk(lib().vpin_ctx_set_shared_device(self.h, 1 if on else 0), "vpin_ctx_set_shared_device")

@@ -795,6 +795,7 @@ int vpin_gadget_point_mult_dev(vpin_ctx* c, const uint8_t* weights_le16, const u
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // caller buffers
   if (e != hipSuccess) { set_last_error("vpin_gadget_point_mult_dev", e); vpin_dev_instance_free(c, g); return VPIN_EHIP; }
+  c->witness_redo_ops = literal_only ? N : n_redo;
   *out = g;
   return VPIN_OK;
 }
