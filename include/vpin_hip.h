@@ -689,6 +689,15 @@ int vpin_conv_trace_instances(vpin_ctx* ctx, const vpin_conv_trace* t, vpin_dev_
  * (+ normalisation, outputs to the host)  [2] PRF (HMAC-SHA256, host team)  [3] RLC sums  [4] host tail  [5] total; a stage the
  * layer does not have (pooling: PRF, RLC) reads 0 */
 void vpin_enc_conv_last_timings(double out[8]);
+/* (ABI 9) Which units made the last encrypted-layer call on this thread answer VPIN_ESHAPE: the planes p of vpin_enc_conv2d and
+ * vpin_enc_avgpool2d, the groups g of vpin_enc_conv2d_mc[_bias], the rows p of vpin_enc_fc[_signed] (for these the folded weight
+ * that does not fit 128 bits and the accumulator rule of the chain included).  Ascending, no duplicates: at most cap of them
+ * into units, *n is their number.  The code and the text of the call stay the first hit's; the scan that refuses runs to its end
+ * and names every unit that breaks ITS rule.  A call that fails at one stage names that stage's units only: the later stages were
+ * not reached, so a unit not named may still break a later rule.  Every layer entry point clears the list on entry, and it stays
+ * empty after VPIN_OK and after VPIN_EVERIFY, VPIN_EINVAL, VPIN_EHIP and VPIN_ENOMEM, which are not a unit's doing or cannot be
+ * attributed here.  VPIN_EINVAL for n = NULL, or units = NULL with cap > 0 */
+int vpin_enc_last_refusals(uint32_t* units, size_t cap, size_t* n);
 
 /* The fully connected layer: FCLayer (flag 1) with the type-1 branch of rLCL / rLCR of src/LeNet/Server.py, where the random
  * scalars fold into the WEIGHTS.  P rows of K input points (the c1 vector, then the c2 vector), one K x N matrix of u32 weights
@@ -1097,6 +1106,50 @@ int vpin_net_trace_image_layer(const vpin_net_trace* t, size_t b, size_t layer, 
 /* image b's label as vpin_net_trace_instances */
 int vpin_net_trace_image_instances(vpin_ctx* ctx, const vpin_net_trace* t, size_t b, vpin_dev_instance** mult_out,
                                    vpin_dev_instance** add_out);
+/* ---- images that leave a running batch (ABI 9) --------------------------------------------------------------------------------
+ * vpin_net_infer_isolated is vpin_net_infer_multi plus status[B]: an image that makes a layer refuse leaves the batch and the
+ * others go on.  An image is named by its SLOT b of the batch handed in, for its whole life: keys32, bias_r_le32 and key_of_image
+ * stay indexed by slot, so a survivor's bytes depend only on its slot, never on who else is or was in the batch.
+ *   a refusal   a layer call that answers VPIN_ESHAPE with units in vpin_enc_last_refusals: the units are mapped to images (plane
+ *               / the planes one image hands to the call: 2 C * repeat for CONV behind its sums and repeat, 2 C for POOL; group /
+ *               2; row / 2), status[b] = {VPIN_ESHAPE, layer, -1, the text the batch would have failed with}, the images are
+ *               removed from the step's input and the call runs again over the survivors, the biases encrypted again with the
+ *               same r.  Every repeat removes an image, so a step runs at most B times.  The list names the units of the stage
+ *               that refused: an image that breaks a later rule is found by the repeat
+ *   a bad point an input or reply point that a layer's load refuses (VPIN_EINVAL, "a coordinate is not below q", ".. is not on
+ *               the curve E2"): the images that own such a point are found with vpin_e2_pack per image and leave the same way
+ *               with the code VPIN_EINVAL
+ *   a drop      inside the round callback (and only there, on its thread) vpin_net_round_images gives the slots of the cnt =
+ *               n * per values at hand, position after position, and vpin_net_round_drop_images takes images out of the batch
+ *               after the round: status[b] = {code, layer, round, text}, what the callback wrote for them is ignored.
+ *               VPIN_EINVAL for a slot that is not at hand, a slot named twice, code = VPIN_OK, a run that is not isolated
+ *               (vpin_net_round_images answers in every run of the vpin_net_infer family)
+ *   the end     status[b].code = VPIN_OK for the survivors.  Nobody left: VPIN_ESHAPE, "vpin_net_infer_isolated: no image is
+ *               left", *out = NULL, every status written
+ * NOT isolated, the batch fails as vpin_net_infer_multi's: VPIN_EVERIFY, VPIN_EHIP, VPIN_ENOMEM, a failing round callback, a
+ * VPIN_ESHAPE whose list is empty and a VPIN_EINVAL that no image's point explains (the server's keys, weights or bias).
+ * The trace: vpin_net_trace_images stays B; vpin_net_trace_layer is the call that succeeded, with P of the images in it, which
+ * vpin_net_trace_layer_images names (slots ascending, borrowed); vpin_net_trace_image_layer, _image_label and _image_instances
+ * keep taking the slot b and answer VPIN_ESHAPE, "..: image b left the batch at layer L", for an image that is not in that layer
+ * (the label: that did not stay to the end; ".. at the last round" for one the last round dropped, which every layer still
+ * holds); vpin_net_trace_label, _instances and _result hold the survivors in slot order.
+ * With no refusal and no drop the run and the trace are byte for byte vpin_net_infer_multi's. */
+typedef struct vpin_net_image_status {
+  int code;   /* VPIN_OK: the image stayed to the end */
+  int layer;  /* the layer whose call refused it, or whose round dropped it */
+  int round;  /* -1: a layer's refusal */
+  char text[256];
+} vpin_net_image_status;
+int vpin_net_infer_isolated(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const uint8_t* hx,
+                            const uint8_t* hy, size_t n_pub, const uint32_t* key_of_image, const uint8_t* keys32, size_t n_keys,
+                            const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user,
+                            vpin_net_image_status* status, vpin_net_trace** out);
+int vpin_net_round_images(const uint32_t** slots, size_t* n);
+int vpin_net_round_drop_images(const uint32_t* slots, size_t n, int code, const char* text);
+int vpin_net_trace_layer_images(const vpin_net_trace* t, size_t layer, const uint32_t** slots, size_t* n);
+/* what the last vpin_net_infer_isolated on this thread did: images a layer refused, images dropped in a round, layer calls repeated */
+void vpin_net_last_isolation(uint64_t out[3]);
 /* The ready-made client of both drivers, for n_rounds rounds (LeNet: 7): owns sk, the tables of G and H = sk * G, a
  * discrete-log table of nb baby steps, one range max_giant per round and the queue of n_r encryption randomness values (32 bytes
  * each, one per encrypt call in order).  vpin_net_client_round is a vpin_lenet_round_fn over vpin_e2_client_round with user =
@@ -1246,17 +1299,35 @@ int vpin_net_serve_batch(vpin_ctx* ctx, const vpin_net_cfg* cfg, vpin_wire* w, s
  * status[i], for wire i: code VPIN_OK and stage VPIN_NET_STAGE_DONE for a client served to DONE; otherwise the code, the text and
  * the stage it left at: VPIN_NET_STAGE_ADMISSION, the round's number, or VPIN_NET_STAGE_SERVER for the server's own failure.
  * first_image and n_images are its slots (0, 0 when it was not admitted).
- * NOT isolated: a client whose well-formed ciphertexts drive a layer into a refusal (an accumulator that is the identity, an s_k
- * that does not fit) still fails the whole batch; that needs isolation per image inside the layers.
+ * Isolation (ABI 9, vpin_net_server_set_isolation; off by default, and off is everything above, byte for byte): a client whose
+ * well-formed ciphertexts drive a layer into a refusal (an identity point the wire format allows, an accumulator that is the
+ * identity, an s_k that does not fit) fails the whole batch when it is off.  When it is on the call runs vpin_net_infer_isolated:
+ *   a refusal   the image leaves the batch inside the driver and the layer runs again over the others.  The schedule of
+ *               vpin_net_client_run fixes cnt = B_i * n per round, so on the wire the unit that leaves is the CLIENT: at the next
+ *               round a client that lost an image is dropped with all its images, gets ERROR with the layer's text, and its
+ *               status holds the layer's code and text and the stage VPIN_NET_STAGE_LAYER
+ *   a drop      a client dropped in a round leaves the batch at that round (vpin_net_round_drop_images): the later layer calls
+ *               run over the images of the others alone, and vpin_net_trace_layer_images names them
+ *   positions   a client keeps its slots [first_image, first_image + n_images) for its status, its keys and its bias r; where its
+ *               images stand in the batch at hand is worked out again before every round.  A surviving client sees exactly the
+ *               frames it would see alone in its slots
+ *   nobody left VPIN_ECOMM, *out = NULL, every status written
+ * vpin_net_server_stats_isolation: out = {images of clients a layer refused, images compacted away after a drop on the wire,
+ * layer calls repeated}, summed over the server's calls.  Still NOT isolated: VPIN_EVERIFY, VPIN_EHIP, VPIN_ENOMEM, and a refusal
+ * that is the server's own keys' doing (a folded weight that does not fit under a slot's key hits that slot whoever sits in it;
+ * one that no image explains fails the batch).
  * VPIN_EINVAL before anything is read: a null argument, n_wires = 0 or > max_batch, the same wire twice, n_keys != max_batch * k,
  * n_bias_r != max_batch * r.  All waits are the wires' own timeout_ms; admission reads the wires one after another. */
 typedef struct vpin_net_server vpin_net_server;
 int vpin_net_server_create(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t max_batch, vpin_net_server** out);
 void vpin_net_server_free(vpin_net_server* s);
 int vpin_net_server_stats(const vpin_net_server* s, uint64_t out[5]);
+int vpin_net_server_set_isolation(vpin_net_server* s, int on);
+int vpin_net_server_stats_isolation(const vpin_net_server* s, uint64_t out[3]);
 #define VPIN_NET_STAGE_DONE (-1)
 #define VPIN_NET_STAGE_ADMISSION (-2)
 #define VPIN_NET_STAGE_SERVER (-3)
+#define VPIN_NET_STAGE_LAYER (-4) /* isolation: a layer refused one of the client's images */
 typedef struct vpin_net_peer_status {
   int code;
   int stage;

@@ -1,6 +1,6 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
 the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
-[--batch 1,2,4,..] [--clients 1,2,4,..]
+[--batch 1,2,4,..] [--clients 1,2,4,..] [--isolation] [--refuse 1]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
@@ -26,7 +26,12 @@ process over socketpairs (at most 8 clients: 9 contexts), three ways that altern
 endpoint's start to the last one's return: the connection's set-up in, the clients' own tables and the server object out) and of
 every layer and every round (the server's host clock): median (minimum .. maximum) of R = 11 warm runs by default.  Every client's
 values of the first run are checked against the plaintext model.  Then two side timings: vpin_e2_base_create of G and of an H,
-and vpin_e2_encrypt_keyed against vpin_e2_encrypt with a ready table at cnt = 236, 944 and 7552.  No proofs in this mode."""
+and vpin_e2_encrypt_keyed against vpin_e2_encrypt with a ready table at cnt = 236, 944 and 7552.  No proofs in this mode.
+--isolation: way (a)'s server with vpin_net_server_set_isolation on (nothing refuses: the cost of the slot bookkeeping alone).
+--clients 2,4,.. --refuse 1: what a refusal costs.  Per K two runs of way (a) on an isolating server alternate: all K clients good,
+and the LAST client a peer by hand whose c1 points are all the identity, so that the first layer refuses its image, runs again over K - 1
+images, and the client is dropped at round 0 while the others finish (their values are checked against the plaintext model).
+Printed: the whole exchange and the first layer's time of both, ms per call, median (minimum .. maximum)."""
 import os
 import socket
 import statistics
@@ -56,6 +61,7 @@ BATCH = [int(b) for b in sys.argv[sys.argv.index("--batch") + 1].split(",")] if 
 CLIENTS = [int(b) for b in sys.argv[sys.argv.index("--clients") + 1].split(",")] if "--clients" in sys.argv else None
 REPS, NB_LOG = opt("--reps", 11 if WIRE or BATCH or CLIENTS else 5), opt("--nb", 24)
 PROOFS = "--no-proofs" not in sys.argv
+ISOLATION, REFUSE = "--isolation" in sys.argv, opt("--refuse", 0)
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
 SEED_C, SEED_P = bytes(range(64)), bytes((11 * i + 5) % 256 for i in range(64))
@@ -87,7 +93,7 @@ def main():
     assert counts == dict(want, rounds=len(giants))
     if BATCH or CLIENTS:
         plain = TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
-        (clients_mode if CLIENTS else batch_mode)(ctx, cfg, model, counts, giants, image, plain)
+        (refuse_mode if CLIENTS and REFUSE else clients_mode if CLIENTS else batch_mode)(ctx, cfg, model, counts, giants, image, plain)
         ctx.close()
         return
     keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
@@ -397,7 +403,7 @@ def clients_mode(ctx, cfg, model, counts, giants, image, plain):
                 queue += client_rs[b][pos:pos + c]
             pos += c
         schedK = VN.schedule(cfg, batch=K)
-        server = VN.Server(ctx, cfg, K)
+        server = VN.Server(ctx, cfg, K, isolation=ISOLATION)
         ways = {w: dict(whole=[], layers=[], rounds=[]) for w in "abc"}
         for rep in range(REPS + 1):
             # (a) one inference over K clients
@@ -493,6 +499,75 @@ def clients_mode(ctx, cfg, model, counts, giants, image, plain):
               (cnt, rng(tt[1:], 1), len(pubs), rng(tk[1:], 1), rng(t1[1:], 1)))
     base_h.free()
     base_g.free()
+    for c in cctx:
+        c.close()
+
+
+def refuse_mode(ctx, cfg, model, counts, giants, image, plain):
+    """--clients .. --refuse 1: way (a) on an isolating server, all clients good against the last one refused by the first layer"""
+    import wire_model as WM
+    from vpin_amd import wire as W
+    assert REFUSE == 1 and min(CLIENTS) >= 2 and max(CLIENTS) <= 8, "--refuse 1 with 2 .. 8 clients: somebody has to be left"
+    top = max(CLIENTS)
+    cctx = [vpin_amd.Context(0) for _ in range(top)]
+    sks = [(SK + 977 * k) % EL.ORDER for k in range(top)]
+    n, nr, size = len(cfg.layers), len(giants), image.size
+    k_keys, r_bias, r_client = counts["prf_keys"], counts["bias_r"], counts["encryptions"] - size
+    images = [np.roll(image, (b % 8, b // 8), axis=(0, 1)) for b in range(top)]
+    expect = [plain(model, im) for im in images]
+    keys = [NM.net_key(k_keys * b + i) for b in range(top) for i in range(k_keys)]
+    image_rs = [EL.splitmix_scalars(SEEDS["image_r"] + 0x1000 * b, size) for b in range(top)]
+    bias_rs = [r for b in range(top) for r in EL.splitmix_scalars(SEEDS["bias_r"] + 0x1000 * b, r_bias)]
+    client_rs = [EL.splitmix_scalars(SEEDS["client_r"] + 0x1000 * b, r_client) for b in range(top)]
+    sched1 = VN.schedule(cfg)
+    rng = lambda xs: "%9.2f (%8.2f .. %8.2f)" % (statistics.median(xs), min(xs), max(xs))
+
+    def peer(k, client, wire):  # HELLO, an INPUT whose every c1 point is the identity, then whatever the server says
+        c = cctx[k]
+        wire.send(W.HELLO, bytes(c.e2_pack(*c.e2_base_mul(client.base_g, [sks[k]])).reshape(-1)), cnt=1)
+        c1, c2 = client.encrypt(images[k].reshape(-1).astype(np.int64), image_rs[k])
+        packed = bytes(c.e2_pack(*[np.concatenate([a, b]) for a, b in zip(c1, c2)]).reshape(-1))
+        wire.send(W.INPUT, WM.pack(None) * size + packed[32 * size:], cnt=size)
+        return wire.recv()
+
+    for K in CLIENTS:
+        server = VN.Server(ctx, cfg, K, isolation=True)
+        runs = {w: dict(whole=[], layer0=[]) for w in ("good", "refused")}
+        for rep in range(REPS + 1):
+            for way in ("good", "refused"):
+                cl = [VN.Client(cctx[k], sks[k], 1 << NB_LOG, giants, client_rs[k]) for k in range(K)]
+                socks = [socket.socketpair() for _ in range(K)]
+                ws = [W.Wire.from_fds(a.fileno(), a.fileno(), 600000) for a, _ in socks]
+                wc = [W.Wire.from_fds(b.fileno(), b.fileno(), 600000) for _, b in socks]
+                last = (lambda: peer(K - 1, cl[K - 1], wc[K - 1])) if way == "refused" else (
+                    lambda: cl[K - 1].run(wc[K - 1], images[K - 1].reshape(-1), image_rs[K - 1], sched1))
+                t0 = time.perf_counter()
+                res = threads([lambda: (server.serve(ws, keys[:K * k_keys], bias_rs[:K * r_bias]), VN.timings(n))] +
+                              [lambda k=k: cl[k].run(wc[k], images[k].reshape(-1), image_rs[k], sched1) for k in range(K - 1)] + [last])
+                ms = (time.perf_counter() - t0) * 1e3
+                (trace, statuses), tm = res[0]
+                good = K - 1 if way == "refused" else K
+                assert [s["stage"] for s in statuses] == [VN.STAGE_DONE] * good + [VN.STAGE_LAYER] * (K - good), statuses
+                assert trace.layer_images(0) == list(range(good))
+                if rep == 0:
+                    for k in range(good):
+                        for r in range(nr):
+                            assert [int(a) for a in res[1 + k][1][r][0]] == expect[k][0][r], "client %d round %d" % (k, r)
+                else:
+                    runs[way]["whole"].append(ms)
+                    runs[way]["layer0"].append(tm["layers"][0])
+                trace.free()
+                for o in cl + ws + wc:
+                    o.free()
+                for a, b in socks:
+                    a.close(); b.close()
+        st = server.stats_isolation()
+        assert st == dict(images_refused=REPS + 1, images_compacted=0, layer_calls_repeated=REPS + 1), st
+        server.free()
+        print("K = %d clients on an isolating server; ms PER CALL, warm, median (min .. max) over %d runs, the two alternating" % (K, REPS))
+        print("%-44s %-34s %-34s" % ("", "all K good", "the last one refused at layer 0"))
+        print("%-44s %-34s %-34s" % ("layer 0 (with its repeat over K - 1 images)", rng(runs["good"]["layer0"]), rng(runs["refused"]["layer0"])))
+        print("%-44s %-34s %-34s" % ("the whole exchange", rng(runs["good"]["whole"]), rng(runs["refused"]["whole"])))
     for c in cctx:
         c.close()
 

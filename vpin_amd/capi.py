@@ -86,6 +86,11 @@ class WireRoundSpec(C.Structure):
     _fields_ = [("flags", C.c_int), ("shift_bits", C.c_int), ("cnt", C.c_size_t)]
 
 
+class NetImageStatus(C.Structure):
+    """vpin_net_image_status of include/vpin_hip.h"""
+    _fields_ = [("code", C.c_int), ("layer", C.c_int), ("round", C.c_int), ("text", C.c_char * 256)]
+
+
 class NetPeerStatus(C.Structure):
     """vpin_net_peer_status of include/vpin_hip.h"""
     _fields_ = [("code", C.c_int), ("stage", C.c_int), ("first_image", C.c_uint32), ("n_images", C.c_uint32), ("text", C.c_char * 256)]
@@ -275,6 +280,14 @@ def lib():
     L.vpin_net_infer_batch.argtypes = [vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.vpin_net_infer_multi.argtypes = ([vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp] +
                                        [vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)])
+    L.vpin_net_infer_isolated.argtypes = ([vp, C.POINTER(NetCfg), C.c_size_t] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp] +
+                                          [vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(NetImageStatus), C.POINTER(vp)])
+    L.vpin_net_round_images.argtypes = [C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_net_round_drop_images.argtypes = [vp, C.c_size_t, C.c_int, C.c_char_p]
+    L.vpin_net_trace_layer_images.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_net_last_isolation.restype = None
+    L.vpin_net_last_isolation.argtypes = [C.POINTER(C.c_uint64)]
+    L.vpin_enc_last_refusals.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vpin_net_trace_images.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.vpin_net_trace_image_label.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.vpin_net_trace_image_layer.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]
@@ -304,6 +317,8 @@ def lib():
     L.vpin_net_server_free.argtypes = [vp]
     L.vpin_net_server_free.restype = None
     L.vpin_net_server_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vpin_net_server_set_isolation.argtypes = [vp, C.c_int]
+    L.vpin_net_server_stats_isolation.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vpin_net_serve_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(NetPeerStatus), C.POINTER(vp)]
     L.vpin_net_client_run.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(WireRoundSpec), C.c_size_t]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
@@ -1478,6 +1493,16 @@ class Context:
         out = (C.c_double * 8)()
         lib().vpin_enc_conv_last_timings(out)
         return dict(zip(("validate", "conv", "prf", "rlc", "host_tail", "total"), out))
+
+    @staticmethod
+    def enc_last_refusals():
+        """the units (planes, groups, rows) that made the last encrypted-layer call on this thread answer VPIN_ESHAPE, ascending
+        (vpin_enc_last_refusals); empty after any other outcome"""
+        n = C.c_size_t()
+        _chk(lib().vpin_enc_last_refusals(None, 0, C.byref(n)), "vpin_enc_last_refusals")
+        units = (C.c_uint32 * max(1, n.value))()
+        _chk(lib().vpin_enc_last_refusals(units, n.value, C.byref(n)), "vpin_enc_last_refusals")
+        return [int(v) for v in units[:n.value]]
 
     # ---- the client side: ElGamal on E2 (vpin_amd.elgamal wraps these) ----
     @staticmethod

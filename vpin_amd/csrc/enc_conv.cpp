@@ -187,6 +187,14 @@ int emit_chain(const char* who, vpin_conv_trace* t, size_t* ai, PointBytes prod,
   return VPIN_OK;
 }
 
+static thread_local std::vector<uint32_t> g_refusals;  // ascending: every scan walks its units in order
+
+void clear_refusals() { g_refusals.clear(); }
+
+void note_refusal(size_t unit) {
+  if (g_refusals.empty() || g_refusals.back() != (uint32_t)unit) g_refusals.push_back((uint32_t)unit);
+}
+
 int team_size() { return (int)std::max(1.0, std::min(16.0, vpin::host_cpu_quota())); }
 
 }  // namespace enc
@@ -226,6 +234,7 @@ int vpin_e2_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint
 int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W,
                     const uint8_t* filter_le16, size_t fh, size_t fw, size_t pad, size_t stride, const uint8_t* keys32, int prf_bytes,
                     vpin_conv_trace** out) {
+  clear_refusals();
   if (out) *out = nullptr;
   if (!c || !px || !py || !pinf || !filter_le16 || !keys32 || !out) return fail(VPIN_EINVAL, "vpin_enc_conv2d: null argument");
   if (prf_bytes < 1 || prf_bytes > 16) return fail(VPIN_EINVAL, "vpin_enc_conv2d: prf_bytes must be in 1 .. 16");
@@ -236,6 +245,7 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
   Lap total, lap;
   std::unique_ptr<vpin_conv_trace> t(new (std::nothrow) vpin_conv_trace());
   if (!t) return VPIN_ENOMEM;
+  const char* no_flag = "vpin_enc_conv2d: a multiplication operand B'[k] is the identity (the witness format has no flag for it)";
   const size_t taps = g.taps(), nsum = taps + 1, per_plane = g.oh * g.ow, n_out = g.outputs();
   t->P = P; t->oh = g.oh; t->ow = g.ow;
 
@@ -264,9 +274,11 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
   for (size_t k = 0; k < taps; k++) memcpy(&w[k], filter_le16 + 16 * k, 16);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(team_size())
   for (long i = 0; i < (long)(P * nsum); i++) B[(size_t)i] = to_affine(jac_from_bytes(&sums[96 * (size_t)i]));
+  bool refused = false;
   for (size_t p = 0; p < P; p++)
     for (size_t k = 0; k < taps; k++)
-      if (B[p * nsum + k].inf) return fail(VPIN_ESHAPE, "vpin_enc_conv2d: a multiplication operand B'[k] is the identity (the witness format has no flag for it)");
+      if (B[p * nsum + k].inf) { note_refusal(p); refused = true; break; }
+  if (refused) return fail(VPIN_ESHAPE, no_flag);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(team_size())
   for (long i = 0; i < (long)(P * taps); i++) {
     const size_t p = (size_t)i / taps, k = (size_t)i % taps;
@@ -297,9 +309,14 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
     put_point(l, &t->left_x[32 * p], &t->left_y[32 * p]);
     t->left_inf[p] = l.inf ? 1 : 0;
     bool closes = false;
-    if ((rc = emit_chain("vpin_enc_conv2d", t.get(), &ai, prod, prefix, taps, left.at(p), &closes))) return rc;
+    if (emit_chain("vpin_enc_conv2d", t.get(), &ai, prod, prefix, taps, left.at(p), &closes)) {  // VPIN_ESHAPE, the same text for every plane
+      note_refusal(p);
+      refused = true;
+      ai = (p + 1) * (taps - 1);
+    }
     if (!closes) equal = false;
   }
+  if (refused) return VPIN_ESHAPE;
   tm[4] = lap();
   tm[5] = total();
   if (!equal) return fail(VPIN_EVERIFY, "vpin_enc_conv2d: the two sides of the random linear combination differ");
@@ -350,6 +367,13 @@ int vpin_conv_trace_instances(vpin_ctx* c, const vpin_conv_trace* t, vpin_dev_in
   rc = vpin_gadget_point_add_dev(c, t->a_px.data(), t->a_py.data(), t->a_rx.data(), t->a_ry.data(), t->a_rz.data(), t->n_add, add_out);
   if (rc && *mult_out) { vpin_dev_instance_free(c, *mult_out); *mult_out = nullptr; }
   return rc;
+}
+
+int vpin_enc_last_refusals(uint32_t* units, size_t cap, size_t* n) {
+  if (!n || (cap && !units)) return fail(VPIN_EINVAL, "vpin_enc_last_refusals: null argument");
+  *n = g_refusals.size();
+  for (size_t i = 0; i < g_refusals.size() && i < cap; i++) units[i] = g_refusals[i];
+  return VPIN_OK;
 }
 
 void vpin_enc_conv_last_timings(double out[8]) {

@@ -161,6 +161,12 @@ struct PointBytes {
 // only compared.  *closes: the last prefix equals left[0] (flag and both coordinates)
 int emit_chain(const char* who, vpin_conv_trace* t, size_t* ai, PointBytes prod, PointBytes prefix, size_t len, PointBytes left, bool* closes);
 
+// The units (planes, groups, rows) that break a VPIN_ESHAPE rule, for vpin_enc_last_refusals: per thread, like the error text.
+// Every layer entry point clears the list first; a scan that refuses notes every unit that breaks its rule and then returns the
+// first hit's code and text, so the list holds the units of the ONE stage that refused
+void clear_refusals();
+void note_refusal(size_t unit);
+
 struct Lap {
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   double operator()() {

@@ -73,6 +73,7 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
              const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32, int prf_bytes, vpin_conv_trace** out) {
   const std::string name(who);
   auto failed = [&](int code, const char* why) { return fail(code, (name + ": " + why).c_str()); };
+  clear_refusals();
   if (out) *out = nullptr;
   if (!c || !px || !py || !pinf || !weights || !keys32 || !out || (with_bias && (!bx || !by || !binf))) return failed(VPIN_EINVAL, "null argument");
   if (prf_bytes < 1 || prf_bytes > 16) return failed(VPIN_EINVAL, "prf_bytes must be in 1 .. 16");
@@ -103,9 +104,11 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
   if ((rc = d.conv_mc(g, groups, C, n_out, weights, p.connect.data(), p.top_bit.data(), t->out_x.data(), t->out_y.data(), t->out_inf.data())))
     return rc;
   std::vector<uint8_t> cx, cy;  // C, the first operands of the bias additions; the trace's output becomes C + bias
+  bool refused = false;  // a scan notes every group that breaks its rule; the code and the text are the first hit's
   if (with_bias) {
     for (size_t i = 0; i < n_o; i++)
-      if (t->out_inf[i]) return failed(VPIN_ESHAPE, "an addition accumulator C[t] is the identity (the witness format has no flag for it)");
+      if (t->out_inf[i]) { note_refusal(i / (n_out * per_plane)); refused = true; }
+    if (refused) return failed(VPIN_ESHAPE, "an addition accumulator C[t] is the identity (the witness format has no flag for it)");
     cx = t->out_x; cy = t->out_y;
     if ((rc = d.add_bias(b, groups, n_out, t->out_x.data(), t->out_y.data(), t->out_inf.data()))) return rc;
   }
@@ -142,8 +145,8 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
   // the tail: T_m = |w_m| * S_m and the prefixes of every chain on the device, then the equation and the two lists
   for (size_t q = 0; q < n_pairs; q++)
     for (size_t m = 0; m < p.chan[q % n_out].size() * taps; m++)
-      if (sinf[q * K + m])
-        return failed(VPIN_ESHAPE, "a multiplication operand B'[c][k] is the identity (the witness format has no flag for it)");
+      if (sinf[q * K + m]) { note_refusal(q / n_out); refused = true; }
+  if (refused) return failed(VPIN_ESHAPE, "a multiplication operand B'[c][k] is the identity (the witness format has no flag for it)");
   std::vector<uint8_t> tx(n_chain * 32), ty(n_chain * 32), tinf(n_chain), ax(n_chain * 32), ay(n_chain * 32), ainf(n_chain);
   if ((rc = vpin::mul_chain(c, tail, s.data(), n_pairs, K, tx.data(), ty.data(), tinf.data(), ax.data(), ay.data(), ainf.data()))) return rc;
   t->resize_lists();
@@ -166,9 +169,15 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
     memcpy(&t->left_x[32 * q], left.x, 32); memcpy(&t->left_y[32 * q], left.y, 32);
     t->left_inf[q] = *left.inf;
     bool closes = false;
-    if ((rc = emit_chain(who, t.get(), &ai, prod.at(q * K), prefix.at(q * K), len, left, &closes))) return rc;
+    const size_t chain_end = ai + len - 1;
+    if (emit_chain(who, t.get(), &ai, prod.at(q * K), prefix.at(q * K), len, left, &closes)) {  // VPIN_ESHAPE, one text for every pair
+      note_refusal(q / n_out);
+      refused = true;
+      ai = chain_end;
+    }
     if (!closes) equal = false;
   }
+  if (refused) return VPIN_ESHAPE;
   tm[4] = lap();
   tm[5] = total();
   if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");

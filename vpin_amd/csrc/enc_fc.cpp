@@ -42,6 +42,7 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
              vpin_conv_trace** out) {
   const std::string name(who);
   auto failed = [&](int code, const char* why) { return fail(code, (name + ": " + why).c_str()); };
+  clear_refusals();
   if (out) *out = nullptr;
   if (!c || !px || !py || !pinf || !weights || !bx || !by || !binf || !keys32 || !out) return failed(VPIN_EINVAL, "null argument");
   if (prf_bytes < 1 || prf_bytes > 16) return failed(VPIN_EINVAL, "prf_bytes must be in 1 .. 16");
@@ -68,8 +69,10 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
   t->left_x.resize(P * 32); t->left_y.resize(P * 32); t->left_inf.resize(P);
   std::vector<uint8_t> cx(n_out * 32), cy(n_out * 32), cinf(n_out);
   if ((rc = d.matvec(P, K, N, weights, is_signed, cx.data(), cy.data(), cinf.data()))) return rc;
+  bool refused = false;  // a scan notes every row that breaks its rule; the code and the text are the first hit's
   for (size_t i = 0; i < n_out; i++)
-    if (cinf[i]) return failed(VPIN_ESHAPE, "an addition accumulator C[j] is the identity (the witness format has no flag for it)");
+    if (cinf[i]) { note_refusal(i / N); refused = true; }
+  if (refused) return failed(VPIN_ESHAPE, "an addition accumulator C[j] is the identity (the witness format has no flag for it)");
 #pragma omp parallel for schedule(static) num_threads(team_size())
   for (long li = 0; li < (long)n_out; li++) {
     const size_t i = (size_t)li, ai = (i / N) * adds_per_row + i % N;
@@ -96,25 +99,29 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
   // s_k = pos_k - neg_k over the positive and the negative weights; the gadget's weight is a u128, so the sign goes into the
   // point: S_k = X[k] for s_k >= 0 and -X[k] = (x, q - y) for s_k < 0
   std::vector<size_t> minus_s;  // the m = p * K + k with s_k < 0
-  for (size_t p = 0; p < P; p++)
-    for (size_t k = 0; k < K; k++) {
+  for (size_t p = 0; p < P; p++) {
+    bool fits = true;
+    for (size_t k = 0; k < K && fits; k++) {
       u128 pos = 0, neg = 0;
-      for (size_t j = 0; j < N; j++) {
+      for (size_t j = 0; j < N && fits; j++) {
         u128 rj;
         uint32_t w;
         memcpy(&rj, &r[16 * (p * N + j)], 16);
         memcpy(&w, (const uint8_t*)weights + 4 * (k * N + j), 4);
         const bool minus = is_signed && (w >> 31);  // |INT32_MIN| = 2^31 as 0 - w in unsigned arithmetic
-        if (!mul_add_u128(minus ? neg : pos, rj, minus ? 0u - w : w))
-          return failed(VPIN_ESHAPE, "a folded weight sum_j r_j * W[k][j] does not fit 128 bits");
+        fits = mul_add_u128(minus ? neg : pos, rj, minus ? 0u - w : w);
       }
       const size_t m = p * K + k;
       const u128 s = pos >= neg ? pos - neg : neg - pos;
       memcpy(&t->m_w[16 * m], &s, 16);
       if (pos < neg) minus_s.push_back(m);
     }
+    if (!fits) { note_refusal(p); refused = true; }
+  }
+  if (refused) return failed(VPIN_ESHAPE, "a folded weight sum_j r_j * W[k][j] does not fit 128 bits");
   for (size_t i = 0; i < n_in; i++)
-    if (pinf[i]) return failed(VPIN_ESHAPE, "a multiplication operand X[k] is the identity (the witness format has no flag for it)");
+    if (pinf[i]) { note_refusal(i / K); refused = true; }
+  if (refused) return failed(VPIN_ESHAPE, "a multiplication operand X[k] is the identity (the witness format has no flag for it)");
   memcpy(t->m_px.data(), px, n_in * 32);
   memcpy(t->m_py.data(), py, n_in * 32);
   for (const size_t m : minus_s) {
@@ -138,9 +145,13 @@ int fc_layer(const char* who, vpin_ctx* c, const uint8_t* px, const uint8_t* py,
     t->left_inf[p] = l.inf ? 1 : 0;
     size_t ai = p * adds_per_row + N;  // after the row's bias additions
     bool closes = false;
-    if ((rc = emit_chain(who, t.get(), &ai, prod.at(p * K), prefix.at(p * K), K, left.at(p), &closes))) return rc;
+    if (emit_chain(who, t.get(), &ai, prod.at(p * K), prefix.at(p * K), K, left.at(p), &closes)) {  // VPIN_ESHAPE, one text for every row
+      note_refusal(p);
+      refused = true;
+    }
     if (!closes) equal = false;
   }
+  if (refused) return VPIN_ESHAPE;
   tm[4] = lap();
   tm[5] = total();
   if (!equal) return failed(VPIN_EVERIFY, "the two sides of the random linear combination differ");
@@ -178,6 +189,7 @@ int vpin_enc_fc_signed(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
 
 int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t P, size_t H, size_t W, size_t k,
                        size_t stride, const uint8_t scale_le16[16], vpin_conv_trace** out) {
+  clear_refusals();
   if (out) *out = nullptr;
   if (!c || !px || !py || !pinf || !scale_le16 || !out) return fail(VPIN_EINVAL, "vpin_enc_avgpool2d: null argument");
   ConvGeom g;
@@ -199,8 +211,10 @@ int vpin_enc_avgpool2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const 
   if (t->n_add) {
     std::vector<uint8_t> bad(n_out);
     if ((rc = d.pool_sums(g, t->a_px.data(), t->a_py.data(), bad.data()))) return rc;
+    bool refused = false;
     for (size_t i = 0; i < n_out; i++)
-      if (bad[i]) return fail(VPIN_ESHAPE, "vpin_enc_avgpool2d: an addition accumulator is the identity (the witness format has no flag for it)");
+      if (bad[i]) { note_refusal(i / per_plane); refused = true; }
+    if (refused) return fail(VPIN_ESHAPE, "vpin_enc_avgpool2d: an addition accumulator is the identity (the witness format has no flag for it)");
   }
   std::vector<uint8_t> filt(taps * 16);
   for (size_t m = 0; m < taps; m++) memcpy(&filt[16 * m], scale_le16, 16);

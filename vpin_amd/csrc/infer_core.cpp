@@ -2,9 +2,13 @@
 // vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums_batch) and the interaction with the client as a callback per round: what vpin_lenet_infer
 // (lenet.cpp) and vpin_net_infer[_batch] (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer
 // validates what it is given, the client's answers included.  A batch of B images is the same loop: every layer call and every
-// round takes the planes of all images at once, image after image (infer_core.h, Call).
+// round takes the planes of all images at once, image after image (infer_core.h, Call).  The loop runs over the list of LIVE
+// slots (infer_slots.h): all B unless the run is vpin_net_infer_isolated's, where an image that makes a layer refuse, that owns
+// a point a layer's load refuses, or that the round callback drops leaves the batch and the step runs again over the others.
 #include "infer_core.h"
 
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <utility>
 
@@ -14,20 +18,10 @@ namespace {
 
 using enc::fail;
 
-struct Pts {
-  std::vector<uint8_t> x, y, inf;
-  size_t n() const { return inf.size(); }
-  void resize(size_t k) { x.resize(32 * k); y.resize(32 * k); inf.resize(k); }
-  void append(const uint8_t* px, const uint8_t* py, const uint8_t* pf, size_t k) {
-    x.insert(x.end(), px, px + 32 * k); y.insert(y.end(), py, py + 32 * k); inf.insert(inf.end(), pf, pf + k);
-  }
-  void append(const Pts& o, size_t from, size_t k) { append(o.x.data() + 32 * from, o.y.data() + 32 * from, o.inf.data() + from, k); }
-};
-
 // the planes of the layer call: image after image, the image's C planes of c1 and of c2, `times` over, in the step's order
-Pts gather(Pts& c1, const Pts& c2, size_t B, size_t C, size_t times, Step::Order order) {
+Pts gather(Pts& c1, const Pts& c2, size_t B, size_t C, size_t times, Step::Order order, bool may_move) {
   Pts in;
-  if (B == 1 && times == 1 && order == Step::kBlocked) {  // c1, c2 are rebuilt from the layer's output
+  if (may_move && B == 1 && times == 1 && order == Step::kBlocked) {  // c1, c2 are rebuilt from the layer's output
     in = std::move(c1);
     in.append(c2, 0, c2.n());
     return in;
@@ -67,69 +61,76 @@ size_t bias_values(const Step& s) {
   return s.kind == Step::kFc || s.kind == Step::kFcs ? s.N : s.kind == Step::kConvMc && s.bias ? s.n_out : 0;
 }
 
-// a step's n 32-byte items (PRF keys, bias r) of all B images, image after image: image b's stand at base + 32 (b * stride + ..);
-// `own` holds them when they have to be put together
-const uint8_t* of_all_images(const uint8_t* at, size_t stride, size_t n, size_t B, std::vector<uint8_t>* own) {
-  if (B == 1 || !n) return at;
-  own->resize(32 * n * B);
-  for (size_t b = 0; b < B; b++) memcpy(own->data() + 32 * n * b, at + 32 * stride * b, 32 * n);
-  return own->data();
-}
-
-// every image's n bias values under the client's key (with public keys in the call: under the key of the image's own client),
-// encrypted with the caller's r before the layer (encryptBias) by ONE call, then per image its n c1 halves and its n c2 halves:
-// the layer's rows 2 b and 2 b + 1, or its groups
-int encrypt_bias(const Call& a, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* out) {
+// every live image's n bias values under the client's key (with public keys in the call: under the key of the image's own
+// client, by its slot), encrypted with the caller's r before the layer (encryptBias) by ONE call, then per image its n c1 halves
+// and its n c2 halves: the layer's rows 2 b and 2 b + 1, or its groups.  r_le32: the live images' r, position after position
+int encrypt_bias(const Call& a, const Slots& live, const int64_t* bias, const uint8_t* r_le32, size_t n, Pts* out) {
+  const size_t B = live.n();
   Pts b1, b2;
-  b1.resize(a.B * n); b2.resize(a.B * n);
-  std::vector<int64_t> msgs(a.B * n);
-  for (size_t i = 0; i < a.B * n; i++) msgs[i] = bias[i % n];
+  b1.resize(B * n); b2.resize(B * n);
+  std::vector<int64_t> msgs(B * n);
+  for (size_t i = 0; i < B * n; i++) msgs[i] = bias[i % n];
   int rc;
   if (a.n_pub) {
-    std::vector<uint32_t> key_of(a.B * n);
-    for (size_t i = 0; i < a.B * n; i++) key_of[i] = a.key_of_image[i / n];
-    rc = vpin_e2_encrypt_keyed(a.c, a.baseG, a.hx, a.hy, a.n_pub, key_of.data(), msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(),
+    std::vector<uint32_t> key_of(B * n);
+    for (size_t i = 0; i < B * n; i++) key_of[i] = a.key_of_image[live.live[i / n]];
+    rc = vpin_e2_encrypt_keyed(a.c, a.baseG, a.hx, a.hy, a.n_pub, key_of.data(), msgs.data(), r_le32, B * n, b1.x.data(), b1.y.data(),
                                b1.inf.data(), b2.x.data(), b2.y.data(), b2.inf.data());
   } else {
-    rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, msgs.data(), r_le32, a.B * n, b1.x.data(), b1.y.data(), b1.inf.data(), b2.x.data(),
+    rc = vpin_e2_encrypt(a.c, a.baseG, a.baseH, msgs.data(), r_le32, B * n, b1.x.data(), b1.y.data(), b1.inf.data(), b2.x.data(),
                          b2.y.data(), b2.inf.data());
   }
   if (rc) return rc;
   out->resize(0);
-  for (size_t b = 0; b < a.B; b++) { out->append(b1, b * n, n); out->append(b2, b * n, n); }
+  for (size_t b = 0; b < B; b++) { out->append(b1, b * n, n); out->append(b2, b * n, n); }
   return VPIN_OK;
 }
 
 // the encrypted bias, then the layer on every image's c1 row and c2 row
-int fc(const Call& a, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
+int fc(const Call& a, const Slots& live, const Step& s, const Pts& in, const uint8_t* key, const uint8_t* r_le32, vpin_conv_trace** out) {
   Pts b;
-  const int rc = encrypt_bias(a, s.bias, r_le32, s.N, &b);
+  const int rc = encrypt_bias(a, live, s.bias, r_le32, s.N, &b);
   if (rc) return rc;
   if (s.kind == Step::kFcs)
-    return vpin_enc_fc_signed(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, s.K, s.w, s.N, b.x.data(), b.y.data(), b.inf.data(), key,
+    return vpin_enc_fc_signed(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * live.n(), s.K, s.w, s.N, b.x.data(), b.y.data(), b.inf.data(), key,
                               a.prf_bytes, out);
   std::vector<uint32_t> wu(s.K * s.N);
   for (size_t i = 0; i < s.K * s.N; i++) wu[i] = (uint32_t)s.w[i];
-  return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(),
+  return vpin_enc_fc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * live.n(), s.K, (const uint8_t*)wu.data(), s.N, b.x.data(), b.y.data(),
                      b.inf.data(), key, a.prf_bytes, out);
 }
 
 // the trained convolution over the groups g = 2 b + half; with a bias, n_out values per image encrypted as for fc: an image's c1
 // halves go to its first group, its c2 halves to its second
-int conv_mc(const Call& a, const Step& s, const Pts& in, size_t C, size_t H, size_t W, const uint8_t* key, const uint8_t* r_le32,
-            vpin_conv_trace** out) {
+int conv_mc(const Call& a, const Slots& live, const Step& s, const Pts& in, size_t C, size_t H, size_t W, const uint8_t* key,
+            const uint8_t* r_le32, vpin_conv_trace** out) {
   if (!s.bias)
-    return vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
+    return vpin_enc_conv2d_mc(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * live.n(), C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
                               s.stride, key, a.prf_bytes, out);
   Pts b;
-  const int rc = encrypt_bias(a, s.bias, r_le32, s.n_out, &b);
+  const int rc = encrypt_bias(a, live, s.bias, r_le32, s.n_out, &b);
   if (rc) return rc;
-  return vpin_enc_conv2d_mc_bias(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * a.B, C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
+  return vpin_enc_conv2d_mc_bias(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * live.n(), C, s.n_out, H, W, s.w_mc, s.connect, s.fh, s.fw, s.pad,
                                  s.stride, b.x.data(), b.y.data(), b.inf.data(), key, a.prf_bytes, out);
 }
 
-// one interaction with the client: the step's output goes out, the activated and re-encrypted values come back into c1, c2
-int interact(const Call& a, const Step& s, Pts* c1, Pts* c2) {
+// what the round callback at hand may ask and say (vpin_net_round_images, vpin_net_round_drop_images): per thread, set around
+// the one call of the callback
+struct Dropped {
+  uint32_t slot;
+  int code;
+  std::string text;
+};
+struct RoundState {
+  const Slots* live;
+  bool isolated;
+  std::vector<Dropped> dropped;
+};
+thread_local RoundState* g_round = nullptr;
+
+// one interaction with the client: the step's output goes out, the activated and re-encrypted values come back into c1, c2.
+// *dropped: the images the callback dropped (an isolated run), in the order it named them; they are still in c1 and c2
+int interact(const Call& a, const Slots& live, const Step& s, Pts* c1, Pts* c2, std::vector<Dropped>* dropped) {
   const size_t n = c1->n();
   Pts a1, a2;
   uint8_t* o[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // no outputs when nothing is encrypted again
@@ -139,11 +140,36 @@ int interact(const Call& a, const Step& s, Pts* c1, Pts* c2) {
   }
   const int flags = (s.relu ? VPIN_LENET_RELU : 0) | (s.reencrypt ? VPIN_LENET_REENCRYPT : 0);
   set_last_error_text("");  // a foreign callback may fail without a text of its own: no stale one is quoted then
+  RoundState state{&live, a.iso != nullptr, {}};
+  RoundState* const outer = g_round;  // a callback that runs an inference of its own gets its own
+  g_round = &state;
   const int rc = a.round_fn(a.user, s.round, flags, s.shift_bits, c1->x.data(), c1->y.data(), c1->inf.data(), c2->x.data(), c2->y.data(),
                             c2->inf.data(), n, o[0], o[1], o[2], o[3], o[4], o[5]);
+  g_round = outer;
   if (rc && !*vpin_last_error()) set_last_error_text("the round callback failed");
   if (!rc && s.reencrypt) { std::swap(*c1, a1); std::swap(*c2, a2); }
+  if (!rc) *dropped = std::move(state.dropped);
   return rc;
+}
+
+// the positions of the live images that own a point a layer's load refuses: the c1 and the c2 of every image through
+// vpin_e2_pack, which applies the load's rules.  On the failure path only
+std::vector<size_t> bad_images(const Call& a, const Pts& c1, const Pts& c2, size_t n) {
+  std::vector<size_t> at;
+  const size_t img = c1.n() / n;
+  std::vector<uint8_t> packed(32 * img);
+  for (size_t b = 0; b < n; b++)
+    for (const Pts* h : {&c1, &c2})
+      if (vpin_e2_pack(a.c, &h->x[32 * b * img], &h->y[32 * b * img], &h->inf[b * img], img, packed.data()) == VPIN_EINVAL) {
+        at.push_back(b);
+        break;
+      }
+  return at;
+}
+
+void write_status(vpin_net_image_status* st, int code, size_t layer, int round, const std::string& text) {
+  st->code = code; st->layer = (int)layer; st->round = round;
+  snprintf(st->text, sizeof st->text, "%s", text.c_str());
 }
 
 }  // namespace
@@ -173,58 +199,145 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   out->round_ms.assign(steps.size(), 0.0);
   enc::Lap total, lap;
   const size_t B = a.B;
-  const uint8_t* key = a.keys32;  // image 0's, of the step at hand; image b's stand b * keys (b * bias_r) items on
+  const uint8_t* key = a.keys32;  // slot 0's, of the step at hand; slot b's stand b * keys (b * bias_r) items on
   const uint8_t* br = a.bias_r_le32;
   size_t C = a.C, H = a.H, W = a.W;
-  Pts c1, c2;  // what the server holds: [b][C][H][W] each
+  Slots live(B);  // the images still in the batch; all of them unless the run is isolated
+  Pts c1, c2;     // what the server holds: [position][C][H][W] each
   c1.append(a.c1x, a.c1y, a.c1inf, B * C * H * W);
   c2.append(a.c2x, a.c2y, a.c2inf, B * C * H * W);
+  if (a.iso)
+    for (size_t b = 0; b < B; b++) write_status(&a.iso->status[b], VPIN_OK, 0, -1, "");
+  // an isolated run: the images at these positions leave with their status written; false when nobody is left
+  auto leave = [&](const std::vector<size_t>& at, int code, size_t layer, int round, const std::string& text) {
+    for (const size_t p : at) write_status(&a.iso->status[live.live[p]], code, layer, round, text);
+    remove_images(&c1, live.n(), at);
+    remove_images(&c2, live.n(), at);
+    live.remove(at);
+    return live.n() != 0;
+  };
+  auto nobody = [&]() { return fail(VPIN_ESHAPE, (who + "no image is left").c_str()); };
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     int rc = VPIN_OK;
-    if (s.sum_table) {  // ONE call over the groups g = 2 b + half, then the sums back into c1 and c2
-      const size_t img = C * H * W, out_img = s.sum_out * H * W;
+    while (s.sum_table) {  // ONE call over the groups g = 2 b + half, then the sums back into c1 and c2
+      const size_t n = live.n(), img = C * H * W, out_img = s.sum_out * H * W;
       Pts in, sum;
-      for (size_t b = 0; b < B; b++) { in.append(c1, b * img, img); in.append(c2, b * img, img); }
-      sum.resize(2 * B * out_img);
-      rc = vpin_e2_plane_sums_batch(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * B, C, H, W, s.sum_table, s.sum_out, sum.x.data(),
+      for (size_t b = 0; b < n; b++) { in.append(c1, b * img, img); in.append(c2, b * img, img); }
+      sum.resize(2 * n * out_img);
+      rc = vpin_e2_plane_sums_batch(a.c, in.x.data(), in.y.data(), in.inf.data(), 2 * n, C, H, W, s.sum_table, s.sum_out, sum.x.data(),
                                     sum.y.data(), sum.inf.data());
+      if (rc == VPIN_EINVAL && a.iso) {  // a point the sums' load refuses: its image leaves, the sums run again
+        const std::string text = who + s.name + ": " + vpin_last_error();
+        const std::vector<size_t> at = bad_images(a, c1, c2, n);
+        if (at.empty()) return fail(rc, text.c_str());
+        a.iso->refused += at.size();
+        a.iso->repeats++;
+        if (!leave(at, rc, i, -1, text)) return nobody();
+        continue;
+      }
       if (rc) return named(rc, s.name);
       c1.resize(0); c2.resize(0);
-      for (size_t h = 0; h < 2 * B; h++) (h % 2 ? c2 : c1).append(sum, h * out_img, out_img);
+      for (size_t h = 0; h < 2 * n; h++) (h % 2 ? c2 : c1).append(sum, h * out_img, out_img);
       C = s.sum_out;
+      break;
     }
     if (s.kind == Step::kFc || s.kind == Step::kFcs) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
-    const Pts in = gather(c1, c2, B, C, s.repeat, s.order);
-    C *= s.repeat;
-    std::vector<uint8_t> own_keys, own_r;
-    const uint8_t* k = of_all_images(key, keys, s.keys, B, &own_keys);
-    const uint8_t* r = of_all_images(br, bias_r, bias_values(s), B, &own_r);
+    const size_t Cc = C * s.repeat;  // the planes per half that the call takes
+    const size_t per_image = s.kind == Step::kConv || s.kind == Step::kPool ? 2 * Cc : 2;  // planes, or groups, or rows
     vpin_conv_trace* tr = nullptr;
-    if (s.kind == Step::kConv) {
-      rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), B * 2 * C, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, k,
-                           a.prf_bytes, &tr);
-    } else if (s.kind == Step::kConvMc) {
-      rc = conv_mc(a, s, in, C, H, W, k, r, &tr);
-    } else if (s.kind == Step::kPool) {
-      rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), B * 2 * C, H, W, s.k, s.stride, s.scale_le16, &tr);
-    } else {
-      rc = fc(a, s, in, k, r, &tr);
+    for (;;) {  // the layer call; an isolated run repeats it without the images it refuses, at most B times
+      const size_t n = live.n();
+      const Pts in = gather(c1, c2, n, C, s.repeat, s.order, !a.iso);
+      std::vector<uint8_t> own_keys, own_r;
+      const uint8_t* k = of_live_images(key, keys, s.keys, live, &own_keys);
+      const uint8_t* r = of_live_images(br, bias_r, bias_values(s), live, &own_r);
+      enc::clear_refusals();  // a failure before the layer itself (the bias encryption) leaves no stale list
+      if (s.kind == Step::kConv) {
+        rc = vpin_enc_conv2d(a.c, in.x.data(), in.y.data(), in.inf.data(), n * 2 * Cc, H, W, s.filter_le16, s.fh, s.fw, s.pad, s.stride, k,
+                             a.prf_bytes, &tr);
+      } else if (s.kind == Step::kConvMc) {
+        rc = conv_mc(a, live, s, in, Cc, H, W, k, r, &tr);
+      } else if (s.kind == Step::kPool) {
+        rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), n * 2 * Cc, H, W, s.k, s.stride, s.scale_le16, &tr);
+      } else {
+        rc = fc(a, live, s, in, k, r, &tr);
+      }
+      out->step_ms[i] += 1e3 * lap();
+      if (!rc) break;
+      if (!a.iso || (rc != VPIN_ESHAPE && rc != VPIN_EINVAL)) return named(rc, s.name);
+      const std::string text = who + s.name + ": " + vpin_last_error();
+      std::vector<size_t> at;
+      if (rc == VPIN_ESHAPE) {  // the units the layer names, as images
+        size_t n_units = 0;
+        vpin_enc_last_refusals(nullptr, 0, &n_units);
+        std::vector<uint32_t> units(n_units);
+        vpin_enc_last_refusals(units.data(), units.size(), &n_units);
+        at = positions_of_units(units.data(), units.size(), per_image, n);
+      } else {  // a point the layer's load refuses: the input's, or a reply's
+        at = bad_images(a, c1, c2, n);
+      }
+      if (at.empty()) return fail(rc, text.c_str());  // nobody's doing, or nobody's that can be named
+      a.iso->refused += at.size();
+      a.iso->repeats++;
+      if (!leave(at, rc, i, -1, text)) return nobody();
     }
     br += 32 * bias_values(s);
     key += 32 * s.keys;
-    out->step_ms[i] = 1e3 * lap();
-    if (rc) return named(rc, s.name);
     out->step.push_back(tr);
-    split(*tr, B, s.order, &c1, &c2);
-    C = tr->P / (2 * B); H = tr->oh; W = tr->ow;
+    out->slots.push_back(live.live);
+    split(*tr, live.n(), s.order, &c1, &c2);
+    C = tr->P / (2 * live.n()); H = tr->oh; W = tr->ow;
     if (!s.has_round) continue;
-    rc = interact(a, s, &c1, &c2);
+    std::vector<Dropped> dropped;
+    rc = interact(a, live, s, &c1, &c2, &dropped);
     out->round_ms[i] = 1e3 * lap();
     if (rc) return named(rc, s.round_name);
+    if (dropped.empty()) continue;
+    std::vector<size_t> at;  // what the callback dropped leaves after the round, each image with its own code and text
+    for (const Dropped& d : dropped) {
+      write_status(&a.iso->status[d.slot], d.code, i, s.round, d.text);
+      at.push_back(live.position(d.slot));
+    }
+    std::sort(at.begin(), at.end());
+    a.iso->dropped += at.size();
+    remove_images(&c1, live.n(), at);
+    remove_images(&c2, live.n(), at);
+    live.remove(at);
+    if (!live.n()) return nobody();
   }
+  out->survivors = live.live;
   out->total_ms = 1e3 * total();
   return VPIN_OK;
 }
 
 }  // namespace vpin::infer
+
+extern "C" {
+
+int vpin_net_round_images(const uint32_t** slots, size_t* n) {
+  using namespace vpin::infer;
+  if (!slots || !n) return fail(VPIN_EINVAL, "vpin_net_round_images: null argument");
+  if (!g_round) return fail(VPIN_EINVAL, "vpin_net_round_images: no round callback is running on this thread");
+  *slots = g_round->live->live.data();
+  *n = g_round->live->n();
+  return VPIN_OK;
+}
+
+int vpin_net_round_drop_images(const uint32_t* slots, size_t n, int code, const char* text) {
+  using namespace vpin::infer;
+  if (!g_round) return fail(VPIN_EINVAL, "vpin_net_round_drop_images: no round callback is running on this thread");
+  if (!g_round->isolated) return fail(VPIN_EINVAL, "vpin_net_round_drop_images: the run is not vpin_net_infer_isolated's");
+  if ((n && !slots) || !code) return fail(VPIN_EINVAL, "vpin_net_round_drop_images: null argument, or the code is VPIN_OK");
+  for (size_t i = 0; i < n; i++) {  // all or none
+    bool twice = false;
+    for (size_t j = 0; j < i; j++) twice = twice || slots[j] == slots[i];
+    for (const Dropped& d : g_round->dropped) twice = twice || d.slot == slots[i];
+    if (twice || g_round->live->position(slots[i]) == g_round->live->n())
+      return fail(VPIN_EINVAL, ("vpin_net_round_drop_images: slot " + std::to_string(slots[i]) + " is not in the batch, or is dropped twice").c_str());
+  }
+  for (size_t i = 0; i < n; i++) g_round->dropped.push_back(Dropped{slots[i], code, text ? text : ""});
+  return VPIN_OK;
+}
+
+}  // extern "C"

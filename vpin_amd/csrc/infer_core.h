@@ -7,8 +7,16 @@
 
 #include "../../include/vpin_hip.h"
 #include "enc_conv.h"
+#include "infer_slots.h"
 
 namespace vpin::infer {
+
+// vpin_net_infer_isolated: an image that makes a layer refuse, whose point a layer's load refuses or that the round callback
+// drops leaves the batch with its status written, and the step runs again over the others (infer_core.cpp, run)
+struct Isolation {
+  vpin_net_image_status* status = nullptr;        // [B]
+  uint64_t refused = 0, dropped = 0, repeats = 0;  // images a layer refused, images dropped in a round, layer calls repeated
+};
 
 struct Step {
   enum Kind { kConv, kPool, kFc, kConvMc, kFcs } kind = kConv;
@@ -62,11 +70,15 @@ struct Call {
   const uint8_t *hx = nullptr, *hy = nullptr;
   size_t n_pub = 0;
   const uint32_t* key_of_image = nullptr;
+  Isolation* iso = nullptr;  // NULL: a refusal fails the whole batch
 };
 
-// per step the trace of its layer call, owned; host-clock milliseconds per step (plane sums included), per round (0: none) and in all
+// per step the trace of its layer call, owned, and the slots of the images in that call (0 .. B - 1 unless images left);
+// host-clock milliseconds per step (plane sums included), per round (0: none) and in all
 struct Result {
   std::vector<vpin_conv_trace*> step;
+  std::vector<std::vector<uint32_t>> slots;
+  std::vector<uint32_t> survivors;  // the slots still there after the last round
   std::vector<double> step_ms, round_ms;
   double total_ms = 0.0;
   Result() = default;

@@ -7,9 +7,12 @@
 // callback over the planes of all images, image after image; the label is then the images' labels one after the other, and
 // vpin_net_trace_image_label cuts image b's own out of the layer calls' traces.
 // vpin_net_infer_multi is the batch with the images of several clients: a public key per image instead of one table of H.
+// vpin_net_infer_isolated is that with images that leave: the trace keeps per layer the slots of the images in its call, and an
+// image is asked for by its slot wherever it stands.
 // A CONV layer may say what the reference's LeNet needs (channel sums in front of it, its planes handed over several times, the
 // interleaved plane order: the driver's own Step fields), and vpin_lenet_as_net (lenet.cpp) writes that network as such a list;
 // its labels are single layers: vpin_net_trace_image_layer.
+#include <algorithm>
 #include <memory>
 #include <new>
 #include <string>
@@ -132,9 +135,10 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
 }
 
 thread_local std::vector<double> g_ms;  // [0] the whole, then per layer: the layer, the round after it
+thread_local uint64_t g_isolation[3] = {0, 0, 0};  // vpin_net_last_isolation
 
-// image b's share of a layer call's lists behind L's.  Every layer kind emits its lists plane by plane (row by row, pair by pair)
-// and an image's planes stand together, so the share is the b-th of B equal parts
+// the share of the image at position b among the B of a layer call, of that call's lists, behind L's.  Every layer kind emits its
+// lists plane by plane (row by row, pair by pair) and an image's planes stand together, so the share is the b-th of B equal parts
 void append_image(vpin_conv_trace* L, const vpin_conv_trace& tr, size_t b, size_t B) {
   auto part = [&](std::vector<uint8_t>* to, const std::vector<uint8_t>& from) {
     const size_t n = from.size() / B;
@@ -175,6 +179,21 @@ struct vpin_net_trace {
   vpin::infer::Result run;  // per layer the trace of its layer call over all images
   vpin_conv_trace label;    // per image, in image order, the lists of all layers in layer order; the output and dims of the last layer
   size_t B = 1;
+  // where slot b stands in layer's call (run.slots: the images that were in it), or npos when it had left
+  static constexpr size_t npos = (size_t)-1;
+  size_t position(size_t layer, size_t b) const {
+    const std::vector<uint32_t>& in = run.slots[layer];
+    const auto it = std::lower_bound(in.begin(), in.end(), (uint32_t)b);
+    return it != in.end() && *it == b ? (size_t)(it - in.begin()) : npos;
+  }
+  bool survived(size_t b) const { return std::binary_search(run.survivors.begin(), run.survivors.end(), (uint32_t)b); }
+  // VPIN_ESHAPE naming the first layer whose call image b was not in (n_layers: it left in the last round)
+  int left(const char* who, size_t b) const {
+    size_t layer = 0;
+    while (layer < run.slots.size() && position(layer, b) != npos) layer++;
+    return fail(VPIN_ESHAPE, (std::string(who) + ": image " + std::to_string(b) + " left the batch at " +
+                              (layer < run.slots.size() ? "layer " + std::to_string(layer) : std::string("the last round"))).c_str());
+  }
   mutable std::vector<std::unique_ptr<vpin_conv_trace>> image;  // B > 1: image b's label once it has been asked for
   mutable std::vector<std::unique_ptr<vpin_conv_trace>> image_layer;  // B > 1: [layer][b], image b's share of a layer call likewise
 };
@@ -192,7 +211,7 @@ struct PubKeys {
 int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t* keys32,
           size_t n_keys, const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user, vpin_net_trace** out,
-          const PubKeys& pub = PubKeys()) {
+          const PubKeys& pub = PubKeys(), vpin_net_image_status* status = nullptr) {
   if (out) *out = nullptr;
   if (!c || !g || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !out) return fail(VPIN_EINVAL, (std::string(who) + ": null argument").c_str());
   if (!B || B > VPIN_NET_MAX_BATCH)
@@ -223,13 +242,17 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
   std::unique_ptr<vpin_net_trace> t(new (std::nothrow) vpin_net_trace());
   if (!t) return VPIN_ENOMEM;
   t->B = B;
+  vpin::infer::Isolation iso;  // vpin_net_infer_isolated: with a status array
+  iso.status = status;
   const vpin::infer::Call call{c, who, g->prf_bytes, g->C, g->H, g->W, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, baseH,
-                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, B, pub.hx, pub.hy, pub.n_pub, pub.key_of_image};
+                               keys32, n_keys, bias_r_le32, n_bias_r, round_fn, user, B, pub.hx, pub.hy, pub.n_pub, pub.key_of_image,
+                               status ? &iso : nullptr};
   const vpin::infer::Result& res = t->run;
   const int rc = vpin::infer::run(call, steps, &t->run);
+  if (status) { g_isolation[0] = iso.refused; g_isolation[1] = iso.dropped; g_isolation[2] = iso.repeats; }
   g_ms.assign(1 + 2 * pl.size(), 0.0);
   for (size_t i = 0; i < res.step_ms.size(); i++) { g_ms[1 + 2 * i] = res.step_ms[i]; g_ms[2 + 2 * i] = res.round_ms[i]; }
-  if (rc == VPIN_EINVAL && B > 1 && res.step.empty() && !res.step_ms.empty() && res.step_ms[0] > 0.0) {  // layer 0 ran and failed
+  if (rc == VPIN_EINVAL && !status && B > 1 && res.step.empty() && !res.step_ms.empty() && res.step_ms[0] > 0.0) {  // layer 0 ran and failed
     // the first layer refuses the caller's input without saying which point: of a batch the caller wants to know whose.  The
     // packing names the first point that is not a point of E2, counted over the whole batch (image = index / (C H W))
     const std::string text = vpin_last_error();
@@ -246,10 +269,21 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
   vpin::enc::Lap lap;
   vpin_conv_trace& L = t->label;
   const vpin_conv_trace* last = res.step.back();
-  L.P = last->P; L.oh = last->oh; L.ow = last->ow;
-  L.out_x = last->out_x; L.out_y = last->out_y; L.out_inf = last->out_inf;
-  for (size_t b = 0; b < B; b++)
-    for (const vpin_conv_trace* tr : res.step) append_image(&L, *tr, b, B);
+  const size_t n_last = res.slots.back().size(), n_left = res.survivors.size();
+  L.P = last->P / n_last * n_left; L.oh = last->oh; L.ow = last->ow;
+  if (n_left == n_last) {
+    L.out_x = last->out_x; L.out_y = last->out_y; L.out_inf = last->out_inf;
+  } else {  // images left in the last round: the output of those that stayed, in slot order
+    const size_t n = last->out_inf.size() / n_last;
+    for (const uint32_t b : res.survivors) {
+      const size_t at = t->position(res.step.size() - 1, b);
+      L.out_x.insert(L.out_x.end(), last->out_x.begin() + 32 * at * n, last->out_x.begin() + 32 * (at + 1) * n);
+      L.out_y.insert(L.out_y.end(), last->out_y.begin() + 32 * at * n, last->out_y.begin() + 32 * (at + 1) * n);
+      L.out_inf.insert(L.out_inf.end(), last->out_inf.begin() + at * n, last->out_inf.begin() + (at + 1) * n);
+    }
+  }
+  for (const uint32_t b : res.survivors)
+    for (size_t i = 0; i < res.step.size(); i++) append_image(&L, *res.step[i], t->position(i, b), res.slots[i].size());
   t->image.resize(B);
   t->image_layer.resize(B * res.step.size());
   g_ms[0] = res.total_ms + 1e3 * lap();  // the whole, the label included
@@ -309,6 +343,34 @@ int vpin_net_infer_multi(vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uin
                out, PubKeys{hx, hy, n_pub, key_of_image});
 }
 
+int vpin_net_infer_isolated(vpin_ctx* c, const vpin_net_cfg* g, size_t B, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
+                            const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const vpin_e2_base* baseG, const uint8_t* hx,
+                            const uint8_t* hy, size_t n_pub, const uint32_t* key_of_image, const uint8_t* keys32, size_t n_keys,
+                            const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user,
+                            vpin_net_image_status* status, vpin_net_trace** out) {
+  if (out) *out = nullptr;
+  for (uint64_t& v : g_isolation) v = 0;
+  if (!hx || !hy || !key_of_image || !status) return fail(VPIN_EINVAL, "vpin_net_infer_isolated: null argument");
+  if (!n_pub) return fail(VPIN_EINVAL, "vpin_net_infer_isolated: n_pub = 0: no public key");
+  for (size_t b = 0; b < B && b < VPIN_NET_MAX_BATCH; b++)
+    if (key_of_image[b] >= n_pub)
+      return fail(VPIN_EINVAL, ("vpin_net_infer_isolated: key_of_image[" + std::to_string(b) + "] = " + std::to_string(key_of_image[b]) +
+                                " is not below n_pub = " + std::to_string(n_pub)).c_str());
+  return infer("vpin_net_infer_isolated", c, g, B, c1x, c1y, c1inf, c2x, c2y, c2inf, baseG, nullptr, keys32, n_keys, bias_r_le32, n_bias_r, round_fn,
+               user, out, PubKeys{hx, hy, n_pub, key_of_image}, status);
+}
+
+void vpin_net_last_isolation(uint64_t out[3]) {
+  for (int i = 0; i < 3; i++) out[i] = g_isolation[i];
+}
+
+int vpin_net_trace_layer_images(const vpin_net_trace* t, size_t layer, const uint32_t** slots, size_t* n) {
+  if (!t || !slots || !n || layer >= t->run.slots.size()) return fail(VPIN_EINVAL, "vpin_net_trace_layer_images: null argument or no such layer");
+  *slots = t->run.slots[layer].data();
+  *n = t->run.slots[layer].size();
+  return VPIN_OK;
+}
+
 int vpin_net_trace_images(const vpin_net_trace* t, size_t* B) {
   if (!t || !B) return fail(VPIN_EINVAL, "vpin_net_trace_images: null argument");
   *B = t->B;
@@ -319,16 +381,18 @@ int vpin_net_trace_image_label(const vpin_net_trace* t, size_t b, const vpin_con
   if (out) *out = nullptr;
   if (!t || !out || b >= t->B) return fail(VPIN_EINVAL, "vpin_net_trace_image_label: null argument or no such image");
   if (t->B == 1) { *out = &t->label; return VPIN_OK; }
+  if (!t->survived(b)) return t->left("vpin_net_trace_image_label", b);
   if (!t->image[b]) {
     std::unique_ptr<vpin_conv_trace> L(new (std::nothrow) vpin_conv_trace());
     if (!L) return VPIN_ENOMEM;
-    const vpin_conv_trace& all = t->label;  // its output is the last layer call's: image b's planes are the b-th part
-    const size_t n = all.out_inf.size() / t->B;
-    L->P = all.P / t->B; L->oh = all.oh; L->ow = all.ow;
-    L->out_x.assign(all.out_x.begin() + 32 * b * n, all.out_x.begin() + 32 * (b + 1) * n);
-    L->out_y.assign(all.out_y.begin() + 32 * b * n, all.out_y.begin() + 32 * (b + 1) * n);
-    L->out_inf.assign(all.out_inf.begin() + b * n, all.out_inf.begin() + (b + 1) * n);
-    for (const vpin_conv_trace* tr : t->run.step) append_image(L.get(), *tr, b, t->B);
+    const vpin_conv_trace& all = t->label;  // its output is the survivors': image b's planes are the part at its place among them
+    const size_t left = t->run.survivors.size(), n = all.out_inf.size() / left;
+    const size_t at = (size_t)(std::lower_bound(t->run.survivors.begin(), t->run.survivors.end(), (uint32_t)b) - t->run.survivors.begin());
+    L->P = all.P / left; L->oh = all.oh; L->ow = all.ow;
+    L->out_x.assign(all.out_x.begin() + 32 * at * n, all.out_x.begin() + 32 * (at + 1) * n);
+    L->out_y.assign(all.out_y.begin() + 32 * at * n, all.out_y.begin() + 32 * (at + 1) * n);
+    L->out_inf.assign(all.out_inf.begin() + at * n, all.out_inf.begin() + (at + 1) * n);
+    for (size_t i = 0; i < t->run.step.size(); i++) append_image(L.get(), *t->run.step[i], t->position(i, b), t->run.slots[i].size());
     t->image[b] = std::move(L);
   }
   *out = t->image[b].get();
@@ -340,19 +404,21 @@ int vpin_net_trace_image_layer(const vpin_net_trace* t, size_t b, size_t layer, 
   if (!t || !out || b >= t->B || layer >= t->run.step.size())
     return fail(VPIN_EINVAL, "vpin_net_trace_image_layer: null argument, no such image or no such layer");
   if (t->B == 1) { *out = t->run.step[layer]; return VPIN_OK; }
+  const size_t at = t->position(layer, b), in_call = t->run.slots[layer].size();
+  if (at == vpin_net_trace::npos) return t->left("vpin_net_trace_image_layer", b);
   std::unique_ptr<vpin_conv_trace>& slot = t->image_layer[layer * t->B + b];
   if (!slot) {
     std::unique_ptr<vpin_conv_trace> L(new (std::nothrow) vpin_conv_trace());
     if (!L) return VPIN_ENOMEM;
-    const vpin_conv_trace& all = *t->run.step[layer];  // an image's planes stand together: every array's b-th part
+    const vpin_conv_trace& all = *t->run.step[layer];  // an image's planes stand together: every array's part at its position
     auto part = [&](std::vector<uint8_t>* to, const std::vector<uint8_t>& from) {
-      const size_t n = from.size() / t->B;
-      to->assign(from.begin() + b * n, from.begin() + (b + 1) * n);
+      const size_t n = from.size() / in_call;
+      to->assign(from.begin() + at * n, from.begin() + (at + 1) * n);
     };
-    L->P = all.P / t->B; L->oh = all.oh; L->ow = all.ow;
+    L->P = all.P / in_call; L->oh = all.oh; L->ow = all.ow;
     part(&L->out_x, all.out_x); part(&L->out_y, all.out_y); part(&L->out_inf, all.out_inf);
     part(&L->left_x, all.left_x); part(&L->left_y, all.left_y); part(&L->left_inf, all.left_inf);
-    append_image(L.get(), all, b, t->B);
+    append_image(L.get(), all, at, in_call);
     slot = std::move(L);
   }
   *out = slot.get();
@@ -397,7 +463,7 @@ int vpin_net_trace_instances(vpin_ctx* c, const vpin_net_trace* t, vpin_dev_inst
 
 int vpin_net_trace_result(const vpin_net_trace* t, const uint8_t** x, const uint8_t** y, const uint8_t** inf, size_t* n) {
   if (!t || !x || !y || !inf || !n) return fail(VPIN_EINVAL, "vpin_net_trace_result: null argument");
-  *n = t->label.out_inf.size() / (2 * t->B);
+  *n = t->label.out_inf.size() / (2 * t->run.survivors.size());
   return vpin_conv_trace_output(&t->label, x, y, inf);
 }
 

@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vpin_hip.h"
@@ -62,12 +63,16 @@ int peer_error(vpin_wire* w, const vpin_wire_header& h, const char* who);
 struct Peer {
   vpin_wire* w = nullptr;
   size_t wire = 0;           // its index among the caller's wires, and into the status
-  size_t first = 0, n = 0;   // its image slots [first, first + n)
+  size_t first = 0, n = 0;   // its image slots [first, first + n): for its status, its keys and its bias r, for the whole call
   bool live = true;
+  // where its images stand in the batch at hand: at `at`, `present` of them.  first and n until images leave the batch
+  // (Roster::rebase, the isolated server); slice, place, copy_images and exchange go by these
+  size_t at = 0, present = 0;
 };
 struct Roster {
   const char* who = "";      // the entry point's name, in front of every text
-  size_t max_batch = 0, images = 0;
+  size_t max_batch = 0, images = 0;  // images: the slots given out
+  size_t batch = 0;                  // the images in the batch at hand: `images` until some leave
   std::vector<Peer> peers;   // the admitted clients, in wire order
   vpin_net_peer_status* status = nullptr;  // one per wire of the caller's
   size_t live() const;
@@ -77,6 +82,13 @@ struct Roster {
   void report(size_t wire, int code, int stage, const std::string& text);
   // peer p leaves at `stage`: report, and ERROR to it best effort, unless it has said ERROR itself (tell = false)
   void drop(size_t p, int code, int stage, const std::string& text, bool tell = true);
+  // the batch at hand holds the images `slots` (ascending): every client's position among them and how many of its images are there
+  void rebase(const uint32_t* slots, size_t n);
+  // (the isolated server, before a round) the live clients that lost an image to a layer (image_status[slot].code != 0, the
+  // driver's) leave at VPIN_NET_STAGE_LAYER with the code and the text of their first such image; the images of the clients so dropped
+  size_t drop_refused(const vpin_net_image_status* image_status);
+  // (after a round) the slots still in the batch whose client is gone, client after client: peer, its slots
+  std::vector<std::pair<size_t, std::vector<uint32_t>>> gone(const uint32_t* slots) const;
 };
 // peer's frame out of a packed batch, and a frame's points into their places in one
 void slice(const Roster& r, const Peer& p, const uint8_t* packed, size_t per, std::vector<uint8_t>* frame);

@@ -4,6 +4,9 @@
 // (wire_roster.cpp, plain C++); here are the device's parts: ONE unpack launch over the keys and inputs of all wires at admission,
 // and per round one pack launch over the batch and one unpack launch over all replies, whose rule byte per point says which
 // client owns a bad one.  A client dropped in a round keeps its images in the batch: they go on as what the server sent.
+// With vpin_net_server_set_isolation on the inference is vpin_net_infer_isolated: before a round the roster is re-based on the
+// slots still in the batch and a client that lost an image to a layer is dropped (VPIN_NET_STAGE_LAYER); after it the images of
+// the clients that are gone leave the batch (vpin_net_round_drop_images), so the later layer calls run without them.
 // No table of any client's H is built: the biases are encrypted by vpin_e2_encrypt_keyed.
 #include <cstdio>
 #include <cstring>
@@ -23,6 +26,8 @@ struct vpin_net_server {
   size_t max_batch = 0, k = 0, r = 0, per = 0;  // per image: PRF keys, bias r, input ciphertexts
   vpin_e2_base* g = nullptr;
   uint64_t stats[5] = {0, 0, 0, 0, 0};  // calls, clients admitted, clients served to DONE, images run, base tables built
+  bool isolation = false;
+  uint64_t isolated[3] = {0, 0, 0};  // images of clients a layer refused, images compacted away after a wire drop, layer calls repeated
 };
 
 namespace {
@@ -32,6 +37,7 @@ const char* const kWho = "vpin_net_serve_multi";
 struct Run {
   vpin_net_server* s;
   Roster* r;
+  const vpin_net_image_status* image_status;  // the isolated driver's, per slot; NULL: isolation is off
 };
 
 // "point j: <rule>" for the first bad point among a client's frame of 2 * n points: its c1 part at c1, its c2 part at c2
@@ -52,14 +58,33 @@ int multi_round(void* user, int round, int flags, int shift_bits, const uint8_t*
   Run* run = (Run*)user;
   Roster& r = *run->r;
   vpin_ctx* c = run->s->c;
-  const size_t per = cnt / r.images;
-  if (round < 0 || !cnt || cnt % r.images || per * r.images > VPIN_WIRE_MAX_CNT || shift_bits < 0 || shift_bits > 255 || (flags & ~0xff))
+  const uint32_t* slots = nullptr;
+  if (run->image_status) {  // the batch may have lost images since the last round: where everybody stands now, and who lost one
+    size_t n = 0;
+    const int rc = vpin_net_round_images(&slots, &n);
+    if (rc) return rc;
+    r.rebase(slots, n);
+    run->s->isolated[0] += r.drop_refused(run->image_status);
+    if (!r.live()) return fail(VPIN_ECOMM, (std::string(kWho) + ": round " + std::to_string(round) + ": no client is left").c_str());
+  }
+  const size_t per = r.batch ? cnt / r.batch : 0;
+  if (round < 0 || !cnt || !r.batch || cnt % r.batch || per * r.batch > VPIN_WIRE_MAX_CNT || shift_bits < 0 || shift_bits > 255 || (flags & ~0xff))
     return fail(VPIN_EINVAL, "vpin_net_serve_multi: a round, cnt, shift_bits or flags that no header holds");
   std::vector<uint8_t> packed, reply;
   int rc = pack_pair(c, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, &packed);
   if (rc) return rc;
   if ((rc = exchange(&r, round, flags, shift_bits, packed.data(), per, &reply))) return rc;
-  if (!(flags & VPIN_LENET_REENCRYPT)) return VPIN_OK;
+  // isolation: the images of a client that is gone leave the batch after this round, with the client's code and text
+  auto compact = [&]() {
+    for (const auto& g : r.gone(slots)) {
+      const vpin_net_peer_status& st = r.status[r.peers[g.first].wire];
+      const int bad = vpin_net_round_drop_images(g.second.data(), g.second.size(), st.code, st.text);
+      if (bad) return bad;
+      if (st.stage != VPIN_NET_STAGE_LAYER) run->s->isolated[1] += g.second.size();
+    }
+    return VPIN_OK;
+  };
+  if (!(flags & VPIN_LENET_REENCRYPT)) return run->image_status ? compact() : VPIN_OK;
   std::vector<uint8_t> x(64 * cnt), y(64 * cnt), f(2 * cnt), bad(2 * cnt);
   if ((rc = unpack_rules(c, reply.data(), 2 * cnt, x.data(), y.data(), f.data(), bad.data()))) return rc;
   memcpy(o1x, x.data(), 32 * cnt); memcpy(o2x, x.data() + 32 * cnt, 32 * cnt);
@@ -68,15 +93,15 @@ int multi_round(void* user, int round, int flags, int shift_bits, const uint8_t*
   std::string text;
   for (size_t i = 0; i < r.peers.size(); i++) {
     const Peer& p = r.peers[i];
-    if (p.live && first_bad(bad.data(), p.first * per, cnt + p.first * per, p.n * per, &text))
+    if (p.live && first_bad(bad.data(), p.at * per, cnt + p.at * per, p.n * per, &text))
       r.drop(i, VPIN_EINVAL, round, "round " + std::to_string(round) + ": the reply (c1, then c2): " + text);
-    if (p.live) continue;
+    if (p.live || run->image_status) continue;  // isolation: what is written for an image that leaves is ignored
     // the images of a client that is gone answer with what the server sent
     copy_images(p, per, 32, c1x, o1x); copy_images(p, per, 32, c1y, o1y); copy_images(p, per, 1, c1inf, o1inf);
     copy_images(p, per, 32, c2x, o2x); copy_images(p, per, 32, c2y, o2y); copy_images(p, per, 1, c2inf, o2inf);
   }
   if (!r.live()) return fail(VPIN_ECOMM, (std::string(kWho) + ": round " + std::to_string(round) + ": no client is left").c_str());
-  return VPIN_OK;
+  return run->image_status ? compact() : VPIN_OK;
 }
 
 // what one wire sent at admission
@@ -155,11 +180,25 @@ int serve(vpin_net_server* s, vpin_wire* const* wires, size_t n_wires, const uin
   if (r->peers.empty()) return fail(VPIN_ESHAPE, "vpin_net_serve_multi: no client was admitted");
   const size_t B = r->images;
   s->stats[3] += B;
-  Run run{s, r};
-  rc = vpin_net_infer_multi(s->c, s->cfg, B, c1x.data(), c1y.data(), c1f.data(), c2x.data(), c2y.data(), c2f.data(), s->g, hx.data(), hy.data(),
-                            r->peers.size(), key_of_image.data(), keys32, B * s->k, bias_r_le32, B * s->r, multi_round, &run, out);
+  std::vector<vpin_net_image_status> image_status(s->isolation ? B : 0);
+  Run run{s, r, s->isolation ? image_status.data() : nullptr};
+  if (s->isolation) {
+    rc = vpin_net_infer_isolated(s->c, s->cfg, B, c1x.data(), c1y.data(), c1f.data(), c2x.data(), c2y.data(), c2f.data(), s->g, hx.data(),
+                                 hy.data(), r->peers.size(), key_of_image.data(), keys32, B * s->k, bias_r_le32, B * s->r, multi_round, &run,
+                                 image_status.data(), out);
+    uint64_t did[3];
+    vpin_net_last_isolation(did);
+    s->isolated[2] += did[2];
+  } else {
+    rc = vpin_net_infer_multi(s->c, s->cfg, B, c1x.data(), c1y.data(), c1f.data(), c2x.data(), c2y.data(), c2f.data(), s->g, hx.data(), hy.data(),
+                              r->peers.size(), key_of_image.data(), keys32, B * s->k, bias_r_le32, B * s->r, multi_round, &run, out);
+  }
   if (rc) {  // the last client gone (every status is written), or the server's own failure: the live clients are told
-    const std::string text = vpin_last_error();
+    std::string text = vpin_last_error();
+    if (s->isolation) {  // whose image a layer refused is told the layer's text; nobody left is VPIN_ECOMM however they went
+      s->isolated[0] += r->drop_refused(image_status.data());
+      if (rc == VPIN_ESHAPE && !r->live()) { rc = VPIN_ECOMM; text = std::string(kWho) + ": no client is left: " + text; }
+    }
     for (size_t i = 0; i < r->peers.size(); i++)
       if (r->peers[i].live) r->drop(i, rc, VPIN_NET_STAGE_SERVER, text);
     return fail(rc, text.c_str());
@@ -206,6 +245,18 @@ void vpin_net_server_free(vpin_net_server* s) {
 int vpin_net_server_stats(const vpin_net_server* s, uint64_t out[5]) {
   if (!s || !out) return fail(VPIN_EINVAL, "vpin_net_server_stats: null argument");
   for (int i = 0; i < 5; i++) out[i] = s->stats[i];
+  return VPIN_OK;
+}
+
+int vpin_net_server_set_isolation(vpin_net_server* s, int on) {
+  if (!s) return fail(VPIN_EINVAL, "vpin_net_server_set_isolation: null argument");
+  s->isolation = on != 0;
+  return VPIN_OK;
+}
+
+int vpin_net_server_stats_isolation(const vpin_net_server* s, uint64_t out[3]) {
+  if (!s || !out) return fail(VPIN_EINVAL, "vpin_net_server_stats_isolation: null argument");
+  for (int i = 0; i < 3; i++) out[i] = s->isolated[i];
   return VPIN_OK;
 }
 

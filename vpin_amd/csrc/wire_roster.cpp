@@ -1,7 +1,8 @@
 // wire_roster.cpp -- several clients in one batched inference: who gets which bytes.  The roster gives the admitted clients
 // their image slots in wire order, cuts each client's frame out of a packed round, puts a reply's points back into the batch,
 // and leaves a dropped client's images what the server sent; it reads a client's HELLO and INPUT and runs one round's exchange
-// with all live clients.  Plain C++ beside wire_codec.cpp and wire_stream.cpp: no HIP, no context.  It decides which client's
+// with all live clients.  For the isolated server it re-bases every client's position on the slots still in the batch, drops
+// the clients that lost an image to a layer and names the images of the clients that are gone (tools/wire_check/isolate_check.cpp).  Plain C++ beside wire_codec.cpp and wire_stream.cpp: no HIP, no context.  It decides which client's
 // bytes go where and parses what untrusted peers send, so tools/wire_check/multi_check.cpp links these three files alone and
 // runs them under the host compiler's sanitizers.  wire_multi.cpp is the endpoint around it.
 #include <cstdio>
@@ -19,8 +20,9 @@ size_t Roster::live() const {
 
 void Roster::admit(vpin_wire* w, size_t wire, size_t n_images) {
   Peer p;
-  p.w = w; p.wire = wire; p.first = images; p.n = n_images;
+  p.w = w; p.wire = wire; p.first = p.at = images; p.n = p.present = n_images;
   images += n_images;
+  batch = images;
   peers.push_back(p);
   status[wire].first_image = (uint32_t)p.first;
   status[wire].n_images = (uint32_t)p.n;
@@ -39,21 +41,57 @@ void Roster::drop(size_t p, int code, int stage, const std::string& text, bool t
   if (tell) send_error(peers[p].w, code, status[peers[p].wire].text);
 }
 
+void Roster::rebase(const uint32_t* slots, size_t n) {
+  size_t i = 0;
+  for (Peer& p : peers) {
+    while (i < n && slots[i] < p.first) i++;
+    p.at = i;
+    while (i < n && slots[i] < p.first + p.n) i++;
+    p.present = i - p.at;
+  }
+  batch = n;
+}
+
+size_t Roster::drop_refused(const vpin_net_image_status* image_status) {
+  size_t images_gone = 0;
+  for (size_t i = 0; i < peers.size(); i++) {
+    const Peer& p = peers[i];
+    if (!p.live) continue;
+    const vpin_net_image_status* why = nullptr;  // its first image that left
+    for (size_t b = p.first; b < p.first + p.n && !why; b++)
+      if (image_status[b].code) why = &image_status[b];
+    if (!why) continue;
+    images_gone += p.n;
+    drop(i, why->code, VPIN_NET_STAGE_LAYER, why->text);
+  }
+  return images_gone;
+}
+
+std::vector<std::pair<size_t, std::vector<uint32_t>>> Roster::gone(const uint32_t* slots) const {
+  std::vector<std::pair<size_t, std::vector<uint32_t>>> out;
+  for (size_t i = 0; i < peers.size(); i++) {
+    const Peer& p = peers[i];
+    if (p.live || !p.present) continue;
+    out.emplace_back(i, std::vector<uint32_t>(slots + p.at, slots + p.at + p.present));
+  }
+  return out;
+}
+
 void slice(const Roster& r, const Peer& p, const uint8_t* packed, size_t per, std::vector<uint8_t>* frame) {
-  const size_t part = 32 * p.n * per, c2 = 32 * r.images * per;
+  const size_t part = 32 * p.present * per, c2 = 32 * r.batch * per;
   frame->resize(2 * part);
-  memcpy(frame->data(), packed + 32 * p.first * per, part);
-  memcpy(frame->data() + part, packed + c2 + 32 * p.first * per, part);
+  memcpy(frame->data(), packed + 32 * p.at * per, part);
+  memcpy(frame->data() + part, packed + c2 + 32 * p.at * per, part);
 }
 
 void place(const Roster& r, const Peer& p, const uint8_t* frame, size_t per, uint8_t* packed) {
-  const size_t part = 32 * p.n * per, c2 = 32 * r.images * per;
-  memcpy(packed + 32 * p.first * per, frame, part);
-  memcpy(packed + c2 + 32 * p.first * per, frame + part, part);
+  const size_t part = 32 * p.present * per, c2 = 32 * r.batch * per;
+  memcpy(packed + 32 * p.at * per, frame, part);
+  memcpy(packed + c2 + 32 * p.at * per, frame + part, part);
 }
 
 void copy_images(const Peer& p, size_t per, size_t elem, const uint8_t* from, uint8_t* to) {
-  memcpy(to + elem * p.first * per, from + elem * p.first * per, elem * p.n * per);
+  memcpy(to + elem * p.at * per, from + elem * p.at * per, elem * p.present * per);
 }
 
 int read_client(vpin_wire* w, size_t per, size_t room, std::vector<uint8_t>* hello, std::vector<uint8_t>* input,
@@ -101,7 +139,7 @@ int exchange(Roster* r, int round, int flags, int shift_bits, const uint8_t* pac
   const std::string at = "round " + std::to_string(round) + ": ";
   char why[240];
   reply->clear();
-  if (re) reply->assign(packed, packed + 64 * r->images * per);  // the places of a client that is not live: what the server sent
+  if (re) reply->assign(packed, packed + 64 * r->batch * per);  // the places of a client that is not live: what the server sent
   std::vector<uint8_t> frame;
   for (size_t i = 0; i < r->peers.size(); i++) {
     Peer& p = r->peers[i];

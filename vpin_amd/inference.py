@@ -120,11 +120,15 @@ class Trace:
 
     images = 1
 
+    def result_images(self):
+        """the images whose ciphertexts result() holds"""
+        return self.images
+
     def result(self):
         """the last layer's ciphertext -> (c1, c2), each (x, y, inf); of a batch, every array with the image in front"""
         x, y, f, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
         _chk(getattr(lib(), self.prefix + "_result")(self.h, C.byref(x), C.byref(y), C.byref(f), C.byref(n)), self.prefix + "_result")
-        n, b = n.value, self.images
+        n, b = n.value, self.result_images()
         get = lambda p, k: np.frombuffer((C.c_uint8 * k).from_address(p.value), dtype=np.uint8).copy()
         xs, ys, fs = get(x, 64 * n * b).reshape(b, 2, n, 32), get(y, 64 * n * b).reshape(b, 2, n, 32), get(f, 2 * n * b).reshape(b, 2, n)
         if b == 1:
@@ -138,11 +142,12 @@ class Trace:
             self.h = None
 
 
-def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user, batch=None, pubs=None, key_of_image=None):
+def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn, user, batch=None, pubs=None, key_of_image=None, status=None):
     """`name` = vpin_lenet_infer or vpin_net_infer over the C configuration cfg_c -> the trace's handle.  c1, c2: (x, y, inf) of
     the input points; keys: 32-byte keys in call order; bias_rs: ints; round_fn: a LENET_ROUND_FN (python_round) or a pointer.
     batch: the B of vpin_net_infer_batch, which takes it behind the configuration; everything is then image-major.
-    pubs: for vpin_net_infer_multi, which takes public keys [(x, y)] as Python ints and key_of_image[B] where the others take base_h"""
+    pubs: for vpin_net_infer_multi, which takes public keys [(x, y)] as Python ints and key_of_image[B] where the others take base_h.
+    status: for vpin_net_infer_isolated, its array of B vpin_net_image_status in front of the trace"""
     x1, y1, f1 = ctx._points(*c1)
     x2, y2, f2 = ctx._points(*c2)
     k = np.frombuffer(b"".join(bytes(b) for b in keys), dtype=np.uint8).copy() if len(keys) else np.zeros(32, np.uint8)
@@ -157,7 +162,7 @@ def run_infer(name, ctx, cfg_c, c1, c2, base_g, base_h, keys, bias_rs, round_fn,
         assert ko.shape[0] == batch
         under = [p(hx), p(hy), len(pubs), p(ko)]
     rc = getattr(lib(), name)(ctx.h, C.byref(cfg_c), *([] if batch is None else [batch]), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), base_g, *under,
-                              p(k), len(keys), p(r), len(bias_rs), fn, user, C.byref(h))
+                              p(k), len(keys), p(r), len(bias_rs), fn, user, *([] if status is None else [status]), C.byref(h))
     if rc:
         assert not h.value
         err, lib_text = getattr(round_fn, "error", None), lib().vpin_last_error().decode()

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from . import inference
-from .capi import NetCfg, NetLayer8 as NetLayer, NetPeerStatus, VpinError, _chk, lib
+from .capi import NetCfg, NetImageStatus, NetLayer8 as NetLayer, NetPeerStatus, VpinError, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
 CONV, POOL, FC, CONVMC, FCS = 0, 1, 2, 3, 4
@@ -228,6 +228,17 @@ class Trace(inference.Trace):
         _chk(lib().vpin_net_trace_image_layer(self.h, b, i, C.byref(h)), "vpin_net_trace_image_layer")
         return self._borrowed(h)
 
+    def layer_images(self, i):
+        """the slots of the images in layer i's call, ascending: all of them unless images left (infer_isolated)"""
+        p, n = C.c_void_p(), C.c_size_t()
+        _chk(lib().vpin_net_trace_layer_images(self.h, i, C.byref(p), C.byref(n)), "vpin_net_trace_layer_images")
+        return [int(v) for v in (C.c_uint32 * n.value).from_address(p.value)] if n.value else []
+
+    def result_images(self):
+        """the images of result() and label(): those that stayed to the end; of a run that nobody left, all"""
+        last = self.n_layers - 1  # the label has an image's planes of the last layer call once per image that stayed
+        return self.label().P * len(self.layer_images(last)) // self.layer(last).P
+
     def image_instances(self, b):
         hm, ha = C.c_void_p(), C.c_void_p()
         _chk(lib().vpin_net_trace_image_instances(self.ctx.h, self.h, b, C.byref(hm), C.byref(ha)), "vpin_net_trace_image_instances")
@@ -280,6 +291,42 @@ def infer_multi(ctx, cfg, base_g, pubs, key_of_image, c1, c2, keys, bias_rs, rou
                                           batch=len(key_of_image), pubs=list(pubs), key_of_image=key_of_image))
 
 
+def round_images():
+    """inside a round callback: the slots of the images whose values are at hand, position after position (vpin_net_round_images)"""
+    p, n = C.c_void_p(), C.c_size_t()
+    _chk(lib().vpin_net_round_images(C.byref(p), C.byref(n)), "vpin_net_round_images")
+    return [int(v) for v in (C.c_uint32 * n.value).from_address(p.value)]
+
+
+def round_drop_images(slots, code, text):
+    """inside a round callback of infer_isolated: these images leave the batch after the round (vpin_net_round_drop_images)"""
+    arr = (C.c_uint32 * max(1, len(slots)))(*[int(v) for v in slots])
+    _chk(lib().vpin_net_round_drop_images(arr, len(slots), int(code), str(text).encode()), "vpin_net_round_drop_images")
+
+
+def infer_isolated(ctx, cfg, base_g, pubs, key_of_image, c1, c2, keys, bias_rs, round_fn, user=None):
+    """vpin_net_infer_isolated -> (Trace, statuses): infer_multi in which an image that makes a layer refuse, or that the round
+    function drops, leaves the batch while the others go on.  statuses: per slot dict(code, layer, round, text), code 0 for an
+    image that stayed.  The round function sees the images round_images() names.  When nobody is left the VpinError carries the
+    statuses in `.statuses`"""
+    st = (NetImageStatus * max(1, len(key_of_image)))()
+    statuses = lambda: [dict(code=s.code, layer=s.layer, round=s.round, text=s.text.decode(errors="replace")) for s in st[:len(key_of_image)]]
+    try:
+        h = inference.run_infer("vpin_net_infer_isolated", ctx, cfg.c, c1, c2, base_g, None, keys, bias_rs, round_fn, user,
+                                batch=len(key_of_image), pubs=list(pubs), key_of_image=key_of_image, status=st)
+    except VpinError as e:
+        e.statuses = statuses()
+        raise
+    return Trace(ctx, h), statuses()
+
+
+def last_isolation():
+    """what the last infer_isolated on this thread did: images a layer refused, images dropped in a round, layer calls repeated"""
+    out = (C.c_uint64 * 3)()
+    lib().vpin_net_last_isolation(out)
+    return dict(zip(("refused", "dropped", "repeats"), (int(v) for v in out)))
+
+
 def schedule(cfg, batch=1):
     """what the client of `cfg` agrees to: per round (flags, shift_bits, cnt) from the layers' rounds and vpin_net_cfg_counts, cnt
     times the images of a batch.  The client holds its own copy and answers no round that differs (Client.run)"""
@@ -306,20 +353,23 @@ def serve(ctx, cfg, wire, keys, bias_rs, max_batch=1):
     return Trace(ctx, h)
 
 
-STAGE_DONE, STAGE_ADMISSION, STAGE_SERVER = -1, -2, -3
+STAGE_DONE, STAGE_ADMISSION, STAGE_SERVER, STAGE_LAYER = -1, -2, -3, -4
 
 
 class Server:
     """vpin_net_server: the server's endpoint for several clients in one batched inference.  Checks `cfg` and builds the table of G
     once; every `serve` is then one inference over the images of all the wires it is given, each client under its own key, with no
-    table of any client's H"""
+    table of any client's H.  isolation=True: a client one of whose images makes a layer refuse is dropped (STAGE_LAYER) and a client
+    dropped in a round leaves the batch, while the others finish (vpin_net_server_set_isolation)"""
 
-    def __init__(self, ctx, cfg, max_batch):
+    def __init__(self, ctx, cfg, max_batch, isolation=False):
         self.ctx, self.cfg, self.max_batch = ctx, cfg, max_batch
         self._cfg_c = cfg.c  # the server borrows it until free
         h = C.c_void_p()
         _chk(lib().vpin_net_server_create(ctx.h, C.byref(self._cfg_c), max_batch, C.byref(h)), "vpin_net_server_create")
         self.h = h
+        if isolation:
+            _chk(lib().vpin_net_server_set_isolation(h, 1), "vpin_net_server_set_isolation")
 
     def serve(self, wires, keys, bias_rs):
         """vpin_net_serve_multi over vpin_amd.wire.Wire objects -> (Trace, statuses).  keys, bias_rs: flat, max_batch times one
@@ -345,6 +395,11 @@ class Server:
         out = (C.c_uint64 * 5)()
         _chk(lib().vpin_net_server_stats(self.h, out), "vpin_net_server_stats")
         return dict(zip(("calls", "clients_admitted", "clients_served", "images", "base_tables_built"), (int(v) for v in out)))
+
+    def stats_isolation(self):
+        out = (C.c_uint64 * 3)()
+        _chk(lib().vpin_net_server_stats_isolation(self.h, out), "vpin_net_server_stats_isolation")
+        return dict(zip(("images_refused", "images_compacted", "layer_calls_repeated"), (int(v) for v in out)))
 
     def free(self):
         if self.h:
