@@ -266,6 +266,12 @@ int vpin_hyrax_commit_pippenger(vpin_ctx* ctx, const vpin_gens* g, const vpin_ta
 int vpin_hyrax_commit_pair(vpin_ctx* ctx, const vpin_gens* g, const vpin_table* Za, const vpin_table* Zb,
                            const uint8_t* blinds_a, const uint8_t* blinds_b, size_t L, size_t blind_base,
                            uint8_t* out_a, uint8_t* out_b, uint8_t* out_sum);
+/* The same three outputs the way the provers form them: the two row MSMs without blinds first, then blind_i * g[blind_base]
+ * for the 2L blinds as single-base multiples (eight lanes per scalar) added per row.  Same bytes as vpin_hyrax_commit_pair;
+ * public so that the blind path of the provers can be driven with chosen blinds. */
+int vpin_hyrax_commit_pair_split(vpin_ctx* ctx, const vpin_gens* g, const vpin_table* Za, const vpin_table* Zb,
+                                 const uint8_t* blinds_a, const uint8_t* blinds_b, size_t L, size_t blind_base,
+                                 uint8_t* out_a, uint8_t* out_b, uint8_t* out_sum);
 /* GroupElement::vartime_multiscalar_mul (Spartan/src/group.rs:103-122) over a prefix of the
  * generator stream: out[r] = sum_{j<ncols} s[r][j] * g[j] for `rows` independent rows of
  * host scalars (Montgomery).  Either output may be NULL. */

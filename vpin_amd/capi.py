@@ -1012,6 +1012,19 @@ class Context:
                                           *[o.ctypes.data_as(C.c_void_p) for o in outs]), "vpin_hyrax_commit_pair")
         return outs
 
+    def hyrax_commit_pair_split(self, gens, Za, Zb, blinds_a, blinds_b, blind_base):
+        """vpin_hyrax_commit_pair_split: the same outputs through the provers' split-phase path (blinds as single-base multiples)"""
+        ba = np.ascontiguousarray(blinds_a, dtype=np.uint64).reshape(-1, 4)
+        bb = np.ascontiguousarray(blinds_b, dtype=np.uint64).reshape(-1, 4)
+        Ls = ba.shape[0]
+        outs = [np.zeros((Ls, 32), dtype=np.uint8) for _ in range(3)]
+        L = lib()
+        L.vpin_hyrax_commit_pair_split.argtypes = [C.c_void_p] * 6 + [C.c_size_t, C.c_size_t] + [C.c_void_p] * 3
+        _chk(L.vpin_hyrax_commit_pair_split(self.h, gens.h, Za.h, Zb.h, ba.ctypes.data_as(C.c_void_p),
+                                            bb.ctypes.data_as(C.c_void_p), Ls, blind_base,
+                                            *[o.ctypes.data_as(C.c_void_p) for o in outs]), "vpin_hyrax_commit_pair_split")
+        return outs
+
     def gens_msm(self, gens, scalars, rows, ncols, want_xyzt=False):
         s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(rows * ncols, 4)
         out = np.zeros((rows, 32), dtype=np.uint8)

@@ -2061,6 +2061,17 @@ int commit_pair_finish(vpin_ctx* c, const vpin_gens* g, CommitPairState* st, con
 
 extern "C" {
 
+// vpin_hyrax_commit_pair through the provers' split-phase path (commit_pair_begin / commit_pair_finish): the blind terms are
+// single_base_mul_kernel's
+int vpin_hyrax_commit_pair_split(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za, const vpin_table* Zb,
+                                 const uint8_t* blinds_a, const uint8_t* blinds_b, size_t L, size_t blind_base,
+                                 uint8_t* out_a, uint8_t* out_b, uint8_t* out_sum) {
+  if (!c || !g || !Za || !Zb || !Za->d || !Zb->d || !blinds_a || !blinds_b || !out_a || !out_b || !out_sum || L == 0) return VPIN_EINVAL;
+  vpin::CommitPairState* st = nullptr;
+  if (const int rc = vpin::commit_pair_begin(c, g, Za, Zb, L, &st, 0, (size_t)-1, 1)) return rc;
+  return vpin::commit_pair_finish(c, g, st, blinds_a, blinds_b, blind_base, out_a, out_b, out_sum);
+}
+
 int vpin_gens_msm(vpin_ctx* c, const vpin_gens* g, const uint8_t* scalars_mont, size_t rows, size_t ncols,
                   uint8_t* out_compressed, uint8_t* out_xyzt) {
   if (!c || !g || !scalars_mont || rows == 0 || ncols == 0 || (!out_compressed && !out_xyzt)) return VPIN_EINVAL;
