@@ -88,6 +88,10 @@ int vpin_ctx_set_shared_device(vpin_ctx* ctx, int on);
 unsigned long long vpin_ctx_strip_rows_taken(vpin_ctx* ctx);
 /* rows committed through the row-table kernels so far (tests: the path under test is the one that ran) */
 unsigned long long vpin_ctx_row_table_rows(vpin_ctx* ctx);
+/* scalars (rows x columns, a blind column included) from which a row commitment on this context goes to the row-table kernels
+ * when its stream has a row table: the library's default, or VPIN_MSM_ROW_MIN when that is set (read per call).  part_short != 0:
+ * for the callers whose scalars are partly short (the provers' witness commitments).  0 for a NULL ctx. */
+size_t vpin_msm_row_min_scalars(vpin_ctx* ctx, int part_short);
 /* row chunks the bucket method (vpin_hyrax_commit_pippenger, VPIN_MSM_PIPPENGER) has launched on this context: a commitment
  * whose digit buffer would pass 2 GiB takes its rows in several (the 2^14 x 2^15 polynomials of a 2^25-constraint instance: 15) */
 unsigned long long vpin_ctx_pip_row_chunks(vpin_ctx* ctx);
@@ -230,7 +234,7 @@ size_t vpin_gens_count(const vpin_gens* g);
  * nb generators plus the prefix-sum bases S_k = g_0 + ... + g_{2^k - 1} behind them. */
 int vpin_gens_layout(const vpin_gens* g, size_t out[6]);
 /* The row table beside it, if the table has one: out = {c_row, W_row, bases covered, columns per segment of the row kernel}.
- * T1[j][k] = (k+1) g_j for one window of c_row bits per generator; the row commitments of 2^24 scalars and more accumulate one
+ * T1[j][k] = (k+1) g_j for one window of c_row bits per generator; the row commitments of vpin_msm_row_min_scalars and more accumulate one
  * sum per window from it and apply the powers of two once per row.  All 0 for a table without one. */
 int vpin_gens_row_layout(const vpin_gens* g, size_t out[4]);
 /* TEST ENTRY POINT, not for callers: the provers reach this commitment through vpin_snark_prove*; it validates its indices on the

@@ -40,7 +40,7 @@ def main():
         g = ctx.gens_create(xyzt)
         t_build = time.perf_counter() - t0
         blinds = np.zeros((L, 4), dtype=np.uint64)
-        sub = ctx.wrap(tZ.device_ptr(), L * R) if L * R != n else tZ
+        sub = ctx.wrap(tZ.device_ptr, L * R) if L * R != n else tZ
         ctx.hyrax_commit(g, sub, blinds, R + 1)
         ctx.prof_reset(); ctx.prof_enable(True)
         for _ in range(args.reps):

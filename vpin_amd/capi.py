@@ -845,6 +845,14 @@ class Context:
         L.vpin_ctx_row_table_rows.restype = C.c_ulonglong
         return int(L.vpin_ctx_row_table_rows(self.h))
 
+    def msm_row_min_scalars(self, part_short=False):
+        """scalars from which a row commitment on this context takes the row-table kernels; part_short: of the provers' witness
+        commitments (vpin_msm_row_min_scalars)"""
+        L = lib()
+        L.vpin_msm_row_min_scalars.argtypes = [C.c_void_p, C.c_int]
+        L.vpin_msm_row_min_scalars.restype = C.c_size_t
+        return int(L.vpin_msm_row_min_scalars(self.h, 1 if part_short else 0))
+
     def strip_rows_taken(self):
         """rows handed to the row-per-lane commitment kernel so far (vpin_ctx_strip_rows_taken)"""
         L = lib()

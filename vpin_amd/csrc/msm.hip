@@ -22,7 +22,7 @@
 // lane and window, msm_rows_finish_kernel applies the powers of two once per ROW (c (W - 1) doublings against the 2^13..2^14
 // scalars x 16 additions of the row: free).  A folded scalar then costs 16 additions instead of 21, and the multi-window table,
 // narrowed to 8 bits, is left to the kernels that multiply one scalar by one base (bullet rounds, few-row MSMs, blind terms,
-// hot-column tables, constant rows).  Commitments below 2^24 scalars, a rank's share of a split commitment and tables built
+// hot-column tables, constant rows).  Commitments below row_table_min_scalars (2^20 scalars), a rank's share of a split commitment and tables built
 // through the public entry points keep the multi-window walk.
 #include <algorithm>
 #include <atomic>
@@ -1269,8 +1269,9 @@ static bool row_table_off() {
   const char* e = getenv("VPIN_ROW_TABLE");
   return e && atoi(e) == 0;
 }
-// generators below which a stream gets no row table by policy: the row-table kernels take commitments of 2^24 scalars and more
-// (row_table_min_scalars), and a stream this short commits no such polynomial
+// generators below which a stream gets no row table by policy.  Such a stream serves polynomials of up to 2^22 scalars, some of
+// them above row_table_min_scalars (2^20): the bound is kept as it was because a row table narrows the stream's multi-window
+// table to 8 bits for everything else it serves, which has not been measured for a process of small instances alone
 constexpr size_t kRowTableMinBases = 4096;
 
 static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, size_t budget, int cmax, bool row_policy, vpin_gens** out) {
@@ -1322,7 +1323,7 @@ static int gens_build_once(vpin_ctx* c, const uint8_t* gens_xyzt, size_t nb, siz
   // multiply ONE scalar by one base (bullet rounds, few-row MSMs, blind terms, hot-column tables, constant rows), which spread
   // a scalar's windows over eight lanes: 32 windows of 8 bits are four per lane, as 29 of 9 bits would be.
   // By policy only for the provers' tables of a long-lived process (vpin::gens_shared_rows: sat_prepare and the SPARK views) and
-  // only for streams long enough to commit 2^24 scalars at once; when no such table fits, the geometry is exactly the one above.
+  // only for streams of kRowTableMinBases generators and more; when no such table fits, the geometry is exactly the one above.
   const size_t n_row = std::min(nb, kSplitBases);
   int c_row = row_table_forced_bits();
   if (!c_row && row_policy && !row_table_off() && c->expected_proofs == 0 && nb >= kRowTableMinBases) {
@@ -1585,21 +1586,45 @@ static inline RowTable row_view(const vpin_gens* g) {
   return RowTable{g->table_row, g->n_row, g->c_row, g->W_row, g->E_row, g->s32};
 }
 
-// Scalars from which a commitment goes to the row-table kernels.  Their finishing pass is one lane per row running c (W - 1) = 240
-// doublings and the chunk sums in sequence: 0.56 .. 1.54 ms, 0.73 ms on average (profiles/r12_kernel_trace_row_table.txt), whatever
-// the size, against 24 % of a walk that takes ~1 ms per 2^20 full-width scalars: at 2^24 scalars the pass costs a fifth of what the
-// table saves, at 2^22 most of it.  The threshold was set before that measurement, assuming 1.4 ms, and has not been swept.  VPIN_MSM_ROW_MIN = n overrides (tests: 0; read per call);
-// VPIN_MSM_ROW_TABLE = 0 keeps every commitment on the multi-window walk (A/B runs and parity tests; read per call).
-static size_t row_table_min_scalars() {
+// Scalars from which a commitment goes to the row-table kernels.  The row table saves W - W_row = 32 - 16 additions per
+// full-width scalar against the 8-bit multi-window table beside it; its finishing pass costs one lane per row running
+// c (W_row - 1) = 240 doublings in sequence, ~0.5 ms whatever the size (that floor stays).  One commitment alone, walk against row
+// table, host clock around the call in ms (tools/sweep_row_min.py -> profiles/r20_row_min_sweep.txt; Hyrax shape with a blind
+// column / derefs shape without):
+//   scalars   whole chip (256 CUs): walk -> row table   8 CUs per XCD (64 CUs): walk -> row table
+//   2^17      0.47 -> 0.85 / 0.37 -> 0.83               0.95 -> 1.07 / 0.66 -> 0.98
+//   2^18      0.64 -> 0.94 / 0.46 -> 0.91               1.62 -> 1.39 / 1.11 -> 1.22
+//   2^19      1.00 -> 1.13 / 0.73 -> 1.08               2.74 -> 1.98 / 1.94 -> 1.66
+//   2^20      1.72 -> 1.46 / 1.25 -> 1.27               5.02 -> 3.16 / 3.61 -> 2.54
+//   2^21      3.14 -> 2.25 / 2.31 -> 1.86               9.42 -> 5.41 / 6.91 -> 4.26
+//   2^22      5.84 -> 3.85 / 4.37 -> 3.07               18.6 -> 9.97 / 13.6 -> 7.65
+// The default is the first size at which neither shape loses: 2^20 scalars, and 2^19 on a context confined to a quarter of the
+// chip or less (bench.py's lanes of the smaller instances), where the same saving is worth four times the time.  The four-lane
+// step at thresholds 2^24 / 2^22 / 2^20 / 2^18 / 2^16: 356.8 and 345.9 / 336.6 / 328.1 / 330.4 / 329.4 ms
+// (profiles/r20_ab_row_min.txt): nothing is gained below 2^20.
+// VPIN_MSM_ROW_MIN = n overrides (tests: 0; read per call); VPIN_MSM_ROW_TABLE = 0 keeps every commitment on the multi-window
+// walk (A/B runs and parity tests; read per call).
+// part_short: the caller's scalars are a mix of full-width and short ones (the two halves of a point-mult witness: coordinates
+// beside bits and small constants).  The walk skips a short scalar's empty upper windows, so the row table saves less per scalar:
+// the five point-mult instances of the LeNet trace proven one at a time on the whole chip, witness commitments (two polynomials)
+// walk -> row table: 2^20..2^21 scalars each (L1-, L6-, L7-mult) 1.54 -> 2.13, 1.60 -> 2.10, 1.32 -> 1.95 ms; 2^22 and more
+// (L3-mult) 3.60 -> 3.13 ms.  Such a caller takes the row table from 2^22 scalars.  On the quarter-chip lanes of the four-lane step
+// the same commitments gain at every size (L6-mult 5.2 -> 3.7, L3-mult 14.7 -> 9.7 ms): there the threshold is the one above.
+constexpr size_t kRowMinScalars = (size_t)1 << 20, kRowMinScalarsQuarter = (size_t)1 << 19, kRowMinScalarsPartShort = (size_t)1 << 22;
+static size_t row_table_min_scalars(const vpin_ctx* c, bool part_short = false) {
   const char* e = getenv("VPIN_MSM_ROW_MIN");
-  return e ? (size_t)atoll(e) : (size_t)1 << 24;
+  if (e) return (size_t)atoll(e);
+  if (c->cu_masked && c->num_cus <= 64) return kRowMinScalarsQuarter;
+  return part_short ? kRowMinScalarsPartShort : kRowMinScalars;
 }
-static bool row_table_use(const vpin_ctx* c, const vpin_gens* g, size_t rows, size_t ncols, int n_extra, size_t extra_base0) {
+size_t vpin_msm_row_min_scalars(vpin_ctx* c, int part_short) { return c ? row_table_min_scalars(c, part_short != 0) : 0; }
+static bool row_table_use(const vpin_ctx* c, const vpin_gens* g, size_t rows, size_t ncols, int n_extra, size_t extra_base0,
+                          bool part_short = false) {
   if (!g->table_row || c->comm != nullptr) return false;  // a rank's share of a split commitment keeps the walk
   const char* e = getenv("VPIN_MSM_ROW_TABLE");
   if (e && atoi(e) == 0) return false;
   if (ncols > g->n_row || (n_extra && extra_base0 + (size_t)n_extra > g->n_row)) return false;
-  return rows * (ncols + (size_t)n_extra) >= row_table_min_scalars();
+  return rows * (ncols + (size_t)n_extra) >= row_table_min_scalars(c, part_short);
 }
 
 // rows x (ncols + n_extra) scalars over the row table: msm_rows_win_kernel on `chunks` column chunks per row, then the finishing
@@ -1631,7 +1656,8 @@ static int msm_rows_win(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t ro
 // walk_only: the caller knows its scalars to be mostly short (addresses, counters): the multi-window walk, where a lane skips a
 // short scalar's empty upper windows; in the row-table kernel those windows' lanes would idle
 static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols,
-                    const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points, bool walk_only = false) {
+                    const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points, bool walk_only = false,
+                    bool part_short = false) {
   if (const int pm = pip_mode())
     if (n_extra <= 1 && ncols + (size_t)n_extra <= 32768)
       return msm_rows_pip(c, g, dZ, rows, stride, ncols, d_extra, n_extra, extra_base0, pm < 0 ? 0 : pm, d_points);
@@ -1654,7 +1680,7 @@ static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, 
     chunks = (int)(want < most ? want : most);
     if (chunks < 1) chunks = 1;
   }
-  const bool use_row = !walk_only && row_table_use(c, g, rows, ncols, n_extra, extra_base0);
+  const bool use_row = !walk_only && row_table_use(c, g, rows, ncols, n_extra, extra_base0, part_short);
   DevBuf parts(c);
   ge_ext* dst = d_points;
   if (chunks > 1 && !use_row) {
@@ -2029,8 +2055,9 @@ int commit_pair_begin(vpin_ctx* c, const vpin_gens* g, const vpin_table* Za, con
   st->L = L;
   if (st->pts.alloc(5 * L * sizeof(ge_ext))) { delete st; return VPIN_ENOMEM; }
   ge_ext* pts = (ge_ext*)st->pts.p;
-  int rc = msm_rows(c, g, Za->d + row0 * R, L, row_step * R, R, nullptr, 0, 0, pts);
-  if (!rc) rc = msm_rows(c, g, Zb->d + row0 * R, L, row_step * R, R, nullptr, 0, 0, pts + L);
+  // the provers' witness halves: part_short (see row_table_min_scalars)
+  int rc = msm_rows(c, g, Za->d + row0 * R, L, row_step * R, R, nullptr, 0, 0, pts, false, true);
+  if (!rc) rc = msm_rows(c, g, Zb->d + row0 * R, L, row_step * R, R, nullptr, 0, 0, pts + L, false, true);
   if (rc) { delete st; return rc; }
   *out = st;
   return VPIN_OK;
