@@ -1180,7 +1180,8 @@ int vpin_net_client_round(void* user, int round, int flags, int shift_bits, cons
  * The reference's Server.py / Client.py are two processes (send_data_in_chunks / receive_data_in_chunks); here the server loop
  * (vpin_net_serve) and the client (vpin_net_client_run) meet over any byte stream the caller has: vpin_wire_round is the round
  * callback of vpin_net_infer on the server's side, vpin_net_client_round is called in a loop on the client's.  The library opens,
- * listens on and connects nothing, and sends no proofs; there is no authentication.
+ * listens on and connects nothing; there is no authentication.  The frames carry no proofs: those follow DONE
+ * on the same stream as records of their own (ABI 10, below: vpin_net_send_proofs, vpin_net_client_verify).
  *
  * A packed point is one 256-bit little-endian integer (E2's group order is prime and the only multiple of itself inside the Hasse
  * interval: every point of the curve is in the group, so x and a sign say it all):
@@ -1362,6 +1363,103 @@ typedef struct vpin_wire_round_spec {
 int vpin_net_client_run(vpin_net_client* cl, vpin_wire* w, const int64_t* image, const uint8_t* image_r_le32, size_t n_input,
                         const vpin_wire_round_spec* schedule, size_t n_rounds);
 
+/* ---- proofs over the wire (ABI 10) ----------------------------------------------------------------------------------------------
+ * After DONE the stream is still open (the library closes nothing), and the server can send each client the proofs of its own
+ * images: the reference's my_lib_verify on two proofs per label, one saying that the server knows a witness of n_mult point
+ * multiplications that satisfies the gadget, one saying the same for n_add point additions, each under the Hyrax commitments
+ * comm_para and comm_input it sends.
+ * What acceptance means, and what it does not: as in the reference, vars_input holds the server's intermediate values, and
+ * NOTHING ties the committed points to this session's ciphertexts.  An accepted record says "a satisfying witness of that many
+ * operations exists and the server knows it", not "it is the witness of my inference".  No binding is invented here.
+ * The R1CS itself is not left to the server: the instances' A, B, C depend only on the kind and the number of operations
+ * (point_mult.rs:61-325 and point_addition.rs:67-153 build inst_1 before any witness value is used, and SNARK::encode takes no
+ * randomness), so the client DERIVES the computation commitment and the public inputs from (is_mult, n_ops) on its own GPU and
+ * compares the server's comm with its own byte for byte.  There is no mode that takes comm from the server: such a client would
+ * accept a proof of a trivial instance.
+ *
+ * Proofs are no VPW1 frames.  A record has a header of 40 bytes, little-endian, and a payload:
+ *   magic "VPP1" | kind u8 | is_mult u8 | reserved u16 = 0 | image u32 | label u32 | n_ops u64 | proof_len u64 | comm_len u64
+ *   PROOF  image: the index among the client's own images, in image order; label: 0 for the image's one label, 1 + layer for a
+ *          per-layer label; payload proof | comm | comm_para | comm_input, the last two of vpin_gadget_vars_rows(is_mult, n_ops)
+ *          rows of 32 bytes each (the rule of vpin_snark_verify_batch); proof_len is at most vpin_gadget_proof_max_bytes and
+ *          comm_len exactly vpin_gadget_comm_bytes of the shape
+ *   END    image: the number of PROOF records sent; every other field zero; no payload
+ *   ERROR  proof_len: the payload's length; the payload an int32 code and at most VPIN_WIRE_MAX_TEXT bytes of text; every other
+ *          field zero
+ * vpin_proof_header_encode and vpin_proof_header_decode apply the same rules and answer VPIN_EINVAL naming the one broken: a wrong
+ * magic, an unknown kind, reserved bytes that are not zero, is_mult > 1, n_ops = 0 or above VPIN_PROOF_MAX_OPS, proof_len above
+ * what the shape allows, comm_len other than the shape's, and for END and ERROR a field that must be zero and is not (ERROR: a
+ * proof_len outside 4 .. 4 + VPIN_WIRE_MAX_TEXT).  No receiver allocates before decode has accepted the header, and what it then
+ * allocates is bounded by the shape.  vpin_proof_payload_len: the payload's bytes under an accepted header.
+ * vpin_proof_send / vpin_proof_recv move one record over a vpin_wire and count into its stats as frames; recv decodes the header
+ * first and answers VPIN_EINVAL, reading no payload, when the payload is longer than cap. */
+#define VPIN_PROOF_RECORD 1
+#define VPIN_PROOF_END 2
+#define VPIN_PROOF_ERROR 3
+#define VPIN_PROOF_HEADER_LEN 40
+#define VPIN_PROOF_MAX_OPS ((uint64_t)1 << 24)
+typedef struct vpin_proof_header {
+  uint8_t kind, is_mult;
+  uint32_t image, label;
+  uint64_t n_ops, proof_len, comm_len;
+} vpin_proof_header;
+int vpin_proof_header_encode(const vpin_proof_header* h, uint8_t out40[VPIN_PROOF_HEADER_LEN]);
+int vpin_proof_header_decode(const uint8_t in40[VPIN_PROOF_HEADER_LEN], vpin_proof_header* h);
+uint64_t vpin_proof_payload_len(const vpin_proof_header* h);
+int vpin_proof_send(vpin_wire* w, const vpin_proof_header* h, const uint8_t* payload);
+int vpin_proof_recv(vpin_wire* w, vpin_proof_header* h, uint8_t* payload, size_t cap);
+
+/* The server's side.  vpin_net_send_proofs walks the images [first_image, first_image + n_images) of a trace in image order.
+ * per_layer = 0: the image's label (the lists of vpin_net_trace_image_label, as vpin_net_trace_image_instances takes them);
+ * per_layer = 1: every layer of vpin_net_trace_image_layer in layer order (as vpin_conv_trace_instances), label 1 + layer.  The
+ * multiplication instance comes before the addition instance; one that does not exist (a pooling label, a 1 x 1 filter) is
+ * skipped.  Per instance: build it, vpin_dev_instance_is_sat (a 0 answers VPIN_EVERIFY, sends an ERROR record, and nothing more
+ * is sent), vpin_snark_prove_dev, one PROOF record, free -- the next instance is built after that, so an image never holds two
+ * instances at once.  At the end END.  A failure of its own goes to the peer as an ERROR record, best effort.
+ * Seeds: the 128 bytes SHAKE256(master_seed64 | "vPIN/wire-proof" | le32(slot) | le32(label) | u8(is_mult)), slot = first_image +
+ * image; the first 64 are seed_commit, the last 64 seed_proof.  master_seed64 = NULL: 64 bytes from the operating system.
+ * ms_out (may be NULL): host-clock ms of instance build (with is_sat), prove and send. */
+int vpin_net_send_proofs(vpin_ctx* ctx, const vpin_net_trace* t, size_t first_image, size_t n_images, vpin_wire* w, int per_layer,
+                         const uint8_t master_seed64[64], double ms_out[3]);
+/* After vpin_net_serve_multi, with the status it wrote: every wire with code VPIN_OK and stage VPIN_NET_STAGE_DONE gets the proofs
+ * of its slots [first_image, first_image + n_images), with isolation on too.  A wire that fails here is reported with its code and
+ * text at the stage VPIN_NET_STAGE_PROOFS; the others still get theirs.  VPIN_OK when at least one client received END;
+ * VPIN_ESHAPE when no wire was served to DONE, otherwise the last failing wire's code. */
+#define VPIN_NET_STAGE_PROOFS (-5)
+int vpin_net_server_send_proofs(vpin_net_server* s, const vpin_net_trace* t, vpin_wire* const* wires, size_t n_wires,
+                                vpin_net_peer_status* status, int per_layer, const uint8_t master_seed64[64]);
+
+/* The client's side.  A vpin_net_verifier owns, per (is_mult, n_ops), the derived comm bytes and inputs.  vpin_net_verifier_shape
+ * derives a shape when first asked: the device gadget over n_ops placeholder operations (points as vpin_synthetic_points makes
+ * them, odd weights; for additions operands whose sum is neither a doubling nor the identity), vpin_spark_encode_dev, the
+ * commitment and vpin_dev_instance_inputs kept (borrowed until vpin_net_verifier_free), the instance and the decommitment freed.
+ * A second request is a lookup: a returning client, or one with many images, derives each shape once.
+ * vpin_net_verifier_stats: out = {shapes derived, lookups, proofs accepted, proofs rejected}.  vpin_net_verifier_timings: host-clock
+ * ms of the last vpin_net_client_verify: receiving, deriving shapes and comparing commitments, the batch verification.
+ * vpin_net_client_verify reads the records behind DONE.  The expectation list is the CLIENT's, as the round schedule is and for the
+ * same reason: the same for every image, in the order the server sends, filled from vpin_net_cfg_counts on a configuration of the
+ * same architecture.  Each record must be the next expected (image, label, is_mult, n_ops); otherwise the client sends an ERROR
+ * record and returns VPIN_ESHAPE naming both sides ("vpin_net_client_verify: image 1, label 0: the server proves 131
+ * multiplications, the expectation says 130") before the payload is read or anything is allocated for that record.  After the last
+ * record END must follow with the right count.  A peer's ERROR is VPIN_ECOMM quoting it.
+ * A record whose comm is not the derived one is rejected without verification (ok_out 0, "not the shape's commitment"); all the
+ * others go through ONE vpin_snark_verify_batch with the derived comm and inputs (seed32 as there, may be NULL).  ok_out holds
+ * n_images * n_expect verdicts, image-major.  VPIN_OK when every one is 1, VPIN_EVERIFY otherwise. */
+typedef struct vpin_net_verifier vpin_net_verifier;
+int vpin_net_verifier_create(vpin_ctx* ctx, vpin_net_verifier** out);
+void vpin_net_verifier_free(vpin_net_verifier* v);
+int vpin_net_verifier_shape(vpin_net_verifier* v, int is_mult, size_t n_ops, const uint8_t** comm, size_t* comm_len,
+                            const uint8_t** inputs, size_t* num_inputs);
+int vpin_net_verifier_stats(const vpin_net_verifier* v, uint64_t out[4]);
+int vpin_net_verifier_timings(const vpin_net_verifier* v, double out[3]);
+typedef struct vpin_proof_expect {
+  uint32_t label;
+  uint8_t is_mult;
+  uint64_t n_ops;
+} vpin_proof_expect;
+int vpin_net_client_verify(vpin_net_verifier* v, vpin_wire* w, size_t n_images, const vpin_proof_expect* expect, size_t n_expect,
+                           const uint8_t seed32[32], uint8_t* ok_out /* n_images * n_expect */);
+
 /* BulletReductionProof::prove, Spartan/src/nizk/bullet.rs:32-132, with the round challenges GIVEN (u_mont: log2(R)
  * Montgomery scalars) instead of drawn from a transcript, over the R stream generators of `g` only (the caller's
  * c*Q and blind*H terms are host work: nizk/mod.rs:447-531).  x = the vector being reduced (a in bullet.rs), a = the
@@ -1377,6 +1475,11 @@ int vpin_bullet_reduce(vpin_ctx* c, const vpin_gens* g, const uint8_t* x_mont, c
  * padded num_cons and num_vars and the non-zero entries of A, B, C (point_mult.rs:61-67, point_addition.rs:67-70) -- enough
  * for vpin_sat_prepare / vpin_spark_prepare before the witness has been read */
 int vpin_gadget_shape(int is_mult, size_t n_ops, size_t* num_cons, size_t* num_vars, size_t nnz[3]);
+/* (ABI 10) what vpin_dev_instance_proof_max_bytes and vpin_dev_instance_comm_bytes answer for the instance of that shape, and
+ * the rows of its comm_para / comm_input, from (is_mult, n_ops) alone: what bounds a proof record before anything is allocated */
+size_t vpin_gadget_proof_max_bytes(int is_mult, size_t n_ops);
+size_t vpin_gadget_comm_bytes(int is_mult, size_t n_ops);
+size_t vpin_gadget_vars_rows(int is_mult, size_t n_ops);
 /* MultiCommitGens::new (Spartan/src/commitments.rs:20-38): first nb points of the stream */
 int vpin_host_gens_derive(const char* label, size_t nb, uint8_t* out_xyzt /* nb*128 */);
 /* Merlin: Transcript::new(proto); append_message(label,msg); challenge_bytes(clabel,out) */

@@ -1,6 +1,6 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
 the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
-[--batch 1,2,4,..] [--clients 1,2,4,..] [--isolation] [--refuse 1]
+[--batch 1,2,4,..] [--clients 1,2,4,..] [--isolation] [--refuse 1] [--proofs]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
@@ -59,7 +59,8 @@ VERSION = sys.argv[1]
 WIRE = "--wire" in sys.argv
 BATCH = [int(b) for b in sys.argv[sys.argv.index("--batch") + 1].split(",")] if "--batch" in sys.argv else None
 CLIENTS = [int(b) for b in sys.argv[sys.argv.index("--clients") + 1].split(",")] if "--clients" in sys.argv else None
-REPS, NB_LOG = opt("--reps", 11 if WIRE or BATCH or CLIENTS else 5), opt("--nb", 24)
+WIRE_PROOFS = "--proofs" in sys.argv
+REPS, NB_LOG = opt("--reps", 3 if WIRE_PROOFS else 11 if WIRE or BATCH or CLIENTS else 5), opt("--nb", 24)
 PROOFS = "--no-proofs" not in sys.argv
 ISOLATION, REFUSE = "--isolation" in sys.argv, opt("--refuse", 0)
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
@@ -91,6 +92,11 @@ def main():
     ctx = vpin_amd.Context(0)
     counts, giants = cfg.counts(), cfg.max_giants()
     assert counts == dict(want, rounds=len(giants))
+    if WIRE_PROOFS:
+        assert (WIRE or CLIENTS) and not BATCH and not REFUSE, "--proofs goes with --wire or with --clients"
+        proofs_mode(ctx, cfg, model, counts, giants, image, TM.net_plaintext if VERSION == "lenet5" else NM.plaintext)
+        ctx.close()
+        return
     if BATCH or CLIENTS:
         plain = TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
         (refuse_mode if CLIENTS and REFUSE else clients_mode if CLIENTS else batch_mode)(ctx, cfg, model, counts, giants, image, plain)
@@ -499,6 +505,101 @@ def clients_mode(ctx, cfg, model, counts, giants, image, plain):
               (cnt, rng(tt[1:], 1), len(pubs), rng(tk[1:], 1), rng(t1[1:], 1)))
     base_h.free()
     base_g.free()
+    for c in cctx:
+        c.close()
+
+
+def proofs_mode(ctx, cfg, model, counts, giants, image, plain):
+    """--wire --proofs (one client through vpin_net_serve and vpin_net_send_proofs) and --clients .. --proofs (K clients through
+    vpin_net_serve_multi and vpin_net_server_send_proofs): what the proofs behind DONE cost either side, per image"""
+    from vpin_amd import wire as W
+    top = max(CLIENTS) if CLIENTS else 1
+    assert top <= 8, "at most 8 clients: a context each beside the server's"
+    cctx = [vpin_amd.Context(0) for _ in range(top)]
+    sks = [(SK + 977 * k) % EL.ORDER for k in range(top)]
+    nr, size = len(giants), image.size
+    k_keys, r_bias, r_client = counts["prf_keys"], counts["bias_r"], counts["encryptions"] - size
+    images = [np.roll(image, (b % 8, b // 8), axis=(0, 1)) for b in range(top)]
+    expect_values = [plain(model, im) for im in images]
+    keys = [[NM.net_key(k_keys * b + i) for i in range(k_keys)] for b in range(top)]
+    image_rs = [EL.splitmix_scalars(SEEDS["image_r"] + 0x1000 * b, size) for b in range(top)]
+    bias_rs = [EL.splitmix_scalars(SEEDS["bias_r"] + 0x1000 * b, r_bias) for b in range(top)]
+    client_rs = [EL.splitmix_scalars(SEEDS["client_r"] + 0x1000 * b, r_client) for b in range(top)]
+    sched, expect = VN.schedule(cfg), VN.proof_expectation(cfg)
+    master, seed32 = bytes((7 * i + 1) % 256 for i in range(64)), bytes(range(32))
+    print("per image the server proves:", ", ".join("%d %s" % (n, "multiplications" if m else "additions") for _, m, n in expect))
+    rng = lambda xs: "%9.2f (%8.2f .. %8.2f)" % (statistics.median(xs), min(xs), max(xs)) if xs else "not measured"
+    for K in CLIENTS or [1]:
+        flat = lambda per: [v for one in per[:K] for v in one]
+        server = VN.Server(ctx, cfg, K) if CLIENTS else None
+        verifiers = [VN.Verifier(cctx[k]) for k in range(K)]  # kept across the runs: a returning client
+        rows = dict(build=[], prove=[], send=[], server=[], recv=[], verify=[], derive_first=[], derive_again=[], client=[])
+        per_image = 0
+        for rep in range(REPS + 1):
+            cl = [VN.Client(cctx[k], sks[k], 1 << NB_LOG, giants, client_rs[k]) for k in range(K)]
+            socks = [socket.socketpair() for _ in range(K)]
+            ws = [W.Wire.from_fds(a.fileno(), a.fileno(), 600000) for a, _ in socks]
+            wc = [W.Wire.from_fds(b.fileno(), b.fileno(), 600000) for _, b in socks]
+
+            def serve():
+                if CLIENTS:
+                    trace, statuses = server.serve(ws, flat(keys), flat(bias_rs))
+                    t0 = time.perf_counter()
+                    after = server.send_proofs(trace, ws, statuses, master_seed=master)
+                    assert all(s["code"] == 0 and s["stage"] == VN.STAGE_DONE for s in after)
+                    ms = dict(whole=(time.perf_counter() - t0) * 1e3)
+                else:
+                    trace = VN.serve(ctx, cfg, ws[0], keys[0], bias_rs[0])
+                    t0 = time.perf_counter()
+                    ms = VN.send_proofs(ctx, trace, ws[0], master_seed=master)
+                    ms["whole"] = (time.perf_counter() - t0) * 1e3
+                trace.free()
+                return ms
+
+            def peer(k):
+                _, values = cl[k].run(wc[k], images[k].reshape(-1), image_rs[k], sched)
+                before = wc[k].stats()["bytes_received"]
+                t0 = time.perf_counter()
+                ok = cl[k].verify(wc[k], verifiers[k], 1, expect, seed32)
+                whole = (time.perf_counter() - t0) * 1e3
+                assert ok == [[True] * len(expect)], verifiers[k].last_text
+                return values, verifiers[k].timings(), whole, wc[k].stats()["bytes_received"] - before
+
+            res = threads([serve] + [lambda k=k: peer(k) for k in range(K)])
+            if rep == 0:
+                for k in range(K):
+                    for r in range(nr):
+                        for i in range(2):
+                            assert [int(a) for a in res[1 + k][0][r][i]] == expect_values[k][i][r], "client %d round %d" % (k, r)
+                per_image = res[1][3]
+            for key in ("build", "prove", "send"):
+                if rep and key in res[0]:
+                    rows[key].append(res[0][key])
+            if rep:
+                rows["server"].append(res[0]["whole"] / K)
+            for k in range(K):
+                t = res[1 + k][1]
+                rows["derive_first" if rep == 0 else "derive_again"].append(t["derive"])
+                if rep:
+                    rows["recv"].append(t["recv"])
+                    rows["verify"].append(t["verify"])
+                    rows["client"].append(res[1 + k][2])
+            for x in cl + ws + wc:
+                x.free()
+            for a, b in socks:
+                a.close(); b.close()
+        stats_v = verifiers[0].stats()
+        assert stats_v["shapes_derived"] == len({(m, n) for _, m, n in expect}) and stats_v["rejected"] == 0
+        for v in verifiers:
+            v.free()
+        if server:
+            server.free()
+        print("K = %d client(s) of one image each; ms PER IMAGE, median (min .. max) over %d warm runs; all %d proofs accepted" %
+              (K, REPS, stats_v["accepted"] * K))
+        print("  the server: instance build %s, prove %s, send %s; the whole call %s" % (rng(rows["build"]), rng(rows["prove"]), rng(rows["send"]), rng(rows["server"])))
+        print("  the client: derive, first call %s, again %s; receive (waits for the prover) %s; verify %s; the whole call %s" %
+              (rng(rows["derive_first"]), rng(rows["derive_again"]), rng(rows["recv"]), rng(rows["verify"]), rng(rows["client"])))
+        print("  bytes of the records per image: %d (%d records and END)" % (per_image, len(expect)))
     for c in cctx:
         c.close()
 

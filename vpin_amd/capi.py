@@ -81,6 +81,17 @@ class WireHeader(C.Structure):
                 ("payload_len", C.c_uint64)]
 
 
+class ProofHeader(C.Structure):
+    """vpin_proof_header of include/vpin_hip.h"""
+    _fields_ = [("kind", C.c_uint8), ("is_mult", C.c_uint8), ("image", C.c_uint32), ("label", C.c_uint32), ("n_ops", C.c_uint64),
+                ("proof_len", C.c_uint64), ("comm_len", C.c_uint64)]
+
+
+class ProofExpect(C.Structure):
+    """vpin_proof_expect of include/vpin_hip.h"""
+    _fields_ = [("label", C.c_uint32), ("is_mult", C.c_uint8), ("n_ops", C.c_uint64)]
+
+
 class WireRoundSpec(C.Structure):
     """vpin_wire_round_spec of include/vpin_hip.h"""
     _fields_ = [("flags", C.c_int), ("shift_bits", C.c_int), ("cnt", C.c_size_t)]
@@ -321,6 +332,27 @@ def lib():
     L.vpin_net_server_stats_isolation.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vpin_net_serve_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(NetPeerStatus), C.POINTER(vp)]
     L.vpin_net_client_run.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(WireRoundSpec), C.c_size_t]
+    L.vpin_gadget_proof_max_bytes.argtypes = [C.c_int, C.c_size_t]
+    L.vpin_gadget_proof_max_bytes.restype = C.c_size_t
+    L.vpin_gadget_comm_bytes.argtypes = [C.c_int, C.c_size_t]
+    L.vpin_gadget_comm_bytes.restype = C.c_size_t
+    L.vpin_gadget_vars_rows.argtypes = [C.c_int, C.c_size_t]
+    L.vpin_gadget_vars_rows.restype = C.c_size_t
+    L.vpin_proof_header_encode.argtypes = [C.POINTER(ProofHeader), vp]
+    L.vpin_proof_header_decode.argtypes = [vp, C.POINTER(ProofHeader)]
+    L.vpin_proof_payload_len.argtypes = [C.POINTER(ProofHeader)]
+    L.vpin_proof_payload_len.restype = C.c_uint64
+    L.vpin_proof_send.argtypes = [vp, C.POINTER(ProofHeader), vp]
+    L.vpin_proof_recv.argtypes = [vp, C.POINTER(ProofHeader), vp, C.c_size_t]
+    L.vpin_net_send_proofs.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, vp, C.POINTER(C.c_double)]
+    L.vpin_net_server_send_proofs.argtypes = [vp, vp, C.POINTER(vp), C.c_size_t, C.POINTER(NetPeerStatus), C.c_int, vp]
+    L.vpin_net_verifier_create.argtypes = [vp, C.POINTER(vp)]
+    L.vpin_net_verifier_free.argtypes = [vp]
+    L.vpin_net_verifier_free.restype = None
+    L.vpin_net_verifier_shape.argtypes = [vp, C.c_int, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.vpin_net_verifier_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vpin_net_verifier_timings.argtypes = [vp, C.POINTER(C.c_double)]
+    L.vpin_net_client_verify.argtypes = [vp, vp, C.c_size_t, C.POINTER(ProofExpect), C.c_size_t, vp, vp]
     L.vpin_prof_enable.argtypes = [vp, C.c_int]
     L.vpin_prof_reset.argtypes = [vp]
     L.vpin_prof_read.argtypes = [vp, C.POINTER(KStat)]

@@ -1,8 +1,12 @@
 // infer_client.cpp -- the ready-made client of an encrypted inference, for any number of rounds: a vpin_lenet_round_fn over
 // vpin_e2_client_round (what main of the reference's Client.py does between two layers) around an object that owns the key, the
 // two base tables, the discrete-log table and the queue of encryption randomness, and keeps every round's values.
+// Behind DONE the same client verifies the proofs of its images (vpin_net_verifier, vpin_net_client_verify): the records come off
+// the stream through the state machine of wire_proof.cpp, the computation commitments are derived here, never taken from the peer.
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -182,6 +186,171 @@ int vpin_net_client_run(vpin_net_client* cl, vpin_wire* w, const int64_t* image,
     if ((rc = wr::send_frame_timed(w, slot, h, p.data()))) return failed(rc, why, false);
     done++;
   }
+}
+
+}  // extern "C"
+
+// what the verifier keeps of a shape
+struct DerivedShape {
+  std::vector<uint8_t> comm, inputs;  // bincode(R1CSCommitment); num_inputs x 32 bytes
+  size_t num_inputs = 0;
+};
+
+struct vpin_net_verifier {
+  vpin_ctx* ctx = nullptr;
+  std::map<std::pair<int, uint64_t>, DerivedShape> shapes;
+  uint64_t stats[4] = {0, 0, 0, 0};  // shapes derived, lookups, proofs accepted, proofs rejected
+  double ms[3] = {0.0, 0.0, 0.0};    // the last vpin_net_client_verify: receive, derive and compare, verify
+};
+
+namespace {
+
+// SNARK::encode of the gadget over n_ops placeholder operations: A, B, C depend on the kind and the count alone
+int derive_shape(vpin_ctx* c, int is_mult, size_t n_ops, DerivedShape* out) {
+  std::vector<uint8_t> x(32 * 2 * n_ops), y(32 * 2 * n_ops);
+  // 2 n distinct 64-bit multiples of G: P = the first n, R = the last n, so no R is P (a doubling) or -P (the identity)
+  int rc = vpin_synthetic_points(0x7650494e, 2 * n_ops, x.data(), y.data());
+  if (rc) return rc;
+  vpin_dev_instance* g = nullptr;
+  if (is_mult) {
+    std::vector<uint8_t> w(16 * n_ops, 0);
+    for (size_t i = 0; i < n_ops; i++) {
+      const uint64_t v = (0x9e3779b97f4a7c15ull * (i + 1)) | 1;
+      memcpy(&w[16 * i], &v, 8);
+    }
+    rc = vpin_gadget_point_mult_dev(c, w.data(), x.data(), y.data(), n_ops, &g);
+  } else {
+    const std::vector<uint8_t> rz(n_ops, 0);
+    rc = vpin_gadget_point_add_dev(c, x.data(), y.data(), x.data() + 32 * n_ops, y.data() + 32 * n_ops, rz.data(), n_ops, &g);
+  }
+  if (rc) return rc;
+  vpin_spark_decomm* d = nullptr;
+  out->comm.resize(vpin_dev_instance_comm_bytes(g));
+  size_t len = 0, nc = 0, nv = 0;
+  rc = vpin_spark_encode_dev(c, g, &d, out->comm.data(), out->comm.size(), &len);
+  if (!rc) {
+    out->comm.resize(len);
+    vpin_r1cs_dims(vpin_dev_instance_r1cs(g), &nc, &nv, &out->num_inputs);
+    const uint8_t* in = vpin_dev_instance_inputs(g);
+    if (out->num_inputs && in) out->inputs.assign(in, in + 32 * out->num_inputs);
+    else out->num_inputs = 0;
+  }
+  vpin_spark_decomm_free(c, d);
+  vpin_dev_instance_free(c, g);
+  return rc;
+}
+
+int shape_of(vpin_net_verifier* v, int is_mult, size_t n_ops, const DerivedShape** out) {
+  const auto key = std::make_pair(is_mult ? 1 : 0, (uint64_t)n_ops);
+  auto it = v->shapes.find(key);
+  if (it != v->shapes.end()) {
+    v->stats[1]++;
+    *out = &it->second;
+    return VPIN_OK;
+  }
+  DerivedShape s;
+  const int rc = derive_shape(v->ctx, key.first, n_ops, &s);
+  if (rc) return rc;
+  v->stats[0]++;
+  *out = &(v->shapes[key] = std::move(s));
+  return VPIN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpin_net_verifier_create(vpin_ctx* c, vpin_net_verifier** out) {
+  if (out) *out = nullptr;
+  if (!c || !out) return fail(VPIN_EINVAL, "vpin_net_verifier_create: null argument");
+  vpin_net_verifier* v = new (std::nothrow) vpin_net_verifier();
+  if (!v) return VPIN_ENOMEM;
+  v->ctx = c;
+  *out = v;
+  return VPIN_OK;
+}
+
+void vpin_net_verifier_free(vpin_net_verifier* v) { delete v; }
+
+int vpin_net_verifier_shape(vpin_net_verifier* v, int is_mult, size_t n_ops, const uint8_t** comm, size_t* comm_len, const uint8_t** inputs,
+                            size_t* num_inputs) {
+  if (!v || !comm || !comm_len || !inputs || !num_inputs) return fail(VPIN_EINVAL, "vpin_net_verifier_shape: null argument");
+  if (!n_ops || n_ops > VPIN_PROOF_MAX_OPS) return fail(VPIN_EINVAL, "vpin_net_verifier_shape: n_ops is outside 1 .. VPIN_PROOF_MAX_OPS");
+  const DerivedShape* s = nullptr;
+  const int rc = shape_of(v, is_mult, n_ops, &s);
+  if (rc) return rc;
+  *comm = s->comm.data(); *comm_len = s->comm.size();
+  *inputs = s->num_inputs ? s->inputs.data() : nullptr; *num_inputs = s->num_inputs;
+  return VPIN_OK;
+}
+
+int vpin_net_verifier_stats(const vpin_net_verifier* v, uint64_t out[4]) {
+  if (!v || !out) return fail(VPIN_EINVAL, "vpin_net_verifier_stats: null argument");
+  for (int i = 0; i < 4; i++) out[i] = v->stats[i];
+  return VPIN_OK;
+}
+
+int vpin_net_verifier_timings(const vpin_net_verifier* v, double out[3]) {
+  if (!v || !out) return fail(VPIN_EINVAL, "vpin_net_verifier_timings: null argument");
+  for (int i = 0; i < 3; i++) out[i] = v->ms[i];
+  return VPIN_OK;
+}
+
+int vpin_net_client_verify(vpin_net_verifier* v, vpin_wire* w, size_t n_images, const vpin_proof_expect* expect, size_t n_expect,
+                           const uint8_t seed32[32], uint8_t* ok_out) {
+  namespace wr = vpin::wire;
+  const char* who = "vpin_net_client_verify";
+  if (!v || !w || !expect || !ok_out) return fail(VPIN_EINVAL, "vpin_net_client_verify: null argument");
+  if (!n_images || n_images > VPIN_NET_MAX_BATCH || !n_expect || n_expect > 4096)
+    return fail(VPIN_EINVAL, "vpin_net_client_verify: n_images must be in 1 .. VPIN_NET_MAX_BATCH and n_expect in 1 .. 4096");
+  for (size_t k = 0; k < n_expect; k++)
+    if (expect[k].is_mult > 1 || !expect[k].n_ops || expect[k].n_ops > VPIN_PROOF_MAX_OPS)
+      return fail(VPIN_EINVAL, "vpin_net_client_verify: an expectation with is_mult above 1 or n_ops outside 1 .. VPIN_PROOF_MAX_OPS");
+  const size_t total = n_images * n_expect;
+  memset(ok_out, 0, total);
+  std::vector<wr::ProofRecord> recs;
+  v->ms[0] = v->ms[1] = v->ms[2] = 0.0;
+  int rc = wr::recv_proofs(w, who, n_images, expect, n_expect, &recs, &v->ms[0]);
+  if (rc) return rc;
+  wr::Lap lap;
+  // the computation commitment is the client's own: a record under another one is not looked at any further
+  std::vector<vpin_verify_item> items;
+  std::vector<size_t> at;
+  char why[200] = "";
+  for (size_t k = 0; k < total; k++) {
+    const wr::ProofRecord& r = recs[k];
+    const DerivedShape* s = nullptr;
+    if ((rc = shape_of(v, r.h.is_mult, (size_t)r.h.n_ops, &s))) return rc;
+    if (r.h.comm_len != s->comm.size() || memcmp(r.comm(), s->comm.data(), s->comm.size())) {
+      if (!why[0])
+        snprintf(why, sizeof why, "%s: image %u, label %u, %s: the server's commitment is not the shape's commitment", who, (unsigned)r.h.image,
+                 (unsigned)r.h.label, r.h.is_mult ? "multiplications" : "additions");
+      continue;
+    }
+    vpin_verify_item it;
+    it.proof = r.proof(); it.proof_len = (size_t)r.h.proof_len;
+    it.comm = s->comm.data(); it.comm_len = s->comm.size();
+    it.inputs = s->num_inputs ? s->inputs.data() : nullptr; it.num_inputs = s->num_inputs;
+    it.comm_para = r.comm_para(); it.comm_input = r.comm_input();
+    items.push_back(it);
+    at.push_back(k);
+  }
+  std::vector<uint8_t> ok(items.size(), 0);
+  v->ms[1] = lap();
+  rc = vpin_snark_verify_batch(v->ctx, items.data(), items.size(), seed32, ok.data());
+  v->ms[2] = lap();
+  if (rc && rc != VPIN_EVERIFY) return rc;
+  size_t good = 0;
+  for (size_t j = 0; j < items.size(); j++) {
+    ok_out[at[j]] = ok[j] ? 1 : 0;
+    good += ok[j] ? 1 : 0;
+    if (!ok[j] && !why[0])
+      snprintf(why, sizeof why, "%s: image %u, label %u, %s: the proof is rejected", who, (unsigned)recs[at[j]].h.image, (unsigned)recs[at[j]].h.label,
+               recs[at[j]].h.is_mult ? "multiplications" : "additions");
+  }
+  v->stats[2] += good;
+  v->stats[3] += total - good;
+  return good == total ? VPIN_OK : fail(VPIN_EVERIFY, why);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // The data-parallel work runs in the HIP kernels (sumcheck.hip, msm.hip, poly.hip); this file
 // owns the strictly sequential part: the Merlin transcript, the per-round <=5-term Pedersen
 // commitments, and proof serialisation (bincode layout).  It shares no code with the test-side checker.
+#include "host/proof_sizes.h"
 #include "host/prover_common.h"
 
 namespace {
@@ -499,11 +500,7 @@ int vpin_bullet_reduce(vpin_ctx* c, const vpin_gens* g, const uint8_t* x_mont, c
 
 void vpin_sat_last_timings(double out[8]) { memcpy(out, g_timings, sizeof g_timings); }
 
-size_t vpin_sat_proof_max_bytes(size_t num_cons, size_t num_vars) {
-  size_t lx = log2z(num_cons), ly = log2z(2 * num_vars), ell = log2z(num_vars);
-  size_t L = (size_t)1 << (ell / 2), lgR = ell - ell / 2;
-  return 8 + 32 * L + (lx + ly) * 400 + 2048 + 64 * lgR;
-}
+size_t vpin_sat_proof_max_bytes(size_t num_cons, size_t num_vars) { return vpin_sizes::sat_proof_max_bytes(num_cons, num_vars); }
 
 }  // extern "C"
 

@@ -16,6 +16,7 @@
 // scalars and the bincode image.  It shares no code with the test-side checker.
 #include <cstdio>
 
+#include "host/proof_sizes.h"
 #include "host/prover_common.h"
 #include "gadget_dev.h"
 #include "spark_dev.h"
@@ -105,23 +106,9 @@ static int get_view(vpin_ctx* c, size_t ell, const PcGens** out) {
   return VPIN_OK;
 }
 
-struct Shape { size_t nx, ny, N, M, v_ops, v_mem, v_derefs; };
+using Shape = vpin_sizes::SparkShape;  // host/proof_sizes.h: the sizes are plain arithmetic, shared with the proof record's codec
 
-static size_t next_pow2(size_t n) { size_t p = 1; while (p < n) p <<= 1; return p; }
-
-static Shape shape_of(size_t num_cons, size_t num_vars, const size_t nnz[3]) {
-  Shape s;
-  s.nx = log2z(num_cons);
-  s.ny = log2z(2 * num_vars);
-  s.N = 1;
-  for (int m = 0; m < 3; m++) s.N = std::max(s.N, next_pow2(nnz[m]));  // get_num_nz_entries (sparse_mlpoly.rs:364)
-  s.M = (size_t)1 << std::max(s.nx, s.ny);
-  // SparseMatPolyCommitmentGens::new (sparse_mlpoly.rs:300-329), batch_size = 3
-  s.v_ops = log2z(s.N) + 4;
-  s.v_mem = std::max(s.nx, s.ny) + 1;
-  s.v_derefs = log2z(s.N) + 3;
-  return s;
-}
+static Shape shape_of(size_t num_cons, size_t num_vars, const size_t nnz[3]) { return vpin_sizes::spark_shape(num_cons, num_vars, nnz); }
 
 // DensePolynomial::commit(gens, None) (dense_mlpoly.rs:193-218): zero blinds
 // short_scalars: most of Z is addresses, timestamps and counters (see vpin::hyrax_commit_walk)
@@ -1237,21 +1224,11 @@ static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vecto
 extern "C" {
 
 size_t vpin_spark_comm_bytes(const vpin_r1cs* inst) {
-  if (!inst) return 0;
-  Shape s = shape_of(inst->num_cons, inst->num_vars, inst->nnz);
-  return 8 * 6 + 8 + 32 * ((size_t)1 << (s.v_ops / 2)) + 8 + 32 * ((size_t)1 << (s.v_mem / 2));
+  return inst ? vpin_sizes::spark_comm_bytes(inst->num_cons, inst->num_vars, inst->nnz) : 0;
 }
 
 size_t vpin_snark_proof_max_bytes(const vpin_r1cs* inst) {
-  if (!inst) return 0;
-  Shape s = shape_of(inst->num_cons, inst->num_vars, inst->nnz);
-  const size_t lgN = log2z(s.N), lgM = log2z(s.M);
-  size_t b = vpin_sat_proof_max_bytes(inst->num_cons, inst->num_vars) + 96;
-  b += 8 + 32 * ((size_t)1 << (s.v_derefs / 2)) + 64 * 32;
-  b += lgN * (lgN * 104 + 64 + 24 * 32 + 64) + 18 * 32 + 64;
-  b += lgM * (lgM * 104 + 64 + 8 * 32 + 64) + 64;
-  b += 3 * (16 + 64 * 40 + 128 + 64) + 40 * 32 + 1024;
-  return b;
+  return inst ? vpin_sizes::snark_proof_max_bytes(inst->num_cons, inst->num_vars, inst->nnz) : 0;
 }
 
 int vpin_spark_prepare(vpin_ctx* c, size_t num_cons, size_t num_vars, size_t max_nnz) {

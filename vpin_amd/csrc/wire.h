@@ -107,6 +107,27 @@ int exchange(Roster* r, int round, int flags, int shift_bits, const uint8_t* pac
 // DONE to every live client: VPIN_OK and VPIN_NET_STAGE_DONE into its status; one that cannot be told is dropped.  The clients told
 size_t finish(Roster* r);
 
+// ---- proof records behind DONE (wire_proof.cpp: plain C++ like the codec and the stream) -----------------------------------
+// 40 bytes through vpin_proof_header_decode: nothing is allocated from the lengths before decode has accepted the header
+int recv_proof_header(vpin_wire* w, vpin_proof_header* h);
+int send_proof(vpin_wire* w, const vpin_proof_header& h, const void* payload);
+// an ERROR record with the code and at most VPIN_WIRE_MAX_TEXT bytes of the text, best effort: the caller's error text stays
+void send_proof_error(vpin_wire* w, int code, const char* text);
+struct ProofRecord {
+  vpin_proof_header h;
+  std::vector<uint8_t> payload;  // proof | comm | comm_para | comm_input
+  const uint8_t* proof() const { return payload.data(); }
+  const uint8_t* comm() const { return payload.data() + h.proof_len; }
+  const uint8_t* comm_para() const { return comm() + h.comm_len; }
+  const uint8_t* comm_input() const { return comm_para() + (payload.size() - h.proof_len - h.comm_len) / 2; }
+};
+// The client's receiving state machine: n_images * n_expect PROOF records, each the next expected (image, label, is_mult, n_ops),
+// then END with that count.  A record that is not the next expected one, or an early or miscounted END, is answered with an ERROR
+// record and VPIN_ESHAPE naming both sides before its payload is read; a peer's ERROR is VPIN_ECOMM quoting it.  *out holds the
+// records received so far, in order.  ms_recv (may be NULL): host-clock ms spent receiving
+int recv_proofs(vpin_wire* w, const char* who, size_t n_images, const vpin_proof_expect* expect, size_t n_expect,
+                std::vector<ProofRecord>* out, double* ms_recv);
+
 // what the endpoints share (wire_net.cpp; these reach the device through vpin_e2_pack / vpin_e2_unpack): c1 | c2 as one run of
 // 2 cnt packed points and back, and a frame's send and payload receive, each timed into the wire's slot
 int pack_pair(vpin_ctx* c, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y,

@@ -8,12 +8,15 @@
 // slots still in the batch and a client that lost an image to a layer is dropped (VPIN_NET_STAGE_LAYER); after it the images of
 // the clients that are gone leave the batch (vpin_net_round_drop_images), so the later layer calls run without them.
 // No table of any client's H is built: the biases are encrypted by vpin_e2_encrypt_keyed.
+// vpin_net_server_send_proofs then sends every client served to DONE the proofs of its own slots (vpin_net_send_proofs per wire).
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <new>
 #include <string>
 #include <vector>
+
+#include <sys/random.h>
 
 #include "enc_conv.h"
 #include "wire.h"
@@ -277,6 +280,36 @@ int vpin_net_serve_multi(vpin_net_server* s, vpin_wire* const* wires, size_t n_w
   r.who = kWho; r.max_batch = s->max_batch; r.status = status;
   s->stats[0]++;
   return serve(s, wires, n_wires, keys32, bias_r_le32, &r, out);
+}
+
+int vpin_net_server_send_proofs(vpin_net_server* s, const vpin_net_trace* t, vpin_wire* const* wires, size_t n_wires, vpin_net_peer_status* status,
+                                int per_layer, const uint8_t master_seed64[64]) {
+  const char* who = "vpin_net_server_send_proofs";
+  if (!s || !t || !wires || !status) return fail(VPIN_EINVAL, "vpin_net_server_send_proofs: null argument");
+  if (!n_wires || n_wires > s->max_batch) return fail(VPIN_EINVAL, "vpin_net_server_send_proofs: n_wires is outside 1 .. max_batch");
+  for (size_t i = 0; i < n_wires; i++)
+    if (!wires[i]) return fail(VPIN_EINVAL, "vpin_net_server_send_proofs: null argument");
+  uint8_t master[64];  // one for the call: a slot's seeds do not depend on which wire holds it
+  if (master_seed64) memcpy(master, master_seed64, 64);
+  else if (getrandom(master, 64, 0) != 64) return fail(VPIN_ENOMEM, "vpin_net_server_send_proofs: the operating system gave no randomness");
+  size_t ended = 0, asked = 0;
+  int last = VPIN_OK;
+  std::string last_text;
+  for (size_t i = 0; i < n_wires; i++) {
+    vpin_net_peer_status& st = status[i];
+    if (st.code != VPIN_OK || st.stage != VPIN_NET_STAGE_DONE) continue;  // it left before DONE: nothing was computed for it to the end
+    asked++;
+    const int rc = vpin_net_send_proofs(s->c, t, st.first_image, st.n_images, wires[i], per_layer, master, nullptr);
+    if (!rc) { ended++; continue; }
+    last = rc;
+    last_text = std::string(who) + ": " + vpin_last_error();
+    st.code = rc;
+    st.stage = VPIN_NET_STAGE_PROOFS;
+    snprintf(st.text, sizeof st.text, "%s", last_text.c_str());
+  }
+  if (ended) return VPIN_OK;
+  if (!asked) return fail(VPIN_ESHAPE, "vpin_net_server_send_proofs: no client was served to DONE");
+  return fail(last, last_text.c_str());
 }
 
 }  // extern "C"

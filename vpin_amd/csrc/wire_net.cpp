@@ -4,12 +4,17 @@
 // key.  Everything that arrives is unpacked on the device (e2_wire.hip) and so validated before a layer sees it.
 // vpin_net_serve_batch is the same endpoint for up to max_batch images: it reads B off INPUT's cnt and runs vpin_net_infer_batch;
 // every frame is as it was, with B times the single run's cnt.
+// vpin_net_send_proofs follows DONE on the same stream: per image of a trace and per instance of its label (or of every layer) it
+// builds the instance, proves it and sends one PROOF record (wire_proof.cpp), one instance at a time.
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include <sys/random.h>
+
 #include "enc_conv.h"
+#include "host/transcript.h"
 #include "wire.h"
 
 namespace vpin::wire {
@@ -230,6 +235,127 @@ int vpin_net_serve_batch(vpin_ctx* c, const vpin_net_cfg* cfg, vpin_wire* w, siz
     return rc;
   }
   return serve_checked("vpin_net_serve_batch", c, cfg, w, max_batch, keys32, n_keys, bias_r_le32, n_bias_r, out);
+}
+
+namespace {
+
+// the seeds of one proof: SHAKE256(master | "vPIN/wire-proof" | le32(slot) | le32(label) | u8(is_mult)) -> seed_commit | seed_proof
+void proof_seeds(const uint8_t master64[64], uint32_t slot, uint32_t label, int is_mult, uint8_t out128[128]) {
+  static const char domain[] = "vPIN/wire-proof";
+  uint8_t tail[9];
+  for (int i = 0; i < 4; i++) { tail[i] = (uint8_t)(slot >> (8 * i)); tail[4 + i] = (uint8_t)(label >> (8 * i)); }
+  tail[8] = is_mult ? 1 : 0;
+  vpin_host::Shake256 sh;
+  sh.absorb(master64, 64);
+  sh.absorb(reinterpret_cast<const uint8_t*>(domain), sizeof(domain) - 1);
+  sh.absorb(tail, sizeof tail);
+  sh.finalize();
+  sh.squeeze(out128, 128);
+}
+
+struct InstanceGuard {
+  vpin_ctx* c;
+  vpin_dev_instance* g = nullptr;
+  ~InstanceGuard() { vpin_dev_instance_free(c, g); }
+};
+
+// one list of a label as its instance: built, checked, proven, sent, freed.  *sent counts the PROOF records
+int send_one(const char* who, vpin_ctx* c, const vpin_conv_trace* L, int is_mult, uint32_t slot, uint32_t image, uint32_t label, vpin_wire* w,
+             const uint8_t master64[64], double ms[3], uint32_t* sent) {
+  const size_t n_ops = is_mult ? L->n_mult : L->n_add;
+  if (!n_ops) return VPIN_OK;  // a pooling label multiplies nothing; a 1 x 1 filter adds nothing
+  char why[200];
+  if (n_ops > VPIN_PROOF_MAX_OPS) {
+    snprintf(why, sizeof why, "%s: image %u, label %u: %zu operations are above VPIN_PROOF_MAX_OPS", who, (unsigned)image, (unsigned)label, n_ops);
+    return fail(VPIN_ESHAPE, why);
+  }
+  Lap lap;
+  InstanceGuard inst{c};
+  int rc = is_mult ? vpin_gadget_point_mult_dev(c, L->m_w.data(), L->m_px.data(), L->m_py.data(), n_ops, &inst.g)
+                   : vpin_gadget_point_add_dev(c, L->a_px.data(), L->a_py.data(), L->a_rx.data(), L->a_ry.data(), L->a_rz.data(), n_ops, &inst.g);
+  if (rc) {
+    snprintf(why, sizeof why, "%s: image %u, label %u: the instance of %zu %s could not be built", who, (unsigned)image, (unsigned)label, n_ops,
+             is_mult ? "multiplications" : "additions");
+    return fail(rc, why);
+  }
+  const int sat = vpin_dev_instance_is_sat(c, inst.g);
+  ms[0] += lap();
+  if (sat != 1) {
+    snprintf(why, sizeof why, "%s: image %u, label %u: the witness of %zu %s does not satisfy the gadget", who, (unsigned)image, (unsigned)label, n_ops,
+             is_mult ? "multiplications" : "additions");
+    return fail(sat < 0 ? sat : VPIN_EVERIFY, why);
+  }
+  uint8_t seeds[128];
+  proof_seeds(master64, slot, label, is_mult, seeds);
+  const size_t cap = vpin_dev_instance_proof_max_bytes(inst.g), ccap = vpin_dev_instance_comm_bytes(inst.g);
+  const size_t rows = vpin_gadget_vars_rows(is_mult, n_ops);
+  if (cap != vpin_gadget_proof_max_bytes(is_mult, n_ops) || ccap != vpin_gadget_comm_bytes(is_mult, n_ops)) {
+    snprintf(why, sizeof why, "%s: the instance of %zu %s does not have the sizes of its shape", who, n_ops, is_mult ? "multiplications" : "additions");
+    return fail(VPIN_ESHAPE, why);
+  }
+  // proof | comm | comm_para | comm_input, the proof at its largest first and the rest moved up behind its real length
+  std::vector<uint8_t> p(cap + ccap + 64 * rows), rest(ccap + 64 * rows);
+  size_t len = 0, clen = 0;
+  rc = vpin_snark_prove_dev(c, inst.g, seeds, seeds + 64, p.data(), cap, &len, rest.data(), ccap, &clen, rest.data() + ccap, rest.data() + ccap + 32 * rows);
+  ms[1] += lap();
+  if (rc) {
+    snprintf(why, sizeof why, "%s: image %u, label %u: vpin_snark_prove_dev failed", who, (unsigned)image, (unsigned)label);
+    return fail(rc, why);
+  }
+  if (clen != ccap) return fail(VPIN_ESHAPE, (std::string(who) + ": the commitment does not have the length of its shape").c_str());
+  memcpy(p.data() + len, rest.data(), rest.size());
+  vpin_proof_header h;
+  memset(&h, 0, sizeof h);
+  h.kind = VPIN_PROOF_RECORD; h.is_mult = is_mult ? 1 : 0; h.image = image; h.label = label;
+  h.n_ops = n_ops; h.proof_len = len; h.comm_len = clen;
+  rc = send_proof(w, h, p.data());
+  ms[2] += lap();
+  if (rc) return named(rc, who);
+  ++*sent;
+  return VPIN_OK;
+}
+
+}  // namespace
+
+int vpin_net_send_proofs(vpin_ctx* c, const vpin_net_trace* t, size_t first_image, size_t n_images, vpin_wire* w, int per_layer,
+                         const uint8_t master_seed64[64], double ms_out[3]) {
+  const char* who = "vpin_net_send_proofs";
+  if (ms_out) ms_out[0] = ms_out[1] = ms_out[2] = 0.0;
+  if (!c || !t || !w) return fail(VPIN_EINVAL, "vpin_net_send_proofs: null argument");
+  size_t B = 0, n_layers = 0;
+  int rc = vpin_net_trace_images(t, &B);
+  if (!rc) rc = vpin_net_trace_layers(t, &n_layers);
+  if (rc) return rc;
+  if (!n_images || first_image >= B || n_images > B - first_image)
+    return fail(VPIN_EINVAL, "vpin_net_send_proofs: the images are not images of the trace");
+  uint8_t master[64];
+  if (master_seed64) memcpy(master, master_seed64, 64);
+  else if (getrandom(master, 64, 0) != 64) return fail(VPIN_ENOMEM, "vpin_net_send_proofs: the operating system gave no randomness");
+  double ms[3] = {0.0, 0.0, 0.0};
+  uint32_t sent = 0;
+  for (size_t i = 0; i < n_images && !rc; i++) {
+    const uint32_t slot = (uint32_t)(first_image + i);
+    for (size_t l = 0; l < (per_layer ? n_layers : 1) && !rc; l++) {
+      const vpin_conv_trace* L = nullptr;
+      Lap lap;
+      rc = per_layer ? vpin_net_trace_image_layer(t, slot, l, &L) : vpin_net_trace_image_label(t, slot, &L);
+      ms[0] += lap();
+      const uint32_t label = per_layer ? (uint32_t)(1 + l) : 0;
+      for (int is_mult = 1; is_mult >= 0 && !rc; is_mult--) rc = send_one(who, c, L, is_mult, slot, (uint32_t)i, label, w, master, ms, &sent);
+    }
+  }
+  if (ms_out) memcpy(ms_out, ms, sizeof ms);
+  if (rc) {
+    if (rc != VPIN_ECOMM) send_proof_error(w, rc, vpin_last_error());  // the peer is gone otherwise
+    return rc;
+  }
+  vpin_proof_header h;
+  memset(&h, 0, sizeof h);
+  h.kind = VPIN_PROOF_END; h.image = sent;
+  Lap lap;
+  rc = send_proof(w, h, nullptr);
+  if (ms_out) ms_out[2] += lap();
+  return rc ? named(rc, who) : VPIN_OK;
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, WireRoundSpec, _chk, lib
+from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, ProofExpect, VpinError, WireRoundSpec, _chk, lib
 
 RELU, REENCRYPT = 1, 2
 
@@ -62,6 +62,24 @@ class Client:
         _chk(lib().vpin_net_client_run(self.h, wire.h, p(m), p(r), m.shape[0], spec, len(schedule)), "vpin_net_client_run")
         rounds = [self.values(self.first_round + i) for i in range(len(schedule))]
         return rounds[-1][1], rounds
+
+    def verify(self, wire, verifier, n_images, expectation, seed=None):
+        """vpin_net_client_verify: behind DONE, the proofs of this client's n_images images off the wire, each record the next of
+        `expectation` ([(label, is_mult, n_ops)], net.proof_expectation: the client's own, as the schedule is), its commitment the
+        one `verifier` (net.Verifier) derives, all in one batch verification.  seed: 32 bytes, or None for the library's own
+        randomness -> the verdicts [image][k] (True = accept).  A rejection raises nothing: `verifier.last_text` names the first"""
+        spec = (ProofExpect * max(1, len(expectation)))(*[ProofExpect(int(l), int(m), int(n)) for l, m, n in expectation])
+        ok = np.zeros(max(1, n_images * len(expectation)), np.uint8)
+        sd = None if seed is None else np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+        assert sd is None or sd.size == 32
+        rc = lib().vpin_net_client_verify(verifier.h, wire.h, n_images, spec, len(expectation), None if sd is None else sd.ctypes.data_as(C.c_void_p),
+                                          ok.ctypes.data_as(C.c_void_p))
+        if rc not in (0, -6):
+            raise VpinError(rc, "vpin_net_client_verify")
+        verifier.last_text = lib().vpin_last_error().decode(errors="replace") if rc else ""
+        out = [[bool(v) for v in ok[i * len(expectation):(i + 1) * len(expectation)]] for i in range(n_images)]
+        assert (rc == 0) == all(all(row) for row in out)
+        return out
 
     def values(self, rnd):
         """(v, act) of round first_round .. first_round + n_rounds - 1 as int64 arrays"""

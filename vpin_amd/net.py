@@ -353,7 +353,71 @@ def serve(ctx, cfg, wire, keys, bias_rs, max_batch=1):
     return Trace(ctx, h)
 
 
-STAGE_DONE, STAGE_ADMISSION, STAGE_SERVER, STAGE_LAYER = -1, -2, -3, -4
+def proof_expectation(cfg, per_layer=False):
+    """what the client of `cfg` expects behind DONE for each of its images, in the order the server sends: [(label, is_mult, n_ops)]
+    from vpin_net_cfg_counts.  per_layer false: the image's one label 0, its multiplications and then its additions; true: label
+    1 + i for layer i.  A list that would be empty (a pooling layer multiplies nothing) has no record.  The client holds its own
+    copy, beside `schedule`, and accepts no record that differs (Client.verify)"""
+    c = cfg.counts()
+    labels = [(1 + i, m, a) for i, (m, a) in enumerate(c["layers"])] if per_layer else [(0, c["n_mult"], c["n_add"])]
+    return [(label, is_mult, n) for label, m, a in labels for is_mult, n in ((1, m), (0, a)) if n]
+
+
+def _seed64(seed):
+    if seed is None:
+        return None
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    assert sd.size == 64
+    return sd
+
+
+def send_proofs(ctx, trace, wire, first_image=0, n_images=None, per_layer=False, master_seed=None):
+    """vpin_net_send_proofs: behind DONE, the proofs of the images [first_image, first_image + n_images) of `trace` (default: all
+    behind first_image) over the wire, one instance built, proven, sent and freed at a time, then END.  master_seed: 64 bytes from
+    which every proof's two seeds are derived, or None for the operating system's -> dict(build, prove, send) in host-clock ms"""
+    n = trace.images - first_image if n_images is None else n_images
+    sd = _seed64(master_seed)
+    ms = (C.c_double * 3)()
+    _chk(lib().vpin_net_send_proofs(ctx.h, trace.h, first_image, n, wire.h, int(bool(per_layer)), None if sd is None else sd.ctypes.data_as(C.c_void_p), ms),
+         "vpin_net_send_proofs")
+    return dict(zip(("build", "prove", "send"), (float(v) for v in ms)))
+
+
+class Verifier:
+    """vpin_net_verifier: the client's own computation commitments, derived on its GPU from (is_mult, n_ops) alone and kept, so a
+    shape is derived once however many images or inferences ask for it.  Client.verify compares the server's with these"""
+
+    def __init__(self, ctx):
+        self.ctx, self.last_text = ctx, ""
+        h = C.c_void_p()
+        _chk(lib().vpin_net_verifier_create(ctx.h, C.byref(h)), "vpin_net_verifier_create")
+        self.h = h
+
+    def shape(self, is_mult, n_ops):
+        """-> (comm bytes, inputs as (num_inputs, 4) uint64 Montgomery limbs) of the gadget over n_ops operations"""
+        comm, inputs, n, k = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _chk(lib().vpin_net_verifier_shape(self.h, int(is_mult), n_ops, C.byref(comm), C.byref(n), C.byref(inputs), C.byref(k)), "vpin_net_verifier_shape")
+        get = lambda p, m: bytes((C.c_uint8 * m).from_address(p.value)) if m else b""
+        return get(comm, n.value), np.frombuffer(get(inputs, 32 * k.value), dtype=np.uint64).reshape(k.value, 4).copy()
+
+    def stats(self):
+        out = (C.c_uint64 * 4)()
+        _chk(lib().vpin_net_verifier_stats(self.h, out), "vpin_net_verifier_stats")
+        return dict(zip(("shapes_derived", "lookups", "accepted", "rejected"), (int(v) for v in out)))
+
+    def timings(self):
+        """host-clock ms of the last Client.verify: dict(recv, derive, verify)"""
+        out = (C.c_double * 3)()
+        _chk(lib().vpin_net_verifier_timings(self.h, out), "vpin_net_verifier_timings")
+        return dict(zip(("recv", "derive", "verify"), (float(v) for v in out)))
+
+    def free(self):
+        if self.h:
+            lib().vpin_net_verifier_free(self.h)
+            self.h = None
+
+
+STAGE_DONE, STAGE_ADMISSION, STAGE_SERVER, STAGE_LAYER, STAGE_PROOFS = -1, -2, -3, -4, -5
 
 
 class Server:
@@ -390,6 +454,24 @@ class Server:
             e.statuses = statuses
             raise e
         return Trace(self.ctx, h), statuses
+
+    def send_proofs(self, trace, wires, statuses, per_layer=False, master_seed=None):
+        """vpin_net_server_send_proofs after `serve`, with its trace, its wires and its statuses: every client served to DONE gets
+        the proofs of its own slots -> the statuses again, a wire that failed here with its code and text at STAGE_PROOFS.  Raises
+        VpinError, with the statuses in its `.statuses`, when no client received END"""
+        ws = (C.c_void_p * max(1, len(wires)))(*[w.h for w in wires])
+        st = (NetPeerStatus * max(1, len(wires)))()
+        for s, d in zip(st, statuses):
+            s.code, s.stage, s.first_image, s.n_images, s.text = d["code"], d["stage"], d["first_image"], d["n_images"], d["text"].encode()[:255]
+        sd = _seed64(master_seed)
+        rc = lib().vpin_net_server_send_proofs(self.h, trace.h, ws, len(wires), st, int(bool(per_layer)), None if sd is None else sd.ctypes.data_as(C.c_void_p))
+        out = [dict(code=s.code, stage=s.stage, first_image=s.first_image, n_images=s.n_images, text=s.text.decode(errors="replace"))
+               for s in st[:len(wires)]]
+        if rc:
+            e = VpinError(rc, "vpin_net_server_send_proofs")
+            e.statuses = out
+            raise e
+        return out
 
     def stats(self):
         out = (C.c_uint64 * 5)()
