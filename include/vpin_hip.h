@@ -86,6 +86,13 @@ int vpin_ctx_set_shared_device(vpin_ctx* ctx, int on);
 /* commitment rows this context has handed to the row-per-lane kernel (msm_strip_kernel) since it was created: lets a test
  * or a scheduler see that the path it asked for is the one that ran */
 unsigned long long vpin_ctx_strip_rows_taken(vpin_ctx* ctx);
+/* (ABI 11) sums this context has taken through the shared-scalar bucket walk (e2_sh_window_kernel): every sum of a
+ * vpin_e2_msm_shared call, and the random-linear-combination sums of the layers whose shape the selection rule sends there.  A
+ * call that is rejected adds nothing */
+unsigned long long vpin_ctx_rlc_shared_sums(vpin_ctx* ctx);
+/* Test hook: the bytes of per-window results (sums x windows x 96) the walk holds at once on this context; above it the sums are
+ * taken in chunks.  0 restores the library's 128 MiB.  The results do not depend on it */
+int vpin_ctx_set_rlc_shared_cap(vpin_ctx* ctx, size_t bytes);
 /* rows committed through the row-table kernels so far (tests: the path under test is the one that ran) */
 unsigned long long vpin_ctx_row_table_rows(vpin_ctx* ctx);
 /* scalars (rows x columns, a blind column included) from which a row commitment on this context goes to the row-table kernels
@@ -646,6 +653,21 @@ int vpin_snark_prove_dev(vpin_ctx* ctx, const vpin_dev_instance* g, const uint8_
  * points included (one lane per term, double-and-add, complete additions in the reduction trees) */
 int vpin_e2_msm(vpin_ctx* ctx, const uint8_t* scalars_le16, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t n,
                 uint8_t out_x[32], uint8_t out_y[32], uint8_t* out_inf);
+/* (ABI 11) Many linear combinations at once whose sums share their scalar vectors:
+ *   sum[s] = sum over t < n_terms of  r[vec[s]][t] * P[base[s] + off[pat[s]][t]]        s < n_sums
+ * scalars_le16: n_vec x n_terms u128 values, 16 bytes little-endian each, every one below 2^scalar_bits (scalar_bits in 1 .. 128:
+ * the walk skips the windows above it).  px, py, pinf: n_points points as in vpin_e2_msm, validated on the device.  off: n_pat x
+ * n_terms int32, a negative entry means "no term" (padding).  vec, pat, base: one uint32 per sum.  out_x, out_y, out_inf: n_sums
+ * affine points in canonical bytes, the identity as zeros with flag 1.  Sums of one vector share a wave of a bucket walk over
+ * signed 3-bit windows (e2_msm_shared.hip), so the call pays off when many sums use each vector; the sums may come in any order.
+ * Exact for identity points, repeated points (the same point at every term included), P and -P in one sum, zero scalars and
+ * sums with no term at all (the identity).
+ * VPIN_EINVAL, the rule named in vpin_last_error(): a null argument or a zero count; scalar_bits outside 1 .. 128; a scalar with a
+ * set bit at or above scalar_bits; vec[s] >= n_vec or pat[s] >= n_pat; an address base + off outside [0, n_points); a coordinate
+ * >= q or a point off the curve; n_sums or n_sums * n_terms above 2^31 - 1. */
+int vpin_e2_msm_shared(vpin_ctx* ctx, const uint8_t* scalars_le16, size_t n_vec, size_t n_terms, int scalar_bits, const uint8_t* px,
+                       const uint8_t* py, const uint8_t* pinf, size_t n_points, const int32_t* off, size_t n_pat, const uint32_t* vec,
+                       const uint32_t* pat, const uint32_t* base, size_t n_sums, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
 /* The tail of a layer's RLC check as a stage of its own (rLCR of src/LeNet/Server.py and of src/cnn_networks/Server.py: the
  * products w[k] * B'[k], or s_k * X[k] in FCLayer, and the running sum the additions of the list come from): P chains of K
  * terms, term (p, k) at index p * K + k, each a u128 scalar (16 bytes little-endian) and a point.

@@ -231,6 +231,7 @@ def lib():
     L.vpin_spark_encode_dev.argtypes = [vp, vp, C.POINTER(vp), vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vpin_snark_prove_dev.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
     L.vpin_e2_msm.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.vpin_e2_msm_shared.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_mul_chain.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t] + [vp] * 6
     L.vpin_e2_conv2d.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp] + [C.c_size_t] * 4 + [vp, vp, vp]
     L.vpin_enc_conv2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp] + [C.c_size_t] * 4 + [vp, C.c_int, C.POINTER(vp)]
@@ -892,6 +893,19 @@ class Context:
         L.vpin_ctx_strip_rows_taken.restype = C.c_ulonglong
         return int(L.vpin_ctx_strip_rows_taken(self.h))
 
+    def rlc_shared_sums(self):
+        """sums the shared-scalar bucket walk has taken on this context so far (vpin_ctx_rlc_shared_sums)"""
+        L = lib()
+        L.vpin_ctx_rlc_shared_sums.argtypes = [C.c_void_p]
+        L.vpin_ctx_rlc_shared_sums.restype = C.c_ulonglong
+        return int(L.vpin_ctx_rlc_shared_sums(self.h))
+
+    def set_rlc_shared_cap(self, nbytes):
+        """test hook: bytes of per-window results the walk holds at once, 0 = the library's default (vpin_ctx_set_rlc_shared_cap)"""
+        L = lib()
+        L.vpin_ctx_set_rlc_shared_cap.argtypes = [C.c_void_p, C.c_size_t]
+        _chk(L.vpin_ctx_set_rlc_shared_cap(self.h, nbytes), "vpin_ctx_set_rlc_shared_cap")
+
     def witness_redo_ops(self):
         """operations of the last gadget_point_mult_dev call that the step-by-step witness kernel wrote (vpin_ctx_witness_redo_ops)"""
         L = lib()
@@ -1406,6 +1420,24 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         _chk(lib().vpin_e2_msm(self.h, p(s), p(x), p(y), p(f), x.shape[0], p(ox), p(oy), p(oi)), "vpin_e2_msm")
         return None if oi[0] else (int.from_bytes(bytes(ox), "little"), int.from_bytes(bytes(oy), "little"))
+
+    def e2_msm_shared(self, scalars, x, y, inf, off, vec, pat, base, scalar_bits=128):
+        """sum[s] = sum_t scalars[vec[s]][t] * P[base[s] + off[pat[s]][t]] on E2 (vpin_e2_msm_shared).  scalars: n_vec rows of n_terms
+        Python ints below 2^scalar_bits; off: n_pat rows of n_terms ints, a negative entry is no term; vec, pat, base: one int per
+        sum.  Returns one (x, y) of ints per sum, None for the identity."""
+        x, y, f = self._points(x, y, inf)
+        n_vec, n_terms = len(scalars), len(scalars[0])
+        assert all(len(row) == n_terms for row in scalars) and all(len(row) == n_terms for row in off)
+        s = self._u128s([v for row in scalars for v in row])
+        o = np.ascontiguousarray(off, dtype=np.int32).reshape(-1)
+        v, pt, b = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (vec, pat, base))
+        n = v.shape[0]
+        assert pt.shape[0] == n and b.shape[0] == n
+        ox, oy, oi = np.zeros((max(n, 1), 32), np.uint8), np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _chk(lib().vpin_e2_msm_shared(self.h, p(s), n_vec, n_terms, scalar_bits, p(x), p(y), p(f), x.shape[0], p(o), len(off), p(v), p(pt), p(b),
+                                      n, p(ox), p(oy), p(oi)), "vpin_e2_msm_shared")
+        return [None if oi[i] else (int.from_bytes(bytes(ox[i]), "little"), int.from_bytes(bytes(oy[i]), "little")) for i in range(n)]
 
     def e2_mul_chain(self, scalars, x, y, inf, P, K):
         """P chains of K terms (vpin_e2_mul_chain): scalars are P * K Python ints < 2^128, term (p, k) at index p * K + k.  Returns

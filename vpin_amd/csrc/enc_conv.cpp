@@ -265,7 +265,7 @@ int vpin_enc_conv2d(vpin_ctx* c, const uint8_t* px, const uint8_t* py, const uin
 
   // the f^2 + 1 sums of every plane
   std::vector<uint8_t> sums(P * nsum * 96);
-  if ((rc = d.rlc(r.data(), sums.data()))) return rc;
+  if ((rc = d.rlc(r.data(), sums.data(), 8 * prf_bytes))) return rc;
   tm[3] = lap();
 
   // host tail: T_k = w[k] * B'[k] on the team, the prefixes of every plane's chain, the two lists, the equation

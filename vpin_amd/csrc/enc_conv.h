@@ -82,13 +82,15 @@ int e2_emit(vpin_ctx* c, const e2_jac* jac, size_t n, uint8_t* x, uint8_t* y, ui
 //              window_t(X[plane])[tap]; plane = -1: sum_t r[pair][t] * out[pair][t]; plane = -2: no terms (the padding of a
 //              chain).  neg[i] != 0 negates sum i (e2_negate_kernel).  All sums are normalised by one launch: canonical bytes and
 //              flags to the host, and they stay resident in *sums, ready for mul_chain
+// rlc and rlc_mc take scalar_bits, a bound on their scalars (8 * prf_bytes), and go through the shared-scalar walk
+// (e2_msm_shared.hip) where e2_rlc_shared_wins says so: the sums are the same group elements either way
 struct EncConvDev {
   vpin_ctx* c;
   ConvGeom g;
   E2Points in, out;
   explicit EncConvDev(vpin_ctx* ctx) : c(ctx), in(ctx), out(ctx) {}
   int conv(const ConvGeom& geom, const uint8_t* filter_le16, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
-  int rlc(const uint8_t* r_le16, uint8_t* sums_jac);
+  int rlc(const uint8_t* r_le16, uint8_t* sums_jac, int scalar_bits = 128);
   int msm(const uint8_t* r_le16, size_t n, uint8_t sum_jac[96]);
   int matvec(size_t P, size_t K, size_t N, const void* weights, bool is_signed, uint8_t* c_x, uint8_t* c_y, uint8_t* c_inf);
   int pool_sums(const ConvGeom& geom, uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_identity);
@@ -96,7 +98,7 @@ struct EncConvDev {
               uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
   int add_bias(const E2Points& bias, size_t groups, size_t n_out, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf);
   int rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, E2Points* sums, uint8_t* s_x,
-             uint8_t* s_y, uint8_t* s_inf);
+             uint8_t* s_y, uint8_t* s_inf, int scalar_bits = 128);
 };
 
 // The tail of a layer's RLC check, also vpin_e2_mul_chain (enc_fc.hip: e2_scalar_mul_kernel, e2_chain_scan_kernel, one
@@ -114,6 +116,13 @@ fq e2_curve_a();
 E2Geom e2_geom(const ConvGeom& g);
 int e2_to_affine(vpin_ctx* c, const e2_jac* in, size_t n, fq* mx, fq* my, fq* cx, fq* cy, uint8_t* oinf);
 int e2_reduce(vpin_ctx* c, const e2_jac* parts, size_t n_sums, size_t n_parts, e2_jac* out);
+
+// e2_msm_shared.hip: the selection rule between the one-lane-per-term kernels and the shared-scalar walk (stated there), and the
+// layers' sums through the walk: desc as rlc_mc takes it, n_pairs vectors of oh * ow scalars at r_dev, n_sums Jacobian sums to `sums`
+// in the order of desc.  Synchronises
+bool e2_rlc_shared_wins(size_t sums_per_vec, size_t n_terms, int scalar_bits);
+int e2_rlc_shared(vpin_ctx* c, const E2Points& in, const E2Points& out, const ConvGeom& g, const int32_t* desc, size_t n_sums, size_t n_pairs,
+                  const void* r_dev, int scalar_bits, e2_jac* sums);
 
 inline unsigned blocks_of(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
 

@@ -286,8 +286,25 @@ int EncConvDev::conv(const ConvGeom& geom, const uint8_t* filter_le16, uint8_t* 
   return e2_emit(c, (const e2_jac*)jac.p, n_out, out_x, out_y, out_inf, &out);
 }
 
-int EncConvDev::rlc(const uint8_t* r_le16, uint8_t* sums_jac) {
+int EncConvDev::rlc(const uint8_t* r_le16, uint8_t* sums_jac, int scalar_bits) {
   (void)hipSetDevice(c->device);
+  const size_t nsum = g.taps() + 1, n_terms = g.oh * g.ow, n = g.P * nsum;
+  if (e2_rlc_shared_wins(nsum, n_terms, scalar_bits)) {  // the taps + 1 sums of a plane share its r: the bucket walk
+    std::vector<int32_t> desc(4 * n, 0);  // as rlc_mc's: {plane, tap, pair, 0}, the last sum of a plane over its outputs
+    for (size_t p = 0; p < g.P; p++)
+      for (size_t k = 0; k < nsum; k++) {
+        int32_t* d = &desc[4 * (p * nsum + k)];
+        d[0] = k < g.taps() ? (int32_t)p : -1; d[1] = (int32_t)k; d[2] = (int32_t)p;
+      }
+    DevBuf r(c), sums(c);
+    if (r.alloc(g.P * n_terms * 16) || sums.alloc(n * sizeof(e2_jac))) return VPIN_ENOMEM;
+    VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le16, g.P * n_terms * 16, hipMemcpyHostToDevice, c->stream));
+    const int rc = e2_rlc_shared(c, in, out, g, desc.data(), n, g.P, r.p, scalar_bits, (e2_jac*)sums.p);
+    if (rc) return rc;
+    VPIN_HIP_TRY(hipMemcpyAsync(sums_jac, sums.p, n * sizeof(e2_jac), hipMemcpyDeviceToHost, c->stream));
+    VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+    return VPIN_OK;
+  }
   return run_rlc(c, in.X(), in.Y(), in.F(), out.X(), out.Y(), out.F(), g, g.oh * g.ow, r_le16, sums_jac);
 }
 

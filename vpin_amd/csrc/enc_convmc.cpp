@@ -139,7 +139,7 @@ int mc_layer(const char* who, bool with_bias, vpin_ctx* c, const uint8_t* px, co
     dl[0] = -1; dl[2] = (int32_t)q;
   }
   std::vector<uint8_t> sx(n_sums * 32), sy(n_sums * 32), sinf(n_sums);
-  if ((rc = d.rlc_mc(n_pairs, desc.data(), neg.data(), n_sums, r.data(), &tail, sx.data(), sy.data(), sinf.data()))) return rc;
+  if ((rc = d.rlc_mc(n_pairs, desc.data(), neg.data(), n_sums, r.data(), &tail, sx.data(), sy.data(), sinf.data(), 8 * prf_bytes))) return rc;
   tm[3] = lap();
 
   // the tail: T_m = |w_m| * S_m and the prefixes of every chain on the device, then the equation and the two lists

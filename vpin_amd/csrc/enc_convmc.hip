@@ -162,9 +162,21 @@ int EncConvDev::conv_mc(const ConvGeom& geom, size_t groups, size_t C, size_t n_
 }
 
 int EncConvDev::rlc_mc(size_t n_pairs, const int32_t* desc, const uint8_t* neg, size_t n_sums, const uint8_t* r_le16, E2Points* sums_out,
-                       uint8_t* s_x, uint8_t* s_y, uint8_t* s_inf) {
+                       uint8_t* s_x, uint8_t* s_y, uint8_t* s_inf, int scalar_bits) {
   (void)hipSetDevice(c->device);
   const size_t n_terms = g.oh * g.ow, total = n_pairs * n_terms;
+  if (e2_rlc_shared_wins(n_sums / n_pairs, n_terms, scalar_bits)) {  // the sums of a pair share its r: the bucket walk
+    DevBuf r(c), ng(c), sums(c);
+    if (r.alloc(total * 16) || ng.alloc(n_sums) || sums.alloc(n_sums * sizeof(e2_jac))) return VPIN_ENOMEM;
+    VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le16, total * 16, hipMemcpyHostToDevice, c->stream));
+    VPIN_HIP_TRY(hipMemcpyAsync(ng.p, neg, n_sums, hipMemcpyHostToDevice, c->stream));
+    const int rc = e2_rlc_shared(c, in, out, g, desc, n_sums, n_pairs, r.p, scalar_bits, (e2_jac*)sums.p);
+    if (rc) return rc;
+    hipLaunchKernelGGL(e2_negate_kernel, dim3(blocks_of(n_sums, kE2Block)), dim3(kE2Block), 0, c->stream, (e2_jac*)sums.p, (const uint8_t*)ng.p,
+                       n_sums);
+    VPIN_HIP_TRY(hipGetLastError());
+    return e2_emit(c, (const e2_jac*)sums.p, n_sums, s_x, s_y, s_inf, sums_out);
+  }
   int S = kE2Block;  // lanes per sum
   while (S / 2 >= 1 && (size_t)(S / 2) >= n_terms) S /= 2;
   const size_t nblk = blocks_of(n_terms, S);  // 1 below kE2Block terms
