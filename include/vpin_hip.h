@@ -93,6 +93,14 @@ unsigned long long vpin_ctx_rlc_shared_sums(vpin_ctx* ctx);
 /* Test hook: the bytes of per-window results (sums x windows x 96) the walk holds at once on this context; above it the sums are
  * taken in chunks.  0 restores the library's 128 MiB.  The results do not depend on it */
 int vpin_ctx_set_rlc_shared_cap(vpin_ctx* ctx, size_t bytes);
+/* Test hook: on != 0 makes the context's device pool fill every block it hands out from now on -- fresh from the driver or
+ * recycled, the whole size class and not only the bytes asked for -- with `word`, on the context's stream, before the block is
+ * returned; a temporary then never arrives zeroed or holding the previous call's results.  on = 0 restores the plain allocator.
+ * Covers the pooled temporaries and tables only: not the context's fixed scratch, the pinned mailboxes or the window tables.
+ * The results do not depend on it */
+int vpin_ctx_set_pool_poison(vpin_ctx* ctx, uint32_t word, int on);
+/* Test hook: blocks and bytes the pool has filled on this context since it was created (either pointer may be NULL) */
+int vpin_ctx_pool_poison_stats(vpin_ctx* ctx, unsigned long long* blocks, unsigned long long* bytes);
 /* rows committed through the row-table kernels so far (tests: the path under test is the one that ran) */
 unsigned long long vpin_ctx_row_table_rows(vpin_ctx* ctx);
 /* scalars (rows x columns, a blind column included) from which a row commitment on this context goes to the row-table kernels

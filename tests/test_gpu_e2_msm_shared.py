@@ -28,8 +28,7 @@ def ctx():
     c.close()
 
 
-@pytest.fixture(scope="module")
-def pool():
+def make_pool():
     """N_POINTS synthetic points and their logarithms; point 5 repeats point 4, point 7 is -point 6, points 9 and 20 are flagged"""
     from vpin_amd import gadgets as G
     x, y = G.synthetic_points(0x5348, N_POINTS)
@@ -42,6 +41,11 @@ def pool():
     for i in (9, 20):
         inf[i], logs[i] = 1, 0
     return x, y, inf, logs
+
+
+@pytest.fixture(scope="module")
+def pool():
+    return make_pool()
 
 
 def rand_scalars(seed, n, bits=128):

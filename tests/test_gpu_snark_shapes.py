@@ -127,11 +127,11 @@ def test_hot_column_search(ctx, digests, name):
 
 # ---- several ranks ------------------------------------------------------------------------------------------------------------
 
-def _prove_ranks(world, inst):
-    """as test_gpu_dist._prove_threads, from host triplets: -> (single-GPU proof, [proof of rank r])"""
+def _prove_ranks(world, inst, new_ctx=None):
+    """as test_gpu_dist._prove_threads, from host triplets: -> (single-GPU proof, [proof of rank r]); new_ctx: what makes a rank's context"""
     import vpin_amd
     from vpin_amd import Comm
-    ctxs = [vpin_amd.Context(0) for _ in range(world)]
+    ctxs = [(new_ctx or vpin_amd.Context)(0) for _ in range(world)]
     di = ctxs[0].r1cs_upload(inst)
     dec, comm = ctxs[0].spark_encode(inst)
     tabs = [ctxs[0].upload(inst[k]) for k in ("vars_para", "vars_input", "vars")]

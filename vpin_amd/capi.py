@@ -906,6 +906,20 @@ class Context:
         L.vpin_ctx_set_rlc_shared_cap.argtypes = [C.c_void_p, C.c_size_t]
         _chk(L.vpin_ctx_set_rlc_shared_cap(self.h, nbytes), "vpin_ctx_set_rlc_shared_cap")
 
+    def set_pool_poison(self, word, on=True):
+        """test hook: the pool fills every block it hands out (its whole size class) with the 32-bit `word` (vpin_ctx_set_pool_poison)"""
+        L = lib()
+        L.vpin_ctx_set_pool_poison.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+        _chk(L.vpin_ctx_set_pool_poison(self.h, word, 1 if on else 0), "vpin_ctx_set_pool_poison")
+
+    def pool_poison_stats(self):
+        """(blocks, bytes) the pool has filled with the poison word on this context so far (vpin_ctx_pool_poison_stats)"""
+        L = lib()
+        L.vpin_ctx_pool_poison_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        blocks, nbytes = C.c_ulonglong(0), C.c_ulonglong(0)
+        _chk(L.vpin_ctx_pool_poison_stats(self.h, C.byref(blocks), C.byref(nbytes)), "vpin_ctx_pool_poison_stats")
+        return int(blocks.value), int(nbytes.value)
+
     def witness_redo_ops(self):
         """operations of the last gadget_point_mult_dev call that the step-by-step witness kernel wrote (vpin_ctx_witness_redo_ops)"""
         L = lib()

@@ -144,10 +144,27 @@ hipError_t driver_malloc(void** p, size_t bytes) {
   return hipMalloc(p, bytes);
 }
 
+// vpin_ctx_set_pool_poison (tests): the whole size class of a block dev_alloc is about to hand out is filled with the context's
+// poison word, on the stream in use -- a recycled block may still be read by earlier work of that stream, so the fill must be
+// ordered behind it; enqueued only, never waited for (a resident tail kernel may be waiting for the host, see below)
+static int pool_poison_fill(vpin_ctx* c, void** out, size_t cls) {
+  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)*out, (int)c->pool_poison_word, cls / 4, c->stream);
+  if (e != hipSuccess) {
+    set_last_error("pool poison fill", e);
+    dev_free(c, *out);
+    *out = nullptr;
+    return VPIN_EHIP;
+  }
+  c->pool_poison_blocks++;
+  c->pool_poison_bytes += cls;
+  return VPIN_OK;
+}
+
 int dev_alloc(vpin_ctx* c, size_t bytes, void** out) {
   size_t cls = 256;
   while (cls < bytes) cls <<= 1;
   if (cls > (size_t)1 << 22) cls = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);  // MiB granularity above 4 MiB
+  size_t hit = 0;  // class of the cached block taken, 0: none
   {
     std::lock_guard<std::mutex> g(c->pool_mu);
     // exact class first; for large requests any cached block up to 2x the size will do (proofs of
@@ -158,9 +175,11 @@ int dev_alloc(vpin_ctx* c, size_t bytes, void** out) {
       *out = it->second.back();
       it->second.pop_back();
       if (pool_trace_min()) { g_in_use += (long long)it->first; pool_trace("alloc", it->first, false); }
-      return VPIN_OK;
+      hit = it->first;
+      break;
     }
   }
+  if (hit) return c->pool_poison ? pool_poison_fill(c, out, hit) : VPIN_OK;
   void* p = nullptr;
   const double t_m = pool_trace_min() ? pool_trace_ms() : 0.0;
   if (driver_malloc(&p, cls) != hipSuccess) {
@@ -194,11 +213,13 @@ int dev_alloc(vpin_ctx* c, size_t bytes, void** out) {
     }
   }
   note_driver_alloc(cls);
-  std::lock_guard<std::mutex> g(c->pool_mu);
-  c->pool_sizes[p] = cls;
-  *out = p;
-  if (pool_trace_min()) { g_in_use += (long long)cls; pool_trace("alloc", cls, true, pool_trace_ms() - t_m); }
-  return VPIN_OK;
+  {
+    std::lock_guard<std::mutex> g(c->pool_mu);
+    c->pool_sizes[p] = cls;
+    *out = p;
+    if (pool_trace_min()) { g_in_use += (long long)cls; pool_trace("alloc", cls, true, pool_trace_ms() - t_m); }
+  }
+  return c->pool_poison ? pool_poison_fill(c, out, cls) : VPIN_OK;
 }
 
 void dev_free(vpin_ctx* c, void* p) {
@@ -431,6 +452,19 @@ unsigned long long vpin_ctx_strip_rows_taken(vpin_ctx* c) { return c ? c->strip_
 unsigned long long vpin_ctx_row_table_rows(vpin_ctx* c) { return c ? c->row_table_rows : 0ull; }
 unsigned long long vpin_ctx_pip_row_chunks(vpin_ctx* c) { return c ? c->pip_row_chunks : 0ull; }
 unsigned long long vpin_ctx_witness_redo_ops(vpin_ctx* c) { return c ? c->witness_redo_ops : 0ull; }
+
+int vpin_ctx_set_pool_poison(vpin_ctx* c, uint32_t word, int on) {
+  if (!c) return VPIN_EINVAL;
+  c->pool_poison_word = word;
+  c->pool_poison = on != 0;
+  return VPIN_OK;
+}
+int vpin_ctx_pool_poison_stats(vpin_ctx* c, unsigned long long* blocks, unsigned long long* bytes) {
+  if (!c) return VPIN_EINVAL;
+  if (blocks) *blocks = c->pool_poison_blocks;
+  if (bytes) *bytes = c->pool_poison_bytes;
+  return VPIN_OK;
+}
 
 int vpin_host_register(void* p, size_t bytes) {
   if (!p || !bytes) return VPIN_EINVAL;

@@ -104,6 +104,9 @@ struct vpin_ctx {
   unsigned long long strip_rows_taken = 0;  // rows handed to msm_strip_kernel so far (vpin_ctx_strip_rows_taken: tests)
   unsigned long long rlc_shared_sums = 0;   // sums taken by the shared-scalar walk so far (e2_msm_shared.hip; vpin_ctx_rlc_shared_sums: tests)
   size_t rlc_shared_cap = 0;                // bytes of per-window results it holds at once; 0: its default (vpin_ctx_set_rlc_shared_cap: tests)
+  bool pool_poison = false;                 // dev_alloc fills every block it hands out with pool_poison_word (vpin_ctx_set_pool_poison: tests)
+  uint32_t pool_poison_word = 0;
+  unsigned long long pool_poison_blocks = 0, pool_poison_bytes = 0;  // blocks / bytes filled so far (vpin_ctx_pool_poison_stats: tests)
   unsigned long long witness_redo_ops = 0;  // operations the last vpin_gadget_point_mult_dev gave gd_mult_witness_kernel (vpin_ctx_witness_redo_ops: tests)
   bool low_memory = false;     // vpin_ctx_set_low_memory: trade ~1 % of a large proof's time for a third less working set
   bool shared_device = false;  // other contexts prove on this device at the same time (vpin_ctx_set_shared_device)
