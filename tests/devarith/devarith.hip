@@ -195,6 +195,55 @@ DV_LANE(fq_signed_window, 11, 90, 64,
         co[88] = carry;
         co[89] = fq_is_zero(s) ? 0u : 1u;)
 
+// ---- ge_tree_dev.h: the table walks' digits and the row table's ----------------------------------------------------------
+// in: the canonical scalar, c, W; out: W digits (of at most 44) as sign (bit 15) and magnitude, then the carry the top window
+// leaves.  The sequential walk of table_mul_acc: fq_fold_sign, then fq_take_window and walk_digit per window.
+DV_LANE(walk_digits, 10, 45, 256,
+        fq s = ld8<fq>(ci);
+        const uint32_t c = ci[8]; const int W = (int)ci[9];
+        const bool flip = fq_fold_sign(s);
+        uint32_t carry = 0;
+        for (int w = 0; w < 44; w++) co[w] = 0;
+        for (int w = 0; w < W && w < 44; w++) {
+          bool neg;
+          const uint32_t mag = walk_digit(fq_take_window(s, carry, c), c, flip, carry, neg);
+          co[w] = mag | (neg && mag ? 0x8000u : 0u);
+        }
+        co[44] = carry;)
+// The lane-split walk of table_mul_acc_range, eight lanes of ceil(W / 8) windows: scalar_digit and walk_digit per window, the
+// carry into a lane's first window from carry_into.  out: the W digits and the last carry as above, then carry_into at the
+// first window of each of the eight lanes (0 for a lane without windows).
+DV_LANE(walk_lane_digits, 10, 53, 256,
+        fq s = ld8<fq>(ci);
+        const int c = (int)ci[8]; const int W = (int)ci[9];
+        const bool flip = fq_fold_sign(s);
+        const int wpg = (W + 7) / 8;
+        uint32_t carry = 0;
+        for (int w = 0; w < 53; w++) co[w] = 0;
+        for (int lane = 0; lane < 8; lane++) {
+          const int w0 = lane * wpg; const int w1 = w0 + wpg < W ? w0 + wpg : W;
+          if (w0 >= w1 || w1 > 44) continue;
+          carry = carry_into(s, w0, c);
+          co[45 + lane] = carry;
+          for (int w = w0; w < w1; w++) {
+            bool neg;
+            const uint32_t mag = walk_digit(scalar_digit(s, w, c) + carry, (uint32_t)c, flip, carry, neg);
+            co[w] = mag | (neg && mag ? 0x8000u : 0u);
+          }
+        }
+        co[44] = carry;)
+// in: the canonical scalar, c, W; out: the W digit words of row_digit as they go to LDS (of at most 64; magnitude - 1 and the
+// sign in bit 15, kNoDigit for a zero digit), then the last carry, then 1 if scalar bits are left over
+DV_LANE(row_digits, 10, 66, 256,
+        fq s = ld8<fq>(ci);
+        const int c = (int)ci[8]; const int W = (int)ci[9];
+        const bool flip = fq_fold_sign(s);
+        uint32_t carry = 0;
+        for (int w = 0; w < 64; w++) co[w] = 0;
+        for (int w = 0; w < W && w < 64; w++) co[w] = row_digit(s, carry, c, flip, w == W - 1);
+        co[64] = carry;
+        co[65] = fq_is_zero(s) ? 0u : 1u;)
+
 // ---- fp_dev.h -----------------------------------------------------------------------------------------------------------
 DV_LANE(fp_add, 16, 8, 256, st8(co, fp_add(ld8<fp>(ci), ld8<fp>(ci + 8)));)
 DV_LANE(fp_sub, 16, 8, 256, st8(co, fp_sub(ld8<fp>(ci), ld8<fp>(ci + 8)));)

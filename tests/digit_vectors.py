@@ -6,7 +6,7 @@ plausible mistakes; tests/test_gpu_msm_digits.py and tests/test_gpu_msm_strip.py
 A scalar s of F_q is first folded (fq_fold_sign: s -> q - s when bit 251 or 252 is set, the sign of every digit flipped), then
 cut into W = ceil(254 / c) windows of c bits.  A window value v = digit + carry above half = 2^(c-1) becomes the negative
 digit v - 2^c with a carry into the next window; exactly half stays positive.  Two forms exist on the device:
-    recode_walk   the sequential loop of table_mul_acc / table_mul_acc10 (one lane walks all windows),
+    recode_walk   the sequential loop of table_mul_acc, either accumulator (one lane walks all windows),
     recode_lanes  table_mul_acc_range: eight lanes of wpg = ceil(W / 8) windows each, the carry into a lane's first window
                   rebuilt by carry_into -- the nearest lower digit that is not exactly half decides."""
 from collections import namedtuple

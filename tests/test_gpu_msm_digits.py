@@ -1,7 +1,7 @@
 """The multi-window table walks of msm.hip at their digit edges: every kernel that recodes a scalar into signed digits gets
 every named vector of tests/digit_vectors.py for the window width of the table it walks, byte for byte against the CPU oracle.
 
-    msm_rows_kernel / table_mul_acc10 (sequential walk, ten-limb accumulator)     gens_msm, hyrax_commit (blinds: n_extra)
+    msm_rows_kernel / table_mul_acc<ge10> (sequential walk, ten-limb accumulator)     gens_msm, hyrax_commit (blinds: n_extra)
     msm_wide_kernel<1|4> / table_mul_acc_range (eight lanes per scalar)           gens_msm_parts, 64 and 32768 columns
     single_base_mul_kernel / table_mul_acc_range                                   hyrax_commit_pair_split
     bullet_step_kernel / table_mul_acc_range                                       vpin_bullet_reduce, fused rounds
@@ -128,7 +128,7 @@ def expected(og, vals, rows, vecs):
 
 @pytest.mark.parametrize("c", [12, 8, 7])
 def test_rows_kernel_walks_every_vector(ctx, tables, c):
-    """msm_rows_kernel / table_mul_acc10 through vpin_gens_msm"""
+    """msm_rows_kernel / table_mul_acc<ge10> through vpin_gens_msm"""
     g, og = tables[c]
     vecs = vectors_for(g, c)
     for what, vals, rows in cases(c, vecs):

@@ -51,6 +51,23 @@ def loops(body):
     return out
 
 
+RESOURCE_KEYS = ("vgpr_count", "vgpr_spill_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
+MSM_KERNELS = ("msm_rows_kernel", "msm_rows_hot_kernel", "msm_strip_kernel", "msm_rows_win_kernel", "msm_count_adds_kernel",
+               "scalar_times_bases_kernel", "single_base_mul_kernel", "bullet_step_kernel", "msm_wide_kernel")
+
+
+def resources(lines, kernels):
+    """registers, spills, scratch and LDS of the named kernels from the listing's amdhsa.kernels metadata"""
+    text = "\n".join(lines)
+    out = {}
+    for blk in re.split(r"\n  - ", text[text.index("amdhsa.kernels:"):])[1:]:
+        m = re.search(r"\n    \.name:\s+_ZN4vpin\d+(\w+?_kernel)(?:ILi(\d+)E)?", blk)
+        if m and m.group(1) in kernels:
+            name = m.group(1) + (f"<{m.group(2)}>" if m.group(2) else "")
+            out[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in RESOURCE_KEYS}
+    return out
+
+
 def main():
     res = {"_how": "tools/isa_counts.py: hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S, instructions between a loop's "
                    "label and its backward branch"}
@@ -61,6 +78,7 @@ def main():
                               "loads_per_table_add": add["vmem_loads"],
                               "note": "one iteration of table_mul_acc's window loop: digit extraction, one 96-byte table entry "
                                       "(6 x dwordx4), one ge_add_niels (7 products mod 2^255-19)"}
+    res["msm_resources"] = resources(m, MSM_KERNELS)
     sc = isa(os.path.join(ROOT, "vpin_amd", "csrc", "sumcheck.hip"))
     ls = loops(kernel_body(sc, "_ZN4vpin16sc_cubic3_kernelILb1ELb1EE"))
     big = max(ls, key=lambda l: l["valu"])

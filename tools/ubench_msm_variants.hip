@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256, 3) void chain_ref(const fp* __restrict__ in, f
 }
 
 // the same with one 96-byte gather per addition from `table` (n_entries a power of two), software-pipelined like
-// table_mul_acc10 (the entry of step i+1 is requested before the addition of step i)
+// table_mul_acc<ge10> (the entry of step i+1 is requested before the addition of step i)
 __global__ __launch_bounds__(256, 3) void chain_gather(const ge_niels* __restrict__ table, uint32_t mask, fp* __restrict__ out, int iters) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   ge10 acc = ge10_identity();

@@ -1,5 +1,6 @@
 // ge_tree_dev.h -- the group-element layer the MSM files share (msm.hip, msm_pip.hip, msm_var.hip): points to and from
-// global memory, the limb-strided ten-limb form, the signed-window recoding and the Horner sum of the bucket methods, and
+// global memory, the limb-strided ten-limb form, the signed-window recoding of every MSM (bucket methods, table walks, row
+// table) and the Horner sum of the bucket methods, and
 // the block tree that sums the points of a workgroup with four lanes per addition
 #pragma once
 #include "fp10_dev.h"
@@ -62,21 +63,90 @@ __device__ __forceinline__ ge10 ge10_load_strided(const uint32_t* __restrict__ p
   return a;
 }
 
-// ---- the bucket methods' windows -----------------------------------------------------------------------------------------
-// One signed window of a canonical scalar, low end first: takes the low cw bits of s and the carry of the window below,
-// shifts s right by cw bits and returns the digit as sign and magnitude (|d| in bits 0..14, sign in bit 15, 0 for a zero
-// digit); carry <- 1 when the digit was negated.  The top window is never negated: its value comes back as it is.
-__device__ __forceinline__ uint16_t fq_signed_window(fq& s, uint32_t& carry, uint32_t cw, bool top) {
-  const uint32_t mask = (1u << cw) - 1u, half = 1u << (cw - 1);
-  uint32_t v = (s.v[0] & mask) + carry;
+// ---- signed windows of a scalar ------------------------------------------------------------------------------------------
+// Every method cuts a canonical scalar into windows of c bits, low end first, and turns a window value past half = 2^(c-1)
+// into the negative digit v - 2^c with a carry into the window above.  ONE primitive takes a window; three rules say when
+// a value is negated and how the digit is written: fq_signed_window (bucket methods), walk_digit (table walks), row_digit
+// (row table).
+
+// s -> q - s when s is in the upper half (bit 251 or 252 set): s*g = -((q - s)*g).  Nothing for a random scalar,
+// but the R1CS values -1, -2 (a fifth of comb_ops' val slices) become one table add instead of W.
+__device__ __forceinline__ bool fq_fold_sign(fq& s) {
+  if (s.v[7] < 0x08000000u) return false;
+  fq d;
+  unsigned bw = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) d.v[i] = __builtin_subc(fq_modulus_limb(i), s.v[i], bw, &bw);
+  s = d;
+  return true;
+}
+
+// The primitive: the low cw bits of s plus the carry of the window below; s is shifted right by cw bits (static register
+// indices only).  cw in 1..31.  The bits are taken with one bit-field extract: a mask (1 << cw) - 1 would be a loop invariant
+// that the walks keep in a register of its own, and the row kernels have none to spare (__launch_bounds__(256, 3)).
+__device__ __forceinline__ uint32_t fq_take_window(fq& s, uint32_t carry, uint32_t cw) {
+  const uint32_t v = __builtin_amdgcn_ubfe(s.v[0], 0u, cw) + carry;
 #pragma unroll
   for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], cw);
   s.v[7] >>= cw;
-  const bool neg = !top && v > half;
-  if (neg) v = (mask + 1u) - v;
+  return v;
+}
+
+// The bucket methods' rule: v > half negates, but never in the top window, and nothing is folded (walk_digit negates every
+// window alike and applies the fold; row_digit lets a tie follow the fold).  The digit comes back as sign and magnitude (|d|
+// in bits 0..14, sign in bit 15, 0 for a zero digit); carry <- 1 when the digit was negated.
+__device__ __forceinline__ uint16_t fq_signed_window(fq& s, uint32_t& carry, uint32_t cw, bool top) {
+  uint32_t v = fq_take_window(s, carry, cw);
+  const bool neg = !top && v > (1u << (cw - 1));
+  if (neg) v = (1u << cw) - v;
   carry = neg ? 1u : 0u;
   return (uint16_t)(v | (neg && v ? 0x8000u : 0u));
 }
+
+// The table walks' rule, for a window value v (digit + carry) of a sign-folded scalar: v > half negates in every window, a
+// tie stays positive, then the fold's flip is applied (fq_signed_window spares the top window and knows no fold; row_digit
+// breaks the tie by the fold).  Returns the magnitude (0: nothing to add; the table entry is magnitude - 1), neg <- the
+// digit's sign, carry <- 1 when v was negated.
+__device__ __forceinline__ uint32_t walk_digit(uint32_t v, uint32_t c, bool flip, uint32_t& carry, bool& neg) {
+  const bool past = v > (1u << (c - 1));
+  carry = past ? 1u : 0u;
+  neg = past != flip;
+  return past ? (1u << c) - v : v;
+}
+
+// digit w (c bits) of a canonical scalar, for the kernels that split one scalar over several lanes
+__device__ __forceinline__ uint32_t scalar_digit(const fq& s, int w, int c) {
+  int off = w * c, word = off >> 5, sh = off & 31;
+  uint32_t lo = s.v[word], hi = (word + 1 < 8) ? s.v[word + 1] : 0u;
+  uint64_t both = ((uint64_t)hi << 32) | lo;
+  return (uint32_t)(both >> sh) & ((1u << c) - 1u);
+}
+
+// walk_digit's carry into window w0 without the windows below having been walked: decided by the nearest lower digit that
+// is not exactly 2^(c-1)
+__device__ __forceinline__ uint32_t carry_into(const fq& s, int w0, int c) {
+  const uint32_t half = 1u << (c - 1);
+  for (int w = w0 - 1; w >= 0; w--) {
+    uint32_t d = scalar_digit(s, w, c);
+    if (d != half) return d > half ? 1u : 0u;
+  }
+  return 0u;
+}
+
+// The row table's rule, one digit of a sign-folded scalar in a 16-bit word: magnitude - 1 in bits 0..14, the sign in bit 15,
+// kNoDigit for a zero digit.  Unlike walk_digit a tie at 2^(c-1) follows the fold -- +2^(c-1) without it, -2^(c-1) (carrying)
+// with it -- so that AFTER the flip the negative magnitudes stay below 2^(c-1) and 16 bits hold a 16-bit window's digits; like
+// fq_signed_window the top window is never negated (its value is at most 2^(c-1), see row_windows in msm.hip).
+constexpr uint16_t kNoDigit = 0xffffu;  // never a digit: a negative digit's magnitude is below 2^(c-1), c <= 16
+__device__ __forceinline__ uint16_t row_digit(fq& s, uint32_t& carry, int c, bool flip, bool top) {
+  const uint32_t half = 1u << (c - 1);
+  const uint32_t v = fq_take_window(s, carry, (uint32_t)c);
+  const bool neg = !top && (flip ? v >= half : v > half);
+  const uint32_t mag = neg ? (1u << c) - v : v;
+  carry = neg ? 1u : 0u;
+  return mag ? (uint16_t)((mag - 1u) | ((neg != flip) ? 0x8000u : 0u)) : kNoDigit;
+}
+
 // sum_w 2^(offset of window w) wsum[w] over W windows, window w being width(w) bits wide: Horner from the top window down,
 // one lane
 template <class Width>

@@ -197,24 +197,17 @@ __global__ __launch_bounds__(64) void gens_table_kernel(const ge_ext* __restrict
 
 // ---- scalar handling --------------------------------------------------------------------
 
-// accumulate s * g_j into acc through the window table; s canonical, non-zero
-// s -> q - s when s is in the upper half (bit 251 or 252 set): s*g = -((q - s)*g).  Nothing for a random scalar,
-// but the R1CS values -1, -2 (a fifth of comb_ops' val slices) become one table add instead of W.
-__device__ __forceinline__ bool fq_fold_sign(fq& s) {
-  if (s.v[7] < 0x08000000u) return false;
-  fq d;
-  unsigned bw = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) d.v[i] = __builtin_subc(fq_modulus_limb(i), s.v[i], bw, &bw);
-  s = d;
-  return true;
-}
-
-__device__ __forceinline__ void table_mul_acc(ge_ext& acc, fq s, const TableView& tv, size_t j) {
+// accumulate s * g_j into acc through the window table; s canonical, non-zero.  One walk for both accumulators: ge_ext
+// (ge_add_niels), and the ten-limb form (fp10_dev.h: the product of two field elements is 142 VALU instructions instead of 197
+// and the additions between products carry nothing) of the row-commitment kernels, where a lane adds hundreds of table entries
+// to one accumulator; the entries stay in the packed 96-byte form in HBM.  The digits: fq_fold_sign, then walk_digit per window.
+__device__ __forceinline__ ge_ext acc_add_niels(const ge_ext& a, const ge_niels& e, bool neg) { return ge_add_niels(a, e, neg); }
+__device__ __forceinline__ ge10 acc_add_niels(const ge10& a, const ge_niels& e, bool neg) { return ge10_add_niels(a, e, neg); }
+template <class Acc>
+__device__ __forceinline__ void table_mul_acc(Acc& acc, fq s, const TableView& tv, size_t j) {
   const bool flip = fq_fold_sign(s);
   const TableSeg sg = table_seg(tv, j);
   uint32_t carry = 0;
-  const uint32_t mask = (1u << sg.c) - 1u, half = 1u << (sg.c - 1);
   // software pipeline: the (random, 96-byte) table entry of window w+1 is requested before the
   // 7-multiply add of window w, so the gather latency hides behind arithmetic
   ge_niels e_cur;
@@ -224,56 +217,13 @@ __device__ __forceinline__ void table_mul_acc(ge_ext& acc, fq s, const TableView
     ge_niels e_next;
     bool have_next = false, neg_next = false;
     if (w < sg.W) {
-      uint32_t v = (s.v[0] & mask) + carry;
-      // shift the 256-bit scalar right by c bits (static register indices only)
-#pragma unroll
-      for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], sg.c);
-      s.v[7] >>= sg.c;
-      neg_next = v > half;
-      uint32_t mag = neg_next ? (mask + 1u) - v : v;
-      carry = neg_next ? 1u : 0u;
-      neg_next ^= flip;
+      const uint32_t mag = walk_digit(fq_take_window(s, carry, (uint32_t)sg.c), (uint32_t)sg.c, flip, carry, neg_next);
       if (mag != 0) {
         e_next = ge_load(sg.entry(w, mag - 1));
         have_next = true;
       }
     }
-    if (have_cur) acc = ge_add_niels(acc, e_cur, neg_cur);
-    e_cur = e_next;
-    have_cur = have_next;
-    neg_cur = neg_next;
-  }
-}
-
-// The same walk with the accumulator in the ten-limb form (fp10_dev.h): the product of two field elements is 142 VALU
-// instructions instead of 197 and the additions between products carry nothing.  Used by the row-commitment kernels, where
-// a lane adds hundreds of table entries to one accumulator; the entries stay in the packed 96-byte form in HBM.
-__device__ __forceinline__ void table_mul_acc10(ge10& acc, fq s, const TableView& tv, size_t j) {
-  const bool flip = fq_fold_sign(s);
-  const TableSeg sg = table_seg(tv, j);
-  uint32_t carry = 0;
-  const uint32_t mask = (1u << sg.c) - 1u, half = 1u << (sg.c - 1);
-  ge_niels e_cur;
-  bool have_cur = false, neg_cur = false;
-#pragma unroll 1
-  for (int w = 0; w <= sg.W; w++) {
-    ge_niels e_next;
-    bool have_next = false, neg_next = false;
-    if (w < sg.W) {
-      uint32_t v = (s.v[0] & mask) + carry;
-#pragma unroll
-      for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], sg.c);
-      s.v[7] >>= sg.c;
-      neg_next = v > half;
-      uint32_t mag = neg_next ? (mask + 1u) - v : v;
-      carry = neg_next ? 1u : 0u;
-      neg_next ^= flip;
-      if (mag != 0) {
-        e_next = ge_load(sg.entry(w, mag - 1));
-        have_next = true;
-      }
-    }
-    if (have_cur) acc = ge10_add_niels(acc, e_cur, neg_cur);
+    if (have_cur) acc = acc_add_niels(acc, e_cur, neg_cur);
     e_cur = e_next;
     have_cur = have_next;
     neg_cur = neg_next;
@@ -283,42 +233,21 @@ __device__ __forceinline__ void table_mul_acc10(ge10& acc, fq s, const TableView
 // accumulator of the row kernels, in the ten-limb form (fp10_dev.h)
 struct RowAcc {
   ge10 a = ge10_identity();
-  __device__ __forceinline__ void mul_acc(const fq& s, const TableView& tv, size_t j) { table_mul_acc10(a, s, tv, j); }
+  __device__ __forceinline__ void mul_acc(const fq& s, const TableView& tv, size_t j) { table_mul_acc(a, s, tv, j); }
   __device__ __forceinline__ void add_cached(const ge_cached& q) { a = ge10_add_cached(a, q); }
   __device__ __forceinline__ ge_ext ext() const { return ge10_to_ext(a); }
 };
 
-// digit w (c bits) of a canonical scalar, for the kernels that split one scalar over several lanes
-__device__ __forceinline__ uint32_t scalar_digit(const fq& s, int w, int c) {
-  int off = w * c, word = off >> 5, sh = off & 31;
-  uint32_t lo = s.v[word], hi = (word + 1 < 8) ? s.v[word + 1] : 0u;
-  uint64_t both = ((uint64_t)hi << 32) | lo;
-  return (uint32_t)(both >> sh) & ((1u << c) - 1u);
-}
-
-// signed-digit carry into window w0: decided by the nearest lower digit that is not exactly 2^(c-1)
-__device__ __forceinline__ uint32_t carry_into(const fq& s, int w0, int c) {
-  const uint32_t half = 1u << (c - 1);
-  for (int w = w0 - 1; w >= 0; w--) {
-    uint32_t d = scalar_digit(s, w, c);
-    if (d != half) return d > half ? 1u : 0u;
-  }
-  return 0u;
-}
-
-// windows [w0, w1) of s * g_j (sg = table_seg(tv, j))
+// windows [w0, w1) of s * g_j (sg = table_seg(tv, j)), for the kernels that split one scalar over several lanes
 __device__ __forceinline__ void table_mul_acc_range(ge_ext& acc, const fq& s_in, const TableSeg& sg, int w0, int w1) {
   fq s = s_in;
   const bool flip = fq_fold_sign(s);
   uint32_t carry = carry_into(s, w0, sg.c);
-  const uint32_t full = 1u << sg.c, half = 1u << (sg.c - 1);
 #pragma unroll 1
   for (int w = w0; w < w1; w++) {
-    uint32_t v = scalar_digit(s, w, sg.c) + carry;
-    bool neg = v > half;
-    uint32_t mag = neg ? full - v : v;
-    carry = neg ? 1u : 0u;
-    if (mag != 0) acc = ge_add_niels(acc, ge_load(sg.entry(w, mag - 1)), neg != flip);
+    bool neg;
+    const uint32_t mag = walk_digit(scalar_digit(s, w, sg.c) + carry, (uint32_t)sg.c, flip, carry, neg);
+    if (mag != 0) acc = ge_add_niels(acc, ge_load(sg.entry(w, mag - 1)), neg);
   }
 }
 
@@ -328,79 +257,23 @@ constexpr int kMsmBlock = 256;
 // extra dynamic LDS of the row-commitment kernels when other contexts prove on the device (vpin_ctx_set_shared_device): with
 // it one workgroup per CU instead of three (a wave per SIMD), the rest of every CU stays with the other lanes' kernels
 constexpr unsigned kSharedPad = 40000u;
-// rows x (ncols scalars from Z with row stride `stride`) + optional extra scalars on bases
-// [extra_base0, extra_base0 + n_extra).  out[row] = sum_j s[row][j] * g_j  (extended coords)
 constexpr int kSeg = 8192;  // scalars per compaction segment (uint16 indices, 16 KiB of LDS)
 
-__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
-                                                             const fq* __restrict__ extra, int n_extra, size_t extra_base0,
-                                                             TableView tv, ge_ext* __restrict__ out) {
-  const size_t row = blockIdx.x;
-  RowAcc acc;
-  const size_t total = ncols + (size_t)n_extra;
-  // A row of one repeated scalar s: s * (g_0 + ... + g_{ncols-1}) from the prefix-sum base (see gens_sum_kernel).
-  // Three probes keep ordinary rows from paying for the full comparison pass.
-  if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
-    const fq* zr = Z + row * stride;
-    const fq first = fq_load(zr);
-    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
-      int same = 1;
-      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
-      if (__syncthreads_and(same)) {
-        if (threadIdx.x == 0) {
-          if (blockIdx.y == 0) {  // with column chunks every chunk sees the same row: the first one owns it, the others add nothing
-            if (!fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
-            for (int e = 0; e < n_extra; e++) {
-              const fq x = fq_load(extra + row * (size_t)n_extra + e);
-              if (!fq_is_zero(x)) acc.mul_acc(fq_from_mont(x), tv, extra_base0 + e);
-            }
-          }
-          ge_ext* o = out + row * gridDim.y + blockIdx.y;
-          const ge_ext av = acc.ext();
-          ge_store(o, av);
-        }
-        return;
-      }
-    }
-  }
-  // gridDim.y column chunks per row (few-row MSMs need more than `rows` workgroups)
-  const size_t per = (total + gridDim.y - 1) / gridDim.y;
-  const size_t j0 = (size_t)blockIdx.y * per, j1 = (j0 + per < total) ? j0 + per : total;
-  // The witness is ~40% zeros in irregular positions; lanes that met a zero scalar would idle
-  // while their wave-mates do 32 table adds.  So each segment is first compacted: the indices
-  // of its non-zero scalars go to an LDS list (order is irrelevant: the group is commutative),
-  // then the threads stride over the dense list.
-  __shared__ uint16_t nz_list[kSeg];
-  __shared__ uint32_t nz_count;
-  for (size_t seg = j0; seg < j1; seg += kSeg) {
-    const size_t seg_end = (seg + kSeg < j1) ? seg + kSeg : j1;
-    if (threadIdx.x == 0) nz_count = 0;
-    __syncthreads();
-    for (size_t j = seg + threadIdx.x; j < seg_end; j += kMsmBlock) {
-      const fq* sp = (j < ncols) ? (Z + row * stride + j) : (extra + row * (size_t)n_extra + (j - ncols));
-      if (!fq_is_zero(fq_load(sp))) nz_list[atomicAdd(&nz_count, 1u)] = (uint16_t)(j - seg);
-    }
-    __syncthreads();
-    const uint32_t cnt = nz_count;
-    for (uint32_t k = threadIdx.x; k < cnt; k += kMsmBlock) {
-      const size_t j = seg + nz_list[k];
-      fq s;
-      size_t base;
-      if (j < ncols) { s = fq_load(Z + row * stride + j); base = j; }
-      else { s = fq_load(extra + row * (size_t)n_extra + (j - ncols)); base = extra_base0 + (j - ncols); }
-      acc.mul_acc(fq_from_mont(s), tv, base);
-    }
-    __syncthreads();
-  }
-  __shared__ ge_ext sh[kMsmBlock];
-  sh[threadIdx.x] = acc.ext();
-  __syncthreads();
-  ge_tree_quad(sh, kMsmBlock);
-  if (threadIdx.x == 0) {
-    const ge_ext av = sh[0];
-    ge_store(out + row * gridDim.y + blockIdx.y, av);
-  }
-}
+// "These rows of this polynomial", as every row kernel takes them: launch row i (a workgroup's blockIdx.x, or an entry of the
+// strip list) is row row_base + i * row_step of the polynomial; its ncols scalars go on the generators [0, ncols), its n_extra
+// extra scalars (blinds) on the bases [extra_base0, extra_base0 + n_extra).  Results are indexed by the launch row.
+struct RowArgs {
+  const fq* Z;
+  size_t stride, ncols;  // scalars between two rows of Z, scalars per row
+  const fq* extra;       // [launch rows][n_extra]
+  int n_extra;
+  size_t extra_base0;
+  size_t row_base, row_step;
+  int z_compact;  // Z holds only this launch's rows, densely (a rank's rows of a split commitment gathered on their own)
+  __device__ __forceinline__ size_t row(size_t i) const { return row_base + i * row_step; }  // row of the polynomial
+  __device__ __forceinline__ const fq* scalars(size_t i) const { return Z + (z_compact ? i : row(i)) * stride; }
+  __device__ __forceinline__ const fq* extras(size_t i) const { return extra + i * (size_t)n_extra; }
+};
 
 // ---- row commitment with one repeated scalar per row taken out (the derefs commitment) ---------------------------------
 // Derefs (sparse_mlpoly.rs:267-283): the col-derefs vector of matrix m is E_ry[col_m[i]], and in an R1CS the column of the
@@ -414,6 +287,67 @@ struct HotRows {
   const ge_cached* T[3];    // T[m][j] = E_ry[hot[m]] * g_j, j < ncols
   size_t row0, rows_per_vec;  // matrix m's vector occupies rows [row0 + m*rows_per_vec, row0 + (m+1)*rows_per_vec)
 };
+// the hot column of one row: entry j of the row is hot when idx && idx[j] == hot, and then costs T[j]; idx == nullptr: none
+// (HotRows{}, a row outside the three vectors, a matrix without a hot column)
+struct HotCol {
+  const uint32_t* idx = nullptr;
+  const ge_cached* T = nullptr;
+  uint32_t hot = 0xffffffffu;
+  __device__ __forceinline__ bool at(size_t j) const { return idx && idx[j] == hot; }
+};
+__device__ __forceinline__ HotCol hot_column(const HotRows& hr, size_t row, size_t ncols) {
+  HotCol h;
+  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
+    const size_t m = (row - hr.row0) / hr.rows_per_vec;
+    if (hr.hot[m] != 0xffffffffu) {
+      h.hot = hr.hot[m];
+      h.T = hr.T[m];
+      h.idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols;
+    }
+  }
+  return h;
+}
+
+// A row of one repeated scalar s (padding tails) is s * (g_0 + ... + g_{ncols-1}) from the prefix-sum base (see
+// gens_sum_kernel).  The test, the same answer in every lane of the workgroup, all of which call it.  Three
+// probes keep ordinary rows from paying for the full comparison pass.
+__device__ __forceinline__ bool row_is_constant(const fq* zr, size_t ncols, const TableView& tv) {
+  if (!(ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols)) return false;
+  const fq first = fq_load(zr);
+  if (!(fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1)))) return false;
+  int same = 1;
+  for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
+  return __syncthreads_and(same) != 0;
+}
+// the table base of S_k for a constant row of ncols = 2^k scalars
+__device__ __forceinline__ size_t constant_row_base(const TableView& tv, size_t ncols) {
+  return tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols));
+}
+// The constant row's point, for lane 0: s * S_k (s = the row's first scalar) plus the n_extra extras of launch row i (ra.n_extra, or a literal 0 in a kernel
+// that takes none).  With column chunks every chunk sees the same row: the first one owns it, the others add nothing (the identity).
+__device__ __forceinline__ ge_ext constant_row_point(const RowArgs& ra, size_t i, const TableView& tv, int n_extra) {
+  RowAcc acc;
+  if (blockIdx.y == 0) {
+    const fq first = fq_load(ra.scalars(i));
+    if (!fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, constant_row_base(tv, ra.ncols));
+    for (int e = 0; e < n_extra; e++) {
+      const fq x = fq_load(ra.extras(i) + e);
+      if (!fq_is_zero(x)) acc.mul_acc(fq_from_mont(x), tv, ra.extra_base0 + e);
+    }
+  }
+  return acc.ext();
+}
+
+// the end of a row workgroup: the lanes' partial sums through the LDS tree, lane 0 stores the sum to *o
+__device__ __forceinline__ void row_workgroup_end(ge_ext* sh, const ge_ext& a, ge_ext* o) {
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  ge_tree_quad(sh, kMsmBlock);
+  if (threadIdx.x == 0) {
+    const ge_ext av = sh[0];
+    ge_store(o, av);
+  }
+}
 
 // T[j] = v * g_j for j < n (*vp = v in Montgomery form, read on the device: no round trip), as cached points
 __global__ __launch_bounds__(64) void scalar_times_bases_kernel(const fq* __restrict__ vp, size_t n, TableView tv,
@@ -426,79 +360,75 @@ __global__ __launch_bounds__(64) void scalar_times_bases_kernel(const fq* __rest
   ge_store(T + j, ge_to_cached(acc));
 }
 
-__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols, TableView tv,
-                                                                 HotRows hr, ge_ext* __restrict__ out, size_t row_base, size_t row_step,
-                                                                 int z_compact, const uint8_t* __restrict__ strip_flag) {
-  const size_t row = row_base + (size_t)blockIdx.x * row_step;  // row of the polynomial; out[] is indexed by blockIdx.x
-  // z_compact: Z holds only this launch's rows, densely (a rank's rows of a split commitment gathered on their own)
-  const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
-  RowAcc acc;
-  // strip_flag[row of this launch] != 0: the table walks of this row are msm_strip_kernel's; only its hot entries are added here
-  const bool hot_only = strip_flag && strip_flag[blockIdx.x];
-  // a row of one repeated scalar (padding tails): s * (g_0 + ... + g_{ncols-1}), as in msm_rows_kernel
-  if (!hot_only && ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
-    const fq first = fq_load(zr);
-    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
-      int same = 1;
-      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
-      if (__syncthreads_and(same)) {
-        if (threadIdx.x == 0) {
-          // with column chunks every chunk sees the same row: the first one owns it, the others add nothing
-          if (blockIdx.y == 0 && !fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
-          ge_ext* o = out + (size_t)blockIdx.x * gridDim.y + blockIdx.y;
-          const ge_ext av = acc.ext();
-          ge_store(o, av);
-        }
-        return;
-      }
+// One workgroup per (row, column chunk): out[launch row * gridDim.y + blockIdx.y] = sum_j s[row][j] * g_j over the chunk
+// (extended coords).  kHot = false (msm_rows_kernel): the row's extras are appended to its columns.  kHot = true
+// (msm_rows_hot_kernel): no extras; the row's hot-column entries are added from hr's T instead of walked, and
+// strip_flag[launch row] != 0 says that the table walks of this row are msm_strip_kernel's: only its hot entries are added.
+template <bool kHot>
+__device__ __forceinline__ void msm_rows_body(const RowArgs& ra, const TableView& tv, const HotRows& hr, ge_ext* __restrict__ out,
+                                              const uint8_t* __restrict__ strip_flag) {
+  const size_t i = blockIdx.x;
+  const fq* zr = ra.scalars(i);
+  const size_t ncols = ra.ncols;
+  const bool hot_only = kHot && strip_flag && strip_flag[i];
+  if (!hot_only && row_is_constant(zr, ncols, tv)) {
+    if (threadIdx.x == 0) {
+      const ge_ext av = constant_row_point(ra, i, tv, kHot ? 0 : ra.n_extra);
+      ge_store(out + i * gridDim.y + blockIdx.y, av);
     }
+    return;
   }
-  const uint32_t* idx = nullptr;
-  const ge_cached* T = nullptr;
-  uint32_t hot = 0xffffffffu;
-  if (row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
-    const size_t m = (row - hr.row0) / hr.rows_per_vec;
-    if (hr.hot[m] != 0xffffffffu) {
-      hot = hr.hot[m];
-      T = hr.T[m];
-      idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols;
-    }
-  }
-  // one LDS list, two ends: ordinary non-zero scalars from the front, hot entries from the back
+  HotCol hc;
+  if (kHot) hc = hot_column(hr, ra.row(i), ncols);
+  const fq* xr = kHot ? nullptr : ra.extras(i);
+  const size_t total = kHot ? ncols : ncols + (size_t)ra.n_extra;
+  // gridDim.y column chunks per row: few-row MSMs need more than `rows` workgroups, and a row of 16384 full-width scalars is
+  // ~11 ms of one workgroup: a commitment (or a rank's share of one) of a few waves of such workgroups ends in a long, mostly
+  // idle tail
+  const size_t per = (total + gridDim.y - 1) / gridDim.y;
+  const size_t j0 = (size_t)blockIdx.y * per, j1 = (j0 + per < total) ? j0 + per : total;
+  // The witness is ~40% zeros in irregular positions; lanes that met a zero scalar would idle
+  // while their wave-mates do 32 table adds.  So each segment is first compacted: the indices
+  // of its non-zero scalars go to an LDS list (order is irrelevant: the group is commutative),
+  // then the threads stride over the dense list.
+  // One LDS list, two ends: ordinary non-zero scalars from the front, hot entries from the back.
   __shared__ uint16_t list[kSeg];
   __shared__ uint32_t n_front, n_back;
-  // gridDim.y column chunks per row: a row of 16384 full-width scalars is ~11 ms of one workgroup, and a commitment (or a
-  // rank's share of one) of a few waves of such workgroups ends in a long, mostly idle tail
-  const size_t per = (ncols + gridDim.y - 1) / gridDim.y;
-  const size_t c0 = (size_t)blockIdx.y * per, c1 = (c0 + per < ncols) ? c0 + per : ncols;
-  for (size_t seg = c0; seg < c1; seg += kSeg) {
-    const size_t seg_end = (seg + kSeg < c1) ? seg + kSeg : c1;
-    if (threadIdx.x == 0) { n_front = 0; n_back = 0; }
+  RowAcc acc;
+  for (size_t seg = j0; seg < j1; seg += kSeg) {
+    const size_t seg_end = (seg + kSeg < j1) ? seg + kSeg : j1;
+    if (threadIdx.x == 0) { n_front = 0; if (kHot) n_back = 0; }
     __syncthreads();
     for (size_t j = seg + threadIdx.x; j < seg_end; j += kMsmBlock) {
-      if (fq_is_zero(fq_load(zr + j))) continue;
-      if (idx && idx[j] == hot) list[kSeg - 1 - atomicAdd(&n_back, 1u)] = (uint16_t)(j - seg);
+      if (fq_is_zero(fq_load((kHot || j < ncols) ? zr + j : xr + (j - ncols)))) continue;
+      if (kHot && hc.at(j)) list[kSeg - 1 - atomicAdd(&n_back, 1u)] = (uint16_t)(j - seg);
       else if (!hot_only) list[atomicAdd(&n_front, 1u)] = (uint16_t)(j - seg);
     }
     __syncthreads();
-    const uint32_t nf = n_front, nb = n_back;
+    const uint32_t nf = n_front, nb = kHot ? n_back : 0u;
     for (uint32_t k = threadIdx.x; k < nf; k += kMsmBlock) {
       const size_t j = seg + list[k];
-      acc.mul_acc(fq_from_mont(fq_load(zr + j)), tv, j);
+      fq sc;
+      size_t base;
+      if (kHot || j < ncols) { sc = fq_load(zr + j); base = j; }
+      else { sc = fq_load(xr + (j - ncols)); base = ra.extra_base0 + (j - ncols); }
+      acc.mul_acc(fq_from_mont(sc), tv, base);
     }
-    for (uint32_t k = threadIdx.x; k < nb; k += kMsmBlock) acc.add_cached(ge_load(T + seg + list[kSeg - 1 - k]));
+    if (kHot)
+      for (uint32_t k = threadIdx.x; k < nb; k += kMsmBlock) acc.add_cached(ge_load(hc.T + seg + list[kSeg - 1 - k]));
     __syncthreads();
   }
   __shared__ ge_ext sh[kMsmBlock];
-  sh[threadIdx.x] = acc.ext();
-  __syncthreads();
-  ge_tree_quad(sh, kMsmBlock);
-  if (threadIdx.x == 0) {
-    const ge_ext av = sh[0];
-    ge_store(out + (size_t)blockIdx.x * gridDim.y + blockIdx.y, av);
-  }
+  row_workgroup_end(sh, acc.ext(), out + i * gridDim.y + blockIdx.y);
 }
 
+__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_kernel(RowArgs ra, TableView tv, ge_ext* __restrict__ out) {
+  msm_rows_body<false>(ra, tv, HotRows{}, out, nullptr);
+}
+__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(RowArgs ra, TableView tv, HotRows hr, ge_ext* __restrict__ out,
+                                                                    const uint8_t* __restrict__ strip_flag) {
+  msm_rows_body<true>(ra, tv, hr, out, strip_flag);
+}
 
 // ---- row per lane: the table walks of a LARGE commitment out of L2 instead of HBM -------------------------------------------
 // Under the row kernels above the chip sits at its power limit: tools/ubench_msm_variants (profiles/r04_ubench_msm_variants.txt)
@@ -515,24 +445,17 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_hot_kernel(const fq* __
 // (hot_only), and strip_combine_kernel sums the S partial points of a row into it.
 
 // flag[i] = 1: row i of the launch goes to msm_strip_kernel
-__global__ __launch_bounds__(kMsmBlock) void strip_classify_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols, HotRows hr,
-                                                                    size_t row_base, size_t row_step, int z_compact,
-                                                                    uint8_t* __restrict__ flag) {
-  const size_t row = row_base + (size_t)blockIdx.x * row_step;
-  const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
-  const uint32_t* idx = nullptr;
-  uint32_t hot = 0xffffffffu;
-  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
-    const size_t m = (row - hr.row0) / hr.rows_per_vec;
-    if (hr.hot[m] != 0xffffffffu) { hot = hr.hot[m]; idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols; }
-  }
+__global__ __launch_bounds__(kMsmBlock) void strip_classify_kernel(RowArgs ra, HotRows hr, uint8_t* __restrict__ flag) {
+  const size_t ncols = ra.ncols;
+  const fq* zr = ra.scalars(blockIdx.x);
+  const HotCol hc = hot_column(hr, ra.row(blockIdx.x), ncols);
   const fq first = fq_load(zr);
   int same = 1;
   uint32_t skipped = 0;
   for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) {
     const fq v = fq_load(zr + j);
     same &= fq_eq(first, v) ? 1 : 0;
-    skipped += (fq_is_zero(v) || (idx && idx[j] == hot)) ? 1u : 0u;
+    skipped += (fq_is_zero(v) || hc.at(j)) ? 1u : 0u;
   }
   __shared__ uint32_t sh[kMsmBlock];
   sh[threadIdx.x] = skipped;
@@ -573,24 +496,18 @@ __global__ __launch_bounds__(256) void strip_trim_kernel(const uint32_t* __restr
 }
 
 // parts[li * S + s] = sum over strip s of the table walks of listed row li (ten-limb accumulator)
-__global__ __launch_bounds__(kMsmBlock, 3) void msm_strip_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols, TableView tv, HotRows hr,
-                                                                  const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_count,
-                                                                  int S, size_t row_base, size_t row_step, int z_compact,
+__global__ __launch_bounds__(kMsmBlock, 3) void msm_strip_kernel(RowArgs ra, TableView tv, HotRows hr, const uint32_t* __restrict__ list,
+                                                                  const uint32_t* __restrict__ list_count, int S,
                                                                   ge_ext* __restrict__ parts, uint32_t* __restrict__ sync, int lag) {
   const uint32_t n = *list_count;
   const uint32_t s = blockIdx.x % (uint32_t)S, grp = blockIdx.x / (uint32_t)S;
   if (grp * kMsmBlock >= n) return;
   const uint32_t li = grp * kMsmBlock + threadIdx.x;
   const bool live = li < n;
-  const uint32_t i = list[live ? li : n - 1];
-  const size_t row = row_base + (size_t)i * row_step;
-  const fq* zr = Z + (z_compact ? (size_t)i : row) * stride;
-  const uint32_t* idx = nullptr;
-  uint32_t hot = 0xffffffffu;
-  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
-    const size_t m = (row - hr.row0) / hr.rows_per_vec;
-    if (hr.hot[m] != 0xffffffffu) { hot = hr.hot[m]; idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols; }
-  }
+  const uint32_t i = list[live ? li : n - 1];  // this lane's launch row
+  const size_t ncols = ra.ncols;
+  const fq* zr = ra.scalars(i);
+  const HotCol hc = hot_column(hr, ra.row(i), ncols);
   const size_t per = (ncols + (size_t)S - 1) / (size_t)S, j0 = (size_t)s * per, j1 = j0 + per < ncols ? j0 + per : ncols;
   ge10 acc = ge10_identity();
   // Keeping a strip's workgroups in step (sync != nullptr): a workgroup counts every generator it has finished, and starts
@@ -613,11 +530,11 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_strip_kernel(const fq* __res
       __syncthreads();
     }
     fq v = fq_load(zr + j);
-    const bool act = live && !fq_is_zero(v) && !(idx && idx[j] == hot);
+    const bool act = live && !fq_is_zero(v) && !hc.at(j);
     if (__builtin_amdgcn_ballot_w64(act) != 0) {  // somebody in the wave walks this generator
       fq sc = fq_from_mont(v);
       if (!act) sc = fq_zero();  // all digits zero: the walk below adds nothing for this lane, in step with its wave-mates
-      table_mul_acc10(acc, sc, tv, j);
+      table_mul_acc(acc, sc, tv, j);
     }
     if (my_sync) {
       __syncthreads();
@@ -650,80 +567,32 @@ __global__ __launch_bounds__(64) void strip_combine_kernel(const ge_ext* __restr
 //            to LDS as dig[w][column]: magnitude - 1 in bits 0..14, sign in bit 15, kNoDigit for a zero digit (and for every
 //            digit of a zero scalar or a hot-column entry);
 //   phase 2: the lanes of window w stride over dig[w][.]; a lane skips zero digits on its own (a short LDS scan, not an idle
-//            addition), and the entry of its next digit is requested before the current addition, as in table_mul_acc10.
+//            addition), and the entry of its next digit is requested before the current addition, as in table_mul_acc.
 // The hot-column entries of a derefs row are added afterwards by ALL lanes (add_cached from T[m], as in msm_rows_hot_kernel)
 // and tree-summed into window 0; a constant row is s * S_k over the multi-window table, as before.  LDS: 48 KiB of digits,
 // which the two reductions at the end reuse -- what msm_rows_kernel takes, so msm_lds_pad keeps its meaning.
 constexpr int kRowLdsBytes = 48 * 1024;
-constexpr uint16_t kNoDigit = 0xffffu;  // never a digit: a negative digit's magnitude is below 2^(c-1), c <= 16
 // columns per segment for W windows (host and device agree on it)
 static inline int row_segment(int W) { return ((kRowLdsBytes / 2) / W) & ~3; }
 
-// One signed digit of a sign-folded canonical scalar, low end first: takes the low c bits of s and the carry of the window below,
-// shifts s right by c bits, and returns magnitude - 1 in bits 0..14 with the sign in bit 15, or kNoDigit for a zero digit.
-// flip: the scalar was folded (s -> q - s), every digit changes sign.  A digit of exactly 2^(c-1) is taken as +2^(c-1) without the
-// fold and as -2^(c-1) (carrying) with it, so that AFTER the flip the negative magnitudes stay below 2^(c-1): 16 bits hold a
-// 16-bit window's digits.  The top window is never negated (its value is at most 2^(c-1), see row_windows).
-__device__ __forceinline__ uint16_t row_digit(fq& s, uint32_t& carry, int c, bool flip, bool top) {
-  const uint32_t mask = (1u << c) - 1u, half = 1u << (c - 1);
-  const uint32_t v = (s.v[0] & mask) + carry;
-#pragma unroll
-  for (int i = 0; i < 7; i++) s.v[i] = __builtin_amdgcn_alignbit(s.v[i + 1], s.v[i], c);
-  s.v[7] >>= c;
-  const bool neg = !top && (flip ? v >= half : v > half);
-  const uint32_t mag = neg ? (mask + 1u) - v : v;
-  carry = neg ? 1u : 0u;
-  return mag ? (uint16_t)((mag - 1u) | ((neg != flip) ? 0x8000u : 0u)) : kNoDigit;
-}
-
-__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
-                                                                     const fq* __restrict__ extra, int n_extra, size_t extra_base0,
-                                                                     TableView tv, RowTable rt, HotRows hr, int segn,
-                                                                     ge_ext* __restrict__ parts, size_t row_base, size_t row_step,
-                                                                     int z_compact) {
-  const size_t row = row_base + (size_t)blockIdx.x * row_step;  // row of the polynomial; parts[] is indexed by blockIdx.x
-  const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
-  const fq* xr = extra + (size_t)blockIdx.x * (size_t)n_extra;
+__global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(RowArgs ra, TableView tv, RowTable rt, HotRows hr, int segn,
+                                                                     ge_ext* __restrict__ parts) {
+  const size_t i = blockIdx.x;  // parts[] is indexed by the launch row
+  const size_t ncols = ra.ncols, extra_base0 = ra.extra_base0;
+  const fq* zr = ra.scalars(i);
+  const fq* xr = ra.extras(i);
   const int W = rt.W;
-  ge_ext* o = parts + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (size_t)W;  // the W window sums of this (row, chunk)
+  ge_ext* o = parts + (i * gridDim.y + blockIdx.y) * (size_t)W;  // the W window sums of this (row, chunk)
   __shared__ __align__(16) unsigned char lds[kRowLdsBytes];
   __shared__ uint32_t n_hot;
-  // a row of one repeated scalar (padding tails): s * (g_0 + ... + g_{ncols-1}) into window 0, as in msm_rows_kernel
-  if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
-    const fq first = fq_load(zr);
-    if (fq_eq(first, fq_load(zr + 1)) && fq_eq(first, fq_load(zr + ncols / 2)) && fq_eq(first, fq_load(zr + ncols - 1))) {
-      int same = 1;
-      for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
-      if (__syncthreads_and(same)) {
-        if (threadIdx.x == 0) {
-          RowAcc acc;
-          if (blockIdx.y == 0) {  // the first chunk owns the row, the others add nothing
-            if (!fq_is_zero(first)) acc.mul_acc(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
-            for (int e = 0; e < n_extra; e++) {
-              const fq x = fq_load(xr + e);
-              if (!fq_is_zero(x)) acc.mul_acc(fq_from_mont(x), tv, extra_base0 + e);
-            }
-          }
-          ge_store(o, acc.ext());
-        } else if ((int)threadIdx.x < W) {
-          ge_store_identity(o + threadIdx.x);
-        }
-        return;
-      }
-    }
+  // a constant row: s * S_k over the multi-window table into window 0, as in msm_rows_kernel
+  if (row_is_constant(zr, ncols, tv)) {
+    if (threadIdx.x == 0) ge_store(o, constant_row_point(ra, i, tv, ra.n_extra));
+    else if ((int)threadIdx.x < W) ge_store_identity(o + threadIdx.x);
+    return;
   }
-  const uint32_t* idx = nullptr;
-  const ge_cached* T = nullptr;
-  uint32_t hot = 0xffffffffu;
-  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
-    const size_t m = (row - hr.row0) / hr.rows_per_vec;
-    if (hr.hot[m] != 0xffffffffu) {
-      hot = hr.hot[m];
-      T = hr.T[m];
-      idx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols;
-    }
-  }
-  const size_t total = ncols + (size_t)n_extra;
+  const HotCol hc = hot_column(hr, ra.row(i), ncols);
+  const size_t total = ncols + (size_t)ra.n_extra;
   const size_t per = (total + gridDim.y - 1) / gridDim.y;
   const size_t j0 = (size_t)blockIdx.y * per, j1 = (j0 + per < total) ? j0 + per : total;
   // this lane's window, its rank among the window's lanes and their number
@@ -735,7 +604,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(const fq* __
     for (uint32_t jl = threadIdx.x; jl < n; jl += kMsmBlock) {
       const size_t j = seg + jl;
       fq s = fq_load(j < ncols ? zr + j : xr + (j - ncols));
-      const bool live = !fq_is_zero(s) && !(idx && j < ncols && idx[j] == hot);
+      const bool live = !fq_is_zero(s) && !(j < ncols && hc.at(j));
       bool flip = false;
       if (live) {
         s = fq_from_mont(s);
@@ -789,7 +658,7 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(const fq* __
   ge_ext mine = ge_identity();
   if ((int)threadIdx.x < W) mine = sh[threadIdx.x];
   __syncthreads();
-  if (idx) {  // uniform over the workgroup: the hot entries of this chunk, all lanes, into window 0
+  if (hc.idx) {  // uniform over the workgroup: the hot entries of this chunk, all lanes, into window 0
     uint16_t* list = reinterpret_cast<uint16_t*>(lds);
     RowAcc hacc;
     uint32_t any = 0;
@@ -799,11 +668,11 @@ __global__ __launch_bounds__(kMsmBlock, 3) void msm_rows_win_kernel(const fq* __
       if (threadIdx.x == 0) n_hot = 0;
       __syncthreads();
       for (size_t j = seg + threadIdx.x; j < seg_end; j += kMsmBlock)
-        if (idx[j] == hot && !fq_is_zero(fq_load(zr + j))) list[atomicAdd(&n_hot, 1u)] = (uint16_t)(j - seg);
+        if (hc.at(j) && !fq_is_zero(fq_load(zr + j))) list[atomicAdd(&n_hot, 1u)] = (uint16_t)(j - seg);
       __syncthreads();
       const uint32_t nh = n_hot;
       any |= nh;
-      for (uint32_t kk = threadIdx.x; kk < nh; kk += kMsmBlock) hacc.add_cached(ge_load(T + seg + list[kk]));
+      for (uint32_t kk = threadIdx.x; kk < nh; kk += kMsmBlock) hacc.add_cached(ge_load(hc.T + seg + list[kk]));
       __syncthreads();
     }
     if (any) {  // n_hot is read by every lane between two barriers: uniform
@@ -832,62 +701,45 @@ __global__ __launch_bounds__(64) void msm_rows_finish_kernel(ge_ext* __restrict_
   ge_store(out + i, ge10_to_ext(ge10_horner_windows(p, W, [c](int) { return c; })));
 }
 
-// Profiling aid (vpin_prof_enable(ctx, 2)): the affine table additions msm_rows_kernel performs for the same
-// arguments -- non-zero signed digits of every non-zero scalar, one scalar for a constant row -- summed into *count.
+// Profiling aid (vpin_prof_enable(ctx, 2)): the affine table additions the row kernels perform for the same arguments --
+// non-zero signed digits of every non-zero scalar, one scalar for a constant row -- summed into *count.  The digits are taken
+// with the walks' own steps: table_mul_acc's (fq_take_window, walk_digit) ...
 __device__ __forceinline__ uint32_t count_digits(fq s, const TableView& tv, size_t j) {
-  (void)fq_fold_sign(s);
+  const bool flip = fq_fold_sign(s);
   const TableSeg sg = table_seg(tv, j);
   uint32_t carry = 0, n = 0;
-  const uint32_t full = 1u << sg.c, half = 1u << (sg.c - 1);
-  for (int w = 0; w < sg.W; w++) {
-    uint32_t v = scalar_digit(s, w, sg.c) + carry;
-    const bool neg = v > half;
-    const uint32_t mag = neg ? full - v : v;
-    carry = neg ? 1u : 0u;
-    n += mag != 0;
-  }
+  bool neg;
+  for (int w = 0; w < sg.W; w++) n += walk_digit(fq_take_window(s, carry, (uint32_t)sg.c), (uint32_t)sg.c, flip, carry, neg) != 0;
   return n;
 }
-// the same for a scalar that msm_rows_win_kernel recodes into W digits of c bits
+// ... and msm_rows_win_kernel's, which recodes a scalar into W digits of c bits (row_digit)
 __device__ __forceinline__ uint32_t count_digits_row(fq s, int c, int W) {
   const bool flip = fq_fold_sign(s);
   uint32_t carry = 0, n = 0;
   for (int w = 0; w < W; w++) n += row_digit(s, carry, c, flip, w == W - 1) != kNoDigit;
   return n;
 }
-// c_row != 0: the launch goes to msm_rows_win_kernel with W_row windows of c_row bits (constant rows stay on the multi-window table)
-__global__ __launch_bounds__(kMsmBlock) void msm_count_adds_kernel(const fq* __restrict__ Z, size_t stride, size_t ncols,
-                                                                   const fq* __restrict__ extra, int n_extra, size_t extra_base0,
-                                                                   TableView tv, unsigned long long* __restrict__ count,
-                                                                   HotRows hr = HotRows{}, size_t row_base = 0, size_t row_step = 1,
-                                                                   int z_compact = 0, int c_row = 0, int W_row = 0) {
-  const size_t row = row_base + (size_t)blockIdx.x * row_step;
-  const fq* zr = Z + (z_compact ? (size_t)blockIdx.x : row) * stride;
-  // msm_rows_hot_kernel: the hot-column entries are not table additions
-  const uint32_t* hidx = nullptr;
-  uint32_t hot = 0xffffffffu;
-  if (hr.rows_per_vec && row >= hr.row0 && row < hr.row0 + 3 * hr.rows_per_vec) {
-    const size_t m = (row - hr.row0) / hr.rows_per_vec;
-    if (hr.hot[m] != 0xffffffffu) { hot = hr.hot[m]; hidx = hr.idx[m] + (row - hr.row0 - m * hr.rows_per_vec) * ncols; }
-  }
+// hr: the hot-column entries are not table additions.  c_row != 0: the launch goes to msm_rows_win_kernel with W_row windows of
+// c_row bits (constant rows stay on the multi-window table)
+__global__ __launch_bounds__(kMsmBlock) void msm_count_adds_kernel(RowArgs ra, TableView tv, HotRows hr, int c_row, int W_row,
+                                                                   unsigned long long* __restrict__ count) {
+  const size_t i = blockIdx.x, ncols = ra.ncols;
+  const fq* zr = ra.scalars(i);
+  const HotCol hc = hot_column(hr, ra.row(i), ncols);
   uint32_t n = 0;
-  bool constant = false;
-  if (ncols >= 256 && (ncols & (ncols - 1)) == 0 && ((size_t)1 << (tv.nbt - tv.sum0 - 1)) >= ncols) {
+  const bool constant = row_is_constant(zr, ncols, tv);
+  if (constant && threadIdx.x == 0) {
     const fq first = fq_load(zr);
-    int same = 1;
-    for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) same &= fq_eq(first, fq_load(zr + j)) ? 1 : 0;
-    constant = __syncthreads_and(same) != 0;
-    if (constant && threadIdx.x == 0 && !fq_is_zero(first))
-      n += count_digits(fq_from_mont(first), tv, tv.sum0 + (size_t)(63 - __builtin_clzll((unsigned long long)ncols)));
+    if (!fq_is_zero(first)) n += count_digits(fq_from_mont(first), tv, constant_row_base(tv, ncols));
   }
   if (!constant)
     for (size_t j = threadIdx.x; j < ncols; j += kMsmBlock) {
       const fq s = fq_load(zr + j);
-      if (!fq_is_zero(s) && !(hidx && hidx[j] == hot)) n += c_row ? count_digits_row(fq_from_mont(s), c_row, W_row) : count_digits(fq_from_mont(s), tv, j);
+      if (!fq_is_zero(s) && !hc.at(j)) n += c_row ? count_digits_row(fq_from_mont(s), c_row, W_row) : count_digits(fq_from_mont(s), tv, j);
     }
-  for (int e = threadIdx.x; e < n_extra; e += kMsmBlock) {
-    const fq x = fq_load(extra + row * (size_t)n_extra + e);
-    if (!fq_is_zero(x)) n += (c_row && !constant) ? count_digits_row(fq_from_mont(x), c_row, W_row) : count_digits(fq_from_mont(x), tv, extra_base0 + e);
+  for (int e = threadIdx.x; e < ra.n_extra; e += kMsmBlock) {
+    const fq x = fq_load(ra.extras(i) + e);
+    if (!fq_is_zero(x)) n += (c_row && !constant) ? count_digits_row(fq_from_mont(x), c_row, W_row) : count_digits(fq_from_mont(x), tv, ra.extra_base0 + e);
   }
   __shared__ uint32_t sh[kMsmBlock];
   sh[threadIdx.x] = n;
@@ -1629,82 +1481,249 @@ static bool row_table_use(const vpin_ctx* c, const vpin_gens* g, size_t rows, si
 
 // rows x (ncols + n_extra) scalars over the row table: msm_rows_win_kernel on `chunks` column chunks per row, then the finishing
 // pass into d_points[rows].  hr: the derefs commitment's hot columns (HotRows{} for plain rows).
-static int msm_rows_win(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols, const fq* d_extra,
-                        int n_extra, size_t extra_base0, const HotRows& hr, size_t row_base, size_t row_step, int z_compact,
-                        ge_ext* d_points) {
+static int msm_rows_win(vpin_ctx* c, const vpin_gens* g, const RowArgs& ra, size_t rows, const HotRows& hr, ge_ext* d_points) {
   const RowTable rt = row_view(g);
   const int segn = row_segment(rt.W);
   c->row_table_rows += rows;
-  const size_t total = ncols + (size_t)n_extra;
+  const size_t total = ra.ncols + (size_t)ra.n_extra;
   // Column chunks: a workgroup ends with two LDS trees and W stores, so a chunk is worth several segments; enough of them to
   // give a few-row commitment three workgroups per CU, at most 64.
   const size_t most = std::max<size_t>(1, total / ((size_t)segn * 2));
   size_t want = rows >= 768 ? 1 : (768 + rows - 1) / rows;
-  if (rows >= 768 && total > (size_t)kSeg) want = std::min<size_t>(8, (total + kSeg - 1) / kSeg);  // as msm_rows: short tails
+  if (rows >= 768 && total > (size_t)kSeg) want = std::min<size_t>(8, (total + kSeg - 1) / kSeg);  // as row_chunks: short tails
   const char* ec = getenv("VPIN_MSM_ROW_WIN_CHUNKS");  // tests and A/B runs; read per call
   const int chunks = ec && atoi(ec) > 0 ? std::min(atoi(ec), 64) : (int)std::max<size_t>(1, std::min<size_t>(64, std::min(want, most)));
   DevBuf parts(c);
   if (parts.alloc(rows * (size_t)chunks * (size_t)rt.W * sizeof(ge_ext))) return VPIN_ENOMEM;
-  hipLaunchKernelGGL(msm_rows_win_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, dZ, stride,
-                     ncols, d_extra, n_extra, extra_base0, view(g), rt, hr, segn, (ge_ext*)parts.p, row_base, row_step, z_compact);
+  hipLaunchKernelGGL(msm_rows_win_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, ra, view(g),
+                     rt, hr, segn, (ge_ext*)parts.p);
   hipLaunchKernelGGL(msm_rows_finish_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (ge_ext*)parts.p, rows, chunks,
                      rt.W, rt.c, d_points);
   VPIN_HIP_TRY(hipGetLastError());
   return VPIN_OK;
 }
 
-// walk_only: the caller knows its scalars to be mostly short (addresses, counters): the multi-window walk, where a lane skips a
-// short scalar's empty upper windows; in the row-table kernel those windows' lanes would idle
+// Column chunks per row of the multi-window row kernels (gridDim.y), `total` scalars per row.
+static int row_chunks(size_t rows, size_t total, bool hot_kernel) {
+  if (hot_kernel) {
+    // msm_rows_hot_kernel (the derefs commitment): one workgroup per compaction segment of a row, at most 8
+    static const int env_chunks = [] { const char* e = getenv("VPIN_MSM_HOT_CHUNKS"); return e ? atoi(e) : 0; }();
+    return env_chunks > 0 ? env_chunks : (int)std::max<size_t>(1, std::min<size_t>(8, total / kSeg));
+  }
+  if (rows < 128) {  // spread a few rows over the chip: ~one scalar per thread, <= 64 chunks per row
+    size_t want = (total + kMsmBlock - 1) / kMsmBlock * 4;
+    return (int)(want < 1 ? 1 : want > 64 ? 64 : want);
+  }
+  if (rows >= 768 && total > (size_t)kSeg) {
+    // long rows (more than one compaction segment): one workgroup per segment, so that a launch of a few waves of
+    // workgroups (a rank's share of a split commitment) does not end in a long, mostly idle tail
+    static const int env_chunks = [] { const char* e = getenv("VPIN_MSM_ROW_CHUNKS"); return e ? atoi(e) : 0; }();
+    return env_chunks > 0 ? env_chunks : (int)std::min<size_t>(8, (total + kSeg - 1) / kSeg);
+  }
+  if (rows < 768 && total >= 2 * (size_t)kMsmBlock) {
+    // Fewer than three workgroups per CU: a wave's 22-addition chains run at ~13 us per addition instead of ~9.5 us
+    // with the SIMDs full, and every thread walks several of them.  Split the rows into column chunks until the chip is
+    // full or a thread is down to one scalar (the 2^15..2^17-constraint instances' derefs commitment: 573 -> ~300 us).
+    size_t want = (768 + rows - 1) / rows, most = total / kMsmBlock;
+    return std::max(1, (int)(want < most ? want : most));
+  }
+  return 1;
+}
+
+// The shape of msm_strip_kernel's launch for `eligible` regular rows of R scalars on `slots` workgroup slots: `groups` x
+// `strips` workgroups that take the first `rows_used` eligible rows (0: none; the rows beyond the shape go back to the row
+// kernel).  Host arithmetic only.
+// Every CU must run the SAME number of strip workgroups, or the workgroups of a strip drift apart (a CU with two of them
+// runs each 1.5x faster than a CU with three) and a table block is long evicted from L2 when the slow ones want it: the
+// PMC pass of the first version (608 workgroups on 768 slots) showed 95 B of L2 misses per addition, more than the row
+// kernel's 34 B.
+// Choose the strips: every eligible row (G = ceil(n / 256) groups), S the largest multiple of 8 (a strip stays on one
+// XCD) with G x S workgroups all RESIDENT (3 per CU) -- they wait for each other (msm_strip_kernel's sync) -- and strips of
+// at least 128 generators.  Measured on the 2^25 instance (7844 eligible rows; profiles/r04_ab_strip.txt): free-running
+// workgroups 85.8 ms and 139 M FETCH_SIZE units per dispatch, one generator of slack 81.6 ms and 91 M, two 82.6 / 103, four
+// 85.0 / 111.
+struct StripShape { size_t groups; int strips; uint32_t rows_used; };
+static StripShape strip_shape(size_t R, uint32_t eligible, size_t slots, bool cu_masked, size_t min_list) {
+  const size_t G = ((size_t)eligible + kMsmBlock - 1) / kMsmBlock;
+  size_t bestG = 0;
+  int bestS = 0;
+  for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8)
+    if (G * (size_t)cand <= slots) { bestG = G; bestS = cand; }
+  // On a context confined to some of the CUs (vpin_ctx_create_cumask) "every eligible row" can leave the CUs unevenly
+  // loaded (31 groups x 16 strips on 576 slots): take fewer groups and more strips when that fills more slots.
+  // VPIN_MSM_STRIP_SHAPE=G,S forces a shape (A/B runs).
+  if (cu_masked)
+    for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8) {
+      const size_t g2 = std::min(G, slots / (size_t)cand);
+      if (g2 * kMsmBlock >= min_list && g2 * (size_t)cand > bestG * (size_t)bestS) { bestG = g2; bestS = cand; }
+    }
+  if (const char* eshape = getenv("VPIN_MSM_STRIP_SHAPE")) {
+    int eg = 0, esn = 0;
+    if (sscanf(eshape, "%d,%d", &eg, &esn) == 2 && eg > 0 && esn > 0 && esn % 8 == 0 && (size_t)esn <= R / 8) {
+      // the strip's workgroups wait for each other: a forced shape must be resident as a whole like the chosen ones (ADVICE r5)
+      if (std::min(G, (size_t)eg) * (size_t)esn <= slots) { bestG = std::min(G, (size_t)eg); bestS = esn; }
+      else if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] VPIN_MSM_STRIP_SHAPE=%d,%d refused: %zu workgroups on %zu slots\n", eg, esn, std::min(G, (size_t)eg) * (size_t)esn, slots);
+    }
+  }
+  return StripShape{bestG, bestS, bestG ? (uint32_t)std::min<size_t>(eligible, bestG * kMsmBlock) : 0u};
+}
+
+// What strip_take leaves for the launches of a commitment: the rows taken (n, 0: none), their flags for the row kernel (flag),
+// their list with its count behind it, and the launch shape.
+struct StripTake {
+  DevBuf flag, list, parts, sync;
+  size_t nrows = 0;
+  uint32_t n = 0;
+  int S = 16;
+  bool uniform_shape = false;  // every strip workgroup of the launch is resident at once: they may wait for each other
+  explicit StripTake(vpin_ctx* c) : flag(c), list(c), parts(c), sync(c) {}
+  const uint32_t* d_list() const { return (const uint32_t*)list.p; }
+  const uint32_t* d_count() const { return (const uint32_t*)list.p + nrows; }
+};
+
+// Row per lane (msm_strip_kernel) for a commitment of enough regular rows to keep every strip's block hot in L2 and the
+// chip full: the 2^25-constraint instance's 16384 x 16384 derefs polynomial (9.5 k of its rows qualify).  Smaller ones,
+// and a rank's share of a split commitment, stay with one workgroup per row.  Classifies the rows, lists and trims the regular
+// ones to the launch shape; st.n = the rows taken, whose table walks strip_launch does and strip_combine adds to the row
+// kernel's points.
+// VPIN_MSM_STRIP = 0: off, S: number of strips; VPIN_MSM_STRIP_MIN = n: take the path from n rows on (tests, A/B runs; read per
+// call so that a test can switch it)
+static int strip_take(vpin_ctx* c, const vpin_gens* g, const RowArgs& ra, size_t nrows, const HotRows& hr, StripTake& st) {
+  const char* es = getenv("VPIN_MSM_STRIP");
+  const char* em = getenv("VPIN_MSM_STRIP_MIN");
+  const size_t R = ra.ncols;
+  const int env_strip = es ? atoi(es) : -1;
+  const size_t min_rows = em ? (size_t)atol(em) : 8192, min_list = em ? (size_t)1 : 4096, min_R = em ? (size_t)64 : 4096;
+  st.S = env_strip > 0 ? env_strip : 16;
+  st.nrows = nrows;
+  // Not on a shared device (vpin_ctx_set_shared_device: other contexts prove at the same time and the row kernels run one
+  // workgroup per CU): with a single wave per SIMD nothing hides the strip kernel's per-generator chain scalar load ->
+  // Montgomery conversion -> first gather, and its workgroups no longer step together: the default LeNet step of bench.py
+  // measured 469-473 ms with it against 438-442 ms without (profiles/r04_ab_strip.txt), while the 2^25 instance proven alone
+  // gains (313 -> 303 ms).  VPIN_MSM_STRIP > 0 forces it (A/B runs).
+  // Nor for a rank's share of a split commitment (c->comm set: at W = 2 the share of 16384 rows is exactly min_rows, and
+  // rehearsal ranks share one GPU without saying so): its workgroups would not all be resident and the bounded wait of the
+  // kernel would be sat out per generator.
+  if (!(env_strip != 0 && (env_strip > 0 || (!c->shared_device && c->comm == nullptr)) && nrows >= min_rows && R >= min_R && R <= g->split &&
+        st.S % 8 == 0 && (size_t)st.S <= R / 8))
+    return VPIN_OK;
+  if (st.flag.alloc(nrows) || st.list.alloc((nrows + 1) * sizeof(uint32_t))) return VPIN_ENOMEM;
+  uint32_t* d_list = (uint32_t*)st.list.p;
+  uint32_t* d_count = d_list + nrows;
+  uint32_t n_strip = 0;
+  hipLaunchKernelGGL(strip_classify_kernel, dim3((unsigned)nrows), dim3(kMsmBlock), 0, c->stream, ra, hr, (uint8_t*)st.flag.p);
+  hipLaunchKernelGGL(strip_list_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)st.flag.p, nrows, d_list, d_count);
+  VPIN_HIP_TRY(hipMemcpyAsync(&n_strip, d_count, sizeof n_strip, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_strip < min_list) n_strip = 0;  // too few rows to share a block's fetch: the row kernel takes everything
+  if (n_strip && env_strip < 0) {
+    const size_t slots = (size_t)c->num_cus * (c->shared_device ? 1 : 3);
+    const StripShape shape = strip_shape(R, n_strip, slots, c->cu_masked, min_list);
+    if (shape.rows_used && shape.rows_used < n_strip)
+      hipLaunchKernelGGL(strip_trim_kernel, dim3((n_strip - shape.rows_used + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)d_list,
+                         d_count, shape.rows_used, n_strip, (uint8_t*)st.flag.p);
+    if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] %zu rows: %u eligible, %u taken as %zu groups x %d strips on %zu slots\n", nrows, n_strip, shape.rows_used, shape.groups, shape.strips, slots);
+    n_strip = shape.rows_used;
+    if (n_strip) {
+      st.S = shape.strips;
+      st.uniform_shape = true;
+    }
+  }
+  if (n_strip && st.parts.alloc((size_t)n_strip * (size_t)st.S * sizeof(ge_ext))) return VPIN_ENOMEM;
+  st.n = n_strip;
+  return VPIN_OK;
+}
+// the table walks of the rows taken: st.parts[li * S + s]
+static int strip_launch(vpin_ctx* c, const vpin_gens* g, const RowArgs& ra, const HotRows& hr, StripTake& st, unsigned pad) {
+  c->strip_rows_taken += st.n;
+  const unsigned groups = (unsigned)((st.n + kMsmBlock - 1) / kMsmBlock);
+  const size_t per = (ra.ncols + (size_t)st.S - 1) / (size_t)st.S;
+  const char* el = getenv("VPIN_MSM_STRIP_LAG");  // generators a workgroup may run ahead of its strip's slowest; 0: no sync
+  const int lag = el ? atoi(el) : 1;
+  uint32_t* d_sync = nullptr;
+  if (lag > 0 && st.uniform_shape) {
+    if (st.sync.alloc((size_t)st.S * (per + 1) * sizeof(uint32_t))) return VPIN_ENOMEM;
+    d_sync = (uint32_t*)st.sync.p;
+    VPIN_HIP_TRY(hipMemsetAsync(d_sync, 0, (size_t)st.S * (per + 1) * sizeof(uint32_t), c->stream));
+  }
+  hipLaunchKernelGGL(msm_strip_kernel, dim3(groups * (unsigned)st.S), dim3(kMsmBlock), pad, c->stream, ra, view(g), hr, st.d_list(),
+                     st.d_count(), st.S, (ge_ext*)st.parts.p, d_sync, lag);
+  return VPIN_OK;
+}
+
+// How a commitment's rows are launched.
+struct RowPolicy {
+  // the caller knows its scalars to be mostly short (addresses, counters): the multi-window walk, where a lane skips a short
+  // scalar's empty upper windows; in the row-table kernel those windows' lanes would idle
+  bool walk_only = false;
+  bool part_short = false;  // see row_table_min_scalars
+  // the derefs commitment: without a row table msm_rows_hot_kernel (hr's hot columns) and the strip path may be tried
+  bool may_strip = false;
+};
+
+// The one launch path of the row commitments: d_points[i] = the commitment of launch row i of ra, i < rows.  Over the row table
+// where row_table_use says so, else msm_rows_kernel or (may_strip) msm_rows_hot_kernel beside the strip kernel, on row_chunks
+// column chunks that are summed at the end.
+static int msm_rows_launch(vpin_ctx* c, const vpin_gens* g, const RowArgs& ra, size_t rows, const HotRows& hr, const RowPolicy& pol,
+                           ge_ext* d_points) {
+  const size_t total = ra.ncols + (size_t)ra.n_extra;
+  const int chunks = row_chunks(rows, total, pol.may_strip);
+  // With a row table the whole derefs commitment, regular rows included, goes to msm_rows_win_kernel.  Measured against the strip
+  // kernel forced (which then walks the 8-bit window table): step 345.5-347.1 against 431.6 ms, L5-mult alone 251.8 against 329.8 ms
+  // (profiles/r12_ab_row_table.txt).  An explicit VPIN_MSM_STRIP / VPIN_MSM_STRIP_MIN keeps its meaning: the
+  // strip and hot kernels over the multi-window table.
+  const bool strip_asked = pol.may_strip && (getenv("VPIN_MSM_STRIP") || getenv("VPIN_MSM_STRIP_MIN"));
+  const bool use_row = !pol.walk_only && !strip_asked && row_table_use(c, g, rows, ra.ncols, ra.n_extra, ra.extra_base0, pol.part_short);
+  const bool as_rows = pol.may_strip || rows >= 128;  // counted and profiled as a row commitment (not the few-row MSMs)
+  if (c->prof_count_adds && c->d_add_count && as_rows)
+    hipLaunchKernelGGL(msm_count_adds_kernel, dim3((unsigned)rows), dim3(kMsmBlock), 0, c->stream, ra, view(g), hr, use_row ? g->c_row : 0,
+                       use_row ? g->W_row : 0, c->d_add_count);
+  const double bytes = 32.0 * (double)rows * (double)total;
+  if (use_row) {
+    ProfScope ps(c, VPIN_K_MSM, bytes, as_rows ? VPIN_K_MSM_ROWS : -1);
+    return msm_rows_win(c, g, ra, rows, hr, d_points);
+  }
+  DevBuf parts(c);
+  ge_ext* dst = d_points;
+  if (chunks > 1) {
+    if (parts.alloc(rows * (size_t)chunks * sizeof(ge_ext))) return VPIN_ENOMEM;
+    dst = (ge_ext*)parts.p;
+  }
+  StripTake st(c);
+  if (pol.may_strip)
+    if (const int rc = strip_take(c, g, ra, rows, hr, st)) return rc;
+  {
+    ProfScope ps(c, VPIN_K_MSM, bytes, as_rows ? VPIN_K_MSM_ROWS : -1);
+    const unsigned pad = msm_lds_pad(c);
+    const dim3 grid((unsigned)rows, (unsigned)chunks);
+    if (st.n)
+      if (const int rc = strip_launch(c, g, ra, hr, st, pad)) return rc;
+    if (pol.may_strip)
+      hipLaunchKernelGGL(msm_rows_hot_kernel, grid, dim3(kMsmBlock), pad, c->stream, ra, view(g), hr, dst,
+                         st.n ? (const uint8_t*)st.flag.p : (const uint8_t*)nullptr);
+    else
+      hipLaunchKernelGGL(msm_rows_kernel, grid, dim3(kMsmBlock), pad, c->stream, ra, view(g), dst);
+    if (chunks > 1)
+      hipLaunchKernelGGL(ge_sum_chunks_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dst, rows, chunks,
+                         d_points);
+    if (st.n)
+      hipLaunchKernelGGL(strip_combine_kernel, dim3((st.n + 63) / 64), dim3(64), 0, c->stream, (const ge_ext*)st.parts.p, st.d_list(),
+                         st.d_count(), st.S, d_points);
+  }
+  VPIN_HIP_TRY(hipGetLastError());
+  return VPIN_OK;
+}
+
+// plain rows: rows x (ncols scalars from Z with row stride `stride`) + optional extra scalars on bases
+// [extra_base0, extra_base0 + n_extra).  d_points[row] = sum_j s[row][j] * g_j  (extended coords)
 static int msm_rows(vpin_ctx* c, const vpin_gens* g, const fq* dZ, size_t rows, size_t stride, size_t ncols,
                     const fq* d_extra, int n_extra, size_t extra_base0, ge_ext* d_points, bool walk_only = false,
                     bool part_short = false) {
   if (const int pm = pip_mode())
     if (n_extra <= 1 && ncols + (size_t)n_extra <= 32768)
       return msm_rows_pip(c, g, dZ, rows, stride, ncols, d_extra, n_extra, extra_base0, pm < 0 ? 0 : pm, d_points);
-  double nz_est = (double)rows * ((double)ncols + n_extra);
-  size_t total = ncols + (size_t)n_extra;
-  int chunks = 1;
-  if (rows < 128) {  // spread a few rows over the chip: ~one scalar per thread, <= 64 chunks per row
-    size_t want = (total + kMsmBlock - 1) / kMsmBlock * 4;
-    chunks = (int)(want < 1 ? 1 : want > 64 ? 64 : want);
-  } else if (rows >= 768 && total > (size_t)kSeg) {
-    // long rows (more than one compaction segment): one workgroup per segment, so that a launch of a few waves of
-    // workgroups (a rank's share of a split commitment) does not end in a long, mostly idle tail
-    static const int env_chunks = [] { const char* e = getenv("VPIN_MSM_ROW_CHUNKS"); return e ? atoi(e) : 0; }();
-    chunks = env_chunks > 0 ? env_chunks : (int)std::min<size_t>(8, (total + kSeg - 1) / kSeg);
-  } else if (rows < 768 && total >= 2 * (size_t)kMsmBlock) {
-    // Fewer than three workgroups per CU: a wave's 22-addition chains run at ~13 us per addition instead of ~9.5 us
-    // with the SIMDs full, and every thread walks several of them.  Split the rows into column chunks until the chip is
-    // full or a thread is down to one scalar (the 2^15..2^17-constraint instances' derefs commitment: 573 -> ~300 us).
-    size_t want = (768 + rows - 1) / rows, most = total / kMsmBlock;
-    chunks = (int)(want < most ? want : most);
-    if (chunks < 1) chunks = 1;
-  }
-  const bool use_row = !walk_only && row_table_use(c, g, rows, ncols, n_extra, extra_base0, part_short);
-  DevBuf parts(c);
-  ge_ext* dst = d_points;
-  if (chunks > 1 && !use_row) {
-    if (parts.alloc(rows * (size_t)chunks * sizeof(ge_ext))) return VPIN_ENOMEM;
-    dst = (ge_ext*)parts.p;
-  }
-  if (c->prof_count_adds && c->d_add_count && rows >= 128)
-    hipLaunchKernelGGL(msm_count_adds_kernel, dim3((unsigned)rows), dim3(kMsmBlock), 0, c->stream, dZ, stride, ncols, d_extra,
-                       n_extra, extra_base0, view(g), c->d_add_count, HotRows{}, (size_t)0, (size_t)1, 0, use_row ? g->c_row : 0,
-                       use_row ? g->W_row : 0);
-  if (use_row) {
-    ProfScope ps(c, VPIN_K_MSM, 32.0 * nz_est, rows >= 128 ? VPIN_K_MSM_ROWS : -1);
-    return msm_rows_win(c, g, dZ, rows, stride, ncols, d_extra, n_extra, extra_base0, HotRows{}, 0, 1, 0, d_points);
-  }
-  {
-    ProfScope ps(c, VPIN_K_MSM, 32.0 * nz_est, rows >= 128 ? VPIN_K_MSM_ROWS : -1);
-    hipLaunchKernelGGL(msm_rows_kernel, dim3((unsigned)rows, (unsigned)chunks), dim3(kMsmBlock), msm_lds_pad(c), c->stream, dZ, stride, ncols,
-                       d_extra, n_extra, extra_base0, view(g), dst);
-  }
-  if (chunks > 1)
-    hipLaunchKernelGGL(ge_sum_chunks_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dst,
-                       rows, chunks, d_points);
-  VPIN_HIP_TRY(hipGetLastError());
-  return VPIN_OK;
+  return msm_rows_launch(c, g, RowArgs{dZ, stride, ncols, d_extra, n_extra, extra_base0, 0, 1, 0}, rows, HotRows{},
+                         RowPolicy{walk_only, part_short, false}, d_points);
 }
 
 // The end of every commitment: compress the n points at d_pts and bring the encodings home, the first n / k of them to out0,
@@ -1769,44 +1788,6 @@ int vpin_hyrax_commit_rows(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z,
 
 namespace vpin {
 
-// The shape of msm_strip_kernel's launch for `eligible` regular rows of R scalars on `slots` workgroup slots: `groups` x
-// `strips` workgroups that take the first `rows_used` eligible rows (0: none; the rows beyond the shape go back to the row
-// kernel).  Host arithmetic only.
-// Every CU must run the SAME number of strip workgroups, or the workgroups of a strip drift apart (a CU with two of them
-// runs each 1.5x faster than a CU with three) and a table block is long evicted from L2 when the slow ones want it: the
-// PMC pass of the first version (608 workgroups on 768 slots) showed 95 B of L2 misses per addition, more than the row
-// kernel's 34 B.
-// Choose the strips: every eligible row (G = ceil(n / 256) groups), S the largest multiple of 8 (a strip stays on one
-// XCD) with G x S workgroups all RESIDENT (3 per CU) -- they wait for each other (msm_strip_kernel's sync) -- and strips of
-// at least 128 generators.  Measured on the 2^25 instance (7844 eligible rows; profiles/r04_ab_strip.txt): free-running
-// workgroups 85.8 ms and 139 M FETCH_SIZE units per dispatch, one generator of slack 81.6 ms and 91 M, two 82.6 / 103, four
-// 85.0 / 111.
-struct StripShape { size_t groups; int strips; uint32_t rows_used; };
-static StripShape strip_shape(size_t R, uint32_t eligible, size_t slots, bool cu_masked, size_t min_list) {
-  const size_t G = ((size_t)eligible + kMsmBlock - 1) / kMsmBlock;
-  size_t bestG = 0;
-  int bestS = 0;
-  for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8)
-    if (G * (size_t)cand <= slots) { bestG = G; bestS = cand; }
-  // On a context confined to some of the CUs (vpin_ctx_create_cumask) "every eligible row" can leave the CUs unevenly
-  // loaded (31 groups x 16 strips on 576 slots): take fewer groups and more strips when that fills more slots.
-  // VPIN_MSM_STRIP_SHAPE=G,S forces a shape (A/B runs).
-  if (cu_masked)
-    for (int cand = 8; cand <= 64 && (size_t)cand * 128 <= R; cand += 8) {
-      const size_t g2 = std::min(G, slots / (size_t)cand);
-      if (g2 * kMsmBlock >= min_list && g2 * (size_t)cand > bestG * (size_t)bestS) { bestG = g2; bestS = cand; }
-    }
-  if (const char* eshape = getenv("VPIN_MSM_STRIP_SHAPE")) {
-    int eg = 0, esn = 0;
-    if (sscanf(eshape, "%d,%d", &eg, &esn) == 2 && eg > 0 && esn > 0 && esn % 8 == 0 && (size_t)esn <= R / 8) {
-      // the strip's workgroups wait for each other: a forced shape must be resident as a whole like the chosen ones (ADVICE r5)
-      if (std::min(G, (size_t)eg) * (size_t)esn <= slots) { bestG = std::min(G, (size_t)eg); bestS = esn; }
-      else if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] VPIN_MSM_STRIP_SHAPE=%d,%d refused: %zu workgroups on %zu slots\n", eg, esn, std::min(G, (size_t)eg) * (size_t)esn, slots);
-    }
-  }
-  return StripShape{bestG, bestS, bestG ? (uint32_t)std::min<size_t>(eligible, bestG * kMsmBlock) : 0u};
-}
-
 // DensePolynomial::commit(gens, None) for the derefs polynomial (8N scalars as L rows of R; sparse_mlpoly.rs:525-531) with the
 // hot column of each matrix's col-derefs vector taken out (msm_rows_hot_kernel).  col_idx[m]: the N column indices of matrix
 // m on the device, hot[m]: its hot column or 0xffffffff, e_ry: the table the col-derefs were gathered from.
@@ -1847,101 +1828,9 @@ int hyrax_commit_derefs_hot(vpin_ctx* c, const vpin_gens* g, const vpin_table* Z
     for (int m = 0; m < 3; m++)
       if (hot[m] == distinct[k]) hr.T[m] = Tk;
   }
-  // With a row table the whole commitment, regular rows included, goes to msm_rows_win_kernel.  Measured against the strip kernel
-  // forced (which then walks the 8-bit window table): step 345.5-347.1 against 431.6 ms, L5-mult alone 251.8 against 329.8 ms
-  // (profiles/r12_ab_row_table.txt).  An explicit VPIN_MSM_STRIP / VPIN_MSM_STRIP_MIN keeps its meaning: the
-  // strip and hot kernels over the multi-window table.
-  const char* es = getenv("VPIN_MSM_STRIP");
-  const char* em = getenv("VPIN_MSM_STRIP_MIN");
-  const bool use_row = !es && !em && row_table_use(c, g, nrows, R, 0, 0);
-  if (c->prof_count_adds && c->d_add_count)
-    hipLaunchKernelGGL(msm_count_adds_kernel, dim3((unsigned)nrows), dim3(kMsmBlock), 0, c->stream, zbase, R, R, (const fq*)nullptr, 0,
-                       (size_t)0, view(g), c->d_add_count, hr, row0, row_step, z_compact, use_row ? g->c_row : 0, use_row ? g->W_row : 0);
-  if (use_row) {
-    {
-      ProfScope ps(c, VPIN_K_MSM, 32.0 * (double)(nrows * R), VPIN_K_MSM_ROWS);
-      if (const int rc = msm_rows_win(c, g, zbase, nrows, R, R, nullptr, 0, 0, hr, row0, row_step, z_compact, (ge_ext*)dpts.p)) return rc;
-    }
-    return compress_to_host(c, (const ge_ext*)dpts.p, nrows, out_compressed);
-  }
-  static const int env_chunks = [] { const char* e = getenv("VPIN_MSM_HOT_CHUNKS"); return e ? atoi(e) : 0; }();
-  const int chunks = env_chunks > 0 ? env_chunks : (int)std::max<size_t>(1, std::min<size_t>(8, R / kSeg));
-  DevBuf dparts(c);
-  if (chunks > 1 && dparts.alloc(nrows * (size_t)chunks * sizeof(ge_ext))) return VPIN_ENOMEM;
-  // Row per lane (msm_strip_kernel) for a commitment of enough regular rows to keep every strip's block hot in L2 and the
-  // chip full: the 2^25-constraint instance's 16384 x 16384 derefs polynomial (9.5 k of its rows qualify).  Smaller ones,
-  // and a rank's share of a split commitment, stay with one workgroup per row.
-  // VPIN_MSM_STRIP = 0: off, S: number of strips; VPIN_MSM_STRIP_MIN = n: take the path from n rows on (tests, A/B runs; read per
-  // call so that a test can switch it)
-  const int env_strip = es ? atoi(es) : -1;
-  const size_t min_rows = em ? (size_t)atol(em) : 8192, min_list = em ? (size_t)1 : 4096, min_R = em ? (size_t)64 : 4096;
-  int S = env_strip > 0 ? env_strip : 16;
-  DevBuf dflag(c), dlist(c), dsparts(c), dsync(c);
-  uint32_t n_strip = 0;
-  bool uniform_shape = false;  // every strip workgroup of the launch is resident at once: they may wait for each other
-  // Not on a shared device (vpin_ctx_set_shared_device: other contexts prove at the same time and the row kernels run one
-  // workgroup per CU): with a single wave per SIMD nothing hides the strip kernel's per-generator chain scalar load ->
-  // Montgomery conversion -> first gather, and its workgroups no longer step together: the default LeNet step of bench.py
-  // measured 469-473 ms with it against 438-442 ms without (profiles/r04_ab_strip.txt), while the 2^25 instance proven alone
-  // gains (313 -> 303 ms).  VPIN_MSM_STRIP > 0 forces it (A/B runs).
-  // Nor for a rank's share of a split commitment (c->comm set: at W = 2 the share of 16384 rows is exactly min_rows, and
-  // rehearsal ranks share one GPU without saying so): its workgroups would not all be resident and the bounded wait below
-  // would be sat out per generator.
-  if (env_strip != 0 && (env_strip > 0 || (!c->shared_device && c->comm == nullptr)) && nrows >= min_rows && R >= min_R && R <= g->split &&
-      S % 8 == 0 && (size_t)S <= R / 8) {
-    if (dflag.alloc(nrows) || dlist.alloc((nrows + 1) * sizeof(uint32_t))) return VPIN_ENOMEM;
-    uint32_t* d_list = (uint32_t*)dlist.p;
-    uint32_t* d_count = d_list + nrows;
-    hipLaunchKernelGGL(strip_classify_kernel, dim3((unsigned)nrows), dim3(kMsmBlock), 0, c->stream, zbase, R, R, hr, row0, row_step, z_compact,
-                       (uint8_t*)dflag.p);
-    hipLaunchKernelGGL(strip_list_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint8_t*)dflag.p, nrows, d_list, d_count);
-    VPIN_HIP_TRY(hipMemcpyAsync(&n_strip, d_count, sizeof n_strip, hipMemcpyDeviceToHost, c->stream));
-    VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n_strip < min_list) n_strip = 0;  // too few rows to share a block's fetch: the row kernel takes everything
-    if (n_strip && env_strip < 0) {
-      const size_t slots = (size_t)c->num_cus * (c->shared_device ? 1 : 3);
-      const StripShape shape = strip_shape(R, n_strip, slots, c->cu_masked, min_list);
-      if (shape.rows_used && shape.rows_used < n_strip)
-        hipLaunchKernelGGL(strip_trim_kernel, dim3((n_strip - shape.rows_used + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)d_list,
-                           d_count, shape.rows_used, n_strip, (uint8_t*)dflag.p);
-      if (getenv("VPIN_MSM_STRIP_TRACE")) fprintf(stderr, "[strip] %zu rows: %u eligible, %u taken as %zu groups x %d strips on %zu slots\n", nrows, n_strip, shape.rows_used, shape.groups, shape.strips, slots);
-      n_strip = shape.rows_used;
-      if (n_strip) {
-        S = shape.strips;
-        uniform_shape = true;
-      }
-    }
-    if (n_strip && dsparts.alloc((size_t)n_strip * (size_t)S * sizeof(ge_ext))) return VPIN_ENOMEM;
-  }
-  const uint8_t* d_flag = n_strip ? (const uint8_t*)dflag.p : nullptr;
-  {
-    ProfScope ps(c, VPIN_K_MSM, 32.0 * (double)(nrows * R), VPIN_K_MSM_ROWS);
-    const unsigned pad = msm_lds_pad(c);
-    if (n_strip) {
-      c->strip_rows_taken += n_strip;
-      const unsigned groups = (unsigned)((n_strip + kMsmBlock - 1) / kMsmBlock);
-      const size_t per = (R + (size_t)S - 1) / (size_t)S;
-      const char* el = getenv("VPIN_MSM_STRIP_LAG");  // generators a workgroup may run ahead of its strip's slowest; 0: no sync
-      const int lag = el ? atoi(el) : 1;
-      uint32_t* d_sync = nullptr;
-      if (lag > 0 && uniform_shape) {
-        if (dsync.alloc((size_t)S * (per + 1) * sizeof(uint32_t))) return VPIN_ENOMEM;
-        d_sync = (uint32_t*)dsync.p;
-        VPIN_HIP_TRY(hipMemsetAsync(d_sync, 0, (size_t)S * (per + 1) * sizeof(uint32_t), c->stream));
-      }
-      hipLaunchKernelGGL(msm_strip_kernel, dim3(groups * (unsigned)S), dim3(kMsmBlock), pad, c->stream, zbase, R, R, view(g), hr,
-                         (const uint32_t*)dlist.p, (const uint32_t*)dlist.p + nrows, S, row0, row_step, z_compact, (ge_ext*)dsparts.p,
-                         d_sync, lag);
-    }
-    hipLaunchKernelGGL(msm_rows_hot_kernel, dim3((unsigned)nrows, (unsigned)chunks), dim3(kMsmBlock), pad, c->stream, zbase, R, R,
-                       view(g), hr, chunks > 1 ? (ge_ext*)dparts.p : (ge_ext*)dpts.p, row0, row_step, z_compact, d_flag);
-    if (chunks > 1)
-      hipLaunchKernelGGL(ge_sum_chunks_kernel, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, c->stream, (const ge_ext*)dparts.p, nrows,
-                         chunks, (ge_ext*)dpts.p);
-    if (n_strip)
-      hipLaunchKernelGGL(strip_combine_kernel, dim3((n_strip + 63) / 64), dim3(64), 0, c->stream, (const ge_ext*)dsparts.p,
-                         (const uint32_t*)dlist.p, (const uint32_t*)dlist.p + nrows, S, (ge_ext*)dpts.p);
-  }
+  if (const int rc = msm_rows_launch(c, g, RowArgs{zbase, R, R, nullptr, 0, 0, row0, row_step, z_compact}, nrows, hr,
+                                     RowPolicy{false, false, true}, (ge_ext*)dpts.p))
+    return rc;
   return compress_to_host(c, (const ge_ext*)dpts.p, nrows, out_compressed);
 }
 
