@@ -42,6 +42,7 @@ def up_to_date():
 def build(force=False, verbose=False):
     if not force and up_to_date():
         build_devtest(verbose=verbose)
+        build_hosttest(verbose=verbose)
         return LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)
     objs = []
@@ -68,6 +69,7 @@ def build(force=False, verbose=False):
     subprocess.check_call(cmd)
     build_cli(verbose)
     build_devtest(force=True, verbose=verbose)
+    build_hosttest(force=True, verbose=verbose)
     return LIB_PATH
 
 
@@ -109,6 +111,45 @@ def build_devtest(force=False, verbose=False, out=None, csrc=None):
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", DEVTEST_SRC, "-o", out,
            "-I", csrc or CSRC, "-L", LIB_DIR, "-lvpin_hip", "-Wl,-rpath,$ORIGIN"]
     cmd += os.environ.get("VPIN_HIPCC_FLAGS", "").split()
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return out
+
+
+HOSTTEST_DIR = os.path.join(os.path.dirname(HERE), "tests", "hostarith")
+HOSTTEST_SRC = os.path.join(HOSTTEST_DIR, "hostarith.cpp")
+HOSTTEST_MAIN = os.path.join(HOSTTEST_DIR, "hostarith_main.cpp")
+HOSTTEST_LIB = os.path.join(LIB_DIR, "libvpin_hosttest.so")
+HOSTTEST_FLAGS = ["--offload-host-only", "-O3", "-std=c++17", "-fPIC", "-fopenmp"]  # the host pass with the product's flags
+
+
+def hosttest_deps():
+    return [HOSTTEST_SRC] + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "host", "*.h"))
+
+
+def build_hosttest(force=False, verbose=False, out=None, csrc=None):
+    """vpin_amd/lib/libvpin_hosttest.so: tests/hostarith/hostarith.cpp, one extern "C" function per function of host/field.h,
+    host/curve.h and the UniPoly / eq helpers of host/prover_common.h, compiled by hipcc's host pass with the product's flags.
+    Test-only and a library of its own: nothing of it is in libvpin_hip.so or include/vpin_hip.h, and it refers to neither.
+    out / csrc: another output file and another copy of csrc's headers (a mutated copy, to see that the tests notice)."""
+    if out is None and csrc is None and not force and os.path.exists(HOSTTEST_LIB) and all(
+            os.path.getmtime(s) <= os.path.getmtime(HOSTTEST_LIB) for s in hosttest_deps()):
+        return HOSTTEST_LIB
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = out or HOSTTEST_LIB
+    cmd = [hipcc()] + HOSTTEST_FLAGS + ["-shared", HOSTTEST_SRC, "-o", out, "-I", csrc or CSRC]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_hosttest_program(out, sanitize="address,undefined", verbose=False):
+    """the same harness as a program of its own (tests/hostarith/hostarith_main.cpp reads a vector file and prints the results),
+    host code only, with the sanitizers compiled in: sanitized code is run as a child process, never loaded into python."""
+    cmd = [hipcc()] + HOSTTEST_FLAGS + ["-g", "-fno-omit-frame-pointer", "-Xarch_host", f"-fsanitize={sanitize}", "-fno-sanitize-recover=all",
+                                        HOSTTEST_SRC, HOSTTEST_MAIN, "-o", out, "-I", CSRC]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
