@@ -1,5 +1,6 @@
-// devarith.hip -- test-only harness: every device function of fq_dev.h, fp_dev.h, fp10_dev.h, e2_dev.h and the helpers of
-// ge_tree_dev.h behind one __global__ kernel and one extern "C" launcher each, so that tests/test_gpu_dev_*.py can hand them
+// devarith.hip -- test-only harness: every device function of fq_dev.h, fp_dev.h, fp10_dev.h, e2_dev.h, the helpers of
+// ge_tree_dev.h and the shared sum-check pieces of sc_dev.h (block_sum, take_pd, the pair bodies) behind one __global__
+// kernel and one extern "C" launcher each, so that tests/test_gpu_dev_*.py can hand them
 // chosen LIMB PATTERNS (not only chosen values) and compare with plain integer arithmetic (tests/limb_vectors.py).
 //
 // Conventions: inputs and outputs are flat arrays of raw 32-bit words, IW words in and OW words out per case; one case per
@@ -20,18 +21,15 @@
 #include "fp_dev.h"
 #include "fq_dev.h"
 #include "ge_tree_dev.h"
-
-namespace vpin {
-fq_const make_fq_const(const uint8_t* p);  // sumcheck.hip (declared in sc_dev.h)
-}
+#include "sc_dev.h"
 
 using namespace vpin;
 
 namespace {
 
-struct DevBuf {
+struct DvBuf {
   void* p = nullptr;
-  ~DevBuf() {
+  ~DvBuf() {
     if (p) (void)hipFree(p);
   }
 };
@@ -39,7 +37,7 @@ struct DevBuf {
 template <class Kernel>
 int dv_run(Kernel kernel, const uint32_t* in, size_t iw, uint32_t* out, size_t ow, int n, int block, int grid) {
   if (n <= 0) return 0;
-  DevBuf din, dout;
+  DvBuf din, dout;
   hipError_t e;
   if ((e = hipMalloc(&din.p, iw * n * 4)) != hipSuccess) return (int)e;
   if ((e = hipMalloc(&dout.p, ow * n * 4)) != hipSuccess) return (int)e;
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(64) void k_fq_mul_const_host(const uint32_t* __rest
 extern "C" int dv_fq_mul_const_host(const uint8_t* r32, const uint32_t* in, uint32_t* out, int n) {
   if (n <= 0) return 0;
   const fq_const c = make_fq_const(r32);
-  DevBuf din, dout;
+  DvBuf din, dout;
   hipError_t e;
   const size_t bytes = (size_t)n * 32;
   if ((e = hipMalloc(&din.p, bytes + sizeof(c))) != hipSuccess) return (int)e;
@@ -182,6 +180,94 @@ extern "C" int dv_fq_mul_const_host(const uint8_t* r32, const uint32_t* in, uint
 
 // one wave per case: in 64 elements, out the 64 lanes' totals
 DV_BLOCK(fq_wave_sum, 512, 512, 64, st8(co + 8 * tid, fq_wave_sum(ld8<fq>(ci + 8 * tid)));)
+
+// ---- sc_dev.h: block_sum, take_pd, the pair bodies ------------------------------------------------------------------------
+// in: nw, then two sets of THREADS x NE elements (set, thread, k); out: the NE sums of the first set, then of the second.
+// Two calls in a row, as finish_block makes them; nw = THREADS / 64 goes through the default argument.
+template <int NE, int THREADS>
+__device__ __forceinline__ void block_sum_case(const uint32_t* ci, uint32_t* co, int tid) {
+  const int nw = (int)ci[0];
+  fq e[NE], f[NE];
+  for (int k = 0; k < NE; k++) {
+    e[k] = ld8<fq>(ci + 1 + 8 * (NE * tid + k));
+    f[k] = ld8<fq>(ci + 1 + 8 * NE * THREADS + 8 * (NE * tid + k));
+  }
+  const bool all = nw == THREADS / 64;  // uniform over the workgroup
+  const fq s = all ? block_sum<NE, THREADS>(e) : block_sum<NE, THREADS>(e, nw);
+  const fq t = all ? block_sum<NE, THREADS>(f) : block_sum<NE, THREADS>(f, nw);
+  if (tid < NE) { st8(co + 8 * tid, s); st8(co + 8 * (NE + tid), t); }
+}
+DV_BLOCK(block_sum_2_256, 1 + 16 * 2 * 256, 32, 256, block_sum_case<2, 256>(ci, co, tid);)
+DV_BLOCK(block_sum_3_256, 1 + 16 * 3 * 256, 48, 256, block_sum_case<3, 256>(ci, co, tid);)
+DV_BLOCK(block_sum_2_512, 1 + 16 * 2 * 512, 32, 512, block_sum_case<2, 512>(ci, co, tid);)
+DV_BLOCK(block_sum_3_512, 1 + 16 * 3 * 512, 48, 512, block_sum_case<3, 512>(ci, co, tid);)
+
+// One table of 4 q entries (q <= 64), lane i < q takes pair i.  in: mode (PdMode; 4 = PD_FOLD_TO with dst == src), q, 2 unused
+// words, r, the 64 words of r's constant form (tt[k][i], staged through stage_fq_const), 256 entries.  out: the table
+// afterwards (256 entries), the destination of mode 3 (128 entries), then (p, d) of the 64 lanes.
+DV_BLOCK(take_pd, 4 + 8 + 64 + 2048, 2048 + 1024 + 1024, 64,
+         const int mode = (int)ci[0];
+         const size_t q = ci[1];
+         fq_const rc;
+         for (int k = 0; k < 64; k++) rc.tt[k >> 3][k & 7] = ci[12 + k];
+         const FoldR fr{ld8<fq>(ci + 4), stage_fq_const(rc)};
+         fq* tab = reinterpret_cast<fq*>(co);
+         fq* dst = tab + 256;
+         for (size_t e = tid; e < 4 * q; e += 64) fq_store(tab + e, ld8<fq>(ci + 76 + 8 * e));
+         __syncthreads();
+         fq p = fq_zero(); fq d = fq_zero();
+         if ((size_t)tid < q) {
+           if (mode == 0) take_pd<PD_LOAD>(tab, tid, q, fr, p, d);
+           else if (mode == 1) take_pd<PD_FOLD>(tab, tid, q, fr, p, d);
+           else if (mode == 2) take_pd<PD_FOLD_C>(tab, tid, q, fr, p, d);
+           else take_pd<PD_FOLD_TO>(tab, mode == 3 ? dst : tab, tid, q, fr, p, d);
+         }
+         st8(co + 3072 + 16 * tid, p); st8(co + 3072 + 16 * tid + 8, d);)
+
+// np <= 15 pairs through one pair body on one lane, one lane kernel per fold mode M.  in: body, 1 unused word, np, 1 unused
+// word, r, r's constant form (tt[k][i]), E[15], four tables of 60 entries (4 np used, pair i of np).  out: e[0..2] (e[2] unused
+// by the K = 2 body), one unused row, the four tables afterwards, the dot-product body's three destination tables of 30 entries.
+// body: 0 / 1 pair_ktab with K = 2 / 4; 2 / 3 pair_phase1 without / with LEAD; 4 pair_prod without LEAD; 5 / 6 pair_prod
+// with LEAD through LeadNow / LeadAcc; 7 pair_dotp (BIND when the mode is not PD_LOAD).
+// Everything is inlined into the kernel on purpose.  A body of this size left as a function of its own (a lambda called per
+// mode) needs long branches, and the compiler builds those in s[30:31], the function's return address: it never returns.
+template <PdMode M>
+__device__ __forceinline__ void sc_body_case(const uint32_t* ci, uint32_t* co) {
+  const int body = (int)ci[0];
+  const size_t np = ci[2];
+  alignas(16) uint32_t tt[8][8];
+  for (int k = 0; k < 64; k++) tt[k >> 3][k & 7] = ci[12 + k];
+  const FoldR fr{ld8<fq>(ci + 4), tt};
+  const fq* E = reinterpret_cast<const fq*>(ci + 76);
+  fq* tab = reinterpret_cast<fq*>(co + 32);
+  for (int e = 0; e < 240; e++) fq_store(tab + e, ld8<fq>(ci + 196 + 8 * e));
+  const Tabs<2> t2{{tab, tab + 60}};
+  const Tabs<3> t3{{tab, tab + 60, tab + 120}};
+  const Tabs<4> t4{{tab, tab + 60, tab + 120, tab + 180}};
+  const fq* src[3] = {tab, tab + 60, tab + 120};
+  fq* dst[3] = {tab + 240, tab + 270, tab + 300};
+  Acc<2> a2; a2.init();
+  Acc<4> a4; a4.init();
+  LeadNow now; now.init();
+  LeadAcc lazy; lazy.init();
+  for (size_t p = 0; p < np && p < 15; p++) {
+    if (body == 0) pair_ktab<2, M>(a2, t2, p, np, fr);
+    else if (body == 1) pair_ktab<4, M>(a4, t4, p, np, fr);
+    else if (body == 2) pair_phase1<M, false>(a4, t3, E, p, np, fr);
+    else if (body == 3) pair_phase1<M, true>(a4, t3, E, p, np, fr);
+    else if (body == 4) pair_prod<M, false>(a4, now, tab, tab + 60, E, p, np, fr);
+    else if (body == 5) pair_prod<M, true>(a4, now, tab, tab + 60, E, p, np, fr);
+    else if (body == 6) pair_prod<M, true>(a4, lazy, tab, tab + 60, E, p, np, fr);
+    else pair_dotp<M != PD_LOAD>(a4, src, dst, p, np, fr);
+  }
+  lazy.flush(a4.e);
+  if (body == 0) { st8(co, a2.e[0]); st8(co + 8, a2.e[1]); }
+  else { st8(co, a4.e[0]); st8(co + 8, a4.e[1]); st8(co + 16, a4.e[2]); }
+}
+DV_LANE(sc_body_load, 4 + 8 + 64 + 120 + 1920, 32 + 1920 + 720, 64, sc_body_case<PD_LOAD>(ci, co);)
+DV_LANE(sc_body_fold, 4 + 8 + 64 + 120 + 1920, 32 + 1920 + 720, 64, sc_body_case<PD_FOLD>(ci, co);)
+DV_LANE(sc_body_fold_c, 4 + 8 + 64 + 120 + 1920, 32 + 1920 + 720, 64, sc_body_case<PD_FOLD_C>(ci, co);)
+DV_LANE(sc_body_fold_to, 4 + 8 + 64 + 120 + 1920, 32 + 1920 + 720, 64, sc_body_case<PD_FOLD_TO>(ci, co);)
 
 // ---- ge_tree_dev.h: fq_signed_window ------------------------------------------------------------------------------------
 // in: the canonical scalar, c, W, wide (window w is c bits wide for w < wide and c - 1 above: msm_var.hip; wide = W is

@@ -173,7 +173,8 @@ def batched_round(ctx, forest_v, n, ncirc, length, E_v, e_off, r, lead, dotp=Non
 
 
 @pytest.mark.parametrize("lg_pairs,ncirc,with_dotp,lead", [(13, 12, True, True), (13, 12, True, False), (20, 12, False, True),
-                                                            (20, 4, False, False), (22, 2, False, True), (9, 12, True, True)])
+                                                            (20, 4, False, False), (22, 2, False, True), (9, 12, True, True),
+                                                            (9, 12, True, False), (9, 4, False, False)])
 def test_spark_batched_rounds_vs_oracle(ctx, lg_pairs, ncirc, with_dotp, lead):
     """three consecutive rounds of prove_cubic_batched on level 0 of a forest: round 0 unbound (<false,*>), then two
     bound rounds (<true,*>; the dot-product tables fold into scratch first, then in place)"""

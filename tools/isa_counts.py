@@ -56,16 +56,18 @@ MSM_KERNELS = ("msm_rows_kernel", "msm_rows_hot_kernel", "msm_strip_kernel", "ms
                "scalar_times_bases_kernel", "single_base_mul_kernel", "bullet_step_kernel", "msm_wide_kernel")
 
 
-def resources(lines, kernels):
-    """registers, spills, scratch and LDS of the named kernels from the listing's amdhsa.kernels metadata"""
+def resources(lines, kernels=None):
+    """registers, spills, scratch and LDS of the named kernels (None: every kernel of the listing) from the listing's
+    amdhsa.kernels metadata; int and bool template arguments become name<4> and name<1,0>"""
     text = "\n".join(lines)
     out = {}
     for blk in re.split(r"\n  - ", text[text.index("amdhsa.kernels:"):])[1:]:
-        m = re.search(r"\n    \.name:\s+_ZN4vpin\d+(\w+?_kernel)(?:ILi(\d+)E)?", blk)
-        if m and m.group(1) in kernels:
-            name = m.group(1) + (f"<{m.group(2)}>" if m.group(2) else "")
+        m = re.search(r"\n    \.name:\s+_ZN4vpin\d+(\w+?_kernel)(?:I((?:L[ib]\d+E)+)E)?", blk)
+        if m and (kernels is None or m.group(1) in kernels):
+            targs = re.findall(r"L[ib](\d+)E", m.group(2) or "")
+            name = m.group(1) + (f"<{','.join(targs)}>" if targs else "")
             out[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in RESOURCE_KEYS}
-    return out
+    return dict(sorted(out.items()))
 
 
 def main():
@@ -84,7 +86,9 @@ def main():
     big = max(ls, key=lambda l: l["valu"])
     res["sc_cubic3_kernel<true, true>"] = {"valu_per_pair": big["valu"], "v_mad_u64_u32_per_pair": big["v_mad_u64_u32"],
                                            "loads_per_pair": big["vmem_loads"], "stores_per_pair": big["vmem_stores"]}
+    res["sumcheck_resources"] = resources(sc)
     sp = isa(os.path.join(ROOT, "vpin_amd", "csrc", "spark.hip"))
+    res["spark_resources"] = resources(sp)
     ls = loops(kernel_body(sp, "_ZN4vpin17prod_round_kernelILb1ELb1ELb1EE"))
     big = max(ls, key=lambda l: l["valu"])
     # the loop holds the every-seventh-pair flush of the lazily reduced sums (sc_dev.h LeadAcc): price body and flush apart

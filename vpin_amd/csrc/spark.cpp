@@ -19,6 +19,7 @@
 #include "host/proof_sizes.h"
 #include "host/prover_common.h"
 #include "gadget_dev.h"
+#include "sc_dev.h"
 #include "spark_dev.h"
 
 namespace {
@@ -278,8 +279,6 @@ static void write_batched(Writer& w, const Batched& b) {
   }
   for (int k = 0; k < 3; k++) w_scalars(w, b.dotp[k].data(), b.dotp[k].size());
 }
-
-static inline size_t pyramid_offset(int ell, int k) { return ((size_t)1 << ell) - ((size_t)2 << (ell - k)); }
 
 // The six DotProductCircuit halves ride along on layer 0 of the ops forest.  N leaves per half pair on this rank, vals = the
 // three val slices (3 x N), derefs = the six derefs slices (6 x N): the whole tables, or -- split by residue class -- the
@@ -596,7 +595,7 @@ static int product_prove(vpin_ctx* c, vpin::SparkForest& f, int npc, DotpCtx* do
               res = reinterpret_cast<const Fq*>(vpin::spark_tail_sums(c));
             }
           } else if (runs) {
-            const vpin::fq* E = pyr->d + pyramid_offset(kl, j + 1);
+            const vpin::fq* E = pyr->d + vpin::pyramid_offset(kl, j + 1);
             if ((rc = vpin::spark_prod_round(c, &f, layer_id, len, E, rprev, ndl_here, rd.lead_ok))) return rc;
             if (ndl_here && (rc = vpin::spark_dotp_round(c, dotp->N, dotp->vals, dotp->derefs, dotp->scratch, len, j == 1, rprev, halves, ndl_here))) return rc;
             if ((rc = vpin::spark_wait_flag(c))) return rc;

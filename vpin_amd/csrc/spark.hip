@@ -266,29 +266,9 @@ struct Finisher {
   int fused;           // 0: the workgroups only store their partials, round_finish_kernel sums and publishes (large grids)
 };
 
-// block-wide sums of e[0..2]: valid in threads 0..2 (thread k holds sum k)
-__device__ __forceinline__ fq block_sum3(fq* e) {
-  __shared__ fq sh[kBlock / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    fq t = fq_wave_sum(e[k]);
-    if (lane == 0) sh[wave][k] = t;
-  }
-  __syncthreads();
-  fq t = fq_zero();
-  if (threadIdx.x < 3) {
-    t = sh[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; w++) t = fq_add(t, sh[w][threadIdx.x]);
-  }
-  __syncthreads();  // sh is reused by a second call
-  return t;
-}
-
 // called by every thread of the block after the per-thread accumulators e[3] are final
 __device__ __forceinline__ void finish_block(fq* e, const Finisher& f) {
-  fq t = block_sum3(e);
+  fq t = block_sum<3, kBlock>(e);
   if (!f.fused) {
     // Large grids: the "last block done" pattern below costs every workgroup an agent-scope release fence, and on a part
     // with one L2 per XCD that is an L2 write-back per workgroup, serialised per XCD -- measured 0.14 us x workgroups
@@ -307,11 +287,9 @@ __device__ __forceinline__ void finish_block(fq* e, const Finisher& f) {
     __syncthreads();
     if (!is_last) return;
     __threadfence();  // acquire: the other blocks' partials (never read before by this CU in this kernel)
-    fq s[3] = {fq_zero(), fq_zero(), fq_zero()};
-    for (int b = threadIdx.x; b < (int)gridDim.x; b += kBlock)
-#pragma unroll
-      for (int k = 0; k < 3; k++) s[k] = fq_add(s[k], fq_load(&mine[(size_t)b * 3 + k]));
-    t = block_sum3(s);
+    fq s[3];
+    sum_partial_rows<3>(mine, (int)gridDim.x, threadIdx.x, kBlock, s);
+    t = block_sum<3, kBlock>(s);  // a second call: block_sum's trailing barrier has freed its LDS rows
   }
   if (threadIdx.x < 3) {
     fq_store(&f.out[3 * (size_t)(f.inst0 + blockIdx.y) + threadIdx.x], t);
@@ -330,49 +308,25 @@ __device__ __forceinline__ void finish_block(fq* e, const Finisher& f) {
 
 // ---- batched cubic rounds ------------------------------------------------------------------
 
-// unit-stride fold with separate source and destination (the first fold of the dot-product tables
-// must not overwrite the committed polynomials)
-__device__ __forceinline__ void fold_pd2(const fq* src, fq* dst, size_t i, size_t q, const fq& r, fq& p, fq& d) {
-  fq a0 = fq_load(src + i), a1 = fq_load(src + 2 * q + i);
-  fq b0 = fq_load(src + q + i), b1 = fq_load(src + 3 * q + i);
-  p = fq_add(a0, fq_mul(r, fq_sub(a1, a0)));
-  fq hi = fq_add(b0, fq_mul(r, fq_sub(b1, b0)));
-  fq_store(dst + i, p);
-  fq_store(dst + q + i, hi);
-  d = fq_sub(hi, p);
-}
-
-// LEAD: return sum E*A_0*B_0 and sum E*dA*dB (sc_dev.h lead_bc) instead of the sums at x = 0, 2, 3; its folds use the
-// launch-wide constant form of r (fq_dev.h fq_mul_const, constants in LDS)
+// LEAD: return sum E*A_0*B_0 and sum E*dA*dB (sc_dev.h pair_prod through LeadAcc, the two products by E unreduced) instead
+// of the sums at x = 0, 2, 3; its folds use the launch-wide constant form of r (fq_dev.h fq_mul_const, constants in LDS)
 // BIG: the same code under its own name for launches of >= 2^20 pairs per circuit (the streaming regime), so profilers
 // report that class separately (bench.py roofline.secondary, tools/pmc_summary.py)
 template <bool BIND, bool LEAD, bool BIG = false>
 __global__ __launch_bounds__(kBlock, kMinWaves) void prod_round_kernel(fq* __restrict__ forest, size_t stride, size_t off, size_t h,
                                                                        const fq* __restrict__ E, size_t pairs, fq r, fq_const rc,
                                                                        Finisher fin) {
-  __shared__ __attribute__((aligned(16))) uint32_t tt[8][8];
-  if (BIND && LEAD) {
-    if (threadIdx.x < 64) tt[threadIdx.x >> 3][threadIdx.x & 7] = rc.tt[threadIdx.x >> 3][threadIdx.x & 7];
-    __syncthreads();
-  }
+  constexpr PdMode M = !BIND ? PD_LOAD : LEAD ? PD_FOLD_C : PD_FOLD;
+  FoldR fr{r, nullptr};
+  if constexpr (M == PD_FOLD_C) fr.tt = stage_fq_const(rc);
   fq* A = forest + (size_t)blockIdx.y * stride + off;
   fq* B = A + h;
   Acc<4> acc;
   acc.init();
   LeadAcc lacc;
   if (LEAD) lacc.init();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock) {
-    fq u[3], p1, d1, p2, d2;
-    if (BIND && LEAD) { fold_pd_c(A, i, pairs, tt, p1, d1); fold_pd_c(B, i, pairs, tt, p2, d2); }
-    else if (BIND) { fold_pd(A, i, pairs, r, p1, d1); fold_pd(B, i, pairs, r, p2, d2); }
-    else { load_pd(A, i, pairs, p1, d1); load_pd(B, i, pairs, p2, d2); }
-    if (LEAD) {
-      lacc.add(acc.e, fq_load(E + i), fq_mul(p1, p2), fq_mul(d1, d2));  // lead_bc, the two products by E unreduced
-    } else {
-      acc.stage_bc(u, p1, d1, p2, d2);
-      acc.stage_e(u, fq_load(E + i));
-    }
-  }
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock)
+    pair_prod<M, LEAD>(acc, lacc, A, B, E, i, pairs, fr);
   if (LEAD) lacc.flush(acc.e);
   finish_block(acc.e, fin);
 }
@@ -399,17 +353,12 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void dotp_round_kernel(const fq*
     src[1] = derefs + (size_t)(3 + m) * N + (size_t)half * hN;
     src[2] = vals + (size_t)m * N + (size_t)half * hN;
   }
+  const FoldR fr{r, nullptr};
   Acc<4> acc;
   acc.init();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock) {
-    fq u[3], p1, d1, p2, d2;
-    if (BIND) { fold_pd2(src[0], dst[0], i, pairs, r, p1, d1); fold_pd2(src[1], dst[1], i, pairs, r, p2, d2); }
-    else { load_pd(src[0], i, pairs, p1, d1); load_pd(src[1], i, pairs, p2, d2); }
-    acc.stage_bc(u, p1, d1, p2, d2);
-    if (BIND) fold_pd2(src[2], dst[2], i, pairs, r, p1, d1);
-    else load_pd(src[2], i, pairs, p1, d1);
-    acc.stage_a(u, p1, d1);
-  }
+  // the first fold must not overwrite the committed polynomials: src -> scratch, later rounds scratch in place
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock)
+    pair_dotp<BIND>(acc, src, dst, i, pairs, fr);
   finish_block(acc.e, fin);
 }
 
@@ -426,10 +375,8 @@ __global__ __launch_bounds__(kFinishBlock) void round_finish_kernel(const fq* __
     const bool dp = inst >= ncirc;
     const fq* p = dp ? partials_d + (size_t)(inst - ncirc) * nd * 3 : partials + (size_t)inst * np * 3;
     const int nb = dp ? nd : np;
-    fq e[3] = {fq_zero(), fq_zero(), fq_zero()};
-    for (int b = lane; b < nb; b += 64)
-#pragma unroll
-      for (int k = 0; k < 3; k++) e[k] = fq_add(e[k], fq_load(&p[(size_t)b * 3 + k]));
+    fq e[3];
+    sum_partial_rows<3>(p, nb, lane, 64, e);
 #pragma unroll
     for (int k = 0; k < 3; k++) e[k] = fq_wave_sum(e[k]);
     if (lane == 0) {
@@ -443,30 +390,6 @@ __global__ __launch_bounds__(kFinishBlock) void round_finish_kernel(const fq* __
   if (threadIdx.x == 0) {
     __threadfence_system();
     *(volatile uint32_t*)flag = seq;
-  }
-}
-
-// per-instance finisher: out[3*(inst0 + y) + k] = sum over the instance's block partials
-__global__ __launch_bounds__(kBlock) void inst_finish_kernel(const fq* __restrict__ partials, int nblocks, int inst0,
-                                                             fq* __restrict__ out) {
-  const fq* p = partials + (size_t)blockIdx.x * nblocks * 3;
-  fq e[3] = {fq_zero(), fq_zero(), fq_zero()};
-  for (int b = threadIdx.x; b < nblocks; b += kBlock)
-#pragma unroll
-    for (int k = 0; k < 3; k++) e[k] = fq_add(e[k], fq_load(&p[(size_t)b * 3 + k]));
-  __shared__ fq sh[kBlock / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    fq s = fq_wave_sum(e[k]);
-    if (lane == 0) sh[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    fq s = sh[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; w++) s = fq_add(s, sh[w][threadIdx.x]);
-    fq_store(&out[3 * (size_t)(inst0 + blockIdx.x) + threadIdx.x], s);
   }
 }
 
@@ -1002,13 +925,11 @@ int spark_prod_round(vpin_ctx* c, const SparkForest* f, int level, size_t len, c
     // folded halves written
     const double bytes = (double)f->ncirc * 2 * 32.0 * (r ? (double)len * 1.5 : (double)len) + 32.0 * (r ? (double)len * 1.5 : (double)len);
     ProfScope ps(c, VPIN_K_SPARK_ROUND, bytes, pairs >= ((size_t)1 << 20) ? VPIN_K_SPARK_ROUND_BIG : -1, (double)f->ncirc * (double)pairs);
-#define VPIN_PROD_LAUNCH(B_, L_, G_)                                                                                              \
-  hipLaunchKernelGGL((prod_round_kernel<B_, L_, G_>), dim3(grid, f->ncirc), dim3(kBlock), 0, c->stream, f->base, f->stride(), \
-                     f->level_off(level), h, E, pairs, rr, rconst, fin)
-    const bool big = lead && pairs >= ((size_t)1 << 20);
-    if (r) { if (big) VPIN_PROD_LAUNCH(true, true, true); else if (lead) VPIN_PROD_LAUNCH(true, true, false); else VPIN_PROD_LAUNCH(true, false, false); }
-    else { if (big) VPIN_PROD_LAUNCH(false, true, true); else if (lead) VPIN_PROD_LAUNCH(false, true, false); else VPIN_PROD_LAUNCH(false, false, false); }
-#undef VPIN_PROD_LAUNCH
+    dispatch_bools([&](auto B, auto L, auto G) {
+      constexpr bool kLead = decltype(L)::value, kBig = kLead && decltype(G)::value;  // BIG exists for the LEAD rounds only
+      hipLaunchKernelGGL((prod_round_kernel<decltype(B)::value, kLead, kBig>), dim3(grid, f->ncirc), dim3(kBlock), 0, c->stream,
+                         f->base, f->stride(), f->level_off(level), h, E, pairs, rr, rconst, fin);
+    }, r != nullptr, lead, pairs >= ((size_t)1 << 20));
   }
   VPIN_HIP_TRY(hipGetLastError());
   if (!fin.fused && !with_dotp) return round_finish_launch(c, partials, f->ncirc, grid, 0, 0);
@@ -1040,12 +961,10 @@ int spark_dotp_round(vpin_ctx* c, size_t N, const fq* vals, const fq* comb_deref
   {
     const double bytes = ndotp * 3 * 32.0 * (r ? (double)len * 1.5 : (double)len);
     ProfScope ps(c, VPIN_K_SPARK_ROUND, bytes);
-    if (r)
-      hipLaunchKernelGGL((dotp_round_kernel<true>), dim3(grid, ndotp), dim3(kBlock), 0, c->stream, comb_derefs, vals, N, scratch,
-                         from_scratch, pairs, rr, fin, kmap);
-    else
-      hipLaunchKernelGGL((dotp_round_kernel<false>), dim3(grid, ndotp), dim3(kBlock), 0, c->stream, comb_derefs, vals, N, scratch,
-                         false, pairs, rr, fin, kmap);
+    dispatch_bools([&](auto B) {
+      hipLaunchKernelGGL((dotp_round_kernel<decltype(B)::value>), dim3(grid, ndotp), dim3(kBlock), 0, c->stream, comb_derefs, vals, N,
+                         scratch, from_scratch, pairs, rr, fin, kmap);
+    }, r != nullptr);
   }
   VPIN_HIP_TRY(hipGetLastError());
   if (!fin.fused) return round_finish_launch(c, partials, c->round_split_ncirc, c->round_split_grid, ndotp, grid);
@@ -1081,7 +1000,7 @@ int spark_triple_sums(vpin_ctx* c, const fq* comb_derefs, const fq* vals, size_t
     ProfScope ps(c, VPIN_K_SPARK_BUILD, 1.5 * nh * 32.0 * (double)N);
     hipLaunchKernelGGL(triple_sum_kernel, dim3(grid, nh), dim3(kBlock), 0, c->stream, comb_derefs, vals, N, partials, kmap);
   }
-  hipLaunchKernelGGL(inst_finish_kernel, dim3(nh), dim3(kBlock), 0, c->stream, (const fq*)partials, grid, 0, c->h_spark);
+  hipLaunchKernelGGL(sc_finish_kernel<3>, dim3(nh), dim3(kBlock), 0, c->stream, (const fq*)partials, grid, c->h_spark);  // out[3 * half + k]
   VPIN_HIP_TRY(hipGetLastError());
   return spark_wait(c);
 }
@@ -1103,7 +1022,7 @@ int spark_slice_evals(vpin_ctx* c, const fq* table, size_t len, int nslices, con
     ProfScope ps(c, VPIN_K_SPARK_BUILD, ((double)nslices * 32.0 * (double)len + 32.0 * (double)len) / (double)step);
     hipLaunchKernelGGL(slice_dot3_kernel, dim3(grid, groups), dim3(kBlock), 0, c->stream, table, len, nslices, eq, partials, r0, step);
   }
-  hipLaunchKernelGGL(inst_finish_kernel, dim3(groups), dim3(kBlock), 0, c->stream, (const fq*)partials, grid, 0, c->h_spark);
+  hipLaunchKernelGGL(sc_finish_kernel<3>, dim3(groups), dim3(kBlock), 0, c->stream, (const fq*)partials, grid, c->h_spark);
   VPIN_HIP_TRY(hipGetLastError());
   if ((rc = spark_wait(c))) return rc;
   // group g's three sums sit at h_spark[3g + k] = slice 3g + k: spread them to the h_spark[3 * slice] layout of the callers
@@ -1153,28 +1072,6 @@ __device__ __forceinline__ fq fq_shfl_from(const fq& a, int src) {
   return r;
 }
 
-// sums of e[0..2] over the first `nw` waves of the block; valid in threads 0..2
-__device__ __forceinline__ fq tail_block_sum3(fq* e, int nw) {
-  __shared__ fq sh[kTailBlock / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (wave < nw) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      fq t = e[k];
-      for (int off = 32; off >= 1; off >>= 1) t = fq_add(t, fq_shfl_xor(t, off));
-      if (lane == 0) sh[wave][k] = t;
-    }
-  }
-  __syncthreads();
-  fq t = fq_zero();
-  if (threadIdx.x < 3) {
-    t = sh[0][threadIdx.x];
-    for (int w = 1; w < nw; w++) t = fq_add(t, sh[w][threadIdx.x]);
-  }
-  __syncthreads();
-  return t;
-}
-
 // one workgroup per instance (161 VGPRs)
 __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
   const int inst = (int)blockIdx.x;
@@ -1204,7 +1101,8 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
     const bool bind = j > 0, last = j == a.k - 1;
     const size_t pairs = bind ? len / 4 : len / 2;
     const uint32_t seq = a.seq0 + (uint32_t)(j - a.j0) + 1u;
-    const fq* E = a.pyr + ((((size_t)1) << a.k) - (((size_t)2) << (a.k - (j + 1))));  // pyramid level j + 1
+    const fq* E = a.pyr + pyramid_offset(a.k, j + 1);
+    const FoldR fr{r, nullptr};
     if (a.trace && inst == 0 && threadIdx.x == 0) a.trace[4 * (j - a.j0)] = wall_clock64();
     Acc<4> acc;
     acc.init();
@@ -1237,26 +1135,19 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
       nw = (int)((4 * pairs + 63) / 64);
       lo_off = 4;  // quad layout: e[0] lives in the role-0 lanes, e[1] in the role-1 lanes (reduced over strides 32..4 below)
     } else if (!is_dotp) {
+      LeadNow now;  // a pair or two per lane: every product reduced at once
       for (size_t i = threadIdx.x; i < pairs; i += kTailBlock) {
-        fq p1, d1, p2, d2;
-        if (bind) { fold_pd(A, i, pairs, r, p1, d1); fold_pd(Bt, i, pairs, r, p2, d2); }
-        else { load_pd(A, i, pairs, p1, d1); load_pd(Bt, i, pairs, p2, d2); }
-        acc.lead_bc(p1, d1, p2, d2, fq_load(E + i));
+        if (bind) pair_prod<PD_FOLD, true>(acc, now, A, Bt, E, i, pairs, fr);
+        else pair_prod<PD_LOAD, true>(acc, now, A, Bt, E, i, pairs, fr);
       }
       if (pairs < (size_t)kTailBlock) nw = (int)((pairs + 63) / 64);
     } else {
       // round 0 reads the committed polynomials as they are, round 1 folds them into scratch, later rounds fold scratch in place
       const bool from_src = j <= 1;
-      for (size_t i = threadIdx.x; i < pairs; i += kTailBlock) {
-        fq u[3], p1, d1, p2, d2;
-        if (bind) {
-          fold_pd2(from_src ? src[0] : dst[0], dst[0], i, pairs, r, p1, d1);
-          fold_pd2(from_src ? src[1] : dst[1], dst[1], i, pairs, r, p2, d2);
-        } else { load_pd(src[0], i, pairs, p1, d1); load_pd(src[1], i, pairs, p2, d2); }
-        acc.stage_bc(u, p1, d1, p2, d2);
-        if (bind) fold_pd2(from_src ? src[2] : dst[2], dst[2], i, pairs, r, p1, d1);
-        else load_pd(src[2], i, pairs, p1, d1);
-        acc.stage_a(u, p1, d1);
+      for (size_t i = threadIdx.x; i < pairs; i += kTailBlock) {  // (`from` hoisted out of the loop by hand costs 25 VGPRs)
+        const fq* const from[3] = {from_src ? src[0] : dst[0], from_src ? src[1] : dst[1], from_src ? src[2] : dst[2]};
+        if (bind) pair_dotp<true>(acc, from, dst, i, pairs, fr);
+        else pair_dotp<false>(acc, from, dst, i, pairs, fr);
       }
       if (pairs < (size_t)kTailBlock) nw = (int)((pairs + 63) / 64);
     }
@@ -1278,7 +1169,7 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
         for (int w = 1; w < nw; w++) t = fq_add(t, shq[w][threadIdx.x]);
       }
     } else {
-      t = tail_block_sum3(acc.e, nw);  // its barriers also order this round's folds before the next round's loads
+      t = block_sum<3, kTailBlock>(acc.e, nw);  // its barriers also order this round's folds before the next round's loads
     }
     if ((int)threadIdx.x < (is_dotp ? 3 : 2)) publish_scalar(up + 12 * threadIdx.x, t, seq);  // a product circuit has two sums
     if (last) {

@@ -42,23 +42,8 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void sc_eval_kernel(Tabs<K> tabs
                                                          fq* __restrict__ partials) {
   Acc<K> acc;
   acc.init();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < half; i += (size_t)gridDim.x * kBlock) {
-    if constexpr (K == 4) {
-      fq u[3], p1, d1, p2, d2;
-      load_pd(tabs.t[1], i, half, p1, d1);
-      load_pd(tabs.t[2], i, half, p2, d2);
-      acc.stage_bc(u, p1, d1, p2, d2);
-      load_pd(tabs.t[3], i, half, p1, d1);
-      acc.stage_d(u, p1, d1);
-      load_pd(tabs.t[0], i, half, p1, d1);
-      acc.stage_a(u, p1, d1);
-    } else {
-      fq p[K], d[K];
-#pragma unroll
-      for (int k = 0; k < K; k++) load_pd(tabs.t[k], i, half, p[k], d[k]);
-      acc.add_pair(p, d);
-    }
-  }
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < half; i += (size_t)gridDim.x * kBlock)
+    pair_ktab<K, PD_LOAD>(acc, tabs, i, half, FoldR{});
   block_reduce_store<Acc<K>::NE>(acc.e, partials);
 }
 
@@ -67,25 +52,11 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void sc_eval_kernel(Tabs<K> tabs
 template <int K>
 __global__ __launch_bounds__(kBlock, kMinWaves) void sc_bind_eval_kernel(Tabs<K> tabs, size_t quarter, fq r,
                                                               fq* __restrict__ partials) {
+  const FoldR fr{r, nullptr};
   Acc<K> acc;
   acc.init();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < quarter; i += (size_t)gridDim.x * kBlock) {
-    if constexpr (K == 4) {
-      fq u[3], p1, d1, p2, d2;
-      fold_pd(tabs.t[1], i, quarter, r, p1, d1);
-      fold_pd(tabs.t[2], i, quarter, r, p2, d2);
-      acc.stage_bc(u, p1, d1, p2, d2);
-      fold_pd(tabs.t[3], i, quarter, r, p1, d1);
-      acc.stage_d(u, p1, d1);
-      fold_pd(tabs.t[0], i, quarter, r, p1, d1);
-      acc.stage_a(u, p1, d1);
-    } else {
-      fq p[K], d[K];
-#pragma unroll
-      for (int k = 0; k < K; k++) fold_pd(tabs.t[k], i, quarter, r, p[k], d[k]);
-      acc.add_pair(p, d);
-    }
-  }
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < quarter; i += (size_t)gridDim.x * kBlock)
+    pair_ktab<K, PD_FOLD>(acc, tabs, i, quarter, fr);
   block_reduce_store<Acc<K>::NE>(acc.e, partials);
 }
 
@@ -97,34 +68,16 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void sc_bind_eval_kernel(Tabs<K>
 template <bool BIND, bool LEAD>
 __global__ __launch_bounds__(kBlock, kMinWaves) void sc_cubic3_kernel(Tabs<3> tabs, const fq* __restrict__ E, size_t pairs,
                                                                       fq r, fq_const rc, fq* __restrict__ partials) {
-  __shared__ __attribute__((aligned(16))) uint32_t tt[8][8];
-  if (BIND && LEAD) {
-    if (threadIdx.x < 64) tt[threadIdx.x >> 3][threadIdx.x & 7] = rc.tt[threadIdx.x >> 3][threadIdx.x & 7];
-    __syncthreads();
-  }
+  // the LEAD folds use the launch-wide constant form of r (fq_dev.h fq_mul_const)
+  constexpr PdMode M = !BIND ? PD_LOAD : LEAD ? PD_FOLD_C : PD_FOLD;
+  FoldR fr{r, nullptr};
+  if constexpr (M == PD_FOLD_C) fr.tt = stage_fq_const(rc);
   Acc<4> acc;
   acc.init();
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock) {
-    fq u[3], p1, d1, p2, d2;
-    if (BIND && LEAD) { fold_pd_c(tabs.t[0], i, pairs, tt, p1, d1); fold_pd_c(tabs.t[1], i, pairs, tt, p2, d2); }
-    else if (BIND) { fold_pd(tabs.t[0], i, pairs, r, p1, d1); fold_pd(tabs.t[1], i, pairs, r, p2, d2); }
-    else { load_pd(tabs.t[0], i, pairs, p1, d1); load_pd(tabs.t[1], i, pairs, p2, d2); }
-    if (LEAD) {
-      fq p3, d3;
-      if (BIND) fold_pd_c(tabs.t[2], i, pairs, tt, p3, d3);
-      else load_pd(tabs.t[2], i, pairs, p3, d3);
-      const fq e = fq_load(E + i);
-      acc.lead_bcd(p1, d1, p2, d2, p3, e);  // (the lazily reduced sums of spark.hip's product rounds do not pay here: same-box
-                                            //  A/B 162.3 against 151.9-162.6 us per launch, profiles/r04_ab_lazy.txt)
-      if (!BIND) acc.lead_one(p1, d1, p2, d2, p3, d3, e);
-    } else {
-      acc.stage_bc(u, p1, d1, p2, d2);
-      if (BIND) fold_pd(tabs.t[2], i, pairs, r, p1, d1);
-      else load_pd(tabs.t[2], i, pairs, p1, d1);
-      acc.stage_d(u, p1, d1);
-      acc.stage_e(u, fq_load(E + i));
-    }
-  }
+  // (the lazily reduced sums of spark.hip's product rounds do not pay in the LEAD body here: same-box A/B 162.3 against
+  //  151.9-162.6 us per launch, profiles/r04_ab_lazy.txt)
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kBlock)
+    pair_phase1<M, LEAD>(acc, tabs, E, i, pairs, fr);
   block_reduce_store<3>(acc.e, partials);
 }
 
@@ -134,49 +87,18 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void sc_cubic3_kernel(Tabs<3> ta
 constexpr int kSmallBlock = 512;
 constexpr size_t kSmallPairs = 512;
 
+template <int NE>
+__device__ __forceinline__ void tail_store(const fq* e, fq* __restrict__ out) {
+  const fq s = block_sum<NE, kSmallBlock>(e);
+  if (threadIdx.x < NE) fq_store(&out[threadIdx.x], s);
+}
+
 template <int K, bool BIND>
 __global__ __launch_bounds__(kSmallBlock) void sc_tail_kernel(Tabs<K> tabs, size_t pairs, fq r, fq* __restrict__ out) {
   Acc<K> acc;
   acc.init();
-  const size_t i = threadIdx.x;
-  if (i < pairs) {
-    fq p[K], d[K];
-    if (BIND) {
-      const size_t quarter = pairs, half = 2 * pairs;
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-        fq a0 = fq_load(tabs.t[k] + i), a1 = fq_load(tabs.t[k] + half + i);
-        fq b0 = fq_load(tabs.t[k] + quarter + i), b1 = fq_load(tabs.t[k] + half + quarter + i);
-        p[k] = fq_add(a0, fq_mul(r, fq_sub(a1, a0)));
-        fq hi = fq_add(b0, fq_mul(r, fq_sub(b1, b0)));
-        fq_store(tabs.t[k] + i, p[k]);
-        fq_store(tabs.t[k] + quarter + i, hi);
-        d[k] = fq_sub(hi, p[k]);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-        p[k] = fq_load(tabs.t[k] + i);
-        d[k] = fq_sub(fq_load(tabs.t[k] + pairs + i), p[k]);
-      }
-    }
-    acc.add_pair(p, d);
-  }
-  constexpr int NE = Acc<K>::NE;
-  __shared__ fq sh[kSmallBlock / 64][NE];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NE; k++) {
-    fq s = fq_wave_sum(acc.e[k]);
-    if (lane == 0) sh[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NE) {
-    fq s = sh[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kSmallBlock / 64; w++) s = fq_add(s, sh[w][threadIdx.x]);
-    fq_store(&out[threadIdx.x], s);
-  }
+  if (threadIdx.x < pairs) pair_ktab<K, BIND ? PD_FOLD : PD_LOAD>(acc, tabs, threadIdx.x, pairs, FoldR{r, nullptr});
+  tail_store<Acc<K>::NE>(acc.e, out);
 }
 
 template <bool BIND, bool LEAD>
@@ -184,40 +106,8 @@ __global__ __launch_bounds__(kSmallBlock) void sc_tail3_kernel(Tabs<3> tabs, con
                                                                fq* __restrict__ out) {
   Acc<4> acc;
   acc.init();
-  const size_t i = threadIdx.x;
-  if (i < pairs) {
-    fq u[3], p1, d1, p2, d2;
-    if (BIND) { fold_pd(tabs.t[0], i, pairs, r, p1, d1); fold_pd(tabs.t[1], i, pairs, r, p2, d2); }
-    else { load_pd(tabs.t[0], i, pairs, p1, d1); load_pd(tabs.t[1], i, pairs, p2, d2); }
-    if (LEAD) {
-      fq p3, d3;
-      if (BIND) fold_pd(tabs.t[2], i, pairs, r, p3, d3);
-      else load_pd(tabs.t[2], i, pairs, p3, d3);
-      const fq e = fq_load(E + i);
-      acc.lead_bcd(p1, d1, p2, d2, p3, e);
-      if (!BIND) acc.lead_one(p1, d1, p2, d2, p3, d3, e);
-    } else {
-      acc.stage_bc(u, p1, d1, p2, d2);
-      if (BIND) fold_pd(tabs.t[2], i, pairs, r, p1, d1);
-      else load_pd(tabs.t[2], i, pairs, p1, d1);
-      acc.stage_d(u, p1, d1);
-      acc.stage_e(u, fq_load(E + i));
-    }
-  }
-  __shared__ fq sh[kSmallBlock / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    fq s = fq_wave_sum(acc.e[k]);
-    if (lane == 0) sh[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    fq s = sh[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kSmallBlock / 64; w++) s = fq_add(s, sh[w][threadIdx.x]);
-    fq_store(&out[threadIdx.x], s);
-  }
+  if (threadIdx.x < pairs) pair_phase1<BIND ? PD_FOLD : PD_LOAD, LEAD>(acc, tabs, E, threadIdx.x, pairs, FoldR{r, nullptr});
+  tail_store<3>(acc.e, out);
 }
 
 // suffix-eq pyramid step: level k from level k+1 (m elements): dst[i] = (1-tau_k)*src[i], dst[m+i] = tau_k*src[i]
@@ -539,9 +429,6 @@ int sc_round_launch(vpin_ctx* c, int K, vpin_table* const* tabs, const uint8_t* 
 }
 int sc_round_wait(vpin_ctx* c, int K, uint8_t* out) { return fetch(c, K == 4 ? 3 : 2, out); }
 
-// level k (k = 1..ell) of the suffix pyramid inside one table of 2^ell elements
-static inline size_t pyramid_offset(int ell, int k) { return ((size_t)1 << ell) - ((size_t)2 << (ell - k)); }
-
 // Phase-1 round on (Az,Bz,Cz) + the suffix table of level `level` (= round index + 1); r == nullptr
 // evaluates the tables as they are, otherwise binds them with r first.  Results: the three UNSCALED
 // sums  sum_i E[i]*(B_x C_x - D_x)[i]  for x = 0, 2, 3; with `lead`: the sum at x = 0, the x^2 coefficient
@@ -563,20 +450,20 @@ int sc_cubic3_launch(vpin_ctx* c, vpin_table* const* t, const vpin_table* pyrami
   if (pairs <= kSmallPairs) {
     {
       ProfScope ps(c, VPIN_K_SC_TAIL, bytes);
-#define VPIN_T3(B_, L_) hipLaunchKernelGGL((sc_tail3_kernel<B_, L_>), dim3(1), dim3(kSmallBlock), 0, c->stream, tabs, E, pairs, rr, c->h_out)
-      if (r) { if (lead) VPIN_T3(true, true); else VPIN_T3(true, false); }
-      else { if (lead) VPIN_T3(false, true); else VPIN_T3(false, false); }
-#undef VPIN_T3
+      dispatch_bools([&](auto B, auto L) {
+        hipLaunchKernelGGL((sc_tail3_kernel<decltype(B)::value, decltype(L)::value>), dim3(1), dim3(kSmallBlock), 0, c->stream, tabs, E,
+                           pairs, rr, c->h_out);
+      }, r != nullptr, lead);
     }
     VPIN_HIP_TRY(hipGetLastError());
   } else {
     int grid = grid_for(pairs);
     {
       ProfScope ps(c, r ? VPIN_K_SC_CUBIC_FUSED : VPIN_K_SC_CUBIC, bytes);
-#define VPIN_C3(B_, L_) hipLaunchKernelGGL((sc_cubic3_kernel<B_, L_>), dim3(grid), dim3(kBlock), 0, c->stream, tabs, E, pairs, rr, rconst, c->d_partials)
-      if (r) { if (lead) VPIN_C3(true, true); else VPIN_C3(true, false); }
-      else { if (lead) VPIN_C3(false, true); else VPIN_C3(false, false); }
-#undef VPIN_C3
+      dispatch_bools([&](auto B, auto L) {
+        hipLaunchKernelGGL((sc_cubic3_kernel<decltype(B)::value, decltype(L)::value>), dim3(grid), dim3(kBlock), 0, c->stream, tabs, E,
+                           pairs, rr, rconst, c->d_partials);
+      }, r != nullptr, lead);
     }
     VPIN_HIP_TRY(hipGetLastError());
     rc = finish_launch<3>(c, grid);
