@@ -364,6 +364,7 @@ static int ctx_create(int device, int priority, const uint32_t* cu_mask, uint32_
     e = hipExtStreamCreateWithCUMask(&c->stream, n_words, cu_mask);
     c->num_cus = enabled;
     c->cu_masked = true;
+    c->slot_blocks = true;  // its CUs may be another context's too: one-slot workgroups (sc_dev.h kSlotBlock)
   } else {
     e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio);
   }

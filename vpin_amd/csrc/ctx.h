@@ -55,6 +55,10 @@ struct vpin_ctx {
   hipStream_t stream = nullptr;
   int num_cus = 256;        // compute units the stream may use (the enabled ones of a CU-masked context)
   bool cu_masked = false;   // created by vpin_ctx_create_cumask, or on the second stream of vpin_ctx_set_cumask_after_phase1
+  // created by vpin_ctx_create_cumask: the context's CUs may be shared with contexts that commit rows three workgroups to a
+  // CU, so every kernel a proof launches fits the slot ONE retiring row workgroup frees (slot_tb below).  Not set by the
+  // second stream of vpin_ctx_set_cumask_after_phase1, whose CUs are the context's own.
+  bool slot_blocks = false;
   // vpin_ctx_set_cumask_after_phase1: a second, CU-masked stream a proof moves to after its phase-1 sum-check (capi.hip
   // ctx_enter_alt / ctx_leave_alt; `stream` is always the stream in use)
   hipStream_t stream_main = nullptr, stream_alt = nullptr;

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -541,10 +542,15 @@ struct TableGuard {
 #endif
 
 // prover.cpp
+// evals_from: where inst.evaluate(rx, ry) comes from instead of vpin_r1cs_evaluate -- ie[m] = A, B, C(rx, ry).  A whole SNARK
+// on one GPU passes the SPARK prover's derefs pass, which needs the same gathers anyway (spark.cpp spark_inst_evals).  The claims
+// go to the transcript where they always did, with the same values; the slot inst_evaluate times whichever ran.
+using InstEvalsFn = std::function<int(const Fq* rx, size_t nrx, const Fq* ry, size_t nry, Fq ie[3])>;
 int sat_prove_core(vpin_ctx* c, const vpin_r1cs_dev* dinst, size_t nv, size_t ncons, size_t ni,
                    const vpin_table* d_para, const vpin_table* d_input, const vpin_table* d_vars, const uint8_t* inputs,
                    const uint8_t seed_commit64[64], const uint8_t seed_proof64[64], uint8_t* proof_out, size_t proof_cap,
                    size_t* proof_len, uint8_t* comm_para_out, uint8_t* comm_input_out, uint8_t inst_evals_out[96],
-                   uint8_t* rx_out, uint8_t* ry_out, vpin_host::Transcript* tr_out, vpin_host::Transcript* tape_out);
+                   uint8_t* rx_out, uint8_t* ry_out, vpin_host::Transcript* tr_out, vpin_host::Transcript* tape_out,
+                   const InstEvalsFn* evals_from = nullptr);
 
 }  // namespace vpin_prover

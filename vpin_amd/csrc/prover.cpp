@@ -539,7 +539,8 @@ int sat_prove_core(vpin_ctx* c, const vpin_r1cs_dev* dinst, size_t nv, size_t nc
                    const vpin_table* d_para, const vpin_table* d_input, const vpin_table* d_vars, const uint8_t* inputs,
                    const uint8_t seed_commit64[64], const uint8_t seed_proof64[64], uint8_t* proof_out, size_t proof_cap,
                    size_t* proof_len, uint8_t* comm_para_out, uint8_t* comm_input_out, uint8_t inst_evals_out[96],
-                   uint8_t* rx_out, uint8_t* ry_out, vpin_host::Transcript* tr_out, vpin_host::Transcript* tape_out) {
+                   uint8_t* rx_out, uint8_t* ry_out, vpin_host::Transcript* tr_out, vpin_host::Transcript* tape_out,
+                   const InstEvalsFn* evals_from) {
   auto t_begin = Clock::now();
   memset(g_timings, 0, sizeof g_timings);
   (void)hipSetDevice(c->device);
@@ -733,7 +734,9 @@ int sat_prove_core(vpin_ctx* c, const vpin_r1cs_dev* dinst, size_t nv, size_t nc
   // ---- inst.evaluate(rx, ry) and the claims my_lib_prove appends (commit_test.rs:100-109) ----
   t0 = Clock::now();
   Fq ie[3];
-  {
+  if (evals_from) {
+    if ((rc = (*evals_from)(rx.data(), rx.size(), ry.data(), ry.size(), ie))) return rc;
+  } else {
     vpin_table* d_eq_ry = nullptr;
     if ((rc = vpin_eq_table(c, B(ry.data()), nry, &d_eq_ry))) return rc;
     tg.add(d_eq_ry);

@@ -20,6 +20,19 @@ inline int max_blocks() {
   return n;
 }
 
+// Kernels written for one large workgroup (512 or 1024 threads) take their block size as a template parameter TB: the full
+// size, or kSlotBlock on a context whose CUs other contexts fill with row-commitment workgroups (vpin_ctx::slot_blocks).
+// Such a workgroup is placed as soon as ONE row workgroup retires: at most 256 threads, 176 VGPRs, 60 KB of LDS (DESIGN.md
+// section 4).  kMinWaves caps the registers of the 256-thread forms at 168; the full forms keep the allocator's own bound.
+constexpr int kSlotBlock = 256;
+constexpr int tb_min_waves(int tb) { return tb <= kSlotBlock ? kMinWaves : 1; }
+// f(std::integral_constant<int, TB>) with the context's TB for a kernel whose full size is FULL
+template <int FULL, class F>
+inline void dispatch_block(const vpin_ctx* c, F&& f) {
+  if (c->slot_blocks) f(std::integral_constant<int, kSlotBlock>{});
+  else f(std::integral_constant<int, FULL>{});
+}
+
 // level k (k = 1..ell) of the suffix pyramid inside one table of 2^ell elements
 __host__ __device__ inline size_t pyramid_offset(int ell, int k) { return ((size_t)1 << ell) - ((size_t)2 << (ell - k)); }
 

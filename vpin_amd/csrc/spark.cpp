@@ -756,6 +756,10 @@ struct SparkProof {
   std::vector<Fq> rand_ops, rand_mem;
   Fq ev_derefs[6], ev_ops[15], ev_mem[2];
   DpLog pe_derefs, pe_ops, pe_mem;
+  // a whole SNARK on one GPU (spark_inst_evals): the derefs pass and the six dot-product sums ran before the sat proof's last
+  // transcript appends, which need their sums; stage_derefs and dotp_claims take them from here
+  bool have_derefs = false, have_sums = false;
+  Fq sums6[6];
 
   SparkProof(vpin_ctx* c_, const vpin_spark_decomm* d_, const std::vector<Fq>& rx_, const std::vector<Fq>& ry_, const Fq* evals_,
              Transcript& tr_, Transcript& tape_)
@@ -781,15 +785,15 @@ static int split_plan(SparkProof& S) {
   return VPIN_OK;
 }
 
-// Derefs (sparse_mlpoly.rs:525-531,56-71) and their commitment
-static int stage_derefs(SparkProof& S) {
+// The two memories and the derefs polynomial (sparse_mlpoly.rs:525-531,56-71): a function of rx, ry and the circuit alone, not
+// of the transcript
+static int derefs_tables(SparkProof& S) {
   vpin_ctx* c = S.c;
   const vpin_spark_decomm* d = S.d;
   const DistPlan* dz = S.dz;
   const PcGens* g_derefs = S.g_derefs;
   const size_t N = S.N;
   int rc;
-  S.tr.append_protocol_name("Sparse polynomial evaluation proof");
   // equalize (sparse_mlpoly.rs:1448-1465) + the two memories eq(rx_ext, .), eq(ry_ext, .)
   const size_t nm = std::max(d->nx, d->ny);
   std::vector<Fq> rx_ext(nm, Fq::zero()), ry_ext(nm, Fq::zero());
@@ -817,6 +821,21 @@ static int stage_derefs(SparkProof& S) {
     if ((rc = vpin::spark_gather_derefs(c, d, S.leaves, mem_rx, mem_ry, S.comb->d))) return rc;
     S.derefs = S.comb->d; S.vals = d->vals;
   }
+  S.have_derefs = true;
+  return VPIN_OK;
+}
+
+// Derefs and their commitment
+static int stage_derefs(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const vpin_spark_decomm* d = S.d;
+  const DistPlan* dz = S.dz;
+  const PcGens* g_derefs = S.g_derefs;
+  const size_t N = S.N;
+  int rc;
+  S.tr.append_protocol_name("Sparse polynomial evaluation proof");
+  if (!S.have_derefs && (rc = derefs_tables(S))) return rc;
+  const vpin::fq* mem_ry = S.mem_ry->d;
   if ((rc = vpin::comm_mark(c, "derefs_gather"))) return rc;
   std::vector<CG>& comm_derefs = S.comm_derefs;
   // the entries of each matrix's hot column hold one scalar, E_ry[hot]: one addition each instead of a table walk
@@ -975,9 +994,13 @@ static int dotp_claims(SparkProof& S) {
   // up.  Split by whole circuits: every rank sums the halves it will prove, one scalar per half is exchanged.
   const std::vector<int>* hv = S.by_circuit() ? &dz->dotp_of[dz->rank] : nullptr;
   const size_t nh = hv ? hv->size() : 6;
-  if (nh && (rc = vpin::spark_triple_sums(c, S.derefs, S.vals, S.Nf, hv ? hv->data() : nullptr, (int)nh))) return rc;
   Fq mine6[6] = {};
-  for (size_t i = 0; i < nh; i++) mine6[hv ? (*hv)[i] : i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
+  if (S.have_sums) {  // one GPU, all six: taken by spark_inst_evals
+    std::copy(S.sums6, S.sums6 + 6, mine6);
+  } else {
+    if (nh && (rc = vpin::spark_triple_sums(c, S.derefs, S.vals, S.Nf, hv ? hv->data() : nullptr, (int)nh))) return rc;
+    for (size_t i = 0; i < nh; i++) mine6[hv ? (*hv)[i] : i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
+  }
   if (S.st) rc = dist_sum(c, *dz, mine6, 6, S.dotp.claims, "triple_sums");
   else if (dz) rc = dist_pick(c, *dz, mine6, 6, dz->owner_dotp, S.dotp.claims, "triple_sums");
   else std::copy(mine6, mine6 + 6, S.dotp.claims);
@@ -1192,20 +1215,43 @@ static void write_proof(const SparkProof& S, Writer& w) {
 }
 
 // SparseMatPolyEvalProof::prove (sparse_mlpoly.rs:1466-1533) -> bincode(R1CSEvalProof) appended to w
-static int spark_prove(vpin_ctx* c, const vpin_spark_decomm* d, const std::vector<Fq>& rx, const std::vector<Fq>& ry,
-                       const Fq evals[3], Transcript& tr, Transcript& tape, Writer& w) {
-  if (d->N < 4 || d->M < 4 || rx.size() != d->nx || ry.size() != d->ny) return VPIN_ESHAPE;
+// spark_begin: the shapes, the generator views and the split; spark_finish: the stages and the proof's bytes.  A whole SNARK on
+// one GPU calls spark_inst_evals between the two, from inside its sat proof.
+static int spark_begin(SparkProof& S) {
+  vpin_ctx* c = S.c;
+  const vpin_spark_decomm* d = S.d;
+  if (d->N < 4 || d->M < 4 || S.rx.size() != d->nx || S.ry.size() != d->ny) return VPIN_ESHAPE;
   int rc;
-  SparkProof S(c, d, rx, ry, evals, tr, tape);
   const Shape sh{d->nx, d->ny, S.N, S.M, S.lgN + 4, std::max(d->nx, d->ny) + 1, S.lgN + 3};
   // the longest stream first: a later, longer request would rebuild the table and drop earlier views
   if ((rc = get_view(c, std::max(sh.v_ops, sh.v_mem), &S.g_ops)) || (rc = get_view(c, sh.v_ops, &S.g_ops)) ||
       (rc = get_view(c, sh.v_mem, &S.g_mem)) || (rc = get_view(c, sh.v_derefs, &S.g_derefs)))
     return rc;
+  return split_plan(S);
+}
+
+// inst.evaluate(rx, ry) = (A, B, C)(rx, ry) from the SPARK prover's own first pass: M(rx, ry) = sum_k val_k eq(rx, row_k)
+// eq(ry, col_k) is the sum of the matrix's two dot-product halves over the derefs polynomial.  The tables and the six sums stay in
+// S for stage_derefs and dotp_claims (which still checks left + right against these evaluations).
+static int spark_inst_evals(SparkProof& S, Fq ie[3]) {
+  vpin_ctx* c = S.c;
+  int rc;
+  if (S.dz) return VPIN_EINVAL;  // one GPU only: a split proof sums per rank, after its gather
+  if ((rc = derefs_tables(S))) return rc;
+  if ((rc = vpin::spark_triple_sums(c, S.derefs, S.vals, S.Nf, nullptr, 6))) return rc;
+  for (int i = 0; i < 6; i++) S.sums6[i] = reinterpret_cast<const Fq*>(c->h_spark)[3 * i];
+  S.have_sums = true;
+  for (int m = 0; m < 3; m++) ie[m] = S.sums6[2 * m] + S.sums6[2 * m + 1];
+  return VPIN_OK;
+}
+
+static int spark_finish(SparkProof& S, Writer& w) {
+  vpin_ctx* c = S.c;
+  int rc;
   // one stage per timing slot of vpin_spark_last_timings
   auto t0 = Clock::now();
   auto lap = [&](int slot) { g_spark_timings[slot] = secs(t0, Clock::now()); t0 = Clock::now(); };
-  if ((rc = split_plan(S)) || (rc = stage_derefs(S))) return rc;
+  if ((rc = stage_derefs(S))) return rc;
   lap(1);
   if (c->progress_flag) *c->progress_flag = 2;  // the proof's largest MSM is done (a scheduler may let other streams in now)
   if ((rc = stage_network(S))) return rc;
@@ -1500,17 +1546,30 @@ int vpin_snark_prove_resident(vpin_ctx* c, const vpin_r1cs_dev* dinst, const vpi
   uint8_t ie[96];
   std::vector<Fq> rx(log2z(ncons)), ry(log2z(2 * nv));
   size_t sat_len = 0;
+  Fq evals[3];
+  // One GPU: the sat proof takes inst.evaluate(rx, ry) from the SPARK prover's derefs pass (spark_inst_evals) instead of three
+  // gather passes of its own over the matrices.  A proof split over several GPUs keeps vpin_r1cs_evaluate.
+  const bool fused = !(c->comm && c->comm->world > 1);
+  SparkProof S(c, decomm, rx, ry, evals, tr, tape);
+  const vpin_prover::InstEvalsFn from_derefs = [&](const Fq* rx_, size_t nrx, const Fq* ry_, size_t nry, Fq out[3]) -> int {
+    if (nrx != rx.size() || nry != ry.size()) return VPIN_ESHAPE;
+    std::copy(rx_, rx_ + nrx, rx.begin());
+    std::copy(ry_, ry_ + nry, ry.begin());
+    int rc_ = spark_begin(S);
+    return rc_ ? rc_ : spark_inst_evals(S, out);
+  };
   // collective over c->comm: a failure of this rank alone (memory, a HIP error) fails the peers' next wait (comm_leave)
   int rc = sat_prove_core(c, dinst, nv, ncons, ni, vars_para, vars_input, vars, inputs, seed_commit64, seed_proof64, proof_out,
-                          proof_cap, &sat_len, comm_para_out, comm_input_out, ie, B(rx.data()), B(ry.data()), &tr, &tape);
+                          proof_cap, &sat_len, comm_para_out, comm_input_out, ie, B(rx.data()), B(ry.data()), &tr, &tape,
+                          fused ? &from_derefs : nullptr);
   if (rc) return vpin::comm_leave(c->comm, rc);
   if (c->progress_flag) *c->progress_flag = 1;
   g_spark_timings[5] = secs(t0, Clock::now());
   Writer w;
   w.bytes(ie, 96);  // SNARK.inst_evals (lib.rs:334-338)
-  Fq evals[3];
   memcpy(evals, ie, 96);
-  if ((rc = spark_prove(c, decomm, rx, ry, evals, tr, tape, w))) return vpin::comm_leave(c->comm, rc);
+  if (!fused) rc = spark_begin(S);
+  if (rc || (rc = spark_finish(S, w))) return vpin::comm_leave(c->comm, rc);
   if (sat_len + w.buf.size() > proof_cap) return VPIN_ESHAPE;
   memcpy(proof_out + sat_len, w.buf.data(), w.buf.size());
   *proof_len = sat_len + w.buf.size();

@@ -235,14 +235,20 @@ __global__ __launch_bounds__(kBlock) void tree_level3_kernel(fq* __restrict__ fo
 }
 
 // the top of every tree in one workgroup: levels from `h0` outputs down to 1 (h0 <= 1024)
+// TB threads: kTopBlock, an output per thread, or kSlotBlock (sc_dev.h), up to four per thread on the widest level
 constexpr int kTopBlock = 1024;
-__global__ __launch_bounds__(kTopBlock) void tree_top_kernel(fq* __restrict__ forest, size_t stride, size_t n2, size_t h0) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void tree_top_kernel(fq* __restrict__ forest, size_t stride, size_t n2, size_t h0) {
   fq* t = forest + (size_t)blockIdx.x * stride;
   for (size_t h = h0; h >= 1; h >>= 1) {
     // level with h entries is built from the level with 2h entries
     const fq* src = t + (n2 - 4 * h);
     fq* dst = t + (n2 - 2 * h);
-    if (threadIdx.x < h) fq_store(dst + threadIdx.x, fq_mul(fq_load(src + threadIdx.x), fq_load(src + h + threadIdx.x)));
+    if constexpr (TB >= kTopBlock) {
+      if (threadIdx.x < h) fq_store(dst + threadIdx.x, fq_mul(fq_load(src + threadIdx.x), fq_load(src + h + threadIdx.x)));
+    } else {
+      for (size_t i = threadIdx.x; i < h; i += TB) fq_store(dst + i, fq_mul(fq_load(src + i), fq_load(src + h + i)));
+    }
     __syncthreads();
   }
 }
@@ -675,7 +681,10 @@ static int build_levels(vpin_ctx* c, SparkForest* f) {
     h >>= 1;
     l++;
   }
-  if (h >= 1) hipLaunchKernelGGL(tree_top_kernel, dim3(f->ncirc), dim3(kTopBlock), 0, c->stream, f->base, f->stride(), n2, h);
+  if (h >= 1)
+    dispatch_block<kTopBlock>(c, [&](auto TB) {
+      hipLaunchKernelGGL(tree_top_kernel<TB()>, dim3(f->ncirc), dim3(TB()), 0, c->stream, f->base, f->stride(), n2, h);
+    });
   VPIN_HIP_TRY(hipGetLastError());
   return VPIN_OK;
 }
@@ -1060,10 +1069,11 @@ struct TailArgs {
   unsigned long long* trace;  // VPIN_TAIL_TRACE: pinned, per round {start, published, reply seen, -} in 100 MHz ticks (instance 0)
 };
 
-constexpr int kTailBlock = 512;
+constexpr int kTailBlock = 512;              // threads of a tail workgroup: this, or kSlotBlock (sc_dev.h) -- the kernel's TB
 constexpr int kTailUpChunks = 32;             // 16-byte pieces per instance: 9 for the sums, 18 for the final entries
 constexpr long kTailSpinLimit = 4000000;      // ~10 s of polling: a lost host ends the kernel instead of hanging the GPU
-constexpr size_t kTailQuadPairs = kTailBlock / 4;  // rounds with at most this many pairs run four lanes per pair
+template <int TB>
+constexpr size_t kTailQuadPairs = TB / 4;         // rounds with at most this many pairs run four lanes per pair
 
 __device__ __forceinline__ fq fq_shfl_from(const fq& a, int src) {
   fq r;
@@ -1073,7 +1083,8 @@ __device__ __forceinline__ fq fq_shfl_from(const fq& a, int src) {
 }
 
 // one workgroup per instance (161 VGPRs)
-__global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void spark_tail_kernel(TailArgs a) {
   const int inst = (int)blockIdx.x;
   const bool is_dotp = inst >= a.ncirc;
   __shared__ fq sh_r;
@@ -1106,9 +1117,9 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
     if (a.trace && inst == 0 && threadIdx.x == 0) a.trace[4 * (j - a.j0)] = wall_clock64();
     Acc<4> acc;
     acc.init();
-    int nw = kTailBlock / 64, lo_off = 1;
+    int nw = TB / 64, lo_off = 1;
     fq mine = fq_zero();  // quad mode: this lane's folded entry (A[i], A[q+i], B[i], B[q+i] by role)
-    if (!is_dotp && pairs <= kTailQuadPairs) {
+    if (!is_dotp && pairs <= kTailQuadPairs<TB>) {
       // Four lanes per pair: each folds ONE of the pair's four entries (a lone wave issues one modular product in
       // ~0.7 us whatever its lanes do, so eight products per lane are eight times that), then lane 0 of the quad
       // forms E*A_0*B_0 and lane 1 E*dA*dB.
@@ -1136,27 +1147,27 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
       lo_off = 4;  // quad layout: e[0] lives in the role-0 lanes, e[1] in the role-1 lanes (reduced over strides 32..4 below)
     } else if (!is_dotp) {
       LeadNow now;  // a pair or two per lane: every product reduced at once
-      for (size_t i = threadIdx.x; i < pairs; i += kTailBlock) {
+      for (size_t i = threadIdx.x; i < pairs; i += TB) {
         if (bind) pair_prod<PD_FOLD, true>(acc, now, A, Bt, E, i, pairs, fr);
         else pair_prod<PD_LOAD, true>(acc, now, A, Bt, E, i, pairs, fr);
       }
-      if (pairs < (size_t)kTailBlock) nw = (int)((pairs + 63) / 64);
+      if (pairs < (size_t)TB) nw = (int)((pairs + 63) / 64);
     } else {
       // round 0 reads the committed polynomials as they are, round 1 folds them into scratch, later rounds fold scratch in place
       const bool from_src = j <= 1;
-      for (size_t i = threadIdx.x; i < pairs; i += kTailBlock) {  // (`from` hoisted out of the loop by hand costs 25 VGPRs)
+      for (size_t i = threadIdx.x; i < pairs; i += TB) {  // (`from` hoisted out of the loop by hand costs 25 VGPRs)
         const fq* const from[3] = {from_src ? src[0] : dst[0], from_src ? src[1] : dst[1], from_src ? src[2] : dst[2]};
         if (bind) pair_dotp<true>(acc, from, dst, i, pairs, fr);
         else pair_dotp<false>(acc, from, dst, i, pairs, fr);
       }
-      if (pairs < (size_t)kTailBlock) nw = (int)((pairs + 63) / 64);
+      if (pairs < (size_t)TB) nw = (int)((pairs + 63) / 64);
     }
     if (bind) len /= 2;
     fq t;
     if (lo_off == 4) {
       // quad layout: every lane reduces the sum of its own role over the lanes of that role (strides 32..4)
       fq v = (threadIdx.x & 1) ? acc.e[1] : acc.e[0];
-      __shared__ fq shq[kTailBlock / 64][2];
+      __shared__ fq shq[TB / 64][2];
       const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
       if (wave < nw) {
         for (int off = 32; off >= 4; off >>= 1) v = fq_add(v, fq_shfl_xor(v, off));
@@ -1169,7 +1180,7 @@ __global__ __launch_bounds__(kTailBlock) void spark_tail_kernel(TailArgs a) {
         for (int w = 1; w < nw; w++) t = fq_add(t, shq[w][threadIdx.x]);
       }
     } else {
-      t = block_sum<3, kTailBlock>(acc.e, nw);  // its barriers also order this round's folds before the next round's loads
+      t = block_sum<3, TB>(acc.e, nw);  // its barriers also order this round's folds before the next round's loads
     }
     if ((int)threadIdx.x < (is_dotp ? 3 : 2)) publish_scalar(up + 12 * threadIdx.x, t, seq);  // a product circuit has two sums
     if (last) {
@@ -1257,7 +1268,9 @@ int spark_tail_launch(vpin_ctx* c, const SparkForest* f, int level, int k, int j
   c->tail_rounds = k - j0;
   {
     ProfScope ps(c, VPIN_K_SPARK_TAIL, 0.0);
-    hipLaunchKernelGGL(spark_tail_kernel, dim3((unsigned)ninst), dim3(kTailBlock), 0, c->stream, a);
+    dispatch_block<kTailBlock>(c, [&](auto TB) {
+      hipLaunchKernelGGL(spark_tail_kernel<TB()>, dim3((unsigned)ninst), dim3(TB()), 0, c->stream, a);
+    });
   }
   if (hipGetLastError() != hipSuccess) { c->tail_rounds = 0; return VPIN_EHIP; }
   return VPIN_OK;

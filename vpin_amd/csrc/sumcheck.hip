@@ -84,30 +84,40 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void sc_cubic3_kernel(Tabs<3> ta
 // Tail rounds (tables of at most kSmallPairs pairs): one workgroup does the fold, the evaluation
 // and the whole reduction, and writes the 2-3 scalars straight to the pinned result buffer -- no
 // partials, no finisher launch.  These rounds are launch-latency bound, not bandwidth bound.
+// TB threads: kSmallBlock, a pair per thread, or kSlotBlock (sc_dev.h), up to two pairs per thread.
 constexpr int kSmallBlock = 512;
 constexpr size_t kSmallPairs = 512;
 
-template <int NE>
+template <int NE, int TB>
 __device__ __forceinline__ void tail_store(const fq* e, fq* __restrict__ out) {
-  const fq s = block_sum<NE, kSmallBlock>(e);
+  const fq s = block_sum<NE, TB>(e);
   if (threadIdx.x < NE) fq_store(&out[threadIdx.x], s);
 }
 
-template <int K, bool BIND>
-__global__ __launch_bounds__(kSmallBlock) void sc_tail_kernel(Tabs<K> tabs, size_t pairs, fq r, fq* __restrict__ out) {
+template <int K, bool BIND, int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void sc_tail_kernel(Tabs<K> tabs, size_t pairs, fq r, fq* __restrict__ out) {
   Acc<K> acc;
   acc.init();
-  if (threadIdx.x < pairs) pair_ktab<K, BIND ? PD_FOLD : PD_LOAD>(acc, tabs, threadIdx.x, pairs, FoldR{r, nullptr});
-  tail_store<Acc<K>::NE>(acc.e, out);
+  // (a fold touches entries i, i + pairs, i + 2 pairs, i + 3 pairs of its own pair index i alone: no order between pairs)
+  if constexpr ((size_t)TB >= kSmallPairs) {
+    if (threadIdx.x < pairs) pair_ktab<K, BIND ? PD_FOLD : PD_LOAD>(acc, tabs, threadIdx.x, pairs, FoldR{r, nullptr});
+  } else {
+    for (size_t i = threadIdx.x; i < pairs; i += TB) pair_ktab<K, BIND ? PD_FOLD : PD_LOAD>(acc, tabs, i, pairs, FoldR{r, nullptr});
+  }
+  tail_store<Acc<K>::NE, TB>(acc.e, out);
 }
 
-template <bool BIND, bool LEAD>
-__global__ __launch_bounds__(kSmallBlock) void sc_tail3_kernel(Tabs<3> tabs, const fq* __restrict__ E, size_t pairs, fq r,
-                                                               fq* __restrict__ out) {
+template <bool BIND, bool LEAD, int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void sc_tail3_kernel(Tabs<3> tabs, const fq* __restrict__ E, size_t pairs, fq r,
+                                                                        fq* __restrict__ out) {
   Acc<4> acc;
   acc.init();
-  if (threadIdx.x < pairs) pair_phase1<BIND ? PD_FOLD : PD_LOAD, LEAD>(acc, tabs, E, threadIdx.x, pairs, FoldR{r, nullptr});
-  tail_store<3>(acc.e, out);
+  if constexpr ((size_t)TB >= kSmallPairs) {
+    if (threadIdx.x < pairs) pair_phase1<BIND ? PD_FOLD : PD_LOAD, LEAD>(acc, tabs, E, threadIdx.x, pairs, FoldR{r, nullptr});
+  } else {
+    for (size_t i = threadIdx.x; i < pairs; i += TB) pair_phase1<BIND ? PD_FOLD : PD_LOAD, LEAD>(acc, tabs, E, i, pairs, FoldR{r, nullptr});
+  }
+  tail_store<3, TB>(acc.e, out);
 }
 
 // suffix-eq pyramid step: level k from level k+1 (m elements): dst[i] = (1-tau_k)*src[i], dst[m+i] = tau_k*src[i]
@@ -122,9 +132,12 @@ __global__ __launch_bounds__(kBlock) void eq_pyramid_step_kernel(const fq* __res
 }
 
 // The small end of the pyramid in one workgroup: level ell (the single 1) down to level k_lo, every level
-// of at most 512 elements.  taus.t[k - k_lo] = tau_k.
+// of at most 512 elements.  taus.t[k - k_lo] = tau_k.  A level is written from the m <= 256 entries of the level above it,
+// one per thread: TB = 256 threads do the same work as 512.
 struct TauPack { fq t[10]; };
-__global__ __launch_bounds__(512) void eq_pyramid_top_kernel(fq* __restrict__ base, int ell, int k_lo, TauPack taus) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void eq_pyramid_top_kernel(fq* __restrict__ base, int ell, int k_lo, TauPack taus) {
+  static_assert(TB >= 256, "a thread per entry of the widest source level");
   const size_t n = (size_t)1 << ell;
   if (threadIdx.x == 0) fq_store(base + (n - 2), fq_one());  // level ell
   __syncthreads();
@@ -181,8 +194,11 @@ __global__ __launch_bounds__(kBlock) void eq_step_kernel(const fq* __restrict__ 
 
 // The first k0 <= 9 doubling steps of EqPolynomial::evals in one workgroup (two LDS buffers of 512 elements), so a
 // table of 2^ell entries costs ell - k0 + 1 launches instead of ell: out[0 .. 2^k0) = eq(r_0..r_{k0-1}, .)
+// (a step reads prev <= 256 entries, one per thread; only the copy-out has 512, two per thread of a TB = 256 block)
 struct EqHead { fq r[9]; };
-__global__ __launch_bounds__(512) void eq_head_kernel(fq* __restrict__ out, int k0, EqHead rs) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void eq_head_kernel(fq* __restrict__ out, int k0, EqHead rs) {
+  static_assert(TB >= 256, "a thread per entry of the widest doubling step");
   __shared__ fq buf[2][512];
   if (threadIdx.x == 0) buf[0][0] = fq_one();
   __syncthreads();
@@ -198,7 +214,9 @@ __global__ __launch_bounds__(512) void eq_head_kernel(fq* __restrict__ out, int 
     cur ^= 1;
     __syncthreads();
   }
-  if (threadIdx.x < ((size_t)1 << k0)) fq_store(out + threadIdx.x, buf[cur][threadIdx.x]);
+#pragma unroll
+  for (int i = threadIdx.x; i < 512; i += TB)
+    if (i < (1 << k0)) fq_store(out + i, buf[cur][i]);
 }
 
 // ---- one-launch eq tables -----------------------------------------------------------------------------------------
@@ -231,8 +249,11 @@ __device__ __forceinline__ int eq_lo_build_lsb(fq (*buf)[kEqChunk], const TauAll
 // EqPolynomial::evals (dense_mlpoly.rs:78-94) of ell >= 10 variables in one launch.  A workgroup writes up to 32
 // consecutive chunks of 512 entries: E[((b*32 + m) * 512) + i] = Hhi[b] * Hmid[m] * Lo[i]  (Hmid over the five variables
 // above Lo's nine, Hhi over the rest: index MSB <-> r_0), so the per-workgroup set-up is shared by 16384 outputs.
+// TB = kEqChunk threads, an entry of Lo per thread, or kSlotBlock, two (Lo's doubling steps read at most 256 entries each).
 constexpr int kEqMidVars = 5, kEqMid = 1 << kEqMidVars;
-__global__ __launch_bounds__(kEqChunk) void eq_table_fused_kernel(fq* __restrict__ out, int ell, int nmid, TauAll rs) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void eq_table_fused_kernel(fq* __restrict__ out, int ell, int nmid, TauAll rs) {
+  static_assert(TB >= kEqChunk / 2 && kEqChunk % TB == 0, "eq_lo_build_lsb: a thread per entry of the widest doubling step");
   __shared__ fq buf[2][kEqChunk];
   __shared__ fq hm[kEqMid];
   const int cur = eq_lo_build_lsb(buf, rs, ell - kEqLoVars);
@@ -249,9 +270,13 @@ __global__ __launch_bounds__(kEqChunk) void eq_table_fused_kernel(fq* __restrict
     hm[m] = run;
   }
   __syncthreads();
-  const fq lo = buf[cur][threadIdx.x];
-  fq* dst = out + ((size_t)blockIdx.x << (nmid + kEqLoVars)) + threadIdx.x;
-  for (int m = 0; m < (1 << nmid); m++) fq_store(dst + (size_t)m * kEqChunk, fq_mul(hm[m], lo));
+#pragma unroll
+  for (int s = 0; s < kEqChunk / TB; s++) {
+    const int i = threadIdx.x + s * TB;
+    const fq lo = buf[cur][i];
+    fq* dst = out + ((size_t)blockIdx.x << (nmid + kEqLoVars)) + i;
+    for (int m = 0; m < (1 << nmid); m++) fq_store(dst + (size_t)m * kEqChunk, fq_mul(hm[m], lo));
+  }
 }
 
 // All suffix tables of ell >= 11 variables (vpin_eq_suffix_tables' layout) in one launch.  Level k = eq(tau_k.., .) has
@@ -259,7 +284,9 @@ __global__ __launch_bounds__(kEqChunk) void eq_table_fused_kernel(fq* __restrict
 // ell-9 and P_k(c) the product of the factors of c's low (ell-k-9) bits (bit j <-> tau_{ell-10-j}).  A workgroup covers
 // 32 consecutive chunk indices c = 32 b + m and writes chunk c of every level that has one; workgroup 0 also writes the
 // levels of fewer than 512 entries.  Prefix products: pm[m][j] over m's bits j < 5, pb[j] over b's bits above them.
-__global__ __launch_bounds__(kEqChunk) void eq_pyramid_fused_kernel(fq* __restrict__ base, int ell, int nlow, TauAll ts) {
+template <int TB>
+__global__ __launch_bounds__(TB, tb_min_waves(TB)) void eq_pyramid_fused_kernel(fq* __restrict__ base, int ell, int nlow, TauAll ts) {
+  static_assert(TB >= kEqChunk / 2 && kEqChunk % TB == 0, "a thread per entry of the widest doubling step");
   __shared__ fq buf[2][kEqChunk];
   __shared__ fq pm[kEqMid][kEqMidVars];
   __shared__ fq pb[32];
@@ -280,8 +307,11 @@ __global__ __launch_bounds__(kEqChunk) void eq_pyramid_fused_kernel(fq* __restri
     }
     cur ^= 1;
     __syncthreads();
-    if (blockIdx.x == 0 && (int)threadIdx.x < 2 * m)
-      fq_store(base + (n - ((size_t)2 << (ell - k))) + threadIdx.x, buf[cur][threadIdx.x]);  // level k, 2m entries
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (int i = threadIdx.x; i < kEqChunk; i += TB)
+        if (i < 2 * m) fq_store(base + (n - ((size_t)2 << (ell - k))) + i, buf[cur][i]);  // level k, 2m entries
+    }
   }
   const int nbits = ell - kEqLoVars - 1;  // bits of a chunk index of level 1
   const fq one = fq_one();
@@ -302,19 +332,23 @@ __global__ __launch_bounds__(kEqChunk) void eq_pyramid_fused_kernel(fq* __restri
     }
   }
   __syncthreads();
-  const fq lo = buf[cur][threadIdx.x];
-  for (int k = 1; k <= ell - kEqLoVars - 1; k++) {
-    const int nb = ell - k - kEqLoVars;  // level k has 2^nb chunks
-    fq* lvl = base + (n - ((size_t)2 << (ell - k))) + threadIdx.x;
-    if (nb <= nlow) {
-      if (blockIdx.x != 0) continue;
-      for (int m = 0; m < (1 << nb); m++) fq_store(lvl + (size_t)m * kEqChunk, fq_mul(pm[m][nb - 1], lo));
-    } else {
-      if (((size_t)blockIdx.x >> (nb - nlow)) != 0) continue;
-      const fq hb = fq_mul(pb[nb - 1], lo);
-      if (nlow == 0) { fq_store(lvl + (size_t)blockIdx.x * kEqChunk, hb); continue; }
-      for (int m = 0; m < (1 << nlow); m++)
-        fq_store(lvl + (((size_t)blockIdx.x << nlow) + m) * kEqChunk, fq_mul(pm[m][nlow - 1], hb));
+#pragma unroll
+  for (int s = 0; s < kEqChunk / TB; s++) {
+    const int i = threadIdx.x + s * TB;
+    const fq lo = buf[cur][i];
+    for (int k = 1; k <= ell - kEqLoVars - 1; k++) {
+      const int nb = ell - k - kEqLoVars;  // level k has 2^nb chunks
+      fq* lvl = base + (n - ((size_t)2 << (ell - k))) + i;
+      if (nb <= nlow) {
+        if (blockIdx.x != 0) continue;
+        for (int m = 0; m < (1 << nb); m++) fq_store(lvl + (size_t)m * kEqChunk, fq_mul(pm[m][nb - 1], lo));
+      } else {
+        if (((size_t)blockIdx.x >> (nb - nlow)) != 0) continue;
+        const fq hb = fq_mul(pb[nb - 1], lo);
+        if (nlow == 0) { fq_store(lvl + (size_t)blockIdx.x * kEqChunk, hb); continue; }
+        for (int m = 0; m < (1 << nlow); m++)
+          fq_store(lvl + (((size_t)blockIdx.x << nlow) + m) * kEqChunk, fq_mul(pm[m][nlow - 1], hb));
+      }
     }
   }
 }
@@ -349,7 +383,9 @@ static int launch_eval(vpin_ctx* c, const vpin_table* const* t, int kclass) {
   size_t half = t[0]->len / 2;
   if (half <= kSmallPairs) {
     ProfScope ps(c, VPIN_K_SC_TAIL, (double)K * 32.0 * (double)t[0]->len);
-    hipLaunchKernelGGL((sc_tail_kernel<K, false>), dim3(1), dim3(kSmallBlock), 0, c->stream, tabs, half, fq{}, c->h_out);
+    dispatch_block<kSmallBlock>(c, [&](auto TB) {
+      hipLaunchKernelGGL((sc_tail_kernel<K, false, TB()>), dim3(1), dim3(TB()), 0, c->stream, tabs, half, fq{}, c->h_out);
+    });
     VPIN_HIP_TRY(hipGetLastError());
     return VPIN_OK;
   }
@@ -374,8 +410,9 @@ static int launch_bind_eval(vpin_ctx* c, vpin_table* const* t, const uint8_t* r,
   if (quarter <= kSmallPairs) {
     {
       ProfScope ps(c, VPIN_K_SC_TAIL, (double)K * 32.0 * ((double)len + (double)len / 2));
-      hipLaunchKernelGGL((sc_tail_kernel<K, true>), dim3(1), dim3(kSmallBlock), 0, c->stream, tabs, quarter, load_host_fq(r),
-                         c->h_out);
+      dispatch_block<kSmallBlock>(c, [&](auto TB) {
+        hipLaunchKernelGGL((sc_tail_kernel<K, true, TB()>), dim3(1), dim3(TB()), 0, c->stream, tabs, quarter, load_host_fq(r), c->h_out);
+      });
     }
     VPIN_HIP_TRY(hipGetLastError());
     for (int k = 0; k < K; k++) t[k]->len = len / 2;
@@ -451,8 +488,10 @@ int sc_cubic3_launch(vpin_ctx* c, vpin_table* const* t, const vpin_table* pyrami
     {
       ProfScope ps(c, VPIN_K_SC_TAIL, bytes);
       dispatch_bools([&](auto B, auto L) {
-        hipLaunchKernelGGL((sc_tail3_kernel<decltype(B)::value, decltype(L)::value>), dim3(1), dim3(kSmallBlock), 0, c->stream, tabs, E,
-                           pairs, rr, c->h_out);
+        dispatch_block<kSmallBlock>(c, [&](auto TB) {
+          hipLaunchKernelGGL((sc_tail3_kernel<decltype(B)::value, decltype(L)::value, TB()>), dim3(1), dim3(TB()), 0, c->stream, tabs, E,
+                             pairs, rr, c->h_out);
+        });
       }, r != nullptr, lead);
     }
     VPIN_HIP_TRY(hipGetLastError());
@@ -583,13 +622,17 @@ int vpin_eq_suffix_tables(vpin_ctx* c, const uint8_t* tau, int ell, vpin_table**
       TauAll ta;
       for (int k = 0; k < ell; k++) ta.t[k] = load_host_fq(tau + 32 * (size_t)k);
       const int nbits = ell - kEqLoVars - 1, nlow = std::min(kEqMidVars, std::max(0, nbits - 8));
-      hipLaunchKernelGGL(eq_pyramid_fused_kernel, dim3((unsigned)((size_t)1 << (nbits - nlow))), dim3(kEqChunk), 0, c->stream, t->d, ell, nlow, ta);
+      dispatch_block<kEqChunk>(c, [&](auto TB) {
+        hipLaunchKernelGGL(eq_pyramid_fused_kernel<TB()>, dim3((unsigned)((size_t)1 << (nbits - nlow))), dim3(TB()), 0, c->stream, t->d, ell, nlow, ta);
+      });
     } else {
       // levels of up to 512 elements (k >= ell-9) in one launch, the larger ones one launch each
       const int k_lo = ell - 9 > 1 ? ell - 9 : 1;
       TauPack tp;
       for (int k = k_lo; k <= ell - 1; k++) tp.t[k - k_lo] = load_host_fq(tau + 32 * (size_t)k);
-      hipLaunchKernelGGL(eq_pyramid_top_kernel, dim3(1), dim3(512), 0, c->stream, t->d, ell, k_lo, tp);
+      dispatch_block<512>(c, [&](auto TB) {
+        hipLaunchKernelGGL(eq_pyramid_top_kernel<TB()>, dim3(1), dim3(TB()), 0, c->stream, t->d, ell, k_lo, tp);
+      });
       for (int k = k_lo - 1; k >= 1; k--) {  // level k from level k+1
         size_t m = (size_t)1 << (ell - k - 1);
         hipLaunchKernelGGL(eq_pyramid_step_kernel, dim3(grid_for(m)), dim3(kBlock), 0, c->stream,
@@ -645,7 +688,9 @@ int vpin_eq_table(vpin_ctx* c, const uint8_t* r, int ell, vpin_table** out) {
       ProfScope ps(c, VPIN_K_EQ, 32.0 * (double)n);
       // chunks per workgroup: one while the table has at most 256 chunks (latency), up to 32 for the large ones (set-up amortised)
       const int nmid = std::min(kEqMidVars, std::max(0, ell - kEqLoVars - 8));
-      hipLaunchKernelGGL(eq_table_fused_kernel, dim3((unsigned)(n >> (kEqLoVars + nmid))), dim3(kEqChunk), 0, c->stream, t->d, ell, nmid, ra);
+      dispatch_block<kEqChunk>(c, [&](auto TB) {
+        hipLaunchKernelGGL(eq_table_fused_kernel<TB()>, dim3((unsigned)(n >> (kEqLoVars + nmid))), dim3(TB()), 0, c->stream, t->d, ell, nmid, ra);
+      });
     }
     hipError_t e1 = hipGetLastError();  // no temporaries: nothing to wait for, later work is ordered on the stream
     if (e1 != hipSuccess) { set_last_error("eq_table", e1); vpin_table_free(c, t); return VPIN_EHIP; }
@@ -667,7 +712,9 @@ int vpin_eq_table(vpin_ctx* c, const uint8_t* r, int ell, vpin_table** out) {
     ProfScope ps(c, VPIN_K_EQ, 32.0 * 3.0 * (double)(n - 1));
     EqHead rs;
     for (int j = 0; j < k0; j++) rs.r[j] = load_host_fq(r + 32 * (size_t)j);
-    hipLaunchKernelGGL(eq_head_kernel, dim3(1), dim3(512), 0, c->stream, src->d, k0, rs);
+    dispatch_block<512>(c, [&](auto TB) {
+      hipLaunchKernelGGL(eq_head_kernel<TB()>, dim3(1), dim3(TB()), 0, c->stream, src->d, k0, rs);
+    });
     vpin_table* dst = (src == a) ? b : a;
     size_t prev = (size_t)1 << k0;
     for (int j = k0; j < ell; j++) {
