@@ -729,8 +729,8 @@ int vpin_conv_trace_instances(vpin_ctx* ctx, const vpin_conv_trace* t, vpin_dev_
  * (+ normalisation, outputs to the host)  [2] PRF (HMAC-SHA256, host team)  [3] RLC sums  [4] host tail  [5] total; a stage the
  * layer does not have (pooling: PRF, RLC) reads 0 */
 void vpin_enc_conv_last_timings(double out[8]);
-/* (ABI 9) Which units made the last encrypted-layer call on this thread answer VPIN_ESHAPE: the planes p of vpin_enc_conv2d and
- * vpin_enc_avgpool2d, the groups g of vpin_enc_conv2d_mc[_bias], the rows p of vpin_enc_fc[_signed] (for these the folded weight
+/* (ABI 9) Which units made the last encrypted-layer call on this thread answer VPIN_ESHAPE: the planes p of vpin_enc_conv2d,
+ * vpin_enc_avgpool2d and (ABI 12) vpin_enc_add, the groups g of vpin_enc_conv2d_mc[_bias], the rows p of vpin_enc_fc[_signed] (for these the folded weight
  * that does not fit 128 bits and the accumulator rule of the chain included).  Ascending, no duplicates: at most cap of them
  * into units, *n is their number.  The code and the text of the call stay the first hit's; the scan that refuses runs to its end
  * and names every unit that breaks ITS rule.  A call that fails at one stage names that stage's units only: the later stages were
@@ -817,6 +817,21 @@ int vpin_enc_conv2d_mc_bias(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py,
                             size_t n_out, size_t H, size_t W, const int32_t* weights, const uint8_t* connect, size_t fh, size_t fw,
                             size_t pad, size_t stride, const uint8_t* bx, const uint8_t* by, const uint8_t* binf, const uint8_t* keys32,
                             int prf_bytes, vpin_conv_trace** out);
+/* (ABI 12) The addition layer: the skip connection of a residual block.  Two encrypted tensors of the same shape, P planes of
+ * H x W points each (px, py, pinf: the first operand X; rx, ry, rinf: the second operand R);
+ *   out[p][t] = X[p][t] + R[p][t]
+ * the complete addition by case, as for the bias above with one second operand per element instead of one per plane.  No
+ * multiplication is recorded and no RLC check runs: dims are {P, H, W, 0, P * H * W}, vpin_conv_trace_mults and _left give NULL
+ * views (as for pooling) and vpin_conv_trace_instances leaves *mult_out NULL.  The addition list is plane-major, then t
+ * row-major: (X[p][t], R[p][t], rz) with rz R's identity flag, an identity R written as rx = ry = 0.  R[p][t] = X[p][t] (a
+ * doubling) and R[p][t] = -X[p][t] (out is the flagged identity) are cases of the addition, not errors, exactly as for the bias;
+ * like there, such a row makes the add instance unsatisfiable: the gadget's addition is the chord rule, which neither case meets.
+ * VPIN_ESHAPE when an X[p][t] is the identity: it is the first operand of an addition, which has no flag; the text names the
+ * first such plane and element, vpin_enc_last_refusals every such plane.  VPIN_EINVAL: a null argument, a zero dimension, H or W
+ * above 2^24, more than 65535 planes, 2^31 points or more, a coordinate >= q, a point off the curve (the text says "first
+ * operand" or "second operand").  vpin_enc_conv_last_timings: [0] validate, [1] the additions, [4] host tail, [5] total. */
+int vpin_enc_add(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, const uint8_t* rx, const uint8_t* ry,
+                 const uint8_t* rinf, size_t P, size_t H, size_t W, vpin_conv_trace** out);
 /* the bare stage beside vpin_e2_conv2d: the output ciphertext only (groups * n_out * oh * ow points), no check; a cancelled
  * output is the flagged identity */
 int vpin_e2_conv2d_mc(vpin_ctx* ctx, const uint8_t* px, const uint8_t* py, const uint8_t* pinf, size_t groups, size_t C, size_t n_out,
@@ -1029,6 +1044,21 @@ void vpin_lenet_last_timings(double out[16]);
  *                  `repeat` times, then its c2 planes
  * vpin_lenet_as_net writes the reference's LeNet as such a list */
 #define VPIN_NET_ORDER_INTERLEAVED 1
+/*   (ABI 12) Tensor references, again at the END of vpin_net_layer and all zero for today's behaviour: a layer may read a tensor
+ *   other than its predecessor's, and VPIN_NET_ADD adds two of them (a skip connection).  A reference on layer i is
+ *     0                    the default: for input_from the previous layer's output (the encrypted input on layer 0), for
+ *                          skip_from "none"
+ *     k in 1 .. i          the output of layer k - 1 as the server holds it after that layer's round, or straight after the
+ *                          layer when it has no round
+ *     VPIN_NET_FROM_INPUT  the inference's encrypted input
+ *   input_from     any kind: what the layer reads; the shape that reaches the layer is that tensor's
+ *   skip_from      VPIN_NET_ADD only: the second operand
+ *   VPIN_NET_ADD   vpin_enc_add over the 2 C planes per image in the blocked order (all c1 planes, then all c2 planes): the first
+ *                  operand is the layer's input, the second the tensor skip_from names.  The shape goes through unchanged; no
+ *                  keys, no bias r, 2 C H W additions per image; a round may follow as after any layer.  Adding the c1 halves and
+ *                  the c2 halves adds the plaintexts.  The server keeps a referenced tensor, as host bytes, until its last use */
+#define VPIN_NET_ADD 5
+#define VPIN_NET_FROM_INPUT ((size_t)-1)
 typedef struct vpin_net_layer {
   int kind;
   size_t fh, fw, pad;            /* CONV */
@@ -1048,6 +1078,8 @@ typedef struct vpin_net_layer {
   size_t sum_out;
   size_t repeat;                 /* CONV: 0 or 1: once */
   int plane_order;               /* CONV and POOL: 0, or VPIN_NET_ORDER_INTERLEAVED */
+  size_t input_from;             /* any kind: 0, 1 .. i, or VPIN_NET_FROM_INPUT: what the layer reads */
+  size_t skip_from;              /* ADD: 1 .. i or VPIN_NET_FROM_INPUT: the second operand; the other kinds: 0 */
 } vpin_net_layer;
 typedef struct vpin_net_cfg {
   size_t C, H, W;                /* the encrypted input */
@@ -1063,7 +1095,10 @@ typedef struct vpin_net_cfg {
  * or a row of connect that selects no channel (the table is read here: the counts depend on it; the weights are not); (ABI 8) a
  * sum_table or a repeat > 1 on a layer that is no CONV, a sum_table with sum_out = 0 or with a row that selects no plane (read
  * here likewise), a plane_order that is neither 0 nor VPIN_NET_ORDER_INTERLEAVED.  A CONV behind sums and repeat counts 2 C'
- * planes, keys and C' planes out, C' = (sum_out, or the incoming C) * repeat */
+ * planes, keys and C' planes out, C' = (sum_out, or the incoming C) * repeat.  (ABI 12) The walk follows input_from for the shape
+ * that reaches each layer; VPIN_EINVAL, each with a text of its own, for a reference to the layer itself or a later one, a
+ * skip_from on a kind other than ADD, an ADD without one, an ADD whose two operands are the same tensor (all doublings), an ADD
+ * whose operands differ in C, H or W (the text gives both shapes), an ADD with a plane_order, a sum_table or a repeat */
 int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
 /* (ABI 8) the reference's LeNet as a layer list: the seven layers vpin_lenet_infer runs (CONV with repeat = n1; POOL; CONV behind
  * the sums by cfg->connect; POOL; CONV behind the sum of all planes with repeat = n3; FC; FC), the convolutions and poolings

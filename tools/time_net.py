@@ -1,9 +1,12 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
-the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5 [--reps R] [--nb LOG2] [--no-proofs] [--wire]
+the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5|resnet [--reps R] [--nb LOG2] [--no-proofs] [--wire]
 [--batch 1,2,4,..] [--clients 1,2,4,..] [--isolation] [--refuse 1] [--proofs]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
+resnet is a small residual network on the same image under seeded weights of that kind (tests/residual_model.py, built through
+net.Config.residual_block): CONVMC 1 -> 8 (3 x 3), a block 8 -> 8, a block 8 -> 16 at stride 2 with the 1 x 1 projection, pooling
+over the whole plane, FCS 16 -> 10; its ADD layers (vpin_enc_add) have rounds of their own.
 It prints its fixed seeds, checks the scores and every round's values against the plaintext model (tests/net_model.py) and the
 label's counts against the model's, and then the median / minimum / maximum in ms over R warm runs (after one warm-up run) of
 every layer and every round (the library's host clock, vpin_net_last_timings), of the whole inference, and of the whole
@@ -49,6 +52,7 @@ from vpin_amd import net as VN  # noqa: E402
 import elgamal_model as EL  # noqa: E402
 import fcs_model as TM  # noqa: E402
 import net_model as NM  # noqa: E402
+import residual_model as RM  # noqa: E402
 
 
 def opt(name, default):
@@ -66,7 +70,7 @@ ISOLATION, REFUSE = "--isolation" in sys.argv, opt("--refuse", 0)
 SK = 0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % EL.ORDER
 SEEDS = dict(image_r=0xCA1, bias_r=0xCA2, client_r=0xCA3, keys="sha256('net/key/<i>'), i = 0 ..")
 SEED_C, SEED_P = bytes(range(64)), bytes((11 * i + 5) % 256 for i in range(64))
-KINDS = {VN.CONV: "conv", VN.POOL: "pool", VN.FC: "fc", VN.CONVMC: "convmc", VN.FCS: "fcs"}
+KINDS = {VN.CONV: "conv", VN.POOL: "pool", VN.FC: "fc", VN.CONVMC: "convmc", VN.FCS: "fcs", VN.ADD: "add"}
 
 
 def stats(xs):
@@ -74,10 +78,18 @@ def stats(xs):
 
 
 def main():
-    assert VERSION in VN.VERSIONS + ("lenet5",), "time_net.py A|B|C|D|E|lenet5"
+    assert VERSION in VN.VERSIONS + ("lenet5", "resnet"), "time_net.py A|B|C|D|E|lenet5|resnet"
     print("network", VERSION, "seeds:", SEEDS, "sk: fixed", "nb = 2^%d" % NB_LOG, "reps =", REPS)
     image = NM.reference_image()
-    if VERSION == "lenet5":
+    plain = RM.net_plaintext if VERSION == "resnet" else TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
+    if VERSION == "resnet":
+        model = RM.resnet_model_config()
+        vs, acts = plain(model, image)
+        giant = max(1, (1 << 31) >> NB_LOG)  # the client's range per round: +-2^31
+        assert all(abs(v) < giant << NB_LOG for r in vs for v in r), "the shifts do not keep a round inside the client's range"
+        cfg = RM.resnet_device_config([giant] * RM.RESNET_ROUNDS, model)
+        want = RM.net_counts(model)
+    elif VERSION == "lenet5":
         model = TM.lenet5_model_config()
         vs, acts = TM.net_plaintext(model, image)
         giant = max(1, (1 << 31) >> NB_LOG)  # the client's range per round: +-2^31
@@ -94,11 +106,10 @@ def main():
     assert counts == dict(want, rounds=len(giants))
     if WIRE_PROOFS:
         assert (WIRE or CLIENTS) and not BATCH and not REFUSE, "--proofs goes with --wire or with --clients"
-        proofs_mode(ctx, cfg, model, counts, giants, image, TM.net_plaintext if VERSION == "lenet5" else NM.plaintext)
+        proofs_mode(ctx, cfg, model, counts, giants, image, plain)
         ctx.close()
         return
     if BATCH or CLIENTS:
-        plain = TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
         (refuse_mode if CLIENTS and REFUSE else clients_mode if CLIENTS else batch_mode)(ctx, cfg, model, counts, giants, image, plain)
         ctx.close()
         return
@@ -106,6 +117,8 @@ def main():
     if VERSION == "lenet5":
         fcs = [l for l in model["layers"] if l["kind"] == "fcs"]
         assert all(TM.folded_fit_signed(l["w"], l["N"], keys[44 + 2 * j + i], model["prf_bytes"]) for j, l in enumerate(fcs) for i in range(2))
+    elif VERSION == "resnet":  # its one FCS layer is the last: the last two keys
+        assert all(TM.folded_fit_signed(model["layers"][-1]["w"], 10, k, model["prf_bytes"]) for k in keys[-2:])
     else:
         assert all(NM.keys_fit(model, keys)), "a folded weight does not fit 128 bits under these keys"
     image_rs = EL.splitmix_scalars(SEEDS["image_r"], image.size)

@@ -64,15 +64,20 @@ class NetLayer(C.Structure):
 
 
 class NetLayer8(NetLayer):
-    """the whole vpin_net_layer: behind NetLayer's fields what ABI 8 appended at its end, all zero for a layer as before.  This is
-    the struct the library reads: a vpin_net_cfg points to an array of these"""
+    """vpin_net_layer as ABI 8 to 11 had it: behind NetLayer's fields what ABI 8 appended at its end, all zero for a layer as before"""
     _fields_ = [("sum_table", C.c_void_p), ("sum_out", C.c_size_t), ("repeat", C.c_size_t), ("plane_order", C.c_int)]
+
+
+class NetLayer12(NetLayer8):
+    """the whole vpin_net_layer since ABI 12: behind NetLayer8's fields the tensor references, all zero for a layer as before.  This
+    is the struct the library reads: a vpin_net_cfg points to an array of these"""
+    _fields_ = [("input_from", C.c_size_t), ("skip_from", C.c_size_t)]
 
 
 class NetCfg(C.Structure):
     """vpin_net_cfg of include/vpin_hip.h"""
     _fields_ = [("C", C.c_size_t), ("H", C.c_size_t), ("W", C.c_size_t), ("prf_bytes", C.c_int), ("n_layers", C.c_size_t),
-                ("layers", C.POINTER(NetLayer8))]
+                ("layers", C.POINTER(NetLayer12))]
 
 
 class WireHeader(C.Structure):
@@ -241,6 +246,7 @@ def lib():
     L.vpin_enc_fc_signed.argtypes = L.vpin_enc_fc.argtypes
     L.vpin_enc_conv2d_mc_bias.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, vp] + [C.c_size_t] * 4 + [vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
     L.vpin_enc_avgpool2d.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 5 + [vp, C.POINTER(vp)]
+    L.vpin_enc_add.argtypes = [vp] * 7 + [C.c_size_t] * 3 + [C.POINTER(vp)]
     L.vpin_conv_trace_free.argtypes = [vp]
     L.vpin_conv_trace_free.restype = None
     L.vpin_conv_trace_dims.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -269,7 +275,7 @@ def lib():
     L.vpin_e2_plane_sums.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_plane_sums_batch.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 4 + [vp, C.c_size_t, vp, vp, vp]
     L.vpin_lenet_cfg_default.argtypes = [C.POINTER(LenetCfg)]
-    L.vpin_lenet_as_net.argtypes = [C.POINTER(LenetCfg), C.POINTER(NetLayer8), vp, C.POINTER(NetCfg)]
+    L.vpin_lenet_as_net.argtypes = [C.POINTER(LenetCfg), C.POINTER(NetLayer12), vp, C.POINTER(NetCfg)]
     L.vpin_lenet_cfg_counts.argtypes = [C.POINTER(LenetCfg), C.POINTER(C.c_size_t)]
     L.vpin_lenet_infer.argtypes = [vp, C.POINTER(LenetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.vpin_lenet_trace_free.argtypes = [vp]
@@ -1586,6 +1592,16 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         rc = lib().vpin_enc_avgpool2d(self.h, p(x), p(y), p(f), P, H, W, k, stride, p(s), C.byref(h))
         return self._trace(rc, h, "vpin_enc_avgpool2d")
+
+    def enc_add(self, x, y, inf, rx, ry, rinf, P, H, W):
+        """the addition layer (vpin_enc_add): out[p][t] = X[p][t] + R[p][t] over two tensors of P planes of H x W points -> ConvTrace"""
+        x, y, f = self._points(x, y, inf)
+        rx, ry, rf = self._points(rx, ry, rinf)
+        assert x.shape[0] == P * H * W and rx.shape[0] == P * H * W
+        h = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().vpin_enc_add(self.h, p(x), p(y), p(f), p(rx), p(ry), p(rf), P, H, W, C.byref(h))
+        return self._trace(rc, h, "vpin_enc_add")
 
     @staticmethod
     def enc_conv_timings():

@@ -1,4 +1,4 @@
-// enc_conv.h -- what the encrypted layers share.  Device side (enc_conv.hip, enc_fc.hip, enc_convmc.hip; also used by lenet.hip
+// enc_conv.h -- what the encrypted layers share.  Device side (enc_conv.hip, enc_fc.hip, enc_convmc.hip, enc_add.hip; also used by lenet.hip
 // and e2_client.hip): E2Points, a set of affine points resident on the device; E2Affine / e2_emit, the one path from Jacobian
 // results to canonical bytes on the host; EncConvDev, the stages of one layer.  Host side (enc_conv.cpp, for enc_fc.cpp and
 // enc_convmc.cpp too): E2 on the host, the PRF, the frame of a layer driver and the tail that writes a chain of additions
@@ -107,6 +107,12 @@ struct EncConvDev {
 int mul_chain(vpin_ctx* c, const E2Points& pts, const uint8_t* s_le16, size_t P, size_t K, uint8_t* t_x, uint8_t* t_y, uint8_t* t_inf,
               uint8_t* acc_x, uint8_t* acc_y, uint8_t* acc_inf);
 
+// The addition layer's stage (enc_add.hip: e2_pair_add_kernel, one normalisation): out[p][t] = x[p][t] + r[p][t] over P planes of
+// per_plane loaded points each, the complete addition, canonical bytes and flags to the host; bad_plane: P bytes, 1 = an x of
+// that plane is the identity (the scan of the first operands' flags, on the device).  Synchronises once
+int e2_pair_add(vpin_ctx* c, const E2Points& x, const E2Points& r, size_t P, size_t per_plane, uint8_t* out_x, uint8_t* out_y, uint8_t* out_inf,
+                uint8_t* bad_plane);
+
 // What the other .hip files take from enc_conv.hip (types: fq_dev.h, e2_dev.h): a device constant from 32 canonical
 // little-endian bytes, the curve coefficient a (both in Montgomery form), the geometry as the kernels take it, and the launches
 // of e2_to_affine_kernel (n points) and e2_reduce_kernel (n_sums sums of n_parts partials each) on the context's stream, not
@@ -190,7 +196,7 @@ struct Lap {
 
 }  // namespace vpin
 
-// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias], vpin_enc_fc[_signed], vpin_enc_avgpool2d)
+// what every encrypted layer returns (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias], vpin_enc_fc[_signed], vpin_enc_avgpool2d, vpin_enc_add)
 struct vpin_conv_trace {
   size_t P = 0, oh = 0, ow = 0, n_mult = 0, n_add = 0;
   std::vector<uint8_t> out_x, out_y, out_inf;        // P * oh * ow

@@ -1,5 +1,5 @@
 // infer_core.cpp -- the server loop of an encrypted inference over the layer entry points (vpin_enc_conv2d, vpin_enc_conv2d_mc[_bias],
-// vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_e2_plane_sums_batch) and the interaction with the client as a callback per round: what vpin_lenet_infer
+// vpin_enc_avgpool2d, vpin_enc_fc[_signed], vpin_enc_add, vpin_e2_plane_sums_batch) and the interaction with the client as a callback per round: what vpin_lenet_infer
 // (lenet.cpp) and vpin_net_infer[_batch] (net.cpp) both run.  Ciphertexts cross every layer boundary as host bytes; each layer
 // validates what it is given, the client's answers included.  A batch of B images is the same loop: every layer call and every
 // round takes the planes of all images at once, image after image (infer_core.h, Call).  The loop runs over the list of LIVE
@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <utility>
 
 namespace vpin::infer {
@@ -206,13 +207,36 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   Pts c1, c2;     // what the server holds: [position][C][H][W] each
   c1.append(a.c1x, a.c1y, a.c1inf, B * C * H * W);
   c2.append(a.c2x, a.c2y, a.c2inf, B * C * H * W);
+  // Tensor t is the encrypted input (t = 0) or the output of step t - 1 after its round: step i begins with tensor i in c1, c2.
+  // A tensor that a step names other than as the c1, c2 at hand is kept, a copy of the pair with its shape, from the moment it is
+  // at hand until the last step that names it; the kept pairs follow the live slots like c1 and c2 themselves
+  struct Kept {
+    Pts c1, c2;
+    size_t C = 0, H = 0, W = 0;
+  };
+  constexpr size_t none = (size_t)-1;
+  auto tensor_of = [](size_t ref, size_t i) { return ref == Step::kFromInput ? (size_t)0 : ref ? ref : i; };
+  std::vector<size_t> last_use(steps.size(), none);  // per tensor the last step that takes it from `kept`
+  bool any_kept = false;
+  for (size_t i = 0; i < steps.size(); i++) {
+    const size_t in = tensor_of(steps[i].input_from, i);
+    if (in != i) last_use[in] = i;
+    if (steps[i].skip_from) last_use[tensor_of(steps[i].skip_from, i)] = i;
+    any_kept = any_kept || in != i || steps[i].skip_from;
+  }
+  std::vector<Kept> kept(any_kept ? steps.size() : 0);
+  auto remove_from_all = [&](const std::vector<size_t>& at) {  // before live.remove
+    remove_images(&c1, live.n(), at);
+    remove_images(&c2, live.n(), at);
+    for (Kept& k : kept)
+      if (k.c1.n()) { remove_images(&k.c1, live.n(), at); remove_images(&k.c2, live.n(), at); }
+  };
   if (a.iso)
     for (size_t b = 0; b < B; b++) write_status(&a.iso->status[b], VPIN_OK, 0, -1, "");
   // an isolated run: the images at these positions leave with their status written; false when nobody is left
   auto leave = [&](const std::vector<size_t>& at, int code, size_t layer, int round, const std::string& text) {
     for (const size_t p : at) write_status(&a.iso->status[live.live[p]], code, layer, round, text);
-    remove_images(&c1, live.n(), at);
-    remove_images(&c2, live.n(), at);
+    remove_from_all(at);
     live.remove(at);
     return live.n() != 0;
   };
@@ -220,6 +244,17 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     int rc = VPIN_OK;
+    const size_t in_t = tensor_of(s.input_from, i), skip_t = s.skip_from ? tensor_of(s.skip_from, i) : none;
+    if (any_kept) {
+      if (last_use[i] != none) kept[i] = Kept{c1, c2, C, H, W};  // a later step, or this one by another name, reads what is at hand
+      if (in_t != i) {  // the step reads a kept tensor: a copy, or the pair itself at its last use
+        Kept& k = kept[in_t];
+        const bool last = last_use[in_t] == i && skip_t != in_t;
+        if (last) { c1 = std::move(k.c1); c2 = std::move(k.c2); } else { c1 = k.c1; c2 = k.c2; }
+        C = k.C; H = k.H; W = k.W;
+        if (last) k = Kept();
+      }
+    }
     while (s.sum_table) {  // ONE call over the groups g = 2 b + half, then the sums back into c1 and c2
       const size_t n = live.n(), img = C * H * W, out_img = s.sum_out * H * W;
       Pts in, sum;
@@ -244,7 +279,7 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
     }
     if (s.kind == Step::kFc || s.kind == Step::kFcs) { W *= C * H; C = H = 1; }  // flattened: the c1 row, then the c2 row
     const size_t Cc = C * s.repeat;  // the planes per half that the call takes
-    const size_t per_image = s.kind == Step::kConv || s.kind == Step::kPool ? 2 * Cc : 2;  // planes, or groups, or rows
+    const size_t per_image = s.kind == Step::kConv || s.kind == Step::kPool || s.kind == Step::kAdd ? 2 * Cc : 2;  // planes, or groups, or rows
     vpin_conv_trace* tr = nullptr;
     for (;;) {  // the layer call; an isolated run repeats it without the images it refuses, at most B times
       const size_t n = live.n();
@@ -260,6 +295,9 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
         rc = conv_mc(a, live, s, in, Cc, H, W, k, r, &tr);
       } else if (s.kind == Step::kPool) {
         rc = vpin_enc_avgpool2d(a.c, in.x.data(), in.y.data(), in.inf.data(), n * 2 * Cc, H, W, s.k, s.stride, s.scale_le16, &tr);
+      } else if (s.kind == Step::kAdd) {  // the kept pair is only read: it may have a later use
+        const Pts skip = gather(kept[skip_t].c1, kept[skip_t].c2, n, C, 1, Step::kBlocked, false);
+        rc = vpin_enc_add(a.c, in.x.data(), in.y.data(), in.inf.data(), skip.x.data(), skip.y.data(), skip.inf.data(), n * 2 * Cc, H, W, &tr);
       } else {
         rc = fc(a, live, s, in, k, r, &tr);
       }
@@ -276,12 +314,20 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
         at = positions_of_units(units.data(), units.size(), per_image, n);
       } else {  // a point the layer's load refuses: the input's, or a reply's
         at = bad_images(a, c1, c2, n);
+        if (s.kind == Step::kAdd) {  // or the second operand's
+          const std::vector<size_t> more = bad_images(a, kept[skip_t].c1, kept[skip_t].c2, n);
+          std::vector<size_t> both;
+          std::set_union(at.begin(), at.end(), more.begin(), more.end(), std::back_inserter(both));
+          at = both;
+        }
       }
       if (at.empty()) return fail(rc, text.c_str());  // nobody's doing, or nobody's that can be named
       a.iso->refused += at.size();
       a.iso->repeats++;
       if (!leave(at, rc, i, -1, text)) return nobody();
     }
+    for (size_t t = 0; t < kept.size(); t++)
+      if (last_use[t] == i) kept[t] = Kept();  // its last use
     br += 32 * bias_values(s);
     key += 32 * s.keys;
     out->step.push_back(tr);
@@ -301,8 +347,7 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
     }
     std::sort(at.begin(), at.end());
     a.iso->dropped += at.size();
-    remove_images(&c1, live.n(), at);
-    remove_images(&c2, live.n(), at);
+    remove_from_all(at);
     live.remove(at);
     if (!live.n()) return nobody();
   }

@@ -19,7 +19,12 @@ struct Isolation {
 };
 
 struct Step {
-  enum Kind { kConv, kPool, kFc, kConvMc, kFcs } kind = kConv;
+  enum Kind { kConv, kPool, kFc, kConvMc, kFcs, kAdd } kind = kConv;
+  // what the step reads, as vpin_net_layer says it: 0 the previous step's output (skip_from: none), k the output of step k - 1
+  // after its round, kFromInput the encrypted input.  kAdd: vpin_enc_add over the 2 C planes, kBlocked, the second operand the
+  // tensor skip_from names.  run() keeps, as host Pts pairs, exactly the tensors a later step names, each until its last use
+  static constexpr size_t kFromInput = (size_t)-1;
+  size_t input_from = 0, skip_from = 0;
   // how c1 and c2 make up the layer call's P = 2 C planes, and how its output splits back: all c1 planes and then all c2 planes
   // (first half, second half), or (0, c1), (0, c2), (1, c1), .. (even planes, odd planes).  For kFc and kFcs, P = 2, they coincide
   enum Order { kBlocked, kInterleaved } order = kBlocked;

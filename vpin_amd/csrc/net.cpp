@@ -26,7 +26,8 @@ using vpin::infer::Step;
 namespace {
 
 const char* kind_name(int kind) {
-  return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : kind == VPIN_NET_CONVMC ? "convmc" : kind == VPIN_NET_FCS ? "fcs" : "fc";
+  return kind == VPIN_NET_CONV ? "conv" : kind == VPIN_NET_POOL ? "pool" : kind == VPIN_NET_CONVMC ? "convmc" : kind == VPIN_NET_FCS ? "fcs"
+         : kind == VPIN_NET_ADD ? "add" : "fc";
 }
 
 // per layer what it consumes and leaves; the walk that vpin_net_cfg_counts and vpin_net_infer share
@@ -35,6 +36,7 @@ struct LayerPlan {
   size_t sumC, inC;      // the planes per half that reach the channel sums, and the layer call behind sums and repeat
   size_t mult, add, keys, bias_r;
   int round;             // index of the round after the layer, or -1
+  size_t iH, iW;         // the plane that reaches the layer (input_from followed)
 };
 
 constexpr size_t kMaxLayers = 4096, kMaxSide = 4096, kMaxPlanes = 16384;
@@ -47,14 +49,45 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
   size_t C = g->C, H = g->H, W = g->W;
   int rounds = 0;
   out->clear();
+  // a reference of layer i as a tensor: 0 the encrypted input, t the output of layer t - 1; false: the layer itself or a later one
+  auto tensor_of = [](size_t ref, size_t i, size_t* t) {
+    if (ref == VPIN_NET_FROM_INPUT) { *t = 0; return true; }
+    *t = ref ? ref : i;
+    return ref <= i;
+  };
+  auto shape_of = [&](size_t t, size_t* c, size_t* h, size_t* w) {
+    if (t) { *c = (*out)[t - 1].oC; *h = (*out)[t - 1].oH; *w = (*out)[t - 1].oW; } else { *c = g->C; *h = g->H; *w = g->W; }
+  };
   for (size_t i = 0; i < g->n_layers; i++) {
     const vpin_net_layer& l = g->layers[i];
-    LayerPlan p{C, H, W, C, C, 0, 0, 0, 0, -1};
+    const std::string at = "vpin_net: layer " + std::to_string(i) + ": ";
+    size_t in_t = i, skip_t = 0;
+    if (!tensor_of(l.input_from, i, &in_t))
+      return fail(VPIN_EINVAL, (at + "input_from = " + std::to_string(l.input_from) + " names the layer itself or a later one").c_str());
+    if (l.skip_from && l.kind != VPIN_NET_ADD) return fail(VPIN_EINVAL, (at + "only an addition layer takes a skip_from").c_str());
+    if (l.skip_from && !tensor_of(l.skip_from, i, &skip_t))
+      return fail(VPIN_EINVAL, (at + "skip_from = " + std::to_string(l.skip_from) + " names the layer itself or a later one").c_str());
+    if (l.input_from) shape_of(in_t, &C, &H, &W);
+    LayerPlan p{C, H, W, C, C, 0, 0, 0, 0, -1, H, W};
     const char* fit = "vpin_net: a window does not fit its plane";
+    if (l.kind == VPIN_NET_ADD) {  // before the rules of the other kinds: an addition layer's own texts
+      if (!l.skip_from) return fail(VPIN_EINVAL, (at + "an addition layer has no skip_from").c_str());
+      if (l.plane_order || l.sum_table || l.repeat > 1)
+        return fail(VPIN_EINVAL, (at + "an addition layer takes no plane_order, sum_table or repeat").c_str());
+      if (skip_t == in_t)
+        return fail(VPIN_EINVAL, (at + "an addition layer's two operands are the same tensor (every addition would be a doubling)").c_str());
+      size_t sC, sH, sW;
+      shape_of(skip_t, &sC, &sH, &sW);
+      auto dims = [](size_t c, size_t h, size_t w) { return std::to_string(c) + " x " + std::to_string(h) + " x " + std::to_string(w); };
+      if (sC != C || sH != H || sW != W)
+        return fail(VPIN_EINVAL, (at + "an addition layer's operands differ in shape: C x H x W = " + dims(C, H, W) + " and " + dims(sC, sH, sW)).c_str());
+    }
     if (l.kind != VPIN_NET_CONV && (l.sum_table || l.repeat > 1)) return fail(VPIN_EINVAL, "vpin_net: only a convolution takes a sum_table or a repeat");
     if (l.plane_order != 0 && l.plane_order != VPIN_NET_ORDER_INTERLEAVED)
       return fail(VPIN_EINVAL, "vpin_net: a layer's plane_order is neither 0 nor VPIN_NET_ORDER_INTERLEAVED");
-    if (l.kind == VPIN_NET_CONV) {
+    if (l.kind == VPIN_NET_ADD) {  // the shape goes through; no keys, no bias r
+      p.add = 2 * C * H * W;
+    } else if (l.kind == VPIN_NET_CONV) {
       if (l.sum_table) {  // like a trained convolution's table, architecture: read here
         if (!l.sum_out) return fail(VPIN_EINVAL, "vpin_net: a convolution has a sum_table and sum_out = 0");
         if (l.sum_out > kMaxPlanes) return fail(VPIN_EINVAL, "vpin_net: a dimension is out of range");
@@ -121,7 +154,7 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       p.keys = 2;
       p.bias_r = l.N;
     } else {
-      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc, convmc, fcs");
+      return fail(VPIN_EINVAL, "vpin_net: a layer's kind is none of conv, pool, fc, convmc, fcs, add");
     }
     if (l.has_round) {
       if (l.shift_bits < 0 || l.shift_bits > 62) return fail(VPIN_EINVAL, "vpin_net: a round's shift_bits is outside 0 .. 62");
@@ -158,8 +191,8 @@ int fits(const char* who, const vpin_net_cfg* g, const std::vector<LayerPlan>& p
     const std::string name = std::string(who) + ": layer " + std::to_string(i) + " (" + kind_name(l.kind) + "): ";
     const bool fc = l.kind == VPIN_NET_FC || l.kind == VPIN_NET_FCS;
     const size_t planes = fc ? 2 * B : 2 * B * pl[i].inC;
-    if (l.sum_table) {  // H, W of what reaches the layer: the previous layer's output
-      const size_t hw = i ? pl[i - 1].oH * pl[i - 1].oW : g->H * g->W, most = pl[i].sumC > l.sum_out ? pl[i].sumC : l.sum_out;
+    if (l.sum_table) {  // H, W of what reaches the layer
+      const size_t hw = pl[i].iH * pl[i].iW, most = pl[i].sumC > l.sum_out ? pl[i].sumC : l.sum_out;
       if (2 * B * most * hw >= ((size_t)1 << 31))
         return fail(VPIN_EINVAL, (name + "the planes of all images around the channel sums are 2^31 points or more").c_str());
     }
@@ -226,7 +259,8 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
     const vpin_net_layer& l = g->layers[i];
     Step& s = steps[i];
     s.kind = l.kind == VPIN_NET_CONV ? Step::kConv : l.kind == VPIN_NET_POOL ? Step::kPool : l.kind == VPIN_NET_CONVMC ? Step::kConvMc
-             : l.kind == VPIN_NET_FCS ? Step::kFcs : Step::kFc;
+             : l.kind == VPIN_NET_FCS ? Step::kFcs : l.kind == VPIN_NET_ADD ? Step::kAdd : Step::kFc;
+    s.input_from = l.input_from; s.skip_from = l.skip_from;
     s.filter_le16 = l.filter_le16; s.fh = l.fh; s.fw = l.fw; s.pad = l.pad; s.stride = l.stride;
     if (l.kind == VPIN_NET_CONV) { s.sum_table = l.sum_table; s.sum_out = l.sum_out; s.repeat = l.repeat ? l.repeat : 1; }
     if ((l.kind == VPIN_NET_CONV || l.kind == VPIN_NET_POOL) && l.plane_order == VPIN_NET_ORDER_INTERLEAVED) s.order = Step::kInterleaved;

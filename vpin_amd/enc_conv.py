@@ -1,5 +1,5 @@
-"""The encrypted layers of vPIN's inference server over the C ABI (vpin_enc_conv2d, vpin_enc_conv2d_mc, vpin_enc_fc, vpin_enc_avgpool2d):
-ciphertext planes and a filter (or rows and a weight matrix, or a pooling window) in, the output ciphertext and the two gadget
+"""The encrypted layers of vPIN's inference server over the C ABI (vpin_enc_conv2d, vpin_enc_conv2d_mc, vpin_enc_fc, vpin_enc_avgpool2d,
+vpin_enc_add): ciphertext planes and a filter (or rows and a weight matrix, or a pooling window, or a second tensor) in, the output ciphertext and the two gadget
 operation lists out -- as device instances for vpin_snark_prove_dev, or as the witness files the reference's Python service
 writes, so that the unchanged CLI proves a real layer."""
 import json
@@ -72,6 +72,16 @@ def avgpool_layer(ctx, c1, c2, k, stride, scale=None):
     H, W = shape[1:3]
     x, y, inf = (np.concatenate([p[i] for p in parts]) for i in range(3))
     return ctx.enc_avgpool2d(x, y, inf, x.shape[0] // (H * W), H, W, k, stride, 2**10 // (k * k) if scale is None else scale)
+
+
+def add_layer(ctx, first, second):
+    """The addition layer (vpin_enc_add): out = first + second, point by point.  first, second: two encrypted tensors of one
+    shape, each (x, y, inf) with x, y of shape (planes, H, W, 32) and inf of shape (planes, H, W) or None -- as the driver calls it,
+    the C c1 planes and then the C c2 planes of each.  Returns the ConvTrace (Context.enc_add): additions only, no left sides"""
+    shape = np.asarray(first[0]).shape
+    assert len(shape) == 4 and np.asarray(second[0]).shape == shape, "two tensors of one planes x H x W"
+    a, b = _flat(first), _flat(second)
+    return ctx.enc_add(a[0], a[1], a[2], b[0], b[1], b[2], shape[0], shape[1], shape[2])
 
 
 def write_witness_files(trace, root, label):

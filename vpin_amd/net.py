@@ -3,7 +3,9 @@
 any number of rounds, or a Python callback), and the network's ONE label for the prover: the lists of all layers concatenated
 in layer order, as the reference leaves them in its four global lists.  Beside the reference's three layer kinds there is CONVMC,
 the convolution of a trained model (vpin_enc_conv2d_mc: a signed filter per channel pair, an optional connection table, and with a
-bias vpin_enc_conv2d_mc_bias), and FCS, the fully connected layer over signed weights (vpin_enc_fc_signed).
+bias vpin_enc_conv2d_mc_bias), FCS, the fully connected layer over signed weights (vpin_enc_fc_signed), and ADD, the addition of two
+encrypted tensors (vpin_enc_add).  A layer reads the previous layer's output unless its input_from names another tensor, and an
+ADD's skip_from names its second operand: a skip connection (Config.add, Config.residual_block).
 
 The networks' constants are data, not code: `cnn_config(version)` reads the filter, the pooling windows, the PRF bytes, the
 schedule of the rounds and the names of the weight files from the fixture recorded off runs of the reference
@@ -15,10 +17,11 @@ import os
 import numpy as np
 
 from . import inference
-from .capi import NetCfg, NetImageStatus, NetLayer8 as NetLayer, NetPeerStatus, VpinError, _chk, lib
+from .capi import NetCfg, NetImageStatus, NetLayer12 as NetLayer, NetPeerStatus, VpinError, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
-CONV, POOL, FC, CONVMC, FCS = 0, 1, 2, 3, 4
+CONV, POOL, FC, CONVMC, FCS, ADD = 0, 1, 2, 3, 4, 5
+FROM_INPUT = 2**64 - 1  # VPIN_NET_FROM_INPUT, (size_t)-1
 ORDER_INTERLEAVED = 1  # VPIN_NET_ORDER_INTERLEAVED
 VERSIONS = ("A", "B", "C", "D", "E")
 _GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -33,20 +36,47 @@ class Config:
         self.prf_bytes = prf_bytes
         self.layers, self._keep = [], []
 
-    def _add(self, kind):
+    def _add(self, kind, input_from=0):
         l = NetLayer()
-        l.kind = kind
+        l.kind, l.input_from = kind, input_from
         self.layers.append(l)
         return l
 
-    def conv(self, filt, pad=0, stride=1, sum_table=None, repeat=1, interleaved=False):
+    def here(self):
+        """the reference that names the tensor at hand, for a later layer's input_from or skip_from: the output of the layer
+        added last (after its round), or the encrypted input when there is no layer yet"""
+        return len(self.layers) or FROM_INPUT
+
+    def add(self, skip_from, input_from=0):
+        """the addition layer (VPIN_NET_ADD): the layer's input plus the tensor skip_from names (a reference as `here` gives it: k
+        for the output of layer k - 1, FROM_INPUT for the encrypted input); both of one shape, which goes through"""
+        self._add(ADD, input_from).skip_from = skip_from
+        return self
+
+    def residual_block(self, w1, b1, w2, b2, rounds, stride=1, proj=None):
+        """a residual block over the tensor at hand: CONVMC 3 x 3 pad 1 (stride `stride`) and its round with ReLU; CONVMC 3 x 3
+        pad 1 and its round without; with proj (n_out x C x 1 x 1 weights, or (weights, bias)) a CONVMC 1 x 1 of stride `stride`
+        that reads the block's input, and its round without ReLU; then the ADD of the two branches and its round with ReLU.
+        rounds: the dicts of Config.round for them in that order (three, or four with proj); their relu is set here"""
+        assert len(rounds) == (4 if proj is not None else 3)
+        src = self.here()
+        self.convmc(w1, pad=1, stride=stride, bias=b1).round(**dict(rounds[0], relu=True))
+        self.convmc(w2, pad=1, bias=b2).round(**dict(rounds[1], relu=False))
+        skip = src
+        if proj is not None:
+            skip = self.here()  # the main branch; the projection is then the tensor at hand
+            pw, pb = proj if isinstance(proj, tuple) else (proj, None)
+            self.convmc(pw, stride=stride, bias=pb, input_from=src).round(**dict(rounds[2], relu=False))
+        return self.add(skip).round(**dict(rounds[-1], relu=True))
+
+    def conv(self, filt, pad=0, stride=1, sum_table=None, repeat=1, interleaved=False, input_from=0):
         """filt: fh x fw ints below 2^128.  What the reference's LeNet adds: sum_table, sum_out x C bytes (non-zero = connected): the
         channel sums in front of the layer; repeat: the planes handed to the call that many times over, each under its own key;
         interleaved: the planes as (0, c1), (0, c2), (1, c1), .. instead of all c1 and then all c2"""
         filt = [[int(v) for v in row] for row in filt]
         buf = np.frombuffer(b"".join(v.to_bytes(16, "little") for row in filt for v in row), dtype=np.uint8).copy()
         self._keep.append(buf)
-        l = self._add(CONV)
+        l = self._add(CONV, input_from)
         l.fh, l.fw, l.pad, l.stride, l.filter_le16 = len(filt), len(filt[0]), pad, stride, buf.ctypes.data
         l.repeat, l.plane_order = 0 if repeat == 1 else repeat, ORDER_INTERLEAVED if interleaved else 0  # all zero: a layer as before
         if sum_table is not None:
@@ -56,14 +86,14 @@ class Config:
             l.sum_table, l.sum_out = t.ctypes.data, t.shape[0]
         return self
 
-    def convmc(self, w, connect=None, pad=0, stride=1, bias=None):
+    def convmc(self, w, connect=None, pad=0, stride=1, bias=None, input_from=0):
         """the trained convolution (VPIN_NET_CONVMC): w[o][c][ii][jj] signed ints (int32 range), n_out x C x fh x fw with C the
         planes that reach the layer; connect: n_out x C, non-zero = connected (None: all); bias: n_out ints (None: no bias)"""
         w64 = np.asarray(w, dtype=np.int64)
         w32 = np.ascontiguousarray(w64.astype(np.int32))
         assert w32.ndim == 4 and np.array_equal(w32, w64)
         self._keep.append(w32)
-        l = self._add(CONVMC)
+        l = self._add(CONVMC, input_from)
         l.n_out, l.fh, l.fw, l.pad, l.stride, l.w_mc = w32.shape[0], w32.shape[2], w32.shape[3], pad, stride, w32.ctypes.data
         if connect is not None:
             t = np.ascontiguousarray(np.asarray(connect) != 0, dtype=np.uint8)
@@ -77,13 +107,13 @@ class Config:
             l.bias = b.ctypes.data
         return self
 
-    def pool(self, k, stride, scale, interleaved=False):
-        l = self._add(POOL)
+    def pool(self, k, stride, scale, interleaved=False, input_from=0):
+        l = self._add(POOL, input_from)
         l.k, l.stride, l.plane_order = k, stride, ORDER_INTERLEAVED if interleaved else 0
         l.scale_le16[:] = list(int(scale).to_bytes(16, "little"))
         return self
 
-    def fc(self, w, bias, kind=FC):
+    def fc(self, w, bias, kind=FC, input_from=0):
         """w: K x N ints (int32 range; a negative one is rejected by the driver), bias: N ints"""
         w64 = np.asarray(w, dtype=np.int64)
         w32 = np.ascontiguousarray(w64.astype(np.int32))
@@ -91,13 +121,13 @@ class Config:
         b = np.ascontiguousarray(np.asarray(bias, dtype=np.int64))
         assert b.shape == (w32.shape[1],)
         self._keep += [w32, b]
-        l = self._add(kind)
+        l = self._add(kind, input_from)
         l.K, l.N, l.w, l.bias = w32.shape[0], w32.shape[1], w32.ctypes.data, b.ctypes.data
         return self
 
-    def fcs(self, w, bias):
+    def fcs(self, w, bias, input_from=0):
         """the fully connected layer of a trained model (VPIN_NET_FCS): fc with signed weights"""
-        return self.fc(w, bias, FCS)
+        return self.fc(w, bias, FCS, input_from)
 
     def round(self, relu=False, shift_bits=0, max_giant=1, reencrypt=True):
         l = self.layers[-1]
