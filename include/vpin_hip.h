@@ -914,6 +914,30 @@ int vpin_e2_client_round(vpin_ctx* ctx, const vpin_e2_dlog* t, const vpin_e2_bas
                          const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int relu, int shift_bits, int reencrypt,
                          const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf,
                          uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+/* (ABI 13) vpin_e2_client_round with max pooling between the decryption and the activation: the server cannot take a maximum of
+ * ElGamal ciphertexts, the client, which decrypts every value anyway, can.  The cnt = planes * H * W inputs are `planes` planes of
+ * H x W values, row-major; Ho = (H - k) / stride + 1 and Wo = (W - k) / stride + 1, rounded down, a remainder of rows or columns
+ * dropped as in vpin_enc_avgpool2d; cnt_out = planes * Ho * Wo.  The same launch chain (the activation launch is
+ * e2_act_pool_kernel, one lane per output element; the encryption runs over cnt_out elements); a window never crosses a plane.
+ *   v_out[cnt]        the raw decryptions, every one, also of elements that belong to no window (0 where the walk met no value)
+ *   act_out[cnt_out]  for output (p, oy, ox): a = the maximum of v[p][oy stride + i][ox stride + j] over 0 <= i, j < k, then
+ *                     max(a, 0) when relu, then shifting(a, shift_bits) when shift_bits != 0, exactly as above.  ReLU and shifting
+ *                     are non-decreasing (the rounding to float32, the exact power-of-two scale and the truncation toward zero each
+ *                     preserve order), so this IS the elementwise activation followed by the maximum: act(max v) = max act(v)
+ *   c1o / c2o         cnt_out points: act_out under cnt_out scalars of r_le32; reencrypt = 0 (the last round may pool): nothing is
+ *                     encrypted and baseG, baseH, r_le32 and the six outputs may be NULL
+ * k = 1, stride = 1 gives vpin_e2_client_round's bytes.
+ * VPIN_ESHAPE: "element i, inside a window, has no value within the walk's range" with the first such INPUT index (the walk's
+ * found bytes are read back on this path only; an element that belongs to no window -- a dropped remainder, a gap of stride > k
+ * -- is no error); then "the activated value of output element o (the maximum decrypted, a) does not fit" with the first such
+ * OUTPUT index, by vpin_e2_client_round's rules.
+ * VPIN_EINVAL: everything vpin_e2_client_round rejects (r_le32: cnt_out scalars), and, each with its text: planes, H or W zero;
+ * k or stride zero; k > H or k > W; planes * H * W >= 2^30. */
+int vpin_e2_client_round_pool(vpin_ctx* ctx, const vpin_e2_dlog* t, const vpin_e2_base* baseG, const vpin_e2_base* baseH,
+                              const uint8_t sk_le32[32], const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x,
+                              const uint8_t* c2y, const uint8_t* c2inf, size_t planes, size_t H, size_t W, size_t k, size_t stride,
+                              uint64_t max_giant, int relu, int shift_bits, int reencrypt, const uint8_t* r_le32, int64_t* v_out,
+                              int64_t* act_out, uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
 
 /* ---- the channel sums of the LeNet server loop ---------------------------------------------------------------------------
  * secondConv and thirdConv of src/LeNet/Server.py add whole ciphertext planes pixel by pixel (np.sum(planes, axis=0)) before
@@ -977,6 +1001,8 @@ int vpin_lenet_cfg_counts(const vpin_lenet_cfg* cfg, size_t out[32]);
  * cleared before the call, and a callback that fails without setting one is reported as "the round callback failed" */
 #define VPIN_LENET_RELU 1
 #define VPIN_LENET_REENCRYPT 2
+/* (ABI 13) vpin_net_infer and its family only: the round pools by maximum, the six outputs hold fewer points (vpin_net_round_pool) */
+#define VPIN_LENET_MAXPOOL 4
 typedef int (*vpin_lenet_round_fn)(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y,
                                    const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
                                    uint8_t* c1ox, uint8_t* c1oy, uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
@@ -1059,6 +1085,13 @@ void vpin_lenet_last_timings(double out[16]);
  *                  the c2 halves adds the plaintexts.  The server keeps a referenced tensor, as host bytes, until its last use */
 #define VPIN_NET_ADD 5
 #define VPIN_NET_FROM_INPUT ((size_t)-1)
+/*   (ABI 13) Max pooling inside the client's round, again at the END of vpin_net_layer and all zero for a round as before:
+ *   round_pool_k, round_pool_stride  on a layer with has_round: the client pools the layer's C x H x W output by maximum over
+ *                  k x k windows at that stride before it activates and encrypts again (vpin_e2_client_round_pool over planes =
+ *                  B * C).  The callback is handed the usual cnt = B C H W ciphertexts, VPIN_LENET_MAXPOOL in flags and six outputs
+ *                  of B C Ho Wo points, Ho = (H - k) / stride + 1, Wo likewise; vpin_net_round_pool gives it the shape.  The tensor
+ *                  after the round is C x Ho x Wo, and every later shape follows from it: what input_from and skip_from name, an
+ *                  ADD's comparison, an FC's K.  No layer call and no round of its own, and 1 / k^2 of the encryptions */
 typedef struct vpin_net_layer {
   int kind;
   size_t fh, fw, pad;            /* CONV */
@@ -1080,6 +1113,8 @@ typedef struct vpin_net_layer {
   int plane_order;               /* CONV and POOL: 0, or VPIN_NET_ORDER_INTERLEAVED */
   size_t input_from;             /* any kind: 0, 1 .. i, or VPIN_NET_FROM_INPUT: what the layer reads */
   size_t skip_from;              /* ADD: 1 .. i or VPIN_NET_FROM_INPUT: the second operand; the other kinds: 0 */
+  size_t round_pool_k;           /* with has_round: 0, or the window of the max pooling inside the round */
+  size_t round_pool_stride;      /* 0 exactly when round_pool_k is */
 } vpin_net_layer;
 typedef struct vpin_net_cfg {
   size_t C, H, W;                /* the encrypted input */
@@ -1098,7 +1133,10 @@ typedef struct vpin_net_cfg {
  * planes, keys and C' planes out, C' = (sum_out, or the incoming C) * repeat.  (ABI 12) The walk follows input_from for the shape
  * that reaches each layer; VPIN_EINVAL, each with a text of its own, for a reference to the layer itself or a later one, a
  * skip_from on a kind other than ADD, an ADD without one, an ADD whose two operands are the same tensor (all doublings), an ADD
- * whose operands differ in C, H or W (the text gives both shapes), an ADD with a plane_order, a sum_table or a repeat */
+ * whose operands differ in C, H or W (the text gives both shapes), an ADD with a plane_order, a sum_table or a repeat.
+ * (ABI 13) A round that pools: out[10 + 3 i] stays the C H W decryptions, out[5] counts its C Ho Wo encryptions, and the layers
+ * behind it count over C x Ho x Wo; VPIN_EINVAL, each text naming the layer: a round_pool_k without has_round, one of round_pool_k
+ * and round_pool_stride zero beside the other, a window that does not fit the layer's output */
 int vpin_net_cfg_counts(const vpin_net_cfg* cfg, size_t* out, size_t cap);
 /* (ABI 8) the reference's LeNet as a layer list: the seven layers vpin_lenet_infer runs (CONV with repeat = n1; POOL; CONV behind
  * the sums by cfg->connect; POOL; CONV behind the sum of all planes with repeat = n3; FC; FC), the convolutions and poolings
@@ -1221,6 +1259,11 @@ int vpin_net_infer_isolated(vpin_ctx* ctx, const vpin_net_cfg* cfg, size_t B, co
                             const uint8_t* bias_r_le32, size_t n_bias_r, vpin_lenet_round_fn round_fn, void* user,
                             vpin_net_image_status* status, vpin_net_trace** out);
 int vpin_net_round_images(const uint32_t** slots, size_t* n);
+/* (ABI 13) inside the round callback, on its thread, like vpin_net_round_images: out = {planes = the live images * C, H, W, k,
+ * stride} of the round at hand; k = 0 (and stride = 0): the round does not pool.  A callback handed VPIN_LENET_MAXPOOL writes
+ * planes * Ho * Wo points.  An image dropped in such a round leaves the batch at its pooled per-image size.  VPIN_EINVAL outside
+ * a callback */
+int vpin_net_round_pool(size_t out[5]);
 int vpin_net_round_drop_images(const uint32_t* slots, size_t n, int code, const char* text);
 int vpin_net_trace_layer_images(const vpin_net_trace* t, size_t layer, const uint32_t** slots, size_t* n);
 /* what the last vpin_net_infer_isolated on this thread did: images a layer refused, images dropped in a round, layer calls repeated */
@@ -1240,6 +1283,22 @@ int vpin_net_client_values(const vpin_net_client* cl, size_t round, const int64_
 int vpin_net_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
                           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* c1ox, uint8_t* c1oy,
                           uint8_t* c1oinf, uint8_t* c2ox, uint8_t* c2oy, uint8_t* c2oinf);
+/* (ABI 13) The client's pooling schedule.  Like the rest of the schedule it is the CLIENT's: a client does not pool, or leave it,
+ * because a server says so.  vpin_net_client_set_pools gives the client its own per-round {H, W, k, stride} (n_rounds: the rounds
+ * it was made for; all zero: the round does not pool, which is what a new client holds for every round).  vpin_net_client_round
+ * then answers VPIN_ESHAPE, with a text that gives both sides, before anything is decrypted (vpin_net_client_values is empty for
+ * that round and no r is consumed) when the VPIN_LENET_MAXPOOL bit of flags disagrees with its schedule for the round, or cnt is no
+ * multiple of H * W; otherwise it calls vpin_e2_client_round_pool with planes = cnt / (H W) and consumes cnt_out values of r.
+ * vpin_net_client_values keeps returning v and act with cnt = |v|; vpin_net_client_act_count gives |act|, the pooled count.
+ * On the wire the ROUND frame is as it was, flags carrying bit 4, which vpin_net_client_run compares with its schedule like every
+ * other flag; the REPLY to a round that pools carries cnt_out points, and vpin_wire_round, which learns cnt_out from
+ * vpin_net_round_pool, rejects any other count.  vpin_net_server_create answers VPIN_EINVAL for a configuration with such a round:
+ * the multi-client server copies a dropped client's images from a round's input to its output at one per-image size */
+typedef struct vpin_net_round_pool_spec {
+  size_t H, W, k, stride;
+} vpin_net_round_pool_spec;
+int vpin_net_client_set_pools(vpin_net_client* cl, const vpin_net_round_pool_spec* pools, size_t n_rounds);
+int vpin_net_client_act_count(const vpin_net_client* cl, size_t round, size_t* n);
 
 /* ---- the inference between two processes over a byte stream (ABI 5) ----------------------------------------------------------
  * The reference's Server.py / Client.py are two processes (send_data_in_chunks / receive_data_in_chunks); here the server loop

@@ -1,9 +1,12 @@
 """The full-size encrypted inference of one of the reference's networks A .. E on its image and weights (vpin_net_infer against
-the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5|resnet [--reps R] [--nb LOG2] [--no-proofs] [--wire]
+the ready-made client, vpin_amd.net):  python tools/time_net.py A|B|C|D|E|lenet5|lenet5max|resnet [--reps R] [--nb LOG2] [--no-proofs] [--wire]
 [--batch 1,2,4,..] [--clients 1,2,4,..] [--isolation] [--refuse 1] [--proofs]
 lenet5 is the architecture of the reference's src/accuracy/train_test_lenet5.py (net.lenet5_config: two biased trained convolutions,
 three signed fully connected layers) on the same image under seeded signed weights |w| < 2^4 (tests/fcs_model.py); no trained
 weights exist here.
+lenet5max is lenet5 under the same weights with both average poolings and their rounds removed and max pooling (2, 2) inside the
+rounds behind the two convolutions (tests/maxpool_model.py; net.Config.round(maxpool=)): five layers and five rounds instead of
+seven and seven; in process, --wire and --batch (the multi-client server does not serve a round that pools).
 resnet is a small residual network on the same image under seeded weights of that kind (tests/residual_model.py, built through
 net.Config.residual_block): CONVMC 1 -> 8 (3 x 3), a block 8 -> 8, a block 8 -> 16 at stride 2 with the 1 x 1 projection, pooling
 over the whole plane, FCS 16 -> 10; its ADD layers (vpin_enc_add) have rounds of their own.
@@ -51,6 +54,7 @@ import vpin_amd  # noqa: E402
 from vpin_amd import net as VN  # noqa: E402
 import elgamal_model as EL  # noqa: E402
 import fcs_model as TM  # noqa: E402
+import maxpool_model as MM  # noqa: E402
 import net_model as NM  # noqa: E402
 import residual_model as RM  # noqa: E402
 
@@ -78,10 +82,10 @@ def stats(xs):
 
 
 def main():
-    assert VERSION in VN.VERSIONS + ("lenet5", "resnet"), "time_net.py A|B|C|D|E|lenet5|resnet"
+    assert VERSION in VN.VERSIONS + ("lenet5", "lenet5max", "resnet"), "time_net.py A|B|C|D|E|lenet5|lenet5max|resnet"
     print("network", VERSION, "seeds:", SEEDS, "sk: fixed", "nb = 2^%d" % NB_LOG, "reps =", REPS)
     image = NM.reference_image()
-    plain = RM.net_plaintext if VERSION == "resnet" else TM.net_plaintext if VERSION == "lenet5" else NM.plaintext
+    plain = RM.net_plaintext if VERSION == "resnet" else TM.net_plaintext if VERSION == "lenet5" else MM.net_plaintext if VERSION == "lenet5max" else NM.plaintext
     if VERSION == "resnet":
         model = RM.resnet_model_config()
         vs, acts = plain(model, image)
@@ -89,6 +93,14 @@ def main():
         assert all(abs(v) < giant << NB_LOG for r in vs for v in r), "the shifts do not keep a round inside the client's range"
         cfg = RM.resnet_device_config([giant] * RM.RESNET_ROUNDS, model)
         want = RM.net_counts(model)
+    elif VERSION == "lenet5max":
+        assert not CLIENTS and not WIRE_PROOFS, "lenet5max: in process, --wire or --batch"
+        model = MM.lenet5max_model_config()
+        vs, acts = MM.net_plaintext(model, image)
+        giant = max(1, (1 << 31) >> NB_LOG)  # the client's range per round: +-2^31
+        assert all(abs(v) < giant << NB_LOG for r in vs for v in r), "the shifts do not keep a round inside the client's range"
+        cfg = MM.device_config(model, [giant] * 5)
+        want = MM.net_counts(model)
     elif VERSION == "lenet5":
         model = TM.lenet5_model_config()
         vs, acts = TM.net_plaintext(model, image)
@@ -114,7 +126,7 @@ def main():
         ctx.close()
         return
     keys = [NM.net_key(i) for i in range(counts["prf_keys"])]
-    if VERSION == "lenet5":
+    if VERSION in ("lenet5", "lenet5max"):  # 2 * 6 + 2 * 16 keys of the two convolutions in front
         fcs = [l for l in model["layers"] if l["kind"] == "fcs"]
         assert all(TM.folded_fit_signed(l["w"], l["N"], keys[44 + 2 * j + i], model["prf_bytes"]) for j, l in enumerate(fcs) for i in range(2))
     elif VERSION == "resnet":  # its one FCS layer is the last: the last two keys
@@ -131,7 +143,7 @@ def main():
         return
     layers, rounds, whole, proved = [], [], [], []
     for rep in range(REPS + 1):
-        client = VN.Client(ctx, SK, 1 << NB_LOG, giants, client_rs)
+        client = VN.Client(ctx, SK, 1 << NB_LOG, giants, client_rs).set_pools(VN.pool_schedule(cfg))
         t0 = time.perf_counter()
         scores, values, trace = VN.infer(ctx, cfg, client, image, image_rs, keys, bias_rs)
         t1 = time.perf_counter()
@@ -162,7 +174,8 @@ def main():
         m, a = counts["layers"][i]
         print("%-34s %s" % ("layer %d (%s, %d + %d ops)" % (i, KINDS[l.kind], m, a), stats([x[i] for x in layers])))
         if l.has_round:
-            print("%-34s %s" % ("round %d (client, %d values)" % (rnd, counts["per_round"][rnd]), stats([x[i] for x in rounds])))
+            name = "round %d (client, %d values%s)" % (rnd, counts["per_round"][rnd], ", max pooled" if l.round_pool_k else "")
+            print("%-34s %s" % (name, stats([x[i] for x in rounds])))
             rnd += 1
     print("%-34s %s" % ("inference (image encryption in)", stats(whole)))
     if PROOFS:
@@ -179,14 +192,14 @@ def wire_mode(ctx, cfg, counts, giants, image, image_rs, keys, bias_rs, client_r
     parts = []  # per run, per slot (0: HELLO and INPUT, 1 + r: round r): pack, unpack, socket ms, both sides added
     stats = None
     for rep in range(REPS + 1):
-        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs)
+        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs).set_pools(VN.pool_schedule(cfg))
         t0 = time.perf_counter()
         scores, values, trace = VN.infer(ctx, cfg, client, image, image_rs, keys, bias_rs)
         t1 = time.perf_counter()
         tm = VN.timings(n)
         trace.free()
         client.free()
-        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs)
+        client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, client_rs).set_pools(VN.pool_schedule(cfg))
         a, b = socket.socketpair()
         ws, wc = W.Wire.from_fds(a.fileno(), a.fileno(), 600000), W.Wire.from_fds(b.fileno(), b.fileno(), 600000)
         out = {}
@@ -236,9 +249,10 @@ def wire_mode(ctx, cfg, counts, giants, image, image_rs, keys, bias_rs, client_r
     print("%-26s %9s %9s  %-28s %-28s %-28s %-28s %-28s" % ("", "B down", "B up", "round in process", "round over the wire", "pack", "unpack", "socket"))
     col = lambda k, slot: rng([p[slot][k] for p in parts])
     print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % ("HELLO and INPUT", 0, 2 * 24 + 32 + 64 * image.size, "", "", col(0, 0), col(1, 0), col(2, 0)))
+    replies = [o[0] * o[1] * o[2] for l, (_, _, o) in zip(cfg.layers, VN.shapes(cfg)) if l.has_round]  # the pooled count of a round that pools
     for r, (flags, _, cnt) in enumerate(sched):
         print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % (
-            "round %d (%d values)" % (r, cnt), 24 + 64 * cnt, 24 + (64 * cnt if flags & VN.REENCRYPT else 0), rng([x[r] for x in inproc]),
+            "round %d (%d values)" % (r, cnt), 24 + 64 * cnt, 24 + (64 * replies[r] if flags & VN.REENCRYPT else 0), rng([x[r] for x in inproc]),
             rng([x[r] for x in wired]), col(0, 1 + r), col(1, 1 + r), col(2, 1 + r)))
     tot = lambda k: [sum(p[slot][k] for slot in range(nr + 1)) for p in parts]
     print("%-26s %9d %9d  %-28s %-28s %-28s %-28s %-28s" % ("in all", stats[1]["bytes_sent"], stats[0]["bytes_sent"], rng(whole_in), rng(whole_wire),
@@ -268,7 +282,8 @@ def batch_mode(ctx, cfg, model, counts, giants, image, plain):
     image_rs = [EL.splitmix_scalars(SEEDS["image_r"] + 0x1000 * b, size) for b in range(top)]
     bias_rs = [EL.splitmix_scalars(SEEDS["bias_r"] + 0x1000 * b, r_bias) for b in range(top)]
     client_rs = [EL.splitmix_scalars(SEEDS["client_r"] + 0x1000 * b, r_client) for b in range(top)]
-    stage = [c for c, l in zip(counts["per_round"], [cfg.layers[i] for i in at]) if l.reencrypt]  # per image, per round that encrypts again
+    # per image, per round that encrypts again, what it encrypts: the pooled count of a round that pools
+    stage = [o[0] * o[1] * o[2] for l, (_, _, o) in zip(cfg.layers, VN.shapes(cfg)) if l.has_round and l.reencrypt]
     med = statistics.median
     rng = lambda xs, d=1: "%9.2f (%8.2f .. %8.2f)" % (med(xs) / d, min(xs) / d, max(xs) / d)
     summary = []
@@ -282,7 +297,7 @@ def batch_mode(ctx, cfg, model, counts, giants, image, plain):
         sched = VN.schedule(cfg, batch=B)
         layers, rounds, whole, wired_rounds, wired_whole = [], [], [], [], []
         for rep in range(REPS + 1):
-            client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue)
+            client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue).set_pools(VN.pool_schedule(cfg))
             t0 = time.perf_counter()
             scores, values, trace = VN.infer_batch(ctx, cfg, client, images[:B], image_rs[:B], keys[:B], bias_rs[:B])
             t1 = time.perf_counter()
@@ -297,7 +312,7 @@ def batch_mode(ctx, cfg, model, counts, giants, image, plain):
             trace.free()
             client.free()
             if WIRE:
-                client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue)
+                client = VN.Client(ctx2, SK, 1 << NB_LOG, giants, queue).set_pools(VN.pool_schedule(cfg))
                 a, b = socket.socketpair()
                 ws, wc = W.Wire.from_fds(a.fileno(), a.fileno(), 600000), W.Wire.from_fds(b.fileno(), b.fileno(), 600000)
                 out = {}
@@ -338,7 +353,8 @@ def batch_mode(ctx, cfg, model, counts, giants, image, plain):
             print("%-40s %-32s %12.3f" % ("layer %d (%s, %d + %d ops)" % (i, KINDS[l.kind], B * m, B * a), rng(xs), med(xs) / B))
             if l.has_round:
                 xs = [x[rnd] for x in rounds]
-                print("%-40s %-32s %12.3f" % ("round %d (client, %d values)" % (rnd, sched[rnd][2]), rng(xs), med(xs) / B))
+                name = "round %d (client, %d values%s)" % (rnd, sched[rnd][2], ", max pooled" if l.round_pool_k else "")
+                print("%-40s %-32s %12.3f" % (name, rng(xs), med(xs) / B))
                 if WIRE:
                     xs = [x[rnd] for x in wired_rounds]
                     print("%-40s %-32s %12.3f" % ("round %d over the wire" % rnd, rng(xs), med(xs) / B))

@@ -69,9 +69,20 @@ class NetLayer8(NetLayer):
 
 
 class NetLayer12(NetLayer8):
-    """the whole vpin_net_layer since ABI 12: behind NetLayer8's fields the tensor references, all zero for a layer as before.  This
-    is the struct the library reads: a vpin_net_cfg points to an array of these"""
+    """vpin_net_layer as ABI 12 had it: behind NetLayer8's fields the tensor references, all zero for a layer as before"""
     _fields_ = [("input_from", C.c_size_t), ("skip_from", C.c_size_t)]
+
+
+class NetLayer13(NetLayer12):
+    """the whole vpin_net_layer since ABI 13: behind NetLayer12's fields the max pooling inside the layer's round, all zero for a round
+    as before.  This is the struct the library reads: a vpin_net_cfg's `layers` points to an array of THESE (the field keeps ABI 12's
+    pointer type; vpin_amd.net casts), so an array of any shorter struct must not be handed over"""
+    _fields_ = [("round_pool_k", C.c_size_t), ("round_pool_stride", C.c_size_t)]
+
+
+class NetRoundPoolSpec(C.Structure):
+    """vpin_net_round_pool_spec of include/vpin_hip.h"""
+    _fields_ = [("H", C.c_size_t), ("W", C.c_size_t), ("k", C.c_size_t), ("stride", C.c_size_t)]
 
 
 class NetCfg(C.Structure):
@@ -272,10 +283,12 @@ def lib():
     L.vpin_e2_dlog_solve.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, vp]
     L.vpin_e2_decrypt.argtypes = [vp, vp, vp] + [vp] * 6 + [C.c_size_t, C.c_uint64, vp, vp]
     L.vpin_e2_client_round.argtypes = [vp] * 5 + [vp] * 6 + [C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, vp, vp, vp] + [vp] * 6
+    L.vpin_e2_client_round_pool.argtypes = ([vp] * 5 + [vp] * 6 + [C.c_size_t] * 5 + [C.c_uint64, C.c_int, C.c_int, C.c_int, vp, vp, vp] +
+                                            [vp] * 6)
     L.vpin_e2_plane_sums.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 3 + [vp, C.c_size_t, vp, vp, vp]
     L.vpin_e2_plane_sums_batch.argtypes = [vp, vp, vp, vp] + [C.c_size_t] * 4 + [vp, C.c_size_t, vp, vp, vp]
     L.vpin_lenet_cfg_default.argtypes = [C.POINTER(LenetCfg)]
-    L.vpin_lenet_as_net.argtypes = [C.POINTER(LenetCfg), C.POINTER(NetLayer12), vp, C.POINTER(NetCfg)]
+    L.vpin_lenet_as_net.argtypes = [C.POINTER(LenetCfg), C.POINTER(NetLayer13), vp, C.POINTER(NetCfg)]
     L.vpin_lenet_cfg_counts.argtypes = [C.POINTER(LenetCfg), C.POINTER(C.c_size_t)]
     L.vpin_lenet_infer.argtypes = [vp, C.POINTER(LenetCfg)] + [vp] * 6 + [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.vpin_lenet_trace_free.argtypes = [vp]
@@ -302,6 +315,9 @@ def lib():
                                           [vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(NetImageStatus), C.POINTER(vp)])
     L.vpin_net_round_images.argtypes = [C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_net_round_drop_images.argtypes = [vp, C.c_size_t, C.c_int, C.c_char_p]
+    L.vpin_net_round_pool.argtypes = [C.POINTER(C.c_size_t)]
+    L.vpin_net_client_set_pools.argtypes = [vp, C.POINTER(NetRoundPoolSpec), C.c_size_t]
+    L.vpin_net_client_act_count.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.vpin_net_trace_layer_images.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vpin_net_last_isolation.restype = None
     L.vpin_net_last_isolation.argtypes = [C.POINTER(C.c_uint64)]
@@ -1748,6 +1764,33 @@ class Context:
         if rs is None:
             return v, act, None, None
         return v, act, tuple(out[:3]), tuple(out[3:])
+
+    def e2_client_round_pool(self, table, base_g, base_h, sk, c1, c2, planes, H, W, k, stride, max_giant, relu=False, shift_bits=0, rs=None):
+        """vpin_e2_client_round_pool: e2_client_round over planes x H x W values with the maximum of every k x k window (at `stride`)
+        in front of the activation.  -> (v, act, c1_out, c2_out): v the planes * H * W raw decryptions, act and the ciphertexts
+        (None for rs = None) the planes * Ho * Wo pooled elements; rs: as many ints"""
+        x1, y1, f1 = self._points(*c1)
+        x2, y2, f2 = self._points(*c2)
+        n = x1.shape[0]
+        # a shape the library rejects (before it reads a buffer) reaches it with no outputs to write; any other must match the points
+        ok = planes > 0 and H > 0 and W > 0 and 0 < k <= min(H, W) and stride > 0 and planes * H * W < 2**30
+        m = planes * ((H - k) // stride + 1) * ((W - k) // stride + 1) if ok else 0
+        assert x2.shape[0] == n and (not ok or (n == planes * H * W and (rs is None or len(rs) == m)))
+        key = self._u256s([sk])
+        v, act = np.zeros(max(1, n), np.int64), np.zeros(max(1, m), np.int64)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        r, out = None, [None] * 6
+        if rs is not None:
+            r = self._u256s(rs) if len(rs) else np.zeros(32, np.uint8)
+            out = [np.zeros((max(1, m), 32), np.uint8), np.zeros((max(1, m), 32), np.uint8), np.zeros(max(1, m), np.uint8),
+                   np.zeros((max(1, m), 32), np.uint8), np.zeros((max(1, m), 32), np.uint8), np.zeros(max(1, m), np.uint8)]
+        rc = lib().vpin_e2_client_round_pool(self.h, table, base_g, base_h, p(key), p(x1), p(y1), p(f1), p(x2), p(y2), p(f2), planes, H, W, k,
+                                             stride, max_giant, int(bool(relu)), int(shift_bits), int(rs is not None), p(r), p(v), p(act),
+                                             *[p(a) for a in out])
+        _chk(rc, "vpin_e2_client_round_pool")
+        if rs is None:
+            return v[:n], act[:m], None, None
+        return v[:n], act[:m], tuple(a[:m] for a in out[:3]), tuple(a[:m] for a in out[3:])
 
     def e2_pack(self, x, y, inf=None):
         """vpin_e2_pack: points -> (n, 32) bytes, one packed point per row (x, the parity of y, an identity bit)"""

@@ -317,8 +317,9 @@ const char* vpin_last_error(void) { return g_last_error.c_str(); }
 // 3: vpin_net_layer grew n_out, w_mc, connect at its end (VPIN_NET_CONVMC); 4: VPIN_NET_FCS, CONVMC reads bias; 5: the wire (vpin_e2_pack,
 // vpin_wire_*, vpin_net_serve, vpin_net_client_run), new symbols only; 8: vpin_net_layer grew sum_table, sum_out, repeat, plane_order at
 // its end (all zero: as before), vpin_e2_plane_sums_batch, vpin_lenet_as_net, vpin_net_trace_image_layer; 12: vpin_enc_add, VPIN_NET_ADD,
-// vpin_net_layer grew input_from, skip_from at its end (all zero: as before)
-int vpin_abi_version(void) { return 12; }
+// vpin_net_layer grew input_from, skip_from at its end (all zero: as before); 13: vpin_e2_client_round_pool, VPIN_LENET_MAXPOOL,
+// vpin_net_round_pool, vpin_net_client_set_pools / _act_count, vpin_net_layer grew round_pool_k, round_pool_stride at its end (all zero: as before)
+int vpin_abi_version(void) { return 13; }
 
 static int ctx_create(int device, int priority, const uint32_t* cu_mask, uint32_t n_words, vpin_ctx** out);
 

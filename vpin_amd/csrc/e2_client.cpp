@@ -59,6 +59,31 @@ bool split_messages(const int64_t* msgs, size_t cnt, std::vector<uint8_t>* m, st
   return true;
 }
 
+// what vpin_e2_client_round and vpin_e2_client_round_pool reject alike, behind the entry point's name.  n_r: the scalars of r_le32
+int round_nulls(const char* who, const void* c, const void* t, const void* baseG, const void* baseH, const void* sk, const void* c1x, const void* c1y,
+                const void* c1inf, const void* c2x, const void* c2y, const void* c2inf, int reencrypt, const void* r, const void* v_out,
+                const void* act_out, const void* o1x, const void* o1y, const void* o1inf, const void* o2x, const void* o2y, const void* o2inf) {
+  if (!c || !t || !sk || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !v_out || !act_out ||
+      (reencrypt && (!baseG || !baseH || !r || !o1x || !o1y || !o1inf || !o2x || !o2y || !o2inf)))
+    return fail(VPIN_EINVAL, (std::string(who) + ": null argument").c_str());
+  return VPIN_OK;
+}
+
+int round_rules(const char* who, const vpin_e2_dlog* t, const uint8_t* sk_le32, uint64_t max_giant, int shift_bits, const uint8_t* r_le32, size_t n_r) {
+  const std::string name = std::string(who) + ": ";
+  if (shift_bits < 0 || shift_bits > 62) return fail(VPIN_EINVAL, (name + "shift_bits must be 0 (no shifting) or in 1 .. 62").c_str());
+  if (!walk_fits(max_giant, t->nb)) return fail(VPIN_EINVAL, (name + "max_giant * nb is past 2^62").c_str());
+  switch (check_scalars(sk_le32, 1, true)) {
+    case 1: return fail(VPIN_EINVAL, (name + "the key sk is not below the group order").c_str());
+    case 2: return fail(VPIN_EINVAL, (name + "the key sk is zero").c_str());
+  }
+  if (r_le32) switch (check_scalars(r_le32, n_r, true)) {
+    case 1: return fail(VPIN_EINVAL, (name + "a randomness r is not below the group order").c_str());
+    case 2: return fail(VPIN_EINVAL, (name + "a randomness r is zero").c_str());
+  }
+  return VPIN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -183,24 +208,15 @@ int vpin_e2_client_round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base*
                          const uint8_t* c2inf, size_t cnt, uint64_t max_giant, int relu, int shift_bits, int reencrypt, const uint8_t* r_le32,
                          int64_t* v_out, int64_t* act_out, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y,
                          uint8_t* o2inf) {
-  if (!c || !t || !sk_le32 || !c1x || !c1y || !c1inf || !c2x || !c2y || !c2inf || !v_out || !act_out)
-    return fail(VPIN_EINVAL, "vpin_e2_client_round: null argument");
-  if (reencrypt && (!baseG || !baseH || !r_le32 || !o1x || !o1y || !o1inf || !o2x || !o2y || !o2inf))
-    return fail(VPIN_EINVAL, "vpin_e2_client_round: null argument");
+  const char* who = "vpin_e2_client_round";
+  int rc = round_nulls(who, c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, reencrypt, r_le32, v_out, act_out, o1x, o1y, o1inf, o2x,
+                       o2y, o2inf);
+  if (rc) return rc;
   if (cnt == 0 || cnt >= ((size_t)1 << 30)) return fail(VPIN_EINVAL, "vpin_e2_client_round: cnt must be in 1 .. 2^30 - 1");
-  if (shift_bits < 0 || shift_bits > 62) return fail(VPIN_EINVAL, "vpin_e2_client_round: shift_bits must be 0 (no shifting) or in 1 .. 62");
-  if (!walk_fits(max_giant, t->nb)) return fail(VPIN_EINVAL, "vpin_e2_client_round: max_giant * nb is past 2^62");
-  switch (check_scalars(sk_le32, 1, true)) {
-    case 1: return fail(VPIN_EINVAL, "vpin_e2_client_round: the key sk is not below the group order");
-    case 2: return fail(VPIN_EINVAL, "vpin_e2_client_round: the key sk is zero");
-  }
-  if (reencrypt) switch (check_scalars(r_le32, cnt, true)) {
-    case 1: return fail(VPIN_EINVAL, "vpin_e2_client_round: a randomness r is not below the group order");
-    case 2: return fail(VPIN_EINVAL, "vpin_e2_client_round: a randomness r is zero");
-  }
+  if ((rc = round_rules(who, t, sk_le32, max_giant, shift_bits, reencrypt ? r_le32 : nullptr, cnt))) return rc;
   std::vector<uint8_t> bad(cnt, 0);
-  const int rc = cl::round(c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, max_giant, relu != 0, shift_bits,
-                           reencrypt ? r_le32 : nullptr, v_out, act_out, bad.data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
+  rc = cl::round(c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, max_giant, relu != 0, shift_bits,
+                 reencrypt ? r_le32 : nullptr, v_out, act_out, bad.data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
   if (rc) return rc;
   for (size_t i = 0; i < cnt; i++) {
     if (!bad[i]) continue;
@@ -209,6 +225,50 @@ int vpin_e2_client_round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base*
       snprintf(why, sizeof why, "vpin_e2_client_round: element %zu has no value within the walk's range", i);
     else
       snprintf(why, sizeof why, "vpin_e2_client_round: the activated value of element %zu (decrypted %lld) does not fit", i, (long long)v_out[i]);
+    return fail(VPIN_ESHAPE, why);
+  }
+  return VPIN_OK;
+}
+
+int vpin_e2_client_round_pool(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* baseG, const vpin_e2_base* baseH, const uint8_t sk_le32[32],
+                              const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y,
+                              const uint8_t* c2inf, size_t planes, size_t H, size_t W, size_t k, size_t stride, uint64_t max_giant, int relu,
+                              int shift_bits, int reencrypt, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* o1x, uint8_t* o1y,
+                              uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf) {
+  const char* who = "vpin_e2_client_round_pool";
+  int rc = round_nulls(who, c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, reencrypt, r_le32, v_out, act_out, o1x, o1y, o1inf, o2x,
+                       o2y, o2inf);
+  if (rc) return rc;
+  if (!planes || !H || !W) return fail(VPIN_EINVAL, "vpin_e2_client_round_pool: planes, H or W is zero");
+  if (!k || !stride) return fail(VPIN_EINVAL, "vpin_e2_client_round_pool: the window k or the stride is zero");
+  if (k > H || k > W) return fail(VPIN_EINVAL, "vpin_e2_client_round_pool: the window k does not fit the H x W plane");
+  if ((unsigned __int128)planes * H * W >= ((unsigned __int128)1 << 30) || planes >= ((size_t)1 << 30) || H >= ((size_t)1 << 30) ||
+      W >= ((size_t)1 << 30))
+    return fail(VPIN_EINVAL, "vpin_e2_client_round_pool: planes * H * W must be in 1 .. 2^30 - 1");
+  const cl::PoolShape pool{planes, H, W, k, stride};
+  const size_t cnt = planes * H * W, Ho = pool.Ho(), Wo = pool.Wo(), n_out = planes * Ho * Wo;
+  if ((rc = round_rules(who, t, sk_le32, max_giant, shift_bits, reencrypt ? r_le32 : nullptr, n_out))) return rc;
+  std::vector<uint8_t> bad(n_out, 0), found(cnt, 1);
+  rc = cl::round_pool(c, t, baseG, baseH, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, pool, max_giant, relu != 0, shift_bits,
+                      reencrypt ? r_le32 : nullptr, v_out, act_out, bad.data(), found.data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
+  if (rc) return rc;
+  char why[200];
+  // the maximum needs every value of its window: the first input element inside a window that has none, before any value's fit
+  for (size_t i = 0; i < cnt; i++) {
+    if (found[i]) continue;
+    const size_t y = i % (H * W) / W, x = i % W;
+    const size_t oy = y / stride < Ho ? y / stride : Ho - 1, ox = x / stride < Wo ? x / stride : Wo - 1;
+    if (y - oy * stride >= k || x - ox * stride >= k) continue;  // in no window: a dropped remainder, or a gap of stride > k
+    snprintf(why, sizeof why, "vpin_e2_client_round_pool: element %zu, inside a window, has no value within the walk's range", i);
+    return fail(VPIN_ESHAPE, why);
+  }
+  for (size_t o = 0; o < n_out; o++) {
+    if (!bad[o]) continue;
+    const size_t p = o / (Ho * Wo), at = p * H * W + (o % (Ho * Wo) / Wo) * stride * W + (o % Wo) * stride;
+    long long a = v_out[at];
+    for (size_t i = 0; i < k; i++)
+      for (size_t j = 0; j < k; j++) a = v_out[at + i * W + j] > a ? v_out[at + i * W + j] : a;
+    snprintf(why, sizeof why, "vpin_e2_client_round_pool: the activated value of output element %zu (the maximum decrypted, %lld) does not fit", o, a);
     return fail(VPIN_ESHAPE, why);
   }
   return VPIN_OK;

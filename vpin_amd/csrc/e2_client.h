@@ -63,6 +63,19 @@ int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_
           const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
           uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
           uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf);
+// the input of a round that pools: planes x H x W values, windows of k x k at a stride; a remainder of rows or columns is dropped
+struct PoolShape {
+  size_t planes, H, W, k, stride;
+  size_t Ho() const { return (H - k) / stride + 1; }
+  size_t Wo() const { return (W - k) / stride + 1; }
+};
+// round over pool.planes * H * W elements with the maximum of every window in front of the activation (e2_act_pool_kernel): act_out,
+// bad_out and the ciphertexts have planes * Ho * Wo elements, r_le32 as many scalars.  bad_out bit 0: an element of that window
+// has no value; found_out (cnt bytes) is then, and only then, read back from the walk
+int round_pool(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
+               const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const PoolShape& pool,
+               uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
+               uint8_t* found_out, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf);
 
 }  // namespace client
 }  // namespace vpin

@@ -16,6 +16,7 @@
 //                          is that one inversion, so a walk is as long as its deepest lane)
 //   e2_act_kernel          the client's activation between the walk and the next encryption: ReLU and the reference's
 //                          `shifting`, which goes through float32, one lane per element
+//   e2_act_pool_kernel     the same behind a maximum over k x k windows: one lane per output element (vpin_e2_client_round_pool)
 // Points come in through E2Points::load and results go out through E2Affine / e2_emit (enc_conv.h): e2_to_affine_kernel
 // normalises every output and the baby steps.  As in the layers' kernels the accumulators
 // are named registers: no per-lane arrays.
@@ -251,13 +252,11 @@ __global__ __launch_bounds__(kE2Block) void e2_dlog_walk_kernel(const fq* __rest
 // undefined there) or the message is not below 2^62 in magnitude
 constexpr uint8_t kActNotFound = 1, kActRange = 2;
 
-__global__ __launch_bounds__(kE2Block) void e2_act_kernel(const long long* __restrict__ v, const uint8_t* __restrict__ found, size_t n, int relu,
-                                                          int shift_bits, uint32_t* __restrict__ m, uint8_t* __restrict__ neg,
-                                                          long long* __restrict__ act, uint8_t* __restrict__ bad) {
-  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
-  if (i >= n) return;
-  long long a = v[i];
-  uint8_t b = found[i] ? 0 : kActNotFound;
+// everything after the value a to activate is known, for e2_act_kernel and e2_act_pool_kernel alike: ReLU, the shift, the range
+// check, and the message (magnitude and sign) of output element i.  b: kActNotFound or 0 as the caller found it.  The ONE copy of
+// the float32 rule
+__device__ __forceinline__ void act_emit(long long a, uint8_t b, size_t i, int relu, int shift_bits, uint32_t* __restrict__ m,
+                                         uint8_t* __restrict__ neg, long long* __restrict__ act, uint8_t* __restrict__ bad) {
   if (relu && a < 0) a = 0;
   if (shift_bits) {
     const float s = truncf(ldexpf(__ll2float_rn(a), 16 - shift_bits));  // |a| < 2^63, 16 - bits >= -47: the scale is exact
@@ -274,6 +273,39 @@ __global__ __launch_bounds__(kE2Block) void e2_act_kernel(const long long* __res
   neg[i] = a < 0 ? 1 : 0;
   act[i] = a;
   bad[i] = b;
+}
+
+__global__ __launch_bounds__(kE2Block) void e2_act_kernel(const long long* __restrict__ v, const uint8_t* __restrict__ found, size_t n, int relu,
+                                                          int shift_bits, uint32_t* __restrict__ m, uint8_t* __restrict__ neg,
+                                                          long long* __restrict__ act, uint8_t* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n) return;
+  act_emit(v[i], found[i] ? 0 : kActNotFound, i, relu, shift_bits, m, neg, act, bad);
+}
+
+// The activation of a round that pools by maximum: one lane per OUTPUT element (p, oy, ox) of planes x Ho x Wo, which reads the
+// k x k raw decryptions of its window in plane p of H x W and their found bytes; a is their maximum, kActNotFound when any of
+// them has no value, and the rest is act_emit.  A window never crosses a plane: oy * stride + k <= H and ox * stride + k <= W
+// by Ho = (H - k) / stride + 1 (the host's), so every index is below planes * H * W.  ReLU, the rounding to float32, the
+// power-of-two scale and the truncation are all non-decreasing, so act(max v) = max act(v)
+__global__ __launch_bounds__(kE2Block) void e2_act_pool_kernel(const long long* __restrict__ v, const uint8_t* __restrict__ found, size_t n_out,
+                                                               uint32_t H, uint32_t W, uint32_t Ho, uint32_t Wo, uint32_t k, uint32_t stride,
+                                                               int relu, int shift_bits, uint32_t* __restrict__ m, uint8_t* __restrict__ neg,
+                                                               long long* __restrict__ act, uint8_t* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * kE2Block + threadIdx.x;
+  if (i >= n_out) return;
+  const size_t per = (size_t)Ho * Wo, p = i / per, t = i % per;
+  const size_t base = p * H * W + (t / Wo) * stride * W + (t % Wo) * stride;
+  long long a = v[base];
+  uint8_t all = found[base];
+  for (uint32_t y = 0; y < k; y++)
+    for (uint32_t x = 0; x < k; x++) {
+      const size_t at = base + (size_t)y * W + x;
+      const long long c = v[at];
+      a = c > a ? c : a;
+      all &= found[at];
+    }
+  act_emit(a, all ? 0 : kActNotFound, i, relu, shift_bits, m, neg, act, bad);
 }
 
 // the generator G of E2, canonical little-endian
@@ -581,31 +613,64 @@ int decrypt(vpin_ctx* c, const vpin_e2_dlog* t, const uint8_t sk_le32[32], const
   return run_walk(c, t, d.m.X(), d.m.Y(), d.m.F(), cnt, max_giant, v_out, found_out);
 }
 
+// round and round_pool: pool = NULL activates element by element (cnt_out = cnt)
+static int run_round(vpin_ctx* c, const char* who, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32],
+                     const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf,
+                     size_t cnt, const PoolShape* pool, uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out,
+                     int64_t* act_out, uint8_t* bad_out, uint8_t* found_out, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x,
+                     uint8_t* o2y, uint8_t* o2inf) {
+  (void)hipSetDevice(c->device);
+  const size_t n_out = pool ? pool->planes * pool->Ho() * pool->Wo() : cnt;
+  DevBuf r(c), v(c), f(c), m(c), ng(c), act(c), bad(c);
+  if (v.alloc(cnt * 8) || f.alloc(cnt) || m.alloc(n_out * 32) || ng.alloc(n_out) || act.alloc(n_out * 8) || bad.alloc(n_out)) return VPIN_ENOMEM;
+  if (r_le32) {
+    if (r.alloc(n_out * 32)) return VPIN_ENOMEM;
+    VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, n_out * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  DecryptChain d(c);
+  int rc = d.run(c, who, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
+  if (!rc) rc = launch_walk(c, t, d.m.X(), d.m.Y(), d.m.F(), cnt, max_giant, v.p, f.p);
+  if (rc) return rc;
+  if (pool)
+    hipLaunchKernelGGL(e2_act_pool_kernel, dim3(blocks_of(n_out, kE2Block)), dim3(kE2Block), 0, c->stream, (const long long*)v.p,
+                       (const uint8_t*)f.p, n_out, (uint32_t)pool->H, (uint32_t)pool->W, (uint32_t)pool->Ho(), (uint32_t)pool->Wo(),
+                       (uint32_t)pool->k, (uint32_t)pool->stride, relu ? 1 : 0, shift_bits, (uint32_t*)m.p, (uint8_t*)ng.p, (long long*)act.p,
+                       (uint8_t*)bad.p);
+  else
+    hipLaunchKernelGGL(e2_act_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const long long*)v.p, (const uint8_t*)f.p, cnt,
+                       relu ? 1 : 0, shift_bits, (uint32_t*)m.p, (uint8_t*)ng.p, (long long*)act.p, (uint8_t*)bad.p);
+  VPIN_HIP_TRY(hipGetLastError());
+  EncryptChain e(c);
+  if (r_le32 && (rc = e.run(c, g, h, r.p, m.p, ng.p, n_out, o1x, o1y, o1inf, o2x, o2y, o2inf))) return rc;
+  VPIN_HIP_TRY(hipMemcpyAsync(v_out, v.p, cnt * 8, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(act_out, act.p, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipMemcpyAsync(bad_out, bad.p, n_out, hipMemcpyDeviceToHost, c->stream));
+  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (found_out) {  // the failure path of a pooled round: which input element it was
+    bool any = false;
+    for (size_t i = 0; i < n_out && !any; i++) any = (bad_out[i] & 1) != 0;
+    if (any) {
+      VPIN_HIP_TRY(hipMemcpyAsync(found_out, f.p, cnt, hipMemcpyDeviceToHost, c->stream));
+      VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+  }
+  return VPIN_OK;
+}
+
 int round(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
           const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt,
           uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
           uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf) {
-  (void)hipSetDevice(c->device);
-  DevBuf r(c), v(c), f(c), m(c), ng(c), act(c), bad(c);
-  if (v.alloc(cnt * 8) || f.alloc(cnt) || m.alloc(cnt * 32) || ng.alloc(cnt) || act.alloc(cnt * 8) || bad.alloc(cnt)) return VPIN_ENOMEM;
-  if (r_le32) {
-    if (r.alloc(cnt * 32)) return VPIN_ENOMEM;
-    VPIN_HIP_TRY(hipMemcpyAsync(r.p, r_le32, cnt * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  DecryptChain d(c);
-  int rc = d.run(c, "vpin_e2_client_round", sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt);
-  if (!rc) rc = launch_walk(c, t, d.m.X(), d.m.Y(), d.m.F(), cnt, max_giant, v.p, f.p);
-  if (rc) return rc;
-  hipLaunchKernelGGL(e2_act_kernel, dim3(blocks_of(cnt, kE2Block)), dim3(kE2Block), 0, c->stream, (const long long*)v.p, (const uint8_t*)f.p, cnt,
-                     relu ? 1 : 0, shift_bits, (uint32_t*)m.p, (uint8_t*)ng.p, (long long*)act.p, (uint8_t*)bad.p);
-  VPIN_HIP_TRY(hipGetLastError());
-  EncryptChain e(c);
-  if (r_le32 && (rc = e.run(c, g, h, r.p, m.p, ng.p, cnt, o1x, o1y, o1inf, o2x, o2y, o2inf))) return rc;
-  VPIN_HIP_TRY(hipMemcpyAsync(v_out, v.p, cnt * 8, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(act_out, act.p, cnt * 8, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipMemcpyAsync(bad_out, bad.p, cnt, hipMemcpyDeviceToHost, c->stream));
-  VPIN_HIP_TRY(hipStreamSynchronize(c->stream));
-  return VPIN_OK;
+  return run_round(c, "vpin_e2_client_round", t, g, h, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, nullptr, max_giant, relu, shift_bits, r_le32,
+                   v_out, act_out, bad_out, nullptr, o1x, o1y, o1inf, o2x, o2y, o2inf);
+}
+
+int round_pool(vpin_ctx* c, const vpin_e2_dlog* t, const vpin_e2_base* g, const vpin_e2_base* h, const uint8_t sk_le32[32], const uint8_t* c1x,
+               const uint8_t* c1y, const uint8_t* c1inf, const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, const PoolShape& pool,
+               uint64_t max_giant, bool relu, int shift_bits, const uint8_t* r_le32, int64_t* v_out, int64_t* act_out, uint8_t* bad_out,
+               uint8_t* found_out, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf, uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf) {
+  return run_round(c, "vpin_e2_client_round_pool", t, g, h, sk_le32, c1x, c1y, c1inf, c2x, c2y, c2inf, pool.planes * pool.H * pool.W, &pool,
+                   max_giant, relu, shift_bits, r_le32, v_out, act_out, bad_out, found_out, o1x, o1y, o1inf, o2x, o2y, o2inf);
 }
 
 }  // namespace client

@@ -26,6 +26,7 @@ struct vpin_net_client {
   std::vector<uint8_t> r;           // the queue of encryption randomness, 32 bytes each
   size_t r_pos = 0;
   std::vector<std::vector<int64_t>> v, act;
+  std::vector<vpin_net_round_pool_spec> pools;  // per round, the client's own; all zero: the round does not pool
 };
 
 extern "C" {
@@ -49,6 +50,7 @@ int vpin_net_client_create(vpin_ctx* c, const uint8_t sk_le32[32], uint64_t nb, 
   memcpy(cl->sk, sk_le32, 32);
   cl->max_giant.assign(max_giant, max_giant + n_rounds);
   cl->v.resize(n_rounds); cl->act.resize(n_rounds);
+  cl->pools.assign(n_rounds, vpin_net_round_pool_spec{0, 0, 0, 0});
   if (n_r) cl->r.assign(r_le32, r_le32 + 32 * n_r);
   uint8_t hx[32], hy[32], hinf = 0;
   int rc = vpin_e2_base_create(c, nullptr, nullptr, &cl->g);
@@ -79,19 +81,65 @@ int vpin_net_client_values(const vpin_net_client* cl, size_t round, const int64_
   return VPIN_OK;
 }
 
+int vpin_net_client_act_count(const vpin_net_client* cl, size_t round, size_t* n) {
+  if (!cl || !n || round >= cl->act.size()) return fail(VPIN_EINVAL, "vpin_net_client_act_count: null argument or no such round");
+  *n = cl->act[round].size();
+  return VPIN_OK;
+}
+
+int vpin_net_client_set_pools(vpin_net_client* cl, const vpin_net_round_pool_spec* pools, size_t n_rounds) {
+  if (!cl || !pools) return fail(VPIN_EINVAL, "vpin_net_client_set_pools: null argument");
+  if (n_rounds != cl->pools.size()) return fail(VPIN_EINVAL, "vpin_net_client_set_pools: n_rounds is not the rounds the client was made for");
+  for (size_t i = 0; i < n_rounds; i++) {
+    const vpin_net_round_pool_spec& p = pools[i];
+    if (!p.H && !p.W && !p.k && !p.stride) continue;
+    if (!p.H || !p.W || !p.k || !p.stride || p.k > p.H || p.k > p.W || p.H >= ((size_t)1 << 30) || p.W >= ((size_t)1 << 30))
+      return fail(VPIN_EINVAL, ("vpin_net_client_set_pools: round " + std::to_string(i) +
+                                ": H, W, k and stride are neither all zero nor a window that fits its plane").c_str());
+  }
+  cl->pools.assign(pools, pools + n_rounds);
+  return VPIN_OK;
+}
+
 int vpin_net_client_round(void* user, int round, int flags, int shift_bits, const uint8_t* c1x, const uint8_t* c1y, const uint8_t* c1inf,
                           const uint8_t* c2x, const uint8_t* c2y, const uint8_t* c2inf, size_t cnt, uint8_t* o1x, uint8_t* o1y, uint8_t* o1inf,
                           uint8_t* o2x, uint8_t* o2y, uint8_t* o2inf) {
   vpin_net_client* cl = (vpin_net_client*)user;
   if (!cl || round < 0 || (size_t)round >= cl->v.size()) return fail(VPIN_EINVAL, "vpin_net_client_round: null client or a round it was not made for");
   const bool re = (flags & VPIN_LENET_REENCRYPT) != 0;
-  if (re && cl->r.size() / 32 - cl->r_pos < cnt) return fail(VPIN_EINVAL, "vpin_net_client_round: the queue of randomness r is used up");
+  // the pooling schedule is the client's: it does not pool, or leave it, because a server says so.  Before anything is decrypted
+  const vpin_net_round_pool_spec& pool = cl->pools[round];
+  if (((flags & VPIN_LENET_MAXPOOL) != 0) != (pool.k != 0)) {
+    cl->v[round].clear(); cl->act[round].clear();
+    char why[240];
+    if (pool.k)
+      snprintf(why, sizeof why, "vpin_net_client_round: round %d: the server asks for a round without max pooling, the client's schedule pools "
+               "%zu x %zu planes by k = %zu, stride = %zu", round, pool.H, pool.W, pool.k, pool.stride);
+    else
+      snprintf(why, sizeof why, "vpin_net_client_round: round %d: the server asks for max pooling (flags %d), the client's schedule has none in this round",
+               round, flags);
+    return fail(VPIN_ESHAPE, why);
+  }
+  if (pool.k && (cnt == 0 || cnt % (pool.H * pool.W))) {
+    cl->v[round].clear(); cl->act[round].clear();
+    char why[240];
+    snprintf(why, sizeof why, "vpin_net_client_round: round %d: the server sends %zu ciphertexts, the client's schedule pools planes of %zu x %zu = %zu",
+             round, cnt, pool.H, pool.W, pool.H * pool.W);
+    return fail(VPIN_ESHAPE, why);
+  }
+  const size_t planes = pool.k ? cnt / (pool.H * pool.W) : 0;
+  const size_t n_out = pool.k ? planes * ((pool.H - pool.k) / pool.stride + 1) * ((pool.W - pool.k) / pool.stride + 1) : cnt;
+  if (re && cl->r.size() / 32 - cl->r_pos < n_out) return fail(VPIN_EINVAL, "vpin_net_client_round: the queue of randomness r is used up");
   cl->v[round].assign(cnt, 0);
-  cl->act[round].assign(cnt, 0);
-  const int rc = vpin_e2_client_round(cl->ctx, cl->dlog, cl->g, cl->h, cl->sk, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, cl->max_giant[round],
-                                      (flags & VPIN_LENET_RELU) != 0, shift_bits, re, re ? &cl->r[32 * cl->r_pos] : nullptr,
-                                      cl->v[round].data(), cl->act[round].data(), o1x, o1y, o1inf, o2x, o2y, o2inf);
-  if (re && rc == VPIN_OK) cl->r_pos += cnt;  // a failed round consumes nothing: the client can be used again
+  cl->act[round].assign(n_out, 0);
+  const uint8_t* r = re ? &cl->r[32 * cl->r_pos] : nullptr;
+  const int rc = pool.k ? vpin_e2_client_round_pool(cl->ctx, cl->dlog, cl->g, cl->h, cl->sk, c1x, c1y, c1inf, c2x, c2y, c2inf, planes, pool.H, pool.W,
+                                                    pool.k, pool.stride, cl->max_giant[round], (flags & VPIN_LENET_RELU) != 0, shift_bits, re, r,
+                                                    cl->v[round].data(), cl->act[round].data(), o1x, o1y, o1inf, o2x, o2y, o2inf)
+                        : vpin_e2_client_round(cl->ctx, cl->dlog, cl->g, cl->h, cl->sk, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, cl->max_giant[round],
+                                               (flags & VPIN_LENET_RELU) != 0, shift_bits, re, r, cl->v[round].data(), cl->act[round].data(), o1x,
+                                               o1y, o1inf, o2x, o2y, o2inf);
+  if (re && rc == VPIN_OK) cl->r_pos += n_out;  // a failed round consumes nothing: the client can be used again
   return rc;
 }
 
@@ -178,11 +226,12 @@ int vpin_net_client_run(vpin_net_client* cl, vpin_wire* w, const int64_t* image,
                                re ? o1x.data() : nullptr, re ? o1y.data() : nullptr, re ? o1f.data() : nullptr, re ? o2x.data() : nullptr,
                                re ? o2y.data() : nullptr, re ? o2f.data() : nullptr);
     if (rc) return failed(rc, why, true);
+    const size_t n_out = cl->act[done].size();  // cnt, or the pooled count of a round that pools
     p.clear();
-    if (re && (rc = wr::pack_pair_timed(w, slot, cl->ctx, o1x.data(), o1y.data(), o1f.data(), o2x.data(), o2y.data(), o2f.data(), cnt, &p)))
+    if (re && (rc = wr::pack_pair_timed(w, slot, cl->ctx, o1x.data(), o1y.data(), o1f.data(), o2x.data(), o2y.data(), o2f.data(), n_out, &p)))
       return failed(rc, why, true);
     memset(&h, 0, sizeof h);
-    h.type = VPIN_WIRE_REPLY; h.round = (uint32_t)done; h.cnt = re ? (uint32_t)cnt : 0; h.payload_len = re ? 64 * (uint64_t)cnt : 0;
+    h.type = VPIN_WIRE_REPLY; h.round = (uint32_t)done; h.cnt = re ? (uint32_t)n_out : 0; h.payload_len = re ? 64 * (uint64_t)n_out : 0;
     if ((rc = wr::send_frame_timed(w, slot, h, p.data()))) return failed(rc, why, false);
     done++;
   }

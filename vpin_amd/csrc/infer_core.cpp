@@ -125,23 +125,27 @@ struct Dropped {
 struct RoundState {
   const Slots* live;
   bool isolated;
+  size_t pool[5];  // vpin_net_round_pool
   std::vector<Dropped> dropped;
 };
 thread_local RoundState* g_round = nullptr;
 
 // one interaction with the client: the step's output goes out, the activated and re-encrypted values come back into c1, c2.
-// *dropped: the images the callback dropped (an isolated run), in the order it named them; they are still in c1 and c2
-int interact(const Call& a, const Slots& live, const Step& s, Pts* c1, Pts* c2, std::vector<Dropped>* dropped) {
-  const size_t n = c1->n();
+// *dropped: the images the callback dropped (an isolated run), in the order it named them; they are still in c1 and c2.
+// C, H, W: the shape of what goes out per image; of a round that pools they are the pooled shape afterwards, and so are c1, c2
+int interact(const Call& a, const Slots& live, const Step& s, Pts* c1, Pts* c2, size_t C, size_t* H, size_t* W,
+             std::vector<Dropped>* dropped) {
+  const size_t n = c1->n(), k = s.round_pool_k, stride = s.round_pool_stride;
+  const size_t Ho = k ? (*H - k) / stride + 1 : *H, Wo = k ? (*W - k) / stride + 1 : *W;
   Pts a1, a2;
   uint8_t* o[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // no outputs when nothing is encrypted again
   if (s.reencrypt) {
-    a1.resize(n); a2.resize(n);
+    a1.resize(live.n() * C * Ho * Wo); a2.resize(live.n() * C * Ho * Wo);
     o[0] = a1.x.data(); o[1] = a1.y.data(); o[2] = a1.inf.data(); o[3] = a2.x.data(); o[4] = a2.y.data(); o[5] = a2.inf.data();
   }
-  const int flags = (s.relu ? VPIN_LENET_RELU : 0) | (s.reencrypt ? VPIN_LENET_REENCRYPT : 0);
+  const int flags = (s.relu ? VPIN_LENET_RELU : 0) | (s.reencrypt ? VPIN_LENET_REENCRYPT : 0) | (k ? VPIN_LENET_MAXPOOL : 0);
   set_last_error_text("");  // a foreign callback may fail without a text of its own: no stale one is quoted then
-  RoundState state{&live, a.iso != nullptr, {}};
+  RoundState state{&live, a.iso != nullptr, {live.n() * C, *H, *W, k, stride}, {}};
   RoundState* const outer = g_round;  // a callback that runs an inference of its own gets its own
   g_round = &state;
   const int rc = a.round_fn(a.user, s.round, flags, s.shift_bits, c1->x.data(), c1->y.data(), c1->inf.data(), c2->x.data(), c2->y.data(),
@@ -149,6 +153,7 @@ int interact(const Call& a, const Slots& live, const Step& s, Pts* c1, Pts* c2, 
   g_round = outer;
   if (rc && !*vpin_last_error()) set_last_error_text("the round callback failed");
   if (!rc && s.reencrypt) { std::swap(*c1, a1); std::swap(*c2, a2); }
+  if (!rc) { *H = Ho; *W = Wo; }
   if (!rc) *dropped = std::move(state.dropped);
   return rc;
 }
@@ -336,7 +341,7 @@ int run(const Call& a, const std::vector<Step>& steps, Result* out) {
     C = tr->P / (2 * live.n()); H = tr->oh; W = tr->ow;
     if (!s.has_round) continue;
     std::vector<Dropped> dropped;
-    rc = interact(a, live, s, &c1, &c2, &dropped);
+    rc = interact(a, live, s, &c1, &c2, C, &H, &W, &dropped);
     out->round_ms[i] = 1e3 * lap();
     if (rc) return named(rc, s.round_name);
     if (dropped.empty()) continue;
@@ -366,6 +371,14 @@ int vpin_net_round_images(const uint32_t** slots, size_t* n) {
   if (!g_round) return fail(VPIN_EINVAL, "vpin_net_round_images: no round callback is running on this thread");
   *slots = g_round->live->live.data();
   *n = g_round->live->n();
+  return VPIN_OK;
+}
+
+int vpin_net_round_pool(size_t out[5]) {
+  using namespace vpin::infer;
+  if (!out) return fail(VPIN_EINVAL, "vpin_net_round_pool: null argument");
+  if (!g_round) return fail(VPIN_EINVAL, "vpin_net_round_pool: no round callback is running on this thread");
+  for (int i = 0; i < 5; i++) out[i] = g_round->pool[i];
   return VPIN_OK;
 }
 

@@ -48,6 +48,7 @@ struct Step {
   // the client's round after the call
   bool has_round = false;
   int round = 0, relu = 0, shift_bits = 0, reencrypt = 1;
+  size_t round_pool_k = 0, round_pool_stride = 0;  // both non-zero: the client pools by maximum inside the round (VPIN_LENET_MAXPOOL)
   std::string round_name;
 };
 

@@ -32,11 +32,12 @@ const char* kind_name(int kind) {
 
 // per layer what it consumes and leaves; the walk that vpin_net_cfg_counts and vpin_net_infer share
 struct LayerPlan {
-  size_t oC, oH, oW;     // what goes out
+  size_t oC, oH, oW;     // the tensor after the layer and its round: what the next layer and every reference see
   size_t sumC, inC;      // the planes per half that reach the channel sums, and the layer call behind sums and repeat
   size_t mult, add, keys, bias_r;
   int round;             // index of the round after the layer, or -1
   size_t iH, iW;         // the plane that reaches the layer (input_from followed)
+  size_t dH, dW;         // the plane the layer call leaves and its round decrypts: oH x oW unless the round pools
 };
 
 constexpr size_t kMaxLayers = 4096, kMaxSide = 4096, kMaxPlanes = 16384;
@@ -68,7 +69,7 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
     if (l.skip_from && !tensor_of(l.skip_from, i, &skip_t))
       return fail(VPIN_EINVAL, (at + "skip_from = " + std::to_string(l.skip_from) + " names the layer itself or a later one").c_str());
     if (l.input_from) shape_of(in_t, &C, &H, &W);
-    LayerPlan p{C, H, W, C, C, 0, 0, 0, 0, -1, H, W};
+    LayerPlan p{C, H, W, C, C, 0, 0, 0, 0, -1, H, W, 0, 0};
     const char* fit = "vpin_net: a window does not fit its plane";
     if (l.kind == VPIN_NET_ADD) {  // before the rules of the other kinds: an addition layer's own texts
       if (!l.skip_from) return fail(VPIN_EINVAL, (at + "an addition layer has no skip_from").c_str());
@@ -161,6 +162,18 @@ int plan(const vpin_net_cfg* g, bool weights, std::vector<LayerPlan>* out) {
       if (!l.reencrypt && i + 1 != g->n_layers) return fail(VPIN_EINVAL, "vpin_net: only the last layer's round may leave out the re-encryption");
       p.round = rounds++;
     }
+    p.dH = p.oH; p.dW = p.oW;
+    if (l.round_pool_k || l.round_pool_stride) {  // the client pools inside the round: the tensor that goes on is C x Ho x Wo
+      if (!l.has_round) return fail(VPIN_EINVAL, (at + "round_pool_k or round_pool_stride on a layer without a round").c_str());
+      if (!l.round_pool_k || !l.round_pool_stride)
+        return fail(VPIN_EINVAL, (at + "round_pool_k = " + std::to_string(l.round_pool_k) + " beside round_pool_stride = " +
+                                  std::to_string(l.round_pool_stride) + ": one of the two is zero").c_str());
+      if (l.round_pool_k > p.dH || l.round_pool_k > p.dW)
+        return fail(VPIN_EINVAL, (at + "the round's pooling window " + std::to_string(l.round_pool_k) + " does not fit the layer's " +
+                                  std::to_string(p.dH) + " x " + std::to_string(p.dW) + " output").c_str());
+      p.oH = (p.dH - l.round_pool_k) / l.round_pool_stride + 1;
+      p.oW = (p.dW - l.round_pool_k) / l.round_pool_stride + 1;
+    }
     C = p.oC; H = p.oH; W = p.oW;
     out->push_back(p);
   }
@@ -200,7 +213,7 @@ int fits(const char* who, const vpin_net_cfg* g, const std::vector<LayerPlan>& p
       return fail(VPIN_EINVAL, (name + "2 B * C = " + std::to_string(planes) + " planes are more than the 65535 a layer call takes").c_str());
     if (fc && 2 * B * l.K >= ((size_t)1 << 31))
       return fail(VPIN_EINVAL, (name + "2 B * K = " + std::to_string(2 * B * l.K) + " chain terms are 2^31 or more").c_str());
-    if (2 * B * pl[i].oC * pl[i].oH * pl[i].oW >= ((size_t)1 << 31))
+    if (2 * B * pl[i].oC * pl[i].dH * pl[i].dW >= ((size_t)1 << 31))
       return fail(VPIN_EINVAL, (name + "the outputs of all images are 2^31 or more").c_str());
   }
   return VPIN_OK;
@@ -271,6 +284,7 @@ int infer(const char* who, vpin_ctx* c, const vpin_net_cfg* g, size_t B, const u
     s.name = "layer " + std::to_string(i) + " (" + kind_name(l.kind) + ")";
     s.has_round = pl[i].round >= 0;
     s.round = pl[i].round; s.relu = l.relu; s.shift_bits = l.shift_bits; s.reencrypt = l.reencrypt;
+    s.round_pool_k = l.round_pool_k; s.round_pool_stride = l.round_pool_stride;
     s.round_name = "round " + std::to_string(pl[i].round);
   }
   std::unique_ptr<vpin_net_trace> t(new (std::nothrow) vpin_net_trace());
@@ -337,7 +351,7 @@ int vpin_net_cfg_counts(const vpin_net_cfg* g, size_t* out, size_t cap) {
   if (cap < 8 + 3 * pl.size()) return fail(VPIN_EINVAL, "vpin_net_cfg_counts: out holds fewer than 8 + 3 * n_layers values");
   size_t mult = 0, add = 0, dec = 0, enc = g->C * g->H * g->W, keys = 0, bias_r = 0, rounds = 0;
   for (size_t i = 0; i < pl.size(); i++) {
-    const size_t n_out = pl[i].oC * pl[i].oH * pl[i].oW, d = pl[i].round >= 0 ? n_out : 0;
+    const size_t n_out = pl[i].oC * pl[i].oH * pl[i].oW, d = pl[i].round >= 0 ? pl[i].oC * pl[i].dH * pl[i].dW : 0;
     out[8 + 3 * i] = pl[i].mult; out[9 + 3 * i] = pl[i].add; out[10 + 3 * i] = d;
     mult += pl[i].mult; add += pl[i].add; dec += d; keys += pl[i].keys; bias_r += pl[i].bias_r;
     if (pl[i].round >= 0) { rounds++; if (g->layers[i].reencrypt) enc += n_out; }

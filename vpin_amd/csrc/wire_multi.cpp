@@ -229,6 +229,10 @@ int vpin_net_server_create(vpin_ctx* c, const vpin_net_cfg* cfg, size_t max_batc
   if (!cfg->layers[cfg->n_layers - 1].has_round)
     return fail(VPIN_EINVAL, "vpin_net_server_create: the last layer has no round: its result would never reach the clients");
   if (!max_batch || max_batch > VPIN_NET_MAX_BATCH) return fail(VPIN_EINVAL, "vpin_net_server_create: max_batch is outside 1 .. VPIN_NET_MAX_BATCH");
+  // a dropped client's images are copied from a round's input to its output at ONE per-image size (compact, above)
+  for (size_t i = 0; i < cfg->n_layers; i++)
+    if (cfg->layers[i].round_pool_k)
+      return fail(VPIN_EINVAL, ("vpin_net_server_create: layer " + std::to_string(i) + ": a round with max pooling is not served to several clients yet").c_str());
   std::unique_ptr<vpin_net_server> s(new (std::nothrow) vpin_net_server());
   if (!s) return VPIN_ENOMEM;
   s->c = c; s->cfg = cfg; s->max_batch = max_batch;

@@ -166,6 +166,15 @@ int vpin_wire_round(void* user, int round, int flags, int shift_bits, const uint
   const size_t slot = 1 + (size_t)round;
   char why[200];
   std::vector<uint8_t> p;
+  size_t n_reply = cnt;  // what REPLY must hold: of a round that pools, the pooled count (the driver's own shape, never the peer's)
+  if (flags & VPIN_LENET_MAXPOOL) {
+    size_t pool[5];
+    int bad = vpin_net_round_pool(pool);
+    if (!bad && (!pool[3] || pool[0] * pool[1] * pool[2] != cnt))
+      bad = fail(VPIN_EINVAL, "vpin_wire_round: VPIN_LENET_MAXPOOL in a round whose driver names no pooling shape over cnt values");
+    if (bad) return bad;
+    n_reply = pool[0] * ((pool[1] - pool[3]) / pool[4] + 1) * ((pool[2] - pool[3]) / pool[4] + 1);
+  }
   int rc = pack_pair_timed(w, slot, w->ctx, c1x, c1y, c1inf, c2x, c2y, c2inf, cnt, &p);
   if (rc) return named(rc, who);
   vpin_wire_header h;
@@ -183,13 +192,13 @@ int vpin_wire_round(void* user, int round, int flags, int shift_bits, const uint
     snprintf(why, sizeof why, "%s: round %d: the reply is for round %u", who, round, (unsigned)h.round);
     return fail(VPIN_ESHAPE, why);
   }
-  if (h.cnt != (re ? cnt : 0)) {
-    snprintf(why, sizeof why, "%s: round %d: the reply holds %u ciphertexts, the round asked for %zu", who, round, (unsigned)h.cnt, re ? cnt : (size_t)0);
+  if (h.cnt != (re ? n_reply : 0)) {
+    snprintf(why, sizeof why, "%s: round %d: the reply holds %u ciphertexts, the round asked for %zu", who, round, (unsigned)h.cnt, re ? n_reply : (size_t)0);
     return fail(VPIN_ESHAPE, why);
   }
   if ((rc = recv_payload_timed(w, slot, h, &p))) return named(rc, who);
   if (!re) return VPIN_OK;
-  if ((rc = unpack_pair_timed(w, slot, w->ctx, p, cnt, o1x, o1y, o1inf, o2x, o2y, o2inf))) {
+  if ((rc = unpack_pair_timed(w, slot, w->ctx, p, n_reply, o1x, o1y, o1inf, o2x, o2y, o2inf))) {
     snprintf(why, sizeof why, "%s: round %d: the reply (c1, then c2)", who, round);
     return named(rc, why);
   }

@@ -5,9 +5,9 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, ProofExpect, VpinError, WireRoundSpec, _chk, lib
+from .capi import LENET_ROUND_FN, ConvTrace, DevInstance, NetRoundPoolSpec, ProofExpect, VpinError, WireRoundSpec, _chk, lib
 
-RELU, REENCRYPT = 1, 2
+RELU, REENCRYPT, MAXPOOL = 1, 2, 4
 
 
 def min_max_scaling(image):
@@ -82,11 +82,21 @@ class Client:
         return out
 
     def values(self, rnd):
-        """(v, act) of round first_round .. first_round + n_rounds - 1 as int64 arrays"""
-        v, a, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        """(v, act) of round first_round .. first_round + n_rounds - 1 as int64 arrays; act is the shorter one of a round that pooled"""
+        v, a, n, m = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
         _chk(lib().vpin_net_client_values(self.h, rnd - self.first_round, C.byref(v), C.byref(a), C.byref(n)), "vpin_net_client_values")
-        get = lambda p: np.frombuffer((C.c_int64 * n.value).from_address(p.value), dtype=np.int64).copy() if n.value else np.zeros(0, np.int64)
-        return get(v), get(a)
+        _chk(lib().vpin_net_client_act_count(self.h, rnd - self.first_round, C.byref(m)), "vpin_net_client_act_count")
+        get = lambda p, k: np.frombuffer((C.c_int64 * k).from_address(p.value), dtype=np.int64).copy() if k else np.zeros(0, np.int64)
+        return get(v, n.value), get(a, m.value)
+
+    def set_pools(self, pools):
+        """vpin_net_client_set_pools: the client's own pooling schedule, per round (H, W, k, stride), all zero for a round that
+        does not pool (net.pool_schedule).  A round whose VPIN_LENET_MAXPOOL flag disagrees with it is refused before anything
+        is decrypted"""
+        assert len(pools) == self.n_rounds
+        spec = (NetRoundPoolSpec * max(1, len(pools)))(*[NetRoundPoolSpec(*[int(v) for v in p]) for p in pools])
+        _chk(lib().vpin_net_client_set_pools(self.h, spec, len(pools)), "vpin_net_client_set_pools")
+        return self
 
     def free(self):
         if self.h:
@@ -106,7 +116,13 @@ def python_round(fn):
             c2 = (view(x2, 32 * cnt).reshape(cnt, 32).copy(), view(y2, 32 * cnt).reshape(cnt, 32).copy(), view(f2, cnt).copy())
             out = fn(rnd, bool(flags & RELU), bool(flags & REENCRYPT), bits, c1, c2)
             if flags & REENCRYPT:
-                for dst, src, n in zip((ox1, oy1, of1, ox2, oy2, of2), tuple(out[0]) + tuple(out[1]), (32 * cnt, 32 * cnt, cnt) * 2):
+                m = cnt
+                if flags & MAXPOOL:  # a round that pools takes back the pooled count (vpin_net_round_pool)
+                    shape = (C.c_size_t * 5)()
+                    _chk(lib().vpin_net_round_pool(shape), "vpin_net_round_pool")
+                    planes, H, W, k, stride = (int(v) for v in shape)
+                    m = planes * ((H - k) // stride + 1) * ((W - k) // stride + 1)
+                for dst, src, n in zip((ox1, oy1, of1, ox2, oy2, of2), tuple(out[0]) + tuple(out[1]), (32 * m, 32 * m, m) * 2):
                     C.memmove(dst, np.ascontiguousarray(src, dtype=np.uint8).ctypes.data, n)
             return 0
         except Exception as e:  # noqa: BLE001

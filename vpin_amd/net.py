@@ -17,10 +17,11 @@ import os
 import numpy as np
 
 from . import inference
-from .capi import NetCfg, NetImageStatus, NetLayer12 as NetLayer, NetPeerStatus, VpinError, _chk, lib
+from .capi import NetCfg, NetImageStatus, NetLayer12, NetLayer13 as NetLayer, NetPeerStatus, NetRoundPoolSpec, VpinError, _chk, lib
 from .inference import RELU, REENCRYPT, Client, fixed_point, min_max_scaling, preprocess, python_round  # noqa: F401  (one client protocol)
 
 CONV, POOL, FC, CONVMC, FCS, ADD = 0, 1, 2, 3, 4, 5
+MAXPOOL = 4  # VPIN_LENET_MAXPOOL, beside RELU and REENCRYPT in a round's flags
 FROM_INPUT = 2**64 - 1  # VPIN_NET_FROM_INPUT, (size_t)-1
 ORDER_INTERLEAVED = 1  # VPIN_NET_ORDER_INTERLEAVED
 VERSIONS = ("A", "B", "C", "D", "E")
@@ -129,9 +130,12 @@ class Config:
         """the fully connected layer of a trained model (VPIN_NET_FCS): fc with signed weights"""
         return self.fc(w, bias, FCS, input_from)
 
-    def round(self, relu=False, shift_bits=0, max_giant=1, reencrypt=True):
+    def round(self, relu=False, shift_bits=0, max_giant=1, reencrypt=True, maxpool=None):
+        """maxpool = (k, stride): the client pools the layer's output by maximum inside this round, before it activates and encrypts
+        again; the tensor that goes on is C x Ho x Wo"""
         l = self.layers[-1]
         l.has_round, l.relu, l.shift_bits, l.reencrypt, l.max_giant = 1, int(bool(relu)), shift_bits, int(bool(reencrypt)), int(max_giant)
+        l.round_pool_k, l.round_pool_stride = (int(v) for v in maxpool) if maxpool else (0, 0)
         return self
 
     @property
@@ -140,7 +144,7 @@ class Config:
         cfg.C, cfg.H, cfg.W = self.dims
         cfg.prf_bytes, cfg.n_layers = self.prf_bytes, len(self.layers)
         arr = (NetLayer * max(1, len(self.layers)))(*self.layers)
-        cfg.layers = C.cast(arr, C.POINTER(NetLayer)) if self.layers else None
+        cfg.layers = C.cast(arr, C.POINTER(NetLayer12)) if self.layers else None  # the field's type; the array is the whole struct's
         cfg._arr = arr
         return cfg
 
@@ -328,6 +332,14 @@ def round_images():
     return [int(v) for v in (C.c_uint32 * n.value).from_address(p.value)]
 
 
+def round_pool():
+    """inside a round callback: (planes, H, W, k, stride) of the round at hand, planes = the images at hand times C; k = 0: the round
+    does not pool.  A round that pools hands back planes * Ho * Wo ciphertexts (vpin_net_round_pool)"""
+    out = (C.c_size_t * 5)()
+    _chk(lib().vpin_net_round_pool(out), "vpin_net_round_pool")
+    return tuple(int(v) for v in out)
+
+
 def round_drop_images(slots, code, text):
     """inside a round callback of infer_isolated: these images leave the batch after the round (vpin_net_round_drop_images)"""
     arr = (C.c_uint32 * max(1, len(slots)))(*[int(v) for v in slots])
@@ -362,7 +374,44 @@ def schedule(cfg, batch=1):
     times the images of a batch.  The client holds its own copy and answers no round that differs (Client.run)"""
     per = cfg.counts(batch)["per_round"]
     rounds = [l for l in cfg.layers if l.has_round]
-    return [((RELU if l.relu else 0) | (REENCRYPT if l.reencrypt else 0), int(l.shift_bits), int(n)) for l, n in zip(rounds, per)]
+    return [((RELU if l.relu else 0) | (REENCRYPT if l.reencrypt else 0) | (MAXPOOL if l.round_pool_k else 0), int(l.shift_bits), int(n))
+            for l, n in zip(rounds, per)]
+
+
+def pool_schedule(cfg):
+    """the other half of what the client of `cfg` agrees to: per round (H, W, k, stride) of the max pooling inside it, H x W the
+    planes the round decrypts; (0, 0, 0, 0) for a round that does not pool.  For Client.set_pools; the same for any batch"""
+    out, dims = [], shapes(cfg)
+    for l, (_, (_, H, W), _) in zip(cfg.layers, dims):
+        if l.has_round:
+            out.append((H, W, int(l.round_pool_k), int(l.round_pool_stride)) if l.round_pool_k else (0, 0, 0, 0))
+    return out
+
+
+def shapes(cfg):
+    """per layer ((C, H, W) that reaches it, (C, H, W) its call leaves and its round decrypts, (C, H, W) that goes on): the walk of
+    vpin_net_cfg_counts written out, input_from and a round's max pooling followed.  For a configuration that the library accepts"""
+    tensors, out = [tuple(cfg.dims)], []
+    for i, l in enumerate(cfg.layers):
+        ref = int(l.input_from)
+        C_, H, W = tensors[0 if ref == FROM_INPUT else ref if ref else i]
+        if l.kind == CONV:
+            C_ = (int(l.sum_out) if l.sum_table else C_) * max(1, int(l.repeat))
+        src = (C_, H, W)
+        if l.kind in (CONV, CONVMC):
+            d = (int(l.n_out) if l.kind == CONVMC else C_, (H + 2 * l.pad - l.fh) // l.stride + 1, (W + 2 * l.pad - l.fw) // l.stride + 1)
+        elif l.kind == POOL:
+            d = (C_, (H - l.k) // l.stride + 1, (W - l.k) // l.stride + 1)
+        elif l.kind in (FC, FCS):
+            d = (1, 1, int(l.N))
+        else:
+            d = src
+        o = d
+        if l.has_round and l.round_pool_k:
+            o = (d[0], (d[1] - l.round_pool_k) // l.round_pool_stride + 1, (d[2] - l.round_pool_k) // l.round_pool_stride + 1)
+        out.append((src, d, o))
+        tensors.append(o)
+    return out
 
 
 def serve(ctx, cfg, wire, keys, bias_rs, max_batch=1):
